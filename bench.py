@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- 1080p frames/s of the FCN-ResNet50 segmentation path on N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs when --dump-outputs is given, and prints
+the line (headline + the roofline of the last timed frame's per-kernel HIP events).  --full adds everything else: the
+one-context rate, the side measurements of the other arithmetic modes and BASELINE configs, the PCIe-inclusive rates,
+the CPU baseline, and for N > 1 the ranks' agreement on frame 0's mask.
 
 A "step" is one pass of the hot path (packed BGR frame -> [scale] -> fused pre-proc + stem ->
 FCN-ResNet50 incl. aux head -> bilinear up-sample + argmax + shade -> RGBA mask) over one batch
@@ -11,8 +16,8 @@ itself when it finds no launcher around it (`python bench.py --gpus N`): the wei
 broadcast once over RCCL (timed separately, outside the region), frames are sharded with no
 data-path collective ("weak" scaling: per-GPU work is fixed).  Rank 0 prints ONE JSON line.
 
-The CPU oracle (oracle/) is used here only for the ``cpu_baseline`` leg and a one-frame
-parity spot check; it is never part of the measured path.
+The CPU oracle (oracle/) is used here only for the ``cpu_baseline`` leg (--full); it is never part
+of the measured path.
 """
 import argparse
 import json
@@ -64,7 +69,17 @@ def parse():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend for N > 1 (nccl = RCCL over xGMI; gloo only to exercise the "
                          "multi-process path on a box with fewer GPUs than ranks)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: the one-context rate, the side measurements "
+                         "(other arithmetic modes, BASELINE configs[2..4], PCIe-inclusive rates), the CPU baseline and, for N > 1, "
+                         "the ranks' agreement on frame 0's mask (the --no-* options above switch parts of it off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed -- every frame's RGBA mask and the output-stride-8 "
+                         "logits of each context's last frame -- as DIR/<name>.npy in float32, at most 64 MB in all (see dump_outputs)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def self_launch(a):
@@ -347,6 +362,28 @@ def compact_line(out):
     return text
 
 
+DUMP_LIMIT = 64 << 20  # bytes: all files of --dump-outputs together
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT, seed=0):
+    """name -> array, written as path/<name>.npy in float32.  When the arrays together exceed `limit`, every array larger than an
+    equal share of it is replaced by a fixed seeded sample of its flattened elements (the same positions on every run, so that two
+    builds can be compared output for output), and path/<name>_index.npy holds the flat indices of that sample (float64)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    share = (limit - 4096 * len(arrays)) // max(len(arrays), 1)  # 4 KB per file for the .npy headers
+    total = sum(np.asarray(v).size * 4 for v in arrays.values())
+    for name, arr in arrays.items():
+        flat = np.ascontiguousarray(arr, dtype=np.float32)
+        if total > limit and flat.nbytes > share:
+            k = share // 12  # 4 B of value + 8 B of index per sampled element
+            idx = np.unique(np.random.default_rng(seed).integers(0, flat.size, k))
+            np.save(os.path.join(path, f"{name}_index.npy"), idx.astype(np.float64))
+            flat = flat.reshape(-1)[idx]
+        np.save(os.path.join(path, f"{name}.npy"), flat)
+
+
 def emit(out):
     """bench_detail.json + stderr get the full record; stdout gets the one compact line, last."""
     detail = json.dumps(out, indent=1, default=str)
@@ -440,6 +477,8 @@ def main():
         for c in ctxs:
             c.synchronize()
 
+    last_frame = {}  # context -> the frame it ran last (its logits are that frame's)
+
     def step(profile_last=False):
         for i in range(B):
             k = i % K
@@ -451,6 +490,7 @@ def main():
                 for st in streams[1:]:
                     streams[0].wait_stream(st)
                 ctx.L.infur_profile_enable(ctx.h, 1)
+            last_frame[k] = i
             fps_[k].advance_dev(d_frames[i].data_ptr(), Wd, H, a.scale, d_masks[i].data_ptr(), d_masks[i].numel())
 
     for _ in range(a.warmup):
@@ -482,9 +522,21 @@ def main():
     for c in ctxs:
         c.L.infur_profile_enable(c.h, 0)
 
+    # what the timed path handed back in its last step, before anything below reuses the masks or the contexts' arenas
+    if a.dump_outputs and rank == 0:
+        from infur_amd.processors import Model
+
+        arrays = {f"mask_f{i}": d_masks[i].cpu().numpy() for i in range(B)}
+        for k, i in sorted(last_frame.items()):
+            lo, la = Model(ctxs[k]).lowres()
+            arrays[f"out_low_f{i}"] = lo
+            if la is not None:
+                arrays[f"aux_low_f{i}"] = la
+        dump_outputs(a.dump_outputs, arrays)
+
     # every rank decodes the SAME frame once more (outside the timed region): replicas must agree bit for bit
     agree = None
-    if multi:
+    if multi and a.full:
         f0 = torch.from_numpy(W.synth_frame(H, Wd, index=0)).cuda()
         fps_[K - 1].advance_dev(f0.data_ptr(), Wd, H, a.scale, d_masks[0].data_ptr(), d_masks[0].numel())
         sync_all()
@@ -496,7 +548,7 @@ def main():
     # for reference: the same frames with strictly one frame at a time (context 0 only), outside the timed region,
     # without per-kernel events
     one_ctx_fps = None
-    if K > 1 and world == 1:
+    if a.full and K > 1 and world == 1:
         sync_all()
         t1 = time.perf_counter()
         for _ in range(2):
@@ -642,7 +694,8 @@ def main():
         # the headline's contexts (streams, arenas, weights) are released before the side measurements start
         for c in ctxs:
             c.close()
-        if world == 1 and a.dtype == "f32" and not a.no_split:
+        full = a.full and world == 1  # everything beyond the headline: --full only
+        if full and a.dtype == "f32" and not a.no_split:
             out["f32_split_mode"] = split_mode_rate(a, dev, blob, d_frames, d_masks, Wd, H)
             out["f32_split_fp8_mode"] = split_fp8_mode_rate(a, dev, blob, d_frames, d_masks, Wd, H)
             try:
@@ -658,7 +711,7 @@ def main():
             except Exception as e:  # noqa: BLE001
                 out["int8_quantised_model"] = {"error": f"{type(e).__name__}: {e}"}
         default_workload = (Wd, H, a.scale, a.dtype, a.depth) == (1920, 1080, 1.0, "f32", 50)
-        if world == 1 and not a.no_side:
+        if full and not a.no_side:
             try:
                 out["config"]["pcie_inclusive_frames_per_s"] = pcie_inclusive_rate(a, dev, blob, frames_np, a.dtype)
                 out["config"]["pcie_inclusive_zero_copy_frames_per_s"] = pcie_inclusive_rate(a, dev, blob, frames_np, a.dtype, zero_copy=True)
@@ -669,7 +722,7 @@ def main():
             except Exception as e:  # noqa: BLE001
                 out["config"]["pcie_inclusive_frames_per_s"] = None
                 out["config"]["pcie_inclusive_note"] = f"{type(e).__name__}: {e}"
-        if world == 1 and default_workload and not a.no_side:
+        if full and default_workload and not a.no_side:
             out["configs2_stream_scale05"] = stream_scale05_rate(a, dev, blob, frames_np)
             out["configs4_r101_f16_4k"] = r101_f16_4k_rate(a, dev)
             try:  # a side measurement must never cost the line its headline
@@ -680,7 +733,7 @@ def main():
                 out["configs3_batch64_group_f16hl"] = group_batch64_rate(a, blob, "f16hl")
             except Exception as e:  # noqa: BLE001
                 out["configs3_batch64_group_f16hl"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not a.no_cpu_baseline:
+        if full and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(blob, frames_np[0], a.cpu_seconds)
         emit(out)
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""profiles/rNN_bench_boxes.md from the JSON lines of `python bench.py` runs on different boxes:
+"""profiles/rNN_bench_boxes.md from the JSON lines of `python bench.py --full` runs on different boxes:
     python scripts/boxes_table.py label=path.json [label=path.json ...]"""
 import json
 import sys

@@ -252,7 +252,7 @@ def test_bench_self_launches_two_ranks_on_one_gpu(tmp_path):
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "2",
-                        "--warmup", "1", "--frames-per-step", "2", "--width", "320", "--height", "240", "--no-cpu-baseline",
+                        "--warmup", "1", "--frames-per-step", "2", "--width", "320", "--height", "240", "--full", "--no-cpu-baseline",
                         "--no-split", "--no-side"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -278,7 +278,7 @@ def test_bench_rccl_branch_executes_on_one_rank(tmp_path):
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr",
                         "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--backend",
                         "nccl", "--steps", "2", "--warmup", "1", "--frames-per-step", "2", "--width", "320", "--height",
-                        "240", "--no-cpu-baseline", "--no-split", "--no-side"], cwd=ROOT, env=env, capture_output=True,
+                        "240", "--full", "--no-cpu-baseline", "--no-split", "--no-side"], cwd=ROOT, env=env, capture_output=True,
                        text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     j = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -479,7 +479,7 @@ def test_bench_self_launches_eight_ranks_on_one_gpu(tmp_path):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--backend", "gloo", "--steps", "1",
                         "--warmup", "1", "--frames-per-step", "1", "--contexts-per-gpu", "1", "--width", "160", "--height", "120",
-                        "--no-cpu-baseline", "--no-split", "--no-side", "--no-profile"], cwd=ROOT, env=env, capture_output=True, text=True,
+                        "--full", "--no-cpu-baseline", "--no-split", "--no-side", "--no-profile"], cwd=ROOT, env=env, capture_output=True, text=True,
                        timeout=1500)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     j = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
