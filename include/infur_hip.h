@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define INFUR_ABI_VERSION 6
+#define INFUR_ABI_VERSION 7
 
 /* status codes */
 enum {
@@ -390,6 +390,22 @@ int32_t infur_batch_advance_multi(infur_ctx* const* ctxs, uint32_t n_ctx, const 
  * left the exact range (the logits of that frame are then not f32-grade: re-run it on an INFUR_DTYPE_F32 context).
  * Synchronises the stream.  INFUR_E_INVALID_ARG in the other modes. */
 int32_t infur_split_range(infur_ctx* ctx, float* act_amax, float* wino_amax, uint32_t* saturated);
+
+/* ---- INFUR_DTYPE_F16_HL range monitor (ABI 7) ----
+ * The three-byte mode stores every activation as an f16 hi + e5m2 lo pair, exact while |x| <= 65520; every split first clamps to
+ * that range (silently: a larger value is stored as the f16 maximum, a NaN as the layer's lower bound -- 0 after a ReLU).  While the
+ * monitor is on (opt-in; off by default, when every kernel runs as without it), the kernels that write three-byte tensors record what
+ * their splits saw, ACCUMULATED over every forward of the context since it was enabled or last read: the largest |activation| (a
+ * ReLU layer's max(x, 0); the f32 logits are not split and not included), the largest |Winograd-domain input| (unscaled), whether
+ * any value was changed by the upper clamp, and whether any split received a NaN (+inf counts as saturation).  Read after each
+ * infur_frame_advance for per-frame values, after a batch / ring for all its frames; a frame that saturated is not f16hl-grade:
+ * re-run it on an INFUR_DTYPE_F32 or INFUR_DTYPE_F32_SPLIT context.  Each lane of a stream / member of a group is queried on its own.
+ *   infur_hl_monitor_enable: INFUR_E_INVALID_ARG (nothing changed) unless compute_dtype is INFUR_DTYPE_F16_HL; enabling allocates
+ *     and zeroes the monitor's words; switching drops the context's cached graphs.
+ *   infur_hl_range: INFUR_E_INVALID_ARG while the monitor is off.  Synchronises the stream, returns the values and queues their
+ *     clear on the stream.  Any out-pointer may be NULL.  A quantised model (or none) reads zeros. */
+int32_t infur_hl_monitor_enable(infur_ctx* ctx, uint32_t on);
+int32_t infur_hl_range(infur_ctx* ctx, float* act_amax, float* wino_amax, uint32_t* saturated, uint32_t* nan_seen);
 
 /* ---- tuning database (tile configuration per conv shape, see options.no_autotune) ----
  * Text form: one line per shape, 13 shape integers + the configuration index.  Importing a

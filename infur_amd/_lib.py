@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # INFUR_LIB_PATH: an instrumentation build of the same ABI (scripts/ktrace.py: `make ktrace` -> libinfur_hip_ktrace.so)
 LIB_PATH = os.environ.get("INFUR_LIB_PATH") or os.path.join(_HERE, "libinfur_hip.so")
 
-ABI_VERSION = 6  # INFUR_ABI_VERSION of include/infur_hip.h
+ABI_VERSION = 7  # INFUR_ABI_VERSION of include/infur_hip.h
 
 # status codes (include/infur_hip.h)
 OK = 0
@@ -155,6 +155,8 @@ SIGNATURES = {
     "infur_batch_advance_multi": (C.c_int32, [C.POINTER(_vp), _u32, C.POINTER(_vp), _u32p, _u32p, _u32, _f, _u32,
                                               C.POINTER(_vp), C.POINTER(_sz), _u32p, _u32p]),
     "infur_split_range": (C.c_int32, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float), _u32p]),
+    "infur_hl_monitor_enable": (C.c_int32, [_vp, _u32]),
+    "infur_hl_range": (C.c_int32, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float), _u32p, _u32p]),
     "infur_tune_export": (C.c_int32, [_vp, C.c_char_p, _sz, C.POINTER(_sz)]),
     "infur_tune_import": (C.c_int32, [_vp, C.c_char_p, _sz]),
     "infur_profile_enable": (C.c_int32, [_vp, _u32]),

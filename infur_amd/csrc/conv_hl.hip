@@ -82,9 +82,12 @@ constexpr int hl_ceil_div(int a, int b) { return (a + b - 1) / b; }
 // lgkmcnt(0) in front of the barrier), so the DMA of step k + NIMG goes out there, into the image just freed -- the same two steps of
 // cover as before (ring of three), one image less idle.  Same MFMAs on the same operands in the same order per accumulator:
 // bit-identical to PIPE = false (tests/test_gpu_hl.py).
-template <int BM, int BN, int WM, int WN, bool G1, bool OUTF32, bool DUAL = false, int NIMG = 3, bool PIPE = false>
+// MON: the range monitor (hl_format.h, ConvArgs::hl_mon) -- the epilogue keeps the lane's max / min / NaN of the values it splits and
+// reduces them once per wave at the end; a separate instantiation, so the unmonitored kernels are the ones they were.
+template <int BM, int BN, int WM, int WN, bool G1, bool OUTF32, bool DUAL = false, int NIMG = 3, bool PIPE = false, bool MON = false>
 __global__ void __launch_bounds__(WM* WN * 64, 2) conv_hl_kernel(const ConvArgs a, const int mtiles, const int ntiles) {
     static_assert(!DUAL || (G1 && !OUTF32), "DUAL is a form of the 1x1 GEMM addressing");
+    static_assert(!MON || !OUTF32, "an f32 output is not split");
     constexpr int NW = WM * WN;
     constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
     constexpr int IMG = hl_image_bytes(BM, BN);
@@ -671,6 +674,7 @@ __global__ void __launch_bounds__(WM* WN * 64, 2) conv_hl_kernel(const ConvArgs 
         for (int t = 0; t < CPL; t++) bv[t] = (has_bias && n_ok) ? a.bias[n + t] : 0.f;
         const _Float16* res_hi = static_cast<const _Float16*>(a.res);
         const unsigned char* res_lo = static_cast<const unsigned char*>(a.res_lo);
+        HlMon hm;
         // Tiles too big for the prefetch above (256 x 256: 128 accumulators per lane): ALL residual loads of the wave go out here, at
         // once -- the fragment registers of the K loop are dead by now, so there is room for them -- instead of per 32-row block:
         // one HBM round trip per wave instead of TM of them (one workgroup per CU: nothing else would cover the other three).
@@ -749,6 +753,7 @@ __global__ void __launch_bounds__(WM* WN * 64, 2) conv_hl_kernel(const ConvArgs 
 #pragma unroll
                             for (int t = 0; t < 8; t++) x[t] += (float)rh[it][t] + lo[t];
                         }
+                        if constexpr (MON) hl_mon_see<8>(hm, x);
                         f16x8 hv;
                         u32x2 lv;
                         hl_split8(x, hv, lv, a.relu ? 0.f : -kHlHiMax);  // (the ReLU is the split's lower clamp)
@@ -768,6 +773,7 @@ __global__ void __launch_bounds__(WM* WN * 64, 2) conv_hl_kernel(const ConvArgs 
                 for (int k = 0; k < 8; k++) g_hl_trace[wave * 8 + k] = tr[k];
         }
 #endif
+        if constexpr (MON) hl_mon_flush(hm, a.relu != 0, a.hl_mon + kHlMonAct, a.hl_mon + kHlMonNan);
         return;
     }
     // Cout not a multiple of the vector width (the 21-class logits, f32 out): element-wise from the accumulator layout
@@ -794,12 +800,12 @@ __global__ void __launch_bounds__(WM* WN * 64, 2) conv_hl_kernel(const ConvArgs 
     }
 }
 
-template <int BM, int BN, int WM, int WN, bool G1, bool OUTF32, bool DUAL = false, int NIMG = 3, bool PIPE = false>
+template <int BM, int BN, int WM, int WN, bool G1, bool OUTF32, bool DUAL = false, int NIMG = 3, bool PIPE = false, bool MON = false>
 static hipError_t launch_hl_g(const ConvArgs& a, hipStream_t s) {
     const int M = a.OH * a.OW;
     const int mtiles = (M + BM - 1) / BM, ntiles = (a.Cout + BN - 1) / BN;
     const size_t lds = (size_t)hl_lds_bytes(BM, BN, WM, WN, NIMG);
-    auto k = conv_hl_kernel<BM, BN, WM, WN, G1, OUTF32, DUAL, NIMG, PIPE>;
+    auto k = conv_hl_kernel<BM, BN, WM, WN, G1, OUTF32, DUAL, NIMG, PIPE, MON>;
     static std::atomic<bool> attr_done[64];
     int dev = 0;
     const bool known = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64;
@@ -812,12 +818,17 @@ static hipError_t launch_hl_g(const ConvArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
+template <int BM, int BN, int WM, int WN, int NIMG, bool PIPE, bool MON>
+static hipError_t launch_hl_o(const ConvArgs& a, hipStream_t s) {  // the hi / lo output forms
+    const bool g1 = a.KH == 1 && a.KW == 1 && a.pad == 0;
+    if (a.in2) return launch_hl_g<BM, BN, WM, WN, true, false, true, NIMG, PIPE, MON>(a, s);  // (conv_hl_config_valid: 1x1, stride 1, hi / lo out)
+    return g1 ? launch_hl_g<BM, BN, WM, WN, true, false, false, NIMG, PIPE, MON>(a, s) : launch_hl_g<BM, BN, WM, WN, false, false, false, NIMG, PIPE, MON>(a, s);
+}
 template <int BM, int BN, int WM, int WN, int NIMG, bool PIPE>
 static hipError_t launch_hl_p(const ConvArgs& a, int out_f32, hipStream_t s) {
     const bool g1 = a.KH == 1 && a.KW == 1 && a.pad == 0;
-    if (a.in2) return launch_hl_g<BM, BN, WM, WN, true, false, true, NIMG, PIPE>(a, s);  // (conv_hl_config_valid: 1x1, stride 1, hi / lo out)
-    if (out_f32) return g1 ? launch_hl_g<BM, BN, WM, WN, true, true, false, NIMG, PIPE>(a, s) : launch_hl_g<BM, BN, WM, WN, false, true, false, NIMG, PIPE>(a, s);
-    return g1 ? launch_hl_g<BM, BN, WM, WN, true, false, false, NIMG, PIPE>(a, s) : launch_hl_g<BM, BN, WM, WN, false, false, false, NIMG, PIPE>(a, s);
+    if (out_f32 && !a.in2) return g1 ? launch_hl_g<BM, BN, WM, WN, true, true, false, NIMG, PIPE>(a, s) : launch_hl_g<BM, BN, WM, WN, false, true, false, NIMG, PIPE>(a, s);
+    return a.hl_mon ? launch_hl_o<BM, BN, WM, WN, NIMG, PIPE, true>(a, s) : launch_hl_o<BM, BN, WM, WN, NIMG, PIPE, false>(a, s);
 }
 // INFUR_HL_PIPE=0: the plain K loop (measurement / bisection hook; both loops are bit-identical)
 static bool hl_pipe_on() {

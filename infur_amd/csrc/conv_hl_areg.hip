@@ -68,7 +68,8 @@ __device__ __forceinline__ void ah_wait_loads(const int n) {
 // NW = waves: 8 (4 along the pixels x 2 along the channels, 32 pixels x 64 channels each, two waves per SIMD: Cin <= 256, the
 // fragment is <= 96 VGPRs) or 4 (32 pixels x all 128 channels of a tile each, ONE wave per SIMD with the whole register file:
 // Cin = 512 -- layer4's expansions -- whose fragment is 192 VGPRs)
-template <int KS, int NIMG, int NW>
+// MON: the range monitor (hl_format.h, ConvArgs::hl_mon) over the wave's pixels inside the tensor, reduced once per wave at the end
+template <int KS, int NIMG, int NW, bool MON = false>
 __global__ void __launch_bounds__(NW * 64, NW == 8 ? 2 : 1) conv_hl_areg_kernel(const ConvArgs a, const int mtiles) {
     static_assert(NW == 8 || NW == 4, "waves");
     static_assert(KS % 2 == 0 && KS >= 2 && KS <= (NW == 8 ? 8 : 16), "an image holds two K steps; the fragment is 12 KS VGPRs");
@@ -232,6 +233,8 @@ __global__ void __launch_bounds__(NW * 64, NW == 8 ? 2 : 1) conv_hl_areg_kernel(
     const int b_lo = AH_SUB_LO + (wn * WCH + r) * 32 + ((h ^ hl_swz32(r)) * 16);
     const float acc_scale = a.acc_scale;
     unsigned cur = 0;  // byte offset of the image being multiplied
+    HlMon hm;
+    const bool mon_px = m0 + wm * 32 + r < M;  // (the rows past the tensor split bias values that are never stored)
 
     for (int w = 0; w < ntiles; w++) {
         const unsigned nb = (unsigned)(nt_of(w) * AH_BN);
@@ -319,6 +322,8 @@ __global__ void __launch_bounds__(NW * 64, NW == 8 ? 2 : 1) conv_hl_areg_kernel(
 #pragma unroll
                     for (int t = 0; t < 8; t++) x[t] += (float)rh[t] + lo[t];
                 }
+                if constexpr (MON)
+                    if (mon_px) hl_mon_see<8>(hm, x);
                 f16x8 hv;
                 u32x2 lv;
                 hl_split8(x, hv, lv, a.relu ? 0.f : -kHlHiMax);  // (the ReLU is the split's lower clamp)
@@ -347,13 +352,14 @@ __global__ void __launch_bounds__(NW * 64, NW == 8 ? 2 : 1) conv_hl_areg_kernel(
         }
         AH_T(73);
     }
+    if constexpr (MON) hl_mon_flush(hm, a.relu != 0, a.hl_mon + kHlMonAct, a.hl_mon + kHlMonNan);
 }
 
-template <int KS, int NIMG, int NW>
-hipError_t launch_ah(const ConvArgs& a, hipStream_t s) {
+template <int KS, int NIMG, int NW, bool MON>
+hipError_t launch_ah_m(const ConvArgs& a, hipStream_t s) {
     const int M = a.OH * a.OW;
     const int mtiles = (M + AH_BM - 1) / AH_BM;
-    auto k = conv_hl_areg_kernel<KS, NIMG, NW>;
+    auto k = conv_hl_areg_kernel<KS, NIMG, NW, MON>;
     constexpr int lds = ah_lds_bytes(NIMG);
     static_assert(lds <= 160 * 1024, "LDS");
     static std::atomic<bool> attr_done[64];
@@ -385,6 +391,10 @@ hipError_t launch_ah(const ConvArgs& a, hipStream_t s) {
     }
 #endif
     return hipGetLastError();
+}
+template <int KS, int NIMG, int NW>
+hipError_t launch_ah(const ConvArgs& a, hipStream_t s) {
+    return a.hl_mon ? launch_ah_m<KS, NIMG, NW, true>(a, s) : launch_ah_m<KS, NIMG, NW, false>(a, s);
 }
 
 }  // namespace

@@ -95,6 +95,38 @@ __device__ __forceinline__ void hl_join8(const hl_f16x8 hv, const hl_u32x2 lv, f
 #pragma unroll
     for (int t = 0; t < 8; t++) x[t] = (float)hv[t] + lo[t];
 }
+// ---- range monitor of the three-byte mode (infur_hl_monitor_enable / infur_hl_range), opt-in: every producer takes it as a template
+// flag, so an unmonitored context runs exactly the kernels it ran before.  Device words of the context (accumulated over forwards until
+// the host reads and clears them): [kHlMonAct] max |x| handed to a split of an activation tensor, [kHlMonWino] max |V * v_scale| of the
+// Winograd input transform (bit patterns of non-negative floats, +inf included: atomicMax targets), [kHlMonNan] 1 once a split received
+// a NaN.  x is the value BEFORE the clamp (after bias, residual; the ReLU is the split's lower clamp, so a ReLU layer's |x| is max(x, 0)).
+constexpr int kHlMonAct = 0, kHlMonWino = 1, kHlMonNan = 2, kHlMonWords = 4;
+struct HlMon {
+    float hi = 0.f, lo = 0.f;  // max(0, max x), min(0, min x): a NaN is ignored by both (v_max / v_min return the other operand)
+    bool nan = false;
+};
+template <int N>
+__device__ __forceinline__ void hl_mon_see(HlMon& m, const float* x) {
+#pragma unroll
+    for (int t = 0; t < N; t++) {
+        m.hi = fmaxf(m.hi, x[t]);
+        m.lo = fminf(m.lo, x[t]);
+        m.nan |= x[t] != x[t];
+    }
+}
+// once per wave, all lanes active: reduce, then one atomic per wave that RAISES the stored maximum (conv_igemm_kernel.h: tens of thousands
+// of same-address atomics cost 0.17 ms per launch); only a wave that saw a NaN writes the flag
+__device__ __forceinline__ void hl_mon_flush(const HlMon& m, const bool relu, unsigned* amax, unsigned* nan_flag) {
+    float v = relu ? m.hi : fmaxf(m.hi, -m.lo);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    const bool any_nan = __ballot(m.nan) != 0;
+    if (__lane_id() == 0) {
+        if (__float_as_uint(v) > *reinterpret_cast<volatile unsigned*>(amax)) atomicMax(amax, __float_as_uint(v));
+        if (any_nan) *reinterpret_cast<volatile unsigned*>(nan_flag) = 1u;
+    }
+}
+
 struct HlTag {  // element-type tag of kernels templated on their output type: sizeof == 3
     unsigned char b[3];
 };

@@ -6,24 +6,34 @@
 
 namespace infur {
 
-__global__ void __launch_bounds__(256) hl_from_f32_kernel(const float* __restrict__ in, size_t n8, _Float16* __restrict__ hi, unsigned char* __restrict__ lo) {
+template <bool MON>
+__global__ void __launch_bounds__(256) hl_from_f32_kernel(const float* __restrict__ in, size_t n8, _Float16* __restrict__ hi, unsigned char* __restrict__ lo,
+                                                          unsigned* __restrict__ mon) {
     hl_set_fp16_ovfl();
+    HlMon hm;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (size_t)gridDim.x * 256) {
         const float4 a = reinterpret_cast<const float4*>(in)[2 * i], b = reinterpret_cast<const float4*>(in)[2 * i + 1];
         const float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+        if constexpr (MON) hl_mon_see<8>(hm, x);
         hl_f16x8 hv;
         hl_u32x2 lv;
         hl_split8(x, hv, lv);
         reinterpret_cast<hl_f16x8*>(hi)[i] = hv;
         reinterpret_cast<hl_u32x2*>(lo)[i] = lv;
     }
+    if constexpr (MON) hl_mon_flush(hm, false, mon + kHlMonAct, mon + kHlMonNan);
 }
 
-hipError_t launch_hl_from_f32(const float* in, size_t n, void* hi, void* lo, hipStream_t s) {
+hipError_t launch_hl_from_f32(const float* in, size_t n, void* hi, void* lo, unsigned* hl_mon, hipStream_t s) {
     if (n & 7) return hipErrorInvalidValue;
     size_t blocks = (n / 8 + 255) / 256;
     if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(hl_from_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, s, in, n / 8, static_cast<_Float16*>(hi), static_cast<unsigned char*>(lo));
+    if (hl_mon)
+        hipLaunchKernelGGL(hl_from_f32_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, in, n / 8, static_cast<_Float16*>(hi), static_cast<unsigned char*>(lo),
+                           hl_mon);
+    else
+        hipLaunchKernelGGL(hl_from_f32_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, in, n / 8, static_cast<_Float16*>(hi), static_cast<unsigned char*>(lo),
+                           hl_mon);
     return hipGetLastError();
 }
 

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "blob_dir.h"
+#include "hl_format.h"
 #include "infur_ctx.h"
 #include "infur_rt.h"
 #include "kernels.h"
@@ -593,7 +594,7 @@ int32_t run_conv(infur_ctx* c, const ConvLayer& L, const Tensor& in, const Tenso
         const double direct = 2.0 * oh * ow * (double)L.cout * L.cin * 9.0;
         {
             ProfScope ps(c, L.name + "/in", "wino_input_hl", 0, (double)in.elems() * 3 + (double)V.elems() * 3, 0.0);
-            HIPCHK(c, launch_wino_input_hl(in.p, in.lo, in.h, in.w, in.c, L.dil, mt, split_wino_scale(mt), V.p, V.lo, c->stream));
+            HIPCHK(c, launch_wino_input_hl(in.p, in.lo, in.h, in.w, in.c, L.dil, mt, split_wino_scale(mt), V.p, V.lo, c->d_hlmon, c->stream));
         }
         ConvArgs g;
         g.in = V.p; g.in_lo = V.lo; g.wt = L.d_u; g.wt_lo = L.d_ul; g.bias = nullptr; g.res = nullptr; g.out = M.p;
@@ -612,7 +613,7 @@ int32_t run_conv(infur_ctx* c, const ConvLayer& L, const Tensor& in, const Tenso
         pool_release(c, V);
         {
             ProfScope ps(c, L.name + "/out", "wino_output_hl", 0, (double)M.bytes() + (double)out->elems() * 3, 0.0);
-            HIPCHK(c, launch_wino_output_hl((const float*)M.p, oh, ow, L.cout, L.dil, mt, L.d_b, L.relu ? 1 : 0, out->p, out->lo, c->stream));
+            HIPCHK(c, launch_wino_output_hl((const float*)M.p, oh, ow, L.cout, L.dil, mt, L.d_b, L.relu ? 1 : 0, out->p, out->lo, c->d_hlmon, c->stream));
         }
         pool_release(c, M);
         if (c->opt.keep_activations) c->kept.push_back(*out);
@@ -668,6 +669,7 @@ int32_t run_conv(infur_ctx* c, const ConvLayer& L, const Tensor& in, const Tenso
         a.amax = L.role == 'c' ? nullptr : c->d_range;  // the logits feed no GEMM
     }
     if (hl) a.acc_scale = 1.0f / L.w_scale;  // (activations are stored unscaled: e5m2 lo planes share f16's exponent range)
+    if (hl && !out_f32) a.hl_mon = c->d_hlmon;
     int cfg = -1;
     RETIF(pick_cfg(c, a, conv_mode(c), out_f32, &cfg));
     {
@@ -701,6 +703,7 @@ int32_t run_conv_dual(infur_ctx* c, const ConvLayer& L3, const ConvLayer& D, con
     if (hl) {
         a.in_lo = t2.lo; a.in2_lo = x.lo; a.wt_lo = L3.d_wcatl; a.out_lo = out->lo;
         a.acc_scale = 1.0f / L3.wcat_scale;
+        a.hl_mon = c->d_hlmon;
     }
     const double flops = 2.0 * oh * ow * (double)L3.cout * (L3.cin + D.cin);
     const double bytes = (double)t2.bytes() + (double)oh * ow * x.c * x.es + (double)out->bytes() + (double)L3.cout * (L3.cin + D.cin) * t2.es;
@@ -850,7 +853,7 @@ int32_t forward(infur_ctx* c, const uint8_t* d_bgr, int w, int h) {
                      2.0 * sh * sw * 64 * 147);
         // exact f32 MFMA in the f32 mode; in the f16-rate modes the stem runs on the f16 matrix cores as the conv stack does
         HIPCHK(c, launch_stem_pool(d_bgr, h, w, (const float*)stem.d_w, wimg, stem.d_b, stem_lut(c), x.p, ctx_mode(c), sh, sw, ph, pw,
-                                   kSplitActScale, stem.w_scale, c->d_range, c->stream));  // (mode 5: hi / lo planes, x.lo = x.p + hl_lo_offset)
+                                   kSplitActScale, stem.w_scale, ctx_hl(c) ? c->d_hlmon : c->d_range, c->stream));  // (mode 5: hi / lo planes, x.lo = x.p + hl_lo_offset)
     } else {
         const int es01 = ctx_hl(c) ? 4 : act_es(c);  // three-byte mode: stem and pool in f32 (the exact f32 stem), converted below
         {
@@ -867,7 +870,7 @@ int32_t forward(infur_ctx* c, const uint8_t* d_bgr, int w, int h) {
         }
         if (ctx_hl(c)) {
             RETIF(talloc(c, ph, pw, 64, 3, &x));
-            HIPCHK(c, launch_hl_from_f32((const float*)xp.p, xp.elems(), x.p, x.lo, c->stream));
+            HIPCHK(c, launch_hl_from_f32((const float*)xp.p, xp.elems(), x.p, x.lo, c->d_hlmon, c->stream));
             pool_release(c, xp);
         } else {
             x = xp;
@@ -1150,6 +1153,7 @@ void infur_ctx_destroy(infur_ctx* c) {
     if (c->d_u8_lut) (void)hipFree(c->d_u8_lut);
     if (c->d_color_lut) (void)hipFree(c->d_color_lut);
     if (c->d_range) (void)hipFree(c->d_range);
+    if (c->d_hlmon) (void)hipFree(c->d_hlmon);
     if (c->d_stem16) (void)hipFree(c->d_stem16);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     pool_stream_release(c->device, c->pool_slot);
@@ -1846,6 +1850,52 @@ int32_t infur_split_range(infur_ctx* c, float* act_amax, float* wino_amax, uint3
     // beyond 65504 the hi half clamps (MODE.FP16_OVFL) and the pair stops being exact
     const float ws = split_wino_scale(wino_mt(c));
     if (saturated) *saturated = (v[0] * kSplitActScale > 65504.0f || v[1] * ws > 65504.0f) ? 1u : 0u;
+    return INFUR_OK;
+}
+
+// ---- range monitor of the three-byte mode (opt-in: hl_format.h, kHlMon*) ----
+int32_t infur_hl_monitor_enable(infur_ctx* c, uint32_t on) {
+    enter(c);
+    if (!c) return INFUR_E_INVALID_ARG;
+    if (c->opt.compute_dtype != INFUR_DTYPE_F16_HL) return fail(c, INFUR_E_INVALID_ARG, "the range monitor is a mode of INFUR_DTYPE_F16_HL contexts");
+    if (on && !c->d_hlmon) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        unsigned* p = nullptr;
+        HIPCHK(c, hipMalloc((void**)&p, kHlMonWords * sizeof(unsigned)));
+        if (hipMemset(p, 0, kHlMonWords * sizeof(unsigned)) != hipSuccess) {
+            (void)hipFree(p);
+            return fail(c, INFUR_E_HIP, "hipMemset of the range monitor failed");
+        }
+        c->d_hlmon = p;
+    } else if (!on && c->d_hlmon) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        (void)hipFree(c->d_hlmon);
+        c->d_hlmon = nullptr;
+    } else {
+        return INFUR_OK;
+    }
+    // the kernel arguments of a captured frame name the words (or their absence): like any allocation or release
+    c->mem_gen++;
+    graphs_drop(c);
+    return INFUR_OK;
+}
+
+int32_t infur_hl_range(infur_ctx* c, float* act_amax, float* wino_amax, uint32_t* saturated, uint32_t* nan_seen) {
+    enter(c);
+    if (!c) return INFUR_E_INVALID_ARG;
+    if (!c->d_hlmon) return fail(c, INFUR_E_INVALID_ARG, "the range monitor is not enabled (infur_hl_monitor_enable)");
+    unsigned v[kHlMonWords];
+    HIPCHK(c, hipMemcpyAsync(v, c->d_hlmon, sizeof v, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_hlmon, 0, sizeof v, c->stream));  // (ordered before the next forward on this stream)
+    float act, wino;
+    memcpy(&act, &v[kHlMonAct], 4);
+    memcpy(&wino, &v[kHlMonWino], 4);
+    // values up to kHlHiMax are stored exactly as hi + lo; beyond it the split's upper clamp changed them (+inf included)
+    if (act_amax) *act_amax = act;
+    if (wino_amax) *wino_amax = wino / split_wino_scale(wino_mt(c));  // (the transform stores V * split_wino_scale: a power of two)
+    if (saturated) *saturated = (act > kHlHiMax || wino > kHlHiMax) ? 1u : 0u;
+    if (nan_seen) *nan_seen = v[kHlMonNan] ? 1u : 0u;
     return INFUR_OK;
 }
 

@@ -175,6 +175,9 @@ struct infur_ctx {
     // INFUR_DTYPE_F32_SPLIT range monitor: [0] max |activation| fed to a GEMM, [1] max |Winograd-domain input|
     // of the last forward (bit patterns of non-negative floats, atomicMax targets); infur_split_range
     unsigned* d_range = nullptr;
+    // INFUR_DTYPE_F16_HL range monitor (infur_hl_monitor_enable): kHlMonWords device words (hl_format.h), accumulated over every forward
+    // since it was enabled or last read (infur_hl_range reads and clears them); null while it is off -- the unmonitored kernels run
+    unsigned* d_hlmon = nullptr;
     // the f16-rate / quantised stem's weight image (launch_stem16_pack) and what it was built from: rebuilt when any of it changes
     void* d_stem16 = nullptr;
     const void* stem16_wt = nullptr;

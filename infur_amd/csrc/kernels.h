@@ -59,6 +59,9 @@ struct ConvArgs {
     const void* res_lo = nullptr;
     void* out_lo = nullptr;
     const void* in2_lo = nullptr;
+    // mode 5, optional: the range monitor's device words (hl_format.h: kHlMon*) -- non-null selects the monitored form of the epilogue
+    // (hi / lo output only; an f32 output is never split)
+    unsigned* hl_mon = nullptr;
 };
 
 // conv as implicit GEMM on the matrix cores.  mode 0: f32 operands on the f32 MFMA (Cin % 32 == 0);
@@ -140,17 +143,19 @@ hipError_t launch_wino_output(const float* M, int H, int W, int Cout, int d, int
                               float* out, unsigned* amax, hipStream_t s);
 hipError_t launch_wino_weights(const float* w_oihw, int O, int I, int mt, float* U, hipStream_t s);
 // the same transforms on three-byte tensors (mode 5; C, Cout % 128 == 0): input hi / lo planes -> V * v_scale as hi / lo planes
-// [(mt+2)^2][T][C]; f32 M -> the conv's output as hi / lo planes
+// [(mt+2)^2][T][C]; f32 M -> the conv's output as hi / lo planes.  hl_mon (optional): the range monitor's words (hl_format.h), the
+// monitored form of the kernel -- max |V * v_scale| to [kHlMonWino], max |out| to [kHlMonAct]
 hipError_t launch_wino_input_hl(const void* in_hi, const void* in_lo, int H, int W, int C, int d, int mt, float v_scale, void* V_hi, void* V_lo,
-                                hipStream_t s);
+                                unsigned* hl_mon, hipStream_t s);
 hipError_t launch_wino_output_hl(const float* M, int H, int W, int Cout, int d, int mt, const float* bias, int relu, void* out_hi, void* out_lo,
-                                 hipStream_t s);
+                                 unsigned* hl_mon, hipStream_t s);
 
 // three-byte tensors (hl_format.h): the lo plane of an [elems] tensor starts hl_lo_offset(elems) bytes after the hi plane
 __host__ __device__ inline size_t hl_lo_offset(size_t elems) { return (elems * 2 + 255) & ~(size_t)255; }
 __host__ __device__ inline size_t hl_tensor_bytes(size_t elems) { return hl_lo_offset(elems) + ((elems + 255) & ~(size_t)255); }
-// f32 [n] -> hi / lo planes (n % 8 == 0); NHWC hi / lo planes -> planar f32 [C][H][W] (read-back)
-hipError_t launch_hl_from_f32(const float* in, size_t n, void* hi, void* lo, hipStream_t s);
+// f32 [n] -> hi / lo planes (n % 8 == 0; hl_mon: optional range monitor words, max |in| to [kHlMonAct]); NHWC hi / lo planes ->
+// planar f32 [C][H][W] (read-back)
+hipError_t launch_hl_from_f32(const float* in, size_t n, void* hi, void* lo, unsigned* hl_mon, hipStream_t s);
 hipError_t launch_hl_nhwc_to_planar(const void* hi, const void* lo, int H, int W, int C, float* out, hipStream_t s);
 
 // stem: packed BGR u8 -> (LUT normalise, BGR->RGB) -> conv 7x7/2 pad 3 (3->64) + bias + ReLU,

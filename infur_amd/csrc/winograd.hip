@@ -380,10 +380,12 @@ __device__ __forceinline__ f32x8w hl_load8(const _Float16* hi, const unsigned ch
     for (int t = 0; t < 8; t++) v[t] = x[t];
     return v;
 }
-__device__ __forceinline__ void hl_store8(_Float16* hi, unsigned char* lo, size_t e, const f32x8w v, const float lb = -kHlHiMax) {
+template <bool MON = false>
+__device__ __forceinline__ void hl_store8(_Float16* hi, unsigned char* lo, size_t e, const f32x8w v, const float lb = -kHlHiMax, HlMon* hm = nullptr) {
     float x[8];
 #pragma unroll
     for (int t = 0; t < 8; t++) x[t] = v[t];
+    if constexpr (MON) hl_mon_see<8>(*hm, x);
     hl_f16x8 hv;
     hl_u32x2 lv;
     hl_split8(x, hv, lv, lb);
@@ -391,14 +393,16 @@ __device__ __forceinline__ void hl_store8(_Float16* hi, unsigned char* lo, size_
     *reinterpret_cast<hl_u32x2*>(lo + e) = lv;
 }
 
-template <int MT>
+// MON: the range monitor (hl_format.h) -- max |V * v_scale| to mon[kHlMonWino], max |out| to mon[kHlMonAct]
+template <int MT, bool MON>
 __global__ void __launch_bounds__(128)
     wino_input_hl_kernel(const _Float16* __restrict__ in_hi, const unsigned char* __restrict__ in_lo, WinoGeom g, int C, int T, float v_scale,
-                         _Float16* __restrict__ V_hi, unsigned char* __restrict__ V_lo) {
+                         _Float16* __restrict__ V_hi, unsigned char* __restrict__ V_lo, unsigned* __restrict__ mon) {
     constexpr int AL = MT + 2;
     static_assert(AL <= 8, "one row / column per 16-lane group of a 128-thread workgroup");
     __shared__ f32x8w lds[AL * AL * WH_L];
     hl_set_fp16_ovfl();
+    HlMon hm;
     const int tid = threadIdx.x, q = tid >> 4, cvl = tid & 15;
     const int cgroups = C / (8 * WH_L);
     const size_t units = (size_t)T * cgroups;
@@ -443,20 +447,22 @@ __global__ void __launch_bounds__(128)
             bt_1d<MT, 1>(rin, row);
             const size_t o = (size_t)t * C + c0;
 #pragma unroll
-            for (int b = 0; b < AL; b++) hl_store8(V_hi, V_lo, o + (size_t)(q * AL + b) * plane, row[b] * v_scale);
+            for (int b = 0; b < AL; b++) hl_store8<MON>(V_hi, V_lo, o + (size_t)(q * AL + b) * plane, row[b] * v_scale, -kHlHiMax, &hm);
         }
         __syncthreads();
     }
+    if constexpr (MON) hl_mon_flush(hm, false, mon + kHlMonWino, mon + kHlMonNan);
 }
 
-template <int MT>
+template <int MT, bool MON>
 __global__ void __launch_bounds__(128)
     wino_output_hl_kernel(const float* __restrict__ M, WinoGeom g, int Cout, int T, const float* __restrict__ bias, int relu,
-                          _Float16* __restrict__ out_hi, unsigned char* __restrict__ out_lo) {
+                          _Float16* __restrict__ out_hi, unsigned char* __restrict__ out_lo, unsigned* __restrict__ mon) {
     constexpr int AL = MT + 2;
     static_assert(AL <= 8, "one row / column per 16-lane group of a 128-thread workgroup");
     __shared__ f32x8w lds[MT * AL * WH_L];
     hl_set_fp16_ovfl();
+    HlMon hm;
     const int tid = threadIdx.x, q = tid >> 4, cvl = tid & 15;
     const int cgroups = Cout / (8 * WH_L);
     const size_t units = (size_t)T * cgroups;
@@ -494,12 +500,13 @@ __global__ void __launch_bounds__(128)
                     const int x = g.d * (MT * tx + b) + rx;
                     if (x >= g.W) continue;
                     const f32x8w v = yv[b] + bv;
-                    hl_store8(out_hi, out_lo, ((size_t)y * g.W + x) * Cout + n0, v, relu ? 0.f : -kHlHiMax);  // (the ReLU is the split's lower clamp)
+                    hl_store8<MON>(out_hi, out_lo, ((size_t)y * g.W + x) * Cout + n0, v, relu ? 0.f : -kHlHiMax, &hm);  // (the ReLU is the split's lower clamp)
                 }
             }
         }
         __syncthreads();
     }
+    if constexpr (MON) hl_mon_flush(hm, relu != 0, mon + kHlMonAct, mon + kHlMonNan);
 }
 
 // ---- weight transform: U[xi][o][c] = (G g G^T)[xi],  g = w[o][c][3][3] (OIHW) ----
@@ -608,8 +615,25 @@ hipError_t launch_wino_output(const float* M, int H, int W, int Cout, int d, int
     return hipGetLastError();
 }
 
+template <int MT>
+static void wino_input_hl_go(dim3 grid, hipStream_t s, const _Float16* ih, const unsigned char* il, const WinoGeom& g, int C, int T, float v_scale,
+                             _Float16* vh, unsigned char* vl, unsigned* mon) {
+    if (mon)
+        hipLaunchKernelGGL((wino_input_hl_kernel<MT, true>), grid, dim3(128), 0, s, ih, il, g, C, T, v_scale, vh, vl, mon);
+    else
+        hipLaunchKernelGGL((wino_input_hl_kernel<MT, false>), grid, dim3(128), 0, s, ih, il, g, C, T, v_scale, vh, vl, mon);
+}
+template <int MT>
+static void wino_output_hl_go(dim3 grid, hipStream_t s, const float* M, const WinoGeom& g, int Cout, int T, const float* bias, int relu, _Float16* oh,
+                              unsigned char* ol, unsigned* mon) {
+    if (mon)
+        hipLaunchKernelGGL((wino_output_hl_kernel<MT, true>), grid, dim3(128), 0, s, M, g, Cout, T, bias, relu, oh, ol, mon);
+    else
+        hipLaunchKernelGGL((wino_output_hl_kernel<MT, false>), grid, dim3(128), 0, s, M, g, Cout, T, bias, relu, oh, ol, mon);
+}
+
 hipError_t launch_wino_input_hl(const void* in_hi, const void* in_lo, int H, int W, int C, int d, int mt, float v_scale, void* V_hi, void* V_lo,
-                                hipStream_t s) {
+                                unsigned* hl_mon, hipStream_t s) {
     if (C % (8 * WH_L) != 0) return hipErrorInvalidValue;
     const WinoGeom g = geom(H, W, d, mt);
     const int T = d * d * g.TY * g.TX;
@@ -619,16 +643,16 @@ hipError_t launch_wino_input_hl(const void* in_hi, const void* in_lo, int H, int
     _Float16* vh = static_cast<_Float16*>(V_hi);
     unsigned char* vl = static_cast<unsigned char*>(V_lo);
     if (mt == 6)
-        hipLaunchKernelGGL(wino_input_hl_kernel<6>, grid, dim3(128), 0, s, ih, il, g, C, T, v_scale, vh, vl);
+        wino_input_hl_go<6>(grid, s, ih, il, g, C, T, v_scale, vh, vl, hl_mon);
     else if (mt == 4)
-        hipLaunchKernelGGL(wino_input_hl_kernel<4>, grid, dim3(128), 0, s, ih, il, g, C, T, v_scale, vh, vl);
+        wino_input_hl_go<4>(grid, s, ih, il, g, C, T, v_scale, vh, vl, hl_mon);
     else
-        hipLaunchKernelGGL(wino_input_hl_kernel<2>, grid, dim3(128), 0, s, ih, il, g, C, T, v_scale, vh, vl);
+        wino_input_hl_go<2>(grid, s, ih, il, g, C, T, v_scale, vh, vl, hl_mon);
     return hipGetLastError();
 }
 
 hipError_t launch_wino_output_hl(const float* M, int H, int W, int Cout, int d, int mt, const float* bias, int relu, void* out_hi, void* out_lo,
-                                 hipStream_t s) {
+                                 unsigned* hl_mon, hipStream_t s) {
     if (Cout % (8 * WH_L) != 0) return hipErrorInvalidValue;
     const WinoGeom g = geom(H, W, d, mt);
     const int T = d * d * g.TY * g.TX;
@@ -636,11 +660,11 @@ hipError_t launch_wino_output_hl(const float* M, int H, int W, int Cout, int d, 
     _Float16* oh = static_cast<_Float16*>(out_hi);
     unsigned char* ol = static_cast<unsigned char*>(out_lo);
     if (mt == 6)
-        hipLaunchKernelGGL(wino_output_hl_kernel<6>, grid, dim3(128), 0, s, M, g, Cout, T, bias, relu, oh, ol);
+        wino_output_hl_go<6>(grid, s, M, g, Cout, T, bias, relu, oh, ol, hl_mon);
     else if (mt == 4)
-        hipLaunchKernelGGL(wino_output_hl_kernel<4>, grid, dim3(128), 0, s, M, g, Cout, T, bias, relu, oh, ol);
+        wino_output_hl_go<4>(grid, s, M, g, Cout, T, bias, relu, oh, ol, hl_mon);
     else
-        hipLaunchKernelGGL(wino_output_hl_kernel<2>, grid, dim3(128), 0, s, M, g, Cout, T, bias, relu, oh, ol);
+        wino_output_hl_go<2>(grid, s, M, g, Cout, T, bias, relu, oh, ol, hl_mon);
     return hipGetLastError();
 }
 

@@ -17,7 +17,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 from dataclasses import dataclass
-from typing import Generic, List, Optional, TypeVar
+from typing import Generic, List, NamedTuple, Optional, TypeVar
 
 import numpy as np
 
@@ -98,13 +98,22 @@ def _check_bgr(img: np.ndarray) -> np.ndarray:
 # --------------------------------------------------------------------------- #
 # context
 # --------------------------------------------------------------------------- #
+class HlRange(NamedTuple):
+    """What the splits of an "f16hl" context saw since its monitor was enabled or last read (``infur_hl_range``)."""
+
+    act_amax: float    # largest |activation| stored in three bytes (a ReLU layer's max(x, 0)); the f32 logits are not included
+    wino_amax: float   # largest |Winograd-domain input| (unscaled)
+    saturated: bool    # a value was changed by the upper clamp (beyond 65520; +inf included): re-run the frame on "f32" / "f32s"
+    nan_seen: bool     # a split received a NaN (stored as the layer's lower bound)
+
+
 class Context:
     """One GPU + one HIP stream + device arena (``infur_ctx``).  Not thread-safe."""
 
     def __init__(self, device: int = 0, compute_aux: bool = True, profile: bool = False,
                  keep_activations: bool = False, stream: Optional[int] = None, dtype: str = "f32",
                  winograd_min_cin: int = 0, winograd_tile: int = 0, autotune: bool = True, fuse_downsample: bool = True,
-                 fuse_stem_pool: bool = True, fuse_b2b: bool = True, graph_replay: bool = False):
+                 fuse_stem_pool: bool = True, fuse_b2b: bool = True, graph_replay: bool = False, hl_monitor: bool = False):
         L = self.L = _lib.load()
         o = _lib.Options()
         L.infur_options_default(C.byref(o))
@@ -133,6 +142,8 @@ class Context:
             self.load_tuning(TUNE_DB)
         if graph_replay:  # the fused frame path as a hipGraph once a frame shape has settled (small frames: launch-bound)
             self.check(L.infur_ctx_set_graph_replay(h, 1))
+        if hl_monitor:  # dtype "f16hl" only: the range monitor of the three-byte mode (InfurError otherwise)
+            self.set_hl_monitor(True)
 
     def graph_stats(self):
         """(graphs captured so far, frames replayed from a graph, graphs cached now)"""
@@ -149,6 +160,16 @@ class Context:
         a, w, sat = C.c_float(0), C.c_float(0), C.c_uint32(0)
         self.check(self.L.infur_split_range(self.h, C.byref(a), C.byref(w), C.byref(sat)))
         return a.value, w.value, bool(sat.value)
+
+    def set_hl_monitor(self, on: bool) -> None:
+        """dtype "f16hl" only (InfurError otherwise): switch the opt-in range monitor on / off."""
+        self.check(self.L.infur_hl_monitor_enable(self.h, 1 if on else 0))
+
+    def hl_range(self) -> HlRange:
+        """The monitor's values accumulated over every frame since it was enabled or last read; reading clears them."""
+        a, w, sat, nan = C.c_float(0), C.c_float(0), C.c_uint32(0), C.c_uint32(0)
+        self.check(self.L.infur_hl_range(self.h, C.byref(a), C.byref(w), C.byref(sat), C.byref(nan)))
+        return HlRange(a.value, w.value, bool(sat.value), bool(nan.value))
 
     def tuning_text(self) -> str:
         n = C.c_size_t(0)

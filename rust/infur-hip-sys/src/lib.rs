@@ -69,7 +69,7 @@ pub const INFUR_E_RCCL: i32 = 8;
 pub const INFUR_E_INVALID_ARG: i32 = 9;
 pub const INFUR_E_IO: i32 = 10;
 pub const INFUR_E_CAPACITY: i32 = 11;
-pub const INFUR_ABI_VERSION: u32 = 6;
+pub const INFUR_ABI_VERSION: u32 = 7;
 pub const INFUR_SCALE_NEAREST: u32 = 0;
 pub const INFUR_SCALE_BILINEAR: u32 = 1;
 pub const INFUR_DTYPE_F32: u32 = 0;
@@ -158,6 +158,10 @@ extern "C" {
     /// INFUR_DTYPE_F32_SPLIT: largest |activation| fed to a GEMM and largest |Winograd-domain input| of the last
     /// forward, and whether either left the exact range of the f16 pairs
     pub fn infur_split_range(c: *mut infur_ctx, act_amax: *mut f32, wino_amax: *mut f32, saturated: *mut u32) -> i32;
+    /// INFUR_DTYPE_F16_HL (ABI 7): the opt-in range monitor of the three-byte mode -- switch it on / off; read (and clear) what the
+    /// splits saw since it was enabled or last read: largest |activation|, largest |Winograd-domain input|, saturated, NaN seen
+    pub fn infur_hl_monitor_enable(c: *mut infur_ctx, on: u32) -> i32;
+    pub fn infur_hl_range(c: *mut infur_ctx, act_amax: *mut f32, wino_amax: *mut f32, saturated: *mut u32, nan_seen: *mut u32) -> i32;
     // ---- the rest of the header (round 5): device-resident entry points, stage kernels on device buffers, the ONNX converter,
     //      tuning database, per-kernel profile, device memory helpers -- for hosts that keep frames in HBM (a decoder writing into
     //      device memory, a display reading from it) or want the library's measurements; none is needed by `impl Processor` ----

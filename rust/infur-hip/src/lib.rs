@@ -84,6 +84,20 @@ impl Ctx {
         if rc != sys::INFUR_OK { return Err(self.err(rc)); }
         Ok(())
     }
+    /// INFUR_DTYPE_F16_HL contexts: the opt-in range monitor (`infur_hl_monitor_enable`; an error in the other modes)
+    pub fn set_hl_monitor(&self, on: bool) -> Result<(), HipError> {
+        let rc = unsafe { sys::infur_hl_monitor_enable(self.0, on as u32) };
+        if rc != sys::INFUR_OK { return Err(self.err(rc)); }
+        Ok(())
+    }
+    /// what the monitor saw since it was enabled or last read, and clears it (`infur_hl_range`): (max |activation|, max |Winograd-domain
+    /// input|, saturated, NaN seen).  A saturated frame is not f16hl-grade: re-run it on an f32 / f32-split context
+    pub fn hl_range(&self) -> Result<(f32, f32, bool, bool), HipError> {
+        let (mut act, mut wino, mut sat, mut nan) = (0f32, 0f32, 0u32, 0u32);
+        let rc = unsafe { sys::infur_hl_range(self.0, &mut act, &mut wino, &mut sat, &mut nan) };
+        if rc != sys::INFUR_OK { return Err(self.err(rc)); }
+        Ok((act, wino, sat != 0, nan != 0))
+    }
     pub fn profile(&self) -> Result<Vec<(String, String, f32, f64, f64)>, HipError> {
         let mut n = 0u32;
         let rc = unsafe { sys::infur_profile_count(self.0, &mut n) };
