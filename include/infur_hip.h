@@ -269,6 +269,65 @@ int32_t infur_frame_advance_dev(infur_ctx* ctx, const void* d_bgr, uint32_t w, u
                                 size_t rgba_capacity, void* d_scaled_bgr, uint32_t* ow,
                                 uint32_t* oh);
 
+/* ---- Segments: the segmentation result itself, for a host without a display ----
+ * ColorCode turns a pixel's K class values into one shaded colour for the GUI.  A headless host wants the argmax class
+ * index, a usable confidence and per-class data to caption -- the two open items of the reference's own todo list,
+ * README.md:76-77: "softmax if model predictions are logits (and/or clamp confidence shading)" and "class label captions".
+ * Presence of this group is announced by infur_features() & INFUR_FEATURE_SEGMENTS (INFUR_ABI_VERSION does not move:
+ * nothing existing changed).
+ *
+ * Per pixel, over the class values c_k in class order:
+ *   INFUR_DECODE_RAW      the reference's loop, decode_predict.rs:67-78: k_max = 0, c_max = 0.0, strict '>';
+ *                         conf = (c_max * 255.0) as u8 (saturating, truncating)
+ *   INFUR_DECODE_SOFTMAX  the same loop from c_max = -inf (NaN never wins, the first maximum wins);
+ *                         conf = (p * 255.0) as u8, p = 1 / sum_k exp(c_k - c_max) in f32 (NaN terms count 0);
+ *                         nothing won: class 0, conf 0;  c_max = +inf: conf 255
+ * Outputs, each optional (NULL = not wanted; all NULL is INFUR_E_INVALID_ARG):
+ *   klass  h*w bytes, k_max (not wrapped: more than 256 classes is INFUR_E_INVALID_ARG)
+ *   conf   h*w bytes
+ *   stats  k * INFUR_STAT_WORDS uint64_t, class-major: pixel count, sum of x (column), sum of y (row), sum of the
+ *          confidence bytes, bounding box.  A class without a pixel reads 0 everywhere except MIN_X = MIN_Y = UINT64_MAX.
+ *          Integer sums: exact and repeatable.  The table needs no initialisation.
+ *   rgba   h*w*4 bytes, the context's colour table at [k_max % 20][conf]: in RAW mode exactly infur_colorcode's bytes
+ * h*w == 0 writes nothing; k == 0 writes zero planes, infur_colorcode's rgba, and leaves stats alone. */
+enum { INFUR_DECODE_RAW = 0, INFUR_DECODE_SOFTMAX = 1 };
+enum {
+    INFUR_STAT_PIXELS = 0,
+    INFUR_STAT_SUM_X = 1,
+    INFUR_STAT_SUM_Y = 2,
+    INFUR_STAT_SUM_CONF = 3,
+    INFUR_STAT_MIN_X = 4,
+    INFUR_STAT_MIN_Y = 5,
+    INFUR_STAT_MAX_X = 6,
+    INFUR_STAT_MAX_Y = 7,
+    INFUR_STAT_WORDS = 8
+};
+enum { INFUR_FEATURE_SEGMENTS = 1 };
+uint32_t infur_features(void); /* bit mask of additive capabilities of this build */
+/* the 21 Pascal-VOC names torchvision's FCN heads are trained on (0 = "__background__", 15 = "person"); NULL for k >= 21 */
+const char* infur_voc_class_name(uint32_t k);
+
+/* ColorCode's sibling on given confidences.  khw: [k, h, w] f32 planar */
+int32_t infur_segments(infur_ctx* ctx, const float* khw, uint32_t k, uint32_t h, uint32_t w, uint32_t decode,
+                       uint8_t* klass, uint8_t* conf, uint64_t* stats, uint8_t* rgba);
+int32_t infur_segments_dev(infur_ctx* ctx, const void* d_khw, uint32_t k, uint32_t h, uint32_t w, uint32_t decode,
+                           void* d_klass, void* d_conf, void* d_stats, void* d_rgba);
+/* The fused frame path (scale -> model -> decode(out[0])) with this decode instead of ColorCode, fused into the up-sampling
+ * kernel like the first: the full-resolution logits are never materialised.  plane_capacity is that of klass and of conf,
+ * stats_classes the number of classes the table has room for (model_info.num_classes are written); too small is
+ * INFUR_E_CAPACITY.  With no model loaded the Scale stage still runs and the call returns INFUR_E_MODEL_NOT_LOADED.
+ * infur_model_read_lowres works afterwards.  These calls always enqueue eagerly: they neither use nor disturb the graphs
+ * infur_ctx_set_graph_replay has cached for infur_frame_advance_dev.  (The stream ring, batch and group calls produce RGBA
+ * only.) */
+int32_t infur_frame_segments(infur_ctx* ctx, const uint8_t* bgr, uint32_t w, uint32_t h, float factor,
+                             uint32_t scale_mode, uint32_t decode, uint8_t* klass, uint8_t* conf,
+                             size_t plane_capacity, uint64_t* stats, uint32_t stats_classes, uint8_t* rgba,
+                             size_t rgba_capacity, uint8_t* scaled_bgr, uint32_t* ow, uint32_t* oh);
+int32_t infur_frame_segments_dev(infur_ctx* ctx, const void* d_bgr, uint32_t w, uint32_t h, float factor,
+                                 uint32_t scale_mode, uint32_t decode, void* d_klass, void* d_conf,
+                                 size_t plane_capacity, void* d_stats, uint32_t stats_classes, void* d_rgba,
+                                 size_t rgba_capacity, void* d_scaled_bgr, uint32_t* ow, uint32_t* oh);
+
 /* ---- streaming (infur/src/main.rs:27-99,105): bounded queue, copies overlapped with compute ----
  * The reference back-pressures its producer with sync_channel(2) (main.rs:105); a stream
  * here is a ring of `depth` pinned + device slots.  submit() copies the caller's frame into a

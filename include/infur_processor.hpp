@@ -6,6 +6,7 @@
 //   Scale                    infur/src/processing.rs:179-282
 //   Model<f32>               infur/src/predict_onnx.rs:146-345
 //   ColorCode                infur/src/decode_predict.rs:38-84
+//   Segments                 ColorCode's sibling for a headless host (infur_hip.h: class / confidence planes, statistics)
 //
 // Rust `Result<_, E>` becomes a status code (`infur::Status`, 0 = Ok) carried by small error
 // structs; `&mut Option<T>` outputs become `std::optional<T>&`; buffers are reused across calls
@@ -188,6 +189,50 @@ public:
 
 private:
     Context& c_;
+};
+
+/// What `Segments` produces: ask with the `want_*` flags; planes are h * w bytes, `stats` is k rows of INFUR_STAT_WORDS words
+/// (index with INFUR_STAT_*), `rgba` h * w * 4 bytes.  Unwanted outputs are left empty.
+struct SegmentsOut {
+    bool want_klass = true, want_conf = true, want_stats = true, want_rgba = false;
+    uint32_t width = 0, height = 0, classes = 0;
+    std::vector<uint8_t> klass, conf, rgba;
+    std::vector<uint64_t> stats;
+    uint64_t stat(uint32_t k, uint32_t word) const { return stats[(size_t)k * INFUR_STAT_WORDS + word]; }
+};
+
+/// ColorCode's sibling: per-pixel argmax class, confidence byte, per-class statistics, optionally the shaded overlay.
+/// Command = decode mode (INFUR_DECODE_RAW: decode_predict.rs:67-78; INFUR_DECODE_SOFTMAX: the reference's README.md:76 todo).
+/// Input = Array3<f32> [K,H,W], Output = SegmentsOut.
+class Segments {
+public:
+    explicit Segments(Context& c, uint32_t decode = INFUR_DECODE_RAW) : c_(c), decode_(decode) {}
+    Status control(uint32_t decode) {
+        if (decode > INFUR_DECODE_SOFTMAX) return INFUR_E_INVALID_ARG;  // state untouched
+        dirty_ = decode != decode_;
+        decode_ = decode;
+        return INFUR_OK;
+    }
+    bool is_dirty() const { return dirty_; }
+    Status advance(const Tensor3& inp, SegmentsOut& out) {
+        dirty_ = false;
+        const size_t hw = (size_t)inp.w * inp.h;
+        out.width = inp.w;
+        out.height = inp.h;
+        out.classes = inp.k;
+        out.klass.assign(out.want_klass ? hw : 0, 0);
+        out.conf.assign(out.want_conf ? hw : 0, 0);
+        out.rgba.assign(out.want_rgba ? hw * 4 : 0, 0);
+        out.stats.assign(out.want_stats ? (size_t)inp.k * INFUR_STAT_WORDS : 0, 0);
+        return infur_segments(c_.get(), inp.data.data(), inp.k, inp.h, inp.w, decode_, out.want_klass ? out.klass.data() : nullptr,
+                              out.want_conf ? out.conf.data() : nullptr, out.want_stats ? out.stats.data() : nullptr,
+                              out.want_rgba ? out.rgba.data() : nullptr);
+    }
+
+private:
+    Context& c_;
+    uint32_t decode_;
+    bool dirty_ = true;
 };
 
 /// infur_group: n contexts (one per GPU) of one process -- RCCL weight broadcast + frame-batch sharding

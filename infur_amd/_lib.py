@@ -35,6 +35,12 @@ DTYPE_F32_SPLIT = 2
 DTYPE_F32_SPLIT_FP8 = 3  # split mode with the cross terms on the fp8 MX MFMA ("f32x")
 DTYPE_F16_HL = 5  # three-byte tensors (f16 hi + e5m2 lo planes), two MFMA units per product ("f16hl")
 
+# Segments (infur_segments / infur_frame_segments): decode modes, the columns of the statistics table, the feature bit
+DECODE_RAW, DECODE_SOFTMAX = 0, 1
+STAT_PIXELS, STAT_SUM_X, STAT_SUM_Y, STAT_SUM_CONF, STAT_MIN_X, STAT_MIN_Y, STAT_MAX_X, STAT_MAX_Y = range(8)
+STAT_WORDS = 8
+FEATURE_SEGMENTS = 1
+
 
 class Options(C.Structure):
     _fields_ = [
@@ -125,6 +131,13 @@ SIGNATURES = {
     "infur_bgr_to_rgba_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _vp]),
     "infur_frame_advance": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _vp, _sz, _vp, _u32p, _u32p]),
     "infur_frame_advance_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _vp, _sz, _vp, _u32p, _u32p]),
+    "infur_features": (C.c_uint32, []),
+    "infur_voc_class_name": (C.c_char_p, [_u32]),
+    "infur_segments": (C.c_int32, [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),
+    "infur_segments_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),
+    "infur_frame_segments": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _vp, _vp, _sz, _vp, _u32, _vp, _sz, _vp, _u32p, _u32p]),
+    "infur_frame_segments_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _vp, _vp, _sz, _vp, _u32, _vp, _sz, _vp, _u32p,
+                                             _u32p]),
     "infur_stream_create": (C.c_int32, [_vp, _u32, C.POINTER(_vp)]),
     "infur_stream_destroy": (None, [_vp]),
     "infur_stream_add_lane": (C.c_int32, [_vp, _vp]),

@@ -1117,6 +1117,7 @@ int32_t infur_ctx_create(const infur_options* opts, infur_ctx** out) {
                   hipMalloc((void**)&c->d_color_lut, col.size() * 4) == hipSuccess &&
                   hipMemcpy(c->d_pre_lut, pre.data(), pre.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
                   hipMemcpy(c->d_color_lut, col.data(), col.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
+                  hipMalloc((void**)&c->d_seg_shards, kSegShardBytes) == hipSuccess &&
                   ((o.compute_dtype != INFUR_DTYPE_F32_SPLIT && o.compute_dtype != INFUR_DTYPE_F32_SPLIT_FP8) ||
                    (hipMalloc((void**)&c->d_range, 2 * sizeof(unsigned)) == hipSuccess && hipMemset(c->d_range, 0, 2 * sizeof(unsigned)) == hipSuccess));
         if (!ok) return INFUR_E_HIP;  // (guard destroys the context)
@@ -1145,13 +1146,14 @@ void infur_ctx_destroy(infur_ctx* c) {
     graphs_drop(c);
     model_free(c);
     pool_free(c);
-    for (Buf* b : {&c->st_in, &c->st_scaled, &c->st_rgba, &c->st_f32a, &c->st_f32b})
+    for (Buf* b : {&c->st_in, &c->st_scaled, &c->st_rgba, &c->st_f32a, &c->st_f32b, &c->st_seg})
         if (b->p) (void)hipFree(b->p);
     prof_reset(c);
     for (auto e : c->ev_free) (void)hipEventDestroy(e);
     if (c->d_pre_lut) (void)hipFree(c->d_pre_lut);
     if (c->d_u8_lut) (void)hipFree(c->d_u8_lut);
     if (c->d_color_lut) (void)hipFree(c->d_color_lut);
+    if (c->d_seg_shards) (void)hipFree(c->d_seg_shards);
     if (c->d_range) (void)hipFree(c->d_range);
     if (c->d_hlmon) (void)hipFree(c->d_hlmon);
     if (c->d_stem16) (void)hipFree(c->d_stem16);

@@ -163,6 +163,10 @@ struct infur_ctx {
 
     // staging for the host-pointer entry points
     infur::Buf st_in, st_scaled, st_rgba, st_f32a, st_f32b;
+    // Segments (infur_segments.cpp): the statistics shards the kernels accumulate into (kernels.h: kSegShardBytes, allocated with
+    // the context so that the segments calls never move mem_gen) and the host-pointer calls' staging of table + two byte planes
+    unsigned long long* d_seg_shards = nullptr;
+    infur::Buf st_seg;
 
     // profiling
     std::vector<infur::ProfRec> prof;

@@ -4,6 +4,7 @@
 //   infur_tuner.cpp         tile-configuration tuner (pick_cfg) and its database (infur_tune_import / _export)
 //   infur_stream.cpp        streaming ring, frame batch, pinned host buffers
 //   infur_multi.cpp         groups of contexts, RCCL
+//   infur_segments.cpp      the Segments decode (class / confidence planes, statistics): C entry points
 // Everything here lives in namespace infur and is NOT part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -93,6 +94,8 @@ void build_color_lut(uint32_t* lut);
 std::vector<ConvLayer> build_graph(int depth, int ncls, bool aux);
 void model_free(infur_ctx* c);
 UpQuant head_quant(const infur_ctx* c, int k);
+// FCN-ResNet forward from a packed BGR frame on the device; leaves the output-stride-8 logits in c->out_low / c->aux_low
+int32_t forward(infur_ctx* c, const uint8_t* d_bgr, int w, int h);
 int32_t stem16_image(infur_ctx* c, const float* wt, float w_scale, int split, const void** img);
 // measured tile configuration of the conv kernel for one problem shape (infur_tuner.cpp)
 int32_t pick_cfg(infur_ctx* c, const ConvArgs& a, int mode, int out_f32, int* cfg);

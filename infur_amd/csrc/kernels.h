@@ -254,4 +254,24 @@ hipError_t launch_upsample_argmax_shade(const float* low, int LH, int LW, int K,
                                         const uint32_t* lut, uint32_t* rgba, int OH, int OW,
                                         hipStream_t s, const UpQuant uq = UpQuant());
 
+// Segments (prepost.hip): ColorCode's sibling -- class byte, confidence byte, RGBA shaded by that confidence and per-class
+// statistics, any subset (null = not wanted).  softmax: 0 = INFUR_DECODE_RAW, 1 = INFUR_DECODE_SOFTMAX.
+// shards: kSegShards zeroed tables [K][8] u64 the kernels accumulate into; launch_segments_stats_finalize folds them into
+// the caller's K x INFUR_STAT_WORDS table (which needs no initialisation).  K <= kSegMaxClasses.
+constexpr int kSegShards = 16, kSegMaxClasses = 256;
+constexpr size_t kSegShardBytes = (size_t)kSegShards * kSegMaxClasses * 8 * sizeof(unsigned long long);
+struct SegOut {
+    uint8_t* klass = nullptr;
+    uint8_t* conf = nullptr;
+    uint32_t* rgba = nullptr;
+    unsigned long long* shards = nullptr;
+};
+// unfused, over planar [K][H][W] f32
+hipError_t launch_segments_planar(const float* khw, int K, int H, int W, int softmax, const uint32_t* lut, const SegOut& o,
+                                  hipStream_t s);
+// fused with the bilinear up-sample of the NHWC low-res logits; bit-identical to upsample_planar -> segments_planar
+hipError_t launch_upsample_argmax_segments(const float* low, int LH, int LW, int K, int softmax, const uint32_t* lut,
+                                           const SegOut& o, int OH, int OW, hipStream_t s, const UpQuant uq = UpQuant());
+hipError_t launch_segments_stats_finalize(const unsigned long long* shards, int K, unsigned long long* stats, hipStream_t s);
+
 }  // namespace infur

@@ -554,4 +554,296 @@ hipError_t launch_upsample_argmax_shade(const float* low, int LH, int LW, int K,
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------
+// Segments: ColorCode's sibling for a headless host (the reference's own todo list, README.md:76-77: "softmax if model
+// predictions are logits", "class label captions").  Per pixel it produces any subset of
+//   class byte k_max | confidence byte | premultiplied RGBA LUT[k_max % 20][conf] | per-class statistics
+// in one of two decodes (include/infur_hip.h):
+//   RAW      decode_predict.rs:67-78 as shade() above: k_max = 0, c_max = 0.0, strict '>', conf = (c_max * 255) as u8
+//   SOFTMAX  the same loop from c_max = -inf (negative logits are legitimate maxima; NaN never wins, the first maximum wins),
+//            conf = (p * 255) as u8 with p = 1 / sum_k exp(c_k - c_max) in f32 over the K real classes, NaN terms counting 0;
+//            nothing won (all NaN / -inf): class 0, conf 0; c_max = +inf: conf 255
+// Three kernels -- fused + LDS-staged, fused scalar fallback, unfused planar -- share seg_decode() and the statistics code, so
+// they agree bit for bit.  All three keep a wave on ONE output row (lane = column): y is wave-uniform.
+// ---------------------------------------------------------------------------------------
+struct SegPix {
+    int k, conf;
+};
+
+// `cls(k)` is the class value; it is called twice per class in the SOFTMAX decode.  n is a compile-time constant in the staged
+// kernel (the loops unroll over registers; its pad classes arrive as -inf, which neither wins nor adds to the sum).
+template <class F>
+__device__ __forceinline__ SegPix seg_decode(const int n, const int softmax, F&& cls) {
+    int k_max = 0;
+    float c_max = softmax ? -__builtin_inff() : 0.0f;
+#pragma unroll
+    for (int k = 0; k < n; k++) {
+        const float c = cls(k);
+        if (c > c_max) {
+            k_max = k;
+            c_max = c;
+        }
+    }
+    SegPix r;
+    r.k = k_max;
+    if (!softmax) {
+        const float a = c_max * 255.0f;
+        r.conf = a >= 255.0f ? 255 : (int)a;  // Rust `as u8`: saturate, truncate
+        return r;
+    }
+    // exp(d) as exp2(d * log2 e) on v_exp_f32 (1 ulp): with the product's rounding, |d| * 2^-24 relative per term
+    float s = 0.0f;
+#pragma unroll
+    for (int k = 0; k < n; k++) {
+        const float e = __builtin_amdgcn_exp2f((cls(k) - c_max) * 1.44269504088896341f);
+        s = s + (e == e ? e : 0.0f);  // NaN class, or inf - inf under an infinite maximum: no contribution
+    }
+    const float a = (1.0f / s) * 255.0f;  // finite maximum: its own term is exp2(0) = 1, so s >= 1 and a <= 255
+    r.conf = c_max == __builtin_inff() ? 255 : (c_max == -__builtin_inff() ? 0 : (int)a);
+    return r;
+}
+
+// ---- per-class statistics ----
+// Per workgroup an LDS table [class][8] of u32: PIXELS, SUM_X, SUM_Y, SUM_CONF (added), ~MIN_X, ~MIN_Y, MAX_X, MAX_Y (all four
+// by max: a minimum is kept as the maximum of the complement, so a zeroed table is the empty one and one ds_max serves both).
+// Classes are spatially coherent and a wave is 64 consecutive columns of one row, so a wave-row is folded class by class:
+// readlane of the first unfinished lane's class, ballot of equality, and then everything comes out of the 64-bit mask with
+// scalar bit operations -- count (popcount), min / max x (ctz / clz), sum x (popcounts of the mask under the six bit-position
+// masks).  Sum conf needs no cross-lane adds either: the eight ballots of the confidence's bit planes, taken once per row,
+// give sum = sum_b 2^b * popcount(mask & plane_b).  Lanes 0-7 then apply one word each: two LDS instructions per class.
+__device__ __forceinline__ unsigned seg_bit_positions(const uint64_t m) {
+    return (unsigned)__popcll(m & 0xAAAAAAAAAAAAAAAAull) + 2u * (unsigned)__popcll(m & 0xCCCCCCCCCCCCCCCCull) +
+           4u * (unsigned)__popcll(m & 0xF0F0F0F0F0F0F0F0ull) + 8u * (unsigned)__popcll(m & 0xFF00FF00FF00FF00ull) +
+           16u * (unsigned)__popcll(m & 0xFFFF0000FFFF0000ull) + 32u * (unsigned)__popcll(m & 0xFFFFFFFF00000000ull);
+}
+
+__device__ __forceinline__ void seg_row_stats(unsigned* __restrict__ sstat, const bool live, const int k, const int conf,
+                                              const unsigned x0, const unsigned y) {
+    uint64_t todo = __ballot(live);
+    if (!todo) return;
+    uint64_t plane[8];
+#pragma unroll
+    for (int b = 0; b < 8; b++) plane[b] = __ballot(live && ((conf >> b) & 1));
+    const int lane = threadIdx.x & 63;
+    while (todo) {
+        const int kc = __builtin_amdgcn_readlane(k, __builtin_ctzll(todo));
+        const uint64_t m = __ballot(live && k == kc);
+        todo &= ~m;
+        const unsigned n = (unsigned)__popcll(m);
+        unsigned sconf = 0;
+#pragma unroll
+        for (int b = 0; b < 8; b++) sconf += (unsigned)__popcll(m & plane[b]) << b;
+        const unsigned lo = x0 + (unsigned)__builtin_ctzll(m), hi = x0 + 63u - (unsigned)__builtin_clzll(m);
+        const unsigned word[8] = {n, n * x0 + seg_bit_positions(m), n * y, sconf, ~lo, ~y, hi, y};
+        unsigned v = word[0];
+#pragma unroll
+        for (int i = 1; i < 8; i++) v = lane == i ? word[i] : v;
+        if (lane < 4)
+            atomicAdd(&sstat[kc * 8 + lane], v);
+        else if (lane < 8)
+            atomicMax(&sstat[kc * 8 + lane], v);
+    }
+}
+
+// One atomic per word and workgroup, and only for the classes the workgroup saw, into one of kSegShards copies of the table:
+// at 1080p ~2,000 workgroups nearly all hold the dominant class, and one contended word serialises at L2 (~88 returning
+// atomics / us) -- sixteen shards of non-returning 64-bit atomics keep that off the kernel's tail.
+__device__ __forceinline__ void seg_flush_stats(const unsigned* __restrict__ sstat, const int K, unsigned long long* __restrict__ shards) {
+    __syncthreads();
+    unsigned long long* g = shards + (size_t)((blockIdx.y * gridDim.x + blockIdx.x) % kSegShards) * K * 8;
+    for (int i = threadIdx.x; i < K * 8; i += 256) {
+        if (sstat[i & ~7] == 0) continue;
+        const unsigned long long v = sstat[i];
+        if ((i & 7) < 4)
+            atomicAdd(g + i, v);
+        else
+            atomicMax(g + i, v);
+    }
+}
+
+// shards -> the caller's K x 8 table, with the empty-class values (MIN_* = UINT64_MAX, everything else 0)
+__global__ void __launch_bounds__(256) segments_stats_finalize_kernel(const unsigned long long* __restrict__ shards, int K,
+                                                                      unsigned long long* __restrict__ stats) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= K * 8) return;
+    const int w = i & 7;
+    unsigned long long acc = 0, n = 0;
+    for (int s = 0; s < kSegShards; s++) {
+        const unsigned long long v = shards[(size_t)s * K * 8 + i];
+        n += shards[(size_t)s * K * 8 + (i & ~7)];
+        acc = w < 4 ? acc + v : (v > acc ? v : acc);
+    }
+    if (w == 4 || w == 5) acc = n ? 0xFFFFFFFFull - acc : ~0ull;
+    stats[i] = acc;
+}
+
+hipError_t launch_segments_stats_finalize(const unsigned long long* shards, int K, unsigned long long* stats, hipStream_t s) {
+    if (K <= 0) return hipSuccess;
+    hipLaunchKernelGGL(segments_stats_finalize_kernel, dim3((K * 8 + 255) / 256), dim3(256), 0, s, shards, K, stats);
+    return hipGetLastError();
+}
+
+__device__ __forceinline__ void seg_store_pixel(const SegOut& o, const uint32_t* __restrict__ lut, const SegPix p, const size_t at) {
+    if (o.klass) o.klass[at] = (uint8_t)p.k;
+    if (o.conf) o.conf[at] = (uint8_t)p.conf;
+    if (o.rgba) o.rgba[at] = lut[(p.k % 20) * 256 + p.conf];
+}
+
+// unfused: planar [K][H][W] confidences, as colorcode_planar reads them.  Workgroup = 64 columns x 4 rows, one row per wave.
+__global__ void __launch_bounds__(256)
+    segments_planar_kernel(const float* __restrict__ khw, int K, int H, int W, int softmax, const uint32_t* __restrict__ lut,
+                           const SegOut o) {
+    __shared__ unsigned sstat[kSegMaxClasses * 8];
+    if (o.shards) {
+        for (int i = threadIdx.x; i < K * 8; i += 256) sstat[i] = 0;
+        __syncthreads();
+    }
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const bool live = x < W && y < H;
+    SegPix p = {0, 0};
+    if (live) {
+        const size_t HW = (size_t)H * W, at = (size_t)y * W + x;
+        p = seg_decode(K, softmax, [&](int k) { return khw[(size_t)k * HW + at]; });
+        seg_store_pixel(o, lut, p, at);
+    }
+    if (o.shards) {
+        seg_row_stats(sstat, live, p.k, p.conf, blockIdx.x * 64, y);
+        seg_flush_stats(sstat, K, o.shards);
+    }
+}
+
+hipError_t launch_segments_planar(const float* khw, int K, int H, int W, int softmax, const uint32_t* lut, const SegOut& o,
+                                  hipStream_t s) {
+    dim3 grid((W + 63) / 64, (H + 3) / 4);
+    hipLaunchKernelGGL(segments_planar_kernel, grid, dim3(256), 0, s, khw, K, H, W, softmax, lut, o);
+    return hipGetLastError();
+}
+
+// fused, scalar form (more classes than a staged slot holds, or a ratio that is not staged): upsample_argmax_shade_kernel's loop
+__global__ void __launch_bounds__(256)
+    upsample_argmax_segments_kernel(const float* __restrict__ low, int LH, int LW, int K, int softmax,
+                                    const uint32_t* __restrict__ lut, const SegOut o, int OH, int OW, const UpQuant uq) {
+    __shared__ unsigned sstat[kSegMaxClasses * 8];
+    if (o.shards) {
+        for (int i = threadIdx.x; i < K * 8; i += 256) sstat[i] = 0;
+        __syncthreads();
+    }
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const bool live = x < OW && y < OH;
+    SegPix p = {0, 0};
+    if (live) {
+        const Lerp tx = lerp_coord(x, LW, OW), ty = lerp_coord(y, LH, OH);
+        const float* p11 = low + ((size_t)ty.i1 * LW + tx.i1) * K;
+        const float* p21 = low + ((size_t)ty.i1 * LW + tx.i2) * K;
+        const float* p12 = low + ((size_t)ty.i2 * LW + tx.i1) * K;
+        const float* p22 = low + ((size_t)ty.i2 * LW + tx.i2) * K;
+        p = seg_decode(K, softmax, [&](int k) { return up_post(bilerp(p11[k], p21[k], p12[k], p22[k], tx.d1, tx.d2, ty.d1, ty.d2), uq); });
+        seg_store_pixel(o, lut, p, (size_t)y * OW + x);
+    }
+    if (o.shards) {
+        seg_row_stats(sstat, live, p.k, p.conf, blockIdx.x * 64, y);
+        seg_flush_stats(sstat, K, o.shards);
+    }
+}
+
+// A lane of the staged kernel owns one column and FOUR rows, so its four class (or confidence) bytes are one register and a
+// wave's natural store would be 64 single bytes per row.  Instead the 4 x 4 bytes of four neighbouring lanes are transposed
+// with four quad-broadcast DPP moves: lane j of a quad ends up with row j's four columns and the wave stores 64 dwords
+// (16 per row) in one instruction.  Needs OW % 4 == 0 and a dword-aligned plane (then a quad is live or dead as a whole);
+// other shapes store bytes.
+__device__ __forceinline__ void seg_store_rows4(uint8_t* __restrict__ plane, const uint32_t mine, const bool dwords, const bool live,
+                                                const int x, const int y0, const int OH, const int OW) {
+    if (!plane) return;
+    if (dwords) {
+        const uint32_t q0 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mine, 0x00, 0xf, 0xf, false);
+        const uint32_t q1 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mine, 0x55, 0xf, 0xf, false);
+        const uint32_t q2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mine, 0xAA, 0xf, 0xf, false);
+        const uint32_t q3 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mine, 0xFF, 0xf, 0xf, false);
+        const int j = x & 3, sh = 8 * j;
+        const uint32_t row = ((q0 >> sh) & 255u) | (((q1 >> sh) & 255u) << 8) | (((q2 >> sh) & 255u) << 16) | ((q3 >> sh) << 24);
+        if (live && y0 + j < OH) *reinterpret_cast<uint32_t*>(plane + (size_t)(y0 + j) * OW + (x & ~3)) = row;
+    } else if (live) {
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+            if (y0 + r < OH) plane[(size_t)(y0 + r) * OW + x] = (uint8_t)(mine >> (8 * r));
+    }
+}
+
+// fused, LDS-staged: upsample_argmax_shade_lds_kernel's staging, register quads and expression tree; the decode and the
+// outputs differ.  No lane leaves early (the statistics end in a barrier): columns beyond OW compute on clamped coordinates
+// and are masked at the stores and in the ballots.
+template <int NQ>
+__global__ void __launch_bounds__(256)
+    upsample_argmax_segments_lds_kernel(const float* __restrict__ low, int LH, int LW, int K, int softmax,
+                                        const uint32_t* __restrict__ lut, const SegOut o, int OH, int OW, const UpQuant uq) {
+    static_assert(UP_TH / 4 == 4, "a lane's rows are packed into one dword");
+    extern __shared__ __attribute__((aligned(16))) float up_smem[];
+    __shared__ unsigned sstat[UP_KP * 8];
+    if (o.shards && threadIdx.x < UP_KP * 8) sstat[threadIdx.x] = 0;  // (published by the barriers of the staging)
+    const UpTile t = stage_lowres_tile(low, LH, LW, K, OH, OW, up_smem);
+    const int xl = threadIdx.x & 63;
+    const int x = blockIdx.x * UP_TW + xl;
+    const bool live = x < OW;
+    const Lerp tx = t.tx[xl];
+    const int ca = (tx.i1 - t.c0) * UP_KP, cb = (tx.i2 - t.c0) * UP_KP;
+    float4 v11[NQ], v21[NQ], v12[NQ], v22[NQ];
+    int pi1 = -1, pi2 = -1;
+    const int y0 = blockIdx.y * UP_TH + 4 * (threadIdx.x >> 6);
+    uint32_t kpack = 0, cpack = 0;
+#pragma unroll
+    for (int rr = 0; rr < UP_TH / 4; rr++) {
+        const int y = y0 + rr;
+        if (y >= OH) break;
+        const Lerp ty = t.ty[y - blockIdx.y * UP_TH];
+        const int i1 = __builtin_amdgcn_readfirstlane(ty.i1), i2 = __builtin_amdgcn_readfirstlane(ty.i2);
+        if (i1 != pi1 || i2 != pi2) {
+            load_quads<NQ>(t.pix + (i1 - t.r0) * t.nc * UP_KP, t.pix + (i2 - t.r0) * t.nc * UP_KP, ca, cb, v11, v21, v12, v22);
+            pi1 = i1;
+            pi2 = i2;
+        }
+        const float w11 = tx.d2 * ty.d2, w21 = tx.d1 * ty.d2, w12 = tx.d2 * ty.d1, w22 = tx.d1 * ty.d1;
+        float c[4 * NQ];
+#pragma unroll
+        for (int q = 0; q < NQ; q++) {
+            const f32x2 lo = bilerp2(f32x2{v11[q].x, v11[q].y}, f32x2{v21[q].x, v21[q].y}, f32x2{v12[q].x, v12[q].y},
+                                     f32x2{v22[q].x, v22[q].y}, w11, w21, w12, w22);
+            const f32x2 hi = bilerp2(f32x2{v11[q].z, v11[q].w}, f32x2{v21[q].z, v21[q].w}, f32x2{v12[q].z, v12[q].w},
+                                     f32x2{v22[q].z, v22[q].w}, w11, w21, w12, w22);
+            c[4 * q + 0] = up_post(lo.x, uq);
+            c[4 * q + 1] = up_post(lo.y, uq);
+            c[4 * q + 2] = up_post(hi.x, uq);
+            c[4 * q + 3] = up_post(hi.y, uq);
+        }
+        // the zero pad classes of the staged slot (only the last quad has any: NQ = ceil(K / 4)) must neither win against a
+        // negative maximum nor enter the softmax sum
+#pragma unroll
+        for (int e = 1; e < 4; e++)
+            if (4 * (NQ - 1) + e >= K) c[4 * (NQ - 1) + e] = -__builtin_inff();
+        const SegPix p = seg_decode(4 * NQ, softmax, [&](int k) { return c[k]; });
+        if (live && o.rgba) o.rgba[(size_t)y * OW + x] = lut[(p.k % 20) * 256 + p.conf];
+        kpack |= (uint32_t)p.k << (8 * rr);
+        cpack |= (uint32_t)p.conf << (8 * rr);
+        if (o.shards) seg_row_stats(sstat, live, p.k, p.conf, blockIdx.x * UP_TW, y);
+    }
+    const bool dwords = (OW & 3) == 0 && ((reinterpret_cast<uintptr_t>(o.klass) | reinterpret_cast<uintptr_t>(o.conf)) & 3) == 0;
+    seg_store_rows4(o.klass, kpack, dwords, live, x, y0, OH, OW);
+    seg_store_rows4(o.conf, cpack, dwords, live, x, y0, OH, OW);
+    if (o.shards) seg_flush_stats(sstat, K, o.shards);
+}
+
+hipError_t launch_upsample_argmax_segments(const float* low, int LH, int LW, int K, int softmax, const uint32_t* lut,
+                                           const SegOut& o, int OH, int OW, hipStream_t s, const UpQuant uq) {
+    const size_t lds = up_tile_lds_bytes(LH, LW, K, OH, OW);
+    if (lds) {
+        dim3 grid((OW + UP_TW - 1) / UP_TW, (OH + UP_TH - 1) / UP_TH);
+        UP_DISPATCH_NQ(upsample_argmax_segments_lds_kernel, K, grid, dim3(256), lds, s, low, LH, LW, K, softmax, lut, o, OH, OW, uq)
+    } else {
+        dim3 grid((OW + 63) / 64, (OH + 3) / 4);
+        hipLaunchKernelGGL(upsample_argmax_segments_kernel, grid, dim3(256), 0, s, low, LH, LW, K, softmax, lut, o, OH, OW, uq);
+    }
+    return hipGetLastError();
+}
+
 }  // namespace infur

@@ -419,6 +419,107 @@ class ColorCode(Processor):
         self.ctx.check(self.ctx.L.infur_colorcode(self.ctx.h, khw.ctypes.data, k, h, w, img.ctypes.data))
 
 
+class SegmentsOut:
+    """``Segments``' ``&mut Output``: what to produce (``want_*``) and, after ``advance``, the results -- ``klass`` / ``conf``
+    [H, W] u8, ``stats`` [K, 8] uint64 (columns ``_lib.STAT_*``), ``rgba`` [H, W, 4] u8; None where not wanted."""
+
+    def __init__(self, want_klass: bool = True, want_conf: bool = True, want_stats: bool = True, want_rgba: bool = False):
+        self.want_klass, self.want_conf, self.want_stats, self.want_rgba = want_klass, want_conf, want_stats, want_rgba
+        self.klass = self.conf = self.stats = self.rgba = None
+
+
+class Segments(Processor):
+    """ColorCode's sibling for a host without a display: per-pixel argmax class, confidence byte, per-class statistics and
+    (optionally) the RGBA overlay shaded by that confidence.
+
+    Command = decode mode (``_lib.DECODE_RAW``: the reference's loop, decode_predict.rs:67-78; ``_lib.DECODE_SOFTMAX``: the
+    same loop over logits with the softmax probability of the winner as confidence -- the reference's README.md:76 todo).
+    Input = Array3<f32> [K, H, W]; Output = ``SegmentsOut``.
+    """
+
+    def __init__(self, ctx: Context, decode: int = _lib.DECODE_RAW):
+        self.ctx = ctx
+        self.decode = decode
+        self.dirty = True
+
+    def control(self, cmd: int) -> "Segments":
+        if cmd not in (_lib.DECODE_RAW, _lib.DECODE_SOFTMAX):
+            raise InfurError(_lib.E_INVALID_ARG, f"unknown decode mode {cmd}")  # state untouched
+        self.dirty = cmd != self.decode
+        self.decode = cmd
+        return self
+
+    def is_dirty(self) -> bool:
+        return self.dirty
+
+    def advance(self, inp: np.ndarray, out: SegmentsOut) -> None:
+        self.dirty = False
+        if inp.ndim != 3:
+            raise InfurError(_lib.E_SHAPE, f"expected [K,H,W], got {inp.shape}")
+        khw = np.ascontiguousarray(inp, np.float32)
+        k, h, w = khw.shape
+
+        def buf(want, old, shape, dtype):
+            if not want:
+                return None
+            return old if old is not None and old.shape == shape and old.dtype == dtype and old.flags.c_contiguous else np.zeros(shape, dtype)
+
+        out.klass = buf(out.want_klass, out.klass, (h, w), np.uint8)
+        out.conf = buf(out.want_conf, out.conf, (h, w), np.uint8)
+        out.stats = buf(out.want_stats, out.stats, (k, _lib.STAT_WORDS), np.uint64)
+        out.rgba = buf(out.want_rgba, out.rgba, (h, w, 4), np.uint8)
+        ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
+        self.ctx.check(self.ctx.L.infur_segments(self.ctx.h, khw.ctypes.data, k, h, w, self.decode, ptr(out.klass), ptr(out.conf),
+                                                 ptr(out.stats), ptr(out.rgba)))
+
+
+class SegmentsFrame(NamedTuple):
+    """``FramePath.advance_segments``: class plane and confidence plane [oh, ow] u8, statistics [K, 8] uint64, RGBA overlay
+    [oh, ow, 4] u8 or None, scaled BGR frame or None"""
+
+    klass: Optional[np.ndarray]
+    conf: Optional[np.ndarray]
+    stats: Optional[np.ndarray]
+    rgba: Optional[np.ndarray]
+    scaled: Optional[np.ndarray]
+
+
+def voc_class_name(ctx_or_lib, k: int) -> Optional[str]:
+    """The Pascal-VOC name torchvision's FCN heads give class ``k`` (None beyond the 21)."""
+    L = getattr(ctx_or_lib, "L", ctx_or_lib)
+    s = L.infur_voc_class_name(k)
+    return s.decode() if s is not None else None
+
+
+def class_summary(stats: np.ndarray, ow: int, oh: int, names=None) -> List[dict]:
+    """The caption records of a frame: one dict per class that occurs, largest first -- ``klass``, ``name``, ``pixels``,
+    ``share`` of the ow x oh mask, ``centroid`` (x, y), ``box`` (min_x, min_y, max_x, max_y; inclusive) and
+    ``mean_confidence`` in [0, 1].  ``names``: class index -> label (default: the library's Pascal-VOC names)."""
+    if names is None:
+        L = _lib.load()
+        names = lambda k: voc_class_name(L, k)  # noqa: E731
+    elif not callable(names):
+        table = list(names)
+        names = lambda k: table[k] if k < len(table) else None  # noqa: E731
+    recs = []
+    total = float(ow) * float(oh)
+    for k, row in enumerate(np.asarray(stats, np.uint64)):
+        n = int(row[_lib.STAT_PIXELS])
+        if n == 0:
+            continue
+        recs.append({
+            "klass": k,
+            "name": names(k) or f"class{k}",
+            "pixels": n,
+            "share": n / total if total else 0.0,
+            "centroid": (int(row[_lib.STAT_SUM_X]) / n, int(row[_lib.STAT_SUM_Y]) / n),
+            "box": (int(row[_lib.STAT_MIN_X]), int(row[_lib.STAT_MIN_Y]), int(row[_lib.STAT_MAX_X]), int(row[_lib.STAT_MAX_Y])),
+            "mean_confidence": int(row[_lib.STAT_SUM_CONF]) / (255.0 * n),
+        })
+    recs.sort(key=lambda r: (-r["pixels"], r["klass"]))
+    return recs
+
+
 def pack_normalize(ctx: Context, img: np.ndarray) -> np.ndarray:
     """The pre-proc stage on its own (predict_onnx.rs:103-137): BGR u8 HWC -> RGB f32 CHW."""
     img = _check_bgr(img)
@@ -459,6 +560,38 @@ class FramePath:
             return None, scaled  # mask cleared (app.rs:127-129)
         self.ctx.check(rc)
         return rgba, scaled
+
+    def advance_segments(self, img: np.ndarray, factor: float = 1.0, decode: int = _lib.DECODE_RAW, want_rgba: bool = False,
+                         want_scaled: bool = False, want_klass: bool = True, want_conf: bool = True,
+                         want_stats: bool = True) -> SegmentsFrame:
+        """The same fused path with the Segments decode instead of ColorCode -> ``SegmentsFrame``; every result field is None
+        when no model is loaded (``scaled`` is still produced)."""
+        img = _check_bgr(img)
+        h, w = img.shape[:2]
+        L = self.ctx.L
+        f = float(np.float32(factor))
+        rc = L.infur_scale_validate(f)
+        if rc:
+            raise ValidScaleError(rc)
+        ow, oh = C.c_uint32(0), C.c_uint32(0)
+        rc = L.infur_scale_out_dims(w, h, f, C.byref(ow), C.byref(oh))
+        if rc:
+            raise ScaleProcError(rc)
+        mi = _lib.ModelInfoC()
+        k = mi.num_classes if L.infur_model_info_get(self.ctx.h, C.byref(mi)) == _lib.OK else 0
+        klass = np.empty((oh.value, ow.value), np.uint8) if want_klass else None
+        conf = np.empty((oh.value, ow.value), np.uint8) if want_conf else None
+        stats = np.zeros((k, _lib.STAT_WORDS), np.uint64) if want_stats else None
+        rgba = np.empty((oh.value, ow.value, 4), np.uint8) if want_rgba else None
+        scaled = np.empty((oh.value, ow.value, 3), np.uint8) if want_scaled else None
+        ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
+        rc = L.infur_frame_segments(self.ctx.h, img.ctypes.data, w, h, f, self.scale_mode, decode, ptr(klass), ptr(conf),
+                                    oh.value * ow.value, ptr(stats), k, ptr(rgba), rgba.nbytes if want_rgba else 0, ptr(scaled),
+                                    C.byref(ow), C.byref(oh))
+        if rc == _lib.E_MODEL_NOT_LOADED:
+            return SegmentsFrame(None, None, None, None, scaled)
+        self.ctx.check(rc)
+        return SegmentsFrame(klass, conf, stats, rgba, scaled)
 
     def advance_batch(self, imgs, factor: float = 1.0, outs=None):
         """A batch of independent frames (BASELINE configs[3]) -> list of masks, in order.  ``outs``: caller-owned mask arrays to fill

@@ -81,6 +81,21 @@ pub const INFUR_DTYPE_F32_SPLIT_FP8: u32 = 3;
 /// three-byte tensors (f16 hi + e5m2 lo planes written by the producer, staged by LDS-DMA), two MFMA units per product:
 /// logits ~1.5e-4 from f32 on heavy-tailed weights, ~2.5x the f32 MFMA rate (round 5; 4 is not an option value)
 pub const INFUR_DTYPE_F16_HL: u32 = 5;
+/// Segments: decode modes (the reference's loop / the same from -inf with a softmax confidence)
+pub const INFUR_DECODE_RAW: u32 = 0;
+pub const INFUR_DECODE_SOFTMAX: u32 = 1;
+/// Segments: the columns of one class's row of the statistics table (`INFUR_STAT_WORDS` u64 each)
+pub const INFUR_STAT_PIXELS: u32 = 0;
+pub const INFUR_STAT_SUM_X: u32 = 1;
+pub const INFUR_STAT_SUM_Y: u32 = 2;
+pub const INFUR_STAT_SUM_CONF: u32 = 3;
+pub const INFUR_STAT_MIN_X: u32 = 4;
+pub const INFUR_STAT_MIN_Y: u32 = 5;
+pub const INFUR_STAT_MAX_X: u32 = 6;
+pub const INFUR_STAT_MAX_Y: u32 = 7;
+pub const INFUR_STAT_WORDS: u32 = 8;
+/// bit of `infur_features()`: the Segments calls below exist
+pub const INFUR_FEATURE_SEGMENTS: u32 = 1;
 
 extern "C" {
     pub fn infur_abi_version() -> u32;
@@ -194,4 +209,18 @@ extern "C" {
     pub fn infur_dev_free(c: *mut infur_ctx, d_ptr: *mut c_void) -> i32;
     pub fn infur_memcpy_h2d(c: *mut infur_ctx, d_dst: *mut c_void, src: *const c_void, bytes: usize) -> i32;
     pub fn infur_memcpy_d2h(c: *mut infur_ctx, dst: *mut c_void, d_src: *const c_void, bytes: usize) -> i32;
+    // ---- Segments: class plane, confidence plane, per-class statistics, RGBA shaded by that confidence (any may be null) ----
+    pub fn infur_features() -> u32;
+    pub fn infur_voc_class_name(k: u32) -> *const c_char;
+    pub fn infur_segments(c: *mut infur_ctx, khw: *const f32, k: u32, h: u32, w: u32, decode: u32, klass: *mut u8, conf: *mut u8,
+                          stats: *mut u64, rgba: *mut u8) -> i32;
+    pub fn infur_segments_dev(c: *mut infur_ctx, d_khw: *const c_void, k: u32, h: u32, w: u32, decode: u32, d_klass: *mut c_void,
+                              d_conf: *mut c_void, d_stats: *mut c_void, d_rgba: *mut c_void) -> i32;
+    pub fn infur_frame_segments(c: *mut infur_ctx, bgr: *const u8, w: u32, h: u32, factor: f32, scale_mode: u32, decode: u32,
+                                klass: *mut u8, conf: *mut u8, plane_capacity: usize, stats: *mut u64, stats_classes: u32,
+                                rgba: *mut u8, rgba_capacity: usize, scaled_bgr: *mut u8, ow: *mut u32, oh: *mut u32) -> i32;
+    pub fn infur_frame_segments_dev(c: *mut infur_ctx, d_bgr: *const c_void, w: u32, h: u32, factor: f32, scale_mode: u32,
+                                    decode: u32, d_klass: *mut c_void, d_conf: *mut c_void, plane_capacity: usize,
+                                    d_stats: *mut c_void, stats_classes: u32, d_rgba: *mut c_void, rgba_capacity: usize,
+                                    d_scaled_bgr: *mut c_void, ow: *mut u32, oh: *mut u32) -> i32;
 }

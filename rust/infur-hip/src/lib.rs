@@ -364,6 +364,62 @@ impl Processor for HipColorCode {
     }
 }
 
+// ---------------------------------------------------------------- Segments (ColorCode's sibling for a headless host)
+/// What `HipSegments` produces.  `klass` / `conf` are `h * w` bytes, `stats` is `classes` rows of `INFUR_STAT_WORDS` words (index
+/// with `sys::INFUR_STAT_*`), `rgba` the overlay shaded by `conf`.  The `want_*` flags select the outputs; the others stay empty.
+pub struct Segments {
+    pub want_klass: bool, pub want_conf: bool, pub want_stats: bool, pub want_rgba: bool,
+    pub size: [usize; 2], pub classes: usize,
+    pub klass: Vec<u8>, pub conf: Vec<u8>, pub stats: Vec<u64>, pub rgba: Vec<u8>,
+}
+impl Default for Segments {
+    fn default() -> Self {
+        Self { want_klass: true, want_conf: true, want_stats: true, want_rgba: false, size: [0, 0], classes: 0,
+               klass: Vec::new(), conf: Vec::new(), stats: Vec::new(), rgba: Vec::new() }
+    }
+}
+impl Segments {
+    pub fn stat(&self, k: usize, word: u32) -> u64 { self.stats[k * sys::INFUR_STAT_WORDS as usize + word as usize] }
+}
+/// Per-pixel argmax class, confidence byte, per-class statistics, optionally the shaded overlay.  Command = decode mode:
+/// `INFUR_DECODE_RAW` is the loop of decode_predict.rs:67-78, `INFUR_DECODE_SOFTMAX` the same loop over logits with the softmax
+/// probability of the winner as confidence (the README's "softmax if model predictions are logits").
+pub struct HipSegments { ctx: Rc<Ctx>, decode: u32, dirty: bool }
+impl HipSegments { pub fn new(ctx: Rc<Ctx>) -> Self { Self { ctx, decode: sys::INFUR_DECODE_RAW, dirty: true } } }
+impl Processor for HipSegments {
+    type Command = u32;
+    type ControlError = HipError;
+    type Input = Array3<f32>;
+    type Output = Segments;
+    type ProcessResult = Result<(), HipError>;
+
+    fn control(&mut self, cmd: u32) -> Result<&mut Self, HipError> {
+        if cmd > sys::INFUR_DECODE_SOFTMAX { return Err(HipError::status(sys::INFUR_E_INVALID_ARG)); } // state untouched
+        self.dirty = cmd != self.decode;
+        self.decode = cmd;
+        Ok(self)
+    }
+    fn is_dirty(&self) -> bool { self.dirty }
+    fn advance(&mut self, inp: &Array3<f32>, out: &mut Segments) -> Result<(), HipError> {
+        self.dirty = false;
+        let s = inp.shape();
+        let (k, h, w) = (s[0], s[1], s[2]);
+        out.size = [w, h];
+        out.classes = k;
+        out.klass.resize(if out.want_klass { h * w } else { 0 }, 0);
+        out.conf.resize(if out.want_conf { h * w } else { 0 }, 0);
+        out.stats.resize(if out.want_stats { k * sys::INFUR_STAT_WORDS as usize } else { 0 }, 0);
+        out.rgba.resize(if out.want_rgba { h * w * 4 } else { 0 }, 0);
+        fn ptr<T>(want: bool, v: &mut Vec<T>) -> *mut T { if want { v.as_mut_ptr() } else { std::ptr::null_mut() } }
+        let std = inp.as_standard_layout();
+        let rc = unsafe {
+            sys::infur_segments(self.ctx.0, std.as_ptr(), k as u32, h as u32, w as u32, self.decode, ptr(out.want_klass, &mut out.klass),
+                                ptr(out.want_conf, &mut out.conf), ptr(out.want_stats, &mut out.stats), ptr(out.want_rgba, &mut out.rgba))
+        };
+        if rc == sys::INFUR_OK { Ok(()) } else { Err(HipError::from_ctx(&self.ctx, rc)) }
+    }
+}
+
 // ---------------------------------------------------------------- streaming ring with zero-copy slots (main.rs:27-99,105; ABI 5)
 /// The bounded queue of frames in flight (`sync_channel(2)`, main.rs:105) over `infur_stream_*`.  `next_slot` / `commit` let the
 /// decoder fill the ring's own pinned buffer in place -- what `ff-video/src/decoder.rs:156-165` does with its reused `BgrImage` --
