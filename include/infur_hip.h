@@ -328,6 +328,58 @@ int32_t infur_frame_segments_dev(infur_ctx* ctx, const void* d_bgr, uint32_t w, 
                                  size_t plane_capacity, void* d_stats, uint32_t stats_classes, void* d_rgba,
                                  size_t rgba_capacity, void* d_scaled_bgr, uint32_t* ow, uint32_t* oh);
 
+/* ---- Regions: the connected components of the class plane, one table row per object ----
+ * Segments' statistics are per class: two people are one "person" row whose centroid lies between them.  Regions is the
+ * third decode stage: per-object captions, counts, boxes and speckle removal.  Presence of this group is announced by
+ * infur_features() & INFUR_FEATURE_REGIONS (INFUR_ABI_VERSION does not move).
+ *
+ * A region is a maximal set of pixels of equal class, connected under INFUR_CONNECT_4 or INFUR_CONNECT_8 (any other
+ * connectivity, or an unknown flag bit, is INFUR_E_INVALID_ARG).
+ *   flags & INFUR_REGIONS_SKIP_BACKGROUND   class-0 pixels form no region and are labelled INFUR_REGION_NONE
+ *   min_pixels                              regions with fewer pixels are dropped, their pixels labelled INFUR_REGION_NONE
+ *                                           (0 and 1 keep everything)
+ * Kept regions are numbered densely from 0 in ascending order of their FIRST pixel (the smallest linear index y*w + x in
+ * the region); the table is in that order.  Everything is an integer and nothing depends on the order in which the
+ * device happened to work: two runs give identical bytes.
+ * Outputs, each optional (NULL = not wanted; all NULL is INFUR_E_INVALID_ARG), none needs initialisation:
+ *   labels     h*w uint32_t: the id of the pixel's region, or INFUR_REGION_NONE
+ *   table      table_rows rows of INFUR_REGION_WORDS uint64_t: words 0-7 are the INFUR_STAT_* words restricted to the
+ *              region (conf == NULL: SUM_CONF = 0), word INFUR_REGION_CLASS its class, word INFUR_REGION_FIRST its first
+ *              pixel.  Only the first min(n, table_rows) rows are written; rows at or beyond n are left alone.
+ *   n_regions  the number of kept regions, even when it exceeds table_rows (truncation is not an error; ids at or above
+ *              table_rows are still written to the label plane)
+ * h*w == 0 writes n_regions = 0 and nothing else; h*w >= 2^32 - 1 is INFUR_E_INVALID_ARG. */
+#define INFUR_REGION_NONE 0xFFFFFFFFu
+enum { INFUR_CONNECT_4 = 4, INFUR_CONNECT_8 = 8 };
+enum { INFUR_REGIONS_SKIP_BACKGROUND = 1 };
+enum { INFUR_REGION_CLASS = 8, INFUR_REGION_FIRST = 9, INFUR_REGION_WORDS = 10 };
+enum { INFUR_FEATURE_REGIONS = 2 };
+
+/* on given planes (klass: h*w class bytes; conf: h*w confidence bytes or NULL) */
+int32_t infur_regions(infur_ctx* ctx, const uint8_t* klass, const uint8_t* conf, uint32_t h, uint32_t w,
+                      uint32_t connectivity, uint32_t min_pixels, uint32_t flags, uint32_t* labels, uint64_t* table,
+                      uint32_t table_rows, uint32_t* n_regions);
+/* device pointers throughout, d_n_regions included (one device uint32_t); enqueued on the context's stream */
+int32_t infur_regions_dev(infur_ctx* ctx, const void* d_klass, const void* d_conf, uint32_t h, uint32_t w,
+                          uint32_t connectivity, uint32_t min_pixels, uint32_t flags, void* d_labels, void* d_table,
+                          uint32_t table_rows, void* d_n_regions);
+/* The fused frame path with both decode stages: scale -> model -> Segments decode(out[0]) -> Regions, in one call.  klass and
+ * conf are optional outputs here (plane_capacity bytes each; the library decodes into scratch of its own otherwise);
+ * labels_capacity is in bytes (ow*oh*4 needed).  Too little capacity is INFUR_E_CAPACITY.  With no model loaded the Scale
+ * stage still runs and the call returns INFUR_E_MODEL_NOT_LOADED.  Like infur_frame_segments these calls always enqueue
+ * eagerly and leave the graphs cached for infur_frame_advance_dev alone.  (The stream ring, batch and group calls produce
+ * RGBA only.) */
+int32_t infur_frame_regions(infur_ctx* ctx, const uint8_t* bgr, uint32_t w, uint32_t h, float factor,
+                            uint32_t scale_mode, uint32_t decode, uint32_t connectivity, uint32_t min_pixels,
+                            uint32_t flags, uint8_t* klass, uint8_t* conf, size_t plane_capacity, uint32_t* labels,
+                            size_t labels_capacity, uint64_t* table, uint32_t table_rows, uint32_t* n_regions,
+                            uint8_t* scaled_bgr, uint32_t* ow, uint32_t* oh);
+int32_t infur_frame_regions_dev(infur_ctx* ctx, const void* d_bgr, uint32_t w, uint32_t h, float factor,
+                                uint32_t scale_mode, uint32_t decode, uint32_t connectivity, uint32_t min_pixels,
+                                uint32_t flags, void* d_klass, void* d_conf, size_t plane_capacity, void* d_labels,
+                                size_t labels_capacity, void* d_table, uint32_t table_rows, void* d_n_regions,
+                                void* d_scaled_bgr, uint32_t* ow, uint32_t* oh);
+
 /* ---- streaming (infur/src/main.rs:27-99,105): bounded queue, copies overlapped with compute ----
  * The reference back-pressures its producer with sync_channel(2) (main.rs:105); a stream
  * here is a ring of `depth` pinned + device slots.  submit() copies the caller's frame into a

@@ -7,6 +7,7 @@
 //   Model<f32>               infur/src/predict_onnx.rs:146-345
 //   ColorCode                infur/src/decode_predict.rs:38-84
 //   Segments                 ColorCode's sibling for a headless host (infur_hip.h: class / confidence planes, statistics)
+//   Regions                  the third decode stage (infur_hip.h: connected components, label plane, per-region table)
 //
 // Rust `Result<_, E>` becomes a status code (`infur::Status`, 0 = Ok) carried by small error
 // structs; `&mut Option<T>` outputs become `std::optional<T>&`; buffers are reused across calls
@@ -232,6 +233,74 @@ public:
 private:
     Context& c_;
     uint32_t decode_;
+    bool dirty_ = true;
+};
+
+/// What `Regions` consumes: the planes `Segments` wrote (`conf` may be empty: the rows' SUM_CONF is then 0).
+struct Planes {
+    uint32_t width = 0, height = 0;
+    std::vector<uint8_t> klass, conf;
+};
+
+/// What `Regions` produces: `labels` is h * w region ids (INFUR_REGION_NONE: no kept region), `table` holds min(n, table_rows)
+/// rows of INFUR_REGION_WORDS words in ascending order of the regions' first pixel, `n` counts every kept region.
+struct RegionsOut {
+    bool want_labels = true;
+    uint32_t table_rows = 1024;
+    uint32_t width = 0, height = 0, n = 0;
+    std::vector<uint32_t> labels;
+    std::vector<uint64_t> table;
+    uint32_t rows() const { return n < table_rows ? n : table_rows; }
+    uint64_t word(uint32_t id, uint32_t w) const { return table[(size_t)id * INFUR_REGION_WORDS + w]; }
+};
+
+/// The third decode stage: connected components of the class plane under 4- or 8-connectivity, regions below `min_pixels`
+/// dropped, optionally without the background class.  Integer results, identical from run to run.
+/// Command = one of connectivity / min_pixels / flags; Input = Planes, Output = RegionsOut.
+class Regions {
+public:
+    struct Cmd {
+        enum Kind { Connectivity, MinPixels, Flags } kind;
+        uint32_t value;
+    };
+    explicit Regions(Context& c, uint32_t connectivity = INFUR_CONNECT_8) : c_(c), connectivity_(connectivity) {}
+    Status control(Cmd cmd) {
+        uint32_t conn = connectivity_, minpx = min_pixels_, flags = flags_;
+        switch (cmd.kind) {
+            case Cmd::Connectivity:
+                if (cmd.value != INFUR_CONNECT_4 && cmd.value != INFUR_CONNECT_8) return INFUR_E_INVALID_ARG;  // state untouched
+                conn = cmd.value;
+                break;
+            case Cmd::MinPixels: minpx = cmd.value; break;
+            case Cmd::Flags:
+                if (cmd.value & ~(uint32_t)INFUR_REGIONS_SKIP_BACKGROUND) return INFUR_E_INVALID_ARG;
+                flags = cmd.value;
+                break;
+            default: return INFUR_E_INVALID_ARG;
+        }
+        dirty_ = dirty_ || conn != connectivity_ || minpx != min_pixels_ || flags != flags_;
+        connectivity_ = conn;
+        min_pixels_ = minpx;
+        flags_ = flags;
+        return INFUR_OK;
+    }
+    bool is_dirty() const { return dirty_; }
+    Status advance(const Planes& inp, RegionsOut& out) {
+        dirty_ = false;
+        const size_t hw = (size_t)inp.width * inp.height;
+        if (inp.klass.size() != hw || (!inp.conf.empty() && inp.conf.size() != hw)) return INFUR_E_SHAPE;
+        out.width = inp.width;
+        out.height = inp.height;
+        out.labels.assign(out.want_labels ? hw : 0, INFUR_REGION_NONE);
+        out.table.assign((size_t)out.table_rows * INFUR_REGION_WORDS, 0);
+        return infur_regions(c_.get(), inp.klass.data(), inp.conf.empty() ? nullptr : inp.conf.data(), inp.height, inp.width, connectivity_,
+                             min_pixels_, flags_, out.want_labels ? out.labels.data() : nullptr,
+                             out.table_rows ? out.table.data() : nullptr, out.table_rows, &out.n);
+    }
+
+private:
+    Context& c_;
+    uint32_t connectivity_, min_pixels_ = 0, flags_ = 0;
     bool dirty_ = true;
 };
 

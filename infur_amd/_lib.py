@@ -40,6 +40,12 @@ DECODE_RAW, DECODE_SOFTMAX = 0, 1
 STAT_PIXELS, STAT_SUM_X, STAT_SUM_Y, STAT_SUM_CONF, STAT_MIN_X, STAT_MIN_Y, STAT_MAX_X, STAT_MAX_Y = range(8)
 STAT_WORDS = 8
 FEATURE_SEGMENTS = 1
+# Regions (infur_regions / infur_frame_regions): connectivity, flags, the two extra columns of a region's row, the feature bit
+CONNECT_4, CONNECT_8 = 4, 8
+REGIONS_SKIP_BACKGROUND = 1
+REGION_CLASS, REGION_FIRST, REGION_WORDS = 8, 9, 10
+REGION_NONE = 0xFFFFFFFF
+FEATURE_REGIONS = 2
 
 
 class Options(C.Structure):
@@ -138,6 +144,12 @@ SIGNATURES = {
     "infur_frame_segments": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _vp, _vp, _sz, _vp, _u32, _vp, _sz, _vp, _u32p, _u32p]),
     "infur_frame_segments_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _vp, _vp, _sz, _vp, _u32, _vp, _sz, _vp, _u32p,
                                              _u32p]),
+    "infur_regions": (C.c_int32, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _u32, _vp]),
+    "infur_regions_dev": (C.c_int32, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _u32, _vp]),
+    "infur_frame_regions": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp, _vp,
+                                        _u32p, _u32p]),
+    "infur_frame_regions_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp,
+                                            _vp, _u32p, _u32p]),
     "infur_stream_create": (C.c_int32, [_vp, _u32, C.POINTER(_vp)]),
     "infur_stream_destroy": (None, [_vp]),
     "infur_stream_add_lane": (C.c_int32, [_vp, _vp]),

@@ -1146,7 +1146,8 @@ void infur_ctx_destroy(infur_ctx* c) {
     graphs_drop(c);
     model_free(c);
     pool_free(c);
-    for (Buf* b : {&c->st_in, &c->st_scaled, &c->st_rgba, &c->st_f32a, &c->st_f32b, &c->st_seg})
+    for (Buf* b : {&c->st_in, &c->st_scaled, &c->st_rgba, &c->st_f32a, &c->st_f32b, &c->st_seg, &c->st_reg, &c->st_reg_planes,
+                   &c->st_reg_io})
         if (b->p) (void)hipFree(b->p);
     prof_reset(c);
     for (auto e : c->ev_free) (void)hipEventDestroy(e);

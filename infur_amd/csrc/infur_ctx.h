@@ -167,6 +167,9 @@ struct infur_ctx {
     // the context so that the segments calls never move mem_gen) and the host-pointer calls' staging of table + two byte planes
     unsigned long long* d_seg_shards = nullptr;
     infur::Buf st_seg;
+    // Regions (infur_regions.cpp): the union-find scratch (parent, counts, ids, scan sums), the planes the frame calls decode into
+    // when the caller does not want them, and the host-pointer calls' staging.  Grown lazily, like st_seg without moving mem_gen.
+    infur::Buf st_reg, st_reg_planes, st_reg_io;
 
     // profiling
     std::vector<infur::ProfRec> prof;

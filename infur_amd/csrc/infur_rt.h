@@ -5,6 +5,7 @@
 //   infur_stream.cpp        streaming ring, frame batch, pinned host buffers
 //   infur_multi.cpp         groups of contexts, RCCL
 //   infur_segments.cpp      the Segments decode (class / confidence planes, statistics): C entry points
+//   infur_regions.cpp       Regions (connected components of the class plane, per-region table): C entry points
 // Everything here lives in namespace infur and is NOT part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -274,4 +274,12 @@ hipError_t launch_upsample_argmax_segments(const float* low, int LH, int LW, int
                                            const SegOut& o, int OH, int OW, hipStream_t s, const UpQuant uq = UpQuant());
 hipError_t launch_segments_stats_finalize(const unsigned long long* shards, int K, unsigned long long* stats, hipStream_t s);
 
+// Regions (regions.hip): connected components of a class plane -- u32 label plane, rows x kRegWords u64 table, region count
+// (each optional; d_n is a device word).  scratch: regions_scratch_bytes(H * W) bytes the launches own for the call.
+// conn8: 0 = 4-connectivity.  Stream-ordered; no workgroup waits for another.  H * W in [1, 2^32 - 2].
+constexpr int kRegWords = 10;
+size_t regions_scratch_bytes(size_t npix);
+hipError_t launch_regions(const uint8_t* klass, const uint8_t* conf, unsigned H, unsigned W, int conn8, unsigned min_pixels, int skip_bg,
+                          void* scratch, unsigned* labels, unsigned long long* table, unsigned rows, unsigned* d_n, hipStream_t s);
+
 }  // namespace infur

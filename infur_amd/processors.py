@@ -520,6 +520,131 @@ def class_summary(stats: np.ndarray, ow: int, oh: int, names=None) -> List[dict]
     return recs
 
 
+@dataclass
+class RegionsCmd:
+    """``Regions``' command: exactly one of connectivity (``_lib.CONNECT_4`` / ``_lib.CONNECT_8``), min_pixels, flags."""
+
+    connectivity: Optional[int] = None
+    min_pixels: Optional[int] = None
+    flags: Optional[int] = None
+
+    @staticmethod
+    def Connectivity(v: int) -> "RegionsCmd":
+        return RegionsCmd(connectivity=v)
+
+    @staticmethod
+    def MinPixels(v: int) -> "RegionsCmd":
+        return RegionsCmd(min_pixels=v)
+
+    @staticmethod
+    def Flags(v: int) -> "RegionsCmd":
+        return RegionsCmd(flags=v)
+
+
+class RegionsOut:
+    """``Regions``' ``&mut Output``: what to produce (``want_labels``, ``table_rows``) and, after ``advance``, the results --
+    ``labels`` [H, W] u32 (``_lib.REGION_NONE``: no kept region) or None, ``table`` [min(n, table_rows), 10] uint64 (columns
+    ``_lib.STAT_*``, ``_lib.REGION_CLASS``, ``_lib.REGION_FIRST``) or None, ``n`` the number of kept regions."""
+
+    def __init__(self, want_labels: bool = True, table_rows: int = 1024):
+        self.want_labels, self.table_rows = want_labels, table_rows
+        self.labels = self.table = None
+        self.n = 0
+
+
+class Regions(Processor):
+    """The third decode stage: the connected components of a class plane, one table row per object.
+
+    Command = ``RegionsCmd``.  Input = (klass [H, W] u8, conf [H, W] u8 or None), e.g. ``SegmentsOut``'s planes;
+    Output = ``RegionsOut``.  Regions are numbered in ascending order of their first pixel; the results are integers and
+    identical from run to run.
+    """
+
+    def __init__(self, ctx: Context, connectivity: int = _lib.CONNECT_8, min_pixels: int = 0, flags: int = 0):
+        self.ctx = ctx
+        self.connectivity, self.min_pixels, self.flags = connectivity, min_pixels, flags
+        self.dirty = True
+
+    def control(self, cmd: RegionsCmd) -> "Regions":
+        given = [v for v in (cmd.connectivity, cmd.min_pixels, cmd.flags) if v is not None]
+        if len(given) != 1:
+            raise InfurError(_lib.E_INVALID_ARG, "a RegionsCmd sets exactly one of connectivity, min_pixels, flags")
+        if cmd.connectivity is not None and cmd.connectivity not in (_lib.CONNECT_4, _lib.CONNECT_8):
+            raise InfurError(_lib.E_INVALID_ARG, f"connectivity {cmd.connectivity}: 4 or 8")  # state untouched
+        if cmd.flags is not None and cmd.flags & ~_lib.REGIONS_SKIP_BACKGROUND:
+            raise InfurError(_lib.E_INVALID_ARG, f"unknown regions flags {cmd.flags:#x}")
+        if cmd.min_pixels is not None and not 0 <= cmd.min_pixels <= 0xFFFFFFFF:
+            raise InfurError(_lib.E_INVALID_ARG, f"min_pixels {cmd.min_pixels}")
+        new = (cmd.connectivity if cmd.connectivity is not None else self.connectivity,
+               cmd.min_pixels if cmd.min_pixels is not None else self.min_pixels, cmd.flags if cmd.flags is not None else self.flags)
+        self.dirty = self.dirty or new != (self.connectivity, self.min_pixels, self.flags)
+        self.connectivity, self.min_pixels, self.flags = new
+        return self
+
+    def is_dirty(self) -> bool:
+        return self.dirty
+
+    def advance(self, inp, out: RegionsOut) -> None:
+        self.dirty = False
+        klass, conf = inp
+        if klass.ndim != 2 or (conf is not None and conf.shape != klass.shape):
+            raise InfurError(_lib.E_SHAPE, f"expected [H,W] planes, got {klass.shape}")
+        klass = np.ascontiguousarray(klass, np.uint8)
+        conf = np.ascontiguousarray(conf, np.uint8) if conf is not None else None
+        h, w = klass.shape
+        rows = max(0, min(int(out.table_rows), h * w))
+        labels = np.empty((h, w), np.uint32) if out.want_labels else None
+        table = np.zeros((rows, _lib.REGION_WORDS), np.uint64) if rows else None
+        n = C.c_uint32(0)
+        ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
+        self.ctx.check(self.ctx.L.infur_regions(self.ctx.h, ptr(klass), ptr(conf), h, w, self.connectivity, self.min_pixels, self.flags,
+                                                ptr(labels), ptr(table), rows, C.addressof(n)))
+        out.labels, out.n = labels, n.value
+        out.table = table[:min(n.value, rows)] if table is not None else None
+
+
+class RegionsFrame(NamedTuple):
+    """``FramePath.advance_regions``: class / confidence planes [oh, ow] u8 (None where not wanted), label plane [oh, ow] u32,
+    region table [min(n, table_rows), 10] uint64, the number of kept regions, scaled BGR frame or None"""
+
+    klass: Optional[np.ndarray]
+    conf: Optional[np.ndarray]
+    labels: Optional[np.ndarray]
+    table: Optional[np.ndarray]
+    n: Optional[int]
+    scaled: Optional[np.ndarray]
+
+
+def region_summary(table: np.ndarray, n: int, ow: int, oh: int, names=None) -> List[dict]:
+    """The caption records of a frame's objects: one dict per table row, in id order -- ``id``, ``klass``, ``name``, ``pixels``,
+    ``share`` of the ow x oh mask, ``centroid`` (x, y), ``box`` (min_x, min_y, max_x, max_y; inclusive), ``mean_confidence``
+    in [0, 1] and ``first`` (x, y), the region's first pixel in raster order.  ``n`` may exceed the rows the table holds (a
+    truncated table): the rows there are are summarised.  ``names`` as in ``class_summary``."""
+    if names is None:
+        L = _lib.load()
+        names = lambda k: voc_class_name(L, k)  # noqa: E731
+    elif not callable(names):
+        lookup = list(names)
+        names = lambda k: lookup[k] if k < len(lookup) else None  # noqa: E731
+    recs = []
+    total = float(ow) * float(oh)
+    rows = np.asarray(table, np.uint64).reshape(-1, _lib.REGION_WORDS)
+    for i, row in enumerate(rows[:min(int(n), len(rows))]):
+        px, k, first = int(row[_lib.STAT_PIXELS]), int(row[_lib.REGION_CLASS]), int(row[_lib.REGION_FIRST])
+        recs.append({
+            "id": i,
+            "klass": k,
+            "name": names(k) or f"class{k}",
+            "pixels": px,
+            "share": px / total if total else 0.0,
+            "centroid": (int(row[_lib.STAT_SUM_X]) / px, int(row[_lib.STAT_SUM_Y]) / px),
+            "box": (int(row[_lib.STAT_MIN_X]), int(row[_lib.STAT_MIN_Y]), int(row[_lib.STAT_MAX_X]), int(row[_lib.STAT_MAX_Y])),
+            "mean_confidence": int(row[_lib.STAT_SUM_CONF]) / (255.0 * px),
+            "first": (first % ow, first // ow) if ow else (0, 0),
+        })
+    return recs
+
+
 def pack_normalize(ctx: Context, img: np.ndarray) -> np.ndarray:
     """The pre-proc stage on its own (predict_onnx.rs:103-137): BGR u8 HWC -> RGB f32 CHW."""
     img = _check_bgr(img)
@@ -592,6 +717,39 @@ class FramePath:
             return SegmentsFrame(None, None, None, None, scaled)
         self.ctx.check(rc)
         return SegmentsFrame(klass, conf, stats, rgba, scaled)
+
+    def advance_regions(self, img: np.ndarray, factor: float = 1.0, decode: int = _lib.DECODE_RAW, connectivity: int = _lib.CONNECT_8,
+                        min_pixels: int = 0, flags: int = 0, table_rows: int = 1024, want_labels: bool = True, want_klass: bool = True,
+                        want_conf: bool = True, want_scaled: bool = False) -> RegionsFrame:
+        """The fused path with both decode stages, scale -> model -> Segments decode -> Regions, in one call -> ``RegionsFrame``;
+        every result field is None when no model is loaded (``scaled`` is still produced)."""
+        img = _check_bgr(img)
+        h, w = img.shape[:2]
+        L = self.ctx.L
+        f = float(np.float32(factor))
+        rc = L.infur_scale_validate(f)
+        if rc:
+            raise ValidScaleError(rc)
+        ow, oh = C.c_uint32(0), C.c_uint32(0)
+        rc = L.infur_scale_out_dims(w, h, f, C.byref(ow), C.byref(oh))
+        if rc:
+            raise ScaleProcError(rc)
+        npix = oh.value * ow.value
+        rows = max(0, min(int(table_rows), npix))
+        klass = np.empty((oh.value, ow.value), np.uint8) if want_klass else None
+        conf = np.empty((oh.value, ow.value), np.uint8) if want_conf else None
+        labels = np.empty((oh.value, ow.value), np.uint32) if want_labels else None
+        table = np.zeros((rows, _lib.REGION_WORDS), np.uint64) if rows else None
+        scaled = np.empty((oh.value, ow.value, 3), np.uint8) if want_scaled else None
+        n = C.c_uint32(0)
+        ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
+        rc = L.infur_frame_regions(self.ctx.h, img.ctypes.data, w, h, f, self.scale_mode, decode, connectivity, min_pixels, flags,
+                                   ptr(klass), ptr(conf), npix, ptr(labels), npix * 4, ptr(table), rows, C.addressof(n), ptr(scaled),
+                                   C.byref(ow), C.byref(oh))
+        if rc == _lib.E_MODEL_NOT_LOADED:
+            return RegionsFrame(None, None, None, None, None, scaled)
+        self.ctx.check(rc)
+        return RegionsFrame(klass, conf, labels, table[:min(n.value, rows)] if table is not None else None, n.value, scaled)
 
     def advance_batch(self, imgs, factor: float = 1.0, outs=None):
         """A batch of independent frames (BASELINE configs[3]) -> list of masks, in order.  ``outs``: caller-owned mask arrays to fill

@@ -9,6 +9,15 @@
 (name, pixels, share, centroid, box, mean confidence of every class that occurs -- the "class label captions" of the
 reference's todo list).  ``--softmax`` decodes logits with the softmax probability as confidence instead of the
 reference's raw ``c_max * 255``.  Frames go through the fused scale -> model -> segments path one at a time.
+
+``--regions`` adds the per-object view: each JSON line gains ``"regions": [region_summary records]`` (id, class, name, pixels,
+share, box, centroid, mean confidence and first pixel of every connected region of the class plane, in raster order of their
+first pixels) and ``"n_regions"``; ``--connectivity 4|8``, ``--min-pixels N`` (drop speckle) and ``--skip-background`` select
+them, ``--max-regions`` bounds the records per frame, ``--regions-out`` receives the u32 label planes back to back
+(0xFFFFFFFF: no kept region).  With ``--regions`` the frame stays on the device between the decode stages: the class and
+confidence planes are written to device buffers, labelled there, and only what is written out or summarised comes back.
+``--conf-out`` receives the confidence planes (one byte per pixel).  Without these options the output is what it was before
+they existed.
 """
 from __future__ import annotations
 
@@ -32,11 +41,20 @@ def main(argv=None) -> int:
     ap.add_argument("--input", default="-", help="raw bgr24 file (default stdin)")
     ap.add_argument("--labels-out", default="", help="raw class planes, one byte per pixel")
     ap.add_argument("--stats-out", default="-", help="JSON lines (default stdout)")
+    ap.add_argument("--regions", action="store_true", help="add the connected regions of the class plane to every record")
+    ap.add_argument("--connectivity", type=int, default=8, choices=[4, 8])
+    ap.add_argument("--min-pixels", type=int, default=0, help="drop regions with fewer pixels")
+    ap.add_argument("--skip-background", action="store_true", help="class 0 forms no region")
+    ap.add_argument("--max-regions", type=int, default=1024, help="region records per frame (the count is always complete)")
+    ap.add_argument("--regions-out", default="", help="raw u32 label planes, four bytes per pixel (needs --regions)")
+    ap.add_argument("--conf-out", default="", help="raw confidence planes, one byte per pixel")
     a = ap.parse_args(argv)
+    if a.regions_out and not a.regions:
+        ap.error("--regions-out needs --regions")
 
     from . import _lib
     from .app import RawVideoSource, VideoProcError
-    from .processors import Context, FramePath, Model, ModelCmd, class_summary
+    from .processors import Context, FramePath, Model, ModelCmd, class_summary, region_summary
 
     ctx = Context(device=a.device, dtype=a.dtype)
     model = Model(ctx)
@@ -56,6 +74,13 @@ def main(argv=None) -> int:
     fp = FramePath(ctx, scale_mode=_lib.SCALE_BILINEAR if a.bilinear else _lib.SCALE_NEAREST)
     decode = _lib.DECODE_SOFTMAX if a.softmax else _lib.DECODE_RAW
     img = src.empty_image()
+    freg = open(a.regions_out, "wb") if a.regions_out else None
+    fconf = open(a.conf_out, "wb") if a.conf_out else None
+    rpath = None
+    if a.regions:
+        oh, ow = _out_dims(ctx, a.width, a.height, a.scale)
+        rpath = _RegionsPath(ctx, a.width, a.height, ow, oh, a.scale, fp.scale_mode, model.get_info().num_classes, max(0, a.max_regions))
+        flags = _lib.REGIONS_SKIP_BACKGROUND if a.skip_background else 0
     n, t0 = 0, time.perf_counter()
     while True:
         try:
@@ -64,19 +89,90 @@ def main(argv=None) -> int:
             if e.kind == "FinishedNormally":
                 break
             raise
-        s = fp.advance_segments(img, a.scale, decode, want_klass=flab is not None, want_conf=False)
+        if rpath is not None:
+            s, labels, table, nreg = rpath.advance(img, decode, a.connectivity, a.min_pixels, flags, flab is not None, fconf is not None,
+                                                   freg is not None)
+        else:
+            s = fp.advance_segments(img, a.scale, decode, want_klass=flab is not None, want_conf=fconf is not None)
         oh, ow = (s.klass.shape if s.klass is not None else _out_dims(ctx, a.width, a.height, a.scale))
         if flab is not None:
             flab.write(memoryview(s.klass).cast("B"))
-        fst.write(json.dumps({"frame": fid, "width": ow, "height": oh, "classes": class_summary(s.stats, ow, oh)}) + "\n")
+        if fconf is not None:
+            fconf.write(memoryview(s.conf).cast("B"))
+        rec = {"frame": fid, "width": ow, "height": oh, "classes": class_summary(s.stats, ow, oh)}
+        if rpath is not None:
+            rec["n_regions"] = nreg
+            rec["regions"] = region_summary(table, nreg, ow, oh)
+            if freg is not None:
+                freg.write(memoryview(labels).cast("B"))
+        fst.write(json.dumps(rec) + "\n")
         n += 1
-    for f in (flab, fst):
+    for f in (flab, fconf, freg, fst):
         if f is not None:
             f.flush()
     el = time.perf_counter() - t0
     sys.stderr.write(f"infur segments: {n} frames in {el:.2f} s ({n / max(el, 1e-9):.1f} frames/s)\n")
+    if rpath is not None:
+        rpath.close()
     ctx.close()
     return 0
+
+
+class _RegionsPath:
+    """--regions: scale -> model -> Segments decode -> Regions with the frame resident on the device.  infur_frame_segments_dev
+    writes class plane, confidence plane and per-class table into device buffers, infur_regions_dev labels those planes where
+    they are; the tables, the count and the planes that are written out are all that is copied back."""
+
+    def __init__(self, ctx, w, h, ow, oh, factor, scale_mode, classes, rows):
+        import ctypes as C
+
+        self.ctx, self.w, self.h, self.ow, self.oh, self.factor, self.mode = ctx, w, h, ow, oh, float(factor), scale_mode
+        self.k, self.rows = classes, min(rows, ow * oh)
+        self.d = {}
+        for name, n in (("bgr", w * h * 3), ("klass", ow * oh), ("conf", ow * oh), ("stats", classes * _STAT_BYTES), ("labels", ow * oh * 4),
+                        ("table", self.rows * _ROW_BYTES), ("n", 4)):
+            p = C.c_void_p(None)
+            ctx.check(ctx.L.infur_dev_alloc(ctx.h, max(n, 4), C.byref(p)))
+            self.d[name] = p
+
+    def _read(self, name, shape, dtype):
+        import numpy as np
+
+        out = np.empty(shape, dtype)
+        if out.nbytes:
+            self.ctx.check(self.ctx.L.infur_memcpy_d2h(self.ctx.h, out.ctypes.data, self.d[name], out.nbytes))
+        return out
+
+    def advance(self, img, decode, connectivity, min_pixels, flags, want_klass, want_conf, want_labels):
+        """-> (SegmentsFrame with the planes that were asked for and the per-class table, labels or None, table rows, n)"""
+        import ctypes as C
+
+        import numpy as np
+
+        from .processors import SegmentsFrame
+
+        c, L, d = self.ctx, self.ctx.L, self.d
+        ow, oh = C.c_uint32(0), C.c_uint32(0)
+        c.check(L.infur_memcpy_h2d(c.h, d["bgr"], img.ctypes.data, img.nbytes))
+        c.check(L.infur_frame_segments_dev(c.h, d["bgr"], self.w, self.h, self.factor, self.mode, decode, d["klass"], d["conf"], self.ow * self.oh,
+                                           d["stats"], self.k, None, 0, None, C.byref(ow), C.byref(oh)))
+        c.check(L.infur_regions_dev(c.h, d["klass"], d["conf"], self.oh, self.ow, connectivity, min_pixels, flags, d["labels"] if want_labels else None,
+                                    d["table"] if self.rows else None, self.rows, d["n"]))
+        n = int(self._read("n", (1,), np.uint32)[0])
+        seg = SegmentsFrame(self._read("klass", (self.oh, self.ow), np.uint8) if want_klass else None,
+                            self._read("conf", (self.oh, self.ow), np.uint8) if want_conf else None,
+                            self._read("stats", (self.k, _STAT_BYTES // 8), np.uint64), None, None)
+        labels = self._read("labels", (self.oh, self.ow), np.uint32) if want_labels else None
+        return seg, labels, self._read("table", (min(n, self.rows), _ROW_BYTES // 8), np.uint64), n
+
+    def close(self):
+        for p in self.d.values():
+            self.ctx.L.infur_dev_free(self.ctx.h, p)
+        self.d = {}
+
+
+_STAT_BYTES = 8 * 8    # INFUR_STAT_WORDS u64 per class
+_ROW_BYTES = 10 * 8    # INFUR_REGION_WORDS u64 per region
 
 
 def _out_dims(ctx, w, h, factor):

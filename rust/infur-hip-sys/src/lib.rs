@@ -96,6 +96,17 @@ pub const INFUR_STAT_MAX_Y: u32 = 7;
 pub const INFUR_STAT_WORDS: u32 = 8;
 /// bit of `infur_features()`: the Segments calls below exist
 pub const INFUR_FEATURE_SEGMENTS: u32 = 1;
+/// Regions: connectivity, flags, the two extra columns of a region's row (`INFUR_REGION_WORDS` u64 each; words 0-7 are `INFUR_STAT_*`)
+pub const INFUR_CONNECT_4: u32 = 4;
+pub const INFUR_CONNECT_8: u32 = 8;
+pub const INFUR_REGIONS_SKIP_BACKGROUND: u32 = 1;
+pub const INFUR_REGION_CLASS: u32 = 8;
+pub const INFUR_REGION_FIRST: u32 = 9;
+pub const INFUR_REGION_WORDS: u32 = 10;
+/// label of a pixel that belongs to no kept region
+pub const INFUR_REGION_NONE: u32 = 0xFFFF_FFFF;
+/// bit of `infur_features()`: the Regions calls below exist
+pub const INFUR_FEATURE_REGIONS: u32 = 2;
 
 extern "C" {
     pub fn infur_abi_version() -> u32;
@@ -223,4 +234,19 @@ extern "C" {
                                     decode: u32, d_klass: *mut c_void, d_conf: *mut c_void, plane_capacity: usize,
                                     d_stats: *mut c_void, stats_classes: u32, d_rgba: *mut c_void, rgba_capacity: usize,
                                     d_scaled_bgr: *mut c_void, ow: *mut u32, oh: *mut u32) -> i32;
+    // ---- Regions: connected components of the class plane: label plane, per-region table, count (any may be null) ----
+    pub fn infur_regions(c: *mut infur_ctx, klass: *const u8, conf: *const u8, h: u32, w: u32, connectivity: u32, min_pixels: u32,
+                         flags: u32, labels: *mut u32, table: *mut u64, table_rows: u32, n_regions: *mut u32) -> i32;
+    pub fn infur_regions_dev(c: *mut infur_ctx, d_klass: *const c_void, d_conf: *const c_void, h: u32, w: u32, connectivity: u32,
+                             min_pixels: u32, flags: u32, d_labels: *mut c_void, d_table: *mut c_void, table_rows: u32,
+                             d_n_regions: *mut c_void) -> i32;
+    pub fn infur_frame_regions(c: *mut infur_ctx, bgr: *const u8, w: u32, h: u32, factor: f32, scale_mode: u32, decode: u32,
+                               connectivity: u32, min_pixels: u32, flags: u32, klass: *mut u8, conf: *mut u8, plane_capacity: usize,
+                               labels: *mut u32, labels_capacity: usize, table: *mut u64, table_rows: u32, n_regions: *mut u32,
+                               scaled_bgr: *mut u8, ow: *mut u32, oh: *mut u32) -> i32;
+    pub fn infur_frame_regions_dev(c: *mut infur_ctx, d_bgr: *const c_void, w: u32, h: u32, factor: f32, scale_mode: u32, decode: u32,
+                                   connectivity: u32, min_pixels: u32, flags: u32, d_klass: *mut c_void, d_conf: *mut c_void,
+                                   plane_capacity: usize, d_labels: *mut c_void, labels_capacity: usize, d_table: *mut c_void,
+                                   table_rows: u32, d_n_regions: *mut c_void, d_scaled_bgr: *mut c_void, ow: *mut u32,
+                                   oh: *mut u32) -> i32;
 }

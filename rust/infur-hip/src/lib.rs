@@ -420,6 +420,72 @@ impl Processor for HipSegments {
     }
 }
 
+// ---------------------------------------------------------------- Regions (connected components of the class plane)
+/// What `HipRegions` consumes: the planes `HipSegments` wrote (`conf` may be empty: the rows' SUM_CONF is then 0).
+#[derive(Default)]
+pub struct Planes { pub size: [usize; 2], pub klass: Vec<u8>, pub conf: Vec<u8> }
+/// What `HipRegions` produces.  `labels` is `h * w` region ids (`sys::INFUR_REGION_NONE`: no kept region), `table` holds
+/// `min(n, table_rows)` rows of `INFUR_REGION_WORDS` words in ascending order of the regions' first pixel, `n` counts every kept region.
+pub struct Regions {
+    pub want_labels: bool, pub table_rows: usize,
+    pub size: [usize; 2], pub n: u32,
+    pub labels: Vec<u32>, pub table: Vec<u64>,
+}
+impl Default for Regions {
+    fn default() -> Self { Self { want_labels: true, table_rows: 1024, size: [0, 0], n: 0, labels: Vec::new(), table: Vec::new() } }
+}
+impl Regions {
+    pub fn rows(&self) -> usize { (self.n as usize).min(self.table_rows) }
+    pub fn word(&self, id: usize, word: u32) -> u64 { self.table[id * sys::INFUR_REGION_WORDS as usize + word as usize] }
+}
+pub enum RegionsCmd { Connectivity(u32), MinPixels(u32), Flags(u32) }
+/// Connected components of the class plane under 4- or 8-connectivity, speckle below `min_pixels` dropped, optionally without the
+/// background class.  Integer results, identical from run to run.
+pub struct HipRegions { ctx: Rc<Ctx>, connectivity: u32, min_pixels: u32, flags: u32, dirty: bool }
+impl HipRegions {
+    pub fn new(ctx: Rc<Ctx>) -> Self { Self { ctx, connectivity: sys::INFUR_CONNECT_8, min_pixels: 0, flags: 0, dirty: true } }
+}
+impl Processor for HipRegions {
+    type Command = RegionsCmd;
+    type ControlError = HipError;
+    type Input = Planes;
+    type Output = Regions;
+    type ProcessResult = Result<(), HipError>;
+
+    fn control(&mut self, cmd: RegionsCmd) -> Result<&mut Self, HipError> {
+        match cmd {  // a refused command leaves the state untouched
+            RegionsCmd::Connectivity(v) => {
+                if v != sys::INFUR_CONNECT_4 && v != sys::INFUR_CONNECT_8 { return Err(HipError::status(sys::INFUR_E_INVALID_ARG)); }
+                self.dirty |= v != self.connectivity;
+                self.connectivity = v;
+            }
+            RegionsCmd::MinPixels(v) => { self.dirty |= v != self.min_pixels; self.min_pixels = v; }
+            RegionsCmd::Flags(v) => {
+                if v & !sys::INFUR_REGIONS_SKIP_BACKGROUND != 0 { return Err(HipError::status(sys::INFUR_E_INVALID_ARG)); }
+                self.dirty |= v != self.flags;
+                self.flags = v;
+            }
+        }
+        Ok(self)
+    }
+    fn is_dirty(&self) -> bool { self.dirty }
+    fn advance(&mut self, inp: &Planes, out: &mut Regions) -> Result<(), HipError> {
+        self.dirty = false;
+        let [w, h] = inp.size;
+        if inp.klass.len() != w * h || (!inp.conf.is_empty() && inp.conf.len() != w * h) { return Err(HipError::status(sys::INFUR_E_SHAPE)); }
+        out.size = inp.size;
+        out.labels.resize(if out.want_labels { h * w } else { 0 }, sys::INFUR_REGION_NONE);
+        out.table.resize(out.table_rows * sys::INFUR_REGION_WORDS as usize, 0);
+        let rc = unsafe {
+            sys::infur_regions(self.ctx.0, inp.klass.as_ptr(), if inp.conf.is_empty() { std::ptr::null() } else { inp.conf.as_ptr() },
+                               h as u32, w as u32, self.connectivity, self.min_pixels, self.flags,
+                               if out.want_labels { out.labels.as_mut_ptr() } else { std::ptr::null_mut() },
+                               if out.table_rows > 0 { out.table.as_mut_ptr() } else { std::ptr::null_mut() }, out.table_rows as u32, &mut out.n)
+        };
+        if rc == sys::INFUR_OK { Ok(()) } else { Err(HipError::from_ctx(&self.ctx, rc)) }
+    }
+}
+
 // ---------------------------------------------------------------- streaming ring with zero-copy slots (main.rs:27-99,105; ABI 5)
 /// The bounded queue of frames in flight (`sync_channel(2)`, main.rs:105) over `infur_stream_*`.  `next_slot` / `commit` let the
 /// decoder fill the ring's own pinned buffer in place -- what `ff-video/src/decoder.rs:156-165` does with its reused `BgrImage` --
