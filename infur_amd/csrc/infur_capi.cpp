@@ -57,6 +57,14 @@ int32_t fail(infur_ctx* c, int32_t code, const char* fmt, ...) {
 int32_t ensure(infur_ctx* c, Buf& b, size_t bytes) {
     if (b.bytes >= bytes && b.p) return INFUR_OK;
     c->mem_gen++;
+    return ensure_private(c, b, bytes);
+}
+
+// Staging only the host-pointer calls of Segments and Regions use: no captured graph can hold a pointer into it (the graphs of
+// infur_frame_advance_dev hold the caller's pointers, the arena and st_scaled), so growing it leaves mem_gen -- and with it
+// the cached graphs -- alone.  (hipFree synchronises: nothing in flight can still touch the old buffer.)
+int32_t ensure_private(infur_ctx* c, Buf& b, size_t bytes) {
+    if (b.bytes >= bytes && b.p) return INFUR_OK;
     if (b.p) HIPCHK(c, hipFree(b.p));
     b.p = nullptr;
     b.bytes = 0;
@@ -941,17 +949,71 @@ int32_t forward(infur_ctx* c, const uint8_t* d_bgr, int w, int h) {
 
 }  // namespace
 
+// ---- the front half of the fused frame calls (infur_rt.h) ----
+namespace infur {
+
+int32_t scale_dims(infur_ctx* c, uint32_t w, uint32_t h, float factor, uint32_t* ow, uint32_t* oh) {
+    int32_t rc = infur_scale_validate(factor);
+    if (rc) return fail(c, rc, "%s", infur_status_string(rc));
+    rc = infur_scale_out_dims(w, h, factor, ow, oh);
+    if (rc) return fail(c, rc, "%s", infur_status_string(rc));
+    return INFUR_OK;
+}
+
+// the Scale stage of a frame: into the caller's d_scaled, or into st_scaled when only the model needs the scaled frame
+static int32_t frame_scale(infur_ctx* c, const void* d_bgr, uint32_t w, uint32_t h, float factor, uint32_t mode, void* d_scaled, size_t sbytes,
+                           const void** frame) {
+    void* dst = d_scaled;
+    if (!dst) {
+        RETIF(ensure(c, c->st_scaled, sbytes));
+        dst = c->st_scaled.p;
+    }
+    uint32_t a, b;
+    RETIF(infur_scale_dev(c, d_bgr, w, h, factor, mode, dst, sbytes, &a, &b));
+    *frame = dst;
+    return INFUR_OK;
+}
+
+int32_t frame_check(infur_ctx* c, const void* d_bgr, uint32_t w, uint32_t h, float factor, uint32_t mode, void* d_scaled, uint32_t* ow,
+                    uint32_t* oh, size_t* npix) {
+    if (mode > INFUR_SCALE_BILINEAR) return fail(c, INFUR_E_INVALID_ARG, "unknown scale mode %u", mode);
+    RETIF(scale_dims(c, w, h, factor, ow, oh));
+    if (!d_bgr) return INFUR_E_INVALID_ARG;
+    *npix = (size_t)*ow * *oh;
+    if (*npix == 0) return fail(c, INFUR_E_SHAPE, "couldn't transform image: %ux%u", *ow, *oh);
+    if (!c->loaded) {
+        // app.rs:127-129: no model -> the mask is cleared by the caller; the Scale stage still runs
+        if (factor != 1.0f || d_scaled) {
+            const void* frame;
+            prof_reset(c);
+            RETIF(frame_scale(c, d_bgr, w, h, factor, mode, d_scaled, *npix * 3, &frame));
+        }
+        return fail(c, INFUR_E_MODEL_NOT_LOADED, "no model loaded");
+    }
+    return INFUR_OK;
+}
+
+int32_t scale_forward(infur_ctx* c, const void* d_bgr, uint32_t w, uint32_t h, float factor, uint32_t mode, void* d_scaled, uint32_t ow,
+                      uint32_t oh) {
+    const void* frame = d_bgr;
+    prof_reset(c);
+    std::vector<ProfRec> pre;
+    if (factor != 1.0f || d_scaled) {
+        RETIF(frame_scale(c, d_bgr, w, h, factor, mode, d_scaled, (size_t)ow * oh * 3, &frame));
+        pre.swap(c->prof);  // forward() resets the records; keep the scale's
+    }
+    RETIF(forward(c, (const uint8_t*)frame, (int)ow, (int)oh));
+    c->prof.insert(c->prof.begin(), pre.begin(), pre.end());
+    return INFUR_OK;
+}
+
+}  // namespace infur
+
 // =====================================================================================
 // C ABI
 // =====================================================================================
-// Every entry point runs on its context's device: a process may hold contexts on several GPUs, and
-// hipMalloc / kernel launches follow the calling thread's current device, not the stream's.
+// Every entry point runs on its context's device (enter, infur_ctx.h) and lets no exception out (abi_call, infur_rt.h).
 // (infur::stream_orphan -- infur_stream.cpp -- releases a stream's resources and detaches it from its context)
-
-static inline void enter(const infur_ctx* c) {
-    int cur = -1;
-    if (c && (hipGetDevice(&cur) != hipSuccess || cur != c->device)) (void)hipSetDevice(c->device);
-}
 
 extern "C" {
 
@@ -1065,7 +1127,7 @@ static bool pool_stream_reserve(const infur_ctx* c, bool on) {
 }
 
 int32_t infur_ctx_create(const infur_options* opts, infur_ctx** out) {
-    try {
+    return abi_call(nullptr, [&]() -> int32_t {
         if (!out) return INFUR_E_INVALID_ARG;
         *out = nullptr;
         infur_options o;
@@ -1124,11 +1186,7 @@ int32_t infur_ctx_create(const infur_options* opts, infur_ctx** out) {
         guard.c = nullptr;
         *out = c;
         return INFUR_OK;
-    } catch (const std::bad_alloc&) {
-        return fail(nullptr, INFUR_E_CAPACITY, "out of host memory");
-    } catch (const std::exception& e) {
-        return fail(nullptr, INFUR_E_INVALID_ARG, "internal error: %s", e.what());
-    }
+    });
 }
 
 static void graphs_drop(infur_ctx* c);
@@ -1166,10 +1224,11 @@ void infur_ctx_destroy(infur_ctx* c) {
 const char* infur_last_error(const infur_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
 int32_t infur_ctx_synchronize(infur_ctx* c) {
-    enter(c);
-    if (!c) return INFUR_E_INVALID_ARG;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return INFUR_OK;
+    return abi_call(c, [&]() -> int32_t {
+        if (!c) return INFUR_E_INVALID_ARG;
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return INFUR_OK;
+    });
 }
 
 void* infur_ctx_stream(infur_ctx* c) { return c ? (void*)c->stream : nullptr; }
@@ -1197,14 +1256,10 @@ int32_t infur_scale_out_dims(uint32_t w, uint32_t h, float factor, uint32_t* ow,
 
 int32_t infur_scale_dev(infur_ctx* c, const void* d_bgr, uint32_t w, uint32_t h, float factor, uint32_t mode,
                         void* d_out, size_t cap, uint32_t* ow, uint32_t* oh) {
-    try {
-        enter(c);
+    return abi_call(c, [&]() -> int32_t {
         if (!c || !ow || !oh) return INFUR_E_INVALID_ARG;
         if (mode > INFUR_SCALE_BILINEAR) return fail(c, INFUR_E_INVALID_ARG, "unknown scale mode %u", mode);
-        int32_t rc = infur_scale_validate(factor);
-        if (rc) return fail(c, rc, "%s", infur_status_string(rc));
-        rc = infur_scale_out_dims(w, h, factor, ow, oh);
-        if (rc) return fail(c, rc, "%s", infur_status_string(rc));
+        RETIF(scale_dims(c, w, h, factor, ow, oh));
         const size_t need = (size_t)*ow * *oh * 3;
         if (need == 0) return INFUR_OK;
         if (!d_bgr || !d_out) return INFUR_E_INVALID_ARG;
@@ -1216,22 +1271,14 @@ int32_t infur_scale_dev(infur_ctx* c, const void* d_bgr, uint32_t w, uint32_t h,
             HIPCHK(c, launch_scale_bgr((const uint8_t*)d_bgr, (int)w, (int)h, (uint8_t*)d_out, (int)*ow, (int)*oh, (int)mode, c->stream));
         }
         return INFUR_OK;
-    } catch (const std::bad_alloc&) {
-        return fail(c, INFUR_E_CAPACITY, "out of host memory");
-    } catch (const std::exception& e) {
-        return fail(c, INFUR_E_INVALID_ARG, "internal error: %s", e.what());
-    }
+    });
 }
 
 int32_t infur_scale(infur_ctx* c, const uint8_t* bgr, uint32_t w, uint32_t h, float factor, uint32_t mode,
                     uint8_t* out, size_t cap, uint32_t* ow, uint32_t* oh) {
-    try {
-        enter(c);
+    return abi_call(c, [&]() -> int32_t {
         if (!c || !ow || !oh) return INFUR_E_INVALID_ARG;
-        int32_t rc = infur_scale_validate(factor);
-        if (rc) return fail(c, rc, "%s", infur_status_string(rc));
-        rc = infur_scale_out_dims(w, h, factor, ow, oh);
-        if (rc) return fail(c, rc, "%s", infur_status_string(rc));
+        RETIF(scale_dims(c, w, h, factor, ow, oh));
         const size_t in_bytes = (size_t)w * h * 3, need = (size_t)*ow * *oh * 3;
         if (need == 0) return INFUR_OK;
         if (!bgr || !out) return INFUR_E_INVALID_ARG;
@@ -1243,25 +1290,21 @@ int32_t infur_scale(infur_ctx* c, const uint8_t* bgr, uint32_t w, uint32_t h, fl
         HIPCHK(c, hipMemcpyAsync(out, c->st_scaled.p, need, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         return INFUR_OK;
-    } catch (const std::bad_alloc&) {
-        return fail(c, INFUR_E_CAPACITY, "out of host memory");
-    } catch (const std::exception& e) {
-        return fail(c, INFUR_E_INVALID_ARG, "internal error: %s", e.what());
-    }
+    });
 }
 
 // ---- Model ----
 int32_t infur_model_unload(infur_ctx* c) {
-    enter(c);
-    if (!c) return INFUR_E_INVALID_ARG;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    model_free(c);
-    return INFUR_OK;
+    return abi_call(c, [&]() -> int32_t {
+        if (!c) return INFUR_E_INVALID_ARG;
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        model_free(c);
+        return INFUR_OK;
+    });
 }
 
 int32_t infur_model_load_blob_dev(infur_ctx* c, const void* d_blob, size_t len) {
-    try {
-        enter(c);
+    return abi_call(c, [&]() -> int32_t {
         if (!c || !d_blob) return INFUR_E_INVALID_ARG;
         char magic[8] = {0};
         if (len >= 8) {
@@ -1270,16 +1313,11 @@ int32_t infur_model_load_blob_dev(infur_ctx* c, const void* d_blob, size_t len) 
         }
         if (memcmp(magic, "INFURQ01", 8) == 0) return model_load_q_dev(c, d_blob, len);
         return model_load_dev(c, d_blob, len);
-    } catch (const std::bad_alloc&) {
-        return fail(c, INFUR_E_CAPACITY, "out of host memory");
-    } catch (const std::exception& e) {
-        return fail(c, INFUR_E_INVALID_ARG, "internal error: %s", e.what());
-    }
+    });
 }
 
 int32_t infur_model_load_blob(infur_ctx* c, const void* blob, size_t len) {
-    try {
-        enter(c);
+    return abi_call(c, [&]() -> int32_t {
         if (!c || !blob) return INFUR_E_INVALID_ARG;
         const bool quant = len >= kBlobHdr && memcmp(blob, "INFURQ01", 8) == 0;
         if (len < kBlobHdr || (!quant && memcmp(blob, "INFURW01", 8) != 0))
@@ -1292,16 +1330,11 @@ int32_t infur_model_load_blob(infur_ctx* c, const void* blob, size_t len) {
         (void)hipStreamSynchronize(c->stream);
         (void)hipFree(d);
         return rc;
-    } catch (const std::bad_alloc&) {
-        return fail(c, INFUR_E_CAPACITY, "out of host memory");
-    } catch (const std::exception& e) {
-        return fail(c, INFUR_E_INVALID_ARG, "internal error: %s", e.what());
-    }
+    });
 }
 
 int32_t infur_model_load(infur_ctx* c, const char* path) {
-    try {
-        enter(c);
+    return abi_call(c, [&]() -> int32_t {
         if (!c || !path) return INFUR_E_INVALID_ARG;
         if (path[0] == 0) return infur_model_unload(c);  // ModelCmd::Load("") unloads, predict_onnx.rs:310-312
         FILE* f = fopen(path, "rb");
@@ -1331,15 +1364,11 @@ int32_t infur_model_load(infur_ctx* c, const char* path) {
             return rc;
         }
         return fail(c, INFUR_E_MODEL_FORMAT, "'%s' is neither an INFURW01 blob nor an ONNX model", path);
-    } catch (const std::bad_alloc&) {
-        return fail(c, INFUR_E_CAPACITY, "out of host memory");
-    } catch (const std::exception& e) {
-        return fail(c, INFUR_E_INVALID_ARG, "internal error: %s", e.what());
-    }
+    });
 }
 
 int32_t infur_onnx_to_blob(const void* onnx, size_t len, void** blob, size_t* blob_len, char* err, size_t errcap) {
-    try {
+    return abi_call(nullptr, [&]() -> int32_t {
         if (!onnx || !blob || !blob_len) return INFUR_E_INVALID_ARG;
         *blob = nullptr;
         *blob_len = 0;
@@ -1356,11 +1385,7 @@ int32_t infur_onnx_to_blob(const void* onnx, size_t len, void** blob, size_t* bl
         *blob = p;
         *blob_len = out.size();
         return INFUR_OK;
-    } catch (const std::bad_alloc&) {
-        return fail(nullptr, INFUR_E_CAPACITY, "out of host memory");
-    } catch (const std::exception& e) {
-        return fail(nullptr, INFUR_E_INVALID_ARG, "internal error: %s", e.what());
-    }
+    });
 }
 
 void infur_buffer_free(void* p) { free(p); }
@@ -1388,8 +1413,7 @@ int32_t infur_model_lowres_dims(uint32_t h, uint32_t w, uint32_t* lh, uint32_t* 
 
 int32_t infur_model_advance_dev(infur_ctx* c, const void* d_bgr, uint32_t w, uint32_t h, void* d_out, void* d_aux,
                                 uint32_t* n_outputs) {
-    try {
-        enter(c);
+    return abi_call(c, [&]() -> int32_t {
         if (!c) return INFUR_E_INVALID_ARG;
         if (n_outputs) *n_outputs = 0;
         if (!c->loaded) return INFUR_OK;  // no session: out untouched, Ok(()) (predict_onnx.rs:318,333)
@@ -1411,17 +1435,12 @@ int32_t infur_model_advance_dev(infur_ctx* c, const void* d_bgr, uint32_t w, uin
         }
         if (n_outputs) *n_outputs = c->info.n_outputs;
         return INFUR_OK;
-    } catch (const std::bad_alloc&) {
-        return fail(c, INFUR_E_CAPACITY, "out of host memory");
-    } catch (const std::exception& e) {
-        return fail(c, INFUR_E_INVALID_ARG, "internal error: %s", e.what());
-    }
+    });
 }
 
 int32_t infur_model_advance(infur_ctx* c, const uint8_t* bgr, uint32_t w, uint32_t h, float* out, float* aux,
                             uint32_t* n_outputs) {
-    try {
-        enter(c);
+    return abi_call(c, [&]() -> int32_t {
         if (!c) return INFUR_E_INVALID_ARG;
         if (n_outputs) *n_outputs = 0;
         if (!c->loaded) return INFUR_OK;
@@ -1439,16 +1458,11 @@ int32_t infur_model_advance(infur_ctx* c, const uint8_t* bgr, uint32_t w, uint32
         if (aux) HIPCHK(c, hipMemcpyAsync(aux, c->st_f32b.p, lg, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         return INFUR_OK;
-    } catch (const std::bad_alloc&) {
-        return fail(c, INFUR_E_CAPACITY, "out of host memory");
-    } catch (const std::exception& e) {
-        return fail(c, INFUR_E_INVALID_ARG, "internal error: %s", e.what());
-    }
+    });
 }
 
 int32_t infur_model_warmup(infur_ctx* c, uint32_t w, uint32_t h) {
-    try {
-        enter(c);
+    return abi_call(c, [&]() -> int32_t {
         if (!c) return INFUR_E_INVALID_ARG;
         if (!c->loaded) return fail(c, INFUR_E_MODEL_NOT_LOADED, "no model loaded");
         if (w == 0 || h == 0) return fail(c, INFUR_E_SHAPE, "couldn't transform image: %ux%u", w, h);
@@ -1462,16 +1476,11 @@ int32_t infur_model_warmup(infur_ctx* c, uint32_t w, uint32_t h) {
         RETIF(rc);
         HIPCHK(c, hipStreamSynchronize(c->stream));
         return INFUR_OK;
-    } catch (const std::bad_alloc&) {
-        return fail(c, INFUR_E_CAPACITY, "out of host memory");
-    } catch (const std::exception& e) {
-        return fail(c, INFUR_E_INVALID_ARG, "internal error: %s", e.what());
-    }
+    });
 }
 
 int32_t infur_model_read_lowres(infur_ctx* c, float* out_low, float* aux_low, uint32_t* lh, uint32_t* lw) {
-    try {
-        enter(c);
+    return abi_call(c, [&]() -> int32_t {
         if (!c) return INFUR_E_INVALID_ARG;
         if (!c->loaded || !c->out_low.p) return fail(c, INFUR_E_MODEL_NOT_LOADED, "no forward pass has run");
         if (aux_low && !c->aux_low.p) return fail(c, INFUR_E_INVALID_ARG, "aux output requested but the aux head is disabled");
@@ -1496,17 +1505,12 @@ int32_t infur_model_read_lowres(infur_ctx* c, float* out_low, float* aux_low, ui
             }
         }
         return INFUR_OK;
-    } catch (const std::bad_alloc&) {
-        return fail(c, INFUR_E_CAPACITY, "out of host memory");
-    } catch (const std::exception& e) {
-        return fail(c, INFUR_E_INVALID_ARG, "internal error: %s", e.what());
-    }
+    });
 }
 
 int32_t infur_debug_read_activation(infur_ctx* c, uint32_t index, float* host, size_t cap, uint32_t* ch, uint32_t* h,
                                     uint32_t* w) {
-    try {
-        enter(c);
+    return abi_call(c, [&]() -> int32_t {
         if (!c || !host) return INFUR_E_INVALID_ARG;
         if (!c->opt.keep_activations) return fail(c, INFUR_E_INVALID_ARG, "context was created without keep_activations");
         if (index >= c->kept.size()) return fail(c, INFUR_E_INVALID_ARG, "activation %u of %zu", index, c->kept.size());
@@ -1525,27 +1529,23 @@ int32_t infur_debug_read_activation(infur_ctx* c, uint32_t index, float* host, s
         HIPCHK(c, hipMemcpyAsync(host, c->st_f32a.p, t.elems() * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         return INFUR_OK;
-    } catch (const std::bad_alloc&) {
-        return fail(c, INFUR_E_CAPACITY, "out of host memory");
-    } catch (const std::exception& e) {
-        return fail(c, INFUR_E_INVALID_ARG, "internal error: %s", e.what());
-    }
+    });
 }
 
 // ---- pre-proc alone ----
 int32_t infur_pack_normalize_dev(infur_ctx* c, const void* d_bgr, uint32_t w, uint32_t h, void* d_chw) {
-    enter(c);
-    if (!c) return INFUR_E_INVALID_ARG;
-    if ((size_t)w * h == 0) return INFUR_OK;
-    if (!d_bgr || !d_chw) return INFUR_E_INVALID_ARG;
-    ProfScope ps(c, "pre-proc", "pack_normalize", 0, (double)w * h * 15.0);
-    HIPCHK(c, launch_pack_normalize((const uint8_t*)d_bgr, (int)w, (int)h, c->d_pre_lut, (float*)d_chw, c->stream));
-    return INFUR_OK;
+    return abi_call(c, [&]() -> int32_t {
+        if (!c) return INFUR_E_INVALID_ARG;
+        if ((size_t)w * h == 0) return INFUR_OK;
+        if (!d_bgr || !d_chw) return INFUR_E_INVALID_ARG;
+        ProfScope ps(c, "pre-proc", "pack_normalize", 0, (double)w * h * 15.0);
+        HIPCHK(c, launch_pack_normalize((const uint8_t*)d_bgr, (int)w, (int)h, c->d_pre_lut, (float*)d_chw, c->stream));
+        return INFUR_OK;
+    });
 }
 
 int32_t infur_pack_normalize(infur_ctx* c, const uint8_t* bgr, uint32_t w, uint32_t h, float* chw) {
-    try {
-        enter(c);
+    return abi_call(c, [&]() -> int32_t {
         if (!c) return INFUR_E_INVALID_ARG;
         const size_t npix = (size_t)w * h;
         if (npix == 0) return INFUR_OK;
@@ -1557,27 +1557,23 @@ int32_t infur_pack_normalize(infur_ctx* c, const uint8_t* bgr, uint32_t w, uint3
         HIPCHK(c, hipMemcpyAsync(chw, c->st_f32a.p, npix * 12, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         return INFUR_OK;
-    } catch (const std::bad_alloc&) {
-        return fail(c, INFUR_E_CAPACITY, "out of host memory");
-    } catch (const std::exception& e) {
-        return fail(c, INFUR_E_INVALID_ARG, "internal error: %s", e.what());
-    }
+    });
 }
 
 // ---- ColorCode ----
 int32_t infur_colorcode_dev(infur_ctx* c, const void* d_khw, uint32_t k, uint32_t h, uint32_t w, void* d_rgba) {
-    enter(c);
-    if (!c) return INFUR_E_INVALID_ARG;
-    if ((size_t)h * w == 0) return INFUR_OK;  // empty image: nothing to write (decode_predict.rs:68 zips 0 pixels)
-    if (!d_rgba || (k > 0 && !d_khw)) return INFUR_E_INVALID_ARG;
-    ProfScope ps(c, "colorcode", "colorcode_planar", 0, (double)h * w * (4.0 * k + 4.0));
-    HIPCHK(c, launch_colorcode_planar((const float*)d_khw, (int)k, (int)h, (int)w, c->d_color_lut, (uint32_t*)d_rgba, c->stream));
-    return INFUR_OK;
+    return abi_call(c, [&]() -> int32_t {
+        if (!c) return INFUR_E_INVALID_ARG;
+        if ((size_t)h * w == 0) return INFUR_OK;  // empty image: nothing to write (decode_predict.rs:68 zips 0 pixels)
+        if (!d_rgba || (k > 0 && !d_khw)) return INFUR_E_INVALID_ARG;
+        ProfScope ps(c, "colorcode", "colorcode_planar", 0, (double)h * w * (4.0 * k + 4.0));
+        HIPCHK(c, launch_colorcode_planar((const float*)d_khw, (int)k, (int)h, (int)w, c->d_color_lut, (uint32_t*)d_rgba, c->stream));
+        return INFUR_OK;
+    });
 }
 
 int32_t infur_colorcode(infur_ctx* c, const float* khw, uint32_t k, uint32_t h, uint32_t w, uint8_t* rgba) {
-    try {
-        enter(c);
+    return abi_call(c, [&]() -> int32_t {
         if (!c) return INFUR_E_INVALID_ARG;
         const size_t hw = (size_t)h * w;
         if (hw == 0) return INFUR_OK;
@@ -1589,27 +1585,23 @@ int32_t infur_colorcode(infur_ctx* c, const float* khw, uint32_t k, uint32_t h, 
         HIPCHK(c, hipMemcpyAsync(rgba, c->st_rgba.p, hw * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         return INFUR_OK;
-    } catch (const std::bad_alloc&) {
-        return fail(c, INFUR_E_CAPACITY, "out of host memory");
-    } catch (const std::exception& e) {
-        return fail(c, INFUR_E_INVALID_ARG, "internal error: %s", e.what());
-    }
+    });
 }
 
 // ---- display conversion ----
 int32_t infur_bgr_to_rgba_dev(infur_ctx* c, const void* d_bgr, uint32_t w, uint32_t h, void* d_rgba) {
-    enter(c);
-    if (!c) return INFUR_E_INVALID_ARG;
-    if ((size_t)w * h == 0) return INFUR_OK;
-    if (!d_bgr || !d_rgba) return INFUR_E_INVALID_ARG;
-    ProfScope ps(c, "display", "bgr_to_rgba", 0, (double)w * h * 7.0);
-    HIPCHK(c, launch_bgr_to_rgba((const uint8_t*)d_bgr, (int)w, (int)h, (uint32_t*)d_rgba, c->stream));
-    return INFUR_OK;
+    return abi_call(c, [&]() -> int32_t {
+        if (!c) return INFUR_E_INVALID_ARG;
+        if ((size_t)w * h == 0) return INFUR_OK;
+        if (!d_bgr || !d_rgba) return INFUR_E_INVALID_ARG;
+        ProfScope ps(c, "display", "bgr_to_rgba", 0, (double)w * h * 7.0);
+        HIPCHK(c, launch_bgr_to_rgba((const uint8_t*)d_bgr, (int)w, (int)h, (uint32_t*)d_rgba, c->stream));
+        return INFUR_OK;
+    });
 }
 
 int32_t infur_bgr_to_rgba(infur_ctx* c, const uint8_t* bgr, uint32_t w, uint32_t h, uint8_t* rgba) {
-    try {
-        enter(c);
+    return abi_call(c, [&]() -> int32_t {
         if (!c) return INFUR_E_INVALID_ARG;
         const size_t npix = (size_t)w * h;
         if (npix == 0) return INFUR_OK;
@@ -1621,41 +1613,19 @@ int32_t infur_bgr_to_rgba(infur_ctx* c, const uint8_t* bgr, uint32_t w, uint32_t
         HIPCHK(c, hipMemcpyAsync(rgba, c->st_rgba.p, npix * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         return INFUR_OK;
-    } catch (const std::bad_alloc&) {
-        return fail(c, INFUR_E_CAPACITY, "out of host memory");
-    } catch (const std::exception& e) {
-        return fail(c, INFUR_E_INVALID_ARG, "internal error: %s", e.what());
-    }
+    });
 }
 
 // ---- fused frame path ----
 // the fused frame path: Scale -> forward -> up-sample + argmax + shade, everything enqueued on c->stream (arguments validated by
-// the caller; *ow x *oh are the scaled dimensions)
+// the caller; ow x oh are the scaled dimensions)
 static int32_t frame_body(infur_ctx* c, const void* d_bgr, uint32_t w, uint32_t h, float factor, uint32_t mode, void* d_rgba, void* d_scaled,
                           uint32_t ow, uint32_t oh) {
-    const size_t sbytes = (size_t)ow * oh * 3, need = (size_t)ow * oh * 4;
-    const void* frame = d_bgr;
     RoctxRange rr("infur frame");
-    prof_reset(c);
-    std::vector<ProfRec> pre;
-    if (factor != 1.0f || d_scaled) {
-        void* dst = d_scaled;
-        if (!dst) {
-            RETIF(ensure(c, c->st_scaled, sbytes));
-            dst = c->st_scaled.p;
-        }
-        uint32_t a, b;
-        RETIF(infur_scale_dev(c, d_bgr, w, h, factor, mode, dst, sbytes, &a, &b));
-        frame = dst;
-        pre.swap(c->prof);  // forward() resets the records; keep the scale's
-    }
-    RETIF(forward(c, (const uint8_t*)frame, (int)ow, (int)oh));
-    c->prof.insert(c->prof.begin(), pre.begin(), pre.end());
-    {
-        const Tensor& t = c->out_low;  // only out[0] is decoded, app.rs:116
-        ProfScope ps(c, "out.resize+colorcode", "upsample_argmax_shade", 0, (double)t.bytes() + (double)need);
-        HIPCHK(c, launch_upsample_argmax_shade((const float*)t.p, t.h, t.w, t.c, c->d_color_lut, (uint32_t*)d_rgba, (int)oh, (int)ow, c->stream, head_quant(c, 0)));
-    }
+    RETIF(scale_forward(c, d_bgr, w, h, factor, mode, d_scaled, ow, oh));
+    const Tensor& t = c->out_low;  // only out[0] is decoded, app.rs:116
+    ProfScope ps(c, "out.resize+colorcode", "upsample_argmax_shade", 0, (double)t.bytes() + (double)ow * oh * 4);
+    HIPCHK(c, launch_upsample_argmax_shade((const float*)t.p, t.h, t.w, t.c, c->d_color_lut, (uint32_t*)d_rgba, (int)oh, (int)ow, c->stream, head_quant(c, 0)));
     return INFUR_OK;
 }
 
@@ -1679,33 +1649,12 @@ static void graphs_drop(infur_ctx* c) {
 
 int32_t infur_frame_advance_dev(infur_ctx* c, const void* d_bgr, uint32_t w, uint32_t h, float factor, uint32_t mode,
                                 void* d_rgba, size_t cap, void* d_scaled, uint32_t* ow, uint32_t* oh) {
-    try {
-        enter(c);
+    return abi_call(c, [&]() -> int32_t {
         if (!c || !ow || !oh) return INFUR_E_INVALID_ARG;
-        if (mode > INFUR_SCALE_BILINEAR) return fail(c, INFUR_E_INVALID_ARG, "unknown scale mode %u", mode);
-        int32_t rc = infur_scale_validate(factor);
-        if (rc) return fail(c, rc, "%s", infur_status_string(rc));
-        rc = infur_scale_out_dims(w, h, factor, ow, oh);
-        if (rc) return fail(c, rc, "%s", infur_status_string(rc));
-        if (!d_bgr) return INFUR_E_INVALID_ARG;
-        const size_t sbytes = (size_t)*ow * *oh * 3, need = (size_t)*ow * *oh * 4;
-        if (need == 0) return fail(c, INFUR_E_SHAPE, "couldn't transform image: %ux%u", *ow, *oh);
-        if (!c->loaded) {
-            // app.rs:127-129: no model -> the mask is cleared by the caller; the Scale stage still runs
-            if (factor != 1.0f || d_scaled) {
-                void* dst = d_scaled;
-                if (!dst) {
-                    RETIF(ensure(c, c->st_scaled, sbytes));
-                    dst = c->st_scaled.p;
-                }
-                uint32_t a, b;
-                prof_reset(c);
-                RETIF(infur_scale_dev(c, d_bgr, w, h, factor, mode, dst, sbytes, &a, &b));
-            }
-            return fail(c, INFUR_E_MODEL_NOT_LOADED, "no model loaded");
-        }
+        size_t npix;
+        RETIF(frame_check(c, d_bgr, w, h, factor, mode, d_scaled, ow, oh, &npix));
         if (!d_rgba) return INFUR_E_INVALID_ARG;
-        if (cap < need) return fail(c, INFUR_E_CAPACITY, "mask needs %zu bytes, buffer has %zu", need, cap);
+        if (cap < npix * 4) return fail(c, INFUR_E_CAPACITY, "mask needs %zu bytes, buffer has %zu", npix * 4, cap);
 
         const bool graphs_on = c->graph_replay && !c->opt.profile && !c->opt.keep_activations;
         if (!graphs_on) return frame_body(c, d_bgr, w, h, factor, mode, d_rgba, d_scaled, *ow, *oh);
@@ -1728,7 +1677,7 @@ int32_t infur_frame_advance_dev(infur_ctx* c, const void* d_bgr, uint32_t w, uin
             c->graph_streak = 0;
         c->streak_w = w; c->streak_h = h; c->streak_mode = mode; c->streak_factor = fbits;
         if (c->graph_streak < kGraphSettle) {
-            rc = frame_body(c, d_bgr, w, h, factor, mode, d_rgba, d_scaled, *ow, *oh);
+            const int32_t rc = frame_body(c, d_bgr, w, h, factor, mode, d_rgba, d_scaled, *ow, *oh);
             c->streak_gen = c->mem_gen;  // (a frame that allocated, trimmed or tuned restarts the count)
             return rc;
         }
@@ -1743,7 +1692,7 @@ int32_t infur_frame_advance_dev(infur_ctx* c, const void* d_bgr, uint32_t w, uin
             c->graph_replay = false;  // (a stream that cannot capture: stay eager)
             return frame_body(c, d_bgr, w, h, factor, mode, d_rgba, d_scaled, *ow, *oh);
         }
-        rc = frame_body(c, d_bgr, w, h, factor, mode, d_rgba, d_scaled, *ow, *oh);
+        const int32_t rc = frame_body(c, d_bgr, w, h, factor, mode, d_rgba, d_scaled, *ow, *oh);
         hipGraph_t graph = nullptr;
         const hipError_t ee = hipStreamEndCapture(c->stream, &graph);
         hipGraphExec_t exec = nullptr;
@@ -1770,33 +1719,30 @@ int32_t infur_frame_advance_dev(infur_ctx* c, const void* d_bgr, uint32_t w, uin
         (void)hipGetLastError();
         c->graph_replay = false;
         return frame_body(c, d_bgr, w, h, factor, mode, d_rgba, d_scaled, *ow, *oh);
-    } catch (const std::bad_alloc&) {
-        return fail(c, INFUR_E_CAPACITY, "out of host memory");
-    } catch (const std::exception& e) {
-        return fail(c, INFUR_E_INVALID_ARG, "internal error: %s", e.what());
-    }
+    });
 }
 
 int32_t infur_ctx_set_graph_replay(infur_ctx* c, uint32_t enable) {
-    enter(c);
-    if (!c) return INFUR_E_INVALID_ARG;
-    c->graph_replay = enable != 0;
-    if (!enable) {
-        (void)hipSetDevice(c->device);
-        if (c->stream) (void)hipStreamSynchronize(c->stream);
-        graphs_drop(c);
-        (void)pool_stream_reserve(c, false);
-    } else {
-        // The context's stream NEVER changes behind infur_ctx_stream() (a host that had read the handle kept enqueueing
-        // producers of d_bgr on the old stream).  Pool streams are shared from the ninth context of a device on, and a kernel another
-        // context's thread enqueues between BeginCapture and EndCapture would be recorded into this context's graph, not executed
-        // (ThreadLocal capture mode only restricts the capturing thread) -- so the slot is RESERVED instead: while this context is
-        // its only user, pool_stream hands it to nobody else.  A slot that is already shared stays shared and simply never captures
-        // (frame_advance_dev runs eagerly: the reservation at capture time fails).
-        (void)pool_stream_reserve(c, true);
-    }
-    c->graph_streak = 0;
-    return INFUR_OK;
+    return abi_call(c, [&]() -> int32_t {
+        if (!c) return INFUR_E_INVALID_ARG;
+        c->graph_replay = enable != 0;
+        if (!enable) {
+            (void)hipSetDevice(c->device);
+            if (c->stream) (void)hipStreamSynchronize(c->stream);
+            graphs_drop(c);
+            (void)pool_stream_reserve(c, false);
+        } else {
+            // The context's stream NEVER changes behind infur_ctx_stream() (a host that had read the handle kept enqueueing
+            // producers of d_bgr on the old stream).  Pool streams are shared from the ninth context of a device on, and a kernel another
+            // context's thread enqueues between BeginCapture and EndCapture would be recorded into this context's graph, not executed
+            // (ThreadLocal capture mode only restricts the capturing thread) -- so the slot is RESERVED instead: while this context is
+            // its only user, pool_stream hands it to nobody else.  A slot that is already shared stays shared and simply never captures
+            // (frame_advance_dev runs eagerly: the reservation at capture time fails).
+            (void)pool_stream_reserve(c, true);
+        }
+        c->graph_streak = 0;
+        return INFUR_OK;
+    });
 }
 
 int32_t infur_ctx_graph_stats(const infur_ctx* c, uint64_t* captures, uint64_t* replays, uint32_t* cached) {
@@ -1810,96 +1756,89 @@ int32_t infur_ctx_graph_stats(const infur_ctx* c, uint64_t* captures, uint64_t* 
 
 int32_t infur_frame_advance(infur_ctx* c, const uint8_t* bgr, uint32_t w, uint32_t h, float factor, uint32_t mode,
                             uint8_t* rgba, size_t cap, uint8_t* scaled, uint32_t* ow, uint32_t* oh) {
-    try {
-        enter(c);
+    return abi_call(c, [&]() -> int32_t {
         if (!c || !ow || !oh) return INFUR_E_INVALID_ARG;
-        int32_t rc = infur_scale_validate(factor);
-        if (rc) return fail(c, rc, "%s", infur_status_string(rc));
-        rc = infur_scale_out_dims(w, h, factor, ow, oh);
-        if (rc) return fail(c, rc, "%s", infur_status_string(rc));
-        if (!bgr) return INFUR_E_INVALID_ARG;
-        const size_t in_bytes = (size_t)w * h * 3, sbytes = (size_t)*ow * *oh * 3, need = (size_t)*ow * *oh * 4;
-        if (rgba && cap < need) return fail(c, INFUR_E_CAPACITY, "mask needs %zu bytes, buffer has %zu", need, cap);
-        RETIF(ensure(c, c->st_in, in_bytes ? in_bytes : 1));
-        RETIF(ensure(c, c->st_rgba, need ? need : 1));
-        RETIF(ensure(c, c->st_scaled, sbytes ? sbytes : 1));
-        HIPCHK(c, hipMemcpyAsync(c->st_in.p, bgr, in_bytes, hipMemcpyHostToDevice, c->stream));
-        rc = infur_frame_advance_dev(c, c->st_in.p, w, h, factor, mode, c->st_rgba.p, c->st_rgba.bytes,
-                                     (scaled || factor != 1.0f) ? c->st_scaled.p : nullptr, ow, oh);
-        if (rc != INFUR_OK && rc != INFUR_E_MODEL_NOT_LOADED) return rc;
-        if (scaled) HIPCHK(c, hipMemcpyAsync(scaled, c->st_scaled.p, sbytes, hipMemcpyDeviceToHost, c->stream));
-        if (rc == INFUR_OK && rgba) HIPCHK(c, hipMemcpyAsync(rgba, c->st_rgba.p, need, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        return rc;
-    } catch (const std::bad_alloc&) {
-        return fail(c, INFUR_E_CAPACITY, "out of host memory");
-    } catch (const std::exception& e) {
-        return fail(c, INFUR_E_INVALID_ARG, "internal error: %s", e.what());
-    }
+        return frame_host(
+            c, bgr, w, h, factor, scaled, ow, oh,
+            [&](size_t npix) -> int32_t {
+                if (rgba && cap < npix * 4) return fail(c, INFUR_E_CAPACITY, "mask needs %zu bytes, buffer has %zu", npix * 4, cap);
+                return ensure(c, c->st_rgba, npix ? npix * 4 : 1);
+            },
+            [&](void* d_bgr, void* d_scaled) {
+                return infur_frame_advance_dev(c, d_bgr, w, h, factor, mode, c->st_rgba.p, c->st_rgba.bytes, d_scaled, ow, oh);
+            },
+            [&](size_t npix) -> int32_t {
+                if (rgba) HIPCHK(c, hipMemcpyAsync(rgba, c->st_rgba.p, npix * 4, hipMemcpyDeviceToHost, c->stream));
+                return INFUR_OK;
+            });
+    });
 }
 
 // ---- streaming ring, frame batch, pinned host buffers: infur_stream.cpp ----
 
 // ---- range monitor of the split mode ----
 int32_t infur_split_range(infur_ctx* c, float* act_amax, float* wino_amax, uint32_t* saturated) {
-    enter(c);
-    if (!c) return INFUR_E_INVALID_ARG;
-    if (!c->d_range) return fail(c, INFUR_E_INVALID_ARG, "context is not in INFUR_DTYPE_F32_SPLIT mode");
-    float v[2] = {0.f, 0.f};
-    HIPCHK(c, hipMemcpyAsync(v, c->d_range, sizeof v, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (act_amax) *act_amax = v[0];
-    if (wino_amax) *wino_amax = v[1];
-    // beyond 65504 the hi half clamps (MODE.FP16_OVFL) and the pair stops being exact
-    const float ws = split_wino_scale(wino_mt(c));
-    if (saturated) *saturated = (v[0] * kSplitActScale > 65504.0f || v[1] * ws > 65504.0f) ? 1u : 0u;
-    return INFUR_OK;
+    return abi_call(c, [&]() -> int32_t {
+        if (!c) return INFUR_E_INVALID_ARG;
+        if (!c->d_range) return fail(c, INFUR_E_INVALID_ARG, "context is not in INFUR_DTYPE_F32_SPLIT mode");
+        float v[2] = {0.f, 0.f};
+        HIPCHK(c, hipMemcpyAsync(v, c->d_range, sizeof v, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (act_amax) *act_amax = v[0];
+        if (wino_amax) *wino_amax = v[1];
+        // beyond 65504 the hi half clamps (MODE.FP16_OVFL) and the pair stops being exact
+        const float ws = split_wino_scale(wino_mt(c));
+        if (saturated) *saturated = (v[0] * kSplitActScale > 65504.0f || v[1] * ws > 65504.0f) ? 1u : 0u;
+        return INFUR_OK;
+    });
 }
 
 // ---- range monitor of the three-byte mode (opt-in: hl_format.h, kHlMon*) ----
 int32_t infur_hl_monitor_enable(infur_ctx* c, uint32_t on) {
-    enter(c);
-    if (!c) return INFUR_E_INVALID_ARG;
-    if (c->opt.compute_dtype != INFUR_DTYPE_F16_HL) return fail(c, INFUR_E_INVALID_ARG, "the range monitor is a mode of INFUR_DTYPE_F16_HL contexts");
-    if (on && !c->d_hlmon) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        unsigned* p = nullptr;
-        HIPCHK(c, hipMalloc((void**)&p, kHlMonWords * sizeof(unsigned)));
-        if (hipMemset(p, 0, kHlMonWords * sizeof(unsigned)) != hipSuccess) {
-            (void)hipFree(p);
-            return fail(c, INFUR_E_HIP, "hipMemset of the range monitor failed");
+    return abi_call(c, [&]() -> int32_t {
+        if (!c) return INFUR_E_INVALID_ARG;
+        if (c->opt.compute_dtype != INFUR_DTYPE_F16_HL) return fail(c, INFUR_E_INVALID_ARG, "the range monitor is a mode of INFUR_DTYPE_F16_HL contexts");
+        if (on && !c->d_hlmon) {
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            unsigned* p = nullptr;
+            HIPCHK(c, hipMalloc((void**)&p, kHlMonWords * sizeof(unsigned)));
+            if (hipMemset(p, 0, kHlMonWords * sizeof(unsigned)) != hipSuccess) {
+                (void)hipFree(p);
+                return fail(c, INFUR_E_HIP, "hipMemset of the range monitor failed");
+            }
+            c->d_hlmon = p;
+        } else if (!on && c->d_hlmon) {
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            (void)hipFree(c->d_hlmon);
+            c->d_hlmon = nullptr;
+        } else {
+            return INFUR_OK;
         }
-        c->d_hlmon = p;
-    } else if (!on && c->d_hlmon) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        (void)hipFree(c->d_hlmon);
-        c->d_hlmon = nullptr;
-    } else {
+        // the kernel arguments of a captured frame name the words (or their absence): like any allocation or release
+        c->mem_gen++;
+        graphs_drop(c);
         return INFUR_OK;
-    }
-    // the kernel arguments of a captured frame name the words (or their absence): like any allocation or release
-    c->mem_gen++;
-    graphs_drop(c);
-    return INFUR_OK;
+    });
 }
 
 int32_t infur_hl_range(infur_ctx* c, float* act_amax, float* wino_amax, uint32_t* saturated, uint32_t* nan_seen) {
-    enter(c);
-    if (!c) return INFUR_E_INVALID_ARG;
-    if (!c->d_hlmon) return fail(c, INFUR_E_INVALID_ARG, "the range monitor is not enabled (infur_hl_monitor_enable)");
-    unsigned v[kHlMonWords];
-    HIPCHK(c, hipMemcpyAsync(v, c->d_hlmon, sizeof v, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_hlmon, 0, sizeof v, c->stream));  // (ordered before the next forward on this stream)
-    float act, wino;
-    memcpy(&act, &v[kHlMonAct], 4);
-    memcpy(&wino, &v[kHlMonWino], 4);
-    // values up to kHlHiMax are stored exactly as hi + lo; beyond it the split's upper clamp changed them (+inf included)
-    if (act_amax) *act_amax = act;
-    if (wino_amax) *wino_amax = wino / split_wino_scale(wino_mt(c));  // (the transform stores V * split_wino_scale: a power of two)
-    if (saturated) *saturated = (act > kHlHiMax || wino > kHlHiMax) ? 1u : 0u;
-    if (nan_seen) *nan_seen = v[kHlMonNan] ? 1u : 0u;
-    return INFUR_OK;
+    return abi_call(c, [&]() -> int32_t {
+        if (!c) return INFUR_E_INVALID_ARG;
+        if (!c->d_hlmon) return fail(c, INFUR_E_INVALID_ARG, "the range monitor is not enabled (infur_hl_monitor_enable)");
+        unsigned v[kHlMonWords];
+        HIPCHK(c, hipMemcpyAsync(v, c->d_hlmon, sizeof v, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemsetAsync(c->d_hlmon, 0, sizeof v, c->stream));  // (ordered before the next forward on this stream)
+        float act, wino;
+        memcpy(&act, &v[kHlMonAct], 4);
+        memcpy(&wino, &v[kHlMonWino], 4);
+        // values up to kHlHiMax are stored exactly as hi + lo; beyond it the split's upper clamp changed them (+inf included)
+        if (act_amax) *act_amax = act;
+        if (wino_amax) *wino_amax = wino / split_wino_scale(wino_mt(c));  // (the transform stores V * split_wino_scale: a power of two)
+        if (saturated) *saturated = (act > kHlHiMax || wino > kHlHiMax) ? 1u : 0u;
+        if (nan_seen) *nan_seen = v[kHlMonNan] ? 1u : 0u;
+        return INFUR_OK;
+    });
 }
 
 // ---- tuning database: infur_tuner.cpp ----
@@ -1913,71 +1852,67 @@ int32_t infur_profile_enable(infur_ctx* c, uint32_t on) {
 }
 
 int32_t infur_profile_count(infur_ctx* c, uint32_t* n) {
-    enter(c);
-    if (!c || !n) return INFUR_E_INVALID_ARG;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    *n = (uint32_t)c->prof.size();
-    return INFUR_OK;
+    return abi_call(c, [&]() -> int32_t {
+        if (!c || !n) return INFUR_E_INVALID_ARG;
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        *n = (uint32_t)c->prof.size();
+        return INFUR_OK;
+    });
 }
 
 int32_t infur_profile_get(infur_ctx* c, uint32_t i, infur_kernel_record* rec) {
-    enter(c);
-    if (!c || !rec || i >= c->prof.size()) return INFUR_E_INVALID_ARG;
-    const ProfRec& r = c->prof[i];
-    memset(rec, 0, sizeof *rec);
-    snprintf(rec->name, sizeof rec->name, "%s", r.name.c_str());
-    snprintf(rec->kernel, sizeof rec->kernel, "%s", r.kernel);
-    float ms = 0;
-    HIPCHK(c, hipEventElapsedTime(&ms, r.e0, r.e1));
-    rec->ms = ms;
-    rec->flops = r.flops;
-    rec->bytes = r.bytes;
-    rec->algo_flops = r.algo_flops;
-    return INFUR_OK;
+    return abi_call(c, [&]() -> int32_t {
+        if (!c || !rec || i >= c->prof.size()) return INFUR_E_INVALID_ARG;
+        const ProfRec& r = c->prof[i];
+        memset(rec, 0, sizeof *rec);
+        snprintf(rec->name, sizeof rec->name, "%s", r.name.c_str());
+        snprintf(rec->kernel, sizeof rec->kernel, "%s", r.kernel);
+        float ms = 0;
+        HIPCHK(c, hipEventElapsedTime(&ms, r.e0, r.e1));
+        rec->ms = ms;
+        rec->flops = r.flops;
+        rec->bytes = r.bytes;
+        rec->algo_flops = r.algo_flops;
+        return INFUR_OK;
+    });
 }
 
 // ---- device memory helpers ----
 int32_t infur_dev_alloc(infur_ctx* c, size_t bytes, void** d) {
-    enter(c);
-    if (!c || !d) return INFUR_E_INVALID_ARG;
-    HIPCHK(c, hipMalloc(d, bytes ? bytes : 1));
-    return INFUR_OK;
+    return abi_call(c, [&]() -> int32_t {
+        if (!c || !d) return INFUR_E_INVALID_ARG;
+        HIPCHK(c, hipMalloc(d, bytes ? bytes : 1));
+        return INFUR_OK;
+    });
 }
 int32_t infur_dev_free(infur_ctx* c, void* d) {
-    enter(c);
-    if (!c) return INFUR_E_INVALID_ARG;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipFree(d));
-    return INFUR_OK;
+    return abi_call(c, [&]() -> int32_t {
+        if (!c) return INFUR_E_INVALID_ARG;
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipFree(d));
+        return INFUR_OK;
+    });
 }
 int32_t infur_memcpy_h2d(infur_ctx* c, void* d, const void* s, size_t n) {
-    enter(c);
-    if (!c) return INFUR_E_INVALID_ARG;
-    HIPCHK(c, hipMemcpyAsync(d, s, n, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return INFUR_OK;
+    return abi_call(c, [&]() -> int32_t {
+        if (!c) return INFUR_E_INVALID_ARG;
+        HIPCHK(c, hipMemcpyAsync(d, s, n, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return INFUR_OK;
+    });
 }
 int32_t infur_memcpy_d2h(infur_ctx* c, void* d, const void* s, size_t n) {
-    enter(c);
-    if (!c) return INFUR_E_INVALID_ARG;
-    HIPCHK(c, hipMemcpyAsync(d, s, n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return INFUR_OK;
+    return abi_call(c, [&]() -> int32_t {
+        if (!c) return INFUR_E_INVALID_ARG;
+        HIPCHK(c, hipMemcpyAsync(d, s, n, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return INFUR_OK;
+    });
 }
 
 }  // extern "C"
 
 namespace infur {
-int32_t ctx_fail(infur_ctx* c, int32_t code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (c) c->err = buf;
-    return code;
-}
-void ctx_enter(const infur_ctx* c) { enter(c); }
 void ctx_model_free(infur_ctx* c) { model_free(c); }
 }  // namespace infur
 

@@ -195,9 +195,13 @@ struct infur_ctx {
 
 namespace infur {
 // records the message on the context and returns `code`
-int32_t ctx_fail(infur_ctx* c, int32_t code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
-// every entry point runs on its context's device (hipMalloc / launches follow the calling thread's current device)
-void ctx_enter(const infur_ctx* c);
+int32_t fail(infur_ctx* c, int32_t code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
+// Every entry point runs on its context's device: a process may hold contexts on several GPUs, and hipMalloc / kernel
+// launches follow the calling thread's current device, not the stream's.
+inline void enter(const infur_ctx* c) {
+    int cur = -1;
+    if (c && (hipGetDevice(&cur) != hipSuccess || cur != c->device)) (void)hipSetDevice(c->device);
+}
 // releases the context's weights and marks it unloaded
 void ctx_model_free(infur_ctx* c);
 // infur_stream.cpp: releases a streaming ring's resources and detaches it from its context(s); the handle stays allocated

@@ -314,7 +314,7 @@ int32_t infur_group_create(infur_ctx* const* ctxs, uint32_t n_ctx, infur_group**
     for (uint32_t i = 0; i < n_ctx; i++) {
         if (!ctxs[i]) return INFUR_E_INVALID_ARG;
         for (uint32_t j = 0; j < i; j++)
-            if (ctxs[j] == ctxs[i]) return ctx_fail(ctxs[0], INFUR_E_INVALID_ARG, "context %u appears twice in the group", i);
+            if (ctxs[j] == ctxs[i]) return fail(ctxs[0], INFUR_E_INVALID_ARG, "context %u appears twice in the group", i);
     }
     infur_group* g = new (std::nothrow) infur_group();
     if (!g) return INFUR_E_INVALID_ARG;
@@ -325,7 +325,7 @@ int32_t infur_group_create(infur_ctx* const* ctxs, uint32_t n_ctx, infur_group**
         if (g->devs.size() >= 2 || force_rccl()) {
             const Rccl& R = rccl();
             if (!R.ok()) {
-                const int32_t rc = ctx_fail(ctxs[0], INFUR_E_RCCL, "a group over %zu devices needs RCCL, which is not available: %s",
+                const int32_t rc = fail(ctxs[0], INFUR_E_RCCL, "a group over %zu devices needs RCCL, which is not available: %s",
                                             g->devs.size(), R.why.c_str());
                 delete g;
                 return rc;
@@ -336,7 +336,7 @@ int32_t infur_group_create(infur_ctx* const* ctxs, uint32_t n_ctx, infur_group**
             const ncclResult_t r = inject_fail("init") ? ncclInternalError : R.CommInitAll(g->comms.data(), (int)g->devs.size(), g->devs.data());
             if (prev >= 0) (void)hipSetDevice(prev);  // (ncclCommInitAll visits every device)
             if (r != ncclSuccess) {
-                const int32_t rc = ctx_fail(ctxs[0], INFUR_E_RCCL, "ncclCommInitAll over %zu devices failed: %s", g->devs.size(),
+                const int32_t rc = fail(ctxs[0], INFUR_E_RCCL, "ncclCommInitAll over %zu devices failed: %s", g->devs.size(),
                                             R.GetErrorString(r));
                 g->comms.clear();
                 delete g;
@@ -350,7 +350,7 @@ int32_t infur_group_create(infur_ctx* const* ctxs, uint32_t n_ctx, infur_group**
         }
     } catch (...) {
         infur_group_destroy(g);
-        return ctx_fail(ctxs[0], INFUR_E_INVALID_ARG, "could not create the group (out of host memory or threads)");
+        return fail(ctxs[0], INFUR_E_INVALID_ARG, "could not create the group (out of host memory or threads)");
     }
     *out = g;
     return INFUR_OK;
@@ -407,14 +407,14 @@ static int32_t group_weights_broadcast_body(infur_group* g, uint32_t root) {
     auto release = [&]() {
         for (size_t i = 0; i < n; i++)
             if (arena[i] && i != root) {
-                ctx_enter(g->ctxs[i]);
+                enter(g->ctxs[i]);
                 (void)hipFree(arena[i]);
             }
     };
     arena[root] = rc->d_weights;
     for (size_t i = 0; i < n; i++) {
         if (i == root) continue;
-        ctx_enter(g->ctxs[i]);
+        enter(g->ctxs[i]);
         const hipError_t e = hipMalloc(&arena[i], bytes);
         if (e != hipSuccess) {
             arena[i] = nullptr;
@@ -430,7 +430,7 @@ static int32_t group_weights_broadcast_body(infur_group* g, uint32_t root) {
         const int r = rank_of_device(g, g->ctxs[i]->device);
         if (leader[r] < 0) leader[r] = (int)i;
     }
-    ctx_enter(rc);
+    enter(rc);
     hipError_t he = hipStreamSynchronize(rc->stream);  // the root's load has finished
     int32_t status = he == hipSuccess ? INFUR_OK : gfail(g, INFUR_E_HIP, "root stream: %s", hipGetErrorString(he));
 
@@ -440,7 +440,7 @@ static int32_t group_weights_broadcast_body(infur_group* g, uint32_t root) {
         // RCCL's rules for ONE thread driving SEVERAL devices (single-process multi-device): the per-rank calls of one
         // collective must sit inside one ncclGroupStart / ncclGroupEnd -- outside a group the first rank's call would block
         // waiting for peers this same thread has not called yet; every call names its own rank's communicator, runs with
-        // that rank's device current (ctx_enter) and is enqueued on a stream OF that device (the leader context's); the send
+        // that rank's device current (enter) and is enqueued on a stream OF that device (the leader context's); the send
         // buffer argument matters on the root only, where send == recv == the loaded arena (in place).  ncclGroupEnd
         // launches them all; completion is per stream, waited for below.
         const Rccl& R = rccl();
@@ -448,7 +448,7 @@ static int32_t group_weights_broadcast_body(infur_group* g, uint32_t root) {
         const bool started = r == ncclSuccess;
         for (size_t k = 0; k < g->devs.size() && r == ncclSuccess; k++) {
             infur_ctx* c = g->ctxs[leader[k]];
-            ctx_enter(c);
+            enter(c);
             r = R.Broadcast(rc->d_weights, arena[leader[k]], bytes, ncclUint8, root_rank, g->comms[k], c->stream);
         }
         if (started) {
@@ -458,7 +458,7 @@ static int32_t group_weights_broadcast_body(infur_group* g, uint32_t root) {
         if (r != ncclSuccess) status = gfail(g, INFUR_E_RCCL, "ncclBroadcast of %zu weight bytes failed: %s", bytes, R.GetErrorString(r));
         for (size_t k = 0; k < g->devs.size() && status == INFUR_OK; k++) {
             infur_ctx* c = g->ctxs[leader[k]];
-            ctx_enter(c);
+            enter(c);
             he = hipStreamSynchronize(c->stream);
             if (he != hipSuccess) status = gfail(g, INFUR_E_HIP, "broadcast on device %d: %s", c->device, hipGetErrorString(he));
         }
@@ -469,7 +469,7 @@ static int32_t group_weights_broadcast_body(infur_group* g, uint32_t root) {
         const int k = rank_of_device(g, g->ctxs[i]->device);
         if ((int)i == leader[k]) continue;
         infur_ctx* c = g->ctxs[i];
-        ctx_enter(c);
+        enter(c);
         if (!g->comms.empty() && g->devs.size() == 1) {
             const Rccl& R = rccl();
             const ncclResult_t r = inject_fail("broadcast") ? ncclInternalError
@@ -490,7 +490,7 @@ static int32_t group_weights_broadcast_body(infur_group* g, uint32_t root) {
     }
     for (size_t i = 0; i < n; i++) {
         if (i == root) continue;
-        ctx_enter(g->ctxs[i]);
+        enter(g->ctxs[i]);
         (void)hipStreamSynchronize(g->ctxs[i]->stream);  // nothing of the old model is in flight
         adopt_model(g->ctxs[i], rc, arena[i]);
     }

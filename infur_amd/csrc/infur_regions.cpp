@@ -16,17 +16,6 @@ namespace {
 
 static_assert(kRegWords == INFUR_REGION_WORDS, "regions.hip and the header disagree about the row");
 
-// (hipFree synchronises: nothing in flight can still touch the old buffer)
-int32_t ensure_private(infur_ctx* c, Buf& b, size_t bytes) {
-    if (b.bytes >= bytes && b.p) return INFUR_OK;
-    if (b.p) HIPCHK(c, hipFree(b.p));
-    b.p = nullptr;
-    b.bytes = 0;
-    HIPCHK(c, hipMalloc(&b.p, bytes));
-    b.bytes = bytes;
-    return INFUR_OK;
-}
-
 int32_t reg_check(infur_ctx* c, uint32_t connectivity, uint32_t flags) {
     if (connectivity != INFUR_CONNECT_4 && connectivity != INFUR_CONNECT_8)
         return fail(c, INFUR_E_INVALID_ARG, "connectivity %u: 4 or 8", connectivity);
@@ -65,29 +54,29 @@ extern "C" {
 
 int32_t infur_regions_dev(infur_ctx* c, const void* d_klass, const void* d_conf, uint32_t h, uint32_t w, uint32_t connectivity,
                           uint32_t min_pixels, uint32_t flags, void* d_labels, void* d_table, uint32_t table_rows, void* d_n) {
-    ctx_enter(c);
-    if (!c) return INFUR_E_INVALID_ARG;
-    RETIF(reg_check(c, connectivity, flags));
-    const size_t hw = (size_t)h * w;
-    if (hw >= 0xFFFFFFFFull) return fail(c, INFUR_E_INVALID_ARG, "%ux%u: a label plane indexes at most 2^32 - 2 pixels", w, h);
-    if (!d_labels && !d_table && !d_n) return INFUR_E_INVALID_ARG;
-    if (hw == 0) {  // empty image: no region, nothing else to write
-        if (d_n) HIPCHK(c, hipMemsetAsync(d_n, 0, 4, c->stream));
+    return abi_call(c, [&]() -> int32_t {
+        if (!c) return INFUR_E_INVALID_ARG;
+        RETIF(reg_check(c, connectivity, flags));
+        const size_t hw = (size_t)h * w;
+        if (hw >= 0xFFFFFFFFull) return fail(c, INFUR_E_INVALID_ARG, "%ux%u: a label plane indexes at most 2^32 - 2 pixels", w, h);
+        if (!d_labels && !d_table && !d_n) return INFUR_E_INVALID_ARG;
+        if (hw == 0) {  // empty image: no region, nothing else to write
+            if (d_n) HIPCHK(c, hipMemsetAsync(d_n, 0, 4, c->stream));
+            return INFUR_OK;
+        }
+        if (!d_klass) return INFUR_E_INVALID_ARG;
+        RETIF(ensure_private(c, c->st_reg, regions_scratch_bytes(hw)));
+        ProfScope ps(c, "regions", "regions", 0, (double)hw * (1 + (d_conf ? 1 : 0) + (d_labels ? 4 : 0)));
+        HIPCHK(c, launch_regions((const uint8_t*)d_klass, (const uint8_t*)d_conf, h, w, connectivity == INFUR_CONNECT_8, min_pixels,
+                                 (flags & INFUR_REGIONS_SKIP_BACKGROUND) != 0, c->st_reg.p, (unsigned*)d_labels, (unsigned long long*)d_table,
+                                 table_rows, (unsigned*)d_n, c->stream));
         return INFUR_OK;
-    }
-    if (!d_klass) return INFUR_E_INVALID_ARG;
-    RETIF(ensure_private(c, c->st_reg, regions_scratch_bytes(hw)));
-    ProfScope ps(c, "regions", "regions", 0, (double)hw * (1 + (d_conf ? 1 : 0) + (d_labels ? 4 : 0)));
-    HIPCHK(c, launch_regions((const uint8_t*)d_klass, (const uint8_t*)d_conf, h, w, connectivity == INFUR_CONNECT_8, min_pixels,
-                             (flags & INFUR_REGIONS_SKIP_BACKGROUND) != 0, c->st_reg.p, (unsigned*)d_labels, (unsigned long long*)d_table,
-                             table_rows, (unsigned*)d_n, c->stream));
-    return INFUR_OK;
+    });
 }
 
 int32_t infur_regions(infur_ctx* c, const uint8_t* klass, const uint8_t* conf, uint32_t h, uint32_t w, uint32_t connectivity,
                       uint32_t min_pixels, uint32_t flags, uint32_t* labels, uint64_t* table, uint32_t table_rows, uint32_t* n_regions) {
-    try {
-        ctx_enter(c);
+    return abi_call(c, [&]() -> int32_t {
         if (!c) return INFUR_E_INVALID_ARG;
         RETIF(reg_check(c, connectivity, flags));
         const size_t hw = (size_t)h * w;
@@ -106,19 +95,14 @@ int32_t infur_regions(infur_ctx* c, const uint8_t* klass, const uint8_t* conf, u
         RETIF(infur_regions_dev(c, base + st.klass, conf ? base + st.conf : nullptr, h, w, connectivity, min_pixels, flags,
                                 labels ? base + st.labels : nullptr, (table && st.rows) ? base + st.table : nullptr, (uint32_t)st.rows, base));
         return reg_read_back(c, base, st, hw, labels, table, n_regions);
-    } catch (const std::bad_alloc&) {
-        return fail(c, INFUR_E_CAPACITY, "out of host memory");
-    } catch (const std::exception& e) {
-        return fail(c, INFUR_E_INVALID_ARG, "internal error: %s", e.what());
-    }
+    });
 }
 
 int32_t infur_frame_regions_dev(infur_ctx* c, const void* d_bgr, uint32_t w, uint32_t h, float factor, uint32_t mode, uint32_t decode,
                                 uint32_t connectivity, uint32_t min_pixels, uint32_t flags, void* d_klass, void* d_conf, size_t plane_cap,
                                 void* d_labels, size_t labels_cap, void* d_table, uint32_t table_rows, void* d_n, void* d_scaled, uint32_t* ow,
                                 uint32_t* oh) {
-    try {
-        ctx_enter(c);
+    return abi_call(c, [&]() -> int32_t {
         if (!c || !ow || !oh) return INFUR_E_INVALID_ARG;
         RETIF(reg_check(c, connectivity, flags));
         uint32_t a = 0, b = 0;
@@ -140,53 +124,41 @@ int32_t infur_frame_regions_dev(infur_ctx* c, const void* d_bgr, uint32_t w, uin
         RETIF(infur_frame_segments_dev(c, d_bgr, w, h, factor, mode, decode, kl, cf, (d_klass || d_conf) ? plane_cap : npix, nullptr, 0, nullptr,
                                        0, d_scaled, ow, oh));
         return infur_regions_dev(c, kl, cf, *oh, *ow, connectivity, min_pixels, flags, d_labels, d_table, table_rows, d_n);
-    } catch (const std::bad_alloc&) {
-        return fail(c, INFUR_E_CAPACITY, "out of host memory");
-    } catch (const std::exception& e) {
-        return fail(c, INFUR_E_INVALID_ARG, "internal error: %s", e.what());
-    }
+    });
 }
 
 int32_t infur_frame_regions(infur_ctx* c, const uint8_t* bgr, uint32_t w, uint32_t h, float factor, uint32_t mode, uint32_t decode,
                             uint32_t connectivity, uint32_t min_pixels, uint32_t flags, uint8_t* klass, uint8_t* conf, size_t plane_cap,
                             uint32_t* labels, size_t labels_cap, uint64_t* table, uint32_t table_rows, uint32_t* n_regions, uint8_t* scaled,
                             uint32_t* ow, uint32_t* oh) {
-    try {
-        ctx_enter(c);
+    return abi_call(c, [&]() -> int32_t {
         if (!c || !ow || !oh) return INFUR_E_INVALID_ARG;
         RETIF(reg_check(c, connectivity, flags));
-        int32_t rc = infur_scale_validate(factor);
-        if (rc) return fail(c, rc, "%s", infur_status_string(rc));
-        rc = infur_scale_out_dims(w, h, factor, ow, oh);
-        if (rc) return fail(c, rc, "%s", infur_status_string(rc));
-        if (!bgr) return INFUR_E_INVALID_ARG;
-        const size_t in_bytes = (size_t)w * h * 3, npix = (size_t)*ow * *oh, sbytes = npix * 3;
-        if ((klass || conf) && plane_cap < npix) return fail(c, INFUR_E_CAPACITY, "a plane needs %zu bytes, buffer has %zu", npix, plane_cap);
-        if (labels && labels_cap < npix * 4) return fail(c, INFUR_E_CAPACITY, "the label plane needs %zu bytes, buffer has %zu", npix * 4, labels_cap);
-        const RegStage st(npix, table ? table_rows : 0);
-        RETIF(ensure(c, c->st_in, in_bytes ? in_bytes : 1));
-        RETIF(ensure(c, c->st_scaled, sbytes ? sbytes : 1));
-        RETIF(ensure_private(c, c->st_reg_io, st.bytes));
-        uint8_t* base = (uint8_t*)c->st_reg_io.p;
-        HIPCHK(c, hipMemcpyAsync(c->st_in.p, bgr, in_bytes, hipMemcpyHostToDevice, c->stream));
-        rc = infur_frame_regions_dev(c, c->st_in.p, w, h, factor, mode, decode, connectivity, min_pixels, flags, base + st.klass,
-                                     (conf || table) ? base + st.conf : nullptr, npix, labels ? base + st.labels : nullptr, npix * 4,
-                                     (table && st.rows) ? base + st.table : nullptr, (uint32_t)st.rows, (labels || table || n_regions) ? base : nullptr,
-                                     (scaled || factor != 1.0f) ? c->st_scaled.p : nullptr, ow, oh);
-        if (rc != INFUR_OK && rc != INFUR_E_MODEL_NOT_LOADED) return rc;
-        if (scaled) HIPCHK(c, hipMemcpyAsync(scaled, c->st_scaled.p, sbytes, hipMemcpyDeviceToHost, c->stream));
-        if (rc == INFUR_OK) {
-            if (klass) HIPCHK(c, hipMemcpyAsync(klass, base + st.klass, npix, hipMemcpyDeviceToHost, c->stream));
-            if (conf) HIPCHK(c, hipMemcpyAsync(conf, base + st.conf, npix, hipMemcpyDeviceToHost, c->stream));
-            RETIF(reg_read_back(c, base, st, npix, labels, table, n_regions));
-        }
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        return rc;
-    } catch (const std::bad_alloc&) {
-        return fail(c, INFUR_E_CAPACITY, "out of host memory");
-    } catch (const std::exception& e) {
-        return fail(c, INFUR_E_INVALID_ARG, "internal error: %s", e.what());
-    }
+        RegStage st(0, 0);
+        uint8_t* base = nullptr;
+        return frame_host(
+            c, bgr, w, h, factor, scaled, ow, oh,
+            [&](size_t npix) -> int32_t {
+                if ((klass || conf) && plane_cap < npix) return fail(c, INFUR_E_CAPACITY, "a plane needs %zu bytes, buffer has %zu", npix, plane_cap);
+                if (labels && labels_cap < npix * 4) return fail(c, INFUR_E_CAPACITY, "the label plane needs %zu bytes, buffer has %zu", npix * 4, labels_cap);
+                st = RegStage(npix, table ? table_rows : 0);
+                RETIF(ensure_private(c, c->st_reg_io, st.bytes));
+                base = (uint8_t*)c->st_reg_io.p;
+                return INFUR_OK;
+            },
+            [&](void* d_bgr, void* d_scaled) {
+                const size_t npix = (size_t)*ow * *oh;
+                return infur_frame_regions_dev(c, d_bgr, w, h, factor, mode, decode, connectivity, min_pixels, flags, base + st.klass,
+                                               (conf || table) ? base + st.conf : nullptr, npix, labels ? base + st.labels : nullptr, npix * 4,
+                                               (table && st.rows) ? base + st.table : nullptr, (uint32_t)st.rows,
+                                               (labels || table || n_regions) ? base : nullptr, d_scaled, ow, oh);
+            },
+            [&](size_t npix) -> int32_t {
+                if (klass) HIPCHK(c, hipMemcpyAsync(klass, base + st.klass, npix, hipMemcpyDeviceToHost, c->stream));
+                if (conf) HIPCHK(c, hipMemcpyAsync(conf, base + st.conf, npix, hipMemcpyDeviceToHost, c->stream));
+                return reg_read_back(c, base, st, npix, labels, table, n_regions);
+            });
+    });
 }
 
 }  // extern "C"

@@ -10,6 +10,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <exception>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -17,9 +19,6 @@
 #include "kernels.h"
 
 namespace infur {
-
-// records the message on the context and returns `code`
-int32_t fail(infur_ctx* c, int32_t code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
 
 #define HIPCHK(c, expr)                                                                         \
     do {                                                                                        \
@@ -35,8 +34,23 @@ int32_t fail(infur_ctx* c, int32_t code, const char* fmt, ...) __attribute__((fo
         if (rc__ != INFUR_OK) return rc__; \
     } while (0)
 
+// The exception boundary of the C ABI: every entry point that can reach an allocation (a std::string, a std::vector, `new`) runs
+// its body through this, so that nothing unwinds into a C, Python or Rust caller.  Makes the context's device current first.
+template <class F>
+int32_t abi_call(infur_ctx* c, F&& body) {
+    try {
+        enter(c);
+        return body();
+    } catch (const std::bad_alloc&) {
+        return fail(c, INFUR_E_CAPACITY, "out of host memory");
+    } catch (const std::exception& e) {
+        return fail(c, INFUR_E_INVALID_ARG, "internal error: %s", e.what());
+    }
+}
+
 // ---- arena ----
 int32_t ensure(infur_ctx* c, Buf& b, size_t bytes);
+int32_t ensure_private(infur_ctx* c, Buf& b, size_t bytes);
 int32_t pool_acquire(infur_ctx* c, size_t bytes, int* slot);
 void pool_release(infur_ctx* c, Tensor& t);
 void pool_release_all(infur_ctx* c);
@@ -111,6 +125,41 @@ struct EventPair {  // two timing events, released on every return path
         if (e1) (void)hipEventDestroy(e1);
     }
 };
+// ---- the front half of every fused frame call (infur_capi.cpp) ----
+// infur_scale_validate + infur_scale_out_dims, with their messages: -> the scaled dimensions
+int32_t scale_dims(infur_ctx* c, uint32_t w, uint32_t h, float factor, uint32_t* ow, uint32_t* oh);
+// What the _dev frame calls check before their own outputs: the scale mode, scale_dims, the frame, an empty frame -> E_SHAPE,
+// and the no-model rule (the Scale stage still runs, then E_MODEL_NOT_LOADED).  -> *ow x *oh = *npix pixels
+int32_t frame_check(infur_ctx* c, const void* d_bgr, uint32_t w, uint32_t h, float factor, uint32_t mode, void* d_scaled, uint32_t* ow,
+                    uint32_t* oh, size_t* npix);
+// Scale (into d_scaled or st_scaled, when there is anything to scale or the caller wants the frame) -> forward(), leaving the
+// scale's profile records in front of the model's.  The caller holds the frame's RoctxRange, so that it spans the decode too.
+int32_t scale_forward(infur_ctx* c, const void* d_bgr, uint32_t w, uint32_t h, float factor, uint32_t mode, void* d_scaled, uint32_t ow,
+                      uint32_t oh);
+
+// The host-pointer form of a fused frame call around its _dev sibling: dimensions, staging of the frame and the scaled frame,
+// H2D, the device call, scaled frame back (also when no model is loaded), the outputs back on OK, synchronise.
+//   stage(npix)        the call's own capacity checks and output staging
+//   dev(d_bgr, d_sc)   the _dev sibling on the staged frame; d_sc is null when no scaled frame is needed
+//   read_back(npix)    enqueues the copies of the call's outputs to the host
+template <class Stage, class Dev, class ReadBack>
+int32_t frame_host(infur_ctx* c, const uint8_t* bgr, uint32_t w, uint32_t h, float factor, uint8_t* scaled, uint32_t* ow, uint32_t* oh,
+                   Stage&& stage, Dev&& dev, ReadBack&& read_back) {
+    RETIF(scale_dims(c, w, h, factor, ow, oh));
+    if (!bgr) return INFUR_E_INVALID_ARG;
+    const size_t in_bytes = (size_t)w * h * 3, npix = (size_t)*ow * *oh, sbytes = npix * 3;
+    RETIF(stage(npix));
+    RETIF(ensure(c, c->st_in, in_bytes ? in_bytes : 1));
+    RETIF(ensure(c, c->st_scaled, sbytes ? sbytes : 1));
+    HIPCHK(c, hipMemcpyAsync(c->st_in.p, bgr, in_bytes, hipMemcpyHostToDevice, c->stream));
+    const int32_t rc = dev(c->st_in.p, (scaled || factor != 1.0f) ? c->st_scaled.p : nullptr);
+    if (rc != INFUR_OK && rc != INFUR_E_MODEL_NOT_LOADED) return rc;
+    if (scaled) HIPCHK(c, hipMemcpyAsync(scaled, c->st_scaled.p, sbytes, hipMemcpyDeviceToHost, c->stream));
+    if (rc == INFUR_OK) RETIF(read_back(npix));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return rc;
+}
+
 // quantised models (infur_quant_model.cpp)
 int32_t model_load_q_dev(infur_ctx* c, const void* d_blob, size_t len);
 int32_t forward_q(infur_ctx* c, const uint8_t* d_bgr, int w, int h);

@@ -15,19 +15,6 @@ using namespace infur;
 
 namespace {
 
-// Staging only the host-pointer calls below use: no captured graph can hold a pointer into it (the graphs of
-// infur_frame_advance_dev hold the caller's pointers, the arena and st_scaled), so growing it leaves mem_gen -- and with it
-// the cached graphs -- alone.  (hipFree synchronises: nothing in flight can still touch the old buffer.)
-int32_t ensure_private(infur_ctx* c, Buf& b, size_t bytes) {
-    if (b.bytes >= bytes && b.p) return INFUR_OK;
-    if (b.p) HIPCHK(c, hipFree(b.p));
-    b.p = nullptr;
-    b.bytes = 0;
-    HIPCHK(c, hipMalloc(&b.p, bytes));
-    b.bytes = bytes;
-    return INFUR_OK;
-}
-
 // st_seg: [statistics table k x 8 u64][class plane][confidence plane], the planes on 16-byte boundaries
 struct SegStage {
     size_t klass, conf, bytes;
@@ -53,31 +40,15 @@ int32_t seg_stats_begin(infur_ctx* c, int k) {
 // the fused frame path with the Segments decode: Scale -> forward -> up-sample + argmax [+ softmax] + planes / statistics
 int32_t frame_segments_body(infur_ctx* c, const void* d_bgr, uint32_t w, uint32_t h, float factor, uint32_t mode, uint32_t decode,
                             void* d_klass, void* d_conf, void* d_stats, void* d_rgba, void* d_scaled, uint32_t ow, uint32_t oh) {
-    const size_t npix = (size_t)ow * oh, sbytes = npix * 3;
-    const void* frame = d_bgr;
     RoctxRange rr("infur frame segments");
-    prof_reset(c);
-    std::vector<ProfRec> pre;
-    if (factor != 1.0f || d_scaled) {
-        void* dst = d_scaled;
-        if (!dst) {
-            RETIF(ensure(c, c->st_scaled, sbytes));
-            dst = c->st_scaled.p;
-        }
-        uint32_t a, b;
-        RETIF(infur_scale_dev(c, d_bgr, w, h, factor, mode, dst, sbytes, &a, &b));
-        frame = dst;
-        pre.swap(c->prof);  // forward() resets the records; keep the scale's
-    }
-    RETIF(forward(c, (const uint8_t*)frame, (int)ow, (int)oh));
-    c->prof.insert(c->prof.begin(), pre.begin(), pre.end());
+    RETIF(scale_forward(c, d_bgr, w, h, factor, mode, d_scaled, ow, oh));
     const Tensor& t = c->out_low;  // only out[0] is decoded, app.rs:116
     SegOut o;
     o.klass = (uint8_t*)d_klass;
     o.conf = (uint8_t*)d_conf;
     o.rgba = (uint32_t*)d_rgba;
     o.shards = d_stats ? c->d_seg_shards : nullptr;
-    const double out_bytes = (double)npix * ((d_klass ? 1 : 0) + (d_conf ? 1 : 0) + (d_rgba ? 4 : 0));
+    const double out_bytes = (double)ow * oh * ((d_klass ? 1 : 0) + (d_conf ? 1 : 0) + (d_rgba ? 4 : 0));
     ProfScope ps(c, "out.resize+segments", "upsample_argmax_segments", 0, (double)t.bytes() + out_bytes);
     if (d_stats) RETIF(seg_stats_begin(c, t.c));
     HIPCHK(c, launch_upsample_argmax_segments((const float*)t.p, t.h, t.w, t.c, (int)decode, c->d_color_lut, o, (int)oh, (int)ow, c->stream,
@@ -100,27 +71,27 @@ const char* infur_voc_class_name(uint32_t k) { return k < 21 ? kVocNames[k] : nu
 
 int32_t infur_segments_dev(infur_ctx* c, const void* d_khw, uint32_t k, uint32_t h, uint32_t w, uint32_t decode, void* d_klass,
                            void* d_conf, void* d_stats, void* d_rgba) {
-    ctx_enter(c);
-    if (!c) return INFUR_E_INVALID_ARG;
-    RETIF(seg_check(c, decode, k));
-    if ((size_t)h * w == 0) return INFUR_OK;  // empty image: nothing to write, as infur_colorcode
-    if ((!d_klass && !d_conf && !d_stats && !d_rgba) || (k > 0 && !d_khw)) return INFUR_E_INVALID_ARG;
-    SegOut o;
-    o.klass = (uint8_t*)d_klass;
-    o.conf = (uint8_t*)d_conf;
-    o.rgba = (uint32_t*)d_rgba;
-    o.shards = (d_stats && k > 0) ? c->d_seg_shards : nullptr;  // k == 0: there is no table to write
-    ProfScope ps(c, "segments", "segments_planar", 0, (double)h * w * (4.0 * k + (d_klass ? 1 : 0) + (d_conf ? 1 : 0) + (d_rgba ? 4 : 0)));
-    if (o.shards) RETIF(seg_stats_begin(c, (int)k));
-    HIPCHK(c, launch_segments_planar((const float*)d_khw, (int)k, (int)h, (int)w, (int)decode, c->d_color_lut, o, c->stream));
-    if (o.shards) HIPCHK(c, launch_segments_stats_finalize(c->d_seg_shards, (int)k, (unsigned long long*)d_stats, c->stream));
-    return INFUR_OK;
+    return abi_call(c, [&]() -> int32_t {
+        if (!c) return INFUR_E_INVALID_ARG;
+        RETIF(seg_check(c, decode, k));
+        if ((size_t)h * w == 0) return INFUR_OK;  // empty image: nothing to write, as infur_colorcode
+        if ((!d_klass && !d_conf && !d_stats && !d_rgba) || (k > 0 && !d_khw)) return INFUR_E_INVALID_ARG;
+        SegOut o;
+        o.klass = (uint8_t*)d_klass;
+        o.conf = (uint8_t*)d_conf;
+        o.rgba = (uint32_t*)d_rgba;
+        o.shards = (d_stats && k > 0) ? c->d_seg_shards : nullptr;  // k == 0: there is no table to write
+        ProfScope ps(c, "segments", "segments_planar", 0, (double)h * w * (4.0 * k + (d_klass ? 1 : 0) + (d_conf ? 1 : 0) + (d_rgba ? 4 : 0)));
+        if (o.shards) RETIF(seg_stats_begin(c, (int)k));
+        HIPCHK(c, launch_segments_planar((const float*)d_khw, (int)k, (int)h, (int)w, (int)decode, c->d_color_lut, o, c->stream));
+        if (o.shards) HIPCHK(c, launch_segments_stats_finalize(c->d_seg_shards, (int)k, (unsigned long long*)d_stats, c->stream));
+        return INFUR_OK;
+    });
 }
 
 int32_t infur_segments(infur_ctx* c, const float* khw, uint32_t k, uint32_t h, uint32_t w, uint32_t decode, uint8_t* klass,
                        uint8_t* conf, uint64_t* stats, uint8_t* rgba) {
-    try {
-        ctx_enter(c);
+    return abi_call(c, [&]() -> int32_t {
         if (!c) return INFUR_E_INVALID_ARG;
         RETIF(seg_check(c, decode, k));
         const size_t hw = (size_t)h * w;
@@ -140,42 +111,17 @@ int32_t infur_segments(infur_ctx* c, const float* khw, uint32_t k, uint32_t h, u
         if (rgba) HIPCHK(c, hipMemcpyAsync(rgba, c->st_rgba.p, hw * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         return INFUR_OK;
-    } catch (const std::bad_alloc&) {
-        return fail(c, INFUR_E_CAPACITY, "out of host memory");
-    } catch (const std::exception& e) {
-        return fail(c, INFUR_E_INVALID_ARG, "internal error: %s", e.what());
-    }
+    });
 }
 
 int32_t infur_frame_segments_dev(infur_ctx* c, const void* d_bgr, uint32_t w, uint32_t h, float factor, uint32_t mode, uint32_t decode,
                                  void* d_klass, void* d_conf, size_t plane_cap, void* d_stats, uint32_t stats_classes, void* d_rgba,
                                  size_t rgba_cap, void* d_scaled, uint32_t* ow, uint32_t* oh) {
-    try {
-        ctx_enter(c);
+    return abi_call(c, [&]() -> int32_t {
         if (!c || !ow || !oh) return INFUR_E_INVALID_ARG;
-        if (mode > INFUR_SCALE_BILINEAR) return fail(c, INFUR_E_INVALID_ARG, "unknown scale mode %u", mode);
         RETIF(seg_check(c, decode, 0));
-        int32_t rc = infur_scale_validate(factor);
-        if (rc) return fail(c, rc, "%s", infur_status_string(rc));
-        rc = infur_scale_out_dims(w, h, factor, ow, oh);
-        if (rc) return fail(c, rc, "%s", infur_status_string(rc));
-        if (!d_bgr) return INFUR_E_INVALID_ARG;
-        const size_t npix = (size_t)*ow * *oh, sbytes = npix * 3;
-        if (npix == 0) return fail(c, INFUR_E_SHAPE, "couldn't transform image: %ux%u", *ow, *oh);
-        if (!c->loaded) {
-            // as infur_frame_advance_dev: the Scale stage still runs
-            if (factor != 1.0f || d_scaled) {
-                void* dst = d_scaled;
-                if (!dst) {
-                    RETIF(ensure(c, c->st_scaled, sbytes));
-                    dst = c->st_scaled.p;
-                }
-                uint32_t a, b;
-                prof_reset(c);
-                RETIF(infur_scale_dev(c, d_bgr, w, h, factor, mode, dst, sbytes, &a, &b));
-            }
-            return fail(c, INFUR_E_MODEL_NOT_LOADED, "no model loaded");
-        }
+        size_t npix;
+        RETIF(frame_check(c, d_bgr, w, h, factor, mode, d_scaled, ow, oh, &npix));
         if (!d_klass && !d_conf && !d_stats && !d_rgba) return INFUR_E_INVALID_ARG;
         RETIF(seg_check(c, decode, (uint32_t)c->num_classes));
         if ((d_klass || d_conf) && plane_cap < npix) return fail(c, INFUR_E_CAPACITY, "a plane needs %zu bytes, buffer has %zu", npix, plane_cap);
@@ -183,54 +129,41 @@ int32_t infur_frame_segments_dev(infur_ctx* c, const void* d_bgr, uint32_t w, ui
         if (d_stats && stats_classes < (uint32_t)c->num_classes)
             return fail(c, INFUR_E_CAPACITY, "the statistics table needs %d classes, buffer has %u", c->num_classes, stats_classes);
         return frame_segments_body(c, d_bgr, w, h, factor, mode, decode, d_klass, d_conf, d_stats, d_rgba, d_scaled, *ow, *oh);
-    } catch (const std::bad_alloc&) {
-        return fail(c, INFUR_E_CAPACITY, "out of host memory");
-    } catch (const std::exception& e) {
-        return fail(c, INFUR_E_INVALID_ARG, "internal error: %s", e.what());
-    }
+    });
 }
 
 int32_t infur_frame_segments(infur_ctx* c, const uint8_t* bgr, uint32_t w, uint32_t h, float factor, uint32_t mode, uint32_t decode,
                              uint8_t* klass, uint8_t* conf, size_t plane_cap, uint64_t* stats, uint32_t stats_classes, uint8_t* rgba,
                              size_t rgba_cap, uint8_t* scaled, uint32_t* ow, uint32_t* oh) {
-    try {
-        ctx_enter(c);
+    return abi_call(c, [&]() -> int32_t {
         if (!c || !ow || !oh) return INFUR_E_INVALID_ARG;
         RETIF(seg_check(c, decode, 0));
-        int32_t rc = infur_scale_validate(factor);
-        if (rc) return fail(c, rc, "%s", infur_status_string(rc));
-        rc = infur_scale_out_dims(w, h, factor, ow, oh);
-        if (rc) return fail(c, rc, "%s", infur_status_string(rc));
-        if (!bgr) return INFUR_E_INVALID_ARG;
-        const size_t in_bytes = (size_t)w * h * 3, npix = (size_t)*ow * *oh, sbytes = npix * 3;
-        if ((klass || conf) && plane_cap < npix) return fail(c, INFUR_E_CAPACITY, "a plane needs %zu bytes, buffer has %zu", npix, plane_cap);
-        if (rgba && rgba_cap < npix * 4) return fail(c, INFUR_E_CAPACITY, "mask needs %zu bytes, buffer has %zu", npix * 4, rgba_cap);
-        const uint32_t k = c->loaded ? (uint32_t)c->num_classes : 0;
-        const SegStage st(stats ? (stats_classes < (uint32_t)kSegMaxClasses ? stats_classes : (uint32_t)kSegMaxClasses) : 0, npix);
-        RETIF(ensure(c, c->st_in, in_bytes ? in_bytes : 1));
-        if (rgba) RETIF(ensure(c, c->st_rgba, npix ? npix * 4 : 1));
-        RETIF(ensure(c, c->st_scaled, sbytes ? sbytes : 1));
-        RETIF(ensure_private(c, c->st_seg, st.bytes ? st.bytes : 1));
-        uint8_t* base = (uint8_t*)c->st_seg.p;
-        HIPCHK(c, hipMemcpyAsync(c->st_in.p, bgr, in_bytes, hipMemcpyHostToDevice, c->stream));
-        rc = infur_frame_segments_dev(c, c->st_in.p, w, h, factor, mode, decode, klass ? base + st.klass : nullptr, conf ? base + st.conf : nullptr,
-                                      npix, stats ? base : nullptr, stats_classes, rgba ? c->st_rgba.p : nullptr, npix * 4,
-                                      (scaled || factor != 1.0f) ? c->st_scaled.p : nullptr, ow, oh);
-        if (rc != INFUR_OK && rc != INFUR_E_MODEL_NOT_LOADED) return rc;
-        if (scaled) HIPCHK(c, hipMemcpyAsync(scaled, c->st_scaled.p, sbytes, hipMemcpyDeviceToHost, c->stream));
-        if (rc == INFUR_OK) {
-            if (klass) HIPCHK(c, hipMemcpyAsync(klass, base + st.klass, npix, hipMemcpyDeviceToHost, c->stream));
-            if (conf) HIPCHK(c, hipMemcpyAsync(conf, base + st.conf, npix, hipMemcpyDeviceToHost, c->stream));
-            if (stats) HIPCHK(c, hipMemcpyAsync(stats, base, (size_t)k * INFUR_STAT_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
-            if (rgba) HIPCHK(c, hipMemcpyAsync(rgba, c->st_rgba.p, npix * 4, hipMemcpyDeviceToHost, c->stream));
-        }
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        return rc;
-    } catch (const std::bad_alloc&) {
-        return fail(c, INFUR_E_CAPACITY, "out of host memory");
-    } catch (const std::exception& e) {
-        return fail(c, INFUR_E_INVALID_ARG, "internal error: %s", e.what());
-    }
+        SegStage st(0, 0);
+        uint8_t* base = nullptr;
+        return frame_host(
+            c, bgr, w, h, factor, scaled, ow, oh,
+            [&](size_t npix) -> int32_t {
+                if ((klass || conf) && plane_cap < npix) return fail(c, INFUR_E_CAPACITY, "a plane needs %zu bytes, buffer has %zu", npix, plane_cap);
+                if (rgba && rgba_cap < npix * 4) return fail(c, INFUR_E_CAPACITY, "mask needs %zu bytes, buffer has %zu", npix * 4, rgba_cap);
+                st = SegStage(stats ? (stats_classes < (uint32_t)kSegMaxClasses ? stats_classes : (uint32_t)kSegMaxClasses) : 0, npix);
+                if (rgba) RETIF(ensure(c, c->st_rgba, npix ? npix * 4 : 1));
+                RETIF(ensure_private(c, c->st_seg, st.bytes ? st.bytes : 1));
+                base = (uint8_t*)c->st_seg.p;
+                return INFUR_OK;
+            },
+            [&](void* d_bgr, void* d_scaled) {
+                const size_t npix = (size_t)*ow * *oh;
+                return infur_frame_segments_dev(c, d_bgr, w, h, factor, mode, decode, klass ? base + st.klass : nullptr, conf ? base + st.conf : nullptr,
+                                                npix, stats ? base : nullptr, stats_classes, rgba ? c->st_rgba.p : nullptr, npix * 4, d_scaled, ow, oh);
+            },
+            [&](size_t npix) -> int32_t {
+                if (klass) HIPCHK(c, hipMemcpyAsync(klass, base + st.klass, npix, hipMemcpyDeviceToHost, c->stream));
+                if (conf) HIPCHK(c, hipMemcpyAsync(conf, base + st.conf, npix, hipMemcpyDeviceToHost, c->stream));
+                if (stats) HIPCHK(c, hipMemcpyAsync(stats, base, (size_t)c->num_classes * INFUR_STAT_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
+                if (rgba) HIPCHK(c, hipMemcpyAsync(rgba, c->st_rgba.p, npix * 4, hipMemcpyDeviceToHost, c->stream));
+                return INFUR_OK;
+            });
+    });
 }
 
 }  // extern "C"

@@ -9,30 +9,13 @@
 #include <hip/hip_runtime.h>
 
 #include <cstring>
-#include <exception>
-#include <new>
 #include <string>
 #include <vector>
 
 #include "infur_ctx.h"
+#include "infur_rt.h"
 
 using namespace infur;
-
-#define fail ctx_fail
-#define HIPCHK(c, expr)                                                                         \
-    do {                                                                                        \
-        hipError_t e__ = (expr);                                                                \
-        if (e__ != hipSuccess)                                                                  \
-            return ctx_fail((c), INFUR_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), \
-                            __FILE__, __LINE__);                                                \
-    } while (0)
-#define RETIF(expr)                 \
-    do {                            \
-        int32_t rc__ = (expr);      \
-        if (rc__ != INFUR_OK) return rc__; \
-    } while (0)
-static inline void enter(const infur_ctx* c) { ctx_enter(c); }
-
 
 struct infur_stream {
     struct Slot {
@@ -132,8 +115,7 @@ void infur::stream_orphan(infur_stream* st) {
 extern "C" {
 
 int32_t infur_stream_create(infur_ctx* c, uint32_t depth, infur_stream** out) {
-    try {
-        enter(c);
+    return abi_call(c, [&]() -> int32_t {
         if (!c || !out || depth == 0 || depth > 64) return INFUR_E_INVALID_ARG;
         *out = nullptr;
         infur_stream* st = new infur_stream();
@@ -153,11 +135,7 @@ int32_t infur_stream_create(infur_ctx* c, uint32_t depth, infur_stream** out) {
         }
         *out = st;
         return INFUR_OK;
-    } catch (const std::bad_alloc&) {
-        return fail(c, INFUR_E_CAPACITY, "out of host memory");
-    } catch (const std::exception& e) {
-        return fail(c, INFUR_E_INVALID_ARG, "internal error: %s", e.what());
-    }
+    });
 }
 
 void infur_stream_destroy(infur_stream* st) {
@@ -170,22 +148,24 @@ uint32_t infur_stream_pending(const infur_stream* st) { return st ? (uint32_t)(s
 
 int32_t infur_stream_add_lane(infur_stream* st, infur_ctx* other) {
     if (!st || !st->ctx || !other) return INFUR_E_INVALID_ARG;
-    infur_ctx* c = st->ctx;
-    if (other->device != c->device) return fail(c, INFUR_E_INVALID_ARG, "a lane must be a context of the stream's device (%d), got device %d", c->device, other->device);
-    for (infur_ctx* l : st->lanes)
-        if (l == other) return fail(c, INFUR_E_INVALID_ARG, "that context already is a lane of this stream");
-    if (st->head != st->tail) return fail(c, INFUR_E_INVALID_ARG, "add lanes while no frame is pending");
-    // odd and even frames must run the SAME arithmetic: the option set infur_group_weights_broadcast checks (the fusion
-    // switches are bit-identical forms and may differ; F(4x4) and F(6x6) logits differ by ~1e-6, enough to flip a tie)
-    if (other->opt.compute_dtype != c->opt.compute_dtype || other->opt.winograd_tile != c->opt.winograd_tile ||
-        other->opt.winograd_min_cin != c->opt.winograd_min_cin || other->opt.compute_aux != c->opt.compute_aux)
-        return fail(c, INFUR_E_INVALID_ARG, "a lane must share the stream's compute_dtype / winograd_tile / winograd_min_cin / compute_aux: its frames would otherwise differ");
-    if (!other->loaded) return fail(c, INFUR_E_MODEL_NOT_LOADED, "the lane's context has no model loaded (replicate it first: infur_group_weights_broadcast)");
-    if (c->loaded && other->quant != c->quant)
-        return fail(c, INFUR_E_INVALID_ARG, "a lane must hold the stream's model: one of the two contexts has a quantised model, the other a float one");
-    st->lanes.push_back(other);
-    other->streams.push_back(st);
-    return INFUR_OK;
+    return abi_call(st->ctx, [&]() -> int32_t {
+        infur_ctx* c = st->ctx;
+        if (other->device != c->device) return fail(c, INFUR_E_INVALID_ARG, "a lane must be a context of the stream's device (%d), got device %d", c->device, other->device);
+        for (infur_ctx* l : st->lanes)
+            if (l == other) return fail(c, INFUR_E_INVALID_ARG, "that context already is a lane of this stream");
+        if (st->head != st->tail) return fail(c, INFUR_E_INVALID_ARG, "add lanes while no frame is pending");
+        // odd and even frames must run the SAME arithmetic: the option set infur_group_weights_broadcast checks (the fusion
+        // switches are bit-identical forms and may differ; F(4x4) and F(6x6) logits differ by ~1e-6, enough to flip a tie)
+        if (other->opt.compute_dtype != c->opt.compute_dtype || other->opt.winograd_tile != c->opt.winograd_tile ||
+            other->opt.winograd_min_cin != c->opt.winograd_min_cin || other->opt.compute_aux != c->opt.compute_aux)
+            return fail(c, INFUR_E_INVALID_ARG, "a lane must share the stream's compute_dtype / winograd_tile / winograd_min_cin / compute_aux: its frames would otherwise differ");
+        if (!other->loaded) return fail(c, INFUR_E_MODEL_NOT_LOADED, "the lane's context has no model loaded (replicate it first: infur_group_weights_broadcast)");
+        if (c->loaded && other->quant != c->quant)
+            return fail(c, INFUR_E_INVALID_ARG, "a lane must hold the stream's model: one of the two contexts has a quantised model, the other a float one");
+        st->lanes.push_back(other);
+        other->streams.push_back(st);
+        return INFUR_OK;
+    });
 }
 
 namespace {
@@ -209,11 +189,8 @@ bool host_is_pinned(const void* p) {
 // checks + slot reservation shared by submit and acquire: the slot at `head`, sized for a w x h frame scaled by `factor`
 int32_t stream_prepare(infur_stream* st, uint32_t w, uint32_t h, float factor, infur_stream::Slot** slot, uint32_t* ow_out, uint32_t* oh_out) {
     infur_ctx* c = st->ctx;
-    int32_t rc = infur_scale_validate(factor);
-    if (rc) return fail(c, rc, "%s", infur_status_string(rc));
     uint32_t ow = 0, oh = 0;
-    rc = infur_scale_out_dims(w, h, factor, &ow, &oh);
-    if (rc) return fail(c, rc, "%s", infur_status_string(rc));
+    RETIF(scale_dims(c, w, h, factor, &ow, &oh));
     infur_ctx* lane = st->lanes[st->head % st->lanes.size()];
     if (!lane->loaded) return fail(c, INFUR_E_MODEL_NOT_LOADED, "no model loaded");
     // (a model may have been (re)loaded on one context after the lane was added: both kinds of arithmetic in one stream would
@@ -292,7 +269,6 @@ int32_t stream_enqueue(infur_stream* st, infur_stream::Slot& sl, const uint8_t* 
 int32_t stream_submit_impl(infur_stream* st, const uint8_t* bgr, uint32_t w, uint32_t h, float factor, uint32_t mode, uint64_t frame_id,
                            bool pinned_src, uint8_t* direct_out) {
     if (!st || !st->ctx || !bgr) return INFUR_E_INVALID_ARG;  // (a stream whose context was destroyed is dead)
-    enter(st->ctx);
     if (st->acquired) return fail(st->ctx, INFUR_E_INVALID_ARG, "a slot is acquired: commit it before submitting another frame");
     infur_stream::Slot* sl = nullptr;
     uint32_t ow = 0, oh = 0;
@@ -304,20 +280,16 @@ int32_t stream_submit_impl(infur_stream* st, const uint8_t* bgr, uint32_t w, uin
 
 int32_t infur_stream_submit(infur_stream* st, const uint8_t* bgr, uint32_t w, uint32_t h, float factor, uint32_t mode,
                             uint64_t frame_id) {
-    try {
+    if (!st || !st->ctx || !bgr) return INFUR_E_INVALID_ARG;
+    return abi_call(st->ctx, [&]() -> int32_t {
         return stream_submit_impl(st, bgr, w, h, factor, mode, frame_id, false, nullptr);
-    } catch (const std::bad_alloc&) {
-        return fail(st ? st->ctx : nullptr, INFUR_E_CAPACITY, "out of host memory");
-    } catch (const std::exception& e) {
-        return fail(st ? st->ctx : nullptr, INFUR_E_INVALID_ARG, "internal error: %s", e.what());
-    }
+    });
 }
 
 // ---- zero-copy ingest: the producer fills the ring's own pinned slot (ff-video/src/decoder.rs:156-165 reads into a reused BgrImage) ----
 int32_t infur_stream_acquire(infur_stream* st, uint32_t w, uint32_t h, float factor, uint8_t** bgr_slot) {
-    try {
-        if (!st || !st->ctx || !bgr_slot) return INFUR_E_INVALID_ARG;
-        enter(st->ctx);
+    if (!st || !st->ctx || !bgr_slot) return INFUR_E_INVALID_ARG;
+    return abi_call(st->ctx, [&]() -> int32_t {
         *bgr_slot = nullptr;
         // an earlier acquire is void from here on: if the re-size below fails (slot_reserve frees before it allocates) the slot has
         // no buffers, and a commit against the old dimensions must not find `acquired` still set
@@ -333,17 +305,12 @@ int32_t infur_stream_acquire(infur_stream* st, uint32_t w, uint32_t h, float fac
         st->acq_factor_bits = f32_bits(factor);
         *bgr_slot = sl->h_in;
         return INFUR_OK;
-    } catch (const std::bad_alloc&) {
-        return fail(st ? st->ctx : nullptr, INFUR_E_CAPACITY, "out of host memory");
-    } catch (const std::exception& e) {
-        return fail(st ? st->ctx : nullptr, INFUR_E_INVALID_ARG, "internal error: %s", e.what());
-    }
+    });
 }
 
 int32_t infur_stream_commit(infur_stream* st, uint32_t w, uint32_t h, float factor, uint32_t mode, uint64_t frame_id) {
-    try {
-        if (!st || !st->ctx) return INFUR_E_INVALID_ARG;
-        enter(st->ctx);
+    if (!st || !st->ctx) return INFUR_E_INVALID_ARG;
+    return abi_call(st->ctx, [&]() -> int32_t {
         infur_ctx* c = st->ctx;
         if (!st->acquired) return fail(c, INFUR_E_INVALID_ARG, "no slot is acquired");
         if (w != st->acq_w || h != st->acq_h || f32_bits(factor) != st->acq_factor_bits)
@@ -356,11 +323,7 @@ int32_t infur_stream_commit(infur_stream* st, uint32_t w, uint32_t h, float fact
         infur_stream::Slot& sl = st->slots[st->head % st->slots.size()];
         if (!sl.h_in || !sl.d_in) return fail(c, INFUR_E_INVALID_ARG, "the acquired slot has no buffers");
         return stream_enqueue(st, sl, sl.h_in, w, h, factor, mode, frame_id, st->acq_ow, st->acq_oh, nullptr);
-    } catch (const std::bad_alloc&) {
-        return fail(st ? st->ctx : nullptr, INFUR_E_CAPACITY, "out of host memory");
-    } catch (const std::exception& e) {
-        return fail(st ? st->ctx : nullptr, INFUR_E_INVALID_ARG, "internal error: %s", e.what());
-    }
+    });
 }
 
 // the producer found no frame to put into the slot it acquired (end of input, read error): give it back uncommitted
@@ -383,54 +346,58 @@ int32_t infur_stream_next_dims(const infur_stream* st, uint64_t* frame_id, uint3
 int32_t infur_stream_collect(infur_stream* st, uint8_t* rgba, size_t cap, uint8_t* scaled, uint64_t* frame_id,
                              uint32_t* ow, uint32_t* oh) {
     if (!st || !st->ctx) return INFUR_E_INVALID_ARG;
-    enter(st->ctx);
-    infur_ctx* c = st->ctx;
-    if (st->head == st->tail) return fail(c, INFUR_E_INVALID_ARG, "no frame is pending");
-    infur_stream::Slot& sl = st->slots[st->tail % st->slots.size()];
-    const size_t rgba_bytes = (size_t)sl.ow * sl.oh * 4, sc_bytes = (size_t)sl.ow * sl.oh * 3;
-    if (rgba && cap < rgba_bytes) return fail(c, INFUR_E_CAPACITY, "mask needs %zu bytes, buffer has %zu", rgba_bytes, cap);
-    if (scaled && sl.direct_out) return fail(c, INFUR_E_INVALID_ARG, "this frame's mask went straight to a caller-owned buffer: the scaled frame was not kept");
-    HIPCHK(c, hipEventSynchronize(sl.ev_done));
-    if (rgba && rgba != sl.direct_out) memcpy(rgba, sl.direct_out ? sl.direct_out : sl.h_out, rgba_bytes);
-    if (scaled) memcpy(scaled, sl.h_out + rgba_bytes, sc_bytes);
-    if (frame_id) *frame_id = sl.id;
-    if (ow) *ow = sl.ow;
-    if (oh) *oh = sl.oh;
-    sl.busy = false;
-    sl.direct_out = nullptr;
-    st->viewing = false;
-    st->tail++;
-    return INFUR_OK;
+    return abi_call(st->ctx, [&]() -> int32_t {
+        infur_ctx* c = st->ctx;
+        if (st->head == st->tail) return fail(c, INFUR_E_INVALID_ARG, "no frame is pending");
+        infur_stream::Slot& sl = st->slots[st->tail % st->slots.size()];
+        const size_t rgba_bytes = (size_t)sl.ow * sl.oh * 4, sc_bytes = (size_t)sl.ow * sl.oh * 3;
+        if (rgba && cap < rgba_bytes) return fail(c, INFUR_E_CAPACITY, "mask needs %zu bytes, buffer has %zu", rgba_bytes, cap);
+        if (scaled && sl.direct_out) return fail(c, INFUR_E_INVALID_ARG, "this frame's mask went straight to a caller-owned buffer: the scaled frame was not kept");
+        HIPCHK(c, hipEventSynchronize(sl.ev_done));
+        if (rgba && rgba != sl.direct_out) memcpy(rgba, sl.direct_out ? sl.direct_out : sl.h_out, rgba_bytes);
+        if (scaled) memcpy(scaled, sl.h_out + rgba_bytes, sc_bytes);
+        if (frame_id) *frame_id = sl.id;
+        if (ow) *ow = sl.ow;
+        if (oh) *oh = sl.oh;
+        sl.busy = false;
+        sl.direct_out = nullptr;
+        st->viewing = false;
+        st->tail++;
+        return INFUR_OK;
+    });
 }
 
 // ---- zero-copy egress: the oldest finished frame's mask (and scaled frame) in place, in the ring's pinned slot ----
 int32_t infur_stream_collect_view(infur_stream* st, const uint8_t** rgba, const uint8_t** scaled, uint64_t* frame_id, uint32_t* ow, uint32_t* oh) {
     if (!st || !st->ctx) return INFUR_E_INVALID_ARG;
-    enter(st->ctx);
-    infur_ctx* c = st->ctx;
-    if (st->head == st->tail) return fail(c, INFUR_E_INVALID_ARG, "no frame is pending");
-    infur_stream::Slot& sl = st->slots[st->tail % st->slots.size()];
-    HIPCHK(c, hipEventSynchronize(sl.ev_done));
-    const size_t rgba_bytes = (size_t)sl.ow * sl.oh * 4;
-    if (rgba) *rgba = sl.direct_out ? sl.direct_out : sl.h_out;
-    if (scaled) *scaled = sl.direct_out ? nullptr : sl.h_out + rgba_bytes;
-    if (frame_id) *frame_id = sl.id;
-    if (ow) *ow = sl.ow;
-    if (oh) *oh = sl.oh;
-    st->viewing = true;  // the slot stays the consumer's until infur_stream_release (or a copying collect of the same frame)
-    return INFUR_OK;
+    return abi_call(st->ctx, [&]() -> int32_t {
+        infur_ctx* c = st->ctx;
+        if (st->head == st->tail) return fail(c, INFUR_E_INVALID_ARG, "no frame is pending");
+        infur_stream::Slot& sl = st->slots[st->tail % st->slots.size()];
+        HIPCHK(c, hipEventSynchronize(sl.ev_done));
+        const size_t rgba_bytes = (size_t)sl.ow * sl.oh * 4;
+        if (rgba) *rgba = sl.direct_out ? sl.direct_out : sl.h_out;
+        if (scaled) *scaled = sl.direct_out ? nullptr : sl.h_out + rgba_bytes;
+        if (frame_id) *frame_id = sl.id;
+        if (ow) *ow = sl.ow;
+        if (oh) *oh = sl.oh;
+        st->viewing = true;  // the slot stays the consumer's until infur_stream_release (or a copying collect of the same frame)
+        return INFUR_OK;
+    });
 }
 
 int32_t infur_stream_release(infur_stream* st) {
     if (!st || !st->ctx) return INFUR_E_INVALID_ARG;
-    infur_ctx* c = st->ctx;
-    if (!st->viewing || st->head == st->tail) return fail(c, INFUR_E_INVALID_ARG, "no frame is being viewed");
-    infur_stream::Slot& sl = st->slots[st->tail % st->slots.size()];
-    sl.busy = false;
-    sl.direct_out = nullptr;
-    st->viewing = false;
-    st->tail++;
-    return INFUR_OK;
+    return abi_call(st->ctx, [&]() -> int32_t {
+        infur_ctx* c = st->ctx;
+        if (!st->viewing || st->head == st->tail) return fail(c, INFUR_E_INVALID_ARG, "no frame is being viewed");
+        infur_stream::Slot& sl = st->slots[st->tail % st->slots.size()];
+        sl.busy = false;
+        sl.direct_out = nullptr;
+        st->viewing = false;
+        st->tail++;
+        return INFUR_OK;
+    });
 }
 
 // ---- pinned host memory for the caller's own frame / mask buffers: the batch calls move such buffers by DMA, without the
@@ -453,8 +420,7 @@ uint32_t infur_host_is_pinned(const void* p) { return host_is_pinned(p) ? 1u : 0
 int32_t infur_batch_advance(infur_ctx* c, const uint8_t* const* frames, const uint32_t* ws, const uint32_t* hs, uint32_t n,
                             float factor, uint32_t mode, uint8_t* const* rgba, const size_t* caps, uint32_t* ows,
                             uint32_t* ohs) {
-    try {
-        enter(c);
+    return abi_call(c, [&]() -> int32_t {
         if (!c || (n && (!frames || !ws || !hs || !rgba || !caps))) return INFUR_E_INVALID_ARG;
         if (n == 0) return INFUR_OK;
         // The depth-3 ring lives as long as the context (6 pinned + device buffer pairs, 2 streams, 9 events: building it
@@ -497,11 +463,7 @@ int32_t infur_batch_advance(infur_ctx* c, const uint8_t* const* frames, const ui
             c->err = keep;
         }
         return rc;
-    } catch (const std::bad_alloc&) {
-        return fail(c, INFUR_E_CAPACITY, "out of host memory");
-    } catch (const std::exception& e) {
-        return fail(c, INFUR_E_INVALID_ARG, "internal error: %s", e.what());
-    }
+    });
 }
 
 }  // extern "C"

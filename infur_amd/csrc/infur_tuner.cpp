@@ -92,14 +92,11 @@ int32_t pick_cfg(infur_ctx* c, const ConvArgs& a, int mode, int out_f32, int* cf
 
 }  // namespace infur
 
-static inline void enter(const infur_ctx* c) { ctx_enter(c); }
-
 extern "C" {
 
 // ---- tuning database ----
 int32_t infur_tune_export(infur_ctx* c, char* buf, size_t cap, size_t* len) {
-    try {
-        enter(c);
+    return abi_call(c, [&]() -> int32_t {
         if (!c || !len) return INFUR_E_INVALID_ARG;
         std::string out;
         char line[256];
@@ -114,16 +111,11 @@ int32_t infur_tune_export(infur_ctx* c, char* buf, size_t cap, size_t* len) {
         if (cap < out.size()) return fail(c, INFUR_E_CAPACITY, "tuning text needs %zu bytes", out.size());
         memcpy(buf, out.data(), out.size());
         return INFUR_OK;
-    } catch (const std::bad_alloc&) {
-        return fail(c, INFUR_E_CAPACITY, "out of host memory");
-    } catch (const std::exception& e) {
-        return fail(c, INFUR_E_INVALID_ARG, "internal error: %s", e.what());
-    }
+    });
 }
 
 int32_t infur_tune_import(infur_ctx* c, const char* text, size_t len) {
-    try {
-        enter(c);
+    return abi_call(c, [&]() -> int32_t {
         if (!c || (!text && len)) return INFUR_E_INVALID_ARG;
         std::string t(text ? text : "", len);
         size_t pos = 0;
@@ -146,11 +138,7 @@ int32_t infur_tune_import(infur_ctx* c, const char* text, size_t len) {
             c->mem_gen++;
         }
         return INFUR_OK;
-    } catch (const std::bad_alloc&) {
-        return fail(c, INFUR_E_CAPACITY, "out of host memory");
-    } catch (const std::exception& e) {
-        return fail(c, INFUR_E_INVALID_ARG, "internal error: %s", e.what());
-    }
+    });
 }
 
 }  // extern "C"

@@ -483,17 +483,6 @@ __global__ void __launch_bounds__(256)
     }
 }
 
-// NQ = ceil(K / 4) -> the instantiation (K <= UP_KP = 24 is checked by up_tile_lds_bytes)
-#define UP_DISPATCH_NQ(KERNEL, K, ...)                                              \
-    switch (((K) + 3) / 4) {                                                        \
-        case 1: hipLaunchKernelGGL(KERNEL<1>, __VA_ARGS__); break;                  \
-        case 2: hipLaunchKernelGGL(KERNEL<2>, __VA_ARGS__); break;                  \
-        case 3: hipLaunchKernelGGL(KERNEL<3>, __VA_ARGS__); break;                  \
-        case 4: hipLaunchKernelGGL(KERNEL<4>, __VA_ARGS__); break;                  \
-        case 5: hipLaunchKernelGGL(KERNEL<5>, __VA_ARGS__); break;                  \
-        default: hipLaunchKernelGGL(KERNEL<6>, __VA_ARGS__); break;                 \
-    }
-
 // LDS bytes of the staged rectangle for this geometry, or 0 when the scalar fallback must run (more classes than
 // the padded pixel slot holds, or a ratio whose footprint is too big to be worth staging)
 static size_t up_tile_lds_bytes(int LH, int LW, int K, int OH, int OW) {
@@ -504,17 +493,28 @@ static size_t up_tile_lds_bytes(int LH, int LW, int K, int OH, int OW) {
     return bytes <= 48 * 1024 ? bytes : 0;
 }
 
+// The launch of an up-sampling kernel pair, written once for the three launchers (LH, LW, K, OH, OW and s are theirs): the
+// staged kernel's NQ = ceil(K / 4) instantiation on the tile grid where the footprint fits (K <= UP_KP = 24 is checked by
+// up_tile_lds_bytes), else the scalar kernel on its 64 x 4 grid
+#define UP_LAUNCH(STAGED, SCALAR, ...)                                                                           \
+    do {                                                                                                         \
+        const size_t lds = up_tile_lds_bytes(LH, LW, K, OH, OW);                                                 \
+        const dim3 tiles((OW + UP_TW - 1) / UP_TW, (OH + UP_TH - 1) / UP_TH), rows((OW + 63) / 64, (OH + 3) / 4); \
+        switch (lds ? (K + 3) / 4 : 0) {                                                                         \
+            case 0: hipLaunchKernelGGL(SCALAR, rows, dim3(256), 0, s, __VA_ARGS__); break;                       \
+            case 1: hipLaunchKernelGGL(STAGED<1>, tiles, dim3(256), lds, s, __VA_ARGS__); break;                 \
+            case 2: hipLaunchKernelGGL(STAGED<2>, tiles, dim3(256), lds, s, __VA_ARGS__); break;                 \
+            case 3: hipLaunchKernelGGL(STAGED<3>, tiles, dim3(256), lds, s, __VA_ARGS__); break;                 \
+            case 4: hipLaunchKernelGGL(STAGED<4>, tiles, dim3(256), lds, s, __VA_ARGS__); break;                 \
+            case 5: hipLaunchKernelGGL(STAGED<5>, tiles, dim3(256), lds, s, __VA_ARGS__); break;                 \
+            default: hipLaunchKernelGGL(STAGED<6>, tiles, dim3(256), lds, s, __VA_ARGS__); break;                \
+        }                                                                                                        \
+        return hipGetLastError();                                                                                \
+    } while (0)
+
 hipError_t launch_upsample_planar(const float* low, int LH, int LW, int K, float* out, int OH,
                                   int OW, hipStream_t s, const UpQuant uq) {
-    const size_t lds = up_tile_lds_bytes(LH, LW, K, OH, OW);
-    if (lds) {
-        dim3 grid((OW + UP_TW - 1) / UP_TW, (OH + UP_TH - 1) / UP_TH);
-        UP_DISPATCH_NQ(upsample_planar_lds_kernel, K, grid, dim3(256), lds, s, low, LH, LW, K, out, OH, OW, uq)
-    } else {
-        dim3 grid((OW + 63) / 64, (OH + 3) / 4);
-        hipLaunchKernelGGL(upsample_planar_kernel, grid, dim3(256), 0, s, low, LH, LW, K, out, OH, OW, uq);
-    }
-    return hipGetLastError();
+    UP_LAUNCH(upsample_planar_lds_kernel, upsample_planar_kernel, low, LH, LW, K, out, OH, OW, uq);
 }
 
 // fused up-sample + argmax + shade, scalar form: same expression tree as upsample_planar -> colorcode
@@ -543,15 +543,7 @@ __global__ void __launch_bounds__(256)
 
 hipError_t launch_upsample_argmax_shade(const float* low, int LH, int LW, int K, const uint32_t* lut,
                                         uint32_t* rgba, int OH, int OW, hipStream_t s, const UpQuant uq) {
-    const size_t lds = up_tile_lds_bytes(LH, LW, K, OH, OW);
-    if (lds) {
-        dim3 grid((OW + UP_TW - 1) / UP_TW, (OH + UP_TH - 1) / UP_TH);
-        UP_DISPATCH_NQ(upsample_argmax_shade_lds_kernel, K, grid, dim3(256), lds, s, low, LH, LW, K, lut, rgba, OH, OW, uq)
-    } else {
-        dim3 grid((OW + 63) / 64, (OH + 3) / 4);
-        hipLaunchKernelGGL(upsample_argmax_shade_kernel, grid, dim3(256), 0, s, low, LH, LW, K, lut, rgba, OH, OW, uq);
-    }
-    return hipGetLastError();
+    UP_LAUNCH(upsample_argmax_shade_lds_kernel, upsample_argmax_shade_kernel, low, LH, LW, K, lut, rgba, OH, OW, uq);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -835,15 +827,7 @@ __global__ void __launch_bounds__(256)
 
 hipError_t launch_upsample_argmax_segments(const float* low, int LH, int LW, int K, int softmax, const uint32_t* lut,
                                            const SegOut& o, int OH, int OW, hipStream_t s, const UpQuant uq) {
-    const size_t lds = up_tile_lds_bytes(LH, LW, K, OH, OW);
-    if (lds) {
-        dim3 grid((OW + UP_TW - 1) / UP_TW, (OH + UP_TH - 1) / UP_TH);
-        UP_DISPATCH_NQ(upsample_argmax_segments_lds_kernel, K, grid, dim3(256), lds, s, low, LH, LW, K, softmax, lut, o, OH, OW, uq)
-    } else {
-        dim3 grid((OW + 63) / 64, (OH + 3) / 4);
-        hipLaunchKernelGGL(upsample_argmax_segments_kernel, grid, dim3(256), 0, s, low, LH, LW, K, softmax, lut, o, OH, OW, uq);
-    }
-    return hipGetLastError();
+    UP_LAUNCH(upsample_argmax_segments_lds_kernel, upsample_argmax_segments_kernel, low, LH, LW, K, softmax, lut, o, OH, OW, uq);
 }
 
 }  // namespace infur
