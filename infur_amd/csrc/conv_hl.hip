@@ -830,11 +830,13 @@ static hipError_t launch_hl_p(const ConvArgs& a, int out_f32, hipStream_t s) {
     if (out_f32 && !a.in2) return g1 ? launch_hl_g<BM, BN, WM, WN, true, true, false, NIMG, PIPE>(a, s) : launch_hl_g<BM, BN, WM, WN, false, true, false, NIMG, PIPE>(a, s);
     return a.hl_mon ? launch_hl_o<BM, BN, WM, WN, NIMG, PIPE, true>(a, s) : launch_hl_o<BM, BN, WM, WN, NIMG, PIPE, false>(a, s);
 }
-// INFUR_HL_PIPE=0: the plain K loop (measurement / bisection hook; both loops are bit-identical)
+// INFUR_HL_PIPE=0: the plain K loop (measurement / bisection hook; both loops are bit-identical: tests/test_gpu_forms.py runs every
+// form with both, per layer and on the fused frame path, and tells them apart by the ",plain" the profile's kernel name then ends in)
 static bool hl_pipe_on() {
     static const bool on = !(getenv("INFUR_HL_PIPE") && atoi(getenv("INFUR_HL_PIPE")) == 0);
     return on;
 }
+bool conv_hl_pipe_on() { return hl_pipe_on(); }
 template <int BM, int BN, int WM, int WN, int NIMG = 3>
 static hipError_t launch_hl_t(const ConvArgs& a, int out_f32, hipStream_t s) {
     return hl_pipe_on() ? launch_hl_p<BM, BN, WM, WN, NIMG, true>(a, out_f32, s) : launch_hl_p<BM, BN, WM, WN, NIMG, false>(a, out_f32, s);

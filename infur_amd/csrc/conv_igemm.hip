@@ -112,16 +112,18 @@ int conv_igemm_config_tile_area(int cfg) { return cfg < 0 || cfg >= kNumCfgs ? 0
 
 const char* conv_igemm_config_name(int cfg, int mode) {
     if (mode == 5) {  // the three-byte mode's own kernel (conv_hl.hip) on the tile shapes of these four entries
+        // INFUR_HL_PIPE=0: the tiled forms run their plain K loop and say so (conv_hl_areg.hip has one loop only)
+        const bool plain = !conv_hl_pipe_on();
         switch (cfg) {
-            case 11: return "conv_hl<256,256>";
-            case 0: return "conv_hl<128,128>";
-            case 6: return "conv_hl<256,128>";
-            case 5: return "conv_hl<128,256>";
-            case 12: return "conv_hl<256,128,4w>";
-            case 14: return "conv_hl<128,256,4w>";
-            case 13: return "conv_hl<256,256,wn2>";
-            case 16: return "conv_hl<128,256,4w,wn2>";
-            case 17: return "conv_hl<256,128,4w,wn2>";
+            case 11: return plain ? "conv_hl<256,256>,plain" : "conv_hl<256,256>";
+            case 0: return plain ? "conv_hl<128,128>,plain" : "conv_hl<128,128>";
+            case 6: return plain ? "conv_hl<256,128>,plain" : "conv_hl<256,128>";
+            case 5: return plain ? "conv_hl<128,256>,plain" : "conv_hl<128,256>";
+            case 12: return plain ? "conv_hl<256,128,4w>,plain" : "conv_hl<256,128,4w>";
+            case 14: return plain ? "conv_hl<128,256,4w>,plain" : "conv_hl<128,256,4w>";
+            case 13: return plain ? "conv_hl<256,256,wn2>,plain" : "conv_hl<256,256,wn2>";
+            case 16: return plain ? "conv_hl<128,256,4w,wn2>,plain" : "conv_hl<128,256,4w,wn2>";
+            case 17: return plain ? "conv_hl<256,128,4w,wn2>,plain" : "conv_hl<256,128,4w,wn2>";
             case 15: return "conv_hl<128,areg>";
             default: return "conv_hl<?>";
         }

@@ -1,7 +1,7 @@
 // infur_tuner.cpp -- which tile configuration of the conv kernels runs a layer shape: measured on first use (pick_cfg), kept per
 // context, pre-loadable from / exportable to text (infur_tune_import / _export; infur_amd/conv_tune_gfx950.txt holds the decisions
-// for the BASELINE shapes).  Every configuration of a mode gives bit-identical results (tests/test_gpu_conv_configs.py,
-// test_gpu_hl.py), so the choice is a speed knob only.  Split out of infur_capi.cpp in round 5.
+// for the BASELINE shapes).  Every configuration of a mode gives bit-identical results (tests/test_gpu_forms.py,
+// test_gpu_conv_configs.py, test_gpu_hl.py), so the choice is a speed knob only.  Split out of infur_capi.cpp in round 5.
 #include "../../include/infur_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -28,7 +28,9 @@ namespace infur {
 int32_t pick_cfg(infur_ctx* c, const ConvArgs& a, int mode, int out_f32, int* cfg) {
     *cfg = conv_igemm_default_config(a);
     if (mode == 5 && !conv_igemm_config_valid(a, *cfg, mode, out_f32)) *cfg = 0;  // (128 x 128: valid for every mode-5 shape)
-    // test hook: INFUR_CONV_CFG=<k> forces configuration k wherever it is a candidate
+    // test hook: INFUR_CONV_CFG=<k> forces configuration k wherever it is a candidate.  A forced configuration that is NOT a
+    // candidate for the shape falls back to the default silently; tests/test_gpu_forms.py is what checks, from the profile's kernel
+    // names, that the forced form really ran.
     static const int forced = getenv("INFUR_CONV_CFG") ? atoi(getenv("INFUR_CONV_CFG")) : -1;
     if (forced >= 0) {
         if (conv_igemm_config_valid(a, forced, mode, out_f32)) *cfg = forced;

@@ -86,6 +86,7 @@ const char* conv_igemm_config_name(int cfg, int mode);
 // mode 5 (conv_hl.hip)
 bool conv_hl_config_valid(const ConvArgs& a, int cfg, int out_f32);
 hipError_t launch_conv_hl(const ConvArgs& a, int out_f32, int cfg, hipStream_t s);
+bool conv_hl_pipe_on();  // false under INFUR_HL_PIPE=0 (the plain K loop): conv_igemm_config_name then ends the tiled forms' names in ",plain"
 // configuration 15 of mode 5 (conv_hl_areg.hip): 1x1 expansions (Cin 64 / 128 / 256, Cout a multiple of 128) with the activation
 // fragment in registers, weights and residual streamed by LDS-DMA; bit-identical to the tiled forms
 bool conv_hl_areg_valid(const ConvArgs& a, int out_f32);
