@@ -380,6 +380,108 @@ int32_t infur_frame_regions_dev(infur_ctx* ctx, const void* d_bgr, uint32_t w, u
                                 size_t labels_capacity, void* d_table, uint32_t table_rows, void* d_n_regions,
                                 void* d_scaled_bgr, uint32_t* ow, uint32_t* oh);
 
+/* ---- Tracks: region identities carried from frame to frame ----
+ * Regions is stateless: ids are the raster order of each region's first pixel, so the same object is row 3 in one frame and
+ * row 5 in the next.  Tracks is the fourth decode stage: a TRACKER remembers the last frame it saw (its label plane and, per
+ * region, class, track id, age, birth frame and the PIXELS / SUM_X / SUM_Y words) and gives every region of the next frame
+ * either the id of the remembered region it overlaps most, or a new one.  Presence of this group is announced by
+ * infur_features() & INFUR_FEATURE_TRACKS (INFUR_ABI_VERSION does not move).  Integers throughout: identical bytes from run
+ * to run and from device to device.
+ *
+ * A tracker is bound to one context and is used, like it, from one thread at a time.  Its handle is an untyped pointer
+ * (void*) in this header.  Destroying the context first leaves the tracker an empty handle (every call on it returns
+ * INFUR_E_INVALID_ARG) that must still be passed to infur_tracker_destroy.
+ *
+ * One step takes the Regions outputs of the current h x w frame: labels, table (table_rows rows) and n_regions.
+ *   tracked     current regions with id < T = min(n_regions, table_rows, max_regions); every other region gets
+ *               INFUR_TRACK_NONE and the status bit INFUR_TRACKS_TRUNCATED is set
+ *   overlap     overlap(c, p) = the number of pixels whose current label c and remembered label p are both tracked (p in
+ *               the remembered frame's sense); (c, p) is a candidate iff the two regions have the same class and
+ *               overlap >= max(min_overlap, 1)
+ *   match       1. each c chooses the candidate p of largest overlap (ties: the smaller p);  2. each p is kept by the chooser
+ *               c of largest overlap (ties: the smaller c);  3. a kept c inherits p's track id and birth frame, AGE =
+ *               age(p) + 1;  4. every other tracked c starts a new track, AGE = 1.  A loser of step 2 does not fall back to a
+ *               second choice: a split keeps the id on the larger part, a merge the id of the larger contributor
+ *   new ids     next_id + rank, rank counting the new tracks in ascending region id; next_id then advances by their number.
+ *               If next_id + new > 0xFFFFFFFE the step sets INFUR_TRACKS_IDS_EXHAUSTED, gives INFUR_TRACK_NONE to every
+ *               region (rows as for untracked regions; CONTINUED = NEW = 0), leaves next_id alone and forgets the frame
+ *   resets      on the first frame, after infur_tracker_reset, after an exhausted step, or when h or w differs from the
+ *               remembered frame, every tracked region is new (and ENDED = 0).  Ids keep counting; the frame counter counts
+ *               every step since the tracker was created.  There is no memory beyond one frame
+ *   overflow    the pair table has pair_slots slots.  R = the number of runs of equal tracked (c, p) along rows, rows cut
+ *               every 64 columns: a function of the two planes alone that bounds the number of distinct pairs.  If
+ *               2 R > pair_slots the step sets INFUR_TRACKS_OVERFLOW and every tracked region is new; it still remembers
+ *               its frame, so the next step tracks normally
+ * Outputs, each optional (NULL = not wanted; all NULL is INFUR_E_INVALID_ARG), none needs initialisation:
+ *   track_of_region  table_rows uint32_t; rows at or beyond min(n_regions, table_rows) are left alone
+ *   track_plane      h*w uint32_t: each pixel's label mapped through track_of_region (untracked and INFUR_REGION_NONE:
+ *                    INFUR_TRACK_NONE)
+ *   track_table      table_rows rows of INFUR_TRACK_WORDS uint64_t, the same rows left alone: ID, AGE (frames this track has
+ *                    been seen), BORN (the frame counter when it began), PREV_REGION (its region id in the remembered frame,
+ *                    or INFUR_REGION_NONE), OVERLAP with that region, and that region's PIXELS, SUM_X, SUM_Y (0 for a new
+ *                    track): a centroid step is one subtraction on the host.  An untracked region reads ID =
+ *                    INFUR_TRACK_NONE, PREV_REGION = INFUR_REGION_NONE and 0 elsewhere
+ *   summary          four uint32_t: STATUS (INFUR_TRACKS_* bits), CONTINUED, NEW, ENDED (remembered tracked regions that
+ *                    no current region inherits)
+ * h*w == 0 writes the summary (all zero) and forgets the frame.  A null or orphaned tracker, a null labels / table /
+ * n_regions input on a non-empty frame and h*w >= 2^32 - 1 are INFUR_E_INVALID_ARG with no output touched. */
+#define INFUR_TRACK_NONE 0xFFFFFFFFu
+enum {
+    INFUR_TRACK_ID = 0,
+    INFUR_TRACK_AGE = 1,
+    INFUR_TRACK_BORN = 2,
+    INFUR_TRACK_PREV_REGION = 3,
+    INFUR_TRACK_OVERLAP = 4,
+    INFUR_TRACK_PREV_PIXELS = 5,
+    INFUR_TRACK_PREV_SUM_X = 6,
+    INFUR_TRACK_PREV_SUM_Y = 7,
+    INFUR_TRACK_WORDS = 8
+};
+enum { INFUR_TRACKS_TRUNCATED = 1, INFUR_TRACKS_OVERFLOW = 2, INFUR_TRACKS_IDS_EXHAUSTED = 4 };
+enum {
+    INFUR_TRACKS_SUMMARY_STATUS = 0,
+    INFUR_TRACKS_SUMMARY_CONTINUED = 1,
+    INFUR_TRACKS_SUMMARY_NEW = 2,
+    INFUR_TRACKS_SUMMARY_ENDED = 3,
+    INFUR_TRACKS_SUMMARY_WORDS = 4
+};
+enum { INFUR_FEATURE_TRACKS = 4 };
+
+/* max_regions: 0 = 65536 (at most 2^24); pair_slots: 0 = 1 << 20, else a power of two >= 64 (at most 2^28).  The tracker owns
+ * its device memory: 12 bytes per slot, 68 per region and the remembered plane (h*w*4 bytes, grown on demand).  None of it
+ * is visible to the graphs infur_ctx_set_graph_replay caches. */
+int32_t infur_tracker_create(infur_ctx* ctx, uint32_t max_regions, uint32_t pair_slots, void** tracker);
+void infur_tracker_destroy(void* tracker);
+/* stream-ordered: forget the remembered frame, next_id = first_id (a new tracker starts at 0) */
+int32_t infur_tracker_reset(void* tracker, uint32_t first_id);
+/* one step, host pointers (labels: h*w; table: table_rows rows of INFUR_REGION_WORDS, of which min(n_regions, table_rows)
+ * are read) */
+int32_t infur_tracks(void* tracker, const uint32_t* labels, const uint64_t* table, uint32_t table_rows, uint32_t n_regions,
+                     uint32_t h, uint32_t w, uint32_t min_overlap, uint32_t* track_of_region, uint32_t* track_plane,
+                     uint64_t* track_table, uint32_t* summary);
+/* device pointers throughout, d_n_regions included (one device uint32_t, read on the device: no host synchronisation);
+ * enqueued on the context's stream */
+int32_t infur_tracks_dev(void* tracker, const void* d_labels, const void* d_table, uint32_t table_rows,
+                         const void* d_n_regions, uint32_t h, uint32_t w, uint32_t min_overlap, void* d_track_of_region,
+                         void* d_track_plane, void* d_track_table, void* d_summary);
+/* The fused frame path with all three decode stages: scale -> model -> Segments decode -> Regions -> Tracks in one call:
+ * infur_frame_regions' arguments, then the tracker (of this context), min_overlap and the four outputs.  labels, table and
+ * n_regions are optional outputs here (the tracker keeps buffers of its own otherwise); table_rows is the row count of the
+ * region table and of the track outputs either way.  Like infur_frame_regions these calls always enqueue eagerly and leave
+ * the graphs cached for infur_frame_advance_dev alone.  (The stream ring, batch and group calls produce RGBA only.) */
+int32_t infur_frame_tracks(infur_ctx* ctx, const uint8_t* bgr, uint32_t w, uint32_t h, float factor, uint32_t scale_mode,
+                           uint32_t decode, uint32_t connectivity, uint32_t min_pixels, uint32_t flags, uint8_t* klass,
+                           uint8_t* conf, size_t plane_capacity, uint32_t* labels, size_t labels_capacity, uint64_t* table,
+                           uint32_t table_rows, uint32_t* n_regions, uint8_t* scaled_bgr, uint32_t* ow, uint32_t* oh,
+                           void* tracker, uint32_t min_overlap, uint32_t* track_of_region, uint32_t* track_plane,
+                           uint64_t* track_table, uint32_t* summary);
+int32_t infur_frame_tracks_dev(infur_ctx* ctx, const void* d_bgr, uint32_t w, uint32_t h, float factor, uint32_t scale_mode,
+                               uint32_t decode, uint32_t connectivity, uint32_t min_pixels, uint32_t flags, void* d_klass,
+                               void* d_conf, size_t plane_capacity, void* d_labels, size_t labels_capacity, void* d_table,
+                               uint32_t table_rows, void* d_n_regions, void* d_scaled_bgr, uint32_t* ow, uint32_t* oh,
+                               void* tracker, uint32_t min_overlap, void* d_track_of_region, void* d_track_plane,
+                               void* d_track_table, void* d_summary);
+
 /* ---- streaming (infur/src/main.rs:27-99,105): bounded queue, copies overlapped with compute ----
  * The reference back-pressures its producer with sync_channel(2) (main.rs:105); a stream
  * here is a ring of `depth` pinned + device slots.  submit() copies the caller's frame into a

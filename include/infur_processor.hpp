@@ -304,6 +304,72 @@ private:
     bool dirty_ = true;
 };
 
+/// What `Tracks` produces: `track_of_region` and `table` hold min(n, table rows of the input) entries / rows of
+/// INFUR_TRACK_WORDS words in region order (INFUR_TRACK_NONE: not tracked), `plane` is h * w track ids, `summary` the four
+/// INFUR_TRACKS_SUMMARY_* words.
+struct TracksOut {
+    bool want_plane = false;
+    uint32_t rows = 0;
+    std::vector<uint32_t> track_of_region, plane;
+    std::vector<uint64_t> table;
+    uint32_t summary[INFUR_TRACKS_SUMMARY_WORDS] = {0, 0, 0, 0};
+    uint32_t status() const { return summary[INFUR_TRACKS_SUMMARY_STATUS]; }
+    uint64_t word(uint32_t id, uint32_t w) const { return table[(size_t)id * INFUR_TRACK_WORDS + w]; }
+};
+
+/// The fourth decode stage: region identities carried from frame to frame.  Owns its tracker -- one remembered frame on the
+/// device -- and must not outlive its context.  A region inherits the track of the remembered region of its class it overlaps
+/// most (when that region prefers it too), otherwise it starts a new one.  Integer results, identical from run to run.
+/// Command = min_overlap or reset (value: the first id of the tracks that follow); Input = RegionsOut, Output = TracksOut.
+class Tracks {
+public:
+    struct Cmd {
+        enum Kind { MinOverlap, Reset } kind;
+        uint32_t value;
+    };
+    explicit Tracks(Context& c, uint32_t max_regions = 0, uint32_t pair_slots = 0) {
+        status_ = infur_tracker_create(c.get(), max_regions, pair_slots, &t_);
+    }
+    ~Tracks() { infur_tracker_destroy(t_); }
+    Tracks(const Tracks&) = delete;
+    Tracks& operator=(const Tracks&) = delete;
+    bool ok() const { return status_ == INFUR_OK; }
+    void* get() const { return t_; }
+    Status control(Cmd cmd) {
+        switch (cmd.kind) {
+            case Cmd::MinOverlap:
+                dirty_ = dirty_ || cmd.value != min_overlap_;
+                min_overlap_ = cmd.value;
+                return INFUR_OK;
+            case Cmd::Reset: dirty_ = true; return infur_tracker_reset(t_, cmd.value);
+            default: return INFUR_E_INVALID_ARG;
+        }
+    }
+    bool is_dirty() const { return dirty_; }
+    Status advance(const RegionsOut& inp, TracksOut& out) {
+        dirty_ = false;
+        const size_t hw = (size_t)inp.width * inp.height;
+        if (inp.labels.size() != hw) return INFUR_E_SHAPE;  // (a RegionsOut made with want_labels)
+        const uint32_t rows = (uint32_t)(inp.table.size() / INFUR_REGION_WORDS);
+        out.rows = hw ? (inp.n < rows ? inp.n : rows) : 0;
+        out.track_of_region.assign(rows, INFUR_TRACK_NONE);
+        out.table.assign((size_t)rows * INFUR_TRACK_WORDS, 0);
+        out.plane.assign(out.want_plane ? hw : 0, INFUR_TRACK_NONE);
+        const Status s = infur_tracks(t_, inp.labels.data(), inp.table.data(), rows, inp.n, inp.height, inp.width, min_overlap_,
+                                      rows ? out.track_of_region.data() : nullptr, out.want_plane && hw ? out.plane.data() : nullptr,
+                                      rows ? out.table.data() : nullptr, out.summary);
+        out.track_of_region.resize(out.rows);
+        out.table.resize((size_t)out.rows * INFUR_TRACK_WORDS);
+        return s;
+    }
+
+private:
+    void* t_ = nullptr;
+    Status status_ = INFUR_OK;
+    uint32_t min_overlap_ = 1;
+    bool dirty_ = true;
+};
+
 /// infur_group: n contexts (one per GPU) of one process -- RCCL weight broadcast + frame-batch sharding
 /// (BASELINE configs[3]).  The contexts must outlive the group.
 class Group {

@@ -46,6 +46,14 @@ REGIONS_SKIP_BACKGROUND = 1
 REGION_CLASS, REGION_FIRST, REGION_WORDS = 8, 9, 10
 REGION_NONE = 0xFFFFFFFF
 FEATURE_REGIONS = 2
+# Tracks (infur_tracks / infur_frame_tracks): the columns of a track row, the status bits, the words of the summary, the feature bit
+TRACK_ID, TRACK_AGE, TRACK_BORN, TRACK_PREV_REGION, TRACK_OVERLAP, TRACK_PREV_PIXELS, TRACK_PREV_SUM_X, TRACK_PREV_SUM_Y = range(8)
+TRACK_WORDS = 8
+TRACK_NONE = 0xFFFFFFFF
+TRACKS_TRUNCATED, TRACKS_OVERFLOW, TRACKS_IDS_EXHAUSTED = 1, 2, 4
+TRACKS_SUMMARY_STATUS, TRACKS_SUMMARY_CONTINUED, TRACKS_SUMMARY_NEW, TRACKS_SUMMARY_ENDED = range(4)
+TRACKS_SUMMARY_WORDS = 4
+FEATURE_TRACKS = 4
 
 
 class Options(C.Structure):
@@ -150,6 +158,15 @@ SIGNATURES = {
                                         _u32p, _u32p]),
     "infur_frame_regions_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp,
                                             _vp, _u32p, _u32p]),
+    "infur_tracker_create": (C.c_int32, [_vp, _u32, _u32, C.POINTER(_vp)]),
+    "infur_tracker_destroy": (None, [_vp]),
+    "infur_tracker_reset": (C.c_int32, [_vp, _u32]),
+    "infur_tracks": (C.c_int32, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),
+    "infur_tracks_dev": (C.c_int32, [_vp, _vp, _vp, _u32, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),
+    "infur_frame_tracks": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp, _vp,
+                                       _u32p, _u32p, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "infur_frame_tracks_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp,
+                                           _vp, _u32p, _u32p, _vp, _u32, _vp, _vp, _vp, _vp]),
     "infur_stream_create": (C.c_int32, [_vp, _u32, C.POINTER(_vp)]),
     "infur_stream_destroy": (None, [_vp]),
     "infur_stream_add_lane": (C.c_int32, [_vp, _vp]),

@@ -1197,6 +1197,7 @@ void infur_ctx_destroy(infur_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     // streams that outlive their context become empty shells: infur_stream_destroy on them only frees the handle
     while (!c->streams.empty()) stream_orphan(c->streams.back());
+    while (!c->trackers.empty()) tracker_orphan(c->trackers.back());
     if (c->batch_ring) {  // the context's own ring (infur_batch_advance): orphaned above, the handle goes here
         infur_stream_destroy(c->batch_ring);
         c->batch_ring = nullptr;

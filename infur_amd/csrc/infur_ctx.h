@@ -13,6 +13,7 @@
 #include "../../include/infur_hip.h"
 
 struct infur_stream;
+struct infur_tracker;
 
 namespace infur {
 
@@ -170,6 +171,8 @@ struct infur_ctx {
     // Regions (infur_regions.cpp): the union-find scratch (parent, counts, ids, scan sums), the planes the frame calls decode into
     // when the caller does not want them, and the host-pointer calls' staging.  Grown lazily, like st_seg without moving mem_gen.
     infur::Buf st_reg, st_reg_planes, st_reg_io;
+    // Tracks (infur_tracks.cpp): the live trackers of this context; infur_ctx_destroy releases their device memory and orphans them
+    std::vector<infur_tracker*> trackers;
 
     // profiling
     std::vector<infur::ProfRec> prof;
@@ -206,4 +209,6 @@ inline void enter(const infur_ctx* c) {
 void ctx_model_free(infur_ctx* c);
 // infur_stream.cpp: releases a streaming ring's resources and detaches it from its context(s); the handle stays allocated
 void stream_orphan(infur_stream* st);
+// infur_tracks.cpp: releases a tracker's device memory and detaches it from its context; the handle stays allocated
+void tracker_orphan(infur_tracker* t);
 }  // namespace infur

@@ -283,4 +283,32 @@ size_t regions_scratch_bytes(size_t npix);
 hipError_t launch_regions(const uint8_t* klass, const uint8_t* conf, unsigned H, unsigned W, int conn8, unsigned min_pixels, int skip_bg,
                           void* scratch, unsigned* labels, unsigned long long* table, unsigned rows, unsigned* d_n, hipStream_t s);
 
+// Tracks (tracks.hip): region identities from frame to frame.  Everything a tracker remembers lives on the device: the scalars
+// in TrkState, the arrays in TrkMem (M = max_regions entries each; keys / cnts: `slots` entries, a power of two; prev: the
+// remembered label plane, at least H * W words).  The step reads *d_n on the device and is stream-ordered throughout.
+constexpr int kTrkWords = 8;
+constexpr unsigned kTrkTruncated = 1, kTrkOverflow = 2, kTrkExhausted = 4;
+struct TrkState {
+    unsigned next_id, frame, valid, ph, pw, pT;             // across steps: id and frame counters, the remembered frame's shape
+    unsigned T, nrows, trunc, fresh, R, exhausted, base;    // of the running step
+};
+struct TrkMem {
+    TrkState* st;
+    unsigned long long* keys;  // pair table: (c << 32) | p, all ones = empty
+    unsigned* cnts;            //             overlap pixels of the pair
+    unsigned long long *best, *claim;      // per current / per remembered region: (overlap << 32) | (0xFFFFFFFF - partner)
+    unsigned long long *ppix, *psx, *psy;  // remembered regions: PIXELS, SUM_X, SUM_Y
+    unsigned *pclass, *ptrack, *page, *pborn;
+    unsigned *ctrack, *cage, *cborn;  // current regions, until the save launch
+    unsigned* partial;                // block sums of the scan: M / 1024 + 1 words
+    unsigned* prev;
+    unsigned slots, M;
+};
+// one step on an H x W plane, H * W in [1, 2^32 - 2]; outputs optional
+hipError_t launch_tracks(const TrkMem& m, const unsigned* labels, const unsigned long long* table, unsigned rows, const unsigned* d_n, unsigned H,
+                         unsigned W, unsigned min_overlap, unsigned* track_of_region, unsigned* track_plane, unsigned long long* track_table,
+                         unsigned* summary, hipStream_t s);
+// forget the remembered frame; step: advance the frame counter (an empty frame); set_id: next_id = first_id; summary (optional) zeroed
+hipError_t launch_tracks_forget(TrkState* st, int step, int set_id, unsigned first_id, unsigned* summary, hipStream_t s);
+
 }  // namespace infur

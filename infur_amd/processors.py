@@ -645,6 +645,138 @@ def region_summary(table: np.ndarray, n: int, ow: int, oh: int, names=None) -> L
     return recs
 
 
+@dataclass
+class TracksCmd:
+    """``Tracks``' command: exactly one of min_overlap, or reset (the first id of the tracks that follow; the frame is forgotten)."""
+
+    min_overlap: Optional[int] = None
+    reset: Optional[int] = None
+
+    @staticmethod
+    def MinOverlap(v: int) -> "TracksCmd":
+        return TracksCmd(min_overlap=v)
+
+    @staticmethod
+    def Reset(first_id: int = 0) -> "TracksCmd":
+        return TracksCmd(reset=first_id)
+
+
+class TracksOut:
+    """``Tracks``' ``&mut Output``: what to produce (``want_plane``) and, after ``advance``, the results -- ``track_of_region``
+    [min(n, rows)] u32 (``_lib.TRACK_NONE``: not tracked), ``table`` [min(n, rows), 8] uint64 (columns ``_lib.TRACK_*``),
+    ``plane`` [H, W] u32 or None, ``summary`` [4] u32 (``_lib.TRACKS_SUMMARY_*``) and its fields ``status`` (``_lib.TRACKS_*``
+    bits), ``continued``, ``new``, ``ended``."""
+
+    def __init__(self, want_plane: bool = False):
+        self.want_plane = want_plane
+        self.track_of_region = self.table = self.plane = self.summary = None
+        self.status = self.continued = self.new = self.ended = 0
+
+    def _set(self, tor, table, plane, summary, n):
+        self.track_of_region = tor[:n] if tor is not None else None
+        self.table = table[:n] if table is not None else None
+        self.plane, self.summary = plane, summary
+        self.status, self.continued, self.new, self.ended = (int(v) for v in summary)
+
+
+class Tracks(Processor):
+    """The fourth decode stage: region identities carried from frame to frame.  Owns its tracker (one remembered frame on the
+    device): ``close()`` it, or let it go with its context.
+
+    Command = ``TracksCmd``.  Input = (labels [H, W] u32, table [rows, 10] uint64, n), i.e. ``RegionsOut``'s fields;
+    Output = ``TracksOut``.  A region inherits the track of the remembered region of its class it overlaps most (when that
+    region prefers it too), otherwise it starts a new one; integers throughout, identical from run to run.
+    """
+
+    def __init__(self, ctx: Context, max_regions: int = 0, pair_slots: int = 0, min_overlap: int = 1):
+        self.ctx = ctx
+        self.min_overlap = min_overlap
+        self.dirty = True
+        t = C.c_void_p()
+        ctx.check(ctx.L.infur_tracker_create(ctx.h, max_regions, pair_slots, C.byref(t)))
+        self.t = t
+
+    def control(self, cmd: TracksCmd) -> "Tracks":
+        given = [v for v in (cmd.min_overlap, cmd.reset) if v is not None]
+        if len(given) != 1 or not 0 <= given[0] <= 0xFFFFFFFF:
+            raise InfurError(_lib.E_INVALID_ARG, "a TracksCmd sets exactly one of min_overlap, reset, each a u32")
+        if cmd.reset is not None:
+            self.ctx.check(self.ctx.L.infur_tracker_reset(self.t, cmd.reset))
+            self.dirty = True
+        else:
+            self.dirty = self.dirty or cmd.min_overlap != self.min_overlap
+            self.min_overlap = cmd.min_overlap
+        return self
+
+    def is_dirty(self) -> bool:
+        return self.dirty
+
+    def advance(self, inp, out: TracksOut) -> None:
+        self.dirty = False
+        labels, table, n = inp
+        if labels.ndim != 2:
+            raise InfurError(_lib.E_SHAPE, f"expected an [H,W] label plane, got {labels.shape}")
+        labels = np.ascontiguousarray(labels, np.uint32)
+        h, w = labels.shape
+        table = np.ascontiguousarray(table if table is not None else np.zeros((0, _lib.REGION_WORDS)), np.uint64).reshape(-1, _lib.REGION_WORDS)
+        rows = len(table)
+        tor = np.empty(rows, np.uint32)
+        ttab = np.empty((rows, _lib.TRACK_WORDS), np.uint64)
+        plane = np.empty((h, w), np.uint32) if out.want_plane else None
+        summary = np.zeros(_lib.TRACKS_SUMMARY_WORDS, np.uint32)
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        self.ctx.check(self.ctx.L.infur_tracks(self.t, ptr(labels), ptr(table), rows, int(n), h, w, self.min_overlap, ptr(tor), ptr(plane),
+                                               ptr(ttab), summary.ctypes.data))
+        out._set(tor, ttab, plane, summary, min(int(n), rows) if h * w else 0)
+
+    def close(self):
+        if getattr(self, "t", None):
+            self.ctx.L.infur_tracker_destroy(self.t)
+            self.t = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class TracksFrame(NamedTuple):
+    """``FramePath.advance_tracks``: the fields of ``RegionsFrame``, then ``track_of_region`` [min(n, table_rows)] u32, the track
+    table [min(n, table_rows), 8] uint64, the track plane [oh, ow] u32 or None and the summary [4] u32"""
+
+    klass: Optional[np.ndarray]
+    conf: Optional[np.ndarray]
+    labels: Optional[np.ndarray]
+    table: Optional[np.ndarray]
+    n: Optional[int]
+    scaled: Optional[np.ndarray]
+    track_of_region: Optional[np.ndarray]
+    track_table: Optional[np.ndarray]
+    track_plane: Optional[np.ndarray]
+    summary: Optional[np.ndarray]
+
+
+def track_summary(table: np.ndarray, track_table: np.ndarray, n: int, ow: int, oh: int, names=None) -> List[dict]:
+    """``region_summary``'s records joined with the track table, one dict per row both tables hold, in region order: added are
+    ``track`` (None for an untracked region), ``age``, ``born``, ``prev_region`` (None for a new track), ``overlap`` and
+    ``step`` -- this frame's centroid minus the inherited region's, (dx, dy), or None for a new or untracked region."""
+    recs = region_summary(table, n, ow, oh, names)
+    rows = np.asarray(track_table, np.uint64).reshape(-1, _lib.TRACK_WORDS)
+    recs = recs[:len(rows)]
+    for rec, row in zip(recs, rows):
+        tid, prev, ppx = int(row[_lib.TRACK_ID]), int(row[_lib.TRACK_PREV_REGION]), int(row[_lib.TRACK_PREV_PIXELS])
+        rec["track"] = tid if tid != _lib.TRACK_NONE else None
+        rec["age"], rec["born"] = int(row[_lib.TRACK_AGE]), int(row[_lib.TRACK_BORN])
+        rec["prev_region"] = prev if prev != _lib.REGION_NONE else None
+        rec["overlap"] = int(row[_lib.TRACK_OVERLAP])
+        rec["step"] = None
+        if rec["prev_region"] is not None and ppx:
+            cx, cy = rec["centroid"]
+            rec["step"] = (cx - int(row[_lib.TRACK_PREV_SUM_X]) / ppx, cy - int(row[_lib.TRACK_PREV_SUM_Y]) / ppx)
+    return recs
+
+
 def pack_normalize(ctx: Context, img: np.ndarray) -> np.ndarray:
     """The pre-proc stage on its own (predict_onnx.rs:103-137): BGR u8 HWC -> RGB f32 CHW."""
     img = _check_bgr(img)
@@ -750,6 +882,47 @@ class FramePath:
             return RegionsFrame(None, None, None, None, None, scaled)
         self.ctx.check(rc)
         return RegionsFrame(klass, conf, labels, table[:min(n.value, rows)] if table is not None else None, n.value, scaled)
+
+    def advance_tracks(self, tracks: "Tracks", img: np.ndarray, factor: float = 1.0, decode: int = _lib.DECODE_RAW,
+                       connectivity: int = _lib.CONNECT_8, min_pixels: int = 0, flags: int = 0, table_rows: int = 1024,
+                       want_labels: bool = True, want_klass: bool = True, want_conf: bool = True, want_scaled: bool = False,
+                       want_plane: bool = False) -> TracksFrame:
+        """The fused path with all three decode stages, scale -> model -> Segments decode -> Regions -> Tracks, in one call ->
+        ``TracksFrame``; every result field is None when no model is loaded (``scaled`` is still produced)."""
+        img = _check_bgr(img)
+        h, w = img.shape[:2]
+        L = self.ctx.L
+        f = float(np.float32(factor))
+        rc = L.infur_scale_validate(f)
+        if rc:
+            raise ValidScaleError(rc)
+        ow, oh = C.c_uint32(0), C.c_uint32(0)
+        rc = L.infur_scale_out_dims(w, h, f, C.byref(ow), C.byref(oh))
+        if rc:
+            raise ScaleProcError(rc)
+        npix = oh.value * ow.value
+        rows = max(0, min(int(table_rows), npix))
+        klass = np.empty((oh.value, ow.value), np.uint8) if want_klass else None
+        conf = np.empty((oh.value, ow.value), np.uint8) if want_conf else None
+        labels = np.empty((oh.value, ow.value), np.uint32) if want_labels else None
+        table = np.zeros((rows, _lib.REGION_WORDS), np.uint64) if rows else None
+        scaled = np.empty((oh.value, ow.value, 3), np.uint8) if want_scaled else None
+        tor = np.empty(rows, np.uint32) if rows else None
+        ttab = np.empty((rows, _lib.TRACK_WORDS), np.uint64) if rows else None
+        plane = np.empty((oh.value, ow.value), np.uint32) if want_plane else None
+        summary = np.zeros(_lib.TRACKS_SUMMARY_WORDS, np.uint32)
+        n = C.c_uint32(0)
+        ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
+        rc = L.infur_frame_tracks(self.ctx.h, img.ctypes.data, w, h, f, self.scale_mode, decode, connectivity, min_pixels, flags,
+                                  ptr(klass), ptr(conf), npix, ptr(labels), npix * 4, ptr(table), rows, C.addressof(n), ptr(scaled),
+                                  C.byref(ow), C.byref(oh), tracks.t, tracks.min_overlap, ptr(tor), ptr(plane), ptr(ttab),
+                                  summary.ctypes.data)
+        if rc == _lib.E_MODEL_NOT_LOADED:
+            return TracksFrame(None, None, None, None, None, scaled, None, None, None, None)
+        self.ctx.check(rc)
+        k = min(n.value, rows)
+        return TracksFrame(klass, conf, labels, table[:k] if table is not None else None, n.value, scaled,
+                           tor[:k] if tor is not None else None, ttab[:k] if ttab is not None else None, plane, summary)
 
     def advance_batch(self, imgs, factor: float = 1.0, outs=None):
         """A batch of independent frames (BASELINE configs[3]) -> list of masks, in order.  ``outs``: caller-owned mask arrays to fill

@@ -18,6 +18,12 @@ them, ``--max-regions`` bounds the records per frame, ``--regions-out`` receives
 confidence planes are written to device buffers, labelled there, and only what is written out or summarised comes back.
 ``--conf-out`` receives the confidence planes (one byte per pixel).  Without these options the output is what it was before
 they existed.
+
+``--tracks`` (implies ``--regions``) carries the region identities from frame to frame on the device: every region record
+gains ``"track"`` (stable while the object overlaps itself from one frame to the next; null beyond ``--max-regions``),
+``"age"`` in frames and ``"dx"``, ``"dy"``, the step of its centroid since the previous frame (null for a new track), and every
+line ``"tracks": {"status", "continued", "new", "ended"}``.  ``--min-overlap N`` is the least number of common pixels that
+continues a track; ``--tracks-out`` receives the u32 track planes back to back (0xFFFFFFFF: not tracked).
 """
 from __future__ import annotations
 
@@ -48,13 +54,19 @@ def main(argv=None) -> int:
     ap.add_argument("--max-regions", type=int, default=1024, help="region records per frame (the count is always complete)")
     ap.add_argument("--regions-out", default="", help="raw u32 label planes, four bytes per pixel (needs --regions)")
     ap.add_argument("--conf-out", default="", help="raw confidence planes, one byte per pixel")
+    ap.add_argument("--tracks", action="store_true", help="carry region identities from frame to frame (implies --regions)")
+    ap.add_argument("--min-overlap", type=int, default=1, help="common pixels a track needs to continue")
+    ap.add_argument("--tracks-out", default="", help="raw u32 track planes, four bytes per pixel (needs --tracks)")
     a = ap.parse_args(argv)
+    if a.tracks_out and not a.tracks:
+        ap.error("--tracks-out needs --tracks")
+    a.regions = a.regions or a.tracks
     if a.regions_out and not a.regions:
         ap.error("--regions-out needs --regions")
 
     from . import _lib
     from .app import RawVideoSource, VideoProcError
-    from .processors import Context, FramePath, Model, ModelCmd, class_summary, region_summary
+    from .processors import Context, FramePath, Model, ModelCmd, class_summary, region_summary, track_summary
 
     ctx = Context(device=a.device, dtype=a.dtype)
     model = Model(ctx)
@@ -76,10 +88,12 @@ def main(argv=None) -> int:
     img = src.empty_image()
     freg = open(a.regions_out, "wb") if a.regions_out else None
     fconf = open(a.conf_out, "wb") if a.conf_out else None
+    ftrk = open(a.tracks_out, "wb") if a.tracks_out else None
     rpath = None
     if a.regions:
         oh, ow = _out_dims(ctx, a.width, a.height, a.scale)
-        rpath = _RegionsPath(ctx, a.width, a.height, ow, oh, a.scale, fp.scale_mode, model.get_info().num_classes, max(0, a.max_regions))
+        rpath = _RegionsPath(ctx, a.width, a.height, ow, oh, a.scale, fp.scale_mode, model.get_info().num_classes, max(0, a.max_regions),
+                             tracks=a.tracks)
         flags = _lib.REGIONS_SKIP_BACKGROUND if a.skip_background else 0
     n, t0 = 0, time.perf_counter()
     while True:
@@ -92,6 +106,8 @@ def main(argv=None) -> int:
         if rpath is not None:
             s, labels, table, nreg = rpath.advance(img, decode, a.connectivity, a.min_pixels, flags, flab is not None, fconf is not None,
                                                    freg is not None)
+            if a.tracks:
+                ttab, tplane, tsum = rpath.track(max(0, a.min_overlap), ftrk is not None)
         else:
             s = fp.advance_segments(img, a.scale, decode, want_klass=flab is not None, want_conf=fconf is not None)
         oh, ow = (s.klass.shape if s.klass is not None else _out_dims(ctx, a.width, a.height, a.scale))
@@ -103,11 +119,18 @@ def main(argv=None) -> int:
         if rpath is not None:
             rec["n_regions"] = nreg
             rec["regions"] = region_summary(table, nreg, ow, oh)
+            if a.tracks:
+                for r, t in zip(rec["regions"], track_summary(table, ttab, nreg, ow, oh)):
+                    r["track"], r["age"] = t["track"], t["age"]
+                    r["dx"], r["dy"] = t["step"] if t["step"] is not None else (None, None)
+                rec["tracks"] = {"status": int(tsum[0]), "continued": int(tsum[1]), "new": int(tsum[2]), "ended": int(tsum[3])}
+                if ftrk is not None:
+                    ftrk.write(memoryview(tplane).cast("B"))
             if freg is not None:
                 freg.write(memoryview(labels).cast("B"))
         fst.write(json.dumps(rec) + "\n")
         n += 1
-    for f in (flab, fconf, freg, fst):
+    for f in (flab, fconf, freg, ftrk, fst):
         if f is not None:
             f.flush()
     el = time.perf_counter() - t0
@@ -123,17 +146,22 @@ class _RegionsPath:
     writes class plane, confidence plane and per-class table into device buffers, infur_regions_dev labels those planes where
     they are; the tables, the count and the planes that are written out are all that is copied back."""
 
-    def __init__(self, ctx, w, h, ow, oh, factor, scale_mode, classes, rows):
+    def __init__(self, ctx, w, h, ow, oh, factor, scale_mode, classes, rows, tracks=False):
         import ctypes as C
 
         self.ctx, self.w, self.h, self.ow, self.oh, self.factor, self.mode = ctx, w, h, ow, oh, float(factor), scale_mode
         self.k, self.rows = classes, min(rows, ow * oh)
         self.d = {}
         for name, n in (("bgr", w * h * 3), ("klass", ow * oh), ("conf", ow * oh), ("stats", classes * _STAT_BYTES), ("labels", ow * oh * 4),
-                        ("table", self.rows * _ROW_BYTES), ("n", 4)):
+                        ("table", self.rows * _ROW_BYTES), ("n", 4)) + \
+                ((("ttab", self.rows * _TRACK_BYTES), ("tplane", ow * oh * 4), ("tsum", 16)) if tracks else ()):
             p = C.c_void_p(None)
             ctx.check(ctx.L.infur_dev_alloc(ctx.h, max(n, 4), C.byref(p)))
             self.d[name] = p
+        self.tracker = None
+        if tracks:  # --tracks: the label plane stays on the device for the tracker whether it is written out or not
+            self.tracker = C.c_void_p(None)
+            ctx.check(ctx.L.infur_tracker_create(ctx.h, 0, 0, C.byref(self.tracker)))
 
     def _read(self, name, shape, dtype):
         import numpy as np
@@ -156,16 +184,30 @@ class _RegionsPath:
         c.check(L.infur_memcpy_h2d(c.h, d["bgr"], img.ctypes.data, img.nbytes))
         c.check(L.infur_frame_segments_dev(c.h, d["bgr"], self.w, self.h, self.factor, self.mode, decode, d["klass"], d["conf"], self.ow * self.oh,
                                            d["stats"], self.k, None, 0, None, C.byref(ow), C.byref(oh)))
-        c.check(L.infur_regions_dev(c.h, d["klass"], d["conf"], self.oh, self.ow, connectivity, min_pixels, flags, d["labels"] if want_labels else None,
+        c.check(L.infur_regions_dev(c.h, d["klass"], d["conf"], self.oh, self.ow, connectivity, min_pixels, flags, d["labels"] if want_labels or self.tracker else None,
                                     d["table"] if self.rows else None, self.rows, d["n"]))
         n = int(self._read("n", (1,), np.uint32)[0])
         seg = SegmentsFrame(self._read("klass", (self.oh, self.ow), np.uint8) if want_klass else None,
                             self._read("conf", (self.oh, self.ow), np.uint8) if want_conf else None,
                             self._read("stats", (self.k, _STAT_BYTES // 8), np.uint64), None, None)
         labels = self._read("labels", (self.oh, self.ow), np.uint32) if want_labels else None
+        self.n = n
         return seg, labels, self._read("table", (min(n, self.rows), _ROW_BYTES // 8), np.uint64), n
 
+    def track(self, min_overlap, want_plane):
+        """infur_tracks_dev on the frame `advance` just labelled -> (track table rows, track plane or None, summary)"""
+        import numpy as np
+
+        c, d = self.ctx, self.d
+        c.check(c.L.infur_tracks_dev(self.tracker, d["labels"], d["table"], self.rows, d["n"], self.oh, self.ow, min_overlap, None,
+                                     d["tplane"] if want_plane else None, d["ttab"] if self.rows else None, d["tsum"]))
+        return (self._read("ttab", (min(self.n, self.rows), _TRACK_BYTES // 8), np.uint64),
+                self._read("tplane", (self.oh, self.ow), np.uint32) if want_plane else None, self._read("tsum", (4,), np.uint32))
+
     def close(self):
+        if self.tracker:
+            self.ctx.L.infur_tracker_destroy(self.tracker)
+            self.tracker = None
         for p in self.d.values():
             self.ctx.L.infur_dev_free(self.ctx.h, p)
         self.d = {}
@@ -173,6 +215,7 @@ class _RegionsPath:
 
 _STAT_BYTES = 8 * 8    # INFUR_STAT_WORDS u64 per class
 _ROW_BYTES = 10 * 8    # INFUR_REGION_WORDS u64 per region
+_TRACK_BYTES = 8 * 8   # INFUR_TRACK_WORDS u64 per region
 
 
 def _out_dims(ctx, w, h, factor):

@@ -107,6 +107,28 @@ pub const INFUR_REGION_WORDS: u32 = 10;
 pub const INFUR_REGION_NONE: u32 = 0xFFFF_FFFF;
 /// bit of `infur_features()`: the Regions calls below exist
 pub const INFUR_FEATURE_REGIONS: u32 = 2;
+/// Tracks: the columns of a track row (`INFUR_TRACK_WORDS` u64 each), the status bits, the words of the summary
+pub const INFUR_TRACK_ID: u32 = 0;
+pub const INFUR_TRACK_AGE: u32 = 1;
+pub const INFUR_TRACK_BORN: u32 = 2;
+pub const INFUR_TRACK_PREV_REGION: u32 = 3;
+pub const INFUR_TRACK_OVERLAP: u32 = 4;
+pub const INFUR_TRACK_PREV_PIXELS: u32 = 5;
+pub const INFUR_TRACK_PREV_SUM_X: u32 = 6;
+pub const INFUR_TRACK_PREV_SUM_Y: u32 = 7;
+pub const INFUR_TRACK_WORDS: u32 = 8;
+pub const INFUR_TRACKS_TRUNCATED: u32 = 1;
+pub const INFUR_TRACKS_OVERFLOW: u32 = 2;
+pub const INFUR_TRACKS_IDS_EXHAUSTED: u32 = 4;
+pub const INFUR_TRACKS_SUMMARY_STATUS: u32 = 0;
+pub const INFUR_TRACKS_SUMMARY_CONTINUED: u32 = 1;
+pub const INFUR_TRACKS_SUMMARY_NEW: u32 = 2;
+pub const INFUR_TRACKS_SUMMARY_ENDED: u32 = 3;
+pub const INFUR_TRACKS_SUMMARY_WORDS: u32 = 4;
+/// track of a region that is not tracked
+pub const INFUR_TRACK_NONE: u32 = 0xFFFF_FFFF;
+/// bit of `infur_features()`: the Tracks calls below exist
+pub const INFUR_FEATURE_TRACKS: u32 = 4;
 
 extern "C" {
     pub fn infur_abi_version() -> u32;
@@ -249,4 +271,25 @@ extern "C" {
                                    plane_capacity: usize, d_labels: *mut c_void, labels_capacity: usize, d_table: *mut c_void,
                                    table_rows: u32, d_n_regions: *mut c_void, d_scaled_bgr: *mut c_void, ow: *mut u32,
                                    oh: *mut u32) -> i32;
+    // Tracks: the tracker handle is an untyped pointer in the C header
+    pub fn infur_tracker_create(c: *mut infur_ctx, max_regions: u32, pair_slots: u32, tracker: *mut *mut c_void) -> i32;
+    pub fn infur_tracker_destroy(tracker: *mut c_void);
+    pub fn infur_tracker_reset(tracker: *mut c_void, first_id: u32) -> i32;
+    pub fn infur_tracks(tracker: *mut c_void, labels: *const u32, table: *const u64, table_rows: u32, n_regions: u32, h: u32, w: u32,
+                        min_overlap: u32, track_of_region: *mut u32, track_plane: *mut u32, track_table: *mut u64,
+                        summary: *mut u32) -> i32;
+    pub fn infur_tracks_dev(tracker: *mut c_void, d_labels: *const c_void, d_table: *const c_void, table_rows: u32,
+                            d_n_regions: *const c_void, h: u32, w: u32, min_overlap: u32, d_track_of_region: *mut c_void,
+                            d_track_plane: *mut c_void, d_track_table: *mut c_void, d_summary: *mut c_void) -> i32;
+    pub fn infur_frame_tracks(c: *mut infur_ctx, bgr: *const u8, w: u32, h: u32, factor: f32, scale_mode: u32, decode: u32,
+                              connectivity: u32, min_pixels: u32, flags: u32, klass: *mut u8, conf: *mut u8, plane_capacity: usize,
+                              labels: *mut u32, labels_capacity: usize, table: *mut u64, table_rows: u32, n_regions: *mut u32,
+                              scaled_bgr: *mut u8, ow: *mut u32, oh: *mut u32, tracker: *mut c_void, min_overlap: u32,
+                              track_of_region: *mut u32, track_plane: *mut u32, track_table: *mut u64, summary: *mut u32) -> i32;
+    pub fn infur_frame_tracks_dev(c: *mut infur_ctx, d_bgr: *const c_void, w: u32, h: u32, factor: f32, scale_mode: u32, decode: u32,
+                                  connectivity: u32, min_pixels: u32, flags: u32, d_klass: *mut c_void, d_conf: *mut c_void,
+                                  plane_capacity: usize, d_labels: *mut c_void, labels_capacity: usize, d_table: *mut c_void,
+                                  table_rows: u32, d_n_regions: *mut c_void, d_scaled_bgr: *mut c_void, ow: *mut u32,
+                                  oh: *mut u32, tracker: *mut c_void, min_overlap: u32, d_track_of_region: *mut c_void,
+                                  d_track_plane: *mut c_void, d_track_table: *mut c_void, d_summary: *mut c_void) -> i32;
 }

@@ -486,6 +486,75 @@ impl Processor for HipRegions {
     }
 }
 
+// ---------------------------------------------------------------- Tracks (region identities from frame to frame)
+/// What `HipTracks` produces: `track_of_region` and `table` (rows of `INFUR_TRACK_WORDS` words) hold one entry per region row of
+/// the input, in region order (`sys::INFUR_TRACK_NONE`: not tracked); `plane` is `h * w` track ids; `summary` the four
+/// `INFUR_TRACKS_SUMMARY_*` words.
+#[derive(Default)]
+pub struct Tracks {
+    pub want_plane: bool, pub rows: usize,
+    pub track_of_region: Vec<u32>, pub plane: Vec<u32>, pub table: Vec<u64>, pub summary: [u32; 4],
+}
+impl Tracks {
+    pub fn status(&self) -> u32 { self.summary[sys::INFUR_TRACKS_SUMMARY_STATUS as usize] }
+    pub fn word(&self, id: usize, word: u32) -> u64 { self.table[id * sys::INFUR_TRACK_WORDS as usize + word as usize] }
+}
+pub enum TracksCmd { MinOverlap(u32), Reset(u32) }
+/// Owns one tracker (`infur_tracker_*`): the frame it remembers lives on the device.  A region inherits the track of the remembered
+/// region of its class it overlaps most (when that region prefers it too), otherwise it starts a new one.  Integer results.
+pub struct HipTracks { raw: *mut std::ffi::c_void, ctx: Rc<Ctx>, min_overlap: u32, dirty: bool }
+impl HipTracks {
+    /// `max_regions` / `pair_slots`: 0 = the library's defaults (65536, 1 << 20)
+    pub fn new(ctx: Rc<Ctx>, max_regions: u32, pair_slots: u32) -> Result<Self, HipError> {
+        let mut raw = std::ptr::null_mut();
+        let rc = unsafe { sys::infur_tracker_create(ctx.0, max_regions, pair_slots, &mut raw) };
+        if rc != sys::INFUR_OK { return Err(HipError::from_ctx(&ctx, rc)); }
+        Ok(Self { raw, ctx, min_overlap: 1, dirty: true })
+    }
+}
+impl Drop for HipTracks {
+    fn drop(&mut self) { unsafe { sys::infur_tracker_destroy(self.raw) } }
+}
+impl Processor for HipTracks {
+    type Command = TracksCmd;
+    type ControlError = HipError;
+    type Input = Regions;
+    type Output = Tracks;
+    type ProcessResult = Result<(), HipError>;
+
+    fn control(&mut self, cmd: TracksCmd) -> Result<&mut Self, HipError> {
+        match cmd {
+            TracksCmd::MinOverlap(v) => { self.dirty |= v != self.min_overlap; self.min_overlap = v; }
+            TracksCmd::Reset(first_id) => {
+                let rc = unsafe { sys::infur_tracker_reset(self.raw, first_id) };
+                if rc != sys::INFUR_OK { return Err(HipError::from_ctx(&self.ctx, rc)); }
+                self.dirty = true;
+            }
+        }
+        Ok(self)
+    }
+    fn is_dirty(&self) -> bool { self.dirty }
+    fn advance(&mut self, inp: &Regions, out: &mut Tracks) -> Result<(), HipError> {
+        self.dirty = false;
+        let [w, h] = inp.size;
+        if inp.labels.len() != w * h { return Err(HipError::status(sys::INFUR_E_SHAPE)); }  // (Regions made with want_labels)
+        let rows = inp.table.len() / sys::INFUR_REGION_WORDS as usize;
+        out.rows = if w * h > 0 { (inp.n as usize).min(rows) } else { 0 };
+        out.track_of_region.resize(rows, sys::INFUR_TRACK_NONE);
+        out.table.resize(rows * sys::INFUR_TRACK_WORDS as usize, 0);
+        out.plane.resize(if out.want_plane { h * w } else { 0 }, sys::INFUR_TRACK_NONE);
+        let rc = unsafe {
+            sys::infur_tracks(self.raw, inp.labels.as_ptr(), inp.table.as_ptr(), rows as u32, inp.n, h as u32, w as u32, self.min_overlap,
+                              if rows > 0 { out.track_of_region.as_mut_ptr() } else { std::ptr::null_mut() },
+                              if out.want_plane && h * w > 0 { out.plane.as_mut_ptr() } else { std::ptr::null_mut() },
+                              if rows > 0 { out.table.as_mut_ptr() } else { std::ptr::null_mut() }, out.summary.as_mut_ptr())
+        };
+        out.track_of_region.truncate(out.rows);
+        out.table.truncate(out.rows * sys::INFUR_TRACK_WORDS as usize);
+        if rc == sys::INFUR_OK { Ok(()) } else { Err(HipError::from_ctx(&self.ctx, rc)) }
+    }
+}
+
 // ---------------------------------------------------------------- streaming ring with zero-copy slots (main.rs:27-99,105; ABI 5)
 /// The bounded queue of frames in flight (`sync_channel(2)`, main.rs:105) over `infur_stream_*`.  `next_slot` / `commit` let the
 /// decoder fill the ring's own pinned buffer in place -- what `ff-video/src/decoder.rs:156-165` does with its reused `BgrImage` --
