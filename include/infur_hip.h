@@ -482,6 +482,62 @@ int32_t infur_frame_tracks_dev(infur_ctx* ctx, const void* d_bgr, uint32_t w, ui
                                void* tracker, uint32_t min_overlap, void* d_track_of_region, void* d_track_plane,
                                void* d_track_table, void* d_summary);
 
+/* ---- Runs: a class, label or track plane as run-length records ----
+ * The four decode stages end in dense planes: at 1080p a 2 MB class plane, an 8 MB label plane, an 8 MB track plane.  A
+ * segmentation plane is spatially coherent, so run-length encoded (12 bytes per run) it is a fraction of that -- and RLE is
+ * the form in which masks are exchanged, stored and drawn.  Runs encodes any byte or u32 plane on the device, and a host copies out only
+ * as many records as there are.  Presence of this group is announced by infur_features() & INFUR_FEATURE_RUNS
+ * (INFUR_ABI_VERSION does not move).
+ *
+ * The input is a plane of h x w elements of elem_bytes = 1 (a class or confidence plane) or 4 (a label or track plane); any
+ * other elem_bytes is INFUR_E_INVALID_ARG.  A RUN is a maximal sequence of equal values within one row: a run never continues
+ * into the next row, so that a per-row index can exist.  Runs are numbered from 0 in raster order of their first pixel.
+ *   flags & INFUR_RUNS_SKIP   runs whose value equals skip_value are neither emitted nor counted (typically class 0,
+ *                             INFUR_REGION_NONE, INFUR_TRACK_NONE).  An unknown flag bit, or skip_value > 255 with 1-byte
+ *                             elements, is INFUR_E_INVALID_ARG
+ * Outputs, each optional (NULL = not wanted, and so is runs with runs_rows == 0; nothing wanted is INFUR_E_INVALID_ARG), none
+ * needs initialisation:
+ *   runs       runs_rows records of INFUR_RUN_WORDS uint32_t: INFUR_RUN_START the linear index y*w + x of the run's first
+ *              pixel, INFUR_RUN_END one past its last pixel (the length is END - START, the row START / w), INFUR_RUN_VALUE
+ *              the value, zero-extended.  Only the first min(n, runs_rows) records are written; records at or beyond that are
+ *              left alone
+ *   row_start  h + 1 uint32_t: row_start[y] is the number of emitted runs that start before row y, whatever runs_rows is;
+ *              row_start[h] = n
+ *   n_runs     the number of emitted runs n, even when it exceeds runs_rows (truncation is not an error)
+ * h*w == 0 writes n_runs = 0 and row_start[0..h] = 0, and nothing else; h*w >= 2^32 - 1 and a NULL plane with h*w > 0 are
+ * INFUR_E_INVALID_ARG.  No output is touched when a call is rejected.  Everything is an integer and a function of the plane
+ * alone: identical bytes from run to run. */
+enum { INFUR_RUNS_SKIP = 1 };
+enum { INFUR_RUN_START = 0, INFUR_RUN_END = 1, INFUR_RUN_VALUE = 2, INFUR_RUN_WORDS = 3 };
+enum { INFUR_FEATURE_RUNS = 8 };
+
+/* on a given plane, host pointers: the count is read first and only min(n, runs_rows) records are copied back */
+int32_t infur_runs(infur_ctx* ctx, const void* plane, uint32_t elem_bytes, uint32_t h, uint32_t w, uint32_t flags,
+                   uint32_t skip_value, uint32_t* runs, uint32_t runs_rows, uint32_t* row_start, uint32_t* n_runs);
+/* device pointers throughout, d_n_runs included (one device uint32_t); enqueued on the context's stream, never synchronises,
+ * capturable after one call outside the capture (which allocates the scratch: one word per 1024 pixels, owned by the context;
+ * it grows only with a plane of more than 16 Mi pixels that is larger than any before, and a graph captured around the call
+ * is re-captured after that).  This is the call that
+ * composes on the device: infur_frame_regions_dev or infur_frame_tracks_dev, then infur_runs_dev on the label or track plane
+ * they left in device memory, gives per-object runs with no dense plane crossing PCIe. */
+int32_t infur_runs_dev(infur_ctx* ctx, const void* d_plane, uint32_t elem_bytes, uint32_t h, uint32_t w, uint32_t flags,
+                       uint32_t skip_value, void* d_runs, uint32_t runs_rows, void* d_row_start, void* d_n_runs);
+/* The fused frame path with the class plane run-length encoded: scale -> model -> Segments decode(out[0]) -> Runs of the class
+ * plane, in one call.  The class plane is decoded into scratch of the library's own.  row_start_rows counts the words of
+ * row_start: fewer than oh + 1 is INFUR_E_CAPACITY (checked, like the other capacities, once a model is loaded).  stats is Segments' per-class table, optional, so that captions come with
+ * the mask; stats_capacity is the number of classes it has room for, as infur_frame_segments' stats_classes.  At least one of
+ * runs, row_start and n_runs must be given.  The calls inherit infur_frame_segments' checks and errors: with no model loaded
+ * the Scale stage still runs and the call returns INFUR_E_MODEL_NOT_LOADED.  They always enqueue eagerly and leave the graphs
+ * cached for infur_frame_advance_dev alone.  (The stream ring, batch and group calls produce RGBA only.) */
+int32_t infur_frame_runs(infur_ctx* ctx, const uint8_t* bgr, uint32_t w, uint32_t h, float factor, uint32_t scale_mode,
+                         uint32_t decode, uint32_t flags, uint32_t skip_value, uint32_t* runs, uint32_t runs_rows,
+                         uint32_t* row_start, uint32_t row_start_rows, uint32_t* n_runs, uint64_t* stats,
+                         uint32_t stats_capacity, uint8_t* scaled_bgr, uint32_t* ow, uint32_t* oh);
+int32_t infur_frame_runs_dev(infur_ctx* ctx, const void* d_bgr, uint32_t w, uint32_t h, float factor, uint32_t scale_mode,
+                             uint32_t decode, uint32_t flags, uint32_t skip_value, void* d_runs, uint32_t runs_rows,
+                             void* d_row_start, uint32_t row_start_rows, void* d_n_runs, void* d_stats,
+                             uint32_t stats_capacity, void* d_scaled_bgr, uint32_t* ow, uint32_t* oh);
+
 /* ---- streaming (infur/src/main.rs:27-99,105): bounded queue, copies overlapped with compute ----
  * The reference back-pressures its producer with sync_channel(2) (main.rs:105); a stream
  * here is a ring of `depth` pinned + device slots.  submit() copies the caller's frame into a

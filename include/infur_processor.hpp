@@ -370,6 +370,62 @@ private:
     bool dirty_ = true;
 };
 
+/// What `Runs` produces: `runs` holds min(n, runs_rows) records of INFUR_RUN_WORDS words in raster order, `row_start` the
+/// height + 1 words of the per-row index, `n` counts every run (above runs_rows: truncated).
+struct RunsOut {
+    uint32_t runs_rows = 1u << 16;
+    bool want_row_start = true;
+    uint32_t width = 0, height = 0, n = 0;
+    std::vector<uint32_t> runs, row_start;
+    uint32_t rows() const { return n < runs_rows ? n : runs_rows; }
+    uint32_t word(uint32_t run, uint32_t w) const { return runs[(size_t)run * INFUR_RUN_WORDS + w]; }
+};
+
+/// The egress stage: a byte plane (class, confidence) or a u32 plane (labels, tracks) as raster-ordered runs of equal values
+/// within a row.  Integer results, identical from run to run.
+/// Command = skip (the runs of `value` are dropped) or emit everything; Input = a plane of uint8_t or uint32_t, Output = RunsOut.
+class Runs {
+public:
+    struct Cmd {
+        enum Kind { Skip, NoSkip } kind;
+        uint32_t value;
+    };
+    explicit Runs(Context& c) : c_(c) {}
+    Status control(Cmd cmd) {
+        const uint32_t flags = cmd.kind == Cmd::Skip ? (uint32_t)INFUR_RUNS_SKIP : 0u, value = cmd.kind == Cmd::Skip ? cmd.value : 0u;
+        if (cmd.kind != Cmd::Skip && cmd.kind != Cmd::NoSkip) return INFUR_E_INVALID_ARG;
+        dirty_ = dirty_ || flags != flags_ || value != skip_value_;
+        flags_ = flags;
+        skip_value_ = value;
+        return INFUR_OK;
+    }
+    bool is_dirty() const { return dirty_; }
+    Status advance(const std::vector<uint8_t>& plane, uint32_t height, uint32_t width, RunsOut& out) {
+        return run(plane.data(), plane.size(), 1, height, width, out);
+    }
+    Status advance(const std::vector<uint32_t>& plane, uint32_t height, uint32_t width, RunsOut& out) {
+        return run(plane.data(), plane.size(), 4, height, width, out);
+    }
+
+private:
+    Status run(const void* plane, size_t elems, uint32_t elem_bytes, uint32_t height, uint32_t width, RunsOut& out) {
+        dirty_ = false;
+        if (elems != (size_t)width * height) return INFUR_E_SHAPE;
+        out.width = width;
+        out.height = height;
+        out.n = 0;
+        out.runs.assign((size_t)out.runs_rows * INFUR_RUN_WORDS, 0);
+        out.row_start.assign(out.want_row_start ? (size_t)height + 1 : 0, 0);
+        const Status s = infur_runs(c_.get(), plane, elem_bytes, height, width, flags_, skip_value_, out.runs_rows ? out.runs.data() : nullptr,
+                                    out.runs_rows, out.want_row_start ? out.row_start.data() : nullptr, &out.n);
+        out.runs.resize((size_t)out.rows() * INFUR_RUN_WORDS);
+        return s;
+    }
+    Context& c_;
+    uint32_t flags_ = 0, skip_value_ = 0;
+    bool dirty_ = true;
+};
+
 /// infur_group: n contexts (one per GPU) of one process -- RCCL weight broadcast + frame-batch sharding
 /// (BASELINE configs[3]).  The contexts must outlive the group.
 class Group {

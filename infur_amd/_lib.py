@@ -54,6 +54,10 @@ TRACKS_TRUNCATED, TRACKS_OVERFLOW, TRACKS_IDS_EXHAUSTED = 1, 2, 4
 TRACKS_SUMMARY_STATUS, TRACKS_SUMMARY_CONTINUED, TRACKS_SUMMARY_NEW, TRACKS_SUMMARY_ENDED = range(4)
 TRACKS_SUMMARY_WORDS = 4
 FEATURE_TRACKS = 4
+# Runs (infur_runs / infur_frame_runs): the flag, the words of a record, the feature bit
+RUNS_SKIP = 1
+RUN_START, RUN_END, RUN_VALUE, RUN_WORDS = 0, 1, 2, 3
+FEATURE_RUNS = 8
 
 
 class Options(C.Structure):
@@ -167,6 +171,12 @@ SIGNATURES = {
                                        _u32p, _u32p, _vp, _u32, _vp, _vp, _vp, _vp]),
     "infur_frame_tracks_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp,
                                            _vp, _u32p, _u32p, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "infur_runs": (C.c_int32, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _vp]),
+    "infur_runs_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _vp]),
+    "infur_frame_runs": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _u32, _vp, _u32p,
+                                     _u32p]),
+    "infur_frame_runs_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _u32, _vp,
+                                         _u32p, _u32p]),
     "infur_stream_create": (C.c_int32, [_vp, _u32, C.POINTER(_vp)]),
     "infur_stream_destroy": (None, [_vp]),
     "infur_stream_add_lane": (C.c_int32, [_vp, _vp]),

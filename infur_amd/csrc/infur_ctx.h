@@ -171,6 +171,9 @@ struct infur_ctx {
     // Regions (infur_regions.cpp): the union-find scratch (parent, counts, ids, scan sums), the planes the frame calls decode into
     // when the caller does not want them, and the host-pointer calls' staging.  Grown lazily, like st_seg without moving mem_gen.
     infur::Buf st_reg, st_reg_planes, st_reg_io;
+    // Runs (infur_runs.cpp): the scan's block sums, the class plane the frame calls decode into, and the host-pointer calls'
+    // staging.  Private like the above.
+    infur::Buf st_runs, st_runs_plane, st_runs_io;
     // Tracks (infur_tracks.cpp): the live trackers of this context; infur_ctx_destroy releases their device memory and orphans them
     std::vector<infur_tracker*> trackers;
 

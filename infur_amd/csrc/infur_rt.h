@@ -7,6 +7,7 @@
 //   infur_segments.cpp      the Segments decode (class / confidence planes, statistics): C entry points
 //   infur_regions.cpp       Regions (connected components of the class plane, per-region table): C entry points
 //   infur_tracks.cpp        Tracks (region identities from frame to frame): the tracker object and its C entry points
+//   infur_runs.cpp          Runs (a class, label or track plane as run-length records): C entry points
 // Everything here lives in namespace infur and is NOT part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>

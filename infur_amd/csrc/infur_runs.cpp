@@ -1,0 +1,160 @@
+// infur_runs.cpp -- Runs, the egress stage behind the four decodes (include/infur_hip.h): a byte or u32 plane as raster-ordered
+// run-length records, a per-row index and the count, so that a host copies out only as many records as there are.  Kernels:
+// runs.hip.  Everything is enqueued on the context's stream.  Like infur_regions.cpp the frame path here always enqueues
+// eagerly, and every buffer of this file is private scratch no captured graph of the library can point into: growing it leaves
+// mem_gen -- and with it the graphs infur_frame_advance_dev has cached -- alone.
+#include <cstring>
+#include <new>
+
+#include "infur_ctx.h"
+#include "infur_rt.h"
+#include "kernels.h"
+
+using namespace infur;
+
+namespace {
+
+static_assert(kRunWords == INFUR_RUN_WORDS, "runs.hip and the header disagree about the record");
+
+constexpr size_t kRunsScratchFloor = 64 << 10;  // block sums of 16 Mi pixels: a captured infur_runs_dev keeps its pointer
+
+int32_t runs_check(infur_ctx* c, uint32_t elem_bytes, uint32_t flags, uint32_t skip_value) {
+    if (elem_bytes != 1 && elem_bytes != 4) return fail(c, INFUR_E_INVALID_ARG, "elem_bytes %u: 1 or 4", elem_bytes);
+    if (flags & ~(uint32_t)INFUR_RUNS_SKIP) return fail(c, INFUR_E_INVALID_ARG, "unknown runs flags 0x%x", flags);
+    if (elem_bytes == 1 && skip_value > 255) return fail(c, INFUR_E_INVALID_ARG, "skip_value %u: a byte plane holds at most 255", skip_value);
+    return INFUR_OK;
+}
+
+// st_runs_io: [count][row_start, h + 1 words][statistics table k x 8 u64][records, at most one per pixel][plane], on 256-byte boundaries
+struct RunStage {
+    size_t rows, row_start, stats, runs, plane, bytes;
+    RunStage(size_t npix, size_t h, uint32_t runs_rows, uint32_t k, size_t plane_bytes) {
+        rows = runs_rows < npix ? runs_rows : npix;
+        row_start = 256;
+        stats = row_start + align_up((h + 1) * 4, 256);
+        runs = stats + align_up((size_t)k * INFUR_STAT_WORDS * 8, 256);
+        plane = runs + align_up(rows * INFUR_RUN_WORDS * 4, 256);
+        bytes = plane + align_up(plane_bytes, 256);
+    }
+};
+
+// count, per-row index and the written records to the host: the count decides how many records there are to copy
+int32_t runs_read_back(infur_ctx* c, const uint8_t* base, const RunStage& st, size_t h, uint32_t* runs, uint32_t* row_start, uint32_t* n_runs) {
+    uint32_t n = 0;
+    HIPCHK(c, hipMemcpyAsync(&n, base, 4, hipMemcpyDeviceToHost, c->stream));
+    if (row_start) HIPCHK(c, hipMemcpyAsync(row_start, base + st.row_start, (h + 1) * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const size_t rows = n < st.rows ? n : st.rows;
+    if (runs && rows) HIPCHK(c, hipMemcpy(runs, base + st.runs, rows * INFUR_RUN_WORDS * 4, hipMemcpyDeviceToHost));
+    if (n_runs) *n_runs = n;
+    return INFUR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t infur_runs_dev(infur_ctx* c, const void* d_plane, uint32_t elem_bytes, uint32_t h, uint32_t w, uint32_t flags, uint32_t skip_value,
+                       void* d_runs, uint32_t runs_rows, void* d_row_start, void* d_n) {
+    return abi_call(c, [&]() -> int32_t {
+        if (!c) return INFUR_E_INVALID_ARG;
+        RETIF(runs_check(c, elem_bytes, flags, skip_value));
+        const size_t hw = (size_t)h * w;
+        if (hw >= 0xFFFFFFFFull) return fail(c, INFUR_E_INVALID_ARG, "%ux%u: a run indexes at most 2^32 - 2 pixels", w, h);
+        if (!(d_runs && runs_rows) && !d_row_start && !d_n) return fail(c, INFUR_E_INVALID_ARG, "no output wanted: runs (with rows), row_start or n_runs");
+        if (hw == 0) {  // empty plane: no run, every row starts at 0
+            if (d_n) HIPCHK(c, hipMemsetAsync(d_n, 0, 4, c->stream));
+            if (d_row_start) HIPCHK(c, hipMemsetAsync(d_row_start, 0, ((size_t)h + 1) * 4, c->stream));
+            return INFUR_OK;
+        }
+        if (!d_plane) return fail(c, INFUR_E_INVALID_ARG, "a %ux%u plane and no plane pointer", w, h);
+        const size_t scratch = runs_scratch_bytes(hw);
+        RETIF(ensure_private(c, c->st_runs, scratch > kRunsScratchFloor ? scratch : kRunsScratchFloor));
+        ProfScope ps(c, "runs", "runs", 0, (double)hw * elem_bytes * ((d_runs && runs_rows) || d_row_start ? 2 : 1));
+        HIPCHK(c, launch_runs(d_plane, (int)elem_bytes, h, w, (flags & INFUR_RUNS_SKIP) != 0, skip_value, c->st_runs.p, (unsigned*)d_runs, runs_rows,
+                              (unsigned*)d_row_start, (unsigned*)d_n, c->stream));
+        return INFUR_OK;
+    });
+}
+
+int32_t infur_runs(infur_ctx* c, const void* plane, uint32_t elem_bytes, uint32_t h, uint32_t w, uint32_t flags, uint32_t skip_value, uint32_t* runs,
+                   uint32_t runs_rows, uint32_t* row_start, uint32_t* n_runs) {
+    return abi_call(c, [&]() -> int32_t {
+        if (!c) return INFUR_E_INVALID_ARG;
+        RETIF(runs_check(c, elem_bytes, flags, skip_value));
+        const size_t hw = (size_t)h * w;
+        if (hw >= 0xFFFFFFFFull) return fail(c, INFUR_E_INVALID_ARG, "%ux%u: a run indexes at most 2^32 - 2 pixels", w, h);
+        if (!(runs && runs_rows) && !row_start && !n_runs) return fail(c, INFUR_E_INVALID_ARG, "no output wanted: runs (with rows), row_start or n_runs");
+        if (hw == 0) {
+            if (n_runs) *n_runs = 0;
+            if (row_start) std::memset(row_start, 0, ((size_t)h + 1) * 4);
+            return INFUR_OK;
+        }
+        if (!plane) return fail(c, INFUR_E_INVALID_ARG, "a %ux%u plane and no plane pointer", w, h);
+        const RunStage st(hw, h, runs ? runs_rows : 0, 0, hw * elem_bytes);
+        RETIF(ensure_private(c, c->st_runs_io, st.bytes));
+        uint8_t* base = (uint8_t*)c->st_runs_io.p;
+        HIPCHK(c, hipMemcpyAsync(base + st.plane, plane, hw * elem_bytes, hipMemcpyHostToDevice, c->stream));
+        RETIF(infur_runs_dev(c, base + st.plane, elem_bytes, h, w, flags, skip_value, st.rows ? base + st.runs : nullptr, (uint32_t)st.rows,
+                             row_start ? base + st.row_start : nullptr, base));
+        return runs_read_back(c, base, st, h, runs, row_start, n_runs);
+    });
+}
+
+int32_t infur_frame_runs_dev(infur_ctx* c, const void* d_bgr, uint32_t w, uint32_t h, float factor, uint32_t mode, uint32_t decode, uint32_t flags,
+                             uint32_t skip_value, void* d_runs, uint32_t runs_rows, void* d_row_start, uint32_t row_start_rows, void* d_n,
+                             void* d_stats, uint32_t stats_capacity, void* d_scaled, uint32_t* ow, uint32_t* oh) {
+    return abi_call(c, [&]() -> int32_t {
+        if (!c || !ow || !oh) return INFUR_E_INVALID_ARG;
+        RETIF(runs_check(c, 1, flags, skip_value));
+        uint32_t a = 0, b = 0;
+        const bool dims = infur_scale_validate(factor) == INFUR_OK && infur_scale_out_dims(w, h, factor, &a, &b) == INFUR_OK;
+        const size_t npix = dims ? (size_t)a * b : 0;
+        void* kl = nullptr;
+        if (c->loaded && npix) {
+            if (!(d_runs && runs_rows) && !d_row_start && !d_n)
+                return fail(c, INFUR_E_INVALID_ARG, "no output wanted: runs (with rows), row_start or n_runs");
+            if (d_row_start && row_start_rows < (size_t)b + 1)
+                return fail(c, INFUR_E_CAPACITY, "the row index needs %zu words, buffer has %u", (size_t)b + 1, row_start_rows);
+            RETIF(ensure_private(c, c->st_runs_plane, npix));  // the class plane is decoded into scratch
+            kl = c->st_runs_plane.p;
+        }  // (otherwise the call below fails before it decodes: bad scale, empty frame or no model)
+        // scale -> model -> Segments decode, with that call's own checks, errors and MODEL_NOT_LOADED rule
+        RETIF(infur_frame_segments_dev(c, d_bgr, w, h, factor, mode, decode, kl, nullptr, npix, d_stats, stats_capacity, nullptr, 0, d_scaled, ow, oh));
+        return infur_runs_dev(c, kl, 1, *oh, *ow, flags, skip_value, d_runs, runs_rows, d_row_start, d_n);
+    });
+}
+
+int32_t infur_frame_runs(infur_ctx* c, const uint8_t* bgr, uint32_t w, uint32_t h, float factor, uint32_t mode, uint32_t decode, uint32_t flags,
+                         uint32_t skip_value, uint32_t* runs, uint32_t runs_rows, uint32_t* row_start, uint32_t row_start_rows, uint32_t* n_runs,
+                         uint64_t* stats, uint32_t stats_capacity, uint8_t* scaled, uint32_t* ow, uint32_t* oh) {
+    return abi_call(c, [&]() -> int32_t {
+        if (!c || !ow || !oh) return INFUR_E_INVALID_ARG;
+        RETIF(runs_check(c, 1, flags, skip_value));
+        RunStage st(0, 0, 0, 0, 0);
+        uint8_t* base = nullptr;
+        return frame_host(
+            c, bgr, w, h, factor, scaled, ow, oh,
+            [&](size_t npix) -> int32_t {
+                // (as the _dev form: checked only where a model is loaded, so that without one Scale still runs)
+                if (c->loaded && row_start && row_start_rows < (size_t)*oh + 1)
+                    return fail(c, INFUR_E_CAPACITY, "the row index needs %zu words, buffer has %u", (size_t)*oh + 1, row_start_rows);
+                st = RunStage(npix, *oh, runs ? runs_rows : 0,
+                              stats ? (stats_capacity < (uint32_t)kSegMaxClasses ? stats_capacity : (uint32_t)kSegMaxClasses) : 0, 0);
+                RETIF(ensure_private(c, c->st_runs_io, st.bytes));
+                base = (uint8_t*)c->st_runs_io.p;
+                return INFUR_OK;
+            },
+            [&](void* d_bgr, void* d_scaled) {
+                return infur_frame_runs_dev(c, d_bgr, w, h, factor, mode, decode, flags, skip_value, st.rows ? base + st.runs : nullptr, (uint32_t)st.rows,
+                                            row_start ? base + st.row_start : nullptr, row_start_rows, ((runs && runs_rows) || row_start || n_runs) ? base : nullptr,
+                                            stats ? base + st.stats : nullptr, stats_capacity, d_scaled, ow, oh);
+            },
+            [&](size_t) -> int32_t {
+                if (stats) HIPCHK(c, hipMemcpyAsync(stats, base + st.stats, (size_t)c->num_classes * INFUR_STAT_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
+                return runs_read_back(c, base, st, *oh, runs, row_start, n_runs);
+            });
+    });
+}
+
+}  // extern "C"

@@ -311,4 +311,13 @@ hipError_t launch_tracks(const TrkMem& m, const unsigned* labels, const unsigned
 // forget the remembered frame; step: advance the frame counter (an empty frame); set_id: next_id = first_id; summary (optional) zeroed
 hipError_t launch_tracks_forget(TrkState* st, int step, int set_id, unsigned first_id, unsigned* summary, hipStream_t s);
 
+// Runs (runs.hip): an H x W plane of 1- or 4-byte elements as raster-ordered runs -- rows x kRunWords u32 records (START, END,
+// VALUE), the per-row index row_start[H + 1] and the count (each optional; d_n is a device word).  skip: runs of skip_value are
+// neither emitted nor counted.  scratch: runs_scratch_bytes(H * W) bytes the launches own for the call.  Stream-ordered; no
+// workgroup waits for another.  H * W in [1, 2^32 - 2].
+constexpr int kRunWords = 3;
+size_t runs_scratch_bytes(size_t npix);
+hipError_t launch_runs(const void* plane, int elem_bytes, unsigned H, unsigned W, int skip, unsigned skip_value, void* scratch, unsigned* runs,
+                       unsigned rows, unsigned* row_start, unsigned* d_n, hipStream_t s);
+
 }  // namespace infur

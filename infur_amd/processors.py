@@ -777,6 +777,109 @@ def track_summary(table: np.ndarray, track_table: np.ndarray, n: int, ow: int, o
     return recs
 
 
+@dataclass
+class RunsCmd:
+    """``Runs``' command: ``Skip(value)`` drops the runs of that value (``Skip(None)``: every run is emitted again)."""
+
+    skip: Optional[int] = None
+
+    @staticmethod
+    def Skip(v: Optional[int]) -> "RunsCmd":
+        return RunsCmd(skip=v)
+
+
+class RunsOut:
+    """``Runs``' ``&mut Output``: what to produce (``runs_rows`` records at most, ``want_row_start``) and, after ``advance``, the
+    results -- ``runs`` [min(n, runs_rows), 3] u32 (columns ``_lib.RUN_START``, ``_lib.RUN_END``, ``_lib.RUN_VALUE``) or None,
+    ``row_start`` [H + 1] u32 or None, ``n`` the number of runs (above ``len(runs)``: truncated)."""
+
+    def __init__(self, runs_rows: int = 1 << 16, want_row_start: bool = True):
+        self.runs_rows, self.want_row_start = runs_rows, want_row_start
+        self.runs = self.row_start = None
+        self.n = 0
+
+
+class Runs(Processor):
+    """The egress stage: a class / confidence plane (u8) or a label / track plane (u32) as raster-ordered runs.
+
+    Command = ``RunsCmd``.  Input = a plane [H, W] of u8 or u32; Output = ``RunsOut``.  A run is a maximal sequence of equal
+    values within one row; integers throughout, identical from run to run.
+    """
+
+    def __init__(self, ctx: Context, skip: Optional[int] = None):
+        self.ctx = ctx
+        self.skip = skip
+        self.dirty = True
+
+    def control(self, cmd: RunsCmd) -> "Runs":
+        if cmd.skip is not None and not 0 <= cmd.skip <= 0xFFFFFFFF:
+            raise InfurError(_lib.E_INVALID_ARG, f"skip value {cmd.skip}: a u32")
+        self.dirty = self.dirty or cmd.skip != self.skip
+        self.skip = cmd.skip
+        return self
+
+    def is_dirty(self) -> bool:
+        return self.dirty
+
+    def advance(self, inp: np.ndarray, out: RunsOut) -> None:
+        self.dirty = False
+        if inp.ndim != 2 or inp.dtype.itemsize not in (1, 4) or inp.dtype.kind not in "ui":
+            raise InfurError(_lib.E_SHAPE, f"expected an [H,W] plane of 1- or 4-byte integers, got {inp.shape} {inp.dtype}")
+        plane = np.ascontiguousarray(inp)
+        h, w = plane.shape
+        rows = max(0, min(int(out.runs_rows), h * w))
+        runs = np.empty((rows, _lib.RUN_WORDS), np.uint32) if rows else None
+        row_start = np.empty(h + 1, np.uint32) if out.want_row_start else None
+        n = C.c_uint32(0)
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        self.ctx.check(self.ctx.L.infur_runs(self.ctx.h, ptr(plane), plane.dtype.itemsize, h, w, _lib.RUNS_SKIP if self.skip is not None else 0,
+                                             self.skip or 0, ptr(runs), rows, ptr(row_start), C.addressof(n)))
+        out.n, out.row_start = n.value, row_start
+        out.runs = runs[:min(n.value, rows)] if runs is not None else None
+
+
+class RunsFrame(NamedTuple):
+    """``FramePath.advance_runs``: the records [min(n, runs_rows), 3] u32 of the class plane, the per-row index [oh + 1] u32, the
+    number of runs, the per-class statistics [k, 8] uint64 or None, the scaled BGR frame or None"""
+
+    runs: Optional[np.ndarray]
+    row_start: Optional[np.ndarray]
+    n: Optional[int]
+    stats: Optional[np.ndarray]
+    scaled: Optional[np.ndarray]
+
+
+def runs_decode(runs: np.ndarray, n: int, h: int, w: int, fill: int = 0, dtype=None) -> np.ndarray:
+    """The dense [h, w] plane of the first ``min(n, len(runs))`` records; pixels no record covers (skipped or truncated runs) read
+    ``fill``.  ``dtype``: uint8 when every value and ``fill`` fit a byte, else uint32."""
+    runs = np.asarray(runs, np.uint32).reshape(-1, _lib.RUN_WORDS)[:max(0, int(n))]
+    if dtype is None:
+        dtype = np.uint8 if fill <= 255 and (len(runs) == 0 or int(runs[:, _lib.RUN_VALUE].max()) <= 255) else np.uint32
+    out = np.full(h * w, fill, dtype)
+    start, end = runs[:, _lib.RUN_START].astype(np.int64), runs[:, _lib.RUN_END].astype(np.int64)
+    if len(runs):  # +v at each start and -v at each end, summed: runs never overlap
+        edge = np.zeros(h * w + 1, np.int64)
+        cover = np.zeros(h * w + 1, np.int64)
+        val = runs[:, _lib.RUN_VALUE].astype(np.int64)
+        np.add.at(edge, start, val)
+        np.add.at(edge, end, -val)
+        np.add.at(cover, start, 1)
+        np.add.at(cover, end, -1)
+        covered = np.cumsum(cover[:-1]) > 0
+        out[covered] = np.cumsum(edge[:-1])[covered].astype(dtype)
+    return out.reshape(h, w)
+
+
+def runs_by_value(runs: np.ndarray, n: int) -> dict:
+    """The first ``min(n, len(runs))`` records grouped by value: {value: [k, 2] u32 array of (START, END), in raster order} -- one
+    object's (class's, track's) mask as the runs to fill."""
+    runs = np.asarray(runs, np.uint32).reshape(-1, _lib.RUN_WORDS)[:max(0, int(n))]
+    order = np.argsort(runs[:, _lib.RUN_VALUE], kind="stable")
+    vals, first = np.unique(runs[order, _lib.RUN_VALUE], return_index=True)
+    parts = np.split(runs[order][:, [_lib.RUN_START, _lib.RUN_END]], first[1:]) if len(vals) else []
+    return {int(v): p for v, p in zip(vals, parts)}
+
+
 def pack_normalize(ctx: Context, img: np.ndarray) -> np.ndarray:
     """The pre-proc stage on its own (predict_onnx.rs:103-137): BGR u8 HWC -> RGB f32 CHW."""
     img = _check_bgr(img)
@@ -923,6 +1026,40 @@ class FramePath:
         k = min(n.value, rows)
         return TracksFrame(klass, conf, labels, table[:k] if table is not None else None, n.value, scaled,
                            tor[:k] if tor is not None else None, ttab[:k] if ttab is not None else None, plane, summary)
+
+    def advance_runs(self, img: np.ndarray, factor: float = 1.0, decode: int = _lib.DECODE_RAW, skip: Optional[int] = None,
+                     runs_rows: int = 1 << 16, want_row_start: bool = True, want_stats: bool = True,
+                     want_scaled: bool = False) -> RunsFrame:
+        """The fused path with the class plane run-length encoded, scale -> model -> Segments decode -> Runs, in one call ->
+        ``RunsFrame``: no dense plane crosses PCIe.  Every result field is None when no model is loaded (``scaled`` is still
+        produced)."""
+        img = _check_bgr(img)
+        h, w = img.shape[:2]
+        L = self.ctx.L
+        f = float(np.float32(factor))
+        rc = L.infur_scale_validate(f)
+        if rc:
+            raise ValidScaleError(rc)
+        ow, oh = C.c_uint32(0), C.c_uint32(0)
+        rc = L.infur_scale_out_dims(w, h, f, C.byref(ow), C.byref(oh))
+        if rc:
+            raise ScaleProcError(rc)
+        mi = _lib.ModelInfoC()
+        k = mi.num_classes if L.infur_model_info_get(self.ctx.h, C.byref(mi)) == _lib.OK else 0
+        rows = max(0, min(int(runs_rows), oh.value * ow.value))
+        runs = np.empty((rows, _lib.RUN_WORDS), np.uint32) if rows else None
+        row_start = np.empty(oh.value + 1, np.uint32) if want_row_start else None
+        stats = np.zeros((k, _lib.STAT_WORDS), np.uint64) if want_stats else None
+        scaled = np.empty((oh.value, ow.value, 3), np.uint8) if want_scaled else None
+        n = C.c_uint32(0)
+        ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
+        rc = L.infur_frame_runs(self.ctx.h, img.ctypes.data, w, h, f, self.scale_mode, decode, _lib.RUNS_SKIP if skip is not None else 0,
+                                skip or 0, ptr(runs), rows, ptr(row_start), oh.value + 1, C.addressof(n), ptr(stats), k, ptr(scaled),
+                                C.byref(ow), C.byref(oh))
+        if rc == _lib.E_MODEL_NOT_LOADED:
+            return RunsFrame(None, None, None, None, scaled)
+        self.ctx.check(rc)
+        return RunsFrame(runs[:min(n.value, rows)] if runs is not None else None, row_start, n.value, stats, scaled)
 
     def advance_batch(self, imgs, factor: float = 1.0, outs=None):
         """A batch of independent frames (BASELINE configs[3]) -> list of masks, in order.  ``outs``: caller-owned mask arrays to fill

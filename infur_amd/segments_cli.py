@@ -24,6 +24,13 @@ gains ``"track"`` (stable while the object overlaps itself from one frame to the
 ``"age"`` in frames and ``"dx"``, ``"dy"``, the step of its centroid since the previous frame (null for a new track), and every
 line ``"tracks": {"status", "continued", "new", "ended"}``.  ``--min-overlap N`` is the least number of common pixels that
 continues a track; ``--tracks-out`` receives the u32 track planes back to back (0xFFFFFFFF: not tracked).
+
+``--runs-out FILE`` receives a plane run-length encoded on the device: per frame a u32 count n followed by n records of three
+u32 (START = y*ow + x of the run's first pixel, END one past its last, VALUE), runs never crossing a row, in raster order, and
+every line gains ``"n_runs"``.  ``--runs-plane class|labels|tracks`` picks the plane (``labels`` needs ``--regions``, ``tracks``
+needs ``--tracks``); ``--runs-skip VALUE`` leaves the runs of that value out (0: the background class; 4294967295: pixels of no
+region / no track).  With the class plane and neither ``--labels-out`` nor ``--conf-out`` the frame goes through
+``infur_frame_runs``: records, count and the per-class table are all that crosses PCIe.
 """
 from __future__ import annotations
 
@@ -57,6 +64,9 @@ def main(argv=None) -> int:
     ap.add_argument("--tracks", action="store_true", help="carry region identities from frame to frame (implies --regions)")
     ap.add_argument("--min-overlap", type=int, default=1, help="common pixels a track needs to continue")
     ap.add_argument("--tracks-out", default="", help="raw u32 track planes, four bytes per pixel (needs --tracks)")
+    ap.add_argument("--runs-out", default="", help="run-length records of a plane: per frame a u32 count, then count x 3 u32")
+    ap.add_argument("--runs-plane", default="class", choices=["class", "labels", "tracks"], help="the plane --runs-out encodes")
+    ap.add_argument("--runs-skip", type=int, default=None, help="leave out the runs of this value")
     a = ap.parse_args(argv)
     if a.tracks_out and not a.tracks:
         ap.error("--tracks-out needs --tracks")
@@ -64,9 +74,16 @@ def main(argv=None) -> int:
     if a.regions_out and not a.regions:
         ap.error("--regions-out needs --regions")
 
+    if a.runs_out and a.runs_plane == "labels" and not a.regions:
+        ap.error("--runs-plane labels needs --regions")
+    if a.runs_out and a.runs_plane == "tracks" and not a.tracks:
+        ap.error("--runs-plane tracks needs --tracks")
+    if a.runs_skip is not None and not 0 <= a.runs_skip <= (255 if a.runs_plane == "class" else 0xFFFFFFFF):
+        ap.error("--runs-skip: a value of the plane (a byte for the class plane, a u32 otherwise)")
+
     from . import _lib
     from .app import RawVideoSource, VideoProcError
-    from .processors import Context, FramePath, Model, ModelCmd, class_summary, region_summary, track_summary
+    from .processors import Context, FramePath, Model, ModelCmd, Runs, RunsOut, SegmentsFrame, class_summary, region_summary, track_summary
 
     ctx = Context(device=a.device, dtype=a.dtype)
     model = Model(ctx)
@@ -89,11 +106,12 @@ def main(argv=None) -> int:
     freg = open(a.regions_out, "wb") if a.regions_out else None
     fconf = open(a.conf_out, "wb") if a.conf_out else None
     ftrk = open(a.tracks_out, "wb") if a.tracks_out else None
+    fruns = open(a.runs_out, "wb") if a.runs_out else None
     rpath = None
     if a.regions:
         oh, ow = _out_dims(ctx, a.width, a.height, a.scale)
         rpath = _RegionsPath(ctx, a.width, a.height, ow, oh, a.scale, fp.scale_mode, model.get_info().num_classes, max(0, a.max_regions),
-                             tracks=a.tracks)
+                             tracks=a.tracks, runs=fruns is not None)
         flags = _lib.REGIONS_SKIP_BACKGROUND if a.skip_background else 0
     n, t0 = 0, time.perf_counter()
     while True:
@@ -105,11 +123,20 @@ def main(argv=None) -> int:
             raise
         if rpath is not None:
             s, labels, table, nreg = rpath.advance(img, decode, a.connectivity, a.min_pixels, flags, flab is not None, fconf is not None,
-                                                   freg is not None)
+                                                   freg is not None, keep_labels=fruns is not None and a.runs_plane == "labels")
             if a.tracks:
-                ttab, tplane, tsum = rpath.track(max(0, a.min_overlap), ftrk is not None)
+                ttab, tplane, tsum = rpath.track(max(0, a.min_overlap), ftrk is not None, keep_plane=fruns is not None and a.runs_plane == "tracks")
+            if fruns is not None:
+                runs, nruns = rpath.runs(a.runs_plane, a.runs_skip)
+        elif fruns is not None and flab is None and fconf is None:  # records, count and captions: no dense plane comes back
+            r = fp.advance_runs(img, a.scale, decode, skip=a.runs_skip, runs_rows=1 << 32, want_row_start=False)
+            s, runs, nruns = SegmentsFrame(None, None, r.stats, None, None), r.runs, r.n
         else:
-            s = fp.advance_segments(img, a.scale, decode, want_klass=flab is not None, want_conf=fconf is not None)
+            s = fp.advance_segments(img, a.scale, decode, want_klass=flab is not None or fruns is not None, want_conf=fconf is not None)
+            if fruns is not None:  # the class plane is on the host anyway
+                ro = RunsOut(runs_rows=1 << 32, want_row_start=False)
+                Runs(ctx, skip=a.runs_skip).advance(s.klass, ro)
+                runs, nruns = ro.runs, ro.n
         oh, ow = (s.klass.shape if s.klass is not None else _out_dims(ctx, a.width, a.height, a.scale))
         if flab is not None:
             flab.write(memoryview(s.klass).cast("B"))
@@ -128,9 +155,13 @@ def main(argv=None) -> int:
                     ftrk.write(memoryview(tplane).cast("B"))
             if freg is not None:
                 freg.write(memoryview(labels).cast("B"))
+        if fruns is not None:
+            rec["n_runs"] = nruns
+            fruns.write(int(nruns).to_bytes(4, "little"))
+            fruns.write(memoryview(runs).cast("B"))
         fst.write(json.dumps(rec) + "\n")
         n += 1
-    for f in (flab, fconf, freg, ftrk, fst):
+    for f in (flab, fconf, freg, ftrk, fruns, fst):
         if f is not None:
             f.flush()
     el = time.perf_counter() - t0
@@ -146,7 +177,7 @@ class _RegionsPath:
     writes class plane, confidence plane and per-class table into device buffers, infur_regions_dev labels those planes where
     they are; the tables, the count and the planes that are written out are all that is copied back."""
 
-    def __init__(self, ctx, w, h, ow, oh, factor, scale_mode, classes, rows, tracks=False):
+    def __init__(self, ctx, w, h, ow, oh, factor, scale_mode, classes, rows, tracks=False, runs=False):
         import ctypes as C
 
         self.ctx, self.w, self.h, self.ow, self.oh, self.factor, self.mode = ctx, w, h, ow, oh, float(factor), scale_mode
@@ -154,7 +185,8 @@ class _RegionsPath:
         self.d = {}
         for name, n in (("bgr", w * h * 3), ("klass", ow * oh), ("conf", ow * oh), ("stats", classes * _STAT_BYTES), ("labels", ow * oh * 4),
                         ("table", self.rows * _ROW_BYTES), ("n", 4)) + \
-                ((("ttab", self.rows * _TRACK_BYTES), ("tplane", ow * oh * 4), ("tsum", 16)) if tracks else ()):
+                ((("ttab", self.rows * _TRACK_BYTES), ("tplane", ow * oh * 4), ("tsum", 16)) if tracks else ()) + \
+                ((("runs", ow * oh * _RUN_BYTES), ("nruns", 4)) if runs else ()):
             p = C.c_void_p(None)
             ctx.check(ctx.L.infur_dev_alloc(ctx.h, max(n, 4), C.byref(p)))
             self.d[name] = p
@@ -171,8 +203,9 @@ class _RegionsPath:
             self.ctx.check(self.ctx.L.infur_memcpy_d2h(self.ctx.h, out.ctypes.data, self.d[name], out.nbytes))
         return out
 
-    def advance(self, img, decode, connectivity, min_pixels, flags, want_klass, want_conf, want_labels):
-        """-> (SegmentsFrame with the planes that were asked for and the per-class table, labels or None, table rows, n)"""
+    def advance(self, img, decode, connectivity, min_pixels, flags, want_klass, want_conf, want_labels, keep_labels=False):
+        """-> (SegmentsFrame with the planes that were asked for and the per-class table, labels or None, table rows, n).
+        want_*: the plane is copied back; keep_labels: the label plane is written on the device (for `runs`) and stays there"""
         import ctypes as C
 
         import numpy as np
@@ -184,7 +217,7 @@ class _RegionsPath:
         c.check(L.infur_memcpy_h2d(c.h, d["bgr"], img.ctypes.data, img.nbytes))
         c.check(L.infur_frame_segments_dev(c.h, d["bgr"], self.w, self.h, self.factor, self.mode, decode, d["klass"], d["conf"], self.ow * self.oh,
                                            d["stats"], self.k, None, 0, None, C.byref(ow), C.byref(oh)))
-        c.check(L.infur_regions_dev(c.h, d["klass"], d["conf"], self.oh, self.ow, connectivity, min_pixels, flags, d["labels"] if want_labels or self.tracker else None,
+        c.check(L.infur_regions_dev(c.h, d["klass"], d["conf"], self.oh, self.ow, connectivity, min_pixels, flags, d["labels"] if want_labels or keep_labels or self.tracker else None,
                                     d["table"] if self.rows else None, self.rows, d["n"]))
         n = int(self._read("n", (1,), np.uint32)[0])
         seg = SegmentsFrame(self._read("klass", (self.oh, self.ow), np.uint8) if want_klass else None,
@@ -194,15 +227,27 @@ class _RegionsPath:
         self.n = n
         return seg, labels, self._read("table", (min(n, self.rows), _ROW_BYTES // 8), np.uint64), n
 
-    def track(self, min_overlap, want_plane):
-        """infur_tracks_dev on the frame `advance` just labelled -> (track table rows, track plane or None, summary)"""
+    def track(self, min_overlap, want_plane, keep_plane=False):
+        """infur_tracks_dev on the frame `advance` just labelled -> (track table rows, track plane or None, summary).
+        want_plane: the track plane is copied back; keep_plane: it is written on the device (for `runs`) and stays there"""
         import numpy as np
 
         c, d = self.ctx, self.d
         c.check(c.L.infur_tracks_dev(self.tracker, d["labels"], d["table"], self.rows, d["n"], self.oh, self.ow, min_overlap, None,
-                                     d["tplane"] if want_plane else None, d["ttab"] if self.rows else None, d["tsum"]))
+                                     d["tplane"] if want_plane or keep_plane else None, d["ttab"] if self.rows else None, d["tsum"]))
         return (self._read("ttab", (min(self.n, self.rows), _TRACK_BYTES // 8), np.uint64),
                 self._read("tplane", (self.oh, self.ow), np.uint32) if want_plane else None, self._read("tsum", (4,), np.uint32))
+
+    def runs(self, plane, skip):
+        """infur_runs_dev on a plane `advance` / `track` left on the device -> (records [n, 3] u32, n): every run, no dense plane"""
+        import numpy as np
+
+        c, d = self.ctx, self.d
+        src, elem = {"class": ("klass", 1), "labels": ("labels", 4), "tracks": ("tplane", 4)}[plane]
+        c.check(c.L.infur_runs_dev(c.h, d[src], elem, self.oh, self.ow, 1 if skip is not None else 0, skip or 0, d["runs"], self.ow * self.oh, None,
+                                   d["nruns"]))
+        n = int(self._read("nruns", (1,), np.uint32)[0])
+        return self._read("runs", (n, _RUN_BYTES // 4), np.uint32), n
 
     def close(self):
         if self.tracker:
@@ -216,6 +261,7 @@ class _RegionsPath:
 _STAT_BYTES = 8 * 8    # INFUR_STAT_WORDS u64 per class
 _ROW_BYTES = 10 * 8    # INFUR_REGION_WORDS u64 per region
 _TRACK_BYTES = 8 * 8   # INFUR_TRACK_WORDS u64 per region
+_RUN_BYTES = 3 * 4     # INFUR_RUN_WORDS u32 per run
 
 
 def _out_dims(ctx, w, h, factor):

@@ -129,6 +129,14 @@ pub const INFUR_TRACKS_SUMMARY_WORDS: u32 = 4;
 pub const INFUR_TRACK_NONE: u32 = 0xFFFF_FFFF;
 /// bit of `infur_features()`: the Tracks calls below exist
 pub const INFUR_FEATURE_TRACKS: u32 = 4;
+/// Runs: the flag, the words of a record (`INFUR_RUN_WORDS` u32 each)
+pub const INFUR_RUNS_SKIP: u32 = 1;
+pub const INFUR_RUN_START: u32 = 0;
+pub const INFUR_RUN_END: u32 = 1;
+pub const INFUR_RUN_VALUE: u32 = 2;
+pub const INFUR_RUN_WORDS: u32 = 3;
+/// bit of `infur_features()`: the Runs calls below exist
+pub const INFUR_FEATURE_RUNS: u32 = 8;
 
 extern "C" {
     pub fn infur_abi_version() -> u32;
@@ -292,4 +300,17 @@ extern "C" {
                                   table_rows: u32, d_n_regions: *mut c_void, d_scaled_bgr: *mut c_void, ow: *mut u32,
                                   oh: *mut u32, tracker: *mut c_void, min_overlap: u32, d_track_of_region: *mut c_void,
                                   d_track_plane: *mut c_void, d_track_table: *mut c_void, d_summary: *mut c_void) -> i32;
+    // Runs: a byte or u32 plane as run-length records
+    pub fn infur_runs(c: *mut infur_ctx, plane: *const c_void, elem_bytes: u32, h: u32, w: u32, flags: u32, skip_value: u32,
+                      runs: *mut u32, runs_rows: u32, row_start: *mut u32, n_runs: *mut u32) -> i32;
+    pub fn infur_runs_dev(c: *mut infur_ctx, d_plane: *const c_void, elem_bytes: u32, h: u32, w: u32, flags: u32, skip_value: u32,
+                          d_runs: *mut c_void, runs_rows: u32, d_row_start: *mut c_void, d_n_runs: *mut c_void) -> i32;
+    pub fn infur_frame_runs(c: *mut infur_ctx, bgr: *const u8, w: u32, h: u32, factor: f32, scale_mode: u32, decode: u32, flags: u32,
+                            skip_value: u32, runs: *mut u32, runs_rows: u32, row_start: *mut u32, row_start_rows: u32,
+                            n_runs: *mut u32, stats: *mut u64, stats_capacity: u32, scaled_bgr: *mut u8, ow: *mut u32,
+                            oh: *mut u32) -> i32;
+    pub fn infur_frame_runs_dev(c: *mut infur_ctx, d_bgr: *const c_void, w: u32, h: u32, factor: f32, scale_mode: u32, decode: u32,
+                                flags: u32, skip_value: u32, d_runs: *mut c_void, runs_rows: u32, d_row_start: *mut c_void,
+                                row_start_rows: u32, d_n_runs: *mut c_void, d_stats: *mut c_void, stats_capacity: u32,
+                                d_scaled_bgr: *mut c_void, ow: *mut u32, oh: *mut u32) -> i32;
 }

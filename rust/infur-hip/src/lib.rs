@@ -555,6 +555,62 @@ impl Processor for HipTracks {
     }
 }
 
+// ---------------------------------------------------------------- Runs (a plane as run-length records)
+/// A plane for `HipRuns`: class / confidence bytes or label / track words, with its `size` = [w, h].
+pub enum RunsPlaneData { U8(Vec<u8>), U32(Vec<u32>) }
+pub struct RunsPlane { pub size: [usize; 2], pub data: RunsPlaneData }
+/// What `HipRuns` produces: `runs` holds `min(n, runs_rows)` records of `INFUR_RUN_WORDS` words (START, END, VALUE) in raster
+/// order, `row_start` the `h + 1` words of the per-row index, `n` counts every run (above `runs_rows`: truncated).
+pub struct Runs { pub runs_rows: usize, pub want_row_start: bool, pub n: u32, pub runs: Vec<u32>, pub row_start: Vec<u32> }
+impl Default for Runs {
+    fn default() -> Self { Self { runs_rows: 1 << 16, want_row_start: true, n: 0, runs: Vec::new(), row_start: Vec::new() } }
+}
+impl Runs {
+    pub fn rows(&self) -> usize { (self.n as usize).min(self.runs_rows) }
+    pub fn word(&self, run: usize, word: u32) -> u32 { self.runs[run * sys::INFUR_RUN_WORDS as usize + word as usize] }
+}
+pub enum RunsCmd { Skip(u32), NoSkip }
+/// The egress stage: runs of equal values within a row, numbered in raster order.  Integer results, identical from run to run.
+pub struct HipRuns { ctx: Rc<Ctx>, skip: Option<u32>, dirty: bool }
+impl HipRuns {
+    pub fn new(ctx: Rc<Ctx>) -> Self { Self { ctx, skip: None, dirty: true } }
+}
+impl Processor for HipRuns {
+    type Command = RunsCmd;
+    type ControlError = HipError;
+    type Input = RunsPlane;
+    type Output = Runs;
+    type ProcessResult = Result<(), HipError>;
+
+    fn control(&mut self, cmd: RunsCmd) -> Result<&mut Self, HipError> {
+        let skip = match cmd { RunsCmd::Skip(v) => Some(v), RunsCmd::NoSkip => None };
+        self.dirty |= skip != self.skip;
+        self.skip = skip;
+        Ok(self)
+    }
+    fn is_dirty(&self) -> bool { self.dirty }
+    fn advance(&mut self, inp: &RunsPlane, out: &mut Runs) -> Result<(), HipError> {
+        self.dirty = false;
+        let [w, h] = inp.size;
+        let (ptr, len, elem_bytes) = match &inp.data {
+            RunsPlaneData::U8(p) => (p.as_ptr() as *const std::ffi::c_void, p.len(), 1u32),
+            RunsPlaneData::U32(p) => (p.as_ptr() as *const std::ffi::c_void, p.len(), 4u32),
+        };
+        if len != w * h { return Err(HipError::status(sys::INFUR_E_SHAPE)); }
+        out.runs.resize(out.runs_rows * sys::INFUR_RUN_WORDS as usize, 0);
+        out.row_start.resize(if out.want_row_start { h + 1 } else { 0 }, 0);
+        let rc = unsafe {
+            sys::infur_runs(self.ctx.0, ptr, elem_bytes, h as u32, w as u32, if self.skip.is_some() { sys::INFUR_RUNS_SKIP } else { 0 },
+                            self.skip.unwrap_or(0), if out.runs_rows > 0 { out.runs.as_mut_ptr() } else { std::ptr::null_mut() },
+                            out.runs_rows as u32, if out.want_row_start { out.row_start.as_mut_ptr() } else { std::ptr::null_mut() },
+                            &mut out.n)
+        };
+        if rc != sys::INFUR_OK { return Err(HipError::from_ctx(&self.ctx, rc)); }
+        out.runs.truncate(out.rows() * sys::INFUR_RUN_WORDS as usize);
+        Ok(())
+    }
+}
+
 // ---------------------------------------------------------------- streaming ring with zero-copy slots (main.rs:27-99,105; ABI 5)
 /// The bounded queue of frames in flight (`sync_channel(2)`, main.rs:105) over `infur_stream_*`.  `next_slot` / `commit` let the
 /// decoder fill the ring's own pinned buffer in place -- what `ff-video/src/decoder.rs:156-165` does with its reused `BgrImage` --

@@ -45,7 +45,7 @@ def d2d_copy_us(c, nbytes, reps=25):
     e0, e1 = C.c_void_p(None), C.c_void_p(None)
     assert hip.hipEventCreate(C.byref(e0)) == 0 and hip.hipEventCreate(C.byref(e1)) == 0
     src, dst = dev_alloc(c, nbytes), dev_alloc(c, nbytes)
-    stream = C.c_void_p(c.stream())
+    stream = C.c_void_p(c.stream)
     ts = []
     for i in range(reps + 5):
         assert hip.hipEventRecord(e0, stream) == 0
