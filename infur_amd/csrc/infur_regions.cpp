@@ -16,13 +16,6 @@ namespace {
 
 static_assert(kRegWords == INFUR_REGION_WORDS, "regions.hip and the header disagree about the row");
 
-int32_t reg_check(infur_ctx* c, uint32_t connectivity, uint32_t flags) {
-    if (connectivity != INFUR_CONNECT_4 && connectivity != INFUR_CONNECT_8)
-        return fail(c, INFUR_E_INVALID_ARG, "connectivity %u: 4 or 8", connectivity);
-    if (flags & ~(uint32_t)INFUR_REGIONS_SKIP_BACKGROUND) return fail(c, INFUR_E_INVALID_ARG, "unknown regions flags 0x%x", flags);
-    return INFUR_OK;
-}
-
 // st_reg_io: [count][table, at most one row per pixel][label plane][class plane][confidence plane], on 256-byte boundaries
 struct RegStage {
     size_t rows, table, labels, klass, conf, bytes;
@@ -57,8 +50,8 @@ int32_t infur_regions_dev(infur_ctx* c, const void* d_klass, const void* d_conf,
     return abi_call(c, [&]() -> int32_t {
         if (!c) return INFUR_E_INVALID_ARG;
         RETIF(reg_check(c, connectivity, flags));
+        RETIF(plane_check(c, h, w, "a label plane"));
         const size_t hw = (size_t)h * w;
-        if (hw >= 0xFFFFFFFFull) return fail(c, INFUR_E_INVALID_ARG, "%ux%u: a label plane indexes at most 2^32 - 2 pixels", w, h);
         if (!d_labels && !d_table && !d_n) return INFUR_E_INVALID_ARG;
         if (hw == 0) {  // empty image: no region, nothing else to write
             if (d_n) HIPCHK(c, hipMemsetAsync(d_n, 0, 4, c->stream));
@@ -79,8 +72,8 @@ int32_t infur_regions(infur_ctx* c, const uint8_t* klass, const uint8_t* conf, u
     return abi_call(c, [&]() -> int32_t {
         if (!c) return INFUR_E_INVALID_ARG;
         RETIF(reg_check(c, connectivity, flags));
+        RETIF(plane_check(c, h, w, "a label plane"));
         const size_t hw = (size_t)h * w;
-        if (hw >= 0xFFFFFFFFull) return fail(c, INFUR_E_INVALID_ARG, "%ux%u: a label plane indexes at most 2^32 - 2 pixels", w, h);
         if (!labels && !table && !n_regions) return INFUR_E_INVALID_ARG;
         if (hw == 0) {
             if (n_regions) *n_regions = 0;
@@ -105,9 +98,7 @@ int32_t infur_frame_regions_dev(infur_ctx* c, const void* d_bgr, uint32_t w, uin
     return abi_call(c, [&]() -> int32_t {
         if (!c || !ow || !oh) return INFUR_E_INVALID_ARG;
         RETIF(reg_check(c, connectivity, flags));
-        uint32_t a = 0, b = 0;
-        const bool dims = infur_scale_validate(factor) == INFUR_OK && infur_scale_out_dims(w, h, factor, &a, &b) == INFUR_OK;
-        const size_t npix = dims ? (size_t)a * b : 0;
+        const size_t npix = scale_npix(w, h, factor);
         void* kl = d_klass;
         void* cf = d_conf;
         if (c->loaded && npix) {

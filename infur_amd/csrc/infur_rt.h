@@ -8,6 +8,7 @@
 //   infur_regions.cpp       Regions (connected components of the class plane, per-region table): C entry points
 //   infur_tracks.cpp        Tracks (region identities from frame to frame): the tracker object and its C entry points
 //   infur_runs.cpp          Runs (a class, label or track plane as run-length records): C entry points
+// (wave_scan.h, the device code regions.hip, tracks.hip and runs.hip share, also holds kScanBlock, which sizes their block sums)
 // Everything here lives in namespace infur and is NOT part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -130,6 +131,14 @@ struct EventPair {  // two timing events, released on every return path
 // ---- the front half of every fused frame call (infur_capi.cpp) ----
 // infur_scale_validate + infur_scale_out_dims, with their messages: -> the scaled dimensions
 int32_t scale_dims(infur_ctx* c, uint32_t w, uint32_t h, float factor, uint32_t* ow, uint32_t* oh);
+// The same, silently, for the _dev frame calls of the stages behind Segments, which size their scratch before the call that
+// reports the error: -> the scaled frame's pixels (*oh, optional: its rows); 0 when the factor or the dimensions are refused
+inline size_t scale_npix(uint32_t w, uint32_t h, float factor, uint32_t* oh = nullptr) {
+    uint32_t a = 0, b = 0;
+    if (infur_scale_validate(factor) != INFUR_OK || infur_scale_out_dims(w, h, factor, &a, &b) != INFUR_OK) return 0;
+    if (oh) *oh = b;
+    return (size_t)a * b;
+}
 // What the _dev frame calls check before their own outputs: the scale mode, scale_dims, the frame, an empty frame -> E_SHAPE,
 // and the no-model rule (the Scale stage still runs, then E_MODEL_NOT_LOADED).  -> *ow x *oh = *npix pixels
 int32_t frame_check(infur_ctx* c, const void* d_bgr, uint32_t w, uint32_t h, float factor, uint32_t mode, void* d_scaled, uint32_t* ow,
@@ -160,6 +169,20 @@ int32_t frame_host(infur_ctx* c, const uint8_t* bgr, uint32_t w, uint32_t h, flo
     if (rc == INFUR_OK) RETIF(read_back(npix));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return rc;
+}
+
+// ---- argument checks several stages share ----
+// a plane of 32-bit pixel indices; noun: what indexes it ("a run", "a label plane")
+inline int32_t plane_check(infur_ctx* c, uint32_t h, uint32_t w, const char* noun) {
+    if ((size_t)h * w >= 0xFFFFFFFFull) return fail(c, INFUR_E_INVALID_ARG, "%ux%u: %s indexes at most 2^32 - 2 pixels", w, h, noun);
+    return INFUR_OK;
+}
+// Regions' connectivity and flags (infur_regions.cpp, and the fused calls of infur_tracks.cpp)
+inline int32_t reg_check(infur_ctx* c, uint32_t connectivity, uint32_t flags) {
+    if (connectivity != INFUR_CONNECT_4 && connectivity != INFUR_CONNECT_8)
+        return fail(c, INFUR_E_INVALID_ARG, "connectivity %u: 4 or 8", connectivity);
+    if (flags & ~(uint32_t)INFUR_REGIONS_SKIP_BACKGROUND) return fail(c, INFUR_E_INVALID_ARG, "unknown regions flags 0x%x", flags);
+    return INFUR_OK;
 }
 
 // quantised models (infur_quant_model.cpp)

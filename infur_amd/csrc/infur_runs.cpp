@@ -59,8 +59,8 @@ int32_t infur_runs_dev(infur_ctx* c, const void* d_plane, uint32_t elem_bytes, u
     return abi_call(c, [&]() -> int32_t {
         if (!c) return INFUR_E_INVALID_ARG;
         RETIF(runs_check(c, elem_bytes, flags, skip_value));
+        RETIF(plane_check(c, h, w, "a run"));
         const size_t hw = (size_t)h * w;
-        if (hw >= 0xFFFFFFFFull) return fail(c, INFUR_E_INVALID_ARG, "%ux%u: a run indexes at most 2^32 - 2 pixels", w, h);
         if (!(d_runs && runs_rows) && !d_row_start && !d_n) return fail(c, INFUR_E_INVALID_ARG, "no output wanted: runs (with rows), row_start or n_runs");
         if (hw == 0) {  // empty plane: no run, every row starts at 0
             if (d_n) HIPCHK(c, hipMemsetAsync(d_n, 0, 4, c->stream));
@@ -82,8 +82,8 @@ int32_t infur_runs(infur_ctx* c, const void* plane, uint32_t elem_bytes, uint32_
     return abi_call(c, [&]() -> int32_t {
         if (!c) return INFUR_E_INVALID_ARG;
         RETIF(runs_check(c, elem_bytes, flags, skip_value));
+        RETIF(plane_check(c, h, w, "a run"));
         const size_t hw = (size_t)h * w;
-        if (hw >= 0xFFFFFFFFull) return fail(c, INFUR_E_INVALID_ARG, "%ux%u: a run indexes at most 2^32 - 2 pixels", w, h);
         if (!(runs && runs_rows) && !row_start && !n_runs) return fail(c, INFUR_E_INVALID_ARG, "no output wanted: runs (with rows), row_start or n_runs");
         if (hw == 0) {
             if (n_runs) *n_runs = 0;
@@ -107,9 +107,8 @@ int32_t infur_frame_runs_dev(infur_ctx* c, const void* d_bgr, uint32_t w, uint32
     return abi_call(c, [&]() -> int32_t {
         if (!c || !ow || !oh) return INFUR_E_INVALID_ARG;
         RETIF(runs_check(c, 1, flags, skip_value));
-        uint32_t a = 0, b = 0;
-        const bool dims = infur_scale_validate(factor) == INFUR_OK && infur_scale_out_dims(w, h, factor, &a, &b) == INFUR_OK;
-        const size_t npix = dims ? (size_t)a * b : 0;
+        uint32_t b = 0;
+        const size_t npix = scale_npix(w, h, factor, &b);
         void* kl = nullptr;
         if (c->loaded && npix) {
             if (!(d_runs && runs_rows) && !d_row_start && !d_n)

@@ -9,6 +9,7 @@
 #include "infur_ctx.h"
 #include "infur_rt.h"
 #include "kernels.h"
+#include "wave_scan.h"
 
 using namespace infur;
 
@@ -102,7 +103,8 @@ int32_t infur_tracker_create(infur_ctx* c, uint32_t max_regions, uint32_t pair_s
         t->max_regions = M;
         t->pair_slots = S;
         const size_t a8 = align_up((size_t)M * 8, 256), a4 = align_up((size_t)M * 4, 256);
-        const size_t part = align_up(((size_t)M / 1024 + 1) * 4, 256), keys = align_up((size_t)S * 8, 256), cnts = align_up((size_t)S * 4, 256);
+        // (one word more than scan_blocks(M) where kScanBlock divides M: kept, so that the allocation is byte for byte what it was)
+        const size_t part = align_up(((size_t)M / kScanBlock + 1) * 4, 256), keys = align_up((size_t)S * 8, 256), cnts = align_up((size_t)S * 4, 256);
         const size_t bytes = 256 + 5 * a8 + 7 * a4 + part + keys + cnts;
         if (hipMalloc(&t->mem, bytes) != hipSuccess) {
             (void)hipGetLastError();
@@ -176,8 +178,8 @@ int32_t infur_tracks_dev(void* tracker, const void* d_labels, const void* d_tabl
     return abi_call(c, [&]() -> int32_t {
         if (!c) return INFUR_E_INVALID_ARG;
         infur_tracker* t = (infur_tracker*)tracker;
+        RETIF(plane_check(c, h, w, "a label plane"));
         const size_t hw = (size_t)h * w;
-        if (hw >= 0xFFFFFFFFull) return fail(c, INFUR_E_INVALID_ARG, "%ux%u: a label plane indexes at most 2^32 - 2 pixels", w, h);
         if (!d_tor && !d_plane && !d_ttab && !d_summary) return INFUR_E_INVALID_ARG;
         if (hw == 0) {  // empty frame: nothing to track, nothing remembered
             HIPCHK(c, launch_tracks_forget(t->m.st, 1, 0, 0, (unsigned*)d_summary, c->stream));
@@ -200,8 +202,8 @@ int32_t infur_tracks(void* tracker, const uint32_t* labels, const uint64_t* tabl
     return abi_call(c, [&]() -> int32_t {
         if (!c) return INFUR_E_INVALID_ARG;
         infur_tracker* t = (infur_tracker*)tracker;
+        RETIF(plane_check(c, h, w, "a label plane"));
         const size_t hw = (size_t)h * w;
-        if (hw >= 0xFFFFFFFFull) return fail(c, INFUR_E_INVALID_ARG, "%ux%u: a label plane indexes at most 2^32 - 2 pixels", w, h);
         if (!tor && !plane && !ttab && !summary) return INFUR_E_INVALID_ARG;
         if (hw && (!labels || (!table && table_rows && n_regions))) return INFUR_E_INVALID_ARG;
         const TrkStage st(hw, table_rows, false);
@@ -227,9 +229,7 @@ int32_t infur_frame_tracks_dev(infur_ctx* c, const void* d_bgr, uint32_t w, uint
         if (!c || !ow || !oh || trk_ctx(tracker) != c) return INFUR_E_INVALID_ARG;
         if (!d_tor && !d_plane && !d_ttab && !d_summary) return INFUR_E_INVALID_ARG;
         infur_tracker* t = (infur_tracker*)tracker;
-        uint32_t a = 0, b = 0;
-        const bool dims = infur_scale_validate(factor) == INFUR_OK && infur_scale_out_dims(w, h, factor, &a, &b) == INFUR_OK;
-        const size_t npix = dims ? (size_t)a * b : 0;
+        const size_t npix = scale_npix(w, h, factor);
         void* lab = d_labels;
         void* tab = d_table;
         void* dn = d_n;
@@ -258,9 +258,7 @@ int32_t infur_frame_tracks(infur_ctx* c, const uint8_t* bgr, uint32_t w, uint32_
                            uint32_t* summary) {
     return abi_call(c, [&]() -> int32_t {
         if (!c || !ow || !oh || trk_ctx(tracker) != c) return INFUR_E_INVALID_ARG;
-        if (connectivity != INFUR_CONNECT_4 && connectivity != INFUR_CONNECT_8)
-            return fail(c, INFUR_E_INVALID_ARG, "connectivity %u: 4 or 8", connectivity);
-        if (flags & ~(uint32_t)INFUR_REGIONS_SKIP_BACKGROUND) return fail(c, INFUR_E_INVALID_ARG, "unknown regions flags 0x%x", flags);
+        RETIF(reg_check(c, connectivity, flags));
         if (!tor && !plane && !ttab && !summary) return INFUR_E_INVALID_ARG;
         infur_tracker* t = (infur_tracker*)tracker;
         TrkStage st(0, 0, true);

@@ -300,7 +300,7 @@ struct TrkMem {
     unsigned long long *ppix, *psx, *psy;  // remembered regions: PIXELS, SUM_X, SUM_Y
     unsigned *pclass, *ptrack, *page, *pborn;
     unsigned *ctrack, *cage, *cborn;  // current regions, until the save launch
-    unsigned* partial;                // block sums of the scan: M / 1024 + 1 words
+    unsigned* partial;                // block sums of the scan: M / kScanBlock + 1 words (wave_scan.h)
     unsigned* prev;
     unsigned slots, M;
 };

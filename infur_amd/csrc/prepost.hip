@@ -9,6 +9,7 @@
 //   upsample_argmax_shade  fusion of the last two: reads the 2.7 MB output-stride-8 logits
 //                        instead of writing + re-reading 174 MB of full-resolution logits.
 #include "kernels.h"
+#include "wave_scan.h"
 
 namespace infur {
 
@@ -613,18 +614,14 @@ __device__ __forceinline__ void seg_row_stats(unsigned* __restrict__ sstat, cons
                                               const unsigned x0, const unsigned y) {
     uint64_t todo = __ballot(live);
     if (!todo) return;
-    uint64_t plane[8];
-#pragma unroll
-    for (int b = 0; b < 8; b++) plane[b] = __ballot(live && ((conf >> b) & 1));
+    const BitPlanes8 planes((unsigned)conf, live);
     const int lane = threadIdx.x & 63;
     while (todo) {
         const int kc = __builtin_amdgcn_readlane(k, __builtin_ctzll(todo));
         const uint64_t m = __ballot(live && k == kc);
         todo &= ~m;
         const unsigned n = (unsigned)__popcll(m);
-        unsigned sconf = 0;
-#pragma unroll
-        for (int b = 0; b < 8; b++) sconf += (unsigned)__popcll(m & plane[b]) << b;
+        const unsigned sconf = planes.sum(m);
         const unsigned lo = x0 + (unsigned)__builtin_ctzll(m), hi = x0 + 63u - (unsigned)__builtin_clzll(m);
         const unsigned word[8] = {n, n * x0 + seg_bit_positions(m), n * y, sconf, ~lo, ~y, hi, y};
         unsigned v = word[0];

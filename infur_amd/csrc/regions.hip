@@ -2,20 +2,21 @@
 // behind Segments: from the class bytes (and optionally the confidence bytes) a u32 label plane, a per-region table and the
 // region count.  A block-based union-find over parent[h*w] (u32; a root is the smallest linear index of its set), in separate
 // launches -- the kernel boundaries are the only ordering between the phases, no workgroup ever waits for another:
-//   1 tile      64 x 32 tiles labelled in LDS: horizontal runs from one ballot per wave-row, vertical / diagonal links as
-//               unions between run heads, one flatten pass that stores each pixel's tile root as a global index
+//   1 tile      64 x 32 tiles labelled in LDS: horizontal runs from one ballot per wave-row (wave_run_starts), vertical /
+//               diagonal links as unions between run heads, one flatten pass that stores each pixel's tile root as a global index
 //   2 seam      one lane per pixel on a tile border: find + union-by-min over the global array, relaxed agent-scope atomics only
 //   3 flatten   every pixel finds its root; per-root pixel counts, one atomic per run of a wave-row
 //   4 scan      kept roots (count >= min_pixels, not class 0 under the skip flag) flagged, exclusive prefix sum in raster order
-//               = dense ids in ascending order of the root index: block sums, one-workgroup scan of the sums, apply
+//               = dense ids in ascending order of the root index: flag_block_sum, scan_block_sums, flag_rank
 //   5 relabel   label plane (dword stores) and the table rows (64-bit integer atomics, one set per run of a wave-row)
-// Everything is an integer and every id is a function of the partition alone, so the bytes do not depend on the order in
-// which atomics arrive, on the tile shape or on the device.
+// The scan, the wave-row (wave_row) and its runs are wave_scan.h's.  Everything is an integer and every id is a function of the
+// partition alone, so the bytes do not depend on the order in which atomics arrive, on the tile shape or on the device.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "kernels.h"
+#include "wave_scan.h"
 
 namespace infur {
 
@@ -23,7 +24,6 @@ namespace {
 
 constexpr int kRegTW = 64, kRegTH = 32;  // tile: one wave-row wide, eight rows per wave
 constexpr unsigned kRegNone = 0xFFFFFFFFu;
-constexpr int kRegScan = 1024;  // elements per workgroup of the scan launches
 
 // ---- union-find in LDS (tile-local indices r * 64 + lane; the parent of a node is never larger than the node) ----
 __device__ __forceinline__ unsigned lds_find(unsigned* lp, unsigned a) {
@@ -49,17 +49,6 @@ __device__ __forceinline__ void lds_union(unsigned* lp, unsigned a, unsigned b) 
     }
 }
 
-// start of the run lane `lane` belongs to, from the mask of run starts (bit 0 is always set)
-__device__ __forceinline__ unsigned run_start(const uint64_t starts, const int lane) {
-    return 63u - (unsigned)__builtin_clzll(starts & (~0ull >> (63 - lane)));
-}
-
-// length of the run that starts at `lane` (lanes outside the image count as starts, so a run ends at the image edge)
-__device__ __forceinline__ unsigned run_length(const uint64_t starts, const int lane) {
-    const uint64_t above = lane == 63 ? 0ull : (starts >> (lane + 1));
-    return above ? (unsigned)__builtin_ctzll(above) + 1u : 64u - (unsigned)lane;
-}
-
 __global__ void __launch_bounds__(256)
     regions_tile_kernel(const uint8_t* __restrict__ klass, unsigned H, unsigned W, unsigned tilesX, int conn8, unsigned* __restrict__ parent) {
     __shared__ unsigned lp[kRegTH * kRegTW];
@@ -72,8 +61,8 @@ __global__ void __launch_bounds__(256)
         const unsigned y = y0 + r;
         const bool live = x < W && y < H;
         const int c = live ? (int)klass[(size_t)y * W + x] : -1;
-        const int cl = __shfl_up(c, 1, 64);
-        const uint64_t starts = ~__ballot(live && lane > 0 && c == cl);
+        bool cont;
+        const uint64_t starts = wave_run_starts(c, live, &cont);
         lp[r * kRegTW + lane] = (unsigned)(r * kRegTW) + run_start(starts, lane);
         cls[r * kRegTW + lane] = (short)c;
     }
@@ -152,22 +141,6 @@ __global__ void __launch_bounds__(256) regions_seam_kernel(const uint8_t* __rest
     }
 }
 
-// A wave is 64 consecutive columns of one row (four wave-rows per workgroup, numbered in raster order).
-struct WaveRow {
-    unsigned x, y;
-    bool live;
-    size_t at;
-};
-__device__ __forceinline__ WaveRow wave_row(unsigned H, unsigned W, unsigned tilesX) {
-    const size_t u = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    WaveRow r;
-    r.y = (unsigned)(u / tilesX);
-    r.x = (unsigned)(u % tilesX) * 64 + (threadIdx.x & 63);
-    r.live = r.y < H && r.x < W;
-    r.at = (size_t)r.y * W + r.x;
-    return r;
-}
-
 // every pixel finds its root (whatever a racing store of this pass has left in a word is an ancestor too); the pixel count of
 // a root is pre-aggregated per run of equal roots in the wave-row: one atomic per run
 __global__ void __launch_bounds__(256) regions_flatten_count_kernel(unsigned H, unsigned W, unsigned tilesX, unsigned* parent, unsigned* cnt) {
@@ -179,9 +152,8 @@ __global__ void __launch_bounds__(256) regions_flatten_count_kernel(unsigned H, 
         while ((q = parent[a]) != a) a = q;
         parent[p.at] = root = a;
     }
-    const unsigned rl = __shfl_up(root, 1, 64);
-    const bool cont = p.live && lane > 0 && root == rl;
-    const uint64_t starts = ~__ballot(cont);
+    bool cont;
+    const uint64_t starts = wave_run_starts(root, p.live, &cont);
     if (p.live && !cont) atomicAdd(&cnt[root], run_length(starts, lane));
 }
 
@@ -190,68 +162,36 @@ __device__ __forceinline__ bool reg_keep(const size_t i, const unsigned* __restr
     return parent[i] == (unsigned)i && cnt[i] >= min_pixels && !(skip_bg && klass[i] == 0);
 }
 
-// ---- the three-launch exclusive scan of the kept-root flags ----
-__global__ void __launch_bounds__(kRegScan) regions_scan_sums_kernel(const unsigned* __restrict__ parent, const unsigned* __restrict__ cnt,
-                                                                     const uint8_t* __restrict__ klass, size_t N, unsigned min_pixels, int skip_bg,
-                                                                     unsigned* __restrict__ partial) {
-    __shared__ unsigned wsum[kRegScan / 64];
-    const size_t i = (size_t)blockIdx.x * kRegScan + threadIdx.x;
-    const uint64_t m = __ballot(i < N && reg_keep(i, parent, cnt, klass, min_pixels, skip_bg));
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = (unsigned)__popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned s = 0;
-        for (int k = 0; k < kRegScan / 64; k++) s += wsum[k];
-        partial[blockIdx.x] = s;
-    }
+// ---- the three-launch exclusive scan of the kept-root flags (wave_scan.h) ----
+__global__ void __launch_bounds__(kScanBlock) regions_scan_sums_kernel(const unsigned* __restrict__ parent, const unsigned* __restrict__ cnt,
+                                                                       const uint8_t* __restrict__ klass, size_t N, unsigned min_pixels, int skip_bg,
+                                                                       unsigned* __restrict__ partial) {
+    __shared__ unsigned wsum[kScanBlock / 64];
+    const size_t i = (size_t)blockIdx.x * kScanBlock + threadIdx.x;
+    const unsigned s = flag_block_sum(i < N && reg_keep(i, parent, cnt, klass, min_pixels, skip_bg), wsum);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
 // one workgroup: partial[] -> its exclusive prefix sums in place, the total to total[0] and, when wanted, to the caller's word
-__global__ void __launch_bounds__(kRegScan) regions_scan_partials_kernel(unsigned* __restrict__ partial, size_t NB, unsigned* __restrict__ total,
-                                                                         unsigned* __restrict__ d_n) {
-    __shared__ unsigned wsum[kRegScan / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned carry = 0;
-    for (size_t base = 0; base < NB; base += kRegScan) {
-        const size_t i = base + threadIdx.x;
-        const unsigned v = i < NB ? partial[i] : 0u;
-        unsigned inc = v;
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned t = __shfl_up(inc, d, 64);
-            if (lane >= d) inc += t;
-        }
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        unsigned before = 0, all = 0;
-        for (int k = 0; k < kRegScan / 64; k++) {
-            const unsigned s = wsum[k];
-            before += k < wave ? s : 0u;
-            all += s;
-        }
-        __syncthreads();
-        if (i < NB) partial[i] = carry + before + inc - v;
-        carry += all;
-    }
+__global__ void __launch_bounds__(kScanBlock) regions_scan_partials_kernel(unsigned* __restrict__ partial, size_t NB, unsigned* __restrict__ total,
+                                                                           unsigned* __restrict__ d_n) {
+    __shared__ unsigned wsum[kScanBlock / 64];
+    const unsigned n = scan_block_sums(partial, NB, wsum);
     if (threadIdx.x == 0) {
-        total[0] = carry;
-        if (d_n) d_n[0] = carry;
+        total[0] = n;
+        if (d_n) d_n[0] = n;
     }
 }
 
 // ids[i] = dense id of a kept root, INFUR_REGION_NONE for every other pixel
-__global__ void __launch_bounds__(kRegScan) regions_scan_apply_kernel(const unsigned* __restrict__ parent, const unsigned* __restrict__ cnt,
-                                                                      const uint8_t* __restrict__ klass, size_t N, unsigned min_pixels, int skip_bg,
-                                                                      const unsigned* __restrict__ partial, unsigned* __restrict__ ids) {
-    __shared__ unsigned wsum[kRegScan / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const size_t i = (size_t)blockIdx.x * kRegScan + threadIdx.x;
+__global__ void __launch_bounds__(kScanBlock) regions_scan_apply_kernel(const unsigned* __restrict__ parent, const unsigned* __restrict__ cnt,
+                                                                        const uint8_t* __restrict__ klass, size_t N, unsigned min_pixels, int skip_bg,
+                                                                        const unsigned* __restrict__ partial, unsigned* __restrict__ ids) {
+    __shared__ unsigned wsum[kScanBlock / 64];
+    const size_t i = (size_t)blockIdx.x * kScanBlock + threadIdx.x;
     const bool keep = i < N && reg_keep(i, parent, cnt, klass, min_pixels, skip_bg);
-    const uint64_t m = __ballot(keep);
-    if (lane == 0) wsum[wave] = (unsigned)__popcll(m);
-    __syncthreads();
-    unsigned before = partial[blockIdx.x];
-    for (int k = 0; k < wave; k++) before += wsum[k];
-    if (i < N) ids[i] = keep ? before + (unsigned)__popcll(m & ((1ull << lane) - 1ull)) : kRegNone;
+    const unsigned id = flag_rank(keep, partial[blockIdx.x], wsum);
+    if (i < N) ids[i] = keep ? id : kRegNone;
 }
 
 // rows [0, min(n, rows)) of the caller's table get the empty-row values; rows at or beyond n are left alone
@@ -265,7 +205,7 @@ __global__ void __launch_bounds__(256) regions_table_init_kernel(unsigned long l
 }
 
 // label plane + table.  Per run of equal roots in a wave-row its head lane applies the eight statistics words; the sum of the
-// confidence bytes over the run comes from the eight ballots of their bit planes (Segments' idiom).
+// confidence bytes over the run comes from the eight ballots of their bit planes (BitPlanes8).
 __global__ void __launch_bounds__(256)
     regions_relabel_kernel(const uint8_t* __restrict__ klass, const uint8_t* __restrict__ conf, unsigned H, unsigned W, unsigned tilesX,
                            const unsigned* __restrict__ parent, const unsigned* __restrict__ ids, unsigned* __restrict__ labels,
@@ -277,20 +217,15 @@ __global__ void __launch_bounds__(256)
     if (labels && p.live) labels[p.at] = id;
     if (!table) return;
     const unsigned cf = (conf && p.live) ? conf[p.at] : 0u;
-    uint64_t plane[8];
-#pragma unroll
-    for (int b = 0; b < 8; b++) plane[b] = __ballot((cf >> b) & 1u);
-    const unsigned rl = __shfl_up(root, 1, 64);
-    const bool cont = p.live && lane > 0 && root == rl;
-    const uint64_t starts = ~__ballot(cont);
+    const BitPlanes8 planes(cf, true);
+    bool cont;
+    const uint64_t starts = wave_run_starts(root, p.live, &cont);
     if (!p.live || id >= rows) return;
     unsigned long long* row = table + (size_t)id * kRegWords;
     if (!cont) {
         const unsigned long long n = run_length(starts, lane);
         const uint64_t run = (n == 64 ? ~0ull : ((1ull << n) - 1ull)) << lane;
-        unsigned long long sconf = 0;
-#pragma unroll
-        for (int b = 0; b < 8; b++) sconf += (unsigned long long)__popcll(run & plane[b]) << b;
+        const unsigned long long sconf = planes.sum(run);
         atomicAdd(row + 0, n);
         atomicAdd(row + 1, n * p.x + n * (n - 1) / 2);
         atomicAdd(row + 2, n * p.y);
@@ -311,11 +246,11 @@ inline size_t reg_align(size_t v) { return (v + 255) / 256 * 256; }
 }  // namespace
 
 // parent, counts, ids (u32 per pixel each) + the scan's block sums + the total
-size_t regions_scratch_bytes(size_t npix) { return 3 * reg_align(npix * 4) + reg_align((npix + kRegScan - 1) / kRegScan * 4) + 256; }
+size_t regions_scratch_bytes(size_t npix) { return 3 * reg_align(npix * 4) + reg_align(scan_blocks(npix) * 4) + 256; }
 
 hipError_t launch_regions(const uint8_t* klass, const uint8_t* conf, unsigned H, unsigned W, int conn8, unsigned min_pixels, int skip_bg,
                           void* scratch, unsigned* labels, unsigned long long* table, unsigned rows, unsigned* d_n, hipStream_t s) {
-    const size_t N = (size_t)H * W, NB = (N + kRegScan - 1) / kRegScan;
+    const size_t N = (size_t)H * W, NB = scan_blocks(N);
     const unsigned tilesX = (W + kRegTW - 1) / kRegTW, tilesY = (H + kRegTH - 1) / kRegTH;
     const size_t tiles = (size_t)tilesX * tilesY, rowBlocks = ((size_t)tilesX * H + 3) / 4;
     const size_t nV = (size_t)(tilesX - 1) * H, nSeam = nV + (size_t)(tilesY - 1) * W;
@@ -332,10 +267,10 @@ hipError_t launch_regions(const uint8_t* klass, const uint8_t* conf, unsigned H,
     if (nSeam)
         hipLaunchKernelGGL(regions_seam_kernel, dim3((unsigned)((nSeam + 255) / 256)), dim3(256), 0, s, klass, H, W, conn8, nV, nSeam, parent);
     hipLaunchKernelGGL(regions_flatten_count_kernel, dim3((unsigned)rowBlocks), dim3(256), 0, s, H, W, tilesX, parent, cnt);
-    hipLaunchKernelGGL(regions_scan_sums_kernel, dim3((unsigned)NB), dim3(kRegScan), 0, s, parent, cnt, klass, N, min_pixels, skip_bg, partial);
-    hipLaunchKernelGGL(regions_scan_partials_kernel, dim3(1), dim3(kRegScan), 0, s, partial, NB, total, d_n);
+    hipLaunchKernelGGL(regions_scan_sums_kernel, dim3((unsigned)NB), dim3(kScanBlock), 0, s, parent, cnt, klass, N, min_pixels, skip_bg, partial);
+    hipLaunchKernelGGL(regions_scan_partials_kernel, dim3(1), dim3(kScanBlock), 0, s, partial, NB, total, d_n);
     if (labels || (table && rows)) {
-        hipLaunchKernelGGL(regions_scan_apply_kernel, dim3((unsigned)NB), dim3(kRegScan), 0, s, parent, cnt, klass, N, min_pixels, skip_bg, partial, ids);
+        hipLaunchKernelGGL(regions_scan_apply_kernel, dim3((unsigned)NB), dim3(kScanBlock), 0, s, parent, cnt, klass, N, min_pixels, skip_bg, partial, ids);
         if (table && rows) {
             const size_t cap = rows < N ? rows : N;  // there are at most N regions
             hipLaunchKernelGGL(regions_table_init_kernel, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, s, table, rows, total);

@@ -1,12 +1,12 @@
 // runs.hip -- Runs: a byte or u32 plane as raster-ordered runs (include/infur_hip.h).  The egress stage behind
 // Segments, Regions and Tracks: records (START, END, VALUE), a per-row index and the count, so that a host fetches 12 bytes
-// per run and not the dense plane.  One lane per pixel over the linear index, 1024 pixels per workgroup, three launches -- the
+// per run and not the dense plane.  One lane per pixel over the linear index, the flag scan of wave_scan.h, three launches -- the
 // kernel boundaries are the only ordering, no workgroup ever waits for another:
-//   1 sums      head(i) = the pixel starts a run that is emitted; one ballot per wave, popcount, block sum
-//   2 partials  one workgroup turns the block sums into their exclusive prefix sums (looping past 1024 of them); the total
-//   3 emit      the exclusive head count at a pixel is its record's index: the head lane stores START and VALUE, the TAIL lane
-//               stores END into record (inclusive count - 1) -- a run may span many waves and workgroups, and neither end ever
-//               looks for the other; a lane in column 0 stores row_start[y], the last pixel's lane row_start[h]
+//   1 sums      head(i) = the pixel starts a run that is emitted; flag_block_sum of it
+//   2 partials  scan_block_sums: one workgroup, the block sums -> their exclusive prefix sums; the total
+//   3 emit      the exclusive head count at a pixel (flag_rank) is its record's index: the head lane stores START and VALUE, the
+//               TAIL lane stores END into record (inclusive count - 1) -- a run may span many waves and workgroups, and neither
+//               end ever looks for the other; a lane in column 0 stores row_start[y], the last pixel's lane row_start[h]
 // The left / right neighbour comes from a lane shuffle, except on the first / last lane of a wave, which loads it.  Everything is
 // an integer and a function of the plane alone, and every output word has exactly one writer: identical bytes from run to run.
 #include <hip/hip_runtime.h>
@@ -14,12 +14,11 @@
 #include <cstdint>
 
 #include "kernels.h"
+#include "wave_scan.h"
 
 namespace infur {
 
 namespace {
-
-constexpr int kRunBlock = 1024;  // pixels per workgroup
 
 // What one lane knows about its pixel.  Dead lanes (i >= N) are neither head nor tail.
 struct RunPix {
@@ -46,66 +45,32 @@ __device__ __forceinline__ RunPix run_pixel(const T* __restrict__ plane, const s
 }
 
 template <class T>
-__global__ void __launch_bounds__(kRunBlock) runs_sums_kernel(const T* __restrict__ plane, size_t N, unsigned W, int skip, unsigned skip_value,
-                                                              unsigned* __restrict__ partial) {
-    __shared__ unsigned wsum[kRunBlock / 64];
-    const size_t i = (size_t)blockIdx.x * kRunBlock + threadIdx.x;
-    const RunPix p = run_pixel(plane, i, N, W, skip, skip_value);
-    const uint64_t m = __ballot(p.head);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = (unsigned)__popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned s = 0;
-        for (int k = 0; k < kRunBlock / 64; k++) s += wsum[k];
-        partial[blockIdx.x] = s;
-    }
+__global__ void __launch_bounds__(kScanBlock) runs_sums_kernel(const T* __restrict__ plane, size_t N, unsigned W, int skip, unsigned skip_value,
+                                                               unsigned* __restrict__ partial) {
+    __shared__ unsigned wsum[kScanBlock / 64];
+    const size_t i = (size_t)blockIdx.x * kScanBlock + threadIdx.x;
+    const unsigned s = flag_block_sum(run_pixel(plane, i, N, W, skip, skip_value).head, wsum);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
 // one workgroup: partial[0, NB) -> its exclusive prefix sums in place, the total to partial[NB] and, when wanted, to the caller's word
-__global__ void __launch_bounds__(kRunBlock) runs_partials_kernel(unsigned* __restrict__ partial, size_t NB, unsigned* __restrict__ d_n) {
-    __shared__ unsigned wsum[kRunBlock / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned carry = 0;
-    for (size_t base = 0; base < NB; base += kRunBlock) {
-        const size_t i = base + threadIdx.x;
-        const unsigned v = i < NB ? partial[i] : 0u;
-        unsigned inc = v;
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned t = __shfl_up(inc, d, 64);
-            if (lane >= d) inc += t;
-        }
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        unsigned before = 0, all = 0;
-        for (int k = 0; k < kRunBlock / 64; k++) {
-            const unsigned s = wsum[k];
-            before += k < wave ? s : 0u;
-            all += s;
-        }
-        __syncthreads();
-        if (i < NB) partial[i] = carry + before + inc - v;
-        carry += all;
-    }
+__global__ void __launch_bounds__(kScanBlock) runs_partials_kernel(unsigned* __restrict__ partial, size_t NB, unsigned* __restrict__ d_n) {
+    __shared__ unsigned wsum[kScanBlock / 64];
+    const unsigned n = scan_block_sums(partial, NB, wsum);
     if (threadIdx.x == 0) {
-        partial[NB] = carry;
-        if (d_n) d_n[0] = carry;
+        partial[NB] = n;
+        if (d_n) d_n[0] = n;
     }
 }
 
 template <class T>
-__global__ void __launch_bounds__(kRunBlock)
+__global__ void __launch_bounds__(kScanBlock)
     runs_emit_kernel(const T* __restrict__ plane, size_t N, unsigned H, unsigned W, int skip, unsigned skip_value, const unsigned* __restrict__ partial,
                      unsigned* __restrict__ runs, unsigned rows, unsigned* __restrict__ row_start) {
-    __shared__ unsigned wsum[kRunBlock / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const size_t i = (size_t)blockIdx.x * kRunBlock + threadIdx.x;
+    __shared__ unsigned wsum[kScanBlock / 64];
+    const size_t i = (size_t)blockIdx.x * kScanBlock + threadIdx.x;
     const RunPix p = run_pixel(plane, i, N, W, skip, skip_value);
-    const uint64_t m = __ballot(p.head);
-    if (lane == 0) wsum[wave] = (unsigned)__popcll(m);
-    __syncthreads();
-    unsigned before = partial[blockIdx.x];
-    for (int k = 0; k < wave; k++) before += wsum[k];
-    const unsigned excl = before + (unsigned)__popcll(m & ((1ull << lane) - 1ull));  // emitted runs that start before this pixel
+    const unsigned excl = flag_rank(p.head, partial[blockIdx.x], wsum);  // emitted runs that start before this pixel
     const unsigned incl = excl + (p.head ? 1u : 0u);
     if (!p.live) return;
     if (runs) {
@@ -125,11 +90,11 @@ __global__ void __launch_bounds__(kRunBlock)
 template <class T>
 hipError_t launch_runs_t(const T* plane, unsigned H, unsigned W, int skip, unsigned skip_value, unsigned* partial, unsigned* runs, unsigned rows,
                          unsigned* row_start, unsigned* d_n, hipStream_t s) {
-    const size_t N = (size_t)H * W, NB = (N + kRunBlock - 1) / kRunBlock;
-    hipLaunchKernelGGL(runs_sums_kernel<T>, dim3((unsigned)NB), dim3(kRunBlock), 0, s, plane, N, W, skip, skip_value, partial);
-    hipLaunchKernelGGL(runs_partials_kernel, dim3(1), dim3(kRunBlock), 0, s, partial, NB, d_n);
+    const size_t N = (size_t)H * W, NB = scan_blocks(N);
+    hipLaunchKernelGGL(runs_sums_kernel<T>, dim3((unsigned)NB), dim3(kScanBlock), 0, s, plane, N, W, skip, skip_value, partial);
+    hipLaunchKernelGGL(runs_partials_kernel, dim3(1), dim3(kScanBlock), 0, s, partial, NB, d_n);
     if ((runs && rows) || row_start)
-        hipLaunchKernelGGL(runs_emit_kernel<T>, dim3((unsigned)NB), dim3(kRunBlock), 0, s, plane, N, H, W, skip, skip_value, partial,
+        hipLaunchKernelGGL(runs_emit_kernel<T>, dim3((unsigned)NB), dim3(kScanBlock), 0, s, plane, N, H, W, skip, skip_value, partial,
                            rows ? runs : nullptr, rows, row_start);
     return hipGetLastError();
 }
@@ -137,7 +102,7 @@ hipError_t launch_runs_t(const T* plane, unsigned H, unsigned W, int skip, unsig
 }  // namespace
 
 // the block sums and the total
-size_t runs_scratch_bytes(size_t npix) { return ((npix + kRunBlock - 1) / kRunBlock + 1) * 4; }
+size_t runs_scratch_bytes(size_t npix) { return (scan_blocks(npix) + 1) * 4; }
 
 hipError_t launch_runs(const void* plane, int elem_bytes, unsigned H, unsigned W, int skip, unsigned skip_value, void* scratch, unsigned* runs,
                        unsigned rows, unsigned* row_start, unsigned* d_n, hipStream_t s) {

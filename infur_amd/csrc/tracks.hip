@@ -2,23 +2,24 @@
 // stage behind Regions: from the current frame's label plane, region table and count, and the frame the tracker remembers, a
 // track id per region.  Separate launches -- the kernel boundaries are the only ordering, no workgroup ever waits for another:
 //   1 begin    the step's scalars (tracked regions T, fresh frame or not), best[] and claim[] cleared as far as they are read
-//   2 runs     R = the number of runs of equal (current, remembered) label pairs along wave-rows: one ballot per wave-row, one
+//   2 runs     R = the number of runs of equal (current, remembered) label pairs along wave-rows (wave_run_starts), one
 //              atomic per workgroup.  R bounds the distinct pairs; 2 R > pair_slots is the overflow rule
 //   3 insert   the head lane of each run: 64-bit CAS of (c << 32) | p into an open-addressing table, then one non-returning
 //              add of the run length.  Inside this kernel the table is touched by atomics only
 //   4 choose   one lane per slot: candidates (same class, overlap >= min_overlap) -> atomicMax into best[c]
 //   5 keep     one lane per current region: atomicMax into claim[best p]
-//   6 assign   new-track flags, their exclusive prefix sum in region order (block sums, one-workgroup scan, apply), ids,
+//   6 assign   new-track flags, their exclusive prefix sum in region order (flag_block_sum, scan_block_sums, flag_rank), ids,
 //              table rows, summary
 //   7 plane    label plane -> track plane (dword stores)
 //   8 save     the per-region words the next step needs (the label plane itself is a device-to-device copy)
-// The slot a pair lands in depends on timing; everything read from the table goes through sums and maxima, which commute, so
-// the bytes written do not depend on the order in which atomics arrive.
+// The wave-row and the flag scan are wave_scan.h's.  The slot a pair lands in depends on timing; everything read from the table
+// goes through sums and maxima, which commute, so the bytes written do not depend on the order in which atomics arrive.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "kernels.h"
+#include "wave_scan.h"
 
 namespace infur {
 
@@ -26,14 +27,7 @@ namespace {
 
 constexpr unsigned kNone = 0xFFFFFFFFu;
 constexpr unsigned long long kEmpty = ~0ull;
-constexpr int kTrkScan = 1024;  // elements per workgroup of the scan launches
 constexpr unsigned long long kHi = 0xFFFFFFFF00000000ull;
-
-// length of the run that starts at `lane`, from the mask of run starts and dead lanes (regions.hip's idiom)
-__device__ __forceinline__ unsigned trk_run_length(const uint64_t starts, const int lane) {
-    const uint64_t above = lane == 63 ? 0ull : (starts >> (lane + 1));
-    return above ? (unsigned)__builtin_ctzll(above) + 1u : 64u - (unsigned)lane;
-}
 
 __device__ __forceinline__ unsigned trk_hash(unsigned long long k, unsigned mask) {
     k ^= k >> 33;
@@ -59,23 +53,19 @@ __global__ void __launch_bounds__(256) tracks_begin_kernel(TrkMem m, unsigned H,
     }
 }
 
-// A wave is 64 consecutive columns of one row.  -> the pair key of this lane's pixel, kEmpty when either label is untracked
-// (or the lane is outside the image, or nothing is remembered); *head: the lane starts a run of a tracked pair.
+// -> the pair key of this lane's pixel of the wave-row, kEmpty when either label is untracked (or the lane is outside the image,
+// or nothing is remembered); *head: the lane starts a run of a tracked pair.
 __device__ __forceinline__ unsigned long long trk_pair(const TrkMem& m, const unsigned* __restrict__ labels, unsigned H, unsigned W, unsigned tilesX,
                                                        bool* head, uint64_t* starts) {
-    const size_t u = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    const unsigned y = (unsigned)(u / tilesX), x = (unsigned)(u % tilesX) * 64 + lane;
+    const WaveRow r = wave_row(H, W, tilesX);
     const TrkState* st = m.st;
     unsigned long long key = kEmpty;
-    if (y < H && x < W && !st->fresh) {
-        const size_t at = (size_t)y * W + x;
-        const unsigned c = labels[at], p = m.prev[at];
+    if (r.live && !st->fresh) {
+        const unsigned c = labels[r.at], p = m.prev[r.at];
         if (c < st->T && p < st->pT) key = ((unsigned long long)c << 32) | p;
     }
-    const unsigned long long left = __shfl_up(key, 1, 64);
-    const bool cont = lane > 0 && key == left;
-    *starts = ~__ballot(cont);  // (dead lanes continue each other: they never count, and a live run ends where they begin)
+    bool cont;
+    *starts = wave_run_starts(key, key != kEmpty, &cont);
     *head = key != kEmpty && !cont;
     return key;
 }
@@ -85,13 +75,8 @@ __global__ void __launch_bounds__(256) tracks_runs_kernel(TrkMem m, const unsign
     bool head;
     uint64_t starts;
     (void)trk_pair(m, labels, H, W, tilesX, &head, &starts);
-    const uint64_t heads = __ballot(head);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = (unsigned)__popcll(heads);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned s = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        if (s) atomicAdd(&m.st->R, s);
-    }
+    const unsigned s = flag_block_sum<256>(head, wsum);
+    if (threadIdx.x == 0 && s) atomicAdd(&m.st->R, s);
 }
 
 __device__ __forceinline__ bool trk_overflow(const TrkMem& m) { return 2ull * m.st->R > (unsigned long long)m.slots; }
@@ -102,7 +87,7 @@ __global__ void __launch_bounds__(256) tracks_insert_kernel(TrkMem m, const unsi
     uint64_t starts;
     const unsigned long long key = trk_pair(m, labels, H, W, tilesX, &head, &starts);
     if (!head) return;
-    const unsigned n = trk_run_length(starts, threadIdx.x & 63);
+    const unsigned n = run_length(starts, threadIdx.x & 63);
     const unsigned mask = m.slots - 1;
     unsigned s = trk_hash(key, mask);
     for (unsigned it = 0; it < m.slots; it++) {  // at most half the slots are ever taken: the loop ends long before its bound
@@ -141,47 +126,20 @@ __device__ __forceinline__ bool trk_new(const TrkMem& m, const size_t i) {
     return !b || m.claim[kNone - (unsigned)b] != ((b & kHi) | (kNone - (unsigned)i));
 }
 
-__global__ void __launch_bounds__(kTrkScan) tracks_scan_sums_kernel(TrkMem m) {
-    __shared__ unsigned wsum[kTrkScan / 64];
-    const size_t i = (size_t)blockIdx.x * kTrkScan + threadIdx.x;
-    const uint64_t b = __ballot(i < m.st->T && trk_new(m, i));
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = (unsigned)__popcll(b);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned s = 0;
-        for (int k = 0; k < kTrkScan / 64; k++) s += wsum[k];
-        m.partial[blockIdx.x] = s;
-    }
+__global__ void __launch_bounds__(kScanBlock) tracks_scan_sums_kernel(TrkMem m) {
+    __shared__ unsigned wsum[kScanBlock / 64];
+    const size_t i = (size_t)blockIdx.x * kScanBlock + threadIdx.x;
+    const unsigned s = flag_block_sum(i < m.st->T && trk_new(m, i), wsum);
+    if (threadIdx.x == 0) m.partial[blockIdx.x] = s;
 }
 
 // one workgroup: partial[] -> its exclusive prefix sums in place; then the step's decisions: ids exhausted or not, next_id, summary
-__global__ void __launch_bounds__(kTrkScan) tracks_scan_partials_kernel(TrkMem m, size_t NB, unsigned* __restrict__ summary) {
-    __shared__ unsigned wsum[kTrkScan / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned carry = 0;
-    for (size_t base = 0; base < NB; base += kTrkScan) {
-        const size_t i = base + threadIdx.x;
-        const unsigned v = i < NB ? m.partial[i] : 0u;
-        unsigned inc = v;
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned t = __shfl_up(inc, d, 64);
-            if (lane >= d) inc += t;
-        }
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        unsigned before = 0, all = 0;
-        for (int k = 0; k < kTrkScan / 64; k++) {
-            const unsigned s = wsum[k];
-            before += k < wave ? s : 0u;
-            all += s;
-        }
-        __syncthreads();
-        if (i < NB) m.partial[i] = carry + before + inc - v;
-        carry += all;
-    }
+__global__ void __launch_bounds__(kScanBlock) tracks_scan_partials_kernel(TrkMem m, size_t NB, unsigned* __restrict__ summary) {
+    __shared__ unsigned wsum[kScanBlock / 64];
+    const unsigned fresh_n = scan_block_sums(m.partial, NB, wsum);
     if (threadIdx.x == 0) {
         TrkState* st = m.st;
-        const unsigned fresh_n = carry, remembered = st->fresh ? 0u : st->pT, cont = st->T - fresh_n;
+        const unsigned remembered = st->fresh ? 0u : st->pT, cont = st->T - fresh_n;
         const bool exhausted = (unsigned long long)st->next_id + fresh_n > 0xFFFFFFFEull;
         st->exhausted = exhausted;
         st->base = st->next_id;
@@ -196,16 +154,14 @@ __global__ void __launch_bounds__(kTrkScan) tracks_scan_partials_kernel(TrkMem m
 }
 
 // rows [0, min(n, rows)) of the caller's outputs; the tracker's own copy of id / age / birth for rows below T
-__global__ void __launch_bounds__(kTrkScan) tracks_apply_kernel(TrkMem m, unsigned* __restrict__ track_of_region, unsigned long long* __restrict__ ttab) {
-    __shared__ unsigned wsum[kTrkScan / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const size_t i = (size_t)blockIdx.x * kTrkScan + threadIdx.x;
+__global__ void __launch_bounds__(kScanBlock) tracks_apply_kernel(TrkMem m, unsigned* __restrict__ track_of_region, unsigned long long* __restrict__ ttab) {
+    __shared__ unsigned wsum[kScanBlock / 64];
+    const size_t i = (size_t)blockIdx.x * kScanBlock + threadIdx.x;
     const TrkState* st = m.st;
     const unsigned T = st->T;
     const bool fresh = i < T && trk_new(m, i);
-    const uint64_t b = __ballot(fresh);
-    if (lane == 0) wsum[wave] = (unsigned)__popcll(b);
-    __syncthreads();
+    // (the rank within the workgroup; partial[] is read below, by new tracks only: it has no word for a workgroup beyond T)
+    const unsigned rank = flag_rank(fresh, 0u, wsum);
     if (i >= st->nrows) return;
     unsigned long long row[kTrkWords] = {kNone, 0ull, 0ull, kNone, 0ull, 0ull, 0ull, 0ull};
     if (i < T) {
@@ -213,9 +169,7 @@ __global__ void __launch_bounds__(kTrkScan) tracks_apply_kernel(TrkMem m, unsign
             m.ctrack[i] = kNone;
             m.cage[i] = m.cborn[i] = 0u;
         } else if (fresh) {
-            unsigned before = m.partial[blockIdx.x];
-            for (int k = 0; k < wave; k++) before += wsum[k];
-            row[0] = m.ctrack[i] = st->base + before + (unsigned)__popcll(b & ((1ull << lane) - 1ull));
+            row[0] = m.ctrack[i] = st->base + m.partial[blockIdx.x] + rank;
             row[1] = m.cage[i] = 1u;
             row[2] = m.cborn[i] = st->frame;
         } else {
@@ -291,7 +245,7 @@ hipError_t launch_tracks(const TrkMem& m, const unsigned* labels, const unsigned
     if (rowBlocks > 0x7FFFFFFFull || (N + 255) / 256 > 0x7FFFFFFFull) return hipErrorInvalidValue;
     const size_t capRows = rows < N ? rows : N;               // >= min(n, rows): there are at most N regions
     const size_t cap = capRows < m.M ? capRows : (size_t)m.M;  // >= T
-    const size_t NB = (cap + kTrkScan - 1) / kTrkScan;
+    const size_t NB = scan_blocks(cap);
     hipError_t e = hipMemsetAsync(m.keys, 0xFF, (size_t)m.slots * 8, s);
     if (e == hipSuccess) e = hipMemsetAsync(m.cnts, 0, (size_t)m.slots * 4, s);
     if (e != hipSuccess) return e;
@@ -300,10 +254,10 @@ hipError_t launch_tracks(const TrkMem& m, const unsigned* labels, const unsigned
     hipLaunchKernelGGL(tracks_insert_kernel, dim3((unsigned)rowBlocks), dim3(256), 0, s, m, labels, H, W, tilesX);
     hipLaunchKernelGGL(tracks_choose_kernel, dim3((m.slots + 255) / 256), dim3(256), 0, s, m, table, min_overlap);
     if (cap) hipLaunchKernelGGL(tracks_keep_kernel, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, s, m);
-    if (NB) hipLaunchKernelGGL(tracks_scan_sums_kernel, dim3((unsigned)NB), dim3(kTrkScan), 0, s, m);
-    hipLaunchKernelGGL(tracks_scan_partials_kernel, dim3(1), dim3(kTrkScan), 0, s, m, NB, summary);
+    if (NB) hipLaunchKernelGGL(tracks_scan_sums_kernel, dim3((unsigned)NB), dim3(kScanBlock), 0, s, m);
+    hipLaunchKernelGGL(tracks_scan_partials_kernel, dim3(1), dim3(kScanBlock), 0, s, m, NB, summary);
     if (capRows)
-        hipLaunchKernelGGL(tracks_apply_kernel, dim3((unsigned)((capRows + kTrkScan - 1) / kTrkScan)), dim3(kTrkScan), 0, s, m, track_of_region,
+        hipLaunchKernelGGL(tracks_apply_kernel, dim3((unsigned)scan_blocks(capRows)), dim3(kScanBlock), 0, s, m, track_of_region,
                            track_table);
     if (track_plane) hipLaunchKernelGGL(tracks_plane_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, m, labels, N, track_plane);
     e = hipMemcpyAsync(m.prev, labels, N * 4, hipMemcpyDeviceToDevice, s);

@@ -166,6 +166,34 @@ def test_edge_shapes_equal_the_reference(ctx, size):
         run_sequence(ctx, name, *size)
 
 
+@functools.lru_cache(maxsize=None)
+def ragged_scan_frames():
+    """two 96 x 128 planes of 3-class noise labelled at 4-connectivity: more than 2 * 1024 regions each, no multiple of 64; the
+    second is the first with the rows 24 .. 71 drawn again"""
+    a = R.noise(96, 128, 3, 0)
+    b = a.copy()
+    b[24:72] = R.noise(96, 128, 3, 100)[24:72]
+    return tuple(T.regions_of(k, R.CONNECT_4) for k in (a, b))
+
+
+def test_the_new_track_scan_spans_several_blocks_with_ragged_ends(ctx):
+    """the ranks of the new tracks cross two boundaries between scan blocks of 1024 regions, the last block and its last wave
+    are partly filled, and in the second frame continued and new tracks interleave, more than a block of each"""
+    trk, ref = Tracker(ctx), T.Tracker()
+    try:
+        for i, (labels, table, n) in enumerate(ragged_scan_frames()):
+            rows = n + 3
+            want = ref.step(labels, table, n, rows)
+            status, continued, new, _ = want.summary.tolist()
+            print(f"frame {i}: {n} regions, {want.runs} runs, summary {want.summary.tolist()}")
+            assert n > 2048 and n % 64 != 0
+            assert 2 * want.runs <= T.DEFAULT_SLOTS and n <= T.DEFAULT_REGIONS and not status  # neither overflow nor truncation
+            assert (continued, new) == (0, n) if i == 0 else (continued > 1024 and new > 1024)
+            check_step(dev_step(ctx, trk, labels, table, n, rows), want, n, rows, f"frame {i}")
+    finally:
+        trk.close()
+
+
 def test_the_sequences_do_what_they_are_for(ctx):
     """ids stable and ages 1, 2, 3 on identical frames; the shifted blobs keep their tracks; a cross has h * w pairs"""
     ref = T.Tracker()
