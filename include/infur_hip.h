@@ -538,6 +538,97 @@ int32_t infur_frame_runs_dev(infur_ctx* ctx, const void* d_bgr, uint32_t w, uint
                              void* d_row_start, uint32_t row_start_rows, void* d_n_runs, void* d_stats,
                              uint32_t stats_capacity, void* d_scaled_bgr, uint32_t* ow, uint32_t* oh);
 
+/* ---- Outlines: the boundaries of a class, label or track plane as closed polygon loops ----
+ * Runs gives a mask as records to fill; a polygon is what GeoJSON and COCO `segmentation` hold, what a GUI strokes as a vector
+ * outline, what a simplifier, a hit test or a tracker gate takes.  Outlines turns the boundary of every value-region of a byte
+ * or u32 plane into closed loops of lattice vertices on the device, in a deterministic order.  Presence of this group is
+ * announced by infur_features() & INFUR_FEATURE_OUTLINES (INFUR_ABI_VERSION does not move).
+ *
+ * INPUT.  A plane of h x w elements of elem_bytes = 1 or 4.  Runs' rules hold for elem_bytes, for a NULL plane, for unknown flag
+ * bits and for skip_value > 255 on bytes (each INFUR_E_INVALID_ARG).  In addition 4*h*w must be below 2^32 - 1, otherwise the
+ * call returns INFUR_E_INVALID_ARG.
+ * FLAGS.
+ *   INFUR_OUTLINES_SKIP   pixels whose value equals skip_value belong to no region: they own no edges, and a kept pixel beside
+ *                         one has a boundary there
+ *   INFUR_OUTLINES_CONN8  the saddle rule below.  Callers pass the connectivity they gave Regions
+ * LATTICE.  Vertices are (X, Y) with 0 <= X <= w and 0 <= Y <= h; the vertex id is Y*(w+1) + X.
+ * EDGES.  Pixel p = (x, y) has the linear index i = y*w + x and the sides N=0, E=1, S=2, W=3.  Side s of a kept pixel is a
+ * boundary EDGE when the neighbour across it is outside the plane, is skipped, or has a different value; the edge id is 4*i + s.
+ * Edges are directed with their pixel on the right hand (clockwise on a y-down screen):
+ *   N goes (x,y) -> (x+1,y), heading east         E goes (x+1,y) -> (x+1,y+1), heading south
+ *   S goes (x+1,y+1) -> (x,y+1), heading west     W goes (x,y+1) -> (x,y), heading north
+ * so the side index is also the heading d.
+ * SUCCESSOR.  Take an edge of pixel p with value v and heading d that ends at vertex V = (X, Y).  R is the right-ahead pixel and
+ * L the left-ahead pixel:
+ *   d      R            L
+ *   east   (X, Y)       (X, Y-1)
+ *   south  (X-1, Y)     (X, Y)
+ *   west   (X-1, Y-1)   (X-1, Y)
+ *   north  (X, Y-1)     (X-1, Y-1)
+ * A pixel "is v" when it is inside the plane, kept, and equal to v.  The successor is:
+ *   R and L are both v          turn left: edge (L, side (d+3)%4)
+ *   only R is v                 go straight: edge (R, side d)
+ *   only L is v (the saddle)    under CONN8 turn left: edge (L, (d+3)%4); otherwise turn right: edge (p, (d+1)%4)
+ *   neither is v                turn right: edge (p, (d+1)%4)
+ * Every edge has exactly one successor and one predecessor (the predecessor rule is the mirror image and as local: the 2 x 2
+ * pixels around the edge's tail), so the edges fall into disjoint cycles.  Each cycle is a LOOP.
+ * CORNER EDGES AND LOOP ORDER.  An edge is a CORNER EDGE when its heading differs from its predecessor's; its tail vertex is a
+ * polygon vertex.  A loop's START is its corner edge with the smallest edge id.  Loops are numbered from 0 in ascending order of
+ * their start edge id.  A loop's vertices are the tail vertices of its corner edges, in succession order beginning at the start.
+ * Collinear lattice points are never emitted: a rectangle is 4 vertices whatever its size.
+ * OUTPUTS, each optional (NULL = not wanted, and so are loops with loops_rows == 0 and vertices with vertex_rows == 0; nothing
+ * wanted is INFUR_E_INVALID_ARG), none needs initialisation; a rejected call touches no output:
+ *   loops     loops_rows records of INFUR_LOOP_WORDS uint32_t: INFUR_LOOP_OFFSET the index of the loop's first vertex in
+ *             `vertices` (a full exclusive prefix sum: it does not depend on any truncation), INFUR_LOOP_COUNT its number of
+ *             vertices, INFUR_LOOP_VALUE the region's value, zero-extended, INFUR_LOOP_START the start edge id.  Only the first
+ *             min(n_loops, loops_rows) records are written
+ *   vertices  vertex_rows uint32_t vertex ids, loops back to back.  Positions at or beyond min(n_vertices, vertex_rows) are
+ *             left alone
+ *   counts    3 uint32_t {n_loops, n_vertices, n_edges}: the full counts whatever the rows are
+ * EDGE CAPACITY.  The stage needs scratch per boundary edge, and a noise plane has up to 4*h*w of them.  max_edges = 0 means
+ * 4*h*w, the worst case, so that no plane is ever refused for its content (a larger value is taken as 4*h*w).  When n_edges >
+ * max_edges, counts is written as {0, 0, n_edges} and no other output is touched: overflow is visible and is not an error, the
+ * sibling of Runs' truncation rule.  h*w == 0 writes counts = {0, 0, 0} and nothing else.
+ * FACTS THAT FOLLOW.  Every loop has an even number of vertices, at least 4.  START & 3 is 0 (N) for an outer boundary and 2 (S)
+ * for the boundary of a hole.  The shoelace sum of (x[i]*y[i+1] - x[i+1]*y[i]) is positive exactly for the outer loops, and over
+ * all loops it is twice the number of kept pixels.  For an outer loop of a Regions label plane START >> 2 is the region's
+ * INFUR_REGION_FIRST (a region that 4-connectivity holds together only around a hole's diagonal has further outer loops, with
+ * larger starts).  Everything is an integer and a function of the plane alone: identical bytes from run to run. */
+enum { INFUR_OUTLINES_SKIP = 1, INFUR_OUTLINES_CONN8 = 2 };
+enum { INFUR_LOOP_OFFSET = 0, INFUR_LOOP_COUNT = 1, INFUR_LOOP_VALUE = 2, INFUR_LOOP_START = 3, INFUR_LOOP_WORDS = 4 };
+enum { INFUR_FEATURE_OUTLINES = 16 };
+
+/* on a given plane, host pointers: the counts are read first, then min(n_loops, loops_rows) records and min(n_vertices,
+ * vertex_rows) vertices are copied back */
+int32_t infur_outlines(infur_ctx* ctx, const void* plane, uint32_t elem_bytes, uint32_t h, uint32_t w, uint32_t flags,
+                       uint32_t skip_value, uint32_t max_edges, uint32_t* loops, uint32_t loops_rows, uint32_t* vertices,
+                       uint32_t vertex_rows, uint32_t* counts);
+/* device pointers throughout, d_counts included (three device uint32_t); enqueued on the context's stream in 9 + ceil(log2(edge
+ * capacity)) launches, a number fixed by the arguments: the call never synchronises.  Capturable after one call outside the
+ * capture, which allocates the scratch: 36 bytes per edge of capacity, 4 bytes per pixel and the scan's sums, owned by the
+ * context.  It grows only with a request larger than any before, and a graph captured around the call is re-captured after
+ * that.  This is the call that composes on the device: infur_frame_regions_dev (or infur_frame_tracks_dev), then
+ * infur_outlines_dev on the label (track) plane they left in device memory with INFUR_OUTLINES_SKIP, skip_value =
+ * INFUR_REGION_NONE (INFUR_TRACK_NONE) and the same connectivity gives per-object polygons with no dense plane crossing PCIe. */
+int32_t infur_outlines_dev(infur_ctx* ctx, const void* d_plane, uint32_t elem_bytes, uint32_t h, uint32_t w, uint32_t flags,
+                           uint32_t skip_value, uint32_t max_edges, void* d_loops, uint32_t loops_rows, void* d_vertices,
+                           uint32_t vertex_rows, void* d_counts);
+/* The fused frame path with the class plane outlined: scale -> model -> Segments decode(out[0]) -> Outlines of the class plane,
+ * in one call.  The class plane is decoded into scratch of the library's own.  stats is Segments' per-class table, optional;
+ * stats_capacity is the number of classes it has room for, as infur_frame_segments' stats_classes.  At least one of loops,
+ * vertices and counts must be given (checked once a model is loaded).  The calls inherit infur_frame_segments' checks and
+ * errors: with no model loaded the Scale stage still runs and the call returns INFUR_E_MODEL_NOT_LOADED.  They always enqueue
+ * eagerly and leave the graphs cached for infur_frame_advance_dev alone.  (The stream ring, batch and group calls produce RGBA
+ * only.) */
+int32_t infur_frame_outlines(infur_ctx* ctx, const uint8_t* bgr, uint32_t w, uint32_t h, float factor, uint32_t scale_mode,
+                             uint32_t decode, uint32_t flags, uint32_t skip_value, uint32_t max_edges, uint32_t* loops,
+                             uint32_t loops_rows, uint32_t* vertices, uint32_t vertex_rows, uint32_t* counts, uint64_t* stats,
+                             uint32_t stats_capacity, uint8_t* scaled_bgr, uint32_t* ow, uint32_t* oh);
+int32_t infur_frame_outlines_dev(infur_ctx* ctx, const void* d_bgr, uint32_t w, uint32_t h, float factor, uint32_t scale_mode,
+                                 uint32_t decode, uint32_t flags, uint32_t skip_value, uint32_t max_edges, void* d_loops,
+                                 uint32_t loops_rows, void* d_vertices, uint32_t vertex_rows, void* d_counts, void* d_stats,
+                                 uint32_t stats_capacity, void* d_scaled_bgr, uint32_t* ow, uint32_t* oh);
+
 /* ---- streaming (infur/src/main.rs:27-99,105): bounded queue, copies overlapped with compute ----
  * The reference back-pressures its producer with sync_channel(2) (main.rs:105); a stream
  * here is a ring of `depth` pinned + device slots.  submit() copies the caller's frame into a

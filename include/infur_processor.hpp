@@ -426,6 +426,81 @@ private:
     bool dirty_ = true;
 };
 
+/// What `Outlines` produces: `loops` holds min(n_loops, loops_rows) records of INFUR_LOOP_WORDS words, `vertices` the first
+/// min(n_vertices, vertex_rows) vertex ids Y*(width+1) + X, loops back to back; the three counts are complete whatever the rows
+/// are (n_loops == 0 with n_edges > 0: the edges exceeded the capacity).
+struct OutlinesOut {
+    uint32_t loops_rows = 1u << 16, vertex_rows = 1u << 20;
+    uint32_t width = 0, height = 0, n_loops = 0, n_vertices = 0, n_edges = 0;
+    std::vector<uint32_t> loops, vertices;
+    uint32_t rows() const { return n_loops < loops_rows ? n_loops : loops_rows; }
+    uint32_t word(uint32_t loop, uint32_t w) const { return loops[(size_t)loop * INFUR_LOOP_WORDS + w]; }
+    bool is_hole(uint32_t loop) const { return (word(loop, INFUR_LOOP_START) & 3u) == 2u; }
+    uint32_t x(uint32_t vertex) const { return vertices[vertex] % (width + 1); }
+    uint32_t y(uint32_t vertex) const { return vertices[vertex] / (width + 1); }
+};
+
+/// The polygon stage: the boundaries of the value-regions of a byte plane (class) or a u32 plane (labels, tracks) as closed loops
+/// of lattice vertices, outer loops clockwise on a y-down screen, holes counter-clockwise.  Integer results, identical from run to run.
+/// Command = skip (pixels of `value` belong to no region) / no skip, the connectivity Regions was given (the saddle rule), the
+/// edge capacity (0: four per pixel); Input = a plane of uint8_t or uint32_t, Output = OutlinesOut.
+class Outlines {
+public:
+    struct Cmd {
+        enum Kind { Skip, NoSkip, Connectivity, MaxEdges } kind;
+        uint32_t value;
+    };
+    explicit Outlines(Context& c) : c_(c) {}
+    Status control(Cmd cmd) {
+        uint32_t flags = flags_, skip_value = skip_value_, max_edges = max_edges_;
+        switch (cmd.kind) {
+            case Cmd::Skip: flags |= (uint32_t)INFUR_OUTLINES_SKIP, skip_value = cmd.value; break;
+            case Cmd::NoSkip: flags &= ~(uint32_t)INFUR_OUTLINES_SKIP, skip_value = 0; break;
+            case Cmd::Connectivity:
+                if (cmd.value != 4 && cmd.value != 8) return INFUR_E_INVALID_ARG;
+                flags = cmd.value == 8 ? flags | (uint32_t)INFUR_OUTLINES_CONN8 : flags & ~(uint32_t)INFUR_OUTLINES_CONN8;
+                break;
+            case Cmd::MaxEdges: max_edges = cmd.value; break;
+            default: return INFUR_E_INVALID_ARG;
+        }
+        dirty_ = dirty_ || flags != flags_ || skip_value != skip_value_ || max_edges != max_edges_;
+        flags_ = flags;
+        skip_value_ = skip_value;
+        max_edges_ = max_edges;
+        return INFUR_OK;
+    }
+    bool is_dirty() const { return dirty_; }
+    Status advance(const std::vector<uint8_t>& plane, uint32_t height, uint32_t width, OutlinesOut& out) {
+        return run(plane.data(), plane.size(), 1, height, width, out);
+    }
+    Status advance(const std::vector<uint32_t>& plane, uint32_t height, uint32_t width, OutlinesOut& out) {
+        return run(plane.data(), plane.size(), 4, height, width, out);
+    }
+
+private:
+    Status run(const void* plane, size_t elems, uint32_t elem_bytes, uint32_t height, uint32_t width, OutlinesOut& out) {
+        dirty_ = false;
+        if (elems != (size_t)width * height) return INFUR_E_SHAPE;
+        out.width = width;
+        out.height = height;
+        out.loops.assign((size_t)out.loops_rows * INFUR_LOOP_WORDS, 0);
+        out.vertices.assign(out.vertex_rows, 0);
+        uint32_t counts[3] = {0, 0, 0};
+        const Status s = infur_outlines(c_.get(), plane, elem_bytes, height, width, flags_, skip_value_, max_edges_,
+                                        out.loops_rows ? out.loops.data() : nullptr, out.loops_rows, out.vertex_rows ? out.vertices.data() : nullptr,
+                                        out.vertex_rows, counts);
+        out.n_loops = counts[0];
+        out.n_vertices = counts[1];
+        out.n_edges = counts[2];
+        out.loops.resize((size_t)out.rows() * INFUR_LOOP_WORDS);
+        out.vertices.resize(out.n_vertices < out.vertex_rows ? out.n_vertices : out.vertex_rows);
+        return s;
+    }
+    Context& c_;
+    uint32_t flags_ = 0, skip_value_ = 0, max_edges_ = 0;
+    bool dirty_ = true;
+};
+
 /// infur_group: n contexts (one per GPU) of one process -- RCCL weight broadcast + frame-batch sharding
 /// (BASELINE configs[3]).  The contexts must outlive the group.
 class Group {

@@ -58,6 +58,10 @@ FEATURE_TRACKS = 4
 RUNS_SKIP = 1
 RUN_START, RUN_END, RUN_VALUE, RUN_WORDS = 0, 1, 2, 3
 FEATURE_RUNS = 8
+# Outlines (infur_outlines / infur_frame_outlines): the flags, the words of a loop record, the feature bit
+OUTLINES_SKIP, OUTLINES_CONN8 = 1, 2
+LOOP_OFFSET, LOOP_COUNT, LOOP_VALUE, LOOP_START, LOOP_WORDS = 0, 1, 2, 3, 4
+FEATURE_OUTLINES = 16
 
 
 class Options(C.Structure):
@@ -177,6 +181,12 @@ SIGNATURES = {
                                      _u32p]),
     "infur_frame_runs_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _u32, _vp,
                                          _u32p, _u32p]),
+    "infur_outlines": (C.c_int32, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _vp]),
+    "infur_outlines_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _vp]),
+    "infur_frame_outlines": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _u32, _vp,
+                                         _u32p, _u32p]),
+    "infur_frame_outlines_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _u32,
+                                             _vp, _u32p, _u32p]),
     "infur_stream_create": (C.c_int32, [_vp, _u32, C.POINTER(_vp)]),
     "infur_stream_destroy": (None, [_vp]),
     "infur_stream_add_lane": (C.c_int32, [_vp, _vp]),

@@ -174,6 +174,9 @@ struct infur_ctx {
     // Runs (infur_runs.cpp): the scan's block sums, the class plane the frame calls decode into, and the host-pointer calls'
     // staging.  Private like the above.
     infur::Buf st_runs, st_runs_plane, st_runs_io;
+    // Outlines (infur_outlines.cpp): the edge state and scan sums, the class plane the frame calls decode into, and the
+    // host-pointer calls' staging.  Private like the above.
+    infur::Buf st_outl, st_outl_plane, st_outl_io;
     // Tracks (infur_tracks.cpp): the live trackers of this context; infur_ctx_destroy releases their device memory and orphans them
     std::vector<infur_tracker*> trackers;
 

@@ -8,6 +8,7 @@
 //   infur_regions.cpp       Regions (connected components of the class plane, per-region table): C entry points
 //   infur_tracks.cpp        Tracks (region identities from frame to frame): the tracker object and its C entry points
 //   infur_runs.cpp          Runs (a class, label or track plane as run-length records): C entry points
+//   infur_outlines.cpp      Outlines (region boundaries of a class, label or track plane as polygon loops): C entry points
 // (wave_scan.h, the device code regions.hip, tracks.hip and runs.hip share, also holds kScanBlock, which sizes their block sums)
 // Everything here lives in namespace infur and is NOT part of the public ABI.
 #pragma once

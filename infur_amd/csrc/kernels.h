@@ -320,4 +320,16 @@ size_t runs_scratch_bytes(size_t npix);
 hipError_t launch_runs(const void* plane, int elem_bytes, unsigned H, unsigned W, int skip, unsigned skip_value, void* scratch, unsigned* runs,
                        unsigned rows, unsigned* row_start, unsigned* d_n, hipStream_t s);
 
+// Outlines (outlines.hip): the boundaries of the value-regions of an H x W plane of 1- or 4-byte elements as closed loops --
+// loops_rows x kLoopWords u32 records (OFFSET, COUNT, VALUE, START), vertex_rows u32 vertex ids Y * (W + 1) + X, and counts[3] =
+// {n_loops, n_vertices, n_edges} (each optional; device memory).  skip: pixels of skip_value belong to no region; conn8: the
+// saddle turns left.  cap: the edge capacity, in [1, 4 * H * W]; with more edges counts = {0, 0, n_edges} and nothing else is
+// written.  scratch: outlines_scratch_bytes(H * W, cap) bytes the launches own for the call.  Stream-ordered; 9 + ceil(log2(cap))
+// launches, no workgroup waits for another.  4 * H * W in [4, 2^32 - 2].
+constexpr int kLoopWords = 4;
+size_t outlines_scratch_bytes(size_t npix, size_t cap);
+hipError_t launch_outlines(const void* plane, int elem_bytes, unsigned H, unsigned W, int skip, int conn8, unsigned skip_value, size_t cap,
+                           void* scratch, unsigned* loops, unsigned loops_rows, unsigned* vertices, unsigned vertex_rows, unsigned* counts,
+                           hipStream_t s);
+
 }  // namespace infur

@@ -880,6 +880,136 @@ def runs_by_value(runs: np.ndarray, n: int) -> dict:
     return {int(v): p for v, p in zip(vals, parts)}
 
 
+@dataclass
+class OutlinesCmd:
+    """``Outlines``' command: ``Skip(value)`` takes the pixels of that value out of every region (``Skip(None)``: every pixel is
+    kept again); ``Connectivity(4 | 8)`` sets the saddle rule -- what Regions was given; ``MaxEdges(n)`` the edge capacity
+    (0: the worst case, four per pixel)."""
+
+    skip: Optional[int] = None
+    connectivity: Optional[int] = None
+    max_edges: Optional[int] = None
+    set_skip: bool = False
+
+    @staticmethod
+    def Skip(v: Optional[int]) -> "OutlinesCmd":
+        return OutlinesCmd(skip=v, set_skip=True)
+
+    @staticmethod
+    def Connectivity(k: int) -> "OutlinesCmd":
+        return OutlinesCmd(connectivity=k)
+
+    @staticmethod
+    def MaxEdges(n: int) -> "OutlinesCmd":
+        return OutlinesCmd(max_edges=n)
+
+
+class OutlinesOut:
+    """``Outlines``' ``&mut Output``: what to produce (``loops_rows`` records and ``vertex_rows`` vertices at most) and, after
+    ``advance``, the results -- ``loops`` [min(n_loops, loops_rows), 4] u32 (columns ``_lib.LOOP_OFFSET``, ``LOOP_COUNT``,
+    ``LOOP_VALUE``, ``LOOP_START``) or None, ``vertices`` [min(n_vertices, vertex_rows)] u32 vertex ids Y*(w+1) + X or None, and
+    the full counts ``n_loops``, ``n_vertices``, ``n_edges`` ({0, 0, n_edges} when the edges exceed the capacity)."""
+
+    def __init__(self, loops_rows: int = 1 << 16, vertex_rows: int = 1 << 20):
+        self.loops_rows, self.vertex_rows = loops_rows, vertex_rows
+        self.loops = self.vertices = None
+        self.n_loops = self.n_vertices = self.n_edges = 0
+
+
+def _outlines_flags(skip: Optional[int], connectivity: int) -> int:
+    if connectivity not in (4, 8):
+        raise InfurError(_lib.E_INVALID_ARG, f"connectivity {connectivity}: 4 or 8")
+    return (_lib.OUTLINES_SKIP if skip is not None else 0) | (_lib.OUTLINES_CONN8 if connectivity == 8 else 0)
+
+
+class Outlines(Processor):
+    """The polygon stage: the boundaries of the value-regions of a class plane (u8) or a label / track plane (u32) as closed loops.
+
+    Command = ``OutlinesCmd``.  Input = a plane [H, W] of u8 or u32; Output = ``OutlinesOut``.  Outer loops run clockwise on a
+    y-down screen, holes counter-clockwise; integers throughout, identical from run to run.
+    """
+
+    def __init__(self, ctx: Context, skip: Optional[int] = None, connectivity: int = 4, max_edges: int = 0):
+        self.ctx = ctx
+        self.skip, self.connectivity, self.max_edges = skip, connectivity, max_edges
+        self.dirty = True
+
+    def control(self, cmd: OutlinesCmd) -> "Outlines":
+        skip = cmd.skip if cmd.set_skip else self.skip
+        connectivity = cmd.connectivity if cmd.connectivity is not None else self.connectivity
+        max_edges = cmd.max_edges if cmd.max_edges is not None else self.max_edges
+        if skip is not None and not 0 <= skip <= 0xFFFFFFFF:
+            raise InfurError(_lib.E_INVALID_ARG, f"skip value {skip}: a u32")
+        if connectivity not in (4, 8) or not 0 <= max_edges <= 0xFFFFFFFF:
+            raise InfurError(_lib.E_INVALID_ARG, f"connectivity {connectivity}: 4 or 8; max_edges {max_edges}: a u32")
+        self.dirty = self.dirty or (skip, connectivity, max_edges) != (self.skip, self.connectivity, self.max_edges)
+        self.skip, self.connectivity, self.max_edges = skip, connectivity, max_edges
+        return self
+
+    def is_dirty(self) -> bool:
+        return self.dirty
+
+    def advance(self, inp: np.ndarray, out: OutlinesOut) -> None:
+        self.dirty = False
+        if inp.ndim != 2 or inp.dtype.itemsize not in (1, 4) or inp.dtype.kind not in "ui":
+            raise InfurError(_lib.E_SHAPE, f"expected an [H,W] plane of 1- or 4-byte integers, got {inp.shape} {inp.dtype}")
+        plane = np.ascontiguousarray(inp)
+        h, w = plane.shape
+        lrows, vrows = max(0, min(int(out.loops_rows), h * w)), max(0, min(int(out.vertex_rows), 4 * h * w))
+        loops = np.empty((lrows, _lib.LOOP_WORDS), np.uint32) if lrows else None
+        vertices = np.empty(vrows, np.uint32) if vrows else None
+        counts = np.zeros(3, np.uint32)
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        self.ctx.check(self.ctx.L.infur_outlines(self.ctx.h, ptr(plane), plane.dtype.itemsize, h, w, _outlines_flags(self.skip, self.connectivity),
+                                                 self.skip or 0, self.max_edges, ptr(loops), lrows, ptr(vertices), vrows, counts.ctypes.data))
+        out.n_loops, out.n_vertices, out.n_edges = (int(v) for v in counts)
+        out.loops = loops[:min(out.n_loops, lrows)] if loops is not None else None
+        out.vertices = vertices[:min(out.n_vertices, vrows)] if vertices is not None else None
+
+
+class OutlinesFrame(NamedTuple):
+    """``FramePath.advance_outlines``: the loop records [min(n_loops, loops_rows), 4] u32 of the class plane, the vertex ids
+    [min(n_vertices, vertex_rows)] u32, the counts (n_loops, n_vertices, n_edges), the per-class statistics [k, 8] uint64 or None,
+    the scaled BGR frame or None, and the plane's (height, width) -- a vertex id is Y*(width + 1) + X"""
+
+    loops: Optional[np.ndarray]
+    vertices: Optional[np.ndarray]
+    counts: Optional[tuple]
+    stats: Optional[np.ndarray]
+    scaled: Optional[np.ndarray]
+    shape: tuple
+
+
+def outlines_polygons(loops: np.ndarray, vertices: np.ndarray, w: int) -> list:
+    """The loops whose vertices are all there (a truncated ``vertices`` ends the list) as [(value, is_hole, xy int32 [k, 2])]:
+    ``xy`` are the lattice points (x, y) of the closed polygon in order, ``is_hole`` the boundary of a hole (counter-clockwise on a
+    y-down screen).  ``w`` is the plane's width."""
+    loops = np.asarray(loops, np.uint32).reshape(-1, _lib.LOOP_WORDS)
+    vertices = np.asarray(vertices, np.uint32).reshape(-1)
+    out = []
+    for off, cnt, val, start in loops.tolist():
+        if off + cnt > len(vertices):
+            break
+        ids = vertices[off:off + cnt].astype(np.int64)
+        out.append((val, (start & 3) == 2, np.stack([ids % (w + 1), ids // (w + 1)], axis=1).astype(np.int32)))
+    return out
+
+
+def outlines_by_value(loops: np.ndarray, vertices: np.ndarray, w: int) -> dict:
+    """``outlines_polygons`` grouped: {value: [(outer xy, [hole xy, ...]), ...]} -- each outer loop with the holes of its value
+    that follow it before the value's next outer loop.  On a label or track plane a value is one region, so that a group is one
+    object's polygon with its holes (what GeoJSON calls a Polygon); on a class plane, where one value has many regions, a hole is
+    listed with the nearest outer loop of its class before it in loop order, which need not be the region it is a hole of."""
+    out = {}
+    for val, hole, xy in outlines_polygons(loops, vertices, w):
+        groups = out.setdefault(int(val), [])
+        if hole and groups:
+            groups[-1][1].append(xy)
+        elif not hole:
+            groups.append((xy, []))
+    return out
+
+
 def pack_normalize(ctx: Context, img: np.ndarray) -> np.ndarray:
     """The pre-proc stage on its own (predict_onnx.rs:103-137): BGR u8 HWC -> RGB f32 CHW."""
     img = _check_bgr(img)
@@ -1060,6 +1190,43 @@ class FramePath:
             return RunsFrame(None, None, None, None, scaled)
         self.ctx.check(rc)
         return RunsFrame(runs[:min(n.value, rows)] if runs is not None else None, row_start, n.value, stats, scaled)
+
+    def advance_outlines(self, img: np.ndarray, factor: float = 1.0, decode: int = _lib.DECODE_RAW, skip: Optional[int] = None,
+                         connectivity: int = 4, max_edges: int = 0, loops_rows: int = 1 << 16, vertex_rows: int = 1 << 20,
+                         want_stats: bool = True, want_scaled: bool = False) -> OutlinesFrame:
+        """The fused path with the class plane outlined, scale -> model -> Segments decode -> Outlines, in one call ->
+        ``OutlinesFrame``: no dense plane crosses PCIe.  Every result field is None when no model is loaded (``scaled`` is still
+        produced)."""
+        img = _check_bgr(img)
+        h, w = img.shape[:2]
+        L = self.ctx.L
+        f = float(np.float32(factor))
+        rc = L.infur_scale_validate(f)
+        if rc:
+            raise ValidScaleError(rc)
+        ow, oh = C.c_uint32(0), C.c_uint32(0)
+        rc = L.infur_scale_out_dims(w, h, f, C.byref(ow), C.byref(oh))
+        if rc:
+            raise ScaleProcError(rc)
+        mi = _lib.ModelInfoC()
+        k = mi.num_classes if L.infur_model_info_get(self.ctx.h, C.byref(mi)) == _lib.OK else 0
+        npix = oh.value * ow.value
+        lrows, vrows = max(0, min(int(loops_rows), npix)), max(0, min(int(vertex_rows), 4 * npix))
+        loops = np.empty((lrows, _lib.LOOP_WORDS), np.uint32) if lrows else None
+        vertices = np.empty(vrows, np.uint32) if vrows else None
+        counts = np.zeros(3, np.uint32)
+        stats = np.zeros((k, _lib.STAT_WORDS), np.uint64) if want_stats else None
+        scaled = np.empty((oh.value, ow.value, 3), np.uint8) if want_scaled else None
+        ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
+        rc = L.infur_frame_outlines(self.ctx.h, img.ctypes.data, w, h, f, self.scale_mode, decode, _outlines_flags(skip, connectivity), skip or 0,
+                                    max_edges, ptr(loops), lrows, ptr(vertices), vrows, counts.ctypes.data, ptr(stats), k, ptr(scaled),
+                                    C.byref(ow), C.byref(oh))
+        if rc == _lib.E_MODEL_NOT_LOADED:
+            return OutlinesFrame(None, None, None, None, scaled, (oh.value, ow.value))
+        self.ctx.check(rc)
+        nl, nv, ne = (int(v) for v in counts)
+        return OutlinesFrame(loops[:min(nl, lrows)] if loops is not None else None, vertices[:min(nv, vrows)] if vertices is not None else None,
+                             (nl, nv, ne), stats, scaled, (oh.value, ow.value))
 
     def advance_batch(self, imgs, factor: float = 1.0, outs=None):
         """A batch of independent frames (BASELINE configs[3]) -> list of masks, in order.  ``outs``: caller-owned mask arrays to fill

@@ -31,6 +31,14 @@ every line gains ``"n_runs"``.  ``--runs-plane class|labels|tracks`` picks the p
 needs ``--tracks``); ``--runs-skip VALUE`` leaves the runs of that value out (0: the background class; 4294967295: pixels of no
 region / no track).  With the class plane and neither ``--labels-out`` nor ``--conf-out`` the frame goes through
 ``infur_frame_runs``: records, count and the per-class table are all that crosses PCIe.
+
+``--outlines-out FILE`` receives the region boundaries as closed polygon loops, traced on the device: per frame three u32
+(n_loops, n_vertices, n_edges), then n_loops records of four u32 (OFFSET of the loop's first vertex, COUNT of its vertices,
+VALUE, START edge id; START & 3 == 2 marks the boundary of a hole), then n_vertices u32 vertex ids Y*(ow + 1) + X, and every line
+gains ``"n_loops"``.  With ``--regions`` the label plane is outlined where Regions left it on the device (one polygon with its
+holes per object), otherwise the class plane; ``--outlines-skip VALUE`` takes the pixels of that value out (0: the background
+class; 4294967295: pixels of no region); ``--connectivity`` is the saddle rule.  With the class plane and no other plane or
+records asked for the frame goes through ``infur_frame_outlines``.
 """
 from __future__ import annotations
 
@@ -67,6 +75,8 @@ def main(argv=None) -> int:
     ap.add_argument("--runs-out", default="", help="run-length records of a plane: per frame a u32 count, then count x 3 u32")
     ap.add_argument("--runs-plane", default="class", choices=["class", "labels", "tracks"], help="the plane --runs-out encodes")
     ap.add_argument("--runs-skip", type=int, default=None, help="leave out the runs of this value")
+    ap.add_argument("--outlines-out", default="", help="polygon loops: per frame 3 u32 counts, then n_loops x 4 u32, then n_vertices u32")
+    ap.add_argument("--outlines-skip", type=int, default=None, help="pixels of this value belong to no outlined region")
     a = ap.parse_args(argv)
     if a.tracks_out and not a.tracks:
         ap.error("--tracks-out needs --tracks")
@@ -81,9 +91,15 @@ def main(argv=None) -> int:
     if a.runs_skip is not None and not 0 <= a.runs_skip <= (255 if a.runs_plane == "class" else 0xFFFFFFFF):
         ap.error("--runs-skip: a value of the plane (a byte for the class plane, a u32 otherwise)")
 
+    if a.outlines_skip is not None and not 0 <= a.outlines_skip <= (0xFFFFFFFF if a.regions else 255):
+        ap.error("--outlines-skip: a value of the plane (a byte for the class plane, a u32 for the label plane)")
+
+    import numpy as np
+
     from . import _lib
     from .app import RawVideoSource, VideoProcError
-    from .processors import Context, FramePath, Model, ModelCmd, Runs, RunsOut, SegmentsFrame, class_summary, region_summary, track_summary
+    from .processors import (Context, FramePath, Model, ModelCmd, Outlines, OutlinesOut, Runs, RunsOut, SegmentsFrame, class_summary,
+                             region_summary, track_summary)
 
     ctx = Context(device=a.device, dtype=a.dtype)
     model = Model(ctx)
@@ -107,11 +123,12 @@ def main(argv=None) -> int:
     fconf = open(a.conf_out, "wb") if a.conf_out else None
     ftrk = open(a.tracks_out, "wb") if a.tracks_out else None
     fruns = open(a.runs_out, "wb") if a.runs_out else None
+    foutl = open(a.outlines_out, "wb") if a.outlines_out else None
     rpath = None
     if a.regions:
         oh, ow = _out_dims(ctx, a.width, a.height, a.scale)
         rpath = _RegionsPath(ctx, a.width, a.height, ow, oh, a.scale, fp.scale_mode, model.get_info().num_classes, max(0, a.max_regions),
-                             tracks=a.tracks, runs=fruns is not None)
+                             tracks=a.tracks, runs=fruns is not None, outlines=foutl is not None)
         flags = _lib.REGIONS_SKIP_BACKGROUND if a.skip_background else 0
     n, t0 = 0, time.perf_counter()
     while True:
@@ -123,16 +140,25 @@ def main(argv=None) -> int:
             raise
         if rpath is not None:
             s, labels, table, nreg = rpath.advance(img, decode, a.connectivity, a.min_pixels, flags, flab is not None, fconf is not None,
-                                                   freg is not None, keep_labels=fruns is not None and a.runs_plane == "labels")
+                                                   freg is not None, keep_labels=(fruns is not None and a.runs_plane == "labels") or foutl is not None)
             if a.tracks:
                 ttab, tplane, tsum = rpath.track(max(0, a.min_overlap), ftrk is not None, keep_plane=fruns is not None and a.runs_plane == "tracks")
             if fruns is not None:
                 runs, nruns = rpath.runs(a.runs_plane, a.runs_skip)
-        elif fruns is not None and flab is None and fconf is None:  # records, count and captions: no dense plane comes back
+            if foutl is not None:
+                outl = rpath.outlines(a.outlines_skip, a.connectivity)
+        elif foutl is not None and fruns is None and flab is None and fconf is None:  # polygons, counts and captions: no dense plane
+            r = fp.advance_outlines(img, a.scale, decode, skip=a.outlines_skip, connectivity=a.connectivity, loops_rows=1 << 32, vertex_rows=1 << 32)
+            s, outl = SegmentsFrame(None, None, r.stats, None, None), (np.array(r.counts, np.uint32), r.loops, r.vertices)
+        elif fruns is not None and flab is None and fconf is None and foutl is None:  # records, count and captions: no dense plane comes back
             r = fp.advance_runs(img, a.scale, decode, skip=a.runs_skip, runs_rows=1 << 32, want_row_start=False)
             s, runs, nruns = SegmentsFrame(None, None, r.stats, None, None), r.runs, r.n
         else:
-            s = fp.advance_segments(img, a.scale, decode, want_klass=flab is not None or fruns is not None, want_conf=fconf is not None)
+            s = fp.advance_segments(img, a.scale, decode, want_klass=flab is not None or fruns is not None or foutl is not None, want_conf=fconf is not None)
+            if foutl is not None:  # the class plane is on the host anyway
+                oo = OutlinesOut(loops_rows=1 << 32, vertex_rows=1 << 32)
+                Outlines(ctx, skip=a.outlines_skip, connectivity=a.connectivity).advance(s.klass, oo)
+                outl = (np.array([oo.n_loops, oo.n_vertices, oo.n_edges], np.uint32), oo.loops, oo.vertices)
             if fruns is not None:  # the class plane is on the host anyway
                 ro = RunsOut(runs_rows=1 << 32, want_row_start=False)
                 Runs(ctx, skip=a.runs_skip).advance(s.klass, ro)
@@ -159,9 +185,13 @@ def main(argv=None) -> int:
             rec["n_runs"] = nruns
             fruns.write(int(nruns).to_bytes(4, "little"))
             fruns.write(memoryview(runs).cast("B"))
+        if foutl is not None:
+            rec["n_loops"] = int(outl[0][0])
+            for part in outl:
+                foutl.write(memoryview(np.ascontiguousarray(part)).cast("B"))
         fst.write(json.dumps(rec) + "\n")
         n += 1
-    for f in (flab, fconf, freg, ftrk, fruns, fst):
+    for f in (flab, fconf, freg, ftrk, fruns, foutl, fst):
         if f is not None:
             f.flush()
     el = time.perf_counter() - t0
@@ -177,7 +207,7 @@ class _RegionsPath:
     writes class plane, confidence plane and per-class table into device buffers, infur_regions_dev labels those planes where
     they are; the tables, the count and the planes that are written out are all that is copied back."""
 
-    def __init__(self, ctx, w, h, ow, oh, factor, scale_mode, classes, rows, tracks=False, runs=False):
+    def __init__(self, ctx, w, h, ow, oh, factor, scale_mode, classes, rows, tracks=False, runs=False, outlines=False):
         import ctypes as C
 
         self.ctx, self.w, self.h, self.ow, self.oh, self.factor, self.mode = ctx, w, h, ow, oh, float(factor), scale_mode
@@ -186,7 +216,8 @@ class _RegionsPath:
         for name, n in (("bgr", w * h * 3), ("klass", ow * oh), ("conf", ow * oh), ("stats", classes * _STAT_BYTES), ("labels", ow * oh * 4),
                         ("table", self.rows * _ROW_BYTES), ("n", 4)) + \
                 ((("ttab", self.rows * _TRACK_BYTES), ("tplane", ow * oh * 4), ("tsum", 16)) if tracks else ()) + \
-                ((("runs", ow * oh * _RUN_BYTES), ("nruns", 4)) if runs else ()):
+                ((("runs", ow * oh * _RUN_BYTES), ("nruns", 4)) if runs else ()) + \
+                ((("loops", ow * oh * _LOOP_BYTES), ("vertices", ow * oh * 16), ("ocounts", 12)) if outlines else ()):
             p = C.c_void_p(None)
             ctx.check(ctx.L.infur_dev_alloc(ctx.h, max(n, 4), C.byref(p)))
             self.d[name] = p
@@ -249,6 +280,17 @@ class _RegionsPath:
         n = int(self._read("nruns", (1,), np.uint32)[0])
         return self._read("runs", (n, _RUN_BYTES // 4), np.uint32), n
 
+    def outlines(self, skip, connectivity):
+        """infur_outlines_dev on the label plane `advance` left on the device -> (counts [3], loops [n_loops, 4], vertices
+        [n_vertices]) u32: every object's polygon, no dense plane"""
+        import numpy as np
+
+        c, d = self.ctx, self.d
+        c.check(c.L.infur_outlines_dev(c.h, d["labels"], 4, self.oh, self.ow, (1 if skip is not None else 0) | (2 if connectivity == 8 else 0), skip or 0,
+                                       0, d["loops"], self.ow * self.oh, d["vertices"], 4 * self.ow * self.oh, d["ocounts"]))
+        counts = self._read("ocounts", (3,), np.uint32)
+        return counts, self._read("loops", (int(counts[0]), _LOOP_BYTES // 4), np.uint32), self._read("vertices", (int(counts[1]),), np.uint32)
+
     def close(self):
         if self.tracker:
             self.ctx.L.infur_tracker_destroy(self.tracker)
@@ -262,6 +304,7 @@ _STAT_BYTES = 8 * 8    # INFUR_STAT_WORDS u64 per class
 _ROW_BYTES = 10 * 8    # INFUR_REGION_WORDS u64 per region
 _TRACK_BYTES = 8 * 8   # INFUR_TRACK_WORDS u64 per region
 _RUN_BYTES = 3 * 4     # INFUR_RUN_WORDS u32 per run
+_LOOP_BYTES = 4 * 4    # INFUR_LOOP_WORDS u32 per loop
 
 
 def _out_dims(ctx, w, h, factor):

@@ -137,6 +137,16 @@ pub const INFUR_RUN_VALUE: u32 = 2;
 pub const INFUR_RUN_WORDS: u32 = 3;
 /// bit of `infur_features()`: the Runs calls below exist
 pub const INFUR_FEATURE_RUNS: u32 = 8;
+/// Outlines: the flags, the words of a loop record (`INFUR_LOOP_WORDS` u32 each)
+pub const INFUR_OUTLINES_SKIP: u32 = 1;
+pub const INFUR_OUTLINES_CONN8: u32 = 2;
+pub const INFUR_LOOP_OFFSET: u32 = 0;
+pub const INFUR_LOOP_COUNT: u32 = 1;
+pub const INFUR_LOOP_VALUE: u32 = 2;
+pub const INFUR_LOOP_START: u32 = 3;
+pub const INFUR_LOOP_WORDS: u32 = 4;
+/// bit of `infur_features()`: the Outlines calls below exist
+pub const INFUR_FEATURE_OUTLINES: u32 = 16;
 
 extern "C" {
     pub fn infur_abi_version() -> u32;
@@ -313,4 +323,20 @@ extern "C" {
                                 flags: u32, skip_value: u32, d_runs: *mut c_void, runs_rows: u32, d_row_start: *mut c_void,
                                 row_start_rows: u32, d_n_runs: *mut c_void, d_stats: *mut c_void, stats_capacity: u32,
                                 d_scaled_bgr: *mut c_void, ow: *mut u32, oh: *mut u32) -> i32;
+    // Outlines: the region boundaries of a byte or u32 plane as polygon loops
+    pub fn infur_outlines(c: *mut infur_ctx, plane: *const c_void, elem_bytes: u32, h: u32, w: u32, flags: u32, skip_value: u32,
+                          max_edges: u32, loops: *mut u32, loops_rows: u32, vertices: *mut u32, vertex_rows: u32,
+                          counts: *mut u32) -> i32;
+    pub fn infur_outlines_dev(c: *mut infur_ctx, d_plane: *const c_void, elem_bytes: u32, h: u32, w: u32, flags: u32,
+                              skip_value: u32, max_edges: u32, d_loops: *mut c_void, loops_rows: u32, d_vertices: *mut c_void,
+                              vertex_rows: u32, d_counts: *mut c_void) -> i32;
+    pub fn infur_frame_outlines(c: *mut infur_ctx, bgr: *const u8, w: u32, h: u32, factor: f32, scale_mode: u32, decode: u32,
+                                flags: u32, skip_value: u32, max_edges: u32, loops: *mut u32, loops_rows: u32, vertices: *mut u32,
+                                vertex_rows: u32, counts: *mut u32, stats: *mut u64, stats_capacity: u32, scaled_bgr: *mut u8,
+                                ow: *mut u32, oh: *mut u32) -> i32;
+    pub fn infur_frame_outlines_dev(c: *mut infur_ctx, d_bgr: *const c_void, w: u32, h: u32, factor: f32, scale_mode: u32,
+                                    decode: u32, flags: u32, skip_value: u32, max_edges: u32, d_loops: *mut c_void,
+                                    loops_rows: u32, d_vertices: *mut c_void, vertex_rows: u32, d_counts: *mut c_void,
+                                    d_stats: *mut c_void, stats_capacity: u32, d_scaled_bgr: *mut c_void, ow: *mut u32,
+                                    oh: *mut u32) -> i32;
 }

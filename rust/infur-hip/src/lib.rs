@@ -611,6 +611,80 @@ impl Processor for HipRuns {
     }
 }
 
+// ---------------------------------------------------------------- Outlines (region boundaries as polygon loops)
+/// What `HipOutlines` produces: `loops` holds `min(n_loops, loops_rows)` records of `INFUR_LOOP_WORDS` words (OFFSET, COUNT, VALUE,
+/// START), `vertices` the first `min(n_vertices, vertex_rows)` vertex ids `Y*(w+1) + X`, loops back to back; the three counts are
+/// complete whatever the rows are (`n_loops == 0 && n_edges > 0`: the edges exceeded `max_edges`).
+pub struct Outlines { pub loops_rows: usize, pub vertex_rows: usize, pub n_loops: u32, pub n_vertices: u32, pub n_edges: u32,
+                      pub loops: Vec<u32>, pub vertices: Vec<u32> }
+impl Default for Outlines {
+    fn default() -> Self {
+        Self { loops_rows: 1 << 16, vertex_rows: 1 << 20, n_loops: 0, n_vertices: 0, n_edges: 0, loops: Vec::new(), vertices: Vec::new() }
+    }
+}
+impl Outlines {
+    pub fn rows(&self) -> usize { (self.n_loops as usize).min(self.loops_rows) }
+    pub fn word(&self, l: usize, word: u32) -> u32 { self.loops[l * sys::INFUR_LOOP_WORDS as usize + word as usize] }
+    /// the boundary of a hole (counter-clockwise on a y-down screen)
+    pub fn is_hole(&self, l: usize) -> bool { self.word(l, sys::INFUR_LOOP_START) & 3 == 2 }
+}
+pub enum OutlinesCmd { Skip(u32), NoSkip, Connectivity(u32), MaxEdges(u32) }
+/// The polygon stage: the boundaries of the value-regions of a plane as closed loops.  Integer results, identical from run to run.
+pub struct HipOutlines { ctx: Rc<Ctx>, skip: Option<u32>, conn8: bool, max_edges: u32, dirty: bool }
+impl HipOutlines {
+    pub fn new(ctx: Rc<Ctx>) -> Self { Self { ctx, skip: None, conn8: false, max_edges: 0, dirty: true } }
+}
+impl Processor for HipOutlines {
+    type Command = OutlinesCmd;
+    type ControlError = HipError;
+    type Input = RunsPlane;
+    type Output = Outlines;
+    type ProcessResult = Result<(), HipError>;
+
+    fn control(&mut self, cmd: OutlinesCmd) -> Result<&mut Self, HipError> {
+        let (skip, conn8, max_edges) = match cmd {
+            OutlinesCmd::Skip(v) => (Some(v), self.conn8, self.max_edges),
+            OutlinesCmd::NoSkip => (None, self.conn8, self.max_edges),
+            OutlinesCmd::Connectivity(4) => (self.skip, false, self.max_edges),
+            OutlinesCmd::Connectivity(8) => (self.skip, true, self.max_edges),
+            OutlinesCmd::Connectivity(_) => return Err(HipError::status(sys::INFUR_E_INVALID_ARG)),
+            OutlinesCmd::MaxEdges(n) => (self.skip, self.conn8, n),
+        };
+        self.dirty |= (skip, conn8, max_edges) != (self.skip, self.conn8, self.max_edges);
+        self.skip = skip;
+        self.conn8 = conn8;
+        self.max_edges = max_edges;
+        Ok(self)
+    }
+    fn is_dirty(&self) -> bool { self.dirty }
+    fn advance(&mut self, inp: &RunsPlane, out: &mut Outlines) -> Result<(), HipError> {
+        self.dirty = false;
+        let [w, h] = inp.size;
+        let (ptr, len, elem_bytes) = match &inp.data {
+            RunsPlaneData::U8(p) => (p.as_ptr() as *const std::ffi::c_void, p.len(), 1u32),
+            RunsPlaneData::U32(p) => (p.as_ptr() as *const std::ffi::c_void, p.len(), 4u32),
+        };
+        if len != w * h { return Err(HipError::status(sys::INFUR_E_SHAPE)); }
+        out.loops.resize(out.loops_rows * sys::INFUR_LOOP_WORDS as usize, 0);
+        out.vertices.resize(out.vertex_rows, 0);
+        let mut counts = [0u32; 3];
+        let flags = if self.skip.is_some() { sys::INFUR_OUTLINES_SKIP } else { 0 } | if self.conn8 { sys::INFUR_OUTLINES_CONN8 } else { 0 };
+        let rc = unsafe {
+            sys::infur_outlines(self.ctx.0, ptr, elem_bytes, h as u32, w as u32, flags, self.skip.unwrap_or(0), self.max_edges,
+                                if out.loops_rows > 0 { out.loops.as_mut_ptr() } else { std::ptr::null_mut() }, out.loops_rows as u32,
+                                if out.vertex_rows > 0 { out.vertices.as_mut_ptr() } else { std::ptr::null_mut() }, out.vertex_rows as u32,
+                                counts.as_mut_ptr())
+        };
+        if rc != sys::INFUR_OK { return Err(HipError::from_ctx(&self.ctx, rc)); }
+        out.n_loops = counts[0];
+        out.n_vertices = counts[1];
+        out.n_edges = counts[2];
+        out.loops.truncate(out.rows() * sys::INFUR_LOOP_WORDS as usize);
+        out.vertices.truncate((out.n_vertices as usize).min(out.vertex_rows));
+        Ok(())
+    }
+}
+
 // ---------------------------------------------------------------- streaming ring with zero-copy slots (main.rs:27-99,105; ABI 5)
 /// The bounded queue of frames in flight (`sync_channel(2)`, main.rs:105) over `infur_stream_*`.  `next_slot` / `commit` let the
 /// decoder fill the ring's own pinned buffer in place -- what `ff-video/src/decoder.rs:156-165` does with its reused `BgrImage` --
