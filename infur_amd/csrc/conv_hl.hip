@@ -842,12 +842,10 @@ static hipError_t launch_hl_t(const ConvArgs& a, int out_f32, hipStream_t s) {
     return hl_pipe_on() ? launch_hl_p<BM, BN, WM, WN, NIMG, true>(a, out_f32, s) : launch_hl_p<BM, BN, WM, WN, NIMG, false>(a, out_f32, s);
 }
 
-// configurations of mode 5 (indices of conv_igemm.hip's table whose tile dimensions they share): 11 = 256x256 (8 waves of
-// 128x64), 0 = 128x128 (4 waves of 64x64), 6 = 256x128 (8 waves of 64x64), 5 = 128x256 (8 waves of 64x64); 12 = 256x128 and
-// 14 = 128x256 as FOUR waves of 128x64 with a ring of two images: two workgroups per CU
-bool conv_hl_config_valid(const ConvArgs& a, int cfg, int out_f32) {
-    if (cfg == 15) return conv_hl_areg_valid(a, out_f32);  // conv_hl_areg.hip: the activation fragment in registers (1x1 expansions)
-    if (cfg != 11 && cfg != 0 && cfg != 6 && cfg != 5 && cfg != 12 && cfg != 14 && cfg != 13 && cfg != 16 && cfg != 17) return false;
+// the forms of mode 5: conv_forms.h (kFamHL: this file's kernel, kFamHLAreg: conv_hl_areg.hip)
+bool conv_hl_config_valid(const ConvArgs& a, const ConvForm& f, int out_f32) {
+    if (f.family == kFamHLAreg) return conv_hl_areg_valid(a, out_f32);
+    if (f.family != kFamHL) return false;
     if (!a.in_lo || !a.wt_lo) return false;
     if (a.in2 && (!a.in2_lo || out_f32 || a.res || a.KH != 1 || a.KW != 1 || a.pad != 0 || a.stride != 1 || a.Cin2 % HL_KC != 0 || a.batch > 1 ||
                   (size_t)a.H2 * a.W2 * a.Cin2 * 2 >= 0x80000000ull))
@@ -857,28 +855,17 @@ bool conv_hl_config_valid(const ConvArgs& a, int cfg, int out_f32) {
     if (out_f32 ? (a.res != nullptr) : (!a.out_lo || (a.res != nullptr) != (a.res_lo != nullptr) || (a.Cout & 7))) return false;
     if (a.batch > 1 && (a.in_bs & 1 || a.wt_bs & 1 || !out_f32)) return false;
     if ((size_t)a.Cout * (a.in2 ? a.Cin + a.Cin2 : a.KH * a.KW * a.Cin) * 2 >= 0x80000000ull) return false;
-    const int bn = (cfg == 11 || cfg == 5 || cfg == 14 || cfg == 13 || cfg == 16) ? 256 : 128;
-    return bn <= a.Cout || bn == 128;  // Cout < 128 (layer1, the logits): the 128-wide N tile with its surplus rows out of range
+    return f.bn <= a.Cout || f.bn == 128;  // Cout < 128 (layer1, the logits): the 128-wide N tile with its surplus rows out of range
 }
 
 hipError_t launch_conv_hl(const ConvArgs& a, int out_f32, int cfg, hipStream_t s) {
-    if (cfg < 0) cfg = a.Cout >= 256 && (size_t)a.OH * a.OW * (a.batch > 1 ? a.batch : 1) >= 256 * 200 ? 11 : 0;
-    if (!conv_hl_config_valid(a, cfg, out_f32)) return hipErrorInvalidValue;
-    switch (cfg) {
-        case 15: return launch_conv_hl_areg(a, s);
-        case 11: return launch_hl_t<256, 256, 2, 4>(a, out_f32, s);
-        case 0: return launch_hl_t<128, 128, 2, 2>(a, out_f32, s);
-        case 6: return launch_hl_t<256, 128, 4, 2>(a, out_f32, s);
-        case 5: return launch_hl_t<128, 256, 2, 4>(a, out_f32, s);
-        case 12: return launch_hl_t<256, 128, 2, 2, 2>(a, out_f32, s);
-        case 14: return launch_hl_t<128, 256, 1, 4, 2>(a, out_f32, s);
-        case 13: return launch_hl_t<256, 256, 4, 2>(a, out_f32, s);  // 8 waves of 64 x 128: a wave's epilogue rows are 128 channels wide
-        // round 6: the two-workgroups-per-CU forms with 64 x 128 wave tiles (the expansions' epilogue moves whole 256 / 128-byte rows
-        // of the hi / lo planes per pixel instead of 128 / 64)
-        case 16: return launch_hl_t<128, 256, 2, 2, 2>(a, out_f32, s);
-        case 17: return launch_hl_t<256, 128, 4, 1, 2>(a, out_f32, s);
-        default: return hipErrorInvalidValue;
-    }
+    const ConvForm* form = conv_form(cfg, kModeHL);
+    if (!form || !conv_hl_config_valid(a, *form, out_f32)) return hipErrorInvalidValue;
+    return conv_form_visit<kFirstHLForm, kNumConvForms>(cfg, hipErrorInvalidValue, [&](auto row) {
+        constexpr ConvForm f = kConvForms[decltype(row)::value];
+        if constexpr (f.family == kFamHL) return launch_hl_t<f.bm, f.bn, f.wm, f.wn, f.stage>(a, out_f32, s);
+        else return launch_conv_hl_areg(a, s);
+    });
 }
 
 // ---- weights: f32 [rows][cols] (already in the kernel's K order) * scale -> hi f16 at dst, lo e5m2 at dst_lo, both K-BLOCK-MAJOR:

@@ -22,16 +22,13 @@
 // 4 MFMAs; A and B use the same permutation of k, so the sum is complete.  Template flags select the addressing
 // form (G1: 1x1 GEMM), the residual prefetch (RESPF) and the two-source form (DUAL: conv3 + downsample branch).
 // Every tile configuration accumulates k in the same order: they are bit-identical, the choice is a speed knob
-// (pick_cfg in infur_capi.cpp measures it per layer shape).
+// (pick_cfg in infur_tuner.cpp measures it per layer shape).
 //
 // This header holds the kernel template and its launchers; it is compiled once per arithmetic mode (conv_igemm_f32.hip,
 // conv_igemm_f16.hip, conv_igemm_split.hip, conv_igemm_i8.hip: the instantiations of one mode each, built in parallel), and
-// conv_igemm.hip holds the configuration table and the dispatch.
+// conv_forms.h holds the table of configurations, conv_igemm.hip the dispatch.
 #pragma once
 #include <atomic>
-#include <mutex>
-#include <string>
-#include <cstdlib>
 #include <type_traits>
 
 #include "kernels.h"
@@ -1012,6 +1009,29 @@ static hipError_t launch_cfg(const ConvArgs& a, hipStream_t s) {
     return launch_cfg_g<T, OutT, SPLIT, FP8X, false, false, false, BM, BN, WM, WN, NBUF>(a, s);
 }
 
+// one row of conv_forms.h's table on the operand types of this translation unit; what the row's modes exclude is not instantiated
+template <typename T, typename OutT, bool SPLIT, bool FP8X, int I>
+static hipError_t launch_form(const ConvArgs& a, hipStream_t s) {
+    constexpr ConvForm f = kConvForms[I];
+    constexpr ConvMode kMode = std::is_same<T, signed char>::value ? kModeI8 : std::is_same<T, _Float16>::value ? kModeF16
+                               : !SPLIT ? kModeF32 : FP8X ? kModeSplitFp8 : kModeSplit;
+    if constexpr ((f.modes & mode_bit(kMode)) != 0 && f.family == kFamTiled) {
+        return launch_cfg<T, OutT, SPLIT, FP8X, f.bm, f.bn, f.wm, f.wn, f.stage>(a, s);
+    } else if constexpr ((f.modes & mode_bit(kMode)) != 0 && !std::is_same<OutT, float>::value) {  // (never the f32 logits)
+        if constexpr (f.family == kFamHalo) {
+            return kMode == kModeI8 ? launch_conv3x3_halo_q(a, f.bn, s) : launch_conv3x3_halo(a, f.bn, s);
+        } else if constexpr (f.family == kFamHalo4) {
+            return launch_conv3x3_halo4(a, s);
+        } else if constexpr (kMode == kModeI8) {  // kFamAreg, kFamAregNsplit
+            const int nsplit = f.family == kFamAreg ? 1 : conv1x1_q8_nsplit(a);
+            if (conv1x1_q8_valid(a, kMode, 0) && (f.family == kFamAreg || nsplit > 1)) return launch_conv1x1_q8(a, nsplit, s);
+        } else {
+            if (conv1x1_areg_valid(a, kMode, 0)) return launch_conv1x1_areg(a, s);
+        }
+    }
+    return hipErrorInvalidValue;
+}
+
 template <typename T, typename OutT, bool SPLIT = false, bool FP8X = false>
 static hipError_t launch_t(const ConvArgs& a, int cfg, hipStream_t s) {
     constexpr size_t ES = sizeof(T);
@@ -1019,59 +1039,7 @@ static hipError_t launch_t(const ConvArgs& a, int cfg, hipStream_t s) {
     // 32-bit buffer offsets with 0x80000000 as the out-of-range marker
     if ((size_t)a.H * a.W * a.Cin * ES >= 0x80000000ull || (size_t)a.Cout * a.KH * a.KW * a.Cin * ES >= 0x80000000ull)
         return hipErrorInvalidValue;
-    if (cfg < 0) cfg = conv_igemm_default_config(a);
-    switch (cfg) {
-        case 0: return launch_cfg<T, OutT, SPLIT, FP8X, 128, 128, 2, 2>(a, s);
-        case 1: return launch_cfg<T, OutT, SPLIT, FP8X, 64, 128, 2, 2>(a, s);
-        case 2: return launch_cfg<T, OutT, SPLIT, FP8X, 128, 64, 2, 2>(a, s);
-        case 3: return launch_cfg<T, OutT, SPLIT, FP8X, 64, 64, 2, 2>(a, s);
-        case 4: return launch_cfg<T, OutT, SPLIT, FP8X, 256, 32, 4, 1>(a, s);
-        case 5: return launch_cfg<T, OutT, SPLIT, FP8X, 128, 256, 2, 4>(a, s);
-        case 6: return launch_cfg<T, OutT, SPLIT, FP8X, 256, 128, 4, 2>(a, s);
-        case 7: return launch_cfg<T, OutT, SPLIT, FP8X, 128, 128, 2, 2, 1>(a, s);
-        case 8: return launch_cfg<T, OutT, SPLIT, FP8X, 128, 64, 2, 2, 1>(a, s);
-        case 9: return launch_cfg<T, OutT, SPLIT, FP8X, 64, 128, 2, 2, 1>(a, s);
-        case 10: return launch_cfg<T, OutT, SPLIT, FP8X, 64, 64, 2, 2, 1>(a, s);
-        case 11: return launch_cfg<T, OutT, SPLIT, FP8X, 256, 256, 2, 4, 3>(a, s);  // 8 waves of 128x64, one fragment set
-        case 12: return launch_cfg<T, OutT, SPLIT, FP8X, 256, 128, 4, 2, 3>(a, s);  // 8 waves of 64x64, one fragment set
-        case 13:
-        case 14:
-            if constexpr ((std::is_same<T, _Float16>::value || std::is_same<T, signed char>::value) && !SPLIT) {  // LDS-DMA staging
-                if (cfg == 13) return launch_cfg<T, OutT, SPLIT, FP8X, 256, 256, 2, 4, 4>(a, s);
-                return launch_cfg<T, OutT, SPLIT, FP8X, 256, 128, 4, 2, 4>(a, s);
-            }
-            return hipErrorInvalidValue;
-        case 16:
-        case 17:
-            if constexpr ((std::is_same<T, _Float16>::value || std::is_same<T, signed char>::value) && !SPLIT) {
-                if (cfg == 16) return launch_cfg<T, OutT, SPLIT, FP8X, 256, 256, 2, 4, 5>(a, s);
-                return launch_cfg<T, OutT, SPLIT, FP8X, 256, 128, 4, 2, 5>(a, s);
-            }
-            return hipErrorInvalidValue;
-        case 15:
-            if constexpr (std::is_same<T, _Float16>::value && std::is_same<OutT, _Float16>::value && !SPLIT) {
-                if (conv1x1_areg_valid(a, 1, 0)) return launch_conv1x1_areg(a, s);
-            }
-            if constexpr (std::is_same<T, signed char>::value && std::is_same<OutT, unsigned char>::value) {
-                if (conv1x1_q8_valid(a, 4, 0)) return launch_conv1x1_q8(a, 1, s);
-            }
-            return hipErrorInvalidValue;
-        case 19:
-        case 20:
-            if constexpr (std::is_same<T, _Float16>::value && std::is_same<OutT, _Float16>::value && !SPLIT) return launch_conv3x3_halo(a, cfg == 19 ? 128 : 256, s);
-            if constexpr (std::is_same<T, signed char>::value && std::is_same<OutT, unsigned char>::value) return launch_conv3x3_halo_q(a, cfg == 19 ? 128 : 256, s);
-            return hipErrorInvalidValue;
-        case 21:
-            if constexpr (std::is_same<T, _Float16>::value && std::is_same<OutT, _Float16>::value && !SPLIT) return launch_conv3x3_halo4(a, s);
-            return hipErrorInvalidValue;
-        case 18:
-            if constexpr (std::is_same<T, signed char>::value && std::is_same<OutT, unsigned char>::value) {
-                if (conv1x1_q8_valid(a, 4, 0) && conv1x1_q8_nsplit(a) > 1) return launch_conv1x1_q8(a, conv1x1_q8_nsplit(a), s);
-            }
-            return hipErrorInvalidValue;
-        default: return hipErrorInvalidValue;
-    }
+    return conv_form_visit<0, kNumConvCfgs>(cfg, hipErrorInvalidValue, [&](auto row) { return launch_form<T, OutT, SPLIT, FP8X, decltype(row)::value>(a, s); });
 }
-
 
 }  // namespace infur

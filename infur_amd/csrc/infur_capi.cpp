@@ -533,7 +533,7 @@ int32_t model_load_dev(infur_ctx* c, const void* d_blob, size_t len) {
         off += align_up((size_t)L.cout * L.cin * 2, 256);
         HIPCHK(c, launch_b2b_pack_w3(L.d_w, L.d_w3i, L.cin, c->stream));
     }
-    if (ctx_mode(c) == INFUR_DTYPE_F32_SPLIT || ctx_hl(c)) RETIF(split_weights(c, g));
+    if (ctx_mode(c) == kModeSplit || ctx_hl(c)) RETIF(split_weights(c, g));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     model_free(c);  // the old model goes only now
     c->d_weights = d_weights;
@@ -588,80 +588,44 @@ ConvArgs conv_args(const ConvLayer& L, const Tensor& in, const Tensor* res, cons
 // ---- one convolution on the implicit-GEMM kernel ----
 int32_t run_conv(infur_ctx* c, const ConvLayer& L, const Tensor& in, const Tensor* res, Tensor* out) {
     const int oh = conv_out(in.h, L.k, L.stride, L.pad, L.dil), ow = conv_out(in.w, L.k, L.stride, L.pad, L.dil);
-    const int mode = ctx_mode(c);
+    const ConvMode mode = ctx_mode(c);
     const bool hl = ctx_hl(c);
-    const int out_f32 = ((mode != 1 && !hl) || L.role == 'c') ? 1 : 0;  // the logits leave the conv stack in f32
+    const int out_f32 = ((mode != kModeF16 && !hl) || L.role == 'c') ? 1 : 0;  // the logits leave the conv stack in f32
     RETIF(talloc(c, oh, ow, L.cout, out_f32 ? 4 : (hl ? 3 : 2), out));
-    if (L.d_u && !res && hl) {
-        // three-byte mode: V and the conv output are hi / lo planes, the Winograd-domain product M stays f32
+    if (L.d_u && !res) {
+        // Winograd F(mt x mt, 3x3): input transform -> (mt+2)^2 batched GEMMs -> output transform (+bias, ReLU).  Three-byte mode: V
+        // and the conv output are hi / lo planes (es 3; the operand strides count the hi plane), the Winograd-domain product M stays f32
         const int mt = wino_mt(c), P = wino_planes(c);
         const int T = wino_num_tiles(in.h, in.w, L.dil, mt);
+        const int es = hl ? 3 : 4, op_es = hl ? 2 : 4;
         Tensor V, M;
-        RETIF(talloc(c, P, T, in.c, 3, &V));
+        RETIF(talloc(c, P, T, in.c, es, &V));
         RETIF(talloc(c, P, T, L.cout, 4, &M));
         const double direct = 2.0 * oh * ow * (double)L.cout * L.cin * 9.0;
         {
-            ProfScope ps(c, L.name + "/in", "wino_input_hl", 0, (double)in.elems() * 3 + (double)V.elems() * 3, 0.0);
-            HIPCHK(c, launch_wino_input_hl(in.p, in.lo, in.h, in.w, in.c, L.dil, mt, split_wino_scale(mt), V.p, V.lo, c->d_hlmon, c->stream));
+            ProfScope ps(c, L.name + "/in", hl ? "wino_input_hl" : "wino_input", 0, (double)in.elems() * es + (double)V.elems() * es, 0.0);
+            if (hl) HIPCHK(c, launch_wino_input_hl(in.p, in.lo, in.h, in.w, in.c, L.dil, mt, split_wino_scale(mt), V.p, V.lo, c->d_hlmon, c->stream));
+            else HIPCHK(c, launch_wino_input((const float*)in.p, in.h, in.w, in.c, L.dil, mt, (float*)V.p, c->d_range ? c->d_range + 1 : nullptr, c->stream));
         }
         ConvArgs g;
         g.in = V.p; g.in_lo = V.lo; g.wt = L.d_u; g.wt_lo = L.d_ul; g.bias = nullptr; g.res = nullptr; g.out = M.p;
         g.H = 1; g.W = T; g.Cin = in.c; g.OH = 1; g.OW = T; g.Cout = L.cout;
         g.KH = 1; g.KW = 1; g.stride = 1; g.pad = 0; g.dil = 1; g.relu = 0;
         g.batch = P;
-        g.in_bs = (size_t)T * in.c * 2; g.wt_bs = (size_t)L.cout * L.cin * 2; g.out_bs = (size_t)T * L.cout * 4;
-        g.acc_scale_b = L.d_uacc;
-        int gcfg = -1;
-        RETIF(pick_cfg(c, g, 5, 1, &gcfg));
-        {
-            ProfScope ps(c, L.name, conv_igemm_config_name(gcfg, 5), 2.0 * P * T * (double)L.cout * L.cin,
-                         (double)V.elems() * 3 + (double)M.bytes() + (double)P * L.cout * L.cin * 3, direct);
-            HIPCHK(c, launch_conv_igemm(g, 5, 1, gcfg, c->stream));
-        }
-        pool_release(c, V);
-        {
-            ProfScope ps(c, L.name + "/out", "wino_output_hl", 0, (double)M.bytes() + (double)out->elems() * 3, 0.0);
-            HIPCHK(c, launch_wino_output_hl((const float*)M.p, oh, ow, L.cout, L.dil, mt, L.d_b, L.relu ? 1 : 0, out->p, out->lo, c->d_hlmon, c->stream));
-        }
-        pool_release(c, M);
-        if (c->opt.keep_activations) c->kept.push_back(*out);
-        return INFUR_OK;
-    }
-    if (L.d_u && !res) {
-        // Winograd F(mt x mt, 3x3): input transform -> (mt+2)^2 batched GEMMs -> output transform (+bias, ReLU)
-        const int mt = wino_mt(c), P = wino_planes(c);
-        const int T = wino_num_tiles(in.h, in.w, L.dil, mt);
-        Tensor V, M;
-        RETIF(talloc(c, P, T, in.c, 4, &V));
-        RETIF(talloc(c, P, T, L.cout, 4, &M));
-        const double direct = 2.0 * oh * ow * (double)L.cout * L.cin * 9.0;
-        {
-            ProfScope ps(c, L.name + "/in", "wino_input", 0, (double)in.bytes() + (double)V.bytes(), 0.0);
-            HIPCHK(c, launch_wino_input((const float*)in.p, in.h, in.w, in.c, L.dil, mt, (float*)V.p, c->d_range ? c->d_range + 1 : nullptr, c->stream));
-        }
-        ConvArgs g;
-        g.in = V.p; g.wt = L.d_u; g.bias = nullptr; g.res = nullptr; g.out = M.p;
-        g.H = 1; g.W = T; g.Cin = in.c; g.OH = 1; g.OW = T; g.Cout = L.cout;
-        g.KH = 1; g.KW = 1; g.stride = 1; g.pad = 0; g.dil = 1; g.relu = 0;
-        g.batch = P;
-        g.in_bs = (size_t)T * in.c * 4; g.wt_bs = (size_t)L.cout * L.cin * 4; g.out_bs = (size_t)T * L.cout * 4;
-        if (mode == INFUR_DTYPE_F32_SPLIT) {
+        g.in_bs = (size_t)T * in.c * op_es; g.wt_bs = (size_t)L.cout * L.cin * op_es; g.out_bs = (size_t)T * L.cout * 4;
+        if (mode == kModeSplit) {
             g.a_scale = split_wino_scale(mt);
             g.acc_scale = 1.0f / (g.a_scale * L.u_scale);
-            g.acc_scale_b = L.d_uacc;  // one scale per Winograd plane
         }
-        int gcfg = -1;
-        RETIF(pick_cfg(c, g, conv_mode(c), 1, &gcfg));
-        {
-            ProfScope ps(c, L.name, conv_igemm_config_name(gcfg, conv_mode(c)), 2.0 * P * T * (double)L.cout * L.cin,
-                         (double)V.bytes() + (double)M.bytes() + (double)P * L.cout * L.cin * 4, direct);
-            HIPCHK(c, launch_conv_igemm(g, conv_mode(c), 1, gcfg, c->stream));
-        }
+        if (mode == kModeSplit || hl) g.acc_scale_b = L.d_uacc;  // one scale per Winograd plane
+        RETIF(run_tuned(c, L.name, g, conv_mode(c), 1, 2.0 * P * T * (double)L.cout * L.cin,
+                        (double)V.elems() * es + (double)M.bytes() + (double)P * L.cout * L.cin * es, direct));
         pool_release(c, V);
         {
-            ProfScope ps(c, L.name + "/out", "wino_output", 0, (double)M.bytes() + (double)out->bytes(), 0.0);
-            HIPCHK(c, launch_wino_output((const float*)M.p, oh, ow, L.cout, L.dil, mt, L.d_b, L.relu ? 1 : 0, (float*)out->p,
-                                         L.role == 'c' ? nullptr : c->d_range, c->stream));
+            ProfScope ps(c, L.name + "/out", hl ? "wino_output_hl" : "wino_output", 0, (double)M.bytes() + (double)out->elems() * es, 0.0);
+            if (hl) HIPCHK(c, launch_wino_output_hl((const float*)M.p, oh, ow, L.cout, L.dil, mt, L.d_b, L.relu ? 1 : 0, out->p, out->lo, c->d_hlmon, c->stream));
+            else HIPCHK(c, launch_wino_output((const float*)M.p, oh, ow, L.cout, L.dil, mt, L.d_b, L.relu ? 1 : 0, (float*)out->p,
+                                              L.role == 'c' ? nullptr : c->d_range, c->stream));
         }
         pool_release(c, M);
         if (c->opt.keep_activations) c->kept.push_back(*out);
@@ -671,19 +635,14 @@ int32_t run_conv(infur_ctx* c, const ConvLayer& L, const Tensor& in, const Tenso
     const double flops = 2.0 * oh * ow * (double)L.cout * L.cin * L.k * L.k;
     const double bytes = (double)in.bytes() + (double)out->bytes() + (res ? (double)res->bytes() : 0.0) +
                          (double)L.cout * L.cin * L.k * L.k * in.es;
-    if (mode == INFUR_DTYPE_F32_SPLIT) {
+    if (mode == kModeSplit) {
         a.a_scale = kSplitActScale;
         a.acc_scale = 1.0f / (a.a_scale * L.w_scale);
         a.amax = L.role == 'c' ? nullptr : c->d_range;  // the logits feed no GEMM
     }
     if (hl) a.acc_scale = 1.0f / L.w_scale;  // (activations are stored unscaled: e5m2 lo planes share f16's exponent range)
     if (hl && !out_f32) a.hl_mon = c->d_hlmon;
-    int cfg = -1;
-    RETIF(pick_cfg(c, a, conv_mode(c), out_f32, &cfg));
-    {
-        ProfScope ps(c, L.name, conv_igemm_config_name(cfg, conv_mode(c)), flops, bytes);
-        HIPCHK(c, launch_conv_igemm(a, conv_mode(c), out_f32, cfg, c->stream));
-    }
+    RETIF(run_tuned(c, L.name, a, conv_mode(c), out_f32, flops, bytes));
     if (c->opt.keep_activations) c->kept.push_back(*out);
     return INFUR_OK;
 }
@@ -695,14 +654,14 @@ int32_t run_conv_dual(infur_ctx* c, const ConvLayer& L3, const ConvLayer& D, con
     const int oh = t2.h, ow = t2.w;
     if (conv_out(x.h, 1, D.stride, 0, 1) != oh || conv_out(x.w, 1, D.stride, 0, 1) != ow)
         return fail(c, INFUR_E_SHAPE, "downsample branch %dx%d/%d does not land on %dx%d", x.w, x.h, D.stride, ow, oh);
-    const int mode = ctx_mode(c);
+    const ConvMode mode = ctx_mode(c);
     RETIF(talloc(c, oh, ow, L3.cout, act_es(c), out));
     ConvArgs a;
     a.in = t2.p; a.wt = L3.d_wcat; a.bias = L3.d_bcat; a.res = nullptr; a.out = out->p;
     a.H = t2.h; a.W = t2.w; a.Cin = t2.c; a.OH = oh; a.OW = ow; a.Cout = L3.cout;
     a.KH = 1; a.KW = 1; a.stride = 1; a.pad = 0; a.dil = 1; a.relu = L3.relu ? 1 : 0;
     a.in2 = x.p; a.H2 = x.h; a.W2 = x.w; a.Cin2 = x.c; a.stride2 = D.stride;
-    if (mode == INFUR_DTYPE_F32_SPLIT) {
+    if (mode == kModeSplit) {
         a.a_scale = kSplitActScale;
         a.acc_scale = 1.0f / (a.a_scale * L3.wcat_scale);
         a.amax = c->d_range;
@@ -715,14 +674,7 @@ int32_t run_conv_dual(infur_ctx* c, const ConvLayer& L3, const ConvLayer& D, con
     }
     const double flops = 2.0 * oh * ow * (double)L3.cout * (L3.cin + D.cin);
     const double bytes = (double)t2.bytes() + (double)oh * ow * x.c * x.es + (double)out->bytes() + (double)L3.cout * (L3.cin + D.cin) * t2.es;
-    int cfg = -1;
-    const int out_f32 = (mode != 1 && !hl) ? 1 : 0;
-    RETIF(pick_cfg(c, a, conv_mode(c), out_f32, &cfg));
-    {
-        ProfScope ps(c, L3.name + "+downsample", conv_igemm_config_name(cfg, conv_mode(c)), flops, bytes);
-        HIPCHK(c, launch_conv_igemm(a, conv_mode(c), out_f32, cfg, c->stream));
-    }
-    return INFUR_OK;
+    return run_tuned(c, L3.name + "+downsample", a, conv_mode(c), (mode != kModeF16 && !hl) ? 1 : 0, flops, bytes);
 }
 
 // ---- conv3 + residual + ReLU of one bottleneck and conv1 + ReLU of the NEXT one as ONE launch (conv1x1_b2b.hip) ----
@@ -755,8 +707,11 @@ int32_t run_b2b(infur_ctx* c, const ConvLayer& c3, const ConvLayer& n1, const Te
         give_back();
         return INFUR_OK;
     }
-    // the decision lives in the tuning database next to the tile configurations (flag 3 = "conv3 -> next conv1 pair")
-    const std::array<int, 13> key = {t2.h, t2.w, c3.cin, t2.h, t2.w, c3.cout, 1, 1, 1, 1, 3, 1, 0};
+    // the decision lives in the tuning database next to the tile configurations, under the conv3's shape with kTunePairFlag
+    ConvArgs gemm = conv_args(c3, t2, nullptr, *y);  // (c3.k == 1: b2b_candidate)
+    gemm.stride = gemm.dil = 1;
+    TuneKey key = tune_key(gemm, kModeF16, 0);
+    key[10] = kTunePairFlag;
     static const int forced = getenv("INFUR_B2B") ? atoi(getenv("INFUR_B2B")) : -1;  // test hook: 1 always, 0 never
     bool use;
     auto it = c->tuned.find(key);
@@ -769,30 +724,16 @@ int32_t run_b2b(infur_ctx* c, const ConvLayer& c3, const ConvLayer& n1, const Te
     } else {
         const ConvArgs a3 = conv_args(c3, t2, &x, *y), a1 = conv_args(n1, *y, nullptr, *t1n);
         int cfg3 = -1, cfg1 = -1;
-        RETIF(pick_cfg(c, a3, 1, 0, &cfg3));
-        RETIF(pick_cfg(c, a1, 1, 0, &cfg1));
+        RETIF(pick_cfg(c, a3, kModeF16, 0, &cfg3));
+        RETIF(pick_cfg(c, a1, kModeF16, 0, &cfg1));
         EventPair ev;
         HIPCHK(c, ev.create());
-        float t_pair = 1e30f, t_fused = 1e30f;
-        for (int r = 0; r < 5; r++) {  // first round = warm-up
-            HIPCHK(c, hipEventRecord(ev.e0, c->stream));
-            HIPCHK(c, launch_conv_igemm(a3, 1, 0, cfg3, c->stream));
-            HIPCHK(c, launch_conv_igemm(a1, 1, 0, cfg1, c->stream));
-            HIPCHK(c, hipEventRecord(ev.e1, c->stream));
-            HIPCHK(c, hipEventSynchronize(ev.e1));
-            float ms = 0;
-            HIPCHK(c, hipEventElapsedTime(&ms, ev.e0, ev.e1));
-            if (r && ms < t_pair) t_pair = ms;
-        }
-        for (int r = 0; r < 5; r++) {
-            HIPCHK(c, hipEventRecord(ev.e0, c->stream));
-            HIPCHK(c, launch_conv1x1_b2b(b, c->stream));
-            HIPCHK(c, hipEventRecord(ev.e1, c->stream));
-            HIPCHK(c, hipEventSynchronize(ev.e1));
-            float ms = 0;
-            HIPCHK(c, hipEventElapsedTime(&ms, ev.e0, ev.e1));
-            if (r && ms < t_fused) t_fused = ms;
-        }
+        float t_pair, t_fused;  // 5 timings each, the first a warm-up
+        RETIF(min_launch_ms(c, ev, 1, 5, &t_pair, [&] {
+            const hipError_t e = launch_conv_igemm(a3, kModeF16, 0, cfg3, c->stream);
+            return e != hipSuccess ? e : launch_conv_igemm(a1, kModeF16, 0, cfg1, c->stream);
+        }));
+        RETIF(min_launch_ms(c, ev, 1, 5, &t_fused, [&] { return launch_conv1x1_b2b(b, c->stream); }));
         use = t_fused < t_pair;
         c->tuned[key] = use ? 1 : 0;
         c->mem_gen++;
@@ -855,8 +796,8 @@ int32_t forward(infur_ctx* c, const uint8_t* d_bgr, int w, int h) {
     if (!c->opt.keep_activations && !c->opt.no_fuse_stem_pool) {
         RETIF(talloc(c, ph, pw, 64, act_es(c), &x));
         const void* wimg = nullptr;
-        if (ctx_mode(c) == INFUR_DTYPE_F16) RETIF(stem16_image(c, (const float*)stem.d_w, 1.0f, 0, &wimg));
-        if (ctx_mode(c) == INFUR_DTYPE_F32_SPLIT || ctx_hl(c)) RETIF(stem16_image(c, (const float*)stem.d_w, stem.w_scale, 1, &wimg));
+        if (ctx_mode(c) == kModeF16) RETIF(stem16_image(c, (const float*)stem.d_w, 1.0f, 0, &wimg));
+        if (ctx_mode(c) == kModeSplit || ctx_hl(c)) RETIF(stem16_image(c, (const float*)stem.d_w, stem.w_scale, 1, &wimg));
         ProfScope ps(c, "backbone.conv1+maxpool", "stem_pool", 2.0 * sh * sw * 64 * 147, (double)h * w * 3 + (double)x.bytes(),
                      2.0 * sh * sw * 64 * 147);
         // exact f32 MFMA in the f32 mode; in the f16-rate modes the stem runs on the f16 matrix cores as the conv stack does

@@ -281,12 +281,7 @@ int32_t run_qconv(infur_ctx* c, const ConvLayer& L, const Tensor& in, const Tens
     }
     const double flops = 2.0 * oh * ow * (double)L.cout * L.cin * L.k * L.k;
     const double bytes = (double)in.bytes() + (double)out->bytes() + (res ? (double)res->bytes() : 0.0) + (double)cout_k * cin_k * L.k * L.k;
-    int cfg = -1;
-    RETIF(pick_cfg(c, a, 4, out_f32, &cfg));
-    {
-        ProfScope ps(c, L.name, conv_igemm_config_name(cfg, 4), flops, bytes);
-        HIPCHK(c, launch_conv_igemm(a, 4, out_f32, cfg, c->stream));
-    }
+    RETIF(run_tuned(c, L.name, a, kModeI8, out_f32, flops, bytes));
     if (c->opt.keep_activations) c->kept.push_back(*out);
     return INFUR_OK;
 }

@@ -1,7 +1,7 @@
 // infur_rt.h -- internal interface between the host runtime's translation units (round 5: infur_capi.cpp was 2,900 lines):
 //   infur_capi.cpp          context, arena, the float model (load, conv dispatch, forward), the C entry points of the stages
 //   infur_quant_model.cpp   quantised models (INFURQ01): load + forward
-//   infur_tuner.cpp         tile-configuration tuner (pick_cfg) and its database (infur_tune_import / _export)
+//   infur_tuner.cpp         tile-configuration tuner (pick_cfg, tune_key, min_launch_ms) and its database (infur_tune_import / _export)
 //   infur_stream.cpp        streaming ring, frame batch, pinned host buffers
 //   infur_multi.cpp         groups of contexts, RCCL
 //   infur_segments.cpp      the Segments decode (class / confidence planes, statistics): C entry points
@@ -9,11 +9,13 @@
 //   infur_tracks.cpp        Tracks (region identities from frame to frame): the tracker object and its C entry points
 //   infur_runs.cpp          Runs (a class, label or track plane as run-length records): C entry points
 //   infur_outlines.cpp      Outlines (region boundaries of a class, label or track plane as polygon loops): C entry points
+// (conv_forms.h, the table of conv modes, configurations and forms, comes with kernels.h)
 // (wave_scan.h, the device code regions.hip, tracks.hip and runs.hip share, also holds kScanBlock, which sizes their block sums)
 // Everything here lives in namespace infur and is NOT part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <exception>
 #include <new>
 #include <string>
@@ -65,13 +67,15 @@ constexpr uint32_t kPoolTrimAfter = 4;
 
 // ---- arithmetic mode of a context ----
 inline bool ctx_f16(const infur_ctx* c) { return c->opt.compute_dtype == INFUR_DTYPE_F16; }
-// GEMM arithmetic of launch_conv_igemm: 0 f32 MFMA, 1 f16, 2 f32 tensors split into f16 pairs
-// (INFUR_DTYPE_F32_SPLIT_FP8 is the split mode everywhere except inside the GEMM: conv_mode() = 3 selects its MFMA sequence,
-//  its weight rows and its own tuning entries)
+// GEMM arithmetic of launch_conv_igemm (ConvMode, conv_forms.h): a context's compute_dtype, except that INFUR_DTYPE_F32_SPLIT_FP8 is
+// the split mode everywhere but inside the GEMM -- conv_mode() = kModeSplitFp8 selects its MFMA sequence, its weight rows and its own
+// tuning entries -- and that a quantised model runs kModeI8 whatever the context's dtype
+static_assert(kModeF32 == INFUR_DTYPE_F32 && kModeF16 == INFUR_DTYPE_F16 && kModeSplit == INFUR_DTYPE_F32_SPLIT &&
+              kModeSplitFp8 == INFUR_DTYPE_F32_SPLIT_FP8 && kModeHL == INFUR_DTYPE_F16_HL, "ConvMode is the INFUR_DTYPE_* numbering");
 inline bool ctx_fp8x(const infur_ctx* c) { return c->opt.compute_dtype == INFUR_DTYPE_F32_SPLIT_FP8; }
-inline int ctx_mode(const infur_ctx* c) { return ctx_fp8x(c) ? (int)INFUR_DTYPE_F32_SPLIT : (int)c->opt.compute_dtype; }
-inline int conv_mode(const infur_ctx* c) { return ctx_fp8x(c) ? 3 : ctx_mode(c); }
-// INFUR_DTYPE_F16_HL (= conv mode 5): three-byte tensors (f16 hi + e5m2 lo planes), conv_hl.hip
+inline ConvMode ctx_mode(const infur_ctx* c) { return ctx_fp8x(c) ? kModeSplit : (ConvMode)c->opt.compute_dtype; }
+inline ConvMode conv_mode(const infur_ctx* c) { return ctx_fp8x(c) ? kModeSplitFp8 : ctx_mode(c); }
+// INFUR_DTYPE_F16_HL (= kModeHL): three-byte tensors (f16 hi + e5m2 lo planes), conv_hl.hip
 inline bool ctx_hl(const infur_ctx* c) { return c->opt.compute_dtype == INFUR_DTYPE_F16_HL; }
 inline int act_es(const infur_ctx* c) { return ctx_f16(c) ? 2 : (ctx_hl(c) ? 3 : 4); }
 inline const float* stem_lut(const infur_ctx* c) { return c->input_u8 ? c->d_u8_lut : c->d_pre_lut; }
@@ -117,7 +121,17 @@ UpQuant head_quant(const infur_ctx* c, int k);
 int32_t forward(infur_ctx* c, const uint8_t* d_bgr, int w, int h);
 int32_t stem16_image(infur_ctx* c, const float* wt, float w_scale, int split, const void** img);
 // measured tile configuration of the conv kernel for one problem shape (infur_tuner.cpp)
-int32_t pick_cfg(infur_ctx* c, const ConvArgs& a, int mode, int out_f32, int* cfg);
+int32_t pick_cfg(infur_ctx* c, const ConvArgs& a, ConvMode mode, int out_f32, int* cfg);
+// pick_cfg, then the launch inside its profile record (`layer`, the configuration's name)
+int32_t run_tuned(infur_ctx* c, const std::string& layer, const ConvArgs& a, ConvMode mode, int out_f32, double flops, double bytes,
+                  double algo_flops = -1.0);
+// The 13 integers a decision is filed under in the tuning database.  [10]: what enters beside the input -- 0 nothing, 1 a residual,
+// 2 a second source -- or kTunePairFlag: not a conv but the decision "conv3 -> next conv1 pair as one launch" (run_b2b; value 1 = fuse)
+constexpr int kTunePairFlag = 3;
+using TuneKey = std::array<int, 13>;
+inline TuneKey tune_key(const ConvArgs& a, ConvMode mode, int out_f32) {
+    return {a.H, a.W, a.Cin, a.OH, a.OW, a.Cout, a.KH, a.stride, a.dil, a.batch, a.res ? 1 : (a.in2 ? 2 : 0), mode, out_f32};
+}
 struct EventPair {  // two timing events, released on every return path
     hipEvent_t e0 = nullptr, e1 = nullptr;
     hipError_t create() {
@@ -129,6 +143,21 @@ struct EventPair {  // two timing events, released on every return path
         if (e1) (void)hipEventDestroy(e1);
     }
 };
+// *ms = the minimum of n single-launch event timings of launch() on the context's stream, the first `discard` of them left out
+template <class Launch>
+int32_t min_launch_ms(infur_ctx* c, EventPair& ev, int discard, int n, float* ms, Launch&& launch) {
+    *ms = 1e30f;
+    for (int r = 0; r < n; r++) {
+        HIPCHK(c, hipEventRecord(ev.e0, c->stream));
+        HIPCHK(c, launch());
+        HIPCHK(c, hipEventRecord(ev.e1, c->stream));
+        HIPCHK(c, hipEventSynchronize(ev.e1));
+        float t = 0;
+        HIPCHK(c, hipEventElapsedTime(&t, ev.e0, ev.e1));
+        if (r >= discard && t < *ms) *ms = t;
+    }
+    return INFUR_OK;
+}
 // ---- the front half of every fused frame call (infur_capi.cpp) ----
 // infur_scale_validate + infur_scale_out_dims, with their messages: -> the scaled dimensions
 int32_t scale_dims(infur_ctx* c, uint32_t w, uint32_t h, float factor, uint32_t* ow, uint32_t* oh);

@@ -25,9 +25,9 @@ namespace infur {
 // context's lifetime.  All configurations give bit-identical outputs, so the trial launches are
 // simply redundant evaluations of the layer.
 
-int32_t pick_cfg(infur_ctx* c, const ConvArgs& a, int mode, int out_f32, int* cfg) {
+int32_t pick_cfg(infur_ctx* c, const ConvArgs& a, ConvMode mode, int out_f32, int* cfg) {
     *cfg = conv_igemm_default_config(a);
-    if (mode == 5 && !conv_igemm_config_valid(a, *cfg, mode, out_f32)) *cfg = 0;  // (128 x 128: valid for every mode-5 shape)
+    if (mode == kModeHL && !conv_igemm_config_valid(a, *cfg, mode, out_f32)) *cfg = kCfg128x128;  // (valid for every mode-5 shape)
     // test hook: INFUR_CONV_CFG=<k> forces configuration k wherever it is a candidate.  A forced configuration that is NOT a
     // candidate for the shape falls back to the default silently; tests/test_gpu_forms.py is what checks, from the profile's kernel
     // names, that the forced form really ran.
@@ -37,8 +37,7 @@ int32_t pick_cfg(infur_ctx* c, const ConvArgs& a, int mode, int out_f32, int* cf
         return INFUR_OK;
     }
     if (c->opt.no_autotune) return INFUR_OK;
-    const std::array<int, 13> key = {a.H, a.W, a.Cin, a.OH, a.OW, a.Cout, a.KH, a.stride, a.dil, a.batch,
-                                     a.res ? 1 : (a.in2 ? 2 : 0), mode, out_f32};
+    const TuneKey key = tune_key(a, mode, out_f32);
     auto it = c->tuned.find(key);
     if (it != c->tuned.end() && conv_igemm_config_valid(a, it->second, mode, out_f32)) {
         *cfg = it->second;
@@ -53,29 +52,17 @@ int32_t pick_cfg(infur_ctx* c, const ConvArgs& a, int mode, int out_f32, int* cf
     }
     float best = 1e30f;
     std::vector<std::pair<int, float>> timed;
-    // (configuration 20 -- the BN = 256 form of conv3x3_halo.hip -- is not a tuning candidate: timed in isolation, with its operands
-    //  warm in the Infinity Cache, it beats the tiled `dmai` form on the long-K head convs by 2-4 %; inside a frame, where its
-    //  one-patch-image chunk boundaries meet HBM latency, it is 5-12 % slower (classifier.0 at 1080p 535 against 477 us).  It stays
-    //  selectable -- INFUR_CONV_CFG=20, INFUR_TUNE_HALO256=1 -- and bit-identical: tests/test_gpu_halo.py.)
-    static const bool tune_halo256 = getenv("INFUR_TUNE_HALO256") != nullptr;
-    for (int k = 0; k < conv_igemm_num_configs(); k++) {
+    static const bool tune_halo256 = getenv("INFUR_TUNE_HALO256") != nullptr;  // times what the table marks untunable (kCfgHalo256)
+    for (int k = 0; k < kNumConvCfgs; k++) {
         if (!conv_igemm_config_valid(a, k, mode, out_f32)) continue;
-        if (k == 20 && !tune_halo256) continue;
+        if (!conv_form(k, mode)->tunable && !tune_halo256) continue;
         // a candidate that cannot launch on this shape after all (invalid value) is skipped, not fatal: the layer still
         // has the other configurations; anything else (a fault, a lost device) is an error of the frame
         const hipError_t le = launch_conv_igemm(a, mode, out_f32, k, c->stream);  // warm-up (attributes, caches)
         if (le == hipErrorInvalidValue) continue;
         HIPCHK(c, le);
-        float fastest = 1e30f;
-        for (int r = 0; r < 4; r++) {  // minimum of 4 single-launch timings
-            HIPCHK(c, hipEventRecord(ev.e0, c->stream));
-            HIPCHK(c, launch_conv_igemm(a, mode, out_f32, k, c->stream));
-            HIPCHK(c, hipEventRecord(ev.e1, c->stream));
-            HIPCHK(c, hipEventSynchronize(ev.e1));
-            float ms = 0;
-            HIPCHK(c, hipEventElapsedTime(&ms, ev.e0, ev.e1));
-            if (ms < fastest) fastest = ms;
-        }
+        float fastest;  // minimum of 4 single-launch timings
+        RETIF(min_launch_ms(c, ev, 0, 4, &fastest, [&] { return launch_conv_igemm(a, mode, out_f32, k, c->stream); }));
         timed.emplace_back(k, fastest);
         if (fastest < best) {
             best = fastest;
@@ -84,11 +71,19 @@ int32_t pick_cfg(infur_ctx* c, const ConvArgs& a, int mode, int out_f32, int* cf
     }
     // Tie-break towards the larger tile: among the configurations within 2 % of the fastest, the one with the largest
     // BM x BN re-reads its operands least (A once per N tile, B once per M tile) -- the same speed for less L2 / Infinity
-    // Cache / HBM traffic, which is also what leaves room for a second frame in flight
+    // Cache / HBM traffic, which is also what leaves room for a second frame in flight.  (ConvForm::tie_area: not always the tile)
     for (const auto& kt : timed)
-        if (kt.second <= best * 1.02f && conv_igemm_config_tile_area(kt.first) > conv_igemm_config_tile_area(*cfg)) *cfg = kt.first;
+        if (kt.second <= best * 1.02f && conv_form(kt.first, mode)->tie_area > conv_form(*cfg, mode)->tie_area) *cfg = kt.first;
     c->tuned[key] = *cfg;
     c->mem_gen++;  // (a new decision: frames captured as graphs before it are stale)
+    return INFUR_OK;
+}
+
+int32_t run_tuned(infur_ctx* c, const std::string& layer, const ConvArgs& a, ConvMode mode, int out_f32, double flops, double bytes, double algo_flops) {
+    int cfg = -1;
+    RETIF(pick_cfg(c, a, mode, out_f32, &cfg));
+    ProfScope ps(c, layer, conv_igemm_config_name(cfg, mode), flops, bytes, algo_flops);
+    HIPCHK(c, launch_conv_igemm(a, mode, out_f32, cfg, c->stream));
     return INFUR_OK;
 }
 
@@ -127,7 +122,7 @@ int32_t infur_tune_import(infur_ctx* c, const char* text, size_t len) {
             const std::string ln = t.substr(pos, eol - pos);
             pos = eol + 1;
             if (ln.empty() || ln[0] == '#') continue;
-            std::array<int, 13> key;
+            TuneKey key;
             int cfg = -1, off = 0, n = 0;
             bool ok = true;
             for (int i = 0; i < 13 && ok; i++) {
@@ -135,7 +130,7 @@ int32_t infur_tune_import(infur_ctx* c, const char* text, size_t len) {
                 off += n;
             }
             ok = ok && sscanf(ln.c_str() + off, "%d", &cfg) == 1;
-            if (!ok || cfg < 0 || cfg >= conv_igemm_num_configs()) return fail(c, INFUR_E_INVALID_ARG, "bad tuning line: %s", ln.c_str());
+            if (!ok || cfg < 0 || cfg >= kNumConvCfgs) return fail(c, INFUR_E_INVALID_ARG, "bad tuning line: %s", ln.c_str());
             c->tuned[key] = cfg;
             c->mem_gen++;
         }

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "conv_forms.h"
+
 namespace infur {
 
 // NHWC activations (f32 or f16); weights OHWI ([Cout][KH][KW][Cin], K contiguous per output
@@ -64,30 +66,19 @@ struct ConvArgs {
     unsigned* hl_mon = nullptr;
 };
 
-// conv as implicit GEMM on the matrix cores.  mode 0: f32 operands on the f32 MFMA (Cin % 32 == 0);
-// mode 1: f16 operands, f32 accumulation (Cin % 64 == 0), output f16 or (out_f32) f32;
-// mode 2: f32 tensors, each value split into an f16 hi + lo pair while it is staged, three f16
-// MFMAs per product, f32 accumulation (Cin % 32 == 0) -- f32-grade results at f16 matrix rate / 3.
-// mode 3: as mode 2, but the two cross terms hi * lo run on the bf8 (OCP e5m2) MX MFMA: 2 MFMA units per product instead of
-// 3, products exact to ~2^-13 whatever the tensors' dynamic range (e5m2 has f16's exponent range: no scales; round 3 used
-// e4m3 under per-tensor scales, which heavy-tailed weights broke); weights prepared with launch_split_weights(fp8_cross = 1).
-// mode 4: quantised (ConvArgs::q_*): u8 NHWC activations, s8 OHWI weights (Cin % 128 == 0), output u8 or (out_f32) dequantised f32.
-// cfg: tile configuration index (conv_igemm_num_configs), -1 = built-in heuristic.  Every
-// configuration produces bit-identical results; only the speed differs.
-// mode 5: three-byte tensors (f16 hi + e5m2 lo planes, ConvArgs::*_lo), hi * hi on the f16 MFMA + both cross terms on the bf8 MX MFMA,
-// every operand staged by LDS-DMA (conv_hl.hip); Cin % 32 == 0; configurations 11, 0, 6, 5 (their tile shapes).
-hipError_t launch_conv_igemm(const ConvArgs& a, int mode, int out_f32, int cfg, hipStream_t s);
-int conv_igemm_num_configs();
-int conv_igemm_config_tile_area(int cfg);  // BM * BN of a configuration (operand re-reads fall with it)
-int conv_igemm_default_config(const ConvArgs& a);
-bool conv_igemm_config_valid(const ConvArgs& a, int cfg, int mode, int out_f32);
-const char* conv_igemm_config_name(int cfg, int mode);
+// conv as implicit GEMM on the matrix cores in one of the arithmetic modes of conv_forms.h (ConvMode; also ConvCfg and the table of forms).
+// cfg: a configuration that conv_igemm_config_valid admits for the launch (what pick_cfg returns).  Every configuration of a mode
+// produces bit-identical results; only the speed differs.
+hipError_t launch_conv_igemm(const ConvArgs& a, ConvMode mode, int out_f32, int cfg, hipStream_t s);
+ConvCfg conv_igemm_default_config(const ConvArgs& a);  // the configuration of a shape nobody has measured
+bool conv_igemm_config_valid(const ConvArgs& a, int cfg, ConvMode mode, int out_f32);
+const char* conv_igemm_config_name(int cfg, ConvMode mode);
 
 // mode 5 (conv_hl.hip)
-bool conv_hl_config_valid(const ConvArgs& a, int cfg, int out_f32);
+bool conv_hl_config_valid(const ConvArgs& a, const ConvForm& f, int out_f32);  // f: a kFamHL / kFamHLAreg row
 hipError_t launch_conv_hl(const ConvArgs& a, int out_f32, int cfg, hipStream_t s);
 bool conv_hl_pipe_on();  // false under INFUR_HL_PIPE=0 (the plain K loop): conv_igemm_config_name then ends the tiled forms' names in ",plain"
-// configuration 15 of mode 5 (conv_hl_areg.hip): 1x1 expansions (Cin 64 / 128 / 256, Cout a multiple of 128) with the activation
+// kCfgAreg of mode 5 (conv_hl_areg.hip): 1x1 expansions (Cin 64 / 128 / 256, Cout a multiple of 128) with the activation
 // fragment in registers, weights and residual streamed by LDS-DMA; bit-identical to the tiled forms
 bool conv_hl_areg_valid(const ConvArgs& a, int out_f32);
 hipError_t launch_conv_hl_areg(const ConvArgs& a, hipStream_t s);
@@ -100,18 +91,18 @@ hipError_t launch_hl_pack_weights_planes(const float* w, size_t rows, size_t col
 bool conv1x1_areg_valid(const ConvArgs& a, int mode, int out_f32);
 hipError_t launch_conv1x1_areg(const ConvArgs& a, hipStream_t s);
 // quantised models (mode 4, u8 output): activation tile in registers, 16 consecutive channels per lane straight from the
-// accumulators (conv1x1_q8.hip): configuration 15 in that mode
+// accumulators (conv1x1_q8.hip): kCfgAreg in that mode
 bool conv1x1_q8_valid(const ConvArgs& a, int mode, int out_f32);
 hipError_t launch_conv1x1_q8(const ConvArgs& a, int nsplit, hipStream_t s);
-int conv1x1_q8_nsplit(const ConvArgs& a);  // configuration 18: N tiles shared out over this many workgroups per M tile (0: not a candidate)
+int conv1x1_q8_nsplit(const ConvArgs& a);  // kCfgAregNsplit: N tiles shared out over this many workgroups per M tile (0: not a candidate)
 
 // stride-1 3x3 convolutions (pad = dilation 1 / 2 / 4), f16 operands and output, no residual: the input patch of a 16 x 16 output
-// tile stays in LDS for all nine taps (conv3x3_halo.hip).  Configurations 19 (bn = 128), 20 (bn = 256) and 21 (the 4-wave form) of mode 1.
+// tile stays in LDS for all nine taps (conv3x3_halo.hip).  kCfgHalo128, kCfgHalo256 and kCfgHalo4 (the 4-wave form) of kModeF16.
 bool conv3x3_halo_valid(const ConvArgs& a, int mode, int out_f32, int bn);
 hipError_t launch_conv3x3_halo(const ConvArgs& a, int bn, hipStream_t s);
-// the same kernel on the quantised model's tensors (mode 4, u8 out): configurations 19 / 20 of that mode
+// the same kernel on the quantised model's tensors (mode 4, u8 out): kCfgHalo128 / kCfgHalo256 of that mode
 hipError_t launch_conv3x3_halo_q(const ConvArgs& a, int bn, hipStream_t s);
-// the 4-wave form (configuration 21): BN = 256, one wave per SIMD with a 128 x 128 wave tile, dilation 1 / 2
+// the 4-wave form (kCfgHalo4): BN = 256, one wave per SIMD with a 128 x 128 wave tile, dilation 1 / 2
 bool conv3x3_halo4_valid(const ConvArgs& a, int mode, int out_f32);
 hipError_t launch_conv3x3_halo4(const ConvArgs& a, hipStream_t s);
 

@@ -36,7 +36,8 @@ PRE_FRAME[(97, 61)] = (135, 241)
 
 MODES = ("f32", "f32s", "f32x", "f16", "f16hl", "i8")
 
-# configuration index -> kernel name as conv_igemm_config_name reports it ({t} = the mode's tag); conv_igemm.hip: kCfgs
+# configuration index -> kernel name as conv_igemm_config_name reports it ({t} = the mode's tag); conv_forms.h: kConvForms,
+# held against this table by tests/test_conv_forms_cpu.py
 _TILED = {
     0: "conv_igemm_{t}<128,128>", 1: "conv_igemm_{t}<64,128>", 2: "conv_igemm_{t}<128,64>", 3: "conv_igemm_{t}<64,64>",
     4: "conv_igemm_{t}<256,32>", 5: "conv_igemm_{t}<128,256>", 6: "conv_igemm_{t}<256,128>", 7: "conv_igemm_{t}<128,128,1buf>",
@@ -59,8 +60,8 @@ def _tiled(tag, cfgs):
     return {k: _TILED[k].format(t=tag) for k in cfgs}
 
 
-# The configurations that are candidates for at least one layer of FCN-ResNet50 in each mode, read off conv_igemm_config_valid and
-# conv_hl_config_valid: the register-staged tiles 0-12 everywhere; the LDS-DMA forms 13, 14, 16, 17 for byte operands that need no
+# The configurations that are candidates for at least one layer of FCN-ResNet50 in each mode, read off conv_forms.h (ConvForm::modes)
+# and the families' predicates: the register-staged tiles 0-12 everywhere; the LDS-DMA forms 13, 14, 16, 17 for byte operands that need no
 # conversion (f16, i8); 15 = the 1x1 form with the activations in registers (f16, i8; 18 = its N-split, i8 only); 19 / 20 = the 3x3 form
 # with the input patch in LDS (f16, i8), 21 = its four-wave form (f16 only).
 FORMS = {

@@ -33,7 +33,6 @@ terms -- measures 1e-5 there, all thirteen forms give configuration 0's bytes, a
 min(2 x measured, north_star's 1e-3) = 1e-3; the other three keep 5e-4.
 """
 import os
-import re
 import sys
 import time
 
@@ -70,32 +69,7 @@ def rel_err(a, b):
     return float(np.abs(a.astype(np.float64) - b).max() / np.abs(b).max())
 
 
-# ---- what needs no GPU ------------------------------------------------------------------------------------------------------------
-def test_forms_table_matches_the_sources():
-    """every name of the table is a name the library can report (conv_igemm.hip: kCfgs and the mode-5 switch; the f32x and i8 names
-    are derived from the f32s ones there), the index sets are the ones conv_igemm_config_valid / conv_hl_config_valid admit"""
-    src = open(os.path.join(F.ROOT, "infur_amd", "csrc", "conv_igemm.hip")).read()
-    for mode in ("f32", "f16", "f32s", "f16hl"):
-        for cfg, name in F.FORMS[mode].items():
-            assert f'"{name}"' in src, (mode, cfg, name)
-            if mode == "f16hl" and cfg != F.HL_AREG:
-                assert f'"{name},plain"' in src, (cfg, name)
-    rows = re.findall(r'^\s*\{\d+, \d+, \{"([^"]+)", "([^"]+)", "([^"]+)"\}\},', src, re.M)
-    assert len(rows) == 22
-    for cfg, row in enumerate(rows):  # the table's ORDER is the configuration index
-        for mode, name in zip(("f32", "f16", "f32s"), row):
-            assert F.FORMS[mode].get(cfg, name) == name, (mode, cfg)
-        for mode in ("f32x", "i8"):  # conv_igemm_config_name: "...f32s<...>" -> "...f32x<...>" / "...i8<...>"
-            assert F.FORMS[mode].get(cfg, row[2].replace("f32s", mode)) == row[2].replace("f32s", mode), (mode, cfg)
-    assert sorted(F.FORMS["f32"]) == sorted(F.FORMS["f32s"]) == sorted(F.FORMS["f32x"]) == list(range(13))
-    assert sorted(F.FORMS["f16"]) == list(range(18)) + [19, 20, 21]
-    assert sorted(F.FORMS["f16hl"]) == [0, 5, 6, 11, 12, 13, 14, 15, 16, 17]
-    assert {15, 18, 19, 20} <= set(F.FORMS["i8"]) and 21 not in F.FORMS["i8"]
-    assert all(len(n) + len(",plain") < 32 for n in F.FORMS["f16hl"].values())  # infur_kernel_record::kernel is char[32]
-    n_hl = len(F.FORMS["f16hl"])
-    assert len(F.cases()) == sum(len(v) for v in F.FORMS.values()) + n_hl
-
-
+# ---- what needs no GPU (tests/forms.py against the library's own table: tests/test_conv_forms_cpu.py) -------------------------------
 def test_size_bars_stay_under_north_star():
     bars = mode_bars()
     assert set(bars) == set(F.MODES) - {"i8"}

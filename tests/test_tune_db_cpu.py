@@ -4,7 +4,7 @@ import os
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DB = os.path.join(ROOT, "infur_amd", "conv_tune_gfx950.txt")
-HL_FORMS = {0, 5, 6, 11, 12, 13, 14, 15, 16, 17}  # conv_hl.hip: conv_hl_config_valid (16, 17: round 6)
+HL_FORMS = {0, 5, 6, 11, 12, 13, 14, 15, 16, 17}  # conv_forms.h: the kFamHL / kFamHLAreg rows (16, 17: round 6); tests/test_conv_forms_cpu.py
 HL_BN = {0: 128, 6: 128, 12: 128, 17: 128, 5: 256, 11: 256, 13: 256, 14: 256, 16: 256}
 
 
