@@ -14,6 +14,11 @@ from infur_amd import weights as W
 from infur_amd.processors import Context, FramePath, InfurError, Model, ModelCmd
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HERE = os.path.dirname(os.path.abspath(__file__))
+if HERE not in sys.path:
+    sys.path.insert(0, HERE)
+from history import stem_gain_blob  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 HL_HI_MAX = 65520.0  # hl_format.h: kHlHiMax
@@ -22,12 +27,6 @@ HL_HI_MAX = 65520.0  # hl_format.h: kHlHiMax
 def bits(r):
     """an HlRange as comparable bit patterns"""
     return (int(np.float32(r.act_amax).view(np.uint32)), int(np.float32(r.wino_amax).view(np.uint32)), r.saturated, r.nan_seen)
-
-
-def stem_gain_blob(gain):
-    tensors = [(s, w * np.float32(gain), b * np.float32(gain)) if s.name == "backbone.conv1" else (s, w, b)
-               for s, w, b in W.synth_tensors(depth=50)]
-    return W.pack_blob(tensors, 50, W.NUM_CLASSES, True)
 
 
 def test_hl_monitor_mode_gating(blob50):
