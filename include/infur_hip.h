@@ -629,6 +629,89 @@ int32_t infur_frame_outlines_dev(infur_ctx* ctx, const void* d_bgr, uint32_t w, 
                                  uint32_t loops_rows, void* d_vertices, uint32_t vertex_rows, void* d_counts, void* d_stats,
                                  uint32_t stats_capacity, void* d_scaled_bgr, uint32_t* ow, uint32_t* oh);
 
+/* ---- Simplify: Outlines' loops with a tolerance (Douglas-Peucker) ----
+ * On a pixel lattice the boundary of a slanted region is a staircase: every step costs two vertices.  COCO `segmentation`, GeoJSON
+ * and a GUI that strokes an outline want the polygon within a tolerance, not the staircase.  Simplify takes what Outlines left in
+ * device memory and keeps, loop by loop, the vertices the Douglas-Peucker rule keeps, in the same three-array layout.  Presence of
+ * this group is announced by infur_features() & INFUR_FEATURE_SIMPLIFY (INFUR_ABI_VERSION does not move).
+ *
+ * INPUT.  Outlines' three outputs for a plane of width w: `loops` (records OFFSET, COUNT, VALUE, START), `vertices` (ids
+ * Y*(w+1) + X) and `counts` ({n_loops, n_vertices, ..}: the first two words are read), with loops_rows_in and vertex_rows_in, the
+ * rows the caller declares for the two arrays, and tol16, the tolerance in 1/16 pixel (the outer corners of a 45-degree staircase
+ * are 0.707 pixel off their chord: the interesting range lies between 8 and 16).  w must be in 1 .. 8191, h at most 8191 and
+ * tol16 at most 65535, otherwise the call returns INFUR_E_INVALID_ARG.  Then every coordinate difference is below 2^13 and every
+ * quantity below fits 64 bits: 256 * cross^2 < 2^62 and tol16^2 * L < 2^59.  (A vertex id whose Y exceeds 8191 -- no plane the
+ * call accepts has one -- is read as Y = 8191.)  A NULL counts, or a NULL array with rows declared, is INFUR_E_INVALID_ARG.
+ * THE RULE FOR ONE LOOP with vertices v_0 .. v_{n-1}; set v_n := v_0.
+ *   1 ANCHORS.  Vertex 0 is kept.  B is the index in 1 .. n-1 that maximises |v_i - v_0|^2, on ties the smallest; B is kept.
+ *   2 SPLIT(a, c), run for (0, B) and (B, n).  With c - a < 2 nothing happens.  Otherwise, for a < i < c,
+ *       cross_i = (x_c - x_a)(y_i - y_a) - (y_c - y_a)(x_i - x_a),   D_i = cross_i^2,   L = |v_c - v_a|^2.
+ *     When L = 0 (the segment's ends coincide), D_i = |v_i - v_a|^2 and L = 1.  m is the smallest i with maximal D_i.  If
+ *     256 * D_m > tol16^2 * L, then m is kept and SPLIT(a, m) and SPLIT(m, c) run.  (A loop may pass a saddle vertex twice, but
+ *     a kept m has D_m > 0 and so differs from both ends of its segment: L = 0 arises only when all of a loop's vertices are one
+ *     point, which no plane produces; the clause makes the rule total.)
+ *   3 OUTPUT.  The kept vertices come out in their original order, v_0 first; COUNT' >= 2.
+ * The kept set is a function of the loop alone and no segment's decision depends on the order in which segments are visited:
+ * identical bytes from run to run.  tol16 = 0 drops only vertices that lie on the chord of a segment whose other vertices all do.
+ * OUTPUTS, each optional (NULL = not wanted, and so are loops_out with loops_rows_out == 0 and vertices_out with vertex_rows_out
+ * == 0; nothing wanted is INFUR_E_INVALID_ARG), none needs initialisation; a rejected call touches no output:
+ *   loops_out     record i belongs to input loop i: (OFFSET', COUNT', VALUE, START) with VALUE and START copied.  Only the first
+ *                 min(n_loops, loops_rows_out) records are written.  OFFSET' is the number of kept vertices in front of the loop's
+ *                 OFFSET: for Outlines' records, which lie back to back, the full exclusive prefix sum of COUNT', whatever is
+ *                 truncated
+ *   vertices_out  the first min(n_vertices', vertex_rows_out) kept vertex ids, loops back to back
+ *   counts_out    INFUR_SIMPLIFY_COUNT_WORDS uint32_t {n_loops, n_vertices', n_degenerate, status}, always complete
+ * n_degenerate counts the loops with COUNT' < 3: a thin region collapsed to its two anchors.  Such a loop keeps its record, so that
+ * indices stay aligned with Outlines' loops; a consumer skips it.  This is not an error.
+ * STATUS.  INFUR_SIMPLIFY_TRUNCATED: the input was truncated, counts[0] > loops_rows_in or counts[1] > vertex_rows_in (Outlines
+ * was given fewer rows than it had loops or vertices).  Nothing but counts_out is written, as {counts[0], 0, 0, 1}.
+ * INFUR_SIMPLIFY_MALFORMED: some record had COUNT < 2 or OFFSET + COUNT > counts[1].  Such a loop gets COUNT' = 0 (and counts as
+ * degenerate) and keeps none of its vertices.  Every read is clamped to the rows the caller declared: no value held in the input
+ * buffers can take a load or a store outside them.  Records that overlap or leave gaps -- Outlines writes none -- are read
+ * safely: a vertex no record covers is dropped, a vertex two records cover is kept when either keeps it, COUNT' is the number of
+ * kept vertices in the record's range.
+ * COST.  A wave owns a loop and reads a segment once per level of the recursion below it, 64 vertices a step: O(n * depth / 64)
+ * steps for a loop of n vertices, O(n^2 / 64) when every split is lopsided.  The plane's longest loop bounds the call.
+ * WHAT IT DOES NOT DO.  It does not preserve topology: two regions that share a border are simplified independently, so their
+ * polygons may overlap or leave slivers, and a loop may touch or cross itself -- COCO polygons have the same property.  It does
+ * not convert to COCO JSON.  It has no sub-pixel contours.  It offers no Visvalingam simplification and no area-based criterion. */
+enum { INFUR_SIMPLIFY_LOOPS = 0, INFUR_SIMPLIFY_VERTICES = 1, INFUR_SIMPLIFY_DEGENERATE = 2, INFUR_SIMPLIFY_STATUS = 3, INFUR_SIMPLIFY_COUNT_WORDS = 4 };
+enum { INFUR_SIMPLIFY_TRUNCATED = 1, INFUR_SIMPLIFY_MALFORMED = 2 };
+enum { INFUR_FEATURE_SIMPLIFY = 32 };
+
+/* host pointers: counts is read first, min(counts[0], loops_rows_in) records and min(counts[1], vertex_rows_in) vertices travel to
+ * the device; then counts_out is read, and min(n_loops, loops_rows_out) records and min(n_vertices', vertex_rows_out) vertices are
+ * copied back */
+int32_t infur_simplify(infur_ctx* ctx, const uint32_t* loops, uint32_t loops_rows_in, const uint32_t* vertices,
+                       uint32_t vertex_rows_in, const uint32_t* counts, uint32_t h, uint32_t w, uint32_t tol16, uint32_t* loops_out,
+                       uint32_t loops_rows_out, uint32_t* vertices_out, uint32_t vertex_rows_out, uint32_t* counts_out);
+/* device pointers throughout, d_counts and d_counts_out (four device uint32_t) included; enqueued on the context's stream as one
+ * memset and at most 6 launches, a number fixed by the arguments: the call never synchronises, so its grids are sized by
+ * loops_rows_in and vertex_rows_in -- declare the rows Outlines was given, not more.  Capturable after one call outside the
+ * capture, which allocates the scratch: 5 bytes per vertex row (a keep flag and a rank) and the scan's sums, owned by the context.
+ * It grows only with a request larger than any before, and a graph captured around the call is re-captured after that.  The
+ * outputs must not overlap the inputs.  infur_frame_regions_dev, infur_outlines_dev on the label plane, then infur_simplify_dev
+ * gives per-object polygons with a tolerance and no dense plane crossing PCIe. */
+int32_t infur_simplify_dev(infur_ctx* ctx, const void* d_loops, uint32_t loops_rows_in, const void* d_vertices,
+                           uint32_t vertex_rows_in, const void* d_counts, uint32_t h, uint32_t w, uint32_t tol16, void* d_loops_out,
+                           uint32_t loops_rows_out, void* d_vertices_out, uint32_t vertex_rows_out, void* d_counts_out);
+/* The fused frame path with simplified polygons: scale -> model -> Segments decode(out[0]) -> Outlines of the class plane into
+ * scratch of the library's own -> Simplify into the caller's buffers, in one call.  The arguments are infur_frame_outlines' plus
+ * tol16, and counts is Simplify's four words.  The scaled frame must be at most 8191 x 8191 (INFUR_E_INVALID_ARG, before the model
+ * runs).  The scratch holds Outlines' worst case for max_edges: 8 bytes per edge of capacity beside Outlines' own 36 and
+ * Simplify's 5, so callers that know their scenes pass max_edges; a plane with more edges than that reads counts = {0, 0, 0, 0}
+ * (infur_frame_outlines tells the edge count).  The calls inherit infur_frame_outlines' checks and errors: with no model loaded
+ * the Scale stage still runs and the call returns INFUR_E_MODEL_NOT_LOADED.  They always enqueue eagerly and leave the graphs cached
+ * for infur_frame_advance_dev alone.  (The stream ring, batch and group calls produce RGBA only.) */
+int32_t infur_frame_polygons(infur_ctx* ctx, const uint8_t* bgr, uint32_t w, uint32_t h, float factor, uint32_t scale_mode,
+                             uint32_t decode, uint32_t flags, uint32_t skip_value, uint32_t max_edges, uint32_t tol16,
+                             uint32_t* loops, uint32_t loops_rows, uint32_t* vertices, uint32_t vertex_rows, uint32_t* counts,
+                             uint64_t* stats, uint32_t stats_capacity, uint8_t* scaled_bgr, uint32_t* ow, uint32_t* oh);
+int32_t infur_frame_polygons_dev(infur_ctx* ctx, const void* d_bgr, uint32_t w, uint32_t h, float factor, uint32_t scale_mode,
+                                 uint32_t decode, uint32_t flags, uint32_t skip_value, uint32_t max_edges, uint32_t tol16,
+                                 void* d_loops, uint32_t loops_rows, void* d_vertices, uint32_t vertex_rows, void* d_counts,
+                                 void* d_stats, uint32_t stats_capacity, void* d_scaled_bgr, uint32_t* ow, uint32_t* oh);
+
 /* ---- streaming (infur/src/main.rs:27-99,105): bounded queue, copies overlapped with compute ----
  * The reference back-pressures its producer with sync_channel(2) (main.rs:105); a stream
  * here is a ring of `depth` pinned + device slots.  submit() copies the caller's frame into a

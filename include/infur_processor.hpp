@@ -501,6 +501,66 @@ private:
     bool dirty_ = true;
 };
 
+/// What `Simplify` produces, in Outlines' layout: `loops` holds min(n_loops, loops_rows) records (OFFSET', COUNT', VALUE, START),
+/// `vertices` the first min(n_vertices, vertex_rows) kept vertex ids; n_degenerate counts the loops with COUNT' < 3 (skip them);
+/// status: INFUR_SIMPLIFY_TRUNCATED (the input was cut off: nothing was produced), INFUR_SIMPLIFY_MALFORMED.
+struct SimplifyOut {
+    uint32_t loops_rows = 1u << 16, vertex_rows = 1u << 20;
+    uint32_t width = 0, height = 0, n_loops = 0, n_vertices = 0, n_degenerate = 0, status = 0;
+    std::vector<uint32_t> loops, vertices;
+    uint32_t rows() const { return (status & INFUR_SIMPLIFY_TRUNCATED) ? 0 : (n_loops < loops_rows ? n_loops : loops_rows); }
+    uint32_t word(uint32_t loop, uint32_t w) const { return loops[(size_t)loop * INFUR_LOOP_WORDS + w]; }
+    bool is_hole(uint32_t loop) const { return (word(loop, INFUR_LOOP_START) & 3u) == 2u; }
+    bool is_degenerate(uint32_t loop) const { return word(loop, INFUR_LOOP_COUNT) < 3u; }
+    uint32_t x(uint32_t vertex) const { return vertices[vertex] % (width + 1); }
+    uint32_t y(uint32_t vertex) const { return vertices[vertex] / (width + 1); }
+};
+
+/// The stage behind Outlines: Douglas-Peucker on every loop within tol16 sixteenths of a pixel.  Integer results, identical from
+/// run to run; topology is not preserved.  Command = the tolerance; Input = an OutlinesOut, Output = SimplifyOut.
+class Simplify {
+public:
+    struct Cmd {
+        enum Kind { Tol16 } kind;
+        uint32_t value;
+    };
+    explicit Simplify(Context& c) : c_(c) {}
+    Status control(Cmd cmd) {
+        if (cmd.kind != Cmd::Tol16 || cmd.value > 65535) return INFUR_E_INVALID_ARG;
+        dirty_ = dirty_ || cmd.value != tol16_;
+        tol16_ = cmd.value;
+        return INFUR_OK;
+    }
+    bool is_dirty() const { return dirty_; }
+    Status advance(const OutlinesOut& in, SimplifyOut& out) {
+        dirty_ = false;
+        out.width = in.width;
+        out.height = in.height;
+        const uint32_t rows_in = (uint32_t)(in.loops.size() / INFUR_LOOP_WORDS), verts_in = (uint32_t)in.vertices.size();
+        const uint32_t lrows = out.loops_rows < rows_in ? out.loops_rows : rows_in, vrows = out.vertex_rows < verts_in ? out.vertex_rows : verts_in;
+        out.loops.assign((size_t)lrows * INFUR_LOOP_WORDS, 0);
+        out.vertices.assign(vrows, 0);
+        const uint32_t counts_in[2] = {in.n_loops, in.n_vertices};
+        uint32_t counts[INFUR_SIMPLIFY_COUNT_WORDS] = {0, 0, 0, 0};
+        const Status s = infur_simplify(c_.get(), rows_in ? in.loops.data() : nullptr, rows_in, verts_in ? in.vertices.data() : nullptr, verts_in, counts_in,
+                                        in.height, in.width, tol16_, lrows ? out.loops.data() : nullptr, lrows, vrows ? out.vertices.data() : nullptr, vrows,
+                                        counts);
+        out.n_loops = counts[INFUR_SIMPLIFY_LOOPS];
+        out.n_vertices = counts[INFUR_SIMPLIFY_VERTICES];
+        out.n_degenerate = counts[INFUR_SIMPLIFY_DEGENERATE];
+        out.status = counts[INFUR_SIMPLIFY_STATUS];
+        const uint32_t nl = (out.status & INFUR_SIMPLIFY_TRUNCATED) ? 0 : (out.n_loops < lrows ? out.n_loops : lrows);
+        out.loops.resize((size_t)nl * INFUR_LOOP_WORDS);
+        out.vertices.resize(out.n_vertices < vrows ? out.n_vertices : vrows);
+        return s;
+    }
+
+private:
+    Context& c_;
+    uint32_t tol16_ = 16;
+    bool dirty_ = true;
+};
+
 /// infur_group: n contexts (one per GPU) of one process -- RCCL weight broadcast + frame-batch sharding
 /// (BASELINE configs[3]).  The contexts must outlive the group.
 class Group {

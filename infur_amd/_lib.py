@@ -62,6 +62,10 @@ FEATURE_RUNS = 8
 OUTLINES_SKIP, OUTLINES_CONN8 = 1, 2
 LOOP_OFFSET, LOOP_COUNT, LOOP_VALUE, LOOP_START, LOOP_WORDS = 0, 1, 2, 3, 4
 FEATURE_OUTLINES = 16
+# Simplify (infur_simplify / infur_frame_polygons): the words of its counts, the status bits, the feature bit
+SIMPLIFY_LOOPS, SIMPLIFY_VERTICES, SIMPLIFY_DEGENERATE, SIMPLIFY_STATUS, SIMPLIFY_COUNT_WORDS = 0, 1, 2, 3, 4
+SIMPLIFY_TRUNCATED, SIMPLIFY_MALFORMED = 1, 2
+FEATURE_SIMPLIFY = 32
 
 
 class Options(C.Structure):
@@ -187,6 +191,12 @@ SIGNATURES = {
                                          _u32p, _u32p]),
     "infur_frame_outlines_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _u32,
                                              _vp, _u32p, _u32p]),
+    "infur_simplify": (C.c_int32, [_vp, _vp, _u32, _vp, _u32, _vp, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _vp]),
+    "infur_simplify_dev": (C.c_int32, [_vp, _vp, _u32, _vp, _u32, _vp, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _vp]),
+    "infur_frame_polygons": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _u32,
+                                         _vp, _u32p, _u32p]),
+    "infur_frame_polygons_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _vp,
+                                             _u32, _vp, _u32p, _u32p]),
     "infur_stream_create": (C.c_int32, [_vp, _u32, C.POINTER(_vp)]),
     "infur_stream_destroy": (None, [_vp]),
     "infur_stream_add_lane": (C.c_int32, [_vp, _vp]),

@@ -177,6 +177,9 @@ struct infur_ctx {
     // Outlines (infur_outlines.cpp): the edge state and scan sums, the class plane the frame calls decode into, and the
     // host-pointer calls' staging.  Private like the above.
     infur::Buf st_outl, st_outl_plane, st_outl_io;
+    // Simplify (infur_simplify.cpp): the keep flags, ranks and scan sums, the host-pointer calls' staging, and what Outlines leaves
+    // for Simplify inside the polygon frame calls.  Private like the above.
+    infur::Buf st_simp, st_simp_io, st_poly;
     // Tracks (infur_tracks.cpp): the live trackers of this context; infur_ctx_destroy releases their device memory and orphans them
     std::vector<infur_tracker*> trackers;
 

@@ -9,6 +9,7 @@
 //   infur_tracks.cpp        Tracks (region identities from frame to frame): the tracker object and its C entry points
 //   infur_runs.cpp          Runs (a class, label or track plane as run-length records): C entry points
 //   infur_outlines.cpp      Outlines (region boundaries of a class, label or track plane as polygon loops): C entry points
+//   infur_simplify.cpp      Simplify (Douglas-Peucker on Outlines' loops) and the polygon frame calls: C entry points
 // (conv_forms.h, the table of conv modes, configurations and forms, comes with kernels.h)
 // (wave_scan.h, the device code regions.hip, tracks.hip and runs.hip share, also holds kScanBlock, which sizes their block sums)
 // Everything here lives in namespace infur and is NOT part of the public ABI.

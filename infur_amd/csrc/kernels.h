@@ -323,4 +323,15 @@ hipError_t launch_outlines(const void* plane, int elem_bytes, unsigned H, unsign
                            void* scratch, unsigned* loops, unsigned loops_rows, unsigned* vertices, unsigned vertex_rows, unsigned* counts,
                            hipStream_t s);
 
+// Simplify (simplify.hip): Douglas-Peucker on the loops Outlines left in device memory -- loops_rows_in records, vertex_rows_in
+// vertex ids and counts[2] = {n_loops, n_vertices, ..} of a plane of width W in [1, 8191] -- with the tolerance tol16 / 16 pixels,
+// tol16 <= 65535.  Outputs, each optional: loops_rows_out records (OFFSET', COUNT', VALUE, START), vertex_rows_out vertex ids and
+// counts_out[4] = {n_loops, n_vertices', n_degenerate, status}.  scratch: simplify_scratch_bytes(loops_rows_in, vertex_rows_in)
+// bytes the launches own for the call.  Stream-ordered; one memset and at most 6 launches, no workgroup waits for another.  No
+// value held in the input buffers takes a load or a store outside the declared rows.
+size_t simplify_scratch_bytes(size_t loops_rows, size_t vertex_rows);
+hipError_t launch_simplify(const unsigned* loops, unsigned loops_rows_in, const unsigned* vertices, unsigned vertex_rows_in, const unsigned* counts,
+                           unsigned W, unsigned tol16, void* scratch, unsigned* loops_out, unsigned loops_rows_out, unsigned* vertices_out,
+                           unsigned vertex_rows_out, unsigned* counts_out, hipStream_t s);
+
 }  // namespace infur

@@ -1010,6 +1010,100 @@ def outlines_by_value(loops: np.ndarray, vertices: np.ndarray, w: int) -> dict:
     return out
 
 
+@dataclass
+class SimplifyCmd:
+    """``Simplify``' command: ``Tolerance(px)`` sets the tolerance in pixels, rounded to sixteenths (``tol16``); ``Tol16(n)`` sets
+    the sixteenths themselves."""
+
+    tol16: int = 0
+
+    @staticmethod
+    def Tolerance(px: float) -> "SimplifyCmd":
+        return SimplifyCmd(tol16=tolerance_to_tol16(px))
+
+    @staticmethod
+    def Tol16(n: int) -> "SimplifyCmd":
+        return SimplifyCmd(tol16=int(n))
+
+
+def tolerance_to_tol16(px: float) -> int:
+    """a tolerance in pixels -> sixteenths of a pixel, rounded to nearest (half up); what ``segments_cli --outlines-tolerance`` does"""
+    t = int(np.floor(float(px) * 16.0 + 0.5))
+    if not 0 <= t <= 65535:
+        raise InfurError(_lib.E_INVALID_ARG, f"tolerance {px} px: 0 to 4095.9")
+    return t
+
+
+class SimplifyOut:
+    """``Simplify``' ``&mut Output``: what to produce (``loops_rows`` records and ``vertex_rows`` vertices at most) and, after
+    ``advance``, the results in Outlines' layout -- ``loops`` [min(n_loops, loops_rows), 4] u32 with OFFSET' and COUNT', ``vertices``
+    [min(n_vertices, vertex_rows)] u32 -- and the counts ``n_loops``, ``n_vertices``, ``n_degenerate`` (loops with COUNT' < 3: skip
+    them) and ``status`` (``_lib.SIMPLIFY_TRUNCATED``: the input was cut off and nothing was produced; ``SIMPLIFY_MALFORMED``)."""
+
+    def __init__(self, loops_rows: int = 1 << 16, vertex_rows: int = 1 << 20):
+        self.loops_rows, self.vertex_rows = loops_rows, vertex_rows
+        self.loops = self.vertices = None
+        self.n_loops = self.n_vertices = self.n_degenerate = self.status = 0
+
+
+class Simplify(Processor):
+    """The stage behind Outlines: Douglas-Peucker on every loop, within ``tol16`` sixteenths of a pixel.
+
+    Command = ``SimplifyCmd``.  Input = ``(loops, vertices, counts, (h, w))`` as ``Outlines`` left them (an ``OutlinesOut`` plus the
+    plane's shape: ``Simplify.input_of(out, shape)``); Output = ``SimplifyOut``.  ``outlines_polygons`` and ``outlines_by_value``
+    read the result as they read Outlines'.  Integers throughout, identical from run to run; topology is not preserved.
+    """
+
+    def __init__(self, ctx: Context, tol16: int = 16):
+        self.ctx = ctx
+        self.tol16 = tol16
+        self.dirty = True
+
+    @staticmethod
+    def input_of(out: "OutlinesOut", shape: tuple) -> tuple:
+        return out.loops, out.vertices, (out.n_loops, out.n_vertices), shape
+
+    def control(self, cmd: SimplifyCmd) -> "Simplify":
+        if not 0 <= cmd.tol16 <= 65535:
+            raise InfurError(_lib.E_INVALID_ARG, f"tol16 {cmd.tol16}: 0 to 65535")
+        self.dirty = self.dirty or cmd.tol16 != self.tol16
+        self.tol16 = cmd.tol16
+        return self
+
+    def is_dirty(self) -> bool:
+        return self.dirty
+
+    def advance(self, inp: tuple, out: SimplifyOut) -> None:
+        self.dirty = False
+        loops, vertices, counts, (h, w) = inp
+        loops = np.ascontiguousarray(loops if loops is not None else np.zeros((0, _lib.LOOP_WORDS)), np.uint32).reshape(-1, _lib.LOOP_WORDS)
+        vertices = np.ascontiguousarray(vertices if vertices is not None else np.zeros(0), np.uint32).reshape(-1)
+        cin = np.array([int(counts[0]), int(counts[1])], np.uint32)
+        lrows, vrows = max(0, min(int(out.loops_rows), len(loops))), max(0, min(int(out.vertex_rows), len(vertices)))
+        lo = np.empty((lrows, _lib.LOOP_WORDS), np.uint32) if lrows else None
+        vo = np.empty(vrows, np.uint32) if vrows else None
+        cout = np.zeros(_lib.SIMPLIFY_COUNT_WORDS, np.uint32)
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        self.ctx.check(self.ctx.L.infur_simplify(self.ctx.h, ptr(loops), len(loops), ptr(vertices), len(vertices), cin.ctypes.data, h, w, self.tol16,
+                                                 ptr(lo), lrows, ptr(vo), vrows, cout.ctypes.data))
+        out.n_loops, out.n_vertices, out.n_degenerate, out.status = (int(v) for v in cout)
+        cut = bool(out.status & _lib.SIMPLIFY_TRUNCATED)
+        out.loops = lo[:0 if cut else min(out.n_loops, lrows)] if lo is not None else None
+        out.vertices = vo[:min(out.n_vertices, vrows)] if vo is not None else None
+
+
+class PolygonsFrame(NamedTuple):
+    """``FramePath.advance_polygons``: ``OutlinesFrame`` with simplified loops, and the counts (n_loops, n_vertices, n_degenerate,
+    status)"""
+
+    loops: Optional[np.ndarray]
+    vertices: Optional[np.ndarray]
+    counts: Optional[tuple]
+    stats: Optional[np.ndarray]
+    scaled: Optional[np.ndarray]
+    shape: tuple
+
+
 def pack_normalize(ctx: Context, img: np.ndarray) -> np.ndarray:
     """The pre-proc stage on its own (predict_onnx.rs:103-137): BGR u8 HWC -> RGB f32 CHW."""
     img = _check_bgr(img)
@@ -1227,6 +1321,43 @@ class FramePath:
         nl, nv, ne = (int(v) for v in counts)
         return OutlinesFrame(loops[:min(nl, lrows)] if loops is not None else None, vertices[:min(nv, vrows)] if vertices is not None else None,
                              (nl, nv, ne), stats, scaled, (oh.value, ow.value))
+
+    def advance_polygons(self, img: np.ndarray, factor: float = 1.0, decode: int = _lib.DECODE_RAW, tol16: int = 16, skip: Optional[int] = None,
+                         connectivity: int = 4, max_edges: int = 0, loops_rows: int = 1 << 16, vertex_rows: int = 1 << 20,
+                         want_stats: bool = True, want_scaled: bool = False) -> PolygonsFrame:
+        """The fused path with simplified polygons, scale -> model -> Segments decode -> Outlines -> Simplify within ``tol16``
+        sixteenths of a pixel, in one call -> ``PolygonsFrame``.  Every result field is None when no model is loaded (``scaled`` is
+        still produced)."""
+        img = _check_bgr(img)
+        h, w = img.shape[:2]
+        L = self.ctx.L
+        f = float(np.float32(factor))
+        rc = L.infur_scale_validate(f)
+        if rc:
+            raise ValidScaleError(rc)
+        ow, oh = C.c_uint32(0), C.c_uint32(0)
+        rc = L.infur_scale_out_dims(w, h, f, C.byref(ow), C.byref(oh))
+        if rc:
+            raise ScaleProcError(rc)
+        mi = _lib.ModelInfoC()
+        k = mi.num_classes if L.infur_model_info_get(self.ctx.h, C.byref(mi)) == _lib.OK else 0
+        npix = oh.value * ow.value
+        lrows, vrows = max(0, min(int(loops_rows), npix)), max(0, min(int(vertex_rows), 4 * npix))
+        loops = np.empty((lrows, _lib.LOOP_WORDS), np.uint32) if lrows else None
+        vertices = np.empty(vrows, np.uint32) if vrows else None
+        counts = np.zeros(_lib.SIMPLIFY_COUNT_WORDS, np.uint32)
+        stats = np.zeros((k, _lib.STAT_WORDS), np.uint64) if want_stats else None
+        scaled = np.empty((oh.value, ow.value, 3), np.uint8) if want_scaled else None
+        ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
+        rc = L.infur_frame_polygons(self.ctx.h, img.ctypes.data, w, h, f, self.scale_mode, decode, _outlines_flags(skip, connectivity), skip or 0,
+                                    max_edges, tol16, ptr(loops), lrows, ptr(vertices), vrows, counts.ctypes.data, ptr(stats), k, ptr(scaled),
+                                    C.byref(ow), C.byref(oh))
+        if rc == _lib.E_MODEL_NOT_LOADED:
+            return PolygonsFrame(None, None, None, None, scaled, (oh.value, ow.value))
+        self.ctx.check(rc)
+        nl, nv = int(counts[0]), int(counts[1])
+        return PolygonsFrame(loops[:min(nl, lrows)] if loops is not None else None, vertices[:min(nv, vrows)] if vertices is not None else None,
+                             tuple(int(v) for v in counts), stats, scaled, (oh.value, ow.value))
 
     def advance_batch(self, imgs, factor: float = 1.0, outs=None):
         """A batch of independent frames (BASELINE configs[3]) -> list of masks, in order.  ``outs``: caller-owned mask arrays to fill

@@ -38,7 +38,10 @@ VALUE, START edge id; START & 3 == 2 marks the boundary of a hole), then n_verti
 gains ``"n_loops"``.  With ``--regions`` the label plane is outlined where Regions left it on the device (one polygon with its
 holes per object), otherwise the class plane; ``--outlines-skip VALUE`` takes the pixels of that value out (0: the background
 class; 4294967295: pixels of no region); ``--connectivity`` is the saddle rule.  With the class plane and no other plane or
-records asked for the frame goes through ``infur_frame_outlines``.
+records asked for the frame goes through ``infur_frame_outlines``.  ``--outlines-tolerance PX`` (with ``--outlines-out``)
+simplifies every loop on the device within PX pixels (Douglas-Peucker; PX is rounded to sixteenths of a pixel): the file then holds
+the simplified arrays in the same per-frame layout, its three counts being n_loops, the simplified n_vertices and the number of
+degenerate loops (COUNT below 3: a thin region collapsed to two points; skip them), and every line gains ``"n_degenerate"``.
 """
 from __future__ import annotations
 
@@ -77,6 +80,7 @@ def main(argv=None) -> int:
     ap.add_argument("--runs-skip", type=int, default=None, help="leave out the runs of this value")
     ap.add_argument("--outlines-out", default="", help="polygon loops: per frame 3 u32 counts, then n_loops x 4 u32, then n_vertices u32")
     ap.add_argument("--outlines-skip", type=int, default=None, help="pixels of this value belong to no outlined region")
+    ap.add_argument("--outlines-tolerance", type=float, default=None, help="simplify the loops within this many pixels (needs --outlines-out)")
     a = ap.parse_args(argv)
     if a.tracks_out and not a.tracks:
         ap.error("--tracks-out needs --tracks")
@@ -94,12 +98,19 @@ def main(argv=None) -> int:
     if a.outlines_skip is not None and not 0 <= a.outlines_skip <= (0xFFFFFFFF if a.regions else 255):
         ap.error("--outlines-skip: a value of the plane (a byte for the class plane, a u32 for the label plane)")
 
+    if a.outlines_tolerance is not None and not a.outlines_out:
+        ap.error("--outlines-tolerance needs --outlines-out")
+    if a.outlines_tolerance is not None and not 0 <= a.outlines_tolerance * 16 + 0.5 < 65536:
+        ap.error("--outlines-tolerance: 0 to 4095.9 pixels")
+
     import numpy as np
 
     from . import _lib
     from .app import RawVideoSource, VideoProcError
-    from .processors import (Context, FramePath, Model, ModelCmd, Outlines, OutlinesOut, Runs, RunsOut, SegmentsFrame, class_summary,
-                             region_summary, track_summary)
+    from .processors import (Context, FramePath, Model, ModelCmd, Outlines, OutlinesOut, Runs, RunsOut, SegmentsFrame, Simplify, SimplifyOut,
+                             class_summary, region_summary, tolerance_to_tol16, track_summary)
+
+    tol16 = tolerance_to_tol16(a.outlines_tolerance) if a.outlines_tolerance is not None else None
 
     ctx = Context(device=a.device, dtype=a.dtype)
     model = Model(ctx)
@@ -128,7 +139,7 @@ def main(argv=None) -> int:
     if a.regions:
         oh, ow = _out_dims(ctx, a.width, a.height, a.scale)
         rpath = _RegionsPath(ctx, a.width, a.height, ow, oh, a.scale, fp.scale_mode, model.get_info().num_classes, max(0, a.max_regions),
-                             tracks=a.tracks, runs=fruns is not None, outlines=foutl is not None)
+                             tracks=a.tracks, runs=fruns is not None, outlines=foutl is not None, simplify=tol16 is not None)
         flags = _lib.REGIONS_SKIP_BACKGROUND if a.skip_background else 0
     n, t0 = 0, time.perf_counter()
     while True:
@@ -146,10 +157,14 @@ def main(argv=None) -> int:
             if fruns is not None:
                 runs, nruns = rpath.runs(a.runs_plane, a.runs_skip)
             if foutl is not None:
-                outl = rpath.outlines(a.outlines_skip, a.connectivity)
+                outl = rpath.outlines(a.outlines_skip, a.connectivity, tol16)
         elif foutl is not None and fruns is None and flab is None and fconf is None:  # polygons, counts and captions: no dense plane
-            r = fp.advance_outlines(img, a.scale, decode, skip=a.outlines_skip, connectivity=a.connectivity, loops_rows=1 << 32, vertex_rows=1 << 32)
-            s, outl = SegmentsFrame(None, None, r.stats, None, None), (np.array(r.counts, np.uint32), r.loops, r.vertices)
+            if tol16 is None:
+                r = fp.advance_outlines(img, a.scale, decode, skip=a.outlines_skip, connectivity=a.connectivity, loops_rows=1 << 32, vertex_rows=1 << 32)
+            else:
+                r = fp.advance_polygons(img, a.scale, decode, tol16, skip=a.outlines_skip, connectivity=a.connectivity, loops_rows=1 << 32,
+                                        vertex_rows=1 << 32)
+            s, outl = SegmentsFrame(None, None, r.stats, None, None), (np.array(r.counts[:3], np.uint32), r.loops, r.vertices)
         elif fruns is not None and flab is None and fconf is None and foutl is None:  # records, count and captions: no dense plane comes back
             r = fp.advance_runs(img, a.scale, decode, skip=a.runs_skip, runs_rows=1 << 32, want_row_start=False)
             s, runs, nruns = SegmentsFrame(None, None, r.stats, None, None), r.runs, r.n
@@ -159,6 +174,10 @@ def main(argv=None) -> int:
                 oo = OutlinesOut(loops_rows=1 << 32, vertex_rows=1 << 32)
                 Outlines(ctx, skip=a.outlines_skip, connectivity=a.connectivity).advance(s.klass, oo)
                 outl = (np.array([oo.n_loops, oo.n_vertices, oo.n_edges], np.uint32), oo.loops, oo.vertices)
+                if tol16 is not None:
+                    so = SimplifyOut(loops_rows=1 << 32, vertex_rows=1 << 32)
+                    Simplify(ctx, tol16).advance(Simplify.input_of(oo, s.klass.shape), so)
+                    outl = (np.array([so.n_loops, so.n_vertices, so.n_degenerate], np.uint32), so.loops, so.vertices)
             if fruns is not None:  # the class plane is on the host anyway
                 ro = RunsOut(runs_rows=1 << 32, want_row_start=False)
                 Runs(ctx, skip=a.runs_skip).advance(s.klass, ro)
@@ -187,6 +206,8 @@ def main(argv=None) -> int:
             fruns.write(memoryview(runs).cast("B"))
         if foutl is not None:
             rec["n_loops"] = int(outl[0][0])
+            if tol16 is not None:
+                rec["n_degenerate"] = int(outl[0][2])
             for part in outl:
                 foutl.write(memoryview(np.ascontiguousarray(part)).cast("B"))
         fst.write(json.dumps(rec) + "\n")
@@ -207,7 +228,7 @@ class _RegionsPath:
     writes class plane, confidence plane and per-class table into device buffers, infur_regions_dev labels those planes where
     they are; the tables, the count and the planes that are written out are all that is copied back."""
 
-    def __init__(self, ctx, w, h, ow, oh, factor, scale_mode, classes, rows, tracks=False, runs=False, outlines=False):
+    def __init__(self, ctx, w, h, ow, oh, factor, scale_mode, classes, rows, tracks=False, runs=False, outlines=False, simplify=False):
         import ctypes as C
 
         self.ctx, self.w, self.h, self.ow, self.oh, self.factor, self.mode = ctx, w, h, ow, oh, float(factor), scale_mode
@@ -217,7 +238,8 @@ class _RegionsPath:
                         ("table", self.rows * _ROW_BYTES), ("n", 4)) + \
                 ((("ttab", self.rows * _TRACK_BYTES), ("tplane", ow * oh * 4), ("tsum", 16)) if tracks else ()) + \
                 ((("runs", ow * oh * _RUN_BYTES), ("nruns", 4)) if runs else ()) + \
-                ((("loops", ow * oh * _LOOP_BYTES), ("vertices", ow * oh * 16), ("ocounts", 12)) if outlines else ()):
+                ((("loops", ow * oh * _LOOP_BYTES), ("vertices", ow * oh * 16), ("ocounts", 12)) if outlines else ()) + \
+                ((("sloops", ow * oh * _LOOP_BYTES), ("svertices", ow * oh * 16), ("scounts", 16)) if outlines and simplify else ()):
             p = C.c_void_p(None)
             ctx.check(ctx.L.infur_dev_alloc(ctx.h, max(n, 4), C.byref(p)))
             self.d[name] = p
@@ -280,14 +302,20 @@ class _RegionsPath:
         n = int(self._read("nruns", (1,), np.uint32)[0])
         return self._read("runs", (n, _RUN_BYTES // 4), np.uint32), n
 
-    def outlines(self, skip, connectivity):
+    def outlines(self, skip, connectivity, tol16=None):
         """infur_outlines_dev on the label plane `advance` left on the device -> (counts [3], loops [n_loops, 4], vertices
-        [n_vertices]) u32: every object's polygon, no dense plane"""
+        [n_vertices]) u32: every object's polygon, no dense plane.  tol16: infur_simplify_dev behind it, on the device too; the
+        counts are then n_loops, the simplified n_vertices, n_degenerate"""
         import numpy as np
 
         c, d = self.ctx, self.d
         c.check(c.L.infur_outlines_dev(c.h, d["labels"], 4, self.oh, self.ow, (1 if skip is not None else 0) | (2 if connectivity == 8 else 0), skip or 0,
                                        0, d["loops"], self.ow * self.oh, d["vertices"], 4 * self.ow * self.oh, d["ocounts"]))
+        if tol16 is not None:
+            c.check(c.L.infur_simplify_dev(c.h, d["loops"], self.ow * self.oh, d["vertices"], 4 * self.ow * self.oh, d["ocounts"], self.oh, self.ow, tol16,
+                                           d["sloops"], self.ow * self.oh, d["svertices"], 4 * self.ow * self.oh, d["scounts"]))
+            counts = self._read("scounts", (4,), np.uint32)[:3]
+            return counts, self._read("sloops", (int(counts[0]), _LOOP_BYTES // 4), np.uint32), self._read("svertices", (int(counts[1]),), np.uint32)
         counts = self._read("ocounts", (3,), np.uint32)
         return counts, self._read("loops", (int(counts[0]), _LOOP_BYTES // 4), np.uint32), self._read("vertices", (int(counts[1]),), np.uint32)
 

@@ -147,6 +147,16 @@ pub const INFUR_LOOP_START: u32 = 3;
 pub const INFUR_LOOP_WORDS: u32 = 4;
 /// bit of `infur_features()`: the Outlines calls below exist
 pub const INFUR_FEATURE_OUTLINES: u32 = 16;
+/// Simplify: the words of its counts (`INFUR_SIMPLIFY_COUNT_WORDS` u32), the status bits
+pub const INFUR_SIMPLIFY_LOOPS: u32 = 0;
+pub const INFUR_SIMPLIFY_VERTICES: u32 = 1;
+pub const INFUR_SIMPLIFY_DEGENERATE: u32 = 2;
+pub const INFUR_SIMPLIFY_STATUS: u32 = 3;
+pub const INFUR_SIMPLIFY_COUNT_WORDS: u32 = 4;
+pub const INFUR_SIMPLIFY_TRUNCATED: u32 = 1;
+pub const INFUR_SIMPLIFY_MALFORMED: u32 = 2;
+/// bit of `infur_features()`: the Simplify calls below exist
+pub const INFUR_FEATURE_SIMPLIFY: u32 = 32;
 
 extern "C" {
     pub fn infur_abi_version() -> u32;
@@ -336,6 +346,23 @@ extern "C" {
                                 ow: *mut u32, oh: *mut u32) -> i32;
     pub fn infur_frame_outlines_dev(c: *mut infur_ctx, d_bgr: *const c_void, w: u32, h: u32, factor: f32, scale_mode: u32,
                                     decode: u32, flags: u32, skip_value: u32, max_edges: u32, d_loops: *mut c_void,
+                                    loops_rows: u32, d_vertices: *mut c_void, vertex_rows: u32, d_counts: *mut c_void,
+                                    d_stats: *mut c_void, stats_capacity: u32, d_scaled_bgr: *mut c_void, ow: *mut u32,
+                                    oh: *mut u32) -> i32;
+    // Simplify: Douglas-Peucker on Outlines' loops, and the frame path that ends in it
+    pub fn infur_simplify(c: *mut infur_ctx, loops: *const u32, loops_rows_in: u32, vertices: *const u32, vertex_rows_in: u32,
+                          counts: *const u32, h: u32, w: u32, tol16: u32, loops_out: *mut u32, loops_rows_out: u32,
+                          vertices_out: *mut u32, vertex_rows_out: u32, counts_out: *mut u32) -> i32;
+    pub fn infur_simplify_dev(c: *mut infur_ctx, d_loops: *const c_void, loops_rows_in: u32, d_vertices: *const c_void,
+                              vertex_rows_in: u32, d_counts: *const c_void, h: u32, w: u32, tol16: u32, d_loops_out: *mut c_void,
+                              loops_rows_out: u32, d_vertices_out: *mut c_void, vertex_rows_out: u32,
+                              d_counts_out: *mut c_void) -> i32;
+    pub fn infur_frame_polygons(c: *mut infur_ctx, bgr: *const u8, w: u32, h: u32, factor: f32, scale_mode: u32, decode: u32,
+                                flags: u32, skip_value: u32, max_edges: u32, tol16: u32, loops: *mut u32, loops_rows: u32,
+                                vertices: *mut u32, vertex_rows: u32, counts: *mut u32, stats: *mut u64, stats_capacity: u32,
+                                scaled_bgr: *mut u8, ow: *mut u32, oh: *mut u32) -> i32;
+    pub fn infur_frame_polygons_dev(c: *mut infur_ctx, d_bgr: *const c_void, w: u32, h: u32, factor: f32, scale_mode: u32,
+                                    decode: u32, flags: u32, skip_value: u32, max_edges: u32, tol16: u32, d_loops: *mut c_void,
                                     loops_rows: u32, d_vertices: *mut c_void, vertex_rows: u32, d_counts: *mut c_void,
                                     d_stats: *mut c_void, stats_capacity: u32, d_scaled_bgr: *mut c_void, ow: *mut u32,
                                     oh: *mut u32) -> i32;

@@ -685,6 +685,80 @@ impl Processor for HipOutlines {
     }
 }
 
+// ---------------------------------------------------------------- Simplify (Outlines' loops within a tolerance)
+/// What `HipSimplify` produces, in `Outlines`' layout: `loops` holds `min(n_loops, loops_rows)` records (OFFSET', COUNT', VALUE,
+/// START), `vertices` the first `min(n_vertices, vertex_rows)` kept vertex ids; `n_degenerate` counts the loops with COUNT' < 3
+/// (skip them); `status`: `INFUR_SIMPLIFY_TRUNCATED` (the input was cut off: nothing was produced), `INFUR_SIMPLIFY_MALFORMED`.
+pub struct Simplified { pub loops_rows: usize, pub vertex_rows: usize, pub n_loops: u32, pub n_vertices: u32, pub n_degenerate: u32,
+                        pub status: u32, pub loops: Vec<u32>, pub vertices: Vec<u32> }
+impl Default for Simplified {
+    fn default() -> Self {
+        Self { loops_rows: 1 << 16, vertex_rows: 1 << 20, n_loops: 0, n_vertices: 0, n_degenerate: 0, status: 0, loops: Vec::new(),
+               vertices: Vec::new() }
+    }
+}
+impl Simplified {
+    pub fn rows(&self) -> usize {
+        if self.status & sys::INFUR_SIMPLIFY_TRUNCATED != 0 { 0 } else { (self.n_loops as usize).min(self.loops_rows) }
+    }
+    pub fn word(&self, l: usize, word: u32) -> u32 { self.loops[l * sys::INFUR_LOOP_WORDS as usize + word as usize] }
+    /// a thin region that collapsed to its two anchors: no polygon
+    pub fn is_degenerate(&self, l: usize) -> bool { self.word(l, sys::INFUR_LOOP_COUNT) < 3 }
+}
+/// `Outlines` as `HipOutlines` left them, and the plane's `[width, height]`
+pub struct SimplifyInput { pub outlines: Outlines, pub size: [usize; 2] }
+pub enum SimplifyCmd { Tol16(u32) }
+/// Douglas-Peucker on every loop within `tol16` sixteenths of a pixel.  Integer results, identical from run to run; topology is
+/// not preserved.
+pub struct HipSimplify { ctx: Rc<Ctx>, tol16: u32, dirty: bool }
+impl HipSimplify {
+    pub fn new(ctx: Rc<Ctx>) -> Self { Self { ctx, tol16: 16, dirty: true } }
+}
+impl Processor for HipSimplify {
+    type Command = SimplifyCmd;
+    type ControlError = HipError;
+    type Input = SimplifyInput;
+    type Output = Simplified;
+    type ProcessResult = Result<(), HipError>;
+
+    fn control(&mut self, cmd: SimplifyCmd) -> Result<&mut Self, HipError> {
+        let SimplifyCmd::Tol16(t) = cmd;
+        if t > 65535 { return Err(HipError::status(sys::INFUR_E_INVALID_ARG)); }
+        self.dirty |= t != self.tol16;
+        self.tol16 = t;
+        Ok(self)
+    }
+    fn is_dirty(&self) -> bool { self.dirty }
+    fn advance(&mut self, inp: &SimplifyInput, out: &mut Simplified) -> Result<(), HipError> {
+        self.dirty = false;
+        let [w, h] = inp.size;
+        let o = &inp.outlines;
+        let rows_in = o.loops.len() / sys::INFUR_LOOP_WORDS as usize;
+        let lrows = out.loops_rows.min(rows_in);
+        let vrows = out.vertex_rows.min(o.vertices.len());
+        out.loops.resize(lrows * sys::INFUR_LOOP_WORDS as usize, 0);
+        out.vertices.resize(vrows, 0);
+        let counts_in = [o.n_loops, o.n_vertices];
+        let mut counts = [0u32; 4];
+        let rc = unsafe {
+            sys::infur_simplify(self.ctx.0, if rows_in > 0 { o.loops.as_ptr() } else { std::ptr::null() }, rows_in as u32,
+                                if !o.vertices.is_empty() { o.vertices.as_ptr() } else { std::ptr::null() }, o.vertices.len() as u32,
+                                counts_in.as_ptr(), h as u32, w as u32, self.tol16,
+                                if lrows > 0 { out.loops.as_mut_ptr() } else { std::ptr::null_mut() }, lrows as u32,
+                                if vrows > 0 { out.vertices.as_mut_ptr() } else { std::ptr::null_mut() }, vrows as u32, counts.as_mut_ptr())
+        };
+        if rc != sys::INFUR_OK { return Err(HipError::from_ctx(&self.ctx, rc)); }
+        out.n_loops = counts[0];
+        out.n_vertices = counts[1];
+        out.n_degenerate = counts[2];
+        out.status = counts[3];
+        let nl = if out.status & sys::INFUR_SIMPLIFY_TRUNCATED != 0 { 0 } else { (out.n_loops as usize).min(lrows) };
+        out.loops.truncate(nl * sys::INFUR_LOOP_WORDS as usize);
+        out.vertices.truncate((out.n_vertices as usize).min(vrows));
+        Ok(())
+    }
+}
+
 // ---------------------------------------------------------------- streaming ring with zero-copy slots (main.rs:27-99,105; ABI 5)
 /// The bounded queue of frames in flight (`sync_channel(2)`, main.rs:105) over `infur_stream_*`.  `next_slot` / `commit` let the
 /// decoder fill the ring's own pinned buffer in place -- what `ff-video/src/decoder.rs:156-165` does with its reused `BgrImage` --
