@@ -712,6 +712,96 @@ int32_t infur_frame_polygons_dev(infur_ctx* ctx, const void* d_bgr, uint32_t w, 
                                  void* d_loops, uint32_t loops_rows, void* d_vertices, uint32_t vertex_rows, void* d_counts,
                                  void* d_stats, uint32_t stats_capacity, void* d_scaled_bgr, uint32_t* ow, uint32_t* oh);
 
+/* ---- Coverage: shared borders simplified once, so that neighbouring polygons fit ----
+ * Simplify treats every loop on its own: two regions that share a border get two different chords for it, and the polygons of
+ * one frame overlap and leave slivers.  GeoJSON coverages, panoptic exports and stroked overlays want neighbours that fit.  GIS
+ * libraries call the operation coverage simplification.  Coverage takes the plane Outlines was given and what Outlines left,
+ * cuts every loop at the plane's junctions into arcs, and simplifies each arc by a rule that does not depend on the direction of
+ * travel: both neighbours of a border keep the same vertices.  Presence of this group is announced by infur_features() &
+ * INFUR_FEATURE_COVERAGE (INFUR_ABI_VERSION does not move).
+ *
+ * INPUT.  The plane Outlines was given (elem_bytes 1 or 4, h and w both in 1 .. 8191), Outlines' three outputs for it with
+ * loops_rows_in and vertex_rows_in (counts[0..1] are read), flags (INFUR_COVERAGE_SKIP with skip_value: what Outlines got;
+ * unknown bits, and skip_value > 255 on bytes, are INFUR_E_INVALID_ARG), tol16 <= 65535 in 1/16 pixel, and aug_rows (SCRATCH
+ * below).  Connectivity is not an input: junctions are a property of the plane, and the kept set is the same under either
+ * connectivity although the loops differ.  A NULL plane or counts, or a NULL array with rows declared, is INFUR_E_INVALID_ARG.
+ * CELLS AND RAYS.  A cell outside the plane, or (under SKIP) equal to skip_value, is NONE: one value, distinct from every plane
+ * value, 0xFFFFFFFF included.  Lattice vertex (X, Y) has the cells UL = (X-1, Y-1), UR = (X, Y-1), LL = (X-1, Y), LR = (X, Y) and
+ * four rays: N is a border when UL != UR, S when LL != LR, W when UL != LL, E when UR != LR.  Its DEGREE is the number of border
+ * rays: 0, 2, 3 or 4.  A JUNCTION is a vertex of degree >= 3: T- and four-way junctions, both saddles under either connectivity,
+ * and every point where an interior border meets the plane's frame.
+ * 1 AUGMENT.  For every loop and every edge v_i -> v_{i+1} (cyclic): v_i, then the junctions strictly inside the edge in travel
+ *   order.  (A T-junction is a corner for two of its regions and an interior point of a straight edge for the third.)  Every
+ *   junction is inserted into at most one loop: n_aug <= n_vertices + (h+1)(w+1).  An edge that is not axis-parallel, has no
+ *   length, or has an id outside the lattice makes its loop MALFORMED, as does COUNT < 2 or OFFSET + COUNT > counts[1].
+ * 2 ARCS.  The augmented loop is cut at its junction vertices, which are always kept.  The stretch from one junction to the next,
+ *   cyclically, is an ARC (from a junction round to itself when the loop has one).  A loop with no junction is a RING: the whole
+ *   border between an island and its surround.
+ * 3 THE RULE FOR AN ARC u_0 .. u_k: Simplify's SPLIT(0, k) -- D_i, L, the L = 0 clause and the test 256 * D_m > tol16^2 * L are
+ *   exactly Simplify's -- with one change: m is the i with maximal D_i and, on ties, the smallest vertex ID (should a hand-made
+ *   loop hold one id twice, the first in travel order).  FOR A RING: anchor A is the vertex with the smallest id, anchor B
+ *   maximises |v - A|^2 (ties to the smallest id); A and B are kept, and SPLIT runs on A..B and on B..A.  Both neighbours see an
+ *   arc as the same sequence reversed and cross^2 is symmetric in its ends: both keep the same set.
+ * 4 OUTPUT, in Simplify's layout, each optional, none needs initialisation, a rejected call touches nothing:
+ *   loops_out     record i is (OFFSET', COUNT', VALUE, START) of input loop i, VALUE and START copied, OFFSET' the full exclusive
+ *                 prefix sum of COUNT'.  Only the first min(n_loops, loops_rows_out) records are written
+ *   vertices_out  the first min(n_vertices', vertex_rows_out) kept ids, loops back to back, each loop in augmented order from its
+ *                 first kept vertex at or after v_0.  Unlike Simplify's, v_0 may be dropped, and the output is no subset of
+ *                 the input: junctions are inserted.  A kept junction may be collinear with its kept neighbours; it stays,
+ *                 because the neighbour across the border has it
+ *   counts_out    INFUR_COVERAGE_COUNT_WORDS uint32_t {n_loops, n_vertices', n_degenerate (COUNT' < 3), status, n_aug, n_arcs};
+ *                 in n_arcs a ring counts as 1 and an arc once per loop that walks it
+ * STATUS.  INFUR_COVERAGE_TRUNCATED: counts[0] > loops_rows_in or counts[1] > vertex_rows_in; only counts_out is written, as
+ * {counts[0], 0, 0, 1, 0, 0}.  INFUR_COVERAGE_MALFORMED: some loop was malformed; it gets COUNT' = 0 and counts as degenerate, the
+ * other loops are as ever.  INFUR_COVERAGE_OVERFLOW: n_aug > aug_rows; counts_out = {n_loops, 0, 0, 4, n_aug, 0} and nothing else
+ * is touched: visible, and not an error.  Every load is clamped to the declared rows and to the plane: no value held in the
+ * input arrays can move a load or a store outside them.  (n_aug is reported saturated at 2^32 - 1.)
+ * SCRATCH.  aug_rows is the capacity in augmented vertices: 18 bytes each, beside two junction bitmaps of one bit per lattice
+ * vertex and 17 bytes per loop row.  aug_rows = 0 means vertex_rows_in + (h+1)(w+1), which cannot overflow; callers that know
+ * their scenes pass less.
+ * WHAT IT GUARANTEES.  Take the directed segments p -> q of all output loops with multiplicity, N(p, q) = count(p -> q) -
+ * count(q -> p).  With nothing skipped, N is 0 for every segment except those of one simple closed cycle, each with N = 1: the
+ * plane's frame as simplified.  The shoelace sum over all loops equals that cycle's.  tol16 = 0 keeps every augmented vertex.
+ * WHAT IT DOES NOT DO.  Arcs are simplified independently: at a large tolerance two different arcs may still cross (TopoJSON and
+ * mapshaper have the same property), and nothing repairs that.  No hole-to-parent nesting, no COCO JSON. */
+enum { INFUR_COVERAGE_SKIP = 1 };
+enum {
+    INFUR_COVERAGE_LOOPS = 0, INFUR_COVERAGE_VERTICES = 1, INFUR_COVERAGE_DEGENERATE = 2, INFUR_COVERAGE_STATUS = 3, INFUR_COVERAGE_AUG = 4,
+    INFUR_COVERAGE_ARCS = 5, INFUR_COVERAGE_COUNT_WORDS = 6
+};
+enum { INFUR_COVERAGE_TRUNCATED = 1, INFUR_COVERAGE_MALFORMED = 2, INFUR_COVERAGE_OVERFLOW = 4 };
+enum { INFUR_FEATURE_COVERAGE = 64 };
+
+/* host pointers: the plane, counts, min(counts[0], loops_rows_in) records and min(counts[1], vertex_rows_in) vertices travel to
+ * the device; then counts_out is read, and min(n_loops, loops_rows_out) records and min(n_vertices', vertex_rows_out) vertices are
+ * copied back */
+int32_t infur_coverage(infur_ctx* ctx, const void* plane, uint32_t elem_bytes, uint32_t h, uint32_t w, uint32_t flags,
+                       uint32_t skip_value, const uint32_t* loops, uint32_t loops_rows_in, const uint32_t* vertices,
+                       uint32_t vertex_rows_in, const uint32_t* counts, uint32_t tol16, uint32_t aug_rows, uint32_t* loops_out,
+                       uint32_t loops_rows_out, uint32_t* vertices_out, uint32_t vertex_rows_out, uint32_t* counts_out);
+/* device pointers throughout, d_counts and d_counts_out (six device uint32_t) included; enqueued on the context's stream as one
+ * memset and at most 13 launches, a number fixed by the arguments: the call never synchronises, so its grids are sized by h, w,
+ * loops_rows_in and aug_rows.  Capturable after one call outside the capture, which allocates the scratch, owned by the context.
+ * It grows only with a request larger than any before, and a graph captured around the call is re-captured after that.  The
+ * outputs must not overlap the inputs. */
+int32_t infur_coverage_dev(infur_ctx* ctx, const void* d_plane, uint32_t elem_bytes, uint32_t h, uint32_t w, uint32_t flags,
+                           uint32_t skip_value, const void* d_loops, uint32_t loops_rows_in, const void* d_vertices,
+                           uint32_t vertex_rows_in, const void* d_counts, uint32_t tol16, uint32_t aug_rows, void* d_loops_out,
+                           uint32_t loops_rows_out, void* d_vertices_out, uint32_t vertex_rows_out, void* d_counts_out);
+/* The fused frame path with polygons that fit: scale -> model -> Segments decode(out[0]) -> Outlines of the class plane into
+ * scratch of the library's own -> Coverage of that plane into the caller's buffers, in one call: the twins of
+ * infur_frame_polygons(_dev), with their arguments (flags are Outlines': SKIP reaches Coverage, CONN8 only Outlines) and checks;
+ * counts is Coverage's six words and aug_rows is 0.  The scaled frame must be at most 8191 x 8191 (INFUR_E_INVALID_ARG, before the
+ * model runs).  A plane with more edges than max_edges reads all-zero counts. */
+int32_t infur_frame_coverage(infur_ctx* ctx, const uint8_t* bgr, uint32_t w, uint32_t h, float factor, uint32_t scale_mode,
+                             uint32_t decode, uint32_t flags, uint32_t skip_value, uint32_t max_edges, uint32_t tol16,
+                             uint32_t* loops, uint32_t loops_rows, uint32_t* vertices, uint32_t vertex_rows, uint32_t* counts,
+                             uint64_t* stats, uint32_t stats_capacity, uint8_t* scaled_bgr, uint32_t* ow, uint32_t* oh);
+int32_t infur_frame_coverage_dev(infur_ctx* ctx, const void* d_bgr, uint32_t w, uint32_t h, float factor, uint32_t scale_mode,
+                                 uint32_t decode, uint32_t flags, uint32_t skip_value, uint32_t max_edges, uint32_t tol16,
+                                 void* d_loops, uint32_t loops_rows, void* d_vertices, uint32_t vertex_rows, void* d_counts,
+                                 void* d_stats, uint32_t stats_capacity, void* d_scaled_bgr, uint32_t* ow, uint32_t* oh);
+
 /* ---- streaming (infur/src/main.rs:27-99,105): bounded queue, copies overlapped with compute ----
  * The reference back-pressures its producer with sync_channel(2) (main.rs:105); a stream
  * here is a ring of `depth` pinned + device slots.  submit() copies the caller's frame into a

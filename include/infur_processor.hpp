@@ -561,6 +561,88 @@ private:
     bool dirty_ = true;
 };
 
+/// What `Coverage` produces, in Outlines' layout: `loops` holds min(n_loops, loops_rows) records (OFFSET', COUNT', VALUE, START),
+/// `vertices` the first min(n_vertices, vertex_rows) kept vertex ids; n_degenerate counts the loops with COUNT' < 3 (skip them);
+/// status: INFUR_COVERAGE_TRUNCATED and INFUR_COVERAGE_OVERFLOW (nothing was produced), INFUR_COVERAGE_MALFORMED; n_aug: the
+/// vertices once the junctions were inserted; n_arcs: the stretches between junctions, a ring counting as one.
+struct CoverageOut {
+    uint32_t loops_rows = 1u << 16, vertex_rows = 1u << 20;
+    uint32_t width = 0, height = 0, n_loops = 0, n_vertices = 0, n_degenerate = 0, status = 0, n_aug = 0, n_arcs = 0;
+    std::vector<uint32_t> loops, vertices;
+    uint32_t rows() const {
+        return (status & (INFUR_COVERAGE_TRUNCATED | INFUR_COVERAGE_OVERFLOW)) ? 0 : (n_loops < loops_rows ? n_loops : loops_rows);
+    }
+    uint32_t word(uint32_t loop, uint32_t w) const { return loops[(size_t)loop * INFUR_LOOP_WORDS + w]; }
+    bool is_hole(uint32_t loop) const { return (word(loop, INFUR_LOOP_START) & 3u) == 2u; }
+    bool is_degenerate(uint32_t loop) const { return word(loop, INFUR_LOOP_COUNT) < 3u; }
+    uint32_t x(uint32_t vertex) const { return vertices[vertex] % (width + 1); }
+    uint32_t y(uint32_t vertex) const { return vertices[vertex] / (width + 1); }
+};
+
+/// Simplify's sibling behind Outlines: the loops are cut at the plane's junctions and every arc is simplified once within tol16
+/// sixteenths of a pixel, so that neighbouring polygons still share their borders.  Integer results, identical from run to run.
+/// Command = the tolerance, skip / no skip (what Outlines was given), the capacity in augmented vertices (0: the worst case);
+/// Input = the plane Outlines was given and its OutlinesOut, Output = CoverageOut.
+class Coverage {
+public:
+    struct Cmd {
+        enum Kind { Tol16, Skip, NoSkip, AugRows } kind;
+        uint32_t value;
+    };
+    explicit Coverage(Context& c) : c_(c) {}
+    Status control(Cmd cmd) {
+        uint32_t tol16 = tol16_, flags = flags_, skip_value = skip_value_, aug_rows = aug_rows_;
+        switch (cmd.kind) {
+            case Cmd::Tol16:
+                if (cmd.value > 65535) return INFUR_E_INVALID_ARG;
+                tol16 = cmd.value;
+                break;
+            case Cmd::Skip: flags = INFUR_COVERAGE_SKIP, skip_value = cmd.value; break;
+            case Cmd::NoSkip: flags = 0, skip_value = 0; break;
+            case Cmd::AugRows: aug_rows = cmd.value; break;
+            default: return INFUR_E_INVALID_ARG;
+        }
+        dirty_ = dirty_ || tol16 != tol16_ || flags != flags_ || skip_value != skip_value_ || aug_rows != aug_rows_;
+        tol16_ = tol16, flags_ = flags, skip_value_ = skip_value, aug_rows_ = aug_rows;
+        return INFUR_OK;
+    }
+    bool is_dirty() const { return dirty_; }
+    Status advance(const std::vector<uint8_t>& plane, const OutlinesOut& in, CoverageOut& out) { return run(plane.data(), plane.size(), 1, in, out); }
+    Status advance(const std::vector<uint32_t>& plane, const OutlinesOut& in, CoverageOut& out) { return run(plane.data(), plane.size(), 4, in, out); }
+
+private:
+    Status run(const void* plane, size_t elems, uint32_t elem_bytes, const OutlinesOut& in, CoverageOut& out) {
+        dirty_ = false;
+        if (elems != (size_t)in.width * in.height) return INFUR_E_SHAPE;
+        out.width = in.width;
+        out.height = in.height;
+        const uint32_t rows_in = (uint32_t)(in.loops.size() / INFUR_LOOP_WORDS), verts_in = (uint32_t)in.vertices.size();
+        const uint64_t most = (uint64_t)verts_in + (uint64_t)(in.width + 1) * (in.height + 1);  // junctions are inserted
+        const uint32_t lrows = out.loops_rows < rows_in ? out.loops_rows : rows_in, vrows = out.vertex_rows < most ? out.vertex_rows : (uint32_t)most;
+        out.loops.assign((size_t)lrows * INFUR_LOOP_WORDS, 0);
+        out.vertices.assign(vrows, 0);
+        const uint32_t counts_in[2] = {in.n_loops, in.n_vertices};
+        uint32_t counts[INFUR_COVERAGE_COUNT_WORDS] = {0, 0, 0, 0, 0, 0};
+        const Status s = infur_coverage(c_.get(), plane, elem_bytes, in.height, in.width, flags_, skip_value_, rows_in ? in.loops.data() : nullptr, rows_in,
+                                        verts_in ? in.vertices.data() : nullptr, verts_in, counts_in, tol16_, aug_rows_, lrows ? out.loops.data() : nullptr,
+                                        lrows, vrows ? out.vertices.data() : nullptr, vrows, counts);
+        out.n_loops = counts[INFUR_COVERAGE_LOOPS];
+        out.n_vertices = counts[INFUR_COVERAGE_VERTICES];
+        out.n_degenerate = counts[INFUR_COVERAGE_DEGENERATE];
+        out.status = counts[INFUR_COVERAGE_STATUS];
+        out.n_aug = counts[INFUR_COVERAGE_AUG];
+        out.n_arcs = counts[INFUR_COVERAGE_ARCS];
+        const bool nothing = (out.status & (INFUR_COVERAGE_TRUNCATED | INFUR_COVERAGE_OVERFLOW)) != 0;
+        const uint32_t nl = nothing ? 0 : (out.n_loops < lrows ? out.n_loops : lrows);
+        out.loops.resize((size_t)nl * INFUR_LOOP_WORDS);
+        out.vertices.resize(out.n_vertices < vrows ? out.n_vertices : vrows);
+        return s;
+    }
+    Context& c_;
+    uint32_t tol16_ = 16, flags_ = 0, skip_value_ = 0, aug_rows_ = 0;
+    bool dirty_ = true;
+};
+
 /// infur_group: n contexts (one per GPU) of one process -- RCCL weight broadcast + frame-batch sharding
 /// (BASELINE configs[3]).  The contexts must outlive the group.
 class Group {

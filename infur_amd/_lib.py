@@ -66,6 +66,11 @@ FEATURE_OUTLINES = 16
 SIMPLIFY_LOOPS, SIMPLIFY_VERTICES, SIMPLIFY_DEGENERATE, SIMPLIFY_STATUS, SIMPLIFY_COUNT_WORDS = 0, 1, 2, 3, 4
 SIMPLIFY_TRUNCATED, SIMPLIFY_MALFORMED = 1, 2
 FEATURE_SIMPLIFY = 32
+# Coverage (infur_coverage / infur_frame_coverage): the flag, the words of its counts, the status bits, the feature bit
+COVERAGE_SKIP = 1
+COVERAGE_LOOPS, COVERAGE_VERTICES, COVERAGE_DEGENERATE, COVERAGE_STATUS, COVERAGE_AUG, COVERAGE_ARCS, COVERAGE_COUNT_WORDS = 0, 1, 2, 3, 4, 5, 6
+COVERAGE_TRUNCATED, COVERAGE_MALFORMED, COVERAGE_OVERFLOW = 1, 2, 4
+FEATURE_COVERAGE = 64
 
 
 class Options(C.Structure):
@@ -196,6 +201,12 @@ SIGNATURES = {
     "infur_frame_polygons": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _u32,
                                          _vp, _u32p, _u32p]),
     "infur_frame_polygons_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _vp,
+                                             _u32, _vp, _u32p, _u32p]),
+    "infur_coverage": (C.c_int32, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp]),
+    "infur_coverage_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp]),
+    "infur_frame_coverage": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _u32,
+                                         _vp, _u32p, _u32p]),
+    "infur_frame_coverage_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _vp,
                                              _u32, _vp, _u32p, _u32p]),
     "infur_stream_create": (C.c_int32, [_vp, _u32, C.POINTER(_vp)]),
     "infur_stream_destroy": (None, [_vp]),

@@ -10,6 +10,7 @@
 //   infur_runs.cpp          Runs (a class, label or track plane as run-length records): C entry points
 //   infur_outlines.cpp      Outlines (region boundaries of a class, label or track plane as polygon loops): C entry points
 //   infur_simplify.cpp      Simplify (Douglas-Peucker on Outlines' loops) and the polygon frame calls: C entry points
+//   infur_coverage.cpp      Coverage (Outlines' loops simplified arc by arc, shared borders once) and its frame calls: C entry points
 // (conv_forms.h, the table of conv modes, configurations and forms, comes with kernels.h)
 // (wave_scan.h, the device code regions.hip, tracks.hip and runs.hip share, also holds kScanBlock, which sizes their block sums)
 // Everything here lives in namespace infur and is NOT part of the public ABI.

@@ -334,4 +334,18 @@ hipError_t launch_simplify(const unsigned* loops, unsigned loops_rows_in, const 
                            unsigned W, unsigned tol16, void* scratch, unsigned* loops_out, unsigned loops_rows_out, unsigned* vertices_out,
                            unsigned vertex_rows_out, unsigned* counts_out, hipStream_t s);
 
+// Coverage (coverage.hip): Outlines' loops of an H x W plane (both in [1, 8191]) of 1- or 4-byte elements, simplified within
+// tol16 / 16 pixels so that neighbouring polygons still fit: the loops are cut at the plane's junctions and every arc between
+// two of them is simplified by a rule that does not depend on the direction of travel.  Inputs as launch_simplify's plus the
+// plane (skip: pixels of skip_value belong to no region); aug_rows >= 1: the capacity in augmented vertices.  Outputs, each
+// optional: loops_rows_out records, vertex_rows_out vertex ids and counts_out[6] = {n_loops, n_vertices', n_degenerate, status,
+// n_aug, n_arcs}.  scratch: coverage_scratch_bytes(H, W, loops_rows_in, aug_rows) bytes the launches own for the call.
+// Stream-ordered; one memset and at most 13 launches, no workgroup waits for another.  No value held in the input buffers takes
+// a load or a store outside the declared rows, the plane or the scratch.
+size_t coverage_scratch_bytes(size_t H, size_t W, size_t loops_rows, size_t aug_rows);
+hipError_t launch_coverage(const void* plane, int elem_bytes, unsigned H, unsigned W, int skip, unsigned skip_value, const unsigned* loops,
+                           unsigned loops_rows_in, const unsigned* vertices, unsigned vertex_rows_in, const unsigned* counts, unsigned tol16,
+                           unsigned aug_rows, void* scratch, unsigned* loops_out, unsigned loops_rows_out, unsigned* vertices_out,
+                           unsigned vertex_rows_out, unsigned* counts_out, hipStream_t s);
+
 }  // namespace infur

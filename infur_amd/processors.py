@@ -1092,6 +1092,74 @@ class Simplify(Processor):
         out.vertices = vo[:min(out.n_vertices, vrows)] if vo is not None else None
 
 
+class CoverageOut:
+    """``Coverage``'s ``&mut Output``: what to produce (``loops_rows`` records and ``vertex_rows`` vertices at most) and, after
+    ``advance``, the results in Outlines' layout -- ``loops`` [min(n_loops, loops_rows), 4] u32 with OFFSET' and COUNT', ``vertices``
+    [min(n_vertices, vertex_rows)] u32 -- and the counts ``n_loops``, ``n_vertices``, ``n_degenerate`` (loops with COUNT' < 3: skip
+    them), ``status`` (``_lib.COVERAGE_TRUNCATED`` and ``COVERAGE_OVERFLOW``: nothing was produced; ``COVERAGE_MALFORMED``),
+    ``n_aug`` (the vertices after the junctions were inserted) and ``n_arcs``."""
+
+    def __init__(self, loops_rows: int = 1 << 16, vertex_rows: int = 1 << 20):
+        self.loops_rows, self.vertex_rows = loops_rows, vertex_rows
+        self.loops = self.vertices = None
+        self.n_loops = self.n_vertices = self.n_degenerate = self.status = self.n_aug = self.n_arcs = 0
+
+
+class Coverage(Processor):
+    """Simplify's sibling behind Outlines: the loops are cut at the plane's junctions and every arc is simplified once, within
+    ``tol16`` sixteenths of a pixel, so that the polygons of neighbouring regions still share their borders.
+
+    Command = ``SimplifyCmd`` (the tolerance).  Input = ``(plane, loops, vertices, counts, skip)``: the plane Outlines was given,
+    what it left, and the value it skipped or None (``Coverage.input_of(plane, out, skip)``); Output = ``CoverageOut``.
+    ``outlines_polygons`` and ``outlines_by_value`` read the result as they read Outlines'.  Integers throughout, identical from
+    run to run.  ``aug_rows``: the capacity in augmented vertices, 0 for the worst case.
+    """
+
+    def __init__(self, ctx: Context, tol16: int = 16, aug_rows: int = 0):
+        self.ctx = ctx
+        self.tol16 = tol16
+        self.aug_rows = aug_rows
+        self.dirty = True
+
+    @staticmethod
+    def input_of(plane: np.ndarray, out: "OutlinesOut", skip: Optional[int] = None) -> tuple:
+        return plane, out.loops, out.vertices, (out.n_loops, out.n_vertices), skip
+
+    def control(self, cmd: SimplifyCmd) -> "Coverage":
+        if not 0 <= cmd.tol16 <= 65535:
+            raise InfurError(_lib.E_INVALID_ARG, f"tol16 {cmd.tol16}: 0 to 65535")
+        self.dirty = self.dirty or cmd.tol16 != self.tol16
+        self.tol16 = cmd.tol16
+        return self
+
+    def is_dirty(self) -> bool:
+        return self.dirty
+
+    def advance(self, inp: tuple, out: CoverageOut) -> None:
+        self.dirty = False
+        plane, loops, vertices, counts, skip = inp
+        plane = np.ascontiguousarray(plane)
+        if plane.ndim != 2 or plane.dtype not in (np.uint8, np.uint32):
+            raise InfurError(_lib.E_INVALID_ARG, "the plane: [h, w] of uint8 or uint32")
+        h, w = plane.shape
+        loops = np.ascontiguousarray(loops if loops is not None else np.zeros((0, _lib.LOOP_WORDS)), np.uint32).reshape(-1, _lib.LOOP_WORDS)
+        vertices = np.ascontiguousarray(vertices if vertices is not None else np.zeros(0), np.uint32).reshape(-1)
+        cin = np.array([int(counts[0]), int(counts[1])], np.uint32)
+        most = len(vertices) + (h + 1) * (w + 1)  # junctions are inserted: the output may be longer than the input
+        lrows, vrows = max(0, min(int(out.loops_rows), len(loops))), max(0, min(int(out.vertex_rows), most))
+        lo = np.empty((lrows, _lib.LOOP_WORDS), np.uint32) if lrows else None
+        vo = np.empty(vrows, np.uint32) if vrows else None
+        cout = np.zeros(_lib.COVERAGE_COUNT_WORDS, np.uint32)
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        self.ctx.check(self.ctx.L.infur_coverage(self.ctx.h, ptr(plane), plane.itemsize, h, w, _lib.COVERAGE_SKIP if skip is not None else 0, skip or 0,
+                                                 ptr(loops), len(loops), ptr(vertices), len(vertices), cin.ctypes.data, self.tol16, self.aug_rows,
+                                                 ptr(lo), lrows, ptr(vo), vrows, cout.ctypes.data))
+        out.n_loops, out.n_vertices, out.n_degenerate, out.status, out.n_aug, out.n_arcs = (int(v) for v in cout)
+        cut = bool(out.status & (_lib.COVERAGE_TRUNCATED | _lib.COVERAGE_OVERFLOW))
+        out.loops = lo[:0 if cut else min(out.n_loops, lrows)] if lo is not None else None
+        out.vertices = vo[:min(out.n_vertices, vrows)] if vo is not None else None
+
+
 class PolygonsFrame(NamedTuple):
     """``FramePath.advance_polygons``: ``OutlinesFrame`` with simplified loops, and the counts (n_loops, n_vertices, n_degenerate,
     status)"""
@@ -1350,6 +1418,43 @@ class FramePath:
         scaled = np.empty((oh.value, ow.value, 3), np.uint8) if want_scaled else None
         ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
         rc = L.infur_frame_polygons(self.ctx.h, img.ctypes.data, w, h, f, self.scale_mode, decode, _outlines_flags(skip, connectivity), skip or 0,
+                                    max_edges, tol16, ptr(loops), lrows, ptr(vertices), vrows, counts.ctypes.data, ptr(stats), k, ptr(scaled),
+                                    C.byref(ow), C.byref(oh))
+        if rc == _lib.E_MODEL_NOT_LOADED:
+            return PolygonsFrame(None, None, None, None, scaled, (oh.value, ow.value))
+        self.ctx.check(rc)
+        nl, nv = int(counts[0]), int(counts[1])
+        return PolygonsFrame(loops[:min(nl, lrows)] if loops is not None else None, vertices[:min(nv, vrows)] if vertices is not None else None,
+                             tuple(int(v) for v in counts), stats, scaled, (oh.value, ow.value))
+
+    def advance_coverage(self, img: np.ndarray, factor: float = 1.0, decode: int = _lib.DECODE_RAW, tol16: int = 16, skip: Optional[int] = None,
+                         connectivity: int = 4, max_edges: int = 0, loops_rows: int = 1 << 16, vertex_rows: int = 1 << 20,
+                         want_stats: bool = True, want_scaled: bool = False) -> PolygonsFrame:
+        """The fused path with polygons that fit, scale -> model -> Segments decode -> Outlines -> Coverage within ``tol16``
+        sixteenths of a pixel, in one call -> ``PolygonsFrame`` whose counts are Coverage's six (n_loops, n_vertices, n_degenerate,
+        status, n_aug, n_arcs).  Every result field is None when no model is loaded (``scaled`` is still produced)."""
+        img = _check_bgr(img)
+        h, w = img.shape[:2]
+        L = self.ctx.L
+        f = float(np.float32(factor))
+        rc = L.infur_scale_validate(f)
+        if rc:
+            raise ValidScaleError(rc)
+        ow, oh = C.c_uint32(0), C.c_uint32(0)
+        rc = L.infur_scale_out_dims(w, h, f, C.byref(ow), C.byref(oh))
+        if rc:
+            raise ScaleProcError(rc)
+        mi = _lib.ModelInfoC()
+        k = mi.num_classes if L.infur_model_info_get(self.ctx.h, C.byref(mi)) == _lib.OK else 0
+        npix = oh.value * ow.value
+        lrows, vrows = max(0, min(int(loops_rows), npix)), max(0, min(int(vertex_rows), 4 * npix + (oh.value + 1) * (ow.value + 1)))
+        loops = np.empty((lrows, _lib.LOOP_WORDS), np.uint32) if lrows else None
+        vertices = np.empty(vrows, np.uint32) if vrows else None
+        counts = np.zeros(_lib.COVERAGE_COUNT_WORDS, np.uint32)
+        stats = np.zeros((k, _lib.STAT_WORDS), np.uint64) if want_stats else None
+        scaled = np.empty((oh.value, ow.value, 3), np.uint8) if want_scaled else None
+        ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
+        rc = L.infur_frame_coverage(self.ctx.h, img.ctypes.data, w, h, f, self.scale_mode, decode, _outlines_flags(skip, connectivity), skip or 0,
                                     max_edges, tol16, ptr(loops), lrows, ptr(vertices), vrows, counts.ctypes.data, ptr(stats), k, ptr(scaled),
                                     C.byref(ow), C.byref(oh))
         if rc == _lib.E_MODEL_NOT_LOADED:

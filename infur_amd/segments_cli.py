@@ -42,6 +42,8 @@ records asked for the frame goes through ``infur_frame_outlines``.  ``--outlines
 simplifies every loop on the device within PX pixels (Douglas-Peucker; PX is rounded to sixteenths of a pixel): the file then holds
 the simplified arrays in the same per-frame layout, its three counts being n_loops, the simplified n_vertices and the number of
 degenerate loops (COUNT below 3: a thin region collapsed to two points; skip them), and every line gains ``"n_degenerate"``.
+``--outlines-shared`` (with ``--outlines-tolerance``) simplifies every border between two regions once (``infur_coverage``), so that
+the polygons of neighbours still fit: same file layout, and junction vertices may be added to a loop.
 """
 from __future__ import annotations
 
@@ -81,7 +83,11 @@ def main(argv=None) -> int:
     ap.add_argument("--outlines-out", default="", help="polygon loops: per frame 3 u32 counts, then n_loops x 4 u32, then n_vertices u32")
     ap.add_argument("--outlines-skip", type=int, default=None, help="pixels of this value belong to no outlined region")
     ap.add_argument("--outlines-tolerance", type=float, default=None, help="simplify the loops within this many pixels (needs --outlines-out)")
+    ap.add_argument("--outlines-shared", action="store_true",
+                    help="simplify every shared border once, so that neighbouring polygons still fit (needs --outlines-tolerance)")
     a = ap.parse_args(argv)
+    if a.outlines_shared and a.outlines_tolerance is None:
+        ap.error("--outlines-shared needs --outlines-tolerance")
     if a.tracks_out and not a.tracks:
         ap.error("--tracks-out needs --tracks")
     a.regions = a.regions or a.tracks
@@ -107,7 +113,7 @@ def main(argv=None) -> int:
 
     from . import _lib
     from .app import RawVideoSource, VideoProcError
-    from .processors import (Context, FramePath, Model, ModelCmd, Outlines, OutlinesOut, Runs, RunsOut, SegmentsFrame, Simplify, SimplifyOut,
+    from .processors import (Context, Coverage, CoverageOut, FramePath, Model, ModelCmd, Outlines, OutlinesOut, Runs, RunsOut, SegmentsFrame, Simplify, SimplifyOut,
                              class_summary, region_summary, tolerance_to_tol16, track_summary)
 
     tol16 = tolerance_to_tol16(a.outlines_tolerance) if a.outlines_tolerance is not None else None
@@ -139,7 +145,7 @@ def main(argv=None) -> int:
     if a.regions:
         oh, ow = _out_dims(ctx, a.width, a.height, a.scale)
         rpath = _RegionsPath(ctx, a.width, a.height, ow, oh, a.scale, fp.scale_mode, model.get_info().num_classes, max(0, a.max_regions),
-                             tracks=a.tracks, runs=fruns is not None, outlines=foutl is not None, simplify=tol16 is not None)
+                             tracks=a.tracks, runs=fruns is not None, outlines=foutl is not None, simplify=tol16 is not None, shared=a.outlines_shared)
         flags = _lib.REGIONS_SKIP_BACKGROUND if a.skip_background else 0
     n, t0 = 0, time.perf_counter()
     while True:
@@ -157,13 +163,13 @@ def main(argv=None) -> int:
             if fruns is not None:
                 runs, nruns = rpath.runs(a.runs_plane, a.runs_skip)
             if foutl is not None:
-                outl = rpath.outlines(a.outlines_skip, a.connectivity, tol16)
+                outl = rpath.outlines(a.outlines_skip, a.connectivity, tol16, a.outlines_shared)
         elif foutl is not None and fruns is None and flab is None and fconf is None:  # polygons, counts and captions: no dense plane
             if tol16 is None:
                 r = fp.advance_outlines(img, a.scale, decode, skip=a.outlines_skip, connectivity=a.connectivity, loops_rows=1 << 32, vertex_rows=1 << 32)
             else:
-                r = fp.advance_polygons(img, a.scale, decode, tol16, skip=a.outlines_skip, connectivity=a.connectivity, loops_rows=1 << 32,
-                                        vertex_rows=1 << 32)
+                fused = fp.advance_coverage if a.outlines_shared else fp.advance_polygons
+                r = fused(img, a.scale, decode, tol16, skip=a.outlines_skip, connectivity=a.connectivity, loops_rows=1 << 32, vertex_rows=1 << 32)
             s, outl = SegmentsFrame(None, None, r.stats, None, None), (np.array(r.counts[:3], np.uint32), r.loops, r.vertices)
         elif fruns is not None and flab is None and fconf is None and foutl is None:  # records, count and captions: no dense plane comes back
             r = fp.advance_runs(img, a.scale, decode, skip=a.runs_skip, runs_rows=1 << 32, want_row_start=False)
@@ -175,8 +181,11 @@ def main(argv=None) -> int:
                 Outlines(ctx, skip=a.outlines_skip, connectivity=a.connectivity).advance(s.klass, oo)
                 outl = (np.array([oo.n_loops, oo.n_vertices, oo.n_edges], np.uint32), oo.loops, oo.vertices)
                 if tol16 is not None:
-                    so = SimplifyOut(loops_rows=1 << 32, vertex_rows=1 << 32)
-                    Simplify(ctx, tol16).advance(Simplify.input_of(oo, s.klass.shape), so)
+                    so = (CoverageOut if a.outlines_shared else SimplifyOut)(loops_rows=1 << 32, vertex_rows=1 << 32)
+                    if a.outlines_shared:
+                        Coverage(ctx, tol16).advance(Coverage.input_of(s.klass, oo, a.outlines_skip), so)
+                    else:
+                        Simplify(ctx, tol16).advance(Simplify.input_of(oo, s.klass.shape), so)
                     outl = (np.array([so.n_loops, so.n_vertices, so.n_degenerate], np.uint32), so.loops, so.vertices)
             if fruns is not None:  # the class plane is on the host anyway
                 ro = RunsOut(runs_rows=1 << 32, want_row_start=False)
@@ -228,7 +237,7 @@ class _RegionsPath:
     writes class plane, confidence plane and per-class table into device buffers, infur_regions_dev labels those planes where
     they are; the tables, the count and the planes that are written out are all that is copied back."""
 
-    def __init__(self, ctx, w, h, ow, oh, factor, scale_mode, classes, rows, tracks=False, runs=False, outlines=False, simplify=False):
+    def __init__(self, ctx, w, h, ow, oh, factor, scale_mode, classes, rows, tracks=False, runs=False, outlines=False, simplify=False, shared=False):
         import ctypes as C
 
         self.ctx, self.w, self.h, self.ow, self.oh, self.factor, self.mode = ctx, w, h, ow, oh, float(factor), scale_mode
@@ -239,7 +248,8 @@ class _RegionsPath:
                 ((("ttab", self.rows * _TRACK_BYTES), ("tplane", ow * oh * 4), ("tsum", 16)) if tracks else ()) + \
                 ((("runs", ow * oh * _RUN_BYTES), ("nruns", 4)) if runs else ()) + \
                 ((("loops", ow * oh * _LOOP_BYTES), ("vertices", ow * oh * 16), ("ocounts", 12)) if outlines else ()) + \
-                ((("sloops", ow * oh * _LOOP_BYTES), ("svertices", ow * oh * 16), ("scounts", 16)) if outlines and simplify else ()):
+                ((("sloops", ow * oh * _LOOP_BYTES), ("svertices", ow * oh * 16 + (4 * (ow + 1) * (oh + 1) if shared else 0)), ("scounts", 24))
+                 if outlines and simplify else ()):
             p = C.c_void_p(None)
             ctx.check(ctx.L.infur_dev_alloc(ctx.h, max(n, 4), C.byref(p)))
             self.d[name] = p
@@ -302,15 +312,23 @@ class _RegionsPath:
         n = int(self._read("nruns", (1,), np.uint32)[0])
         return self._read("runs", (n, _RUN_BYTES // 4), np.uint32), n
 
-    def outlines(self, skip, connectivity, tol16=None):
+    def outlines(self, skip, connectivity, tol16=None, shared=False):
         """infur_outlines_dev on the label plane `advance` left on the device -> (counts [3], loops [n_loops, 4], vertices
         [n_vertices]) u32: every object's polygon, no dense plane.  tol16: infur_simplify_dev behind it, on the device too; the
-        counts are then n_loops, the simplified n_vertices, n_degenerate"""
+        counts are then n_loops, the simplified n_vertices, n_degenerate.  shared: infur_coverage_dev in its place, which reads the
+        label plane too and may insert junctions: its vertices have room for the lattice beside the input's"""
         import numpy as np
 
         c, d = self.ctx, self.d
         c.check(c.L.infur_outlines_dev(c.h, d["labels"], 4, self.oh, self.ow, (1 if skip is not None else 0) | (2 if connectivity == 8 else 0), skip or 0,
                                        0, d["loops"], self.ow * self.oh, d["vertices"], 4 * self.ow * self.oh, d["ocounts"]))
+        if tol16 is not None and shared:
+            rows = 4 * self.ow * self.oh + (self.ow + 1) * (self.oh + 1)
+            c.check(c.L.infur_coverage_dev(c.h, d["labels"], 4, self.oh, self.ow, 1 if skip is not None else 0, skip or 0, d["loops"], self.ow * self.oh,
+                                           d["vertices"], 4 * self.ow * self.oh, d["ocounts"], tol16, 0, d["sloops"], self.ow * self.oh, d["svertices"], rows,
+                                           d["scounts"]))
+            counts = self._read("scounts", (6,), np.uint32)[:3]
+            return counts, self._read("sloops", (int(counts[0]), _LOOP_BYTES // 4), np.uint32), self._read("svertices", (int(counts[1]),), np.uint32)
         if tol16 is not None:
             c.check(c.L.infur_simplify_dev(c.h, d["loops"], self.ow * self.oh, d["vertices"], 4 * self.ow * self.oh, d["ocounts"], self.oh, self.ow, tol16,
                                            d["sloops"], self.ow * self.oh, d["svertices"], 4 * self.ow * self.oh, d["scounts"]))

@@ -157,6 +157,20 @@ pub const INFUR_SIMPLIFY_TRUNCATED: u32 = 1;
 pub const INFUR_SIMPLIFY_MALFORMED: u32 = 2;
 /// bit of `infur_features()`: the Simplify calls below exist
 pub const INFUR_FEATURE_SIMPLIFY: u32 = 32;
+/// Coverage: its flag, the words of its counts (`INFUR_COVERAGE_COUNT_WORDS` u32), the status bits
+pub const INFUR_COVERAGE_SKIP: u32 = 1;
+pub const INFUR_COVERAGE_LOOPS: u32 = 0;
+pub const INFUR_COVERAGE_VERTICES: u32 = 1;
+pub const INFUR_COVERAGE_DEGENERATE: u32 = 2;
+pub const INFUR_COVERAGE_STATUS: u32 = 3;
+pub const INFUR_COVERAGE_AUG: u32 = 4;
+pub const INFUR_COVERAGE_ARCS: u32 = 5;
+pub const INFUR_COVERAGE_COUNT_WORDS: u32 = 6;
+pub const INFUR_COVERAGE_TRUNCATED: u32 = 1;
+pub const INFUR_COVERAGE_MALFORMED: u32 = 2;
+pub const INFUR_COVERAGE_OVERFLOW: u32 = 4;
+/// bit of `infur_features()`: the Coverage calls below exist
+pub const INFUR_FEATURE_COVERAGE: u32 = 64;
 
 extern "C" {
     pub fn infur_abi_version() -> u32;
@@ -362,6 +376,25 @@ extern "C" {
                                 vertices: *mut u32, vertex_rows: u32, counts: *mut u32, stats: *mut u64, stats_capacity: u32,
                                 scaled_bgr: *mut u8, ow: *mut u32, oh: *mut u32) -> i32;
     pub fn infur_frame_polygons_dev(c: *mut infur_ctx, d_bgr: *const c_void, w: u32, h: u32, factor: f32, scale_mode: u32,
+                                    decode: u32, flags: u32, skip_value: u32, max_edges: u32, tol16: u32, d_loops: *mut c_void,
+                                    loops_rows: u32, d_vertices: *mut c_void, vertex_rows: u32, d_counts: *mut c_void,
+                                    d_stats: *mut c_void, stats_capacity: u32, d_scaled_bgr: *mut c_void, ow: *mut u32,
+                                    oh: *mut u32) -> i32;
+    // Coverage: Outlines' loops simplified arc by arc, shared borders once, and the frame path that ends in it
+    pub fn infur_coverage(c: *mut infur_ctx, plane: *const c_void, elem_bytes: u32, h: u32, w: u32, flags: u32, skip_value: u32,
+                          loops: *const u32, loops_rows_in: u32, vertices: *const u32, vertex_rows_in: u32, counts: *const u32,
+                          tol16: u32, aug_rows: u32, loops_out: *mut u32, loops_rows_out: u32, vertices_out: *mut u32,
+                          vertex_rows_out: u32, counts_out: *mut u32) -> i32;
+    pub fn infur_coverage_dev(c: *mut infur_ctx, d_plane: *const c_void, elem_bytes: u32, h: u32, w: u32, flags: u32,
+                              skip_value: u32, d_loops: *const c_void, loops_rows_in: u32, d_vertices: *const c_void,
+                              vertex_rows_in: u32, d_counts: *const c_void, tol16: u32, aug_rows: u32, d_loops_out: *mut c_void,
+                              loops_rows_out: u32, d_vertices_out: *mut c_void, vertex_rows_out: u32,
+                              d_counts_out: *mut c_void) -> i32;
+    pub fn infur_frame_coverage(c: *mut infur_ctx, bgr: *const u8, w: u32, h: u32, factor: f32, scale_mode: u32, decode: u32,
+                                flags: u32, skip_value: u32, max_edges: u32, tol16: u32, loops: *mut u32, loops_rows: u32,
+                                vertices: *mut u32, vertex_rows: u32, counts: *mut u32, stats: *mut u64, stats_capacity: u32,
+                                scaled_bgr: *mut u8, ow: *mut u32, oh: *mut u32) -> i32;
+    pub fn infur_frame_coverage_dev(c: *mut infur_ctx, d_bgr: *const c_void, w: u32, h: u32, factor: f32, scale_mode: u32,
                                     decode: u32, flags: u32, skip_value: u32, max_edges: u32, tol16: u32, d_loops: *mut c_void,
                                     loops_rows: u32, d_vertices: *mut c_void, vertex_rows: u32, d_counts: *mut c_void,
                                     d_stats: *mut c_void, stats_capacity: u32, d_scaled_bgr: *mut c_void, ow: *mut u32,

@@ -759,6 +759,96 @@ impl Processor for HipSimplify {
     }
 }
 
+// ---------------------------------------------------------------- Coverage (shared borders simplified once)
+/// What `HipCoverage` produces, in `Outlines`' layout: `loops` holds `min(n_loops, loops_rows)` records (OFFSET', COUNT', VALUE,
+/// START), `vertices` the first `min(n_vertices, vertex_rows)` kept vertex ids; `n_degenerate` counts the loops with COUNT' < 3
+/// (skip them); `status`: `INFUR_COVERAGE_TRUNCATED` and `INFUR_COVERAGE_OVERFLOW` (nothing was produced),
+/// `INFUR_COVERAGE_MALFORMED`; `n_aug`: the vertices once the junctions were inserted; `n_arcs`: a ring counts as one.
+pub struct Covered {
+    pub loops_rows: usize, pub vertex_rows: usize,
+    pub loops: Vec<u32>, pub vertices: Vec<u32>,
+    pub n_loops: u32, pub n_vertices: u32, pub n_degenerate: u32, pub status: u32, pub n_aug: u32, pub n_arcs: u32,
+}
+impl Covered {
+    pub fn new(loops_rows: usize, vertex_rows: usize) -> Self {
+        Self { loops_rows, vertex_rows, loops: Vec::new(), vertices: Vec::new(), n_loops: 0, n_vertices: 0, n_degenerate: 0, status: 0, n_aug: 0, n_arcs: 0 }
+    }
+    pub fn rows(&self) -> usize {
+        if self.status & (sys::INFUR_COVERAGE_TRUNCATED | sys::INFUR_COVERAGE_OVERFLOW) != 0 { 0 } else { (self.n_loops as usize).min(self.loops_rows) }
+    }
+    pub fn word(&self, l: usize, word: u32) -> u32 { self.loops[l * sys::INFUR_LOOP_WORDS as usize + word as usize] }
+    pub fn is_degenerate(&self, l: usize) -> bool { self.word(l, sys::INFUR_LOOP_COUNT) < 3 }
+}
+/// the plane `HipOutlines` was given, and the `Outlines` it left
+pub struct CoverageInput { pub plane: RunsPlane, pub outlines: Outlines }
+pub enum CoverageCmd { Tol16(u32), Skip(u32), NoSkip, AugRows(u32) }
+/// `HipSimplify`'s sibling: the loops are cut at the plane's junctions and every arc is simplified once within `tol16` sixteenths
+/// of a pixel, so that neighbouring polygons still share their borders.  Integer results, identical from run to run.
+pub struct HipCoverage { ctx: Rc<Ctx>, tol16: u32, skip: Option<u32>, aug_rows: u32, dirty: bool }
+impl HipCoverage {
+    pub fn new(ctx: Rc<Ctx>) -> Self { Self { ctx, tol16: 16, skip: None, aug_rows: 0, dirty: true } }
+}
+impl Processor for HipCoverage {
+    type Command = CoverageCmd;
+    type ControlError = HipError;
+    type Input = CoverageInput;
+    type Output = Covered;
+    type ProcessResult = Result<(), HipError>;
+
+    fn control(&mut self, cmd: CoverageCmd) -> Result<&mut Self, HipError> {
+        let (tol16, skip, aug_rows) = match cmd {
+            CoverageCmd::Tol16(t) if t > 65535 => return Err(HipError::status(sys::INFUR_E_INVALID_ARG)),
+            CoverageCmd::Tol16(t) => (t, self.skip, self.aug_rows),
+            CoverageCmd::Skip(v) => (self.tol16, Some(v), self.aug_rows),
+            CoverageCmd::NoSkip => (self.tol16, None, self.aug_rows),
+            CoverageCmd::AugRows(n) => (self.tol16, self.skip, n),
+        };
+        self.dirty |= (tol16, skip, aug_rows) != (self.tol16, self.skip, self.aug_rows);
+        self.tol16 = tol16;
+        self.skip = skip;
+        self.aug_rows = aug_rows;
+        Ok(self)
+    }
+    fn is_dirty(&self) -> bool { self.dirty }
+    fn advance(&mut self, inp: &CoverageInput, out: &mut Covered) -> Result<(), HipError> {
+        self.dirty = false;
+        let [w, h] = inp.plane.size;
+        let (ptr, len, elem_bytes) = match &inp.plane.data {
+            RunsPlaneData::U8(p) => (p.as_ptr() as *const std::ffi::c_void, p.len(), 1u32),
+            RunsPlaneData::U32(p) => (p.as_ptr() as *const std::ffi::c_void, p.len(), 4u32),
+        };
+        if len != w * h { return Err(HipError::status(sys::INFUR_E_SHAPE)); }
+        let o = &inp.outlines;
+        let rows_in = o.loops.len() / sys::INFUR_LOOP_WORDS as usize;
+        let lrows = out.loops_rows.min(rows_in);
+        let vrows = out.vertex_rows.min(o.vertices.len() + (w + 1) * (h + 1));  // junctions are inserted
+        out.loops.resize(lrows * sys::INFUR_LOOP_WORDS as usize, 0);
+        out.vertices.resize(vrows, 0);
+        let counts_in = [o.n_loops, o.n_vertices];
+        let mut counts = [0u32; 6];
+        let rc = unsafe {
+            sys::infur_coverage(self.ctx.0, ptr, elem_bytes, h as u32, w as u32, if self.skip.is_some() { sys::INFUR_COVERAGE_SKIP } else { 0 },
+                                self.skip.unwrap_or(0), if rows_in > 0 { o.loops.as_ptr() } else { std::ptr::null() }, rows_in as u32,
+                                if !o.vertices.is_empty() { o.vertices.as_ptr() } else { std::ptr::null() }, o.vertices.len() as u32,
+                                counts_in.as_ptr(), self.tol16, self.aug_rows,
+                                if lrows > 0 { out.loops.as_mut_ptr() } else { std::ptr::null_mut() }, lrows as u32,
+                                if vrows > 0 { out.vertices.as_mut_ptr() } else { std::ptr::null_mut() }, vrows as u32, counts.as_mut_ptr())
+        };
+        if rc != sys::INFUR_OK { return Err(HipError::from_ctx(&self.ctx, rc)); }
+        out.n_loops = counts[0];
+        out.n_vertices = counts[1];
+        out.n_degenerate = counts[2];
+        out.status = counts[3];
+        out.n_aug = counts[4];
+        out.n_arcs = counts[5];
+        let nothing = out.status & (sys::INFUR_COVERAGE_TRUNCATED | sys::INFUR_COVERAGE_OVERFLOW) != 0;
+        let nl = if nothing { 0 } else { (out.n_loops as usize).min(lrows) };
+        out.loops.truncate(nl * sys::INFUR_LOOP_WORDS as usize);
+        out.vertices.truncate((out.n_vertices as usize).min(vrows));
+        Ok(())
+    }
+}
+
 // ---------------------------------------------------------------- streaming ring with zero-copy slots (main.rs:27-99,105; ABI 5)
 /// The bounded queue of frames in flight (`sync_channel(2)`, main.rs:105) over `infur_stream_*`.  `next_slot` / `commit` let the
 /// decoder fill the ring's own pinned buffer in place -- what `ff-video/src/decoder.rs:156-165` does with its reused `BgrImage` --
