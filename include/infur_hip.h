@@ -954,8 +954,15 @@ int32_t infur_profile_enable(infur_ctx* ctx, uint32_t on);
 /* number of kernel records of the last advance (synchronises the stream) */
 int32_t infur_profile_count(infur_ctx* ctx, uint32_t* n);
 int32_t infur_profile_get(infur_ctx* ctx, uint32_t i, infur_kernel_record* rec);
+/* debug (additive, no ABI change): which of a configuration's size-picked kernels ran for record i of the last advance, as a short
+ * NUL-terminated tag ("bm256", "nsplit4", "bn128,mixed,na2", "lds", "form3,dma2", "f32stem"); "" where the launch has one form.
+ * The record's `kernel` names the configuration, this names the kernel inside it.  INFUR_E_CAPACITY when cap is too small (24 is
+ * always enough), INFUR_E_INVALID_ARG for i >= infur_profile_count. */
+int32_t infur_debug_profile_variant(infur_ctx* ctx, uint32_t i, char* buf, size_t cap);
 
-/* ---- device memory helpers for bindings without a HIP runtime of their own ---- */
+/* ---- device memory helpers for bindings without a HIP runtime of their own ----
+ * Device pointers passed to any *_dev entry point need only the natural alignment of their element type (1 byte for frames, byte
+ * planes and masks' sources, 4 for f32 tensors and RGBA words, 8 for the statistics table): no call requires more. */
 int32_t infur_dev_alloc(infur_ctx* ctx, size_t bytes, void** d_ptr);
 int32_t infur_dev_free(infur_ctx* ctx, void* d_ptr);
 int32_t infur_memcpy_h2d(infur_ctx* ctx, void* d_dst, const void* src, size_t bytes);

@@ -245,6 +245,7 @@ SIGNATURES = {
     "infur_profile_enable": (C.c_int32, [_vp, _u32]),
     "infur_profile_count": (C.c_int32, [_vp, _u32p]),
     "infur_profile_get": (C.c_int32, [_vp, _u32, C.POINTER(KernelRecord)]),
+    "infur_debug_profile_variant": (C.c_int32, [_vp, _u32, C.c_char_p, _sz]),
     "infur_dev_alloc": (C.c_int32, [_vp, _sz, C.POINTER(_vp)]),
     "infur_dev_free": (C.c_int32, [_vp, _vp]),
     "infur_memcpy_h2d": (C.c_int32, [_vp, _vp, _vp, _sz]),

@@ -262,12 +262,17 @@ bool conv1x1_areg_valid(const ConvArgs& a, int mode, int out_f32) {
            (size_t)a.H * a.W * a.Cin * 2 < 0x80000000ull && (size_t)a.OH * a.OW * a.Cout * 2 < 0x80000000ull && (size_t)a.Cout * a.Cin * 2 < 0x80000000ull;
 }
 
-hipError_t launch_conv1x1_areg(const ConvArgs& a, hipStream_t s) {
-    // the 128-pixel form where 256-pixel workgroups would leave more than a third of the 256 CUs without one (INFUR_AREG_BM=128 / 256:
-    // measurement hook)
+// the 128-pixel form where 256-pixel workgroups would leave more than a third of the 256 CUs without one (conv_forms.h:
+// areg_small_rule; INFUR_AREG_BM=128 / 256: measurement and test hook)
+static bool areg_small(const ConvArgs& a) {
     static const int bm_env = getenv("INFUR_AREG_BM") ? atoi(getenv("INFUR_AREG_BM")) : 0;
-    const bool small = bm_env == 128 || (bm_env != 256 && (a.OH * a.OW + 255) / 256 <= 170);
-    if (small) {
+    return bm_env == 128 || (bm_env != 256 && areg_small_rule((long)a.OH * a.OW));
+}
+
+const char* conv1x1_areg_variant(const ConvArgs& a) { return areg_small(a) ? "bm128" : "bm256"; }
+
+hipError_t launch_conv1x1_areg(const ConvArgs& a, hipStream_t s) {
+    if (areg_small(a)) {
         switch (a.Cin) {
             case 64: return launch_ks<1, 1, 4, 4>(a, s);
             case 128: return launch_ks<2, 1, 4, 4>(a, s);

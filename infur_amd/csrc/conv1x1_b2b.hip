@@ -393,6 +393,13 @@ __global__ void __launch_bounds__(NW * 64, NW == 8 ? 2 : 1) conv1x1_b2b_kernel(c
     }
 }
 
+// INFUR_B2B_DMA (measurement and test hook): which waves issue the DMA pieces, 0 / 1 / 2 (the default)
+int b2b_dma_phase() {
+    static const int dma_env = getenv("INFUR_B2B_DMA") ? atoi(getenv("INFUR_B2B_DMA")) : 2;
+    static const int dma_phase = dma_env < 0 || dma_env > 2 ? 2 : dma_env;
+    return dma_phase;
+}
+
 template <int KS, int RB, int NW>
 hipError_t launch_form(const B2bArgs& a, hipStream_t s) {
     constexpr int BM = NW * RB * 32;
@@ -409,9 +416,7 @@ hipError_t launch_form(const B2bArgs& a, hipStream_t s) {
     }
     // (0 / 1 / 2 only: any other value would leave the late waves' pieces un-issued -- which, as an ablation, runs the 4K layer3 pair in
     //  157 instead of 188 us with HALF the weight / residual pieces missing: the step is bound by the DMA ingest, not by its MFMAs)
-    static const int dma_env = getenv("INFUR_B2B_DMA") ? atoi(getenv("INFUR_B2B_DMA")) : 2;
-    static const int dma_phase = dma_env < 0 || dma_env > 2 ? 2 : dma_env;
-    hipLaunchKernelGGL(k, dim3(mtiles), dim3(NW * 64), kLds, s, a, mtiles, dma_phase);
+    hipLaunchKernelGGL(k, dim3(mtiles), dim3(NW * 64), kLds, s, a, mtiles, b2b_dma_phase());
     return hipGetLastError();
 }
 
@@ -437,16 +442,22 @@ hipError_t launch_b2b_pack_w3(const void* w3, void* w3i, int C2, hipStream_t s) 
     return hipGetLastError();
 }
 
+// the workgroup form of a launch (conv_forms.h: b2b_form_rule is the default):
+// measurement hook: INFUR_B2B_FORM=1 (default) two waves per SIMD x 32 pixels; 2 one wave per SIMD x 64 pixels with the
+// whole register file -- half the LDS fragment reads, but nothing covers the wave while it is held at a DMA issue or in
+// its epilogue: 237 against 170 us on the 4K layer3 pair (same box)
+// INFUR_B2B_FORM (measurement hook): 1 two waves per SIMD x 32 pixels; 2 one wave per SIMD x 64 pixels; 3 the 128-pixel workgroup;
+// default: 3 when 256-pixel workgroups would leave more than a third of the 256 CUs without one, else 1
+static int b2b_form(const B2bArgs& a) {
+    static const int form_env = getenv("INFUR_B2B_FORM") ? atoi(getenv("INFUR_B2B_FORM")) : 0;
+    return form_env >= 1 && form_env <= 3 ? form_env : b2b_form_rule(a.M);
+}
+
+const char* conv1x1_b2b_variant(const B2bArgs& a) { return b2b_variant_tag(b2b_form(a), b2b_dma_phase()); }
+
 hipError_t launch_conv1x1_b2b(const B2bArgs& a, hipStream_t s) {
     if (!conv1x1_b2b_valid(a)) return hipErrorInvalidValue;
-    // measurement hook: INFUR_B2B_FORM=1 (default) two waves per SIMD x 32 pixels; 2 one wave per SIMD x 64 pixels with the
-    // whole register file -- half the LDS fragment reads, but nothing covers the wave while it is held at a DMA issue or in
-    // its epilogue: 237 against 170 us on the 4K layer3 pair (same box)
-    // INFUR_B2B_FORM (measurement hook): 1 two waves per SIMD x 32 pixels; 2 one wave per SIMD x 64 pixels; 3 the 128-pixel workgroup;
-    // default: 3 when 256-pixel workgroups would leave more than a third of the 256 CUs without one, else 1
-    static const int form_env = getenv("INFUR_B2B_FORM") ? atoi(getenv("INFUR_B2B_FORM")) : 0;
-    const int mt256 = (a.M + 255) / 256;
-    const int form = form_env >= 1 && form_env <= 3 ? form_env : (mt256 <= 170 ? 3 : 1);
+    const int form = b2b_form(a);
     if (form == 1) return a.C2 == 256 ? launch_form<4, 1, 8>(a, s) : launch_form<2, 1, 8>(a, s);
     if (form == 3) return a.C2 == 256 ? launch_form<4, 1, 4>(a, s) : launch_form<2, 1, 4>(a, s);
     return a.C2 == 256 ? launch_form<4, 2, 4>(a, s) : launch_form<2, 2, 4>(a, s);

@@ -264,14 +264,16 @@ bool conv1x1_q8_valid(const ConvArgs& a, int mode, int out_f32) {
 // one round of workgroups that each walk several N tiles beats more, shorter-lived ones (a workgroup's life starts with one full
 // memory latency for its activation tile, and a second round of workgroups pays it again with most of the chip idle).
 int conv1x1_q8_nsplit(const ConvArgs& a) {
+    static_assert(Q8_BM == kQ8TilePixels && Q8_BN == kQ8TileChannels && Q8_MAXC / Q8_BN <= kQ8MaxSplit, "conv_forms.h: q8_nsplit_rule");
     const int mtiles = (a.OH * a.OW + Q8_BM - 1) / Q8_BM, ntiles = a.Cout / Q8_BN;
-    if (mtiles >= 480 || ntiles < 2) return 0;
-    static const int forced = getenv("INFUR_Q8_NSPLIT") ? atoi(getenv("INFUR_Q8_NSPLIT")) : 0;  // (experiment hook)
+    const int rule = q8_nsplit_rule(mtiles, ntiles);
+    if (rule == 0) return 0;
+    static const int forced = getenv("INFUR_Q8_NSPLIT") ? atoi(getenv("INFUR_Q8_NSPLIT")) : 0;  // (experiment and test hook)
     if (forced > 1 && ntiles % forced == 0) return forced;
-    for (int d = 2; d <= ntiles; d++)
-        if (ntiles % d == 0 && (mtiles * d >= 480 || d == ntiles)) return d;
-    return 0;
+    return rule;
 }
+
+const char* conv1x1_q8_variant(const ConvArgs& a) { return q8_nsplit_tag(conv1x1_q8_nsplit(a)); }
 
 hipError_t launch_conv1x1_q8(const ConvArgs& a, int nsplit, hipStream_t s) {
     if (nsplit < 1 || (a.Cout / Q8_BN) % nsplit) return hipErrorInvalidValue;

@@ -853,9 +853,17 @@ static int halo_bn(const ConvArgs& a, int bn) {
     static const int force = getenv("INFUR_HALO_BN") ? atoi(getenv("INFUR_HALO_BN")) : 0;  // measurement hook: 64 / 128
     if (force == 64 && a.Cout % 64 == 0) return 64;
     if (force == 128) return 128;
-    const long tiles = (long)((a.OH + 15) / 16) * ((a.OW + 15) / 16);
-    return (a.Cout % 128 == 0 && tiles * (a.Cout / 128) <= 170) ? 64 : 128;
+    return halo_bn_rule(halo_tiles16(a.OH, a.OW), a.Cout);  // (conv_forms.h)
 }
+
+// what launch_conv3x3_halo / _halo_q / _halo4 run for a launch they take: N tile, tiling of the map, patch images (conv_forms.h)
+static const char* halo_tag(int bn, const HaloPlan& pl) { return pl.na ? halo_variant_tag(bn, pl.g.th1, pl.g.tw1, pl.g.th2, pl.na) : ""; }
+const char* conv3x3_halo_variant(const ConvArgs& a, int mode, int bn) {
+    if (mode == 4) return halo_tag(bn, halo_plan(a, bn, 1));
+    bn = halo_bn(a, bn);
+    return halo_tag(bn, halo_plan(a, bn));
+}
+const char* conv3x3_halo4_variant(const ConvArgs& a) { return halo_tag(H4_BN, halo4_plan(a)); }
 
 bool conv3x3_halo_valid(const ConvArgs& a, int mode, int out_f32, int bn) {
     if (mode == 4) {  // the quantised model's 3x3 convs (u8 out): BN = 128 / 256, 128-byte rows = 128 channels

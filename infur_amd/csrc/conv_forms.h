@@ -184,6 +184,96 @@ inline const char* conv_form_name(int cfg, int mode, bool hl_plain) {
     return mode == kModeHL && hl_plain ? kConvFormNames.plain[cfg] : kConvFormNames.name[mode][cfg];
 }
 
+// ---- sub-forms: the kernels WITHIN a configuration, picked from the size of the map ----
+// Several launchers choose among two to four kernels from M (pixels) and Cout.  The pure size rules live here, so that the launcher,
+// the name function (conv_variant_name, kernels.h) and tests/cpp/conv_forms_test.cpp all evaluate the same expression; the
+// environment hooks that override a rule stay with their launcher.  All sub-forms of a configuration give the same bits.
+constexpr int kTwoThirdsOfCUs = 170;  // of 256: a launch of no more workgroups than this leaves over a third of the chip idle
+constexpr long cdiv_l(long a, long b) { return (a + b - 1) / b; }
+// conv1x1_areg.hip (kModeF16, kCfgAreg): the 128-pixel 4-wave form where 256-pixel workgroups would leave more than a third of the
+// CUs without one
+constexpr bool areg_small_rule(long M) { return cdiv_l(M, 256) <= kTwoThirdsOfCUs; }
+// conv1x1_b2b.hip: INFUR_B2B_FORM's default -- 3 (the 128-pixel workgroup) by the same rule, else 1 (two waves per SIMD x 32 pixels)
+constexpr int b2b_form_rule(long M) { return cdiv_l(M, 256) <= kTwoThirdsOfCUs ? 3 : 1; }
+// conv3x3_halo.hip (kModeF16, kCfgHalo128): N tiles of 64 on the 64-channel convs and wherever 128-wide tiles over 16 x 16 pixel tiles
+// would leave more than a third of the CUs without a workgroup (a Cout that 128 does not divide keeps 128 and is then no candidate)
+constexpr long halo_tiles16(int OH, int OW) { return cdiv_l(OH, 16) * cdiv_l(OW, 16); }
+constexpr int halo_bn_rule(long tiles16, int Cout) {
+    if (Cout == 64) return 64;
+    return (Cout % 128 == 0 && tiles16 * (Cout / 128) <= kTwoThirdsOfCUs) ? 64 : 128;
+}
+// conv1x1_q8.hip (kModeI8, kCfgAregNsplit; M tiles of 128 pixels, N tiles of 128 channels): the smallest divisor of the N tile count
+// that brings the launch to about two workgroups per CU; 0: the plain form already has them, or Cout is a single N tile
+constexpr int kQ8TilePixels = 128, kQ8TileChannels = 128, kQ8TwoPerCU = 480, kQ8MaxSplit = 16;
+constexpr int q8_nsplit_rule(long mtiles, int ntiles) {
+    if (mtiles >= kQ8TwoPerCU || ntiles < 2) return 0;
+    for (int d = 2; d <= ntiles; d++)
+        if (ntiles % d == 0 && (mtiles * d >= kQ8TwoPerCU || d == ntiles)) return d;
+    return 0;
+}
+
+// ---- variant tags: what a profile record says about the sub-form that ran (ProfRec::variant, infur_debug_profile_variant) ----
+// A tag is a comma-separated list of the words below, "" where a launch has one form only.  The halo forms say three things:
+// the N tile, the tiling of the map (uniform 16 x 16, uniform 8 x 32, or 16 x 16 with an (H mod 16) x 32 strip) and the number of
+// patch images.  EVERY word the library can say is in kVariantWords: tests/test_conv_forms_cpu.py holds tests/forms.py against it,
+// so that a new sub-form without a forced case fails there.
+constexpr const char* kVariantWords[] = {
+    "bm128", "bm256",                                // conv1x1_areg.hip
+    "nsplit2", "nsplit4", "nsplit8", "nsplit16",     // conv1x1_q8.hip (N tile counts of 2^k: every Cout the kernel is built for)
+    "bn64", "bn128", "bn256",                        // conv3x3_halo.hip
+    "16x16", "8x32", "mixed", "na1", "na2",          //   halo_plan / halo4_plan
+    "lds", "f32x1", "f32x2", "f32x4w",               // winograd.hip: the transforms' forms
+    "form1", "form2", "form3", "dma0", "dma1", "dma2",  // conv1x1_b2b.hip: workgroup form, which waves issue the DMA pieces
+    "f16stem", "f32stem",                            // stem_pool.hip: the fused stem's arithmetic (split modes: f16stem = its f16 hi + lo pairs)
+};
+constexpr int kNumVariantWords = (int)(sizeof(kVariantWords) / sizeof(kVariantWords[0]));
+
+constexpr const char* q8_nsplit_tag(int nsplit) {
+    constexpr const char* t[kQ8MaxSplit + 1] = {"", "", "nsplit2", "nsplit3", "nsplit4", "nsplit5", "nsplit6", "nsplit7", "nsplit8",
+                                                "nsplit9", "nsplit10", "nsplit11", "nsplit12", "nsplit13", "nsplit14", "nsplit15", "nsplit16"};
+    return nsplit >= 0 && nsplit <= kQ8MaxSplit ? t[nsplit] : "nsplit?";
+}
+
+// the halo forms' tags, built once: [bn 64 / 128 / 256][tiling 16x16 / 8x32 / mixed][patch images 1 / 2]
+constexpr int kVariantLen = 24;
+struct HaloTags {
+    char tag[3][3][2][kVariantLen];
+};
+constexpr HaloTags halo_tags() {
+    HaloTags t{};
+    constexpr const char* bn[3] = {"bn64", "bn128", "bn256"};
+    constexpr const char* geom[3] = {",16x16", ",8x32", ",mixed"};
+    constexpr const char* na[2] = {",na1", ",na2"};
+    for (int b = 0; b < 3; b++)
+        for (int g = 0; g < 3; g++)
+            for (int n = 0; n < 2; n++) conv_name_join(t.tag[b][g][n], bn[b], geom[g], na[n], "");
+    return t;
+}
+inline constexpr HaloTags kHaloTags = halo_tags();
+// th1 x tw1 = the first region's tile, th2 = rows of the strip region (0: none): HaloGeom of conv3x3_halo.hip
+inline const char* halo_variant_tag(int bn, int th1, int tw1, int th2, int na) {
+    const int b = bn == 64 ? 0 : bn == 128 ? 1 : bn == 256 ? 2 : -1;
+    if (b < 0 || na < 1 || na > 2) return "halo?";
+    return kHaloTags.tag[b][th2 ? 2 : (th1 == 8 && tw1 == 32) ? 1 : 0][na - 1];
+}
+
+// conv1x1_b2b.hip: [form 1 / 2 / 3][dma phase 0 / 1 / 2]
+struct B2bTags {
+    char tag[3][3][kVariantLen];
+};
+constexpr B2bTags b2b_tags() {
+    B2bTags t{};
+    constexpr const char* form[3] = {"form1", "form2", "form3"};
+    constexpr const char* dma[3] = {",dma0", ",dma1", ",dma2"};
+    for (int f = 0; f < 3; f++)
+        for (int d = 0; d < 3; d++) conv_name_join(t.tag[f][d], form[f], dma[d], "", "");
+    return t;
+}
+inline constexpr B2bTags kB2bTags = b2b_tags();
+inline const char* b2b_variant_tag(int form, int dma_phase) {
+    return form >= 1 && form <= 3 && dma_phase >= 0 && dma_phase <= 2 ? kB2bTags.tag[form - 1][dma_phase] : "b2b?";
+}
+
 // f(std::integral_constant<int, I>) for the row I of [I, End) that holds configuration `cfg`, `none` without one: how a launcher turns
 // the run-time number into the row's template arguments
 template <int I, int End, class R, class F>

@@ -34,6 +34,18 @@ hipError_t ktrace_read(unsigned long long* out) {  // the buffer of the mode tha
 
 const char* conv_igemm_config_name(int cfg, ConvMode mode) { return conv_form_name(cfg, mode, !conv_hl_pipe_on()); }
 
+const char* conv_variant_name(const ConvArgs& a, ConvMode mode, int cfg, int out_f32) {
+    const ConvForm* f = conv_form(cfg, mode);
+    if (!f || !conv_igemm_config_valid(a, cfg, mode, out_f32)) return "";
+    switch (f->family) {
+        case kFamAreg: return mode == kModeI8 ? "" : conv1x1_areg_variant(a);
+        case kFamAregNsplit: return conv1x1_q8_variant(a);
+        case kFamHalo: return conv3x3_halo_variant(a, mode, f->bn);
+        case kFamHalo4: return conv3x3_halo4_variant(a);
+        default: return "";
+    }
+}
+
 // the configuration of a shape nobody has measured (pick_cfg without a tuning entry)
 ConvCfg conv_igemm_default_config(const ConvArgs& a) {
     if (a.Cout >= 128) return kCfg128x128;

@@ -604,6 +604,7 @@ int32_t run_conv(infur_ctx* c, const ConvLayer& L, const Tensor& in, const Tenso
         const double direct = 2.0 * oh * ow * (double)L.cout * L.cin * 9.0;
         {
             ProfScope ps(c, L.name + "/in", hl ? "wino_input_hl" : "wino_input", 0, (double)in.elems() * es + (double)V.elems() * es, 0.0);
+            if (!hl) ps.r.variant = wino_variant(in.c, mt);
             if (hl) HIPCHK(c, launch_wino_input_hl(in.p, in.lo, in.h, in.w, in.c, L.dil, mt, split_wino_scale(mt), V.p, V.lo, c->d_hlmon, c->stream));
             else HIPCHK(c, launch_wino_input((const float*)in.p, in.h, in.w, in.c, L.dil, mt, (float*)V.p, c->d_range ? c->d_range + 1 : nullptr, c->stream));
         }
@@ -623,6 +624,7 @@ int32_t run_conv(infur_ctx* c, const ConvLayer& L, const Tensor& in, const Tenso
         pool_release(c, V);
         {
             ProfScope ps(c, L.name + "/out", hl ? "wino_output_hl" : "wino_output", 0, (double)M.bytes() + (double)out->elems() * es, 0.0);
+            if (!hl) ps.r.variant = wino_variant(L.cout, mt);
             if (hl) HIPCHK(c, launch_wino_output_hl((const float*)M.p, oh, ow, L.cout, L.dil, mt, L.d_b, L.relu ? 1 : 0, out->p, out->lo, c->d_hlmon, c->stream));
             else HIPCHK(c, launch_wino_output((const float*)M.p, oh, ow, L.cout, L.dil, mt, L.d_b, L.relu ? 1 : 0, (float*)out->p,
                                               L.role == 'c' ? nullptr : c->d_range, c->stream));
@@ -746,6 +748,7 @@ int32_t run_b2b(infur_ctx* c, const ConvLayer& c3, const ConvLayer& n1, const Te
     {
         ProfScope ps(c, c3.name + "+next.conv1", "conv1x1_b2b_f16", 2.0 * M * c3.cout * c3.cin * 2.0,
                      (double)t2.bytes() + (double)x.bytes() + (double)y->bytes() + (double)t1n->bytes() + 2.0 * c3.cout * c3.cin * 2.0);
+        ps.r.variant = conv1x1_b2b_variant(b);
         HIPCHK(c, launch_conv1x1_b2b(b, c->stream));
     }
     if (c->opt.keep_activations) {
@@ -800,6 +803,7 @@ int32_t forward(infur_ctx* c, const uint8_t* d_bgr, int w, int h) {
         if (ctx_mode(c) == kModeSplit || ctx_hl(c)) RETIF(stem16_image(c, (const float*)stem.d_w, stem.w_scale, 1, &wimg));
         ProfScope ps(c, "backbone.conv1+maxpool", "stem_pool", 2.0 * sh * sw * 64 * 147, (double)h * w * 3 + (double)x.bytes(),
                      2.0 * sh * sw * 64 * 147);
+        ps.r.variant = stem_pool_variant(ctx_mode(c));
         // exact f32 MFMA in the f32 mode; in the f16-rate modes the stem runs on the f16 matrix cores as the conv stack does
         HIPCHK(c, launch_stem_pool(d_bgr, h, w, (const float*)stem.d_w, wimg, stem.d_b, stem_lut(c), x.p, ctx_mode(c), sh, sw, ph, pw,
                                    kSplitActScale, stem.w_scale, ctx_hl(c) ? c->d_hlmon : c->d_range, c->stream));  // (mode 5: hi / lo planes, x.lo = x.p + hl_lo_offset)
@@ -1816,6 +1820,16 @@ int32_t infur_profile_get(infur_ctx* c, uint32_t i, infur_kernel_record* rec) {
         rec->flops = r.flops;
         rec->bytes = r.bytes;
         rec->algo_flops = r.algo_flops;
+        return INFUR_OK;
+    });
+}
+
+int32_t infur_debug_profile_variant(infur_ctx* c, uint32_t i, char* buf, size_t cap) {
+    return abi_call(c, [&]() -> int32_t {
+        if (!c || !buf || !cap || i >= c->prof.size()) return INFUR_E_INVALID_ARG;
+        const char* v = c->prof[i].variant ? c->prof[i].variant : "";
+        if (strlen(v) >= cap) return fail(c, INFUR_E_CAPACITY, "variant tag needs %zu bytes", strlen(v) + 1);
+        memcpy(buf, v, strlen(v) + 1);
         return INFUR_OK;
     });
 }

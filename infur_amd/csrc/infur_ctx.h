@@ -91,6 +91,7 @@ struct QAddParams {  // com.microsoft QLinearAdd of one bottleneck: C = A (conv3
 struct ProfRec {
     std::string name;
     const char* kernel;
+    const char* variant = "";  // the sub-form that ran (conv_forms.h: kVariantWords); a static string, never null
     double flops, bytes, algo_flops;
     hipEvent_t e0, e1;
 };

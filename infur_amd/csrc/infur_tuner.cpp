@@ -83,6 +83,7 @@ int32_t run_tuned(infur_ctx* c, const std::string& layer, const ConvArgs& a, Con
     int cfg = -1;
     RETIF(pick_cfg(c, a, mode, out_f32, &cfg));
     ProfScope ps(c, layer, conv_igemm_config_name(cfg, mode), flops, bytes, algo_flops);
+    if (ps.on) ps.r.variant = conv_variant_name(a, mode, cfg, out_f32);
     HIPCHK(c, launch_conv_igemm(a, mode, out_f32, cfg, c->stream));
     return INFUR_OK;
 }

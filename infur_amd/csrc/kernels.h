@@ -73,6 +73,10 @@ hipError_t launch_conv_igemm(const ConvArgs& a, ConvMode mode, int out_f32, int 
 ConvCfg conv_igemm_default_config(const ConvArgs& a);  // the configuration of a shape nobody has measured
 bool conv_igemm_config_valid(const ConvArgs& a, int cfg, ConvMode mode, int out_f32);
 const char* conv_igemm_config_name(int cfg, ConvMode mode);
+// The sub-form of configuration `cfg` that launch_conv_igemm runs for this launch, as a short static tag of conv_forms.h's
+// kVariantWords ("bm256", "nsplit4", "bn128,mixed,na2"); "" where the configuration has one form.  Evaluates the launchers' own
+// selectors (size rules of conv_forms.h and their environment hooks), so it says what runs, whatever the reason.
+const char* conv_variant_name(const ConvArgs& a, ConvMode mode, int cfg, int out_f32);
 
 // mode 5 (conv_hl.hip)
 bool conv_hl_config_valid(const ConvArgs& a, const ConvForm& f, int out_f32);  // f: a kFamHL / kFamHLAreg row
@@ -90,10 +94,12 @@ hipError_t launch_hl_pack_weights_planes(const float* w, size_t rows, size_t col
 // while the workgroup walks all N tiles (conv1x1_areg.hip).  Reached through launch_conv_igemm as one more configuration.
 bool conv1x1_areg_valid(const ConvArgs& a, int mode, int out_f32);
 hipError_t launch_conv1x1_areg(const ConvArgs& a, hipStream_t s);
+const char* conv1x1_areg_variant(const ConvArgs& a);  // "bm128" / "bm256": the workgroup's pixels
 // quantised models (mode 4, u8 output): activation tile in registers, 16 consecutive channels per lane straight from the
 // accumulators (conv1x1_q8.hip): kCfgAreg in that mode
 bool conv1x1_q8_valid(const ConvArgs& a, int mode, int out_f32);
 hipError_t launch_conv1x1_q8(const ConvArgs& a, int nsplit, hipStream_t s);
+const char* conv1x1_q8_variant(const ConvArgs& a);  // "nsplit<conv1x1_q8_nsplit>"
 int conv1x1_q8_nsplit(const ConvArgs& a);  // kCfgAregNsplit: N tiles shared out over this many workgroups per M tile (0: not a candidate)
 
 // stride-1 3x3 convolutions (pad = dilation 1 / 2 / 4), f16 operands and output, no residual: the input patch of a 16 x 16 output
@@ -105,6 +111,9 @@ hipError_t launch_conv3x3_halo_q(const ConvArgs& a, int bn, hipStream_t s);
 // the 4-wave form (kCfgHalo4): BN = 256, one wave per SIMD with a 128 x 128 wave tile, dilation 1 / 2
 bool conv3x3_halo4_valid(const ConvArgs& a, int mode, int out_f32);
 hipError_t launch_conv3x3_halo4(const ConvArgs& a, hipStream_t s);
+// N tile, tiling of the map and patch images of a launch the functions above take ("bn64,16x16,na1"); mode: 1 or 4
+const char* conv3x3_halo_variant(const ConvArgs& a, int mode, int bn);
+const char* conv3x3_halo4_variant(const ConvArgs& a);
 
 // Two 1x1 convolutions back to back on the same pixels, f16 (conv1x1_b2b.hip): y = ReLU(w3 * in + b3 + res) -- a
 // bottleneck's conv3 + residual -- is written once and immediately multiplied by the NEXT bottleneck's conv1 weights:
@@ -125,6 +134,7 @@ bool conv1x1_b2b_valid(const B2bArgs& a);
 // one-off at model load: the conv3 weight matrix ([4*C2][C2] f16, plain row order) in the row order the kernel streams
 hipError_t launch_b2b_pack_w3(const void* w3, void* w3i, int C2, hipStream_t s);
 hipError_t launch_conv1x1_b2b(const B2bArgs& a, hipStream_t s);
+const char* conv1x1_b2b_variant(const B2bArgs& a);  // workgroup form and DMA phase ("form3,dma2")
 
 // Winograd F(mt x mt, 3x3), mt = 2 or 4, for stride-1 3x3 convs (f32, any dilation d with pad = d);
 // (mt+2)^2 transform planes; see winograd.hip
@@ -134,6 +144,8 @@ hipError_t launch_wino_input(const float* in, int H, int W, int C, int d, int mt
 hipError_t launch_wino_output(const float* M, int H, int W, int Cout, int d, int mt, const float* bias, int relu,
                               float* out, unsigned* amax, hipStream_t s);
 hipError_t launch_wino_weights(const float* w_oihw, int O, int I, int mt, float* U, hipStream_t s);
+// the form of launch_wino_input (C = Cin) / launch_wino_output (C = Cout): "lds", "f32x1", "f32x2", "f32x4w"
+const char* wino_variant(int C, int mt);
 // the same transforms on three-byte tensors (mode 5; C, Cout % 128 == 0): input hi / lo planes -> V * v_scale as hi / lo planes
 // [(mt+2)^2][T][C]; f32 M -> the conv's output as hi / lo planes.  hl_mon (optional): the range monitor's words (hl_format.h), the
 // monitored form of the kernel -- max |V * v_scale| to [kHlMonWino], max |out| to [kHlMonAct]
@@ -170,6 +182,7 @@ size_t stem16_image_bytes();
 hipError_t launch_stem16_pack(const float* wt, float w_scale, int split, void* img, hipStream_t s);
 hipError_t launch_stem_pool(const uint8_t* bgr, int H, int W, const float* wt, const void* wimg, const float* bias, const float* lut, void* out,
                             int mode, int SH, int SW, int PH, int PW, float a_scale, float w_scale, unsigned* amax, hipStream_t s);
+const char* stem_pool_variant(int mode);  // "f16stem" / "f32stem" (INFUR_STEM_F32=1: the f32 MFMA stem in modes 1 and 2 as well)
 
 // maxpool 3x3 stride 2 pad 1, NHWC f32 / f16 (C % 4 == 0)
 hipError_t launch_maxpool3x3s2(const void* in, int H, int W, int C, void* out, int f16, int OH, int OW,

@@ -579,12 +579,20 @@ hipError_t launch_stem_pool_q(const uint8_t* bgr, int H, int W, const void* wimg
     return hipGetLastError();
 }
 
+// INFUR_STEM_F32=1 (measurement and test hook): the f32 MFMA stem in every mode but the three-byte one
+static int stem_exact() {
+    static const int exact = getenv("INFUR_STEM_F32") ? atoi(getenv("INFUR_STEM_F32")) : 0;
+    return exact;
+}
+// the arithmetic launch_stem_pool runs in `mode`: the f16 MFMA (modes 2 and 5: on f16 hi + lo pairs) or the exact f32 MFMA
+const char* stem_pool_variant(int mode) { return (mode == 5 || ((mode == 1 || mode == 2) && !stem_exact())) ? "f16stem" : "f32stem"; }
+
 // (wimg: the f16-rate modes' weight image, launch_stem16_pack -- nullptr only where the f32 MFMA stem runs)
 hipError_t launch_stem_pool(const uint8_t* bgr, int H, int W, const float* wt, const void* wimg, const float* bias, const float* lut, void* out,
                             int mode, int SH, int SW, int PH, int PW, float a_scale, float w_scale, unsigned* amax, hipStream_t s) {
     dim3 grid((PW + SP_PC - 1) / SP_PC, (PH + SP_PR - 1) / SP_PR);
     static const int abl = getenv("INFUR_STEM_ABL") ? atoi(getenv("INFUR_STEM_ABL")) : 0;
-    static const int exact = getenv("INFUR_STEM_F32") ? atoi(getenv("INFUR_STEM_F32")) : 0;  // measurement hook: f32 MFMA stem in every mode
+    const int exact = stem_exact();
     if ((mode == 1 || mode == 2 || mode == 5) && !(exact && mode != 5) && !wimg) return hipErrorInvalidValue;
     if (mode == 1 && !exact)
         hipLaunchKernelGGL((stem_pool16_kernel<_Float16, false>), grid, dim3(256), 0, s, bgr, H, W, wt, bias, lut, (_Float16*)out, SH, SW, PH,

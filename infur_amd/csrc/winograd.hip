@@ -248,7 +248,9 @@ __global__ void __launch_bounds__(256)
 // 128 channels), runs the column pass and parks its 8 results in LDS; after one barrier thread (a, cv) reads row a back,
 // runs the row pass and stores 8 x 16 bytes.  8 vectors per lane instead of 64 (~50 VGPRs: 5 workgroups per CU), every
 // global access 16 bytes and 512-byte contiguous per 32 lanes.  Same 1-D functions on the same values in the same order:
-// bit-identical to the per-thread forms (tests/test_gpu_parity.py runs both).
+// bit-identical to the per-thread f32x2 form (tests/test_gpu_subforms.py runs both on the same data, INFUR_WINO_LDS=0).  The 4-byte
+// form (f32x1, INFUR_WINO_VEC=1) is NOT: this file is built with contraction allowed, and the compiler fuses other products of the
+// scalar expressions than of the vector ones -- f32-grade, graded against the float64 reference there.
 constexpr int WL_CV = 32;  // float4 channel vectors per unit = 128 channels
 
 template <int MT>
@@ -570,25 +572,43 @@ static bool wino_lds(int C, int mt) {
 }
 static unsigned grid_units(size_t units) { return (unsigned)(units < 256 * 40 ? units : 256 * 40); }
 
+// the form of the transforms for C channels (launch_wino_input: Cin, launch_wino_output: Cout): ONE selector for the launchers and
+// for the profile's variant tag
+enum WinoForm { kWinoLds, kWino6x1, kWino6x2, kWino2x4, kWino2x2, kWino4x4, kWino4x2 };
+static WinoForm wino_form(int C, int mt) {
+    if (wino_lds(C, mt)) return kWinoLds;
+    if (mt == 6) return wino_forced() == 1 ? kWino6x1 : kWino6x2;  // F(6x6): 64 patch vectors per thread -- 8-byte vectors keep them in registers
+    if (mt == 2) return wino_vec4(C) ? kWino2x4 : kWino2x2;
+    return wino_vec4(C) ? kWino4x4 : kWino4x2;
+}
+const char* wino_variant(int C, int mt) {
+    switch (wino_form(C, mt)) {
+        case kWinoLds: return "lds";
+        case kWino6x1: return "f32x1";
+        case kWino2x4:
+        case kWino4x4: return "f32x4w";
+        default: return "f32x2";
+    }
+}
+
 hipError_t launch_wino_input(const float* in, int H, int W, int C, int d, int mt, float* V, unsigned* amax, hipStream_t s) {
     const WinoGeom g = geom(H, W, d, mt);
     const int T = d * d * g.TY * g.TX;
-    const bool v4 = wino_vec4(C) && mt != 6;  // F(6x6): 64 patch vectors per thread -- 8-byte vectors keep them in registers
+    const bool v4 = wino_vec4(C) && mt != 6;
     const unsigned blocks = grid_for((size_t)T * (C / (v4 ? 4 : 2)));
-    if (wino_lds(C, mt))
-        hipLaunchKernelGGL(wino_input_lds_kernel<6>, dim3(grid_units((size_t)T * (C / (4 * WL_CV)))), dim3(256), 0, s, in, g, C, T, V, amax);
-    else if (mt == 6 && wino_forced() == 1)
-        hipLaunchKernelGGL((wino_input_kernel<6, f32x1>), dim3(grid_for((size_t)T * C)), dim3(256), 0, s, in, g, C, T, V, amax);
-    else if (mt == 6)
-        hipLaunchKernelGGL((wino_input_kernel<6, f32x2>), dim3(blocks), dim3(256), 0, s, in, g, C, T, V, amax);
-    else if (mt == 2 && v4)
-        hipLaunchKernelGGL((wino_input_kernel<2, f32x4w>), dim3(blocks), dim3(256), 0, s, in, g, C, T, V, amax);
-    else if (mt == 2)
-        hipLaunchKernelGGL((wino_input_kernel<2, f32x2>), dim3(blocks), dim3(256), 0, s, in, g, C, T, V, amax);
-    else if (v4)
-        hipLaunchKernelGGL((wino_input_kernel<4, f32x4w>), dim3(blocks), dim3(256), 0, s, in, g, C, T, V, amax);
-    else
-        hipLaunchKernelGGL((wino_input_kernel<4, f32x2>), dim3(blocks), dim3(256), 0, s, in, g, C, T, V, amax);
+    switch (wino_form(C, mt)) {
+        case kWinoLds:
+            hipLaunchKernelGGL(wino_input_lds_kernel<6>, dim3(grid_units((size_t)T * (C / (4 * WL_CV)))), dim3(256), 0, s, in, g, C, T, V, amax);
+            break;
+        case kWino6x1:
+            hipLaunchKernelGGL((wino_input_kernel<6, f32x1>), dim3(grid_for((size_t)T * C)), dim3(256), 0, s, in, g, C, T, V, amax);
+            break;
+        case kWino6x2: hipLaunchKernelGGL((wino_input_kernel<6, f32x2>), dim3(blocks), dim3(256), 0, s, in, g, C, T, V, amax); break;
+        case kWino2x4: hipLaunchKernelGGL((wino_input_kernel<2, f32x4w>), dim3(blocks), dim3(256), 0, s, in, g, C, T, V, amax); break;
+        case kWino2x2: hipLaunchKernelGGL((wino_input_kernel<2, f32x2>), dim3(blocks), dim3(256), 0, s, in, g, C, T, V, amax); break;
+        case kWino4x4: hipLaunchKernelGGL((wino_input_kernel<4, f32x4w>), dim3(blocks), dim3(256), 0, s, in, g, C, T, V, amax); break;
+        case kWino4x2: hipLaunchKernelGGL((wino_input_kernel<4, f32x2>), dim3(blocks), dim3(256), 0, s, in, g, C, T, V, amax); break;
+    }
     return hipGetLastError();
 }
 
@@ -598,20 +618,19 @@ hipError_t launch_wino_output(const float* M, int H, int W, int Cout, int d, int
     const int T = d * d * g.TY * g.TX;
     const bool v4 = wino_vec4(Cout) && mt != 6;
     const unsigned blocks = grid_for((size_t)T * (Cout / (v4 ? 4 : 2)));
-    if (wino_lds(Cout, mt))
-        hipLaunchKernelGGL(wino_output_lds_kernel<6>, dim3(grid_units((size_t)T * (Cout / (4 * WL_CV)))), dim3(256), 0, s, M, g, Cout, T, bias, relu, out, amax);
-    else if (mt == 6 && wino_forced() == 1)
-        hipLaunchKernelGGL((wino_output_kernel<6, f32x1>), dim3(grid_for((size_t)T * Cout)), dim3(256), 0, s, M, g, Cout, T, bias, relu, out, amax);
-    else if (mt == 6)
-        hipLaunchKernelGGL((wino_output_kernel<6, f32x2>), dim3(blocks), dim3(256), 0, s, M, g, Cout, T, bias, relu, out, amax);
-    else if (mt == 2 && v4)
-        hipLaunchKernelGGL((wino_output_kernel<2, f32x4w>), dim3(blocks), dim3(256), 0, s, M, g, Cout, T, bias, relu, out, amax);
-    else if (mt == 2)
-        hipLaunchKernelGGL((wino_output_kernel<2, f32x2>), dim3(blocks), dim3(256), 0, s, M, g, Cout, T, bias, relu, out, amax);
-    else if (v4)
-        hipLaunchKernelGGL((wino_output_kernel<4, f32x4w>), dim3(blocks), dim3(256), 0, s, M, g, Cout, T, bias, relu, out, amax);
-    else
-        hipLaunchKernelGGL((wino_output_kernel<4, f32x2>), dim3(blocks), dim3(256), 0, s, M, g, Cout, T, bias, relu, out, amax);
+    switch (wino_form(Cout, mt)) {
+        case kWinoLds:
+            hipLaunchKernelGGL(wino_output_lds_kernel<6>, dim3(grid_units((size_t)T * (Cout / (4 * WL_CV)))), dim3(256), 0, s, M, g, Cout, T, bias, relu, out, amax);
+            break;
+        case kWino6x1:
+            hipLaunchKernelGGL((wino_output_kernel<6, f32x1>), dim3(grid_for((size_t)T * Cout)), dim3(256), 0, s, M, g, Cout, T, bias, relu, out, amax);
+            break;
+        case kWino6x2: hipLaunchKernelGGL((wino_output_kernel<6, f32x2>), dim3(blocks), dim3(256), 0, s, M, g, Cout, T, bias, relu, out, amax); break;
+        case kWino2x4: hipLaunchKernelGGL((wino_output_kernel<2, f32x4w>), dim3(blocks), dim3(256), 0, s, M, g, Cout, T, bias, relu, out, amax); break;
+        case kWino2x2: hipLaunchKernelGGL((wino_output_kernel<2, f32x2>), dim3(blocks), dim3(256), 0, s, M, g, Cout, T, bias, relu, out, amax); break;
+        case kWino4x4: hipLaunchKernelGGL((wino_output_kernel<4, f32x4w>), dim3(blocks), dim3(256), 0, s, M, g, Cout, T, bias, relu, out, amax); break;
+        case kWino4x2: hipLaunchKernelGGL((wino_output_kernel<4, f32x2>), dim3(blocks), dim3(256), 0, s, M, g, Cout, T, bias, relu, out, amax); break;
+    }
     return hipGetLastError();
 }
 

@@ -198,10 +198,13 @@ class Context:
         self.check(self.L.infur_profile_count(self.h, C.byref(n)))
         out = []
         rec = _lib.KernelRecord()
+        variant = C.create_string_buffer(32)
         for i in range(n.value):
             self.check(self.L.infur_profile_get(self.h, i, C.byref(rec)))
+            self.check(self.L.infur_debug_profile_variant(self.h, i, variant, len(variant)))
             out.append({"name": rec.name.decode(), "kernel": rec.kernel.decode(), "ms": rec.ms,
-                        "flops": rec.flops, "bytes": rec.bytes, "algo_flops": rec.algo_flops})
+                        "flops": rec.flops, "bytes": rec.bytes, "algo_flops": rec.algo_flops,
+                        "variant": variant.value.decode()})  # the size-picked kernel inside the configuration ("" = one form)
         return out
 
     def close(self):

@@ -280,6 +280,7 @@ extern "C" {
     pub fn infur_profile_enable(c: *mut infur_ctx, on: u32) -> i32;
     pub fn infur_profile_count(c: *mut infur_ctx, n: *mut u32) -> i32;
     pub fn infur_profile_get(c: *mut infur_ctx, i: u32, rec: *mut infur_kernel_record) -> i32;
+    pub fn infur_debug_profile_variant(c: *mut infur_ctx, i: u32, buf: *mut c_char, cap: usize) -> i32;
     pub fn infur_dev_alloc(c: *mut infur_ctx, bytes: usize, d_ptr: *mut *mut c_void) -> i32;
     pub fn infur_dev_free(c: *mut infur_ctx, d_ptr: *mut c_void) -> i32;
     pub fn infur_memcpy_h2d(c: *mut infur_ctx, d_dst: *mut c_void, src: *const c_void, bytes: usize) -> i32;

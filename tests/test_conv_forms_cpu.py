@@ -1,7 +1,12 @@
 """The table of conv forms the library is built from (infur_amd/csrc/conv_forms.h), printed by tests/cpp/conv_forms_test.cpp, against
 the hand-written restatements the GPU tests are driven by: tests/forms.py (names and index sets per mode) and
 tests/test_tune_db_cpu.py (the three-byte mode's forms and N tiles).  The program is plain g++ -- the header includes no HIP -- and
-runs a second time built with the address and undefined-behaviour sanitizers."""
+runs a second time built with the address and undefined-behaviour sanitizers.
+
+The same program prints the SUB-forms: the size rules by which a launcher picks a kernel inside one configuration (conv_forms.h:
+areg_small_rule, b2b_form_rule, halo_bn_rule, q8_nsplit_rule) at the values the sources' comments state and at each threshold +- 1,
+and every word a profile record's variant tag can hold (kVariantWords).  tests/forms.py: SUBFORM_CASES, the cases of
+tests/test_gpu_subforms.py, must name every one of those words: a new sub-form without a case fails here."""
 import os
 import subprocess
 import sys
@@ -46,6 +51,8 @@ def table(printed):
     rows, names = {}, {}
     for ln in printed.splitlines():
         p = ln.split()
+        if p[0] in ("R", "V", "T"):  # the sub-forms: `subforms`
+            continue
         if p[0] == "#":  # no form: the name the library would still report
             names[(int(p[1]), int(p[2]))] = (p[3], p[4])
             continue
@@ -110,3 +117,101 @@ def test_tune_db_tests_restate_the_three_byte_rows(table):
     hl = {k: r for (m, k), r in rows.items() if m == MODE_NO["f16hl"]}
     assert set(hl) == T.HL_FORMS
     assert {k: r["bn"] for k, r in hl.items() if k != F.HL_AREG} == T.HL_BN
+
+
+# ---- the sub-forms inside a configuration ---------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def subforms(printed):
+    """rules: (rule, arguments...) -> value; words: the variant words; tags: the composed tags"""
+    rules, words, tags = {}, [], []
+    for ln in printed.splitlines():
+        p = ln.split()
+        if p[0] == "R":
+            rules[(p[1],) + tuple(int(x) for x in p[2:-1])] = int(p[-1])
+        elif p[0] == "V":
+            words.append(p[1])
+        elif p[0] == "T":
+            tags.append(p[1])
+    return rules, words, tags
+
+
+def conv_out(n, k, stride, pad):
+    return (n + 2 * pad - k) // stride + 1
+
+
+def maps(h, w):
+    """the stride-4 map (stem + max-pool) and the stride-8 map (layer2; layer3, layer4 and the heads are dilated) of an h x w frame"""
+    s4 = tuple(conv_out(conv_out(n, 7, 2, 3), 3, 2, 1) for n in (h, w))
+    return s4, tuple(conv_out(n, 3, 2, 1) for n in s4)
+
+
+def test_size_rules_at_the_values_the_sources_state(subforms):
+    rules, _, _ = subforms
+    # conv1x1_areg.hip / conv1x1_b2b.hip: more than 170 workgroups of 256 pixels
+    for m, small in ((1, 1), (104, 1), (4096, 1), (34 * 61, 1), (43519, 1), (43520, 1), (43521, 0), (135 * 240, 1), (270 * 480, 0)):
+        assert rules[("areg_small", m)] == small, m
+        assert rules[("b2b_form", m)] == (3 if small else 1), m
+    # conv3x3_halo.hip: "layer2 conv2 at 1080p: 128 tiles x ONE N tile" runs BN = 64; Cout 256 on the same map BN = 128
+    assert rules[("halo_bn", 135, 240, 128)] == 64 and rules[("halo_bn", 135, 240, 256)] == 128 and rules[("halo_bn", 135, 240, 512)] == 128
+    for hw in ((1, 1), (17, 31), (34, 61)):  # the maps of forms.SIZES: always the small side
+        assert all(rules[("halo_bn",) + hw + (c,)] == 64 for c in (64, 128, 256, 512)), hw
+    assert all(rules[("halo_bn", h, w, 64)] == 64 for h, w in ((98, 113), (195, 225), (135, 240)))
+    # conv1x1_q8.hip: "M = 32400 alone gives 254 workgroups": split 2; 480 workgroups = two per CU
+    assert rules[("q8_nsplit", 32400, 2048)] == 2
+    assert [rules[("q8_nsplit", 1, c)] for c in (128, 256, 512, 1024, 2048)] == [0, 2, 4, 8, 16]
+    assert [rules[("q8_nsplit", 17 * 31, c)] for c in (128, 256, 512, 1024, 2048)] == [0, 2, 4, 8, 16]
+    assert rules[("q8_nsplit", 30592, 2048)] == 4 and rules[("q8_nsplit", 30593, 2048)] == 2  # 239 / 240 M tiles of 128 pixels
+    assert rules[("q8_nsplit", 61312, 2048)] == 2 and rules[("q8_nsplit", 61313, 2048)] == 0  # 479 / 480
+    assert all(rules[("q8_nsplit", m, 128)] == 0 for m in (1, 32400, 61313))  # a single N tile
+
+
+def test_the_natural_size_flips_both_f16_rules(subforms):
+    """forms.NATURAL_SIZES: the figures its comment states, through the library's own rules"""
+    rules, _, _ = subforms
+    assert F.NATURAL_SIZES == [(777, 897)]
+    s4, s8 = maps(777, 897)
+    assert s4 == (195, 225) and s8 == (98, 113)
+    assert rules[("areg_small", s4[0] * s4[1])] == 0 and rules[("areg_small", s8[0] * s8[1])] == 1  # 172 tiles of 256 pixels; 44
+    assert -(-s4[0] * s4[1] // 256) == 172 and -(-s8[0] // 16) * -(-s8[1] // 16) == 56
+    assert rules[("halo_bn",) + s8 + (512,)] == 128 and rules[("halo_bn",) + s8 + (256,)] == 64 and rules[("halo_bn",) + s8 + (128,)] == 64
+    assert rules[("halo_bn",) + s4 + (64,)] == 64
+    # ragged against every tile
+    assert all((s[0] * s[1]) % t for s in (s4, s8) for t in (64, 128, 256)) and all(n % 16 and n % 8 and n % 6 for n in s4 + s8)
+    # the sizes of forms.SIZES stay on the small side of both rules, which is why this size exists
+    for h, w in F.SIZES:
+        for m in maps(h, w):
+            assert rules.get(("areg_small", m[0] * m[1]), 1) == 1
+    assert maps(135, 241) == ((34, 61), (17, 31)) and maps(64, 256) == ((16, 64), (8, 32))
+
+
+def test_subform_cases_name_every_variant_word(subforms):
+    """a word the library can put into a variant tag and no case of tests/test_gpu_subforms.py must see: a sub-form nobody forces"""
+    _, words, tags = subforms
+    assert len(words) == len(set(words)) >= 26
+    covered = set().union(*(c.words() for c in F.SUBFORM_CASES))
+    assert not set(words) - covered, f"variant words without a case in forms.SUBFORM_CASES: {sorted(set(words) - covered)}"
+    assert not covered - set(words), f"forms.SUBFORM_CASES expects words the library never says: {sorted(covered - set(words))}"
+    for c in F.SUBFORM_CASES:
+        assert not set(c.never) - set(words) and not set(c.never) & c.words(), c.id
+    # every composed tag is made of the words (the N split of a Cout that is no power of two times 128 is a number like the others)
+    for t in tags:
+        for w in t.split(","):
+            assert w in words or (w.startswith("nsplit") and w[6:].isdigit() and 2 <= int(w[6:]) <= 16), t
+        assert len(t) < 24
+    # each case has its baseline, each baseline is a case, ids are unique, hooks are the ones run_child clears
+    ids = [c.id for c in F.SUBFORM_CASES]
+    assert len(set(ids)) == len(ids)
+    for c in F.SUBFORM_CASES:
+        assert F.subform_baseline(c).key == c.key and set(c.env) <= set(F.SUBFORM_HOOKS) and c.sizes in F.SIZE_SETS, c.id
+        assert c.mode in F.MODES and c.cfg in F.FORMS[c.mode] and c.tile in (0, 2, 4, 6)
+    # the forced cases the sub-forms were found by
+    have = {(c.mode, c.cfg, tuple(sorted(c.env.items())), c.tile, c.sizes) for c in F.SUBFORM_CASES}
+    for want in [("f16", 15, (("INFUR_AREG_BM", "256"),), 0, "edge"), ("i8", 18, (("INFUR_Q8_NSPLIT", "2"),), 0, "edge"),
+                 ("i8", 18, (("INFUR_Q8_NSPLIT", "4"),), 0, "edge"), ("i8", 18, (("INFUR_Q8_NSPLIT", "8"),), 0, "edge"),
+                 ("f16", 19, (("INFUR_HALO_BN", "128"),), 0, "edge"), ("f32", 0, (("INFUR_WINO_LDS", "0"),), 0, "edge"),
+                 ("f32", 0, (("INFUR_WINO_VEC", "1"),), 0, "edge"), ("f32", 0, (("INFUR_WINO_VEC", "2"),), 2, "edge"),
+                 ("f32", 0, (("INFUR_WINO_VEC", "2"),), 4, "edge"), ("f32", 0, (("INFUR_WINO_VEC", "2"),), 0, "edge"),
+                 ("f16", 0, (("INFUR_B2B", "1"), ("INFUR_B2B_DMA", "0")), 0, "edge"), ("f16", 0, (("INFUR_B2B", "1"), ("INFUR_B2B_DMA", "1")), 0, "edge"),
+                 ("f16", 0, (("INFUR_STEM_F32", "1"),), 0, "edge"), ("f32s", 0, (("INFUR_STEM_F32", "1"),), 0, "edge"),
+                 ("f16", 0, (), 0, "natural"), ("f16", 15, (), 0, "natural"), ("f16", 19, (), 0, "natural")]:
+        assert want in have, want

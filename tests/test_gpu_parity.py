@@ -136,6 +136,81 @@ def test_pack_normalize_all_bytes(ctx, tables):
 
 
 # --------------------------------------------------------------------------- #
+# device pointers need only the natural alignment of their element type (include/infur_hip.h): pack_normalize and bgr_to_rgba take
+# their vector path (dword loads, 16-byte stores) only for 16-byte aligned pointers and whole quads of pixels, and the scalar path
+# otherwise -- which freshly allocated (256-byte aligned) buffers never reach when npix % 4 == 0
+# --------------------------------------------------------------------------- #
+POISON = 0xA5
+
+
+class GuardedDev:
+    """a device buffer of `n` bytes at byte offset `off` inside a poisoned allocation, 64 guard bytes behind it"""
+
+    def __init__(self, ctx, n, off, data=None):
+        self.ctx, self.n, self.off, self.total = ctx, n, off, off + n + 64
+        self.d = C.c_void_p(None)
+        ctx.check(ctx.L.infur_dev_alloc(ctx.h, self.total, C.byref(self.d)))
+        host = np.full(self.total, POISON, np.uint8)
+        if data is not None:
+            host[off:off + n] = np.ascontiguousarray(data).view(np.uint8).ravel()
+        ctx.check(ctx.L.infur_memcpy_h2d(ctx.h, self.d, host.ctypes.data, self.total))
+        self.ptr = C.c_void_p(self.d.value + off)
+
+    def read(self, what):
+        """the n bytes; the bytes before them and the guard behind them must still hold the poison"""
+        host = np.empty(self.total, np.uint8)
+        self.ctx.check(self.ctx.L.infur_memcpy_d2h(self.ctx.h, host.ctypes.data, self.d, self.total))
+        assert (host[:self.off] == POISON).all() and (host[self.off + self.n:] == POISON).all(), ("written outside the buffer", what)
+        return host[self.off:self.off + self.n].copy()
+
+    def free(self):
+        self.ctx.check(self.ctx.L.infur_dev_free(self.ctx.h, self.d))
+
+
+@pytest.mark.parametrize("wh", [(8, 4), (5, 3), (1, 1)])  # npix % 4 == 0 (the vector path when aligned), ragged, one pixel
+def test_pre_proc_and_display_at_unaligned_device_pointers(ctx, oracle, wh):
+    w, h = wh
+    fr = W.synth_frame(h, w, index=13)
+    ref_chw = oracle.pack_normalize(fr)
+    ref_rgba = np.concatenate([fr[..., ::-1], np.full((h, w, 1), 255, np.uint8)], axis=-1)  # app.rs:132-144: [r, g, b, 255]
+    for in_off in (0, 1, 2, 3):
+        d_in = GuardedDev(ctx, fr.nbytes, in_off, fr)
+        for out_off in (0, 4, 8, 12):
+            what = (wh, in_off, out_off)
+            d_chw = GuardedDev(ctx, ref_chw.nbytes, out_off)
+            ctx.check(ctx.L.infur_pack_normalize_dev(ctx.h, d_in.ptr, w, h, d_chw.ptr))
+            ctx.synchronize()
+            assert (d_chw.read(what).view(np.uint32) == ref_chw.view(np.uint32).ravel()).all(), what
+            d_chw.free()
+            d_rgba = GuardedDev(ctx, w * h * 4, out_off)
+            ctx.check(ctx.L.infur_bgr_to_rgba_dev(ctx.h, d_in.ptr, w, h, d_rgba.ptr))
+            ctx.synchronize()
+            assert (d_rgba.read(what) == ref_rgba.ravel()).all(), what
+            d_rgba.free()
+        assert (d_in.read((wh, in_off)) == fr.ravel()).all()
+        d_in.free()
+
+
+def test_frame_advance_dev_at_unaligned_frame_pointers(ctx, model):
+    """the stem reads the frame's bytes: a frame at byte offset 1, 2, 3 gives the aligned call's mask byte for byte"""
+    w = h = 8
+    fr = W.synth_frame(h, w, index=17)
+    masks = []
+    for in_off in (0, 1, 2, 3):
+        d_in, d_rgba = GuardedDev(ctx, fr.nbytes, in_off, fr), GuardedDev(ctx, w * h * 4, 0)
+        ow, oh = C.c_uint32(0), C.c_uint32(0)
+        ctx.check(ctx.L.infur_frame_advance_dev(ctx.h, d_in.ptr, w, h, 1.0, 0, d_rgba.ptr, w * h * 4, None, C.byref(ow), C.byref(oh)))
+        ctx.synchronize()
+        assert (ow.value, oh.value) == (w, h)
+        masks.append(d_rgba.read(in_off))
+        assert (d_in.read(in_off) == fr.ravel()).all()
+        d_in.free()
+        d_rgba.free()
+    ref, _ = FramePath(ctx).advance(fr, 1.0)
+    assert all((m == ref.ravel()).all() for m in masks)
+
+
+# --------------------------------------------------------------------------- #
 # ColorCode (decode_predict.rs:32-79)
 # --------------------------------------------------------------------------- #
 def test_colorcode_reference_kats(ctx, oracle, kats):

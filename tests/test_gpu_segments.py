@@ -297,6 +297,52 @@ def test_fused_outputs_stay_inside_their_buffers(ctx, model):
             ctx.check(L.infur_dev_free(h, d))
 
 
+@pytest.mark.parametrize("ow", [8, 12, 7])  # OW % 4 == 0: the fused kernel's dword row stores when the planes are dword-aligned
+def test_planes_at_unaligned_device_pointers(ctx, model, oracle, ow):
+    """include/infur_hip.h: a device pointer needs only the natural alignment of its element type -- a byte plane may start anywhere.
+    klass / conf at byte offsets 0..3 (each on its own, and both): the planes equal the oracle's, and the bytes before them and the
+    64 guard bytes behind every output still hold the poison"""
+    from test_gpu_parity import GuardedDev
+
+    L, h = ctx.L, ctx.h
+    k = model.get_info().num_classes
+    oh = 5
+    x = crafted(np.random.default_rng(ow), k, oh, ow)
+    kl, cf = oracle.argmax(x)
+    frame = W.synth_frame(oh, ow, index=3)
+    aligned = FramePath(ctx).advance_segments(frame, 1.0, RAW, want_rgba=True)
+    lo, _ = model.lowres()
+    fkl, fcf = oracle.argmax(oracle.upsample_bilinear(lo, oh, ow))
+    assert (aligned.klass == fkl).all() and (aligned.conf == fcf).all()
+    hw = oh * ow
+    d_x, d_bgr = GuardedDev(ctx, x.nbytes, 0, x), GuardedDev(ctx, frame.nbytes, 0, frame)
+    for k_off, c_off in ((1, 0), (2, 0), (3, 0), (0, 1), (0, 2), (0, 3), (1, 1), (2, 3), (3, 2)):
+        what = (ow, k_off, c_off)
+        # unfused
+        d_kl, d_cf, d_st, d_rgba = GuardedDev(ctx, hw, k_off), GuardedDev(ctx, hw, c_off), GuardedDev(ctx, k * 64, 0), GuardedDev(ctx, hw * 4, 0)
+        ctx.check(L.infur_segments_dev(h, d_x.ptr, k, oh, ow, RAW, d_kl.ptr, d_cf.ptr, d_st.ptr, d_rgba.ptr))
+        ctx.synchronize()
+        assert (d_kl.read(what) == kl.ravel()).all() and (d_cf.read(what) == cf.ravel()).all(), what
+        assert (d_st.read(what).view(np.uint64).reshape(k, 8) == R.stats(kl, cf, k)).all(), what
+        assert (d_rgba.read(what) == oracle.colorcode(x).ravel()).all(), what
+        for d in (d_kl, d_cf, d_st, d_rgba):
+            d.free()
+        # fused into the up-sampling kernel
+        d_kl, d_cf, d_st, d_rgba = GuardedDev(ctx, hw, k_off), GuardedDev(ctx, hw, c_off), GuardedDev(ctx, k * 64, 0), GuardedDev(ctx, hw * 4, 0)
+        rw, rh = C.c_uint32(0), C.c_uint32(0)
+        ctx.check(L.infur_frame_segments_dev(h, d_bgr.ptr, ow, oh, 1.0, 0, RAW, d_kl.ptr, d_cf.ptr, hw, d_st.ptr, k, d_rgba.ptr, hw * 4, None,
+                                             C.byref(rw), C.byref(rh)))
+        ctx.synchronize()
+        assert (rw.value, rh.value) == (ow, oh)
+        assert (d_kl.read(what) == fkl.ravel()).all() and (d_cf.read(what) == fcf.ravel()).all(), what
+        assert (d_st.read(what).view(np.uint64).reshape(k, 8) == R.stats(fkl, fcf, k)).all(), what
+        assert (d_rgba.read(what) == aligned.rgba.ravel()).all(), what
+        for d in (d_kl, d_cf, d_st, d_rgba):
+            d.free()
+    d_x.free()
+    d_bgr.free()
+
+
 # --------------------------------------------------------------------------- #
 # 4. fused == unfused (a self-comparison: the link to the oracle is tests 1-3)
 # --------------------------------------------------------------------------- #
