@@ -179,11 +179,12 @@ struct infur_ctx {
     // host-pointer calls' staging.  Private like the above.
     infur::Buf st_outl, st_outl_plane, st_outl_io;
     // Simplify (infur_simplify.cpp): the keep flags, ranks and scan sums, the host-pointer calls' staging, and what Outlines leaves
-    // for Simplify inside the polygon frame calls.  Private like the above.
+    // for Simplify or Coverage inside the polygon and coverage frame calls (egress_layout.h: PolyScratch; one call uses it at a
+    // time, in stream order).  Private like the above.
     infur::Buf st_simp, st_simp_io, st_poly;
-    // Coverage (infur_coverage.cpp): the junction bitmaps, augmented loops, arc table, keep flags, ranks and scan sums, the
-    // host-pointer calls' staging, and what Outlines leaves for Coverage inside the coverage frame calls.  Private like the above.
-    infur::Buf st_cov, st_cov_io, st_cov_poly;
+    // Coverage (infur_coverage.cpp): the junction bitmaps, augmented loops, arc table, keep flags, ranks and scan sums, and the
+    // host-pointer calls' staging.  Private like the above.
+    infur::Buf st_cov, st_cov_io;
     // Tracks (infur_tracks.cpp): the live trackers of this context; infur_ctx_destroy releases their device memory and orphans them
     std::vector<infur_tracker*> trackers;
 

@@ -1,14 +1,8 @@
 // infur_outlines.cpp -- Outlines, the polygon stage behind the four decodes (include/infur_hip.h): the boundaries of the regions
 // of a byte or u32 plane as closed loops of lattice vertices, so that a host copies out polygons and not the dense plane.
-// Kernels: outlines.hip.  Everything is enqueued on the context's stream.  Like infur_runs.cpp the frame path here always
-// enqueues eagerly, and every buffer of this file is private scratch no captured graph of the library can point into: growing
-// it leaves mem_gen -- and with it the graphs infur_frame_advance_dev has cached -- alone.
-#include <cstring>
-#include <new>
-
-#include "infur_ctx.h"
-#include "infur_rt.h"
-#include "kernels.h"
+// Kernels: outlines.hip.  Everything is enqueued on the context's stream; the layout, checks, read-back and frame wrapper it
+// shares with the other egress stages are infur_egress.h's, and so is the rule that its buffers are private scratch.
+#include "infur_egress.h"
 
 using namespace infur;
 
@@ -17,10 +11,7 @@ namespace {
 static_assert(kLoopWords == INFUR_LOOP_WORDS, "outlines.hip and the header disagree about the record");
 
 int32_t outlines_check(infur_ctx* c, uint32_t elem_bytes, uint32_t flags, uint32_t skip_value) {
-    if (elem_bytes != 1 && elem_bytes != 4) return fail(c, INFUR_E_INVALID_ARG, "elem_bytes %u: 1 or 4", elem_bytes);
-    if (flags & ~(uint32_t)(INFUR_OUTLINES_SKIP | INFUR_OUTLINES_CONN8)) return fail(c, INFUR_E_INVALID_ARG, "unknown outlines flags 0x%x", flags);
-    if (elem_bytes == 1 && skip_value > 255) return fail(c, INFUR_E_INVALID_ARG, "skip_value %u: a byte plane holds at most 255", skip_value);
-    return INFUR_OK;
+    return elem_check(c, elem_bytes, flags, INFUR_OUTLINES_SKIP | INFUR_OUTLINES_CONN8, "outlines", skip_value);
 }
 
 // an edge id is 4 * i + s in a u32, and 0xFFFFFFFF stands for none
@@ -29,39 +20,18 @@ int32_t outlines_plane_check(infur_ctx* c, uint32_t h, uint32_t w) {
     return INFUR_OK;
 }
 
-// the capacity in edges: 0 and anything above the worst case are the worst case
-size_t edge_capacity(size_t hw, uint32_t max_edges) { return max_edges && max_edges < hw * 4 ? max_edges : hw * 4; }
-
-// st_outl_io: [counts][statistics table k x 8 u64][loop records, at most one per pixel][vertices, at most four per pixel][plane],
-// on 256-byte boundaries
-struct OutlStage {
-    size_t loops_rows, vertex_rows, stats, loops, vertices, plane, bytes;
-    OutlStage(size_t npix, uint32_t loops_rows_, uint32_t vertex_rows_, uint32_t k, size_t plane_bytes) {
-        loops_rows = loops_rows_ < npix ? loops_rows_ : npix;
-        vertex_rows = vertex_rows_ < npix * 4 ? vertex_rows_ : npix * 4;
-        stats = 256;
-        loops = stats + align_up((size_t)k * INFUR_STAT_WORDS * 8, 256);
-        vertices = loops + align_up(loops_rows * INFUR_LOOP_WORDS * 4, 256);
-        plane = vertices + align_up(vertex_rows * 4, 256);
-        bytes = plane + align_up(plane_bytes, 256);
-    }
-};
-
-// the counts first: they decide how many records and vertices there are to copy
-int32_t outlines_read_back(infur_ctx* c, const uint8_t* base, const OutlStage& st, uint32_t* loops, uint32_t* vertices, uint32_t* counts) {
-    uint32_t n[3] = {0, 0, 0};
-    HIPCHK(c, hipMemcpyAsync(n, base, sizeof n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const size_t nl = n[0] < st.loops_rows ? n[0] : st.loops_rows, nv = n[1] < st.vertex_rows ? n[1] : st.vertex_rows;
-    if (loops && nl) HIPCHK(c, hipMemcpy(loops, base + st.loops, nl * INFUR_LOOP_WORDS * 4, hipMemcpyDeviceToHost));
-    if (vertices && nv) HIPCHK(c, hipMemcpy(vertices, base + st.vertices, nv * 4, hipMemcpyDeviceToHost));
-    if (counts) std::memcpy(counts, n, sizeof n);
-    return INFUR_OK;
-}
-
-const char* const kNothingWanted = "no output wanted: loops (with rows), vertices (with rows) or counts";
-
 }  // namespace
+
+// infur_frame_outlines_dev; *klass: the class plane it decoded into st_outl_plane and outlined, for the stage behind it
+int32_t infur::frame_outlines_dev(infur_ctx* c, const void* d_bgr, uint32_t w, uint32_t h, float factor, uint32_t mode, uint32_t decode, uint32_t flags,
+                                  uint32_t skip_value, uint32_t max_edges, void* d_loops, uint32_t loops_rows, void* d_vertices, uint32_t vertex_rows,
+                                  void* d_counts, void* d_stats, uint32_t stats_capacity, void* d_scaled, uint32_t* ow, uint32_t* oh, void** klass) {
+    if (!c || !ow || !oh) return INFUR_E_INVALID_ARG;
+    RETIF(outlines_check(c, 1, flags, skip_value));
+    RETIF(frame_class_plane(c, c->st_outl_plane, d_bgr, w, h, factor, mode, decode, d_stats, stats_capacity, d_scaled, ow, oh, klass,
+                            [&](uint32_t) { return wanted_check(c, d_loops, loops_rows, d_vertices, vertex_rows, d_counts, ""); }));
+    return infur_outlines_dev(c, *klass, 1, *oh, *ow, flags, skip_value, max_edges, d_loops, loops_rows, d_vertices, vertex_rows, d_counts);
+}
 
 extern "C" {
 
@@ -72,15 +42,16 @@ int32_t infur_outlines_dev(infur_ctx* c, const void* d_plane, uint32_t elem_byte
         RETIF(outlines_check(c, elem_bytes, flags, skip_value));
         RETIF(outlines_plane_check(c, h, w));
         const size_t hw = (size_t)h * w;
-        if (!(d_loops && loops_rows) && !(d_vertices && vertex_rows) && !d_counts) return fail(c, INFUR_E_INVALID_ARG, "%s", kNothingWanted);
+        RETIF(wanted_check(c, d_loops, loops_rows, d_vertices, vertex_rows, d_counts, ""));
         if (hw == 0) {  // empty plane: no edge
             if (d_counts) HIPCHK(c, hipMemsetAsync(d_counts, 0, 12, c->stream));
             return INFUR_OK;
         }
-        if (!d_plane) return fail(c, INFUR_E_INVALID_ARG, "a %ux%u plane and no plane pointer", w, h);
+        if (!d_plane) return no_plane(c, h, w);
         const size_t cap = edge_capacity(hw, max_edges);
         RETIF(ensure_private(c, c->st_outl, outlines_scratch_bytes(hw, cap)));
         ProfScope ps(c, "outlines", "outlines", 0, (double)hw * elem_bytes * 4);
+        // (d_loops goes to the kernel as given, also with no rows: Simplify and Coverage null such a pointer)
         HIPCHK(c, launch_outlines(d_plane, (int)elem_bytes, h, w, (flags & INFUR_OUTLINES_SKIP) != 0, (flags & INFUR_OUTLINES_CONN8) != 0, skip_value, cap,
                                   c->st_outl.p, (unsigned*)d_loops, d_loops ? loops_rows : 0, (unsigned*)d_vertices, d_vertices ? vertex_rows : 0,
                                   (unsigned*)d_counts, c->stream));
@@ -95,19 +66,20 @@ int32_t infur_outlines(infur_ctx* c, const void* plane, uint32_t elem_bytes, uin
         RETIF(outlines_check(c, elem_bytes, flags, skip_value));
         RETIF(outlines_plane_check(c, h, w));
         const size_t hw = (size_t)h * w;
-        if (!(loops && loops_rows) && !(vertices && vertex_rows) && !counts) return fail(c, INFUR_E_INVALID_ARG, "%s", kNothingWanted);
+        RETIF(wanted_check(c, loops, loops_rows, vertices, vertex_rows, counts, ""));
         if (hw == 0) {
             if (counts) std::memset(counts, 0, 12);
             return INFUR_OK;
         }
-        if (!plane) return fail(c, INFUR_E_INVALID_ARG, "a %ux%u plane and no plane pointer", w, h);
-        const OutlStage st(hw, loops ? loops_rows : 0, vertices ? vertex_rows : 0, 0, hw * elem_bytes);
+        if (!plane) return no_plane(c, h, w);
+        const PolyStage st(stage_rows(loops, loops_rows, frame_max_loops(hw)), stage_rows(vertices, vertex_rows, frame_max_vertices(hw)), 0, 0, 0,
+                           hw * elem_bytes);
         RETIF(ensure_private(c, c->st_outl_io, st.bytes));
         uint8_t* base = (uint8_t*)c->st_outl_io.p;
         HIPCHK(c, hipMemcpyAsync(base + st.plane, plane, hw * elem_bytes, hipMemcpyHostToDevice, c->stream));
         RETIF(infur_outlines_dev(c, base + st.plane, elem_bytes, h, w, flags, skip_value, max_edges, st.loops_rows ? base + st.loops : nullptr,
                                  (uint32_t)st.loops_rows, st.vertex_rows ? base + st.vertices : nullptr, (uint32_t)st.vertex_rows, base));
-        return outlines_read_back(c, base, st, loops, vertices, counts);
+        return poly_read_back(c, base, st, 3, 0, loops, vertices, counts);
     });
 }
 
@@ -115,18 +87,9 @@ int32_t infur_frame_outlines_dev(infur_ctx* c, const void* d_bgr, uint32_t w, ui
                                  uint32_t skip_value, uint32_t max_edges, void* d_loops, uint32_t loops_rows, void* d_vertices, uint32_t vertex_rows,
                                  void* d_counts, void* d_stats, uint32_t stats_capacity, void* d_scaled, uint32_t* ow, uint32_t* oh) {
     return abi_call(c, [&]() -> int32_t {
-        if (!c || !ow || !oh) return INFUR_E_INVALID_ARG;
-        RETIF(outlines_check(c, 1, flags, skip_value));
-        const size_t npix = scale_npix(w, h, factor);
-        void* kl = nullptr;
-        if (c->loaded && npix) {
-            if (!(d_loops && loops_rows) && !(d_vertices && vertex_rows) && !d_counts) return fail(c, INFUR_E_INVALID_ARG, "%s", kNothingWanted);
-            RETIF(ensure_private(c, c->st_outl_plane, npix));  // the class plane is decoded into scratch
-            kl = c->st_outl_plane.p;
-        }  // (otherwise the call below fails before it decodes: bad scale, empty frame or no model)
-        // scale -> model -> Segments decode, with that call's own checks, errors and MODEL_NOT_LOADED rule
-        RETIF(infur_frame_segments_dev(c, d_bgr, w, h, factor, mode, decode, kl, nullptr, npix, d_stats, stats_capacity, nullptr, 0, d_scaled, ow, oh));
-        return infur_outlines_dev(c, kl, 1, *oh, *ow, flags, skip_value, max_edges, d_loops, loops_rows, d_vertices, vertex_rows, d_counts);
+        void* klass = nullptr;
+        return frame_outlines_dev(c, d_bgr, w, h, factor, mode, decode, flags, skip_value, max_edges, d_loops, loops_rows, d_vertices, vertex_rows, d_counts,
+                                  d_stats, stats_capacity, d_scaled, ow, oh, &klass);
     });
 }
 
@@ -136,27 +99,11 @@ int32_t infur_frame_outlines(infur_ctx* c, const uint8_t* bgr, uint32_t w, uint3
     return abi_call(c, [&]() -> int32_t {
         if (!c || !ow || !oh) return INFUR_E_INVALID_ARG;
         RETIF(outlines_check(c, 1, flags, skip_value));
-        OutlStage st(0, 0, 0, 0, 0);
-        uint8_t* base = nullptr;
-        const bool any = (loops && loops_rows) || (vertices && vertex_rows) || counts;
-        return frame_host(
-            c, bgr, w, h, factor, scaled, ow, oh,
-            [&](size_t npix) -> int32_t {
-                st = OutlStage(npix, loops ? loops_rows : 0, vertices ? vertex_rows : 0,
-                               stats ? (stats_capacity < (uint32_t)kSegMaxClasses ? stats_capacity : (uint32_t)kSegMaxClasses) : 0, 0);
-                RETIF(ensure_private(c, c->st_outl_io, st.bytes));
-                base = (uint8_t*)c->st_outl_io.p;
-                return INFUR_OK;
-            },
-            [&](void* d_bgr, void* d_scaled) {
-                return infur_frame_outlines_dev(c, d_bgr, w, h, factor, mode, decode, flags, skip_value, max_edges, st.loops_rows ? base + st.loops : nullptr,
-                                                (uint32_t)st.loops_rows, st.vertex_rows ? base + st.vertices : nullptr, (uint32_t)st.vertex_rows,
-                                                any ? base : nullptr, stats ? base + st.stats : nullptr, stats_capacity, d_scaled, ow, oh);
-            },
-            [&](size_t) -> int32_t {
-                if (stats) HIPCHK(c, hipMemcpyAsync(stats, base + st.stats, (size_t)c->num_classes * INFUR_STAT_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
-                return outlines_read_back(c, base, st, loops, vertices, counts);
-            });
+        return poly_frame_host(c, c->st_outl_io, bgr, w, h, factor, scaled, ow, oh, {loops, loops_rows, vertices, vertex_rows, counts, stats, stats_capacity},
+                               3, 0, false, [&](void* d_bgr, void* d_scaled, const PolyDevOut& d) {
+                                   return infur_frame_outlines_dev(c, d_bgr, w, h, factor, mode, decode, flags, skip_value, max_edges, d.loops, d.loops_rows,
+                                                                   d.vertices, d.vertex_rows, d.counts, d.stats, stats_capacity, d_scaled, ow, oh);
+                               });
     });
 }
 

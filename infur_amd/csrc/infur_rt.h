@@ -11,6 +11,10 @@
 //   infur_outlines.cpp      Outlines (region boundaries of a class, label or track plane as polygon loops): C entry points
 //   infur_simplify.cpp      Simplify (Douglas-Peucker on Outlines' loops) and the polygon frame calls: C entry points
 //   infur_coverage.cpp      Coverage (Outlines' loops simplified arc by arc, shared borders once) and its frame calls: C entry points
+// (infur_egress.h, beside this header: what the last four share -- the argument checks with their messages, the read-back of a
+//  polygon stage, the host-pointer frame wrapper and the front halves of the _dev frame calls)
+// (egress_layout.h, HIP-free and included here: align_up, which moved there, the polygon stages' staging layout PolyStage, what
+//  Outlines leaves behind it PolyScratch, edge_capacity, kMaxSide, the statistics-class clamp and the row rules of the copies)
 // (conv_forms.h, the table of conv modes, configurations and forms, comes with kernels.h)
 // (wave_scan.h, the device code regions.hip, tracks.hip and runs.hip share, also holds kScanBlock, which sizes their block sums)
 // Everything here lives in namespace infur and is NOT part of the public ABI.
@@ -23,6 +27,7 @@
 #include <string>
 #include <vector>
 
+#include "egress_layout.h"
 #include "infur_ctx.h"
 #include "kernels.h"
 
@@ -82,7 +87,6 @@ inline bool ctx_hl(const infur_ctx* c) { return c->opt.compute_dtype == INFUR_DT
 inline int act_es(const infur_ctx* c) { return ctx_f16(c) ? 2 : (ctx_hl(c) ? 3 : 4); }
 inline const float* stem_lut(const infur_ctx* c) { return c->input_u8 ? c->d_u8_lut : c->d_pre_lut; }
 inline int conv_out(int n, int k, int s, int p, int d) { return (n + 2 * p - d * (k - 1) - 1) / s + 1; }
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // ---- roctx ranges + per-kernel HIP events (infur_capi.cpp) ----
 struct Roctx {

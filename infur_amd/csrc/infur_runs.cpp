@@ -1,14 +1,8 @@
 // infur_runs.cpp -- Runs, the egress stage behind the four decodes (include/infur_hip.h): a byte or u32 plane as raster-ordered
 // run-length records, a per-row index and the count, so that a host copies out only as many records as there are.  Kernels:
-// runs.hip.  Everything is enqueued on the context's stream.  Like infur_regions.cpp the frame path here always enqueues
-// eagerly, and every buffer of this file is private scratch no captured graph of the library can point into: growing it leaves
-// mem_gen -- and with it the graphs infur_frame_advance_dev has cached -- alone.
-#include <cstring>
-#include <new>
-
-#include "infur_ctx.h"
-#include "infur_rt.h"
-#include "kernels.h"
+// runs.hip.  Everything is enqueued on the context's stream; the checks, the statistics staging and the decode of the class
+// plane it shares with the other egress stages are infur_egress.h's, and so is the rule that its buffers are private scratch.
+#include "infur_egress.h"
 
 using namespace infur;
 
@@ -19,9 +13,16 @@ static_assert(kRunWords == INFUR_RUN_WORDS, "runs.hip and the header disagree ab
 constexpr size_t kRunsScratchFloor = 64 << 10;  // block sums of 16 Mi pixels: a captured infur_runs_dev keeps its pointer
 
 int32_t runs_check(infur_ctx* c, uint32_t elem_bytes, uint32_t flags, uint32_t skip_value) {
-    if (elem_bytes != 1 && elem_bytes != 4) return fail(c, INFUR_E_INVALID_ARG, "elem_bytes %u: 1 or 4", elem_bytes);
-    if (flags & ~(uint32_t)INFUR_RUNS_SKIP) return fail(c, INFUR_E_INVALID_ARG, "unknown runs flags 0x%x", flags);
-    if (elem_bytes == 1 && skip_value > 255) return fail(c, INFUR_E_INVALID_ARG, "skip_value %u: a byte plane holds at most 255", skip_value);
+    return elem_check(c, elem_bytes, flags, INFUR_RUNS_SKIP, "runs", skip_value);
+}
+int32_t runs_wanted(infur_ctx* c, const void* runs, uint32_t runs_rows, const void* row_start, const void* n_runs) {
+    if ((runs && runs_rows) || row_start || n_runs) return INFUR_OK;
+    return fail(c, INFUR_E_INVALID_ARG, "no output wanted: runs (with rows), row_start or n_runs");
+}
+// the frame calls' row index: checked only where a model is loaded, so that without one Scale still runs
+int32_t row_index_check(infur_ctx* c, const void* row_start, uint32_t row_start_rows, uint32_t h) {
+    if (c->loaded && row_start && row_start_rows < (size_t)h + 1)
+        return fail(c, INFUR_E_CAPACITY, "the row index needs %zu words, buffer has %u", (size_t)h + 1, row_start_rows);
     return INFUR_OK;
 }
 
@@ -61,13 +62,13 @@ int32_t infur_runs_dev(infur_ctx* c, const void* d_plane, uint32_t elem_bytes, u
         RETIF(runs_check(c, elem_bytes, flags, skip_value));
         RETIF(plane_check(c, h, w, "a run"));
         const size_t hw = (size_t)h * w;
-        if (!(d_runs && runs_rows) && !d_row_start && !d_n) return fail(c, INFUR_E_INVALID_ARG, "no output wanted: runs (with rows), row_start or n_runs");
+        RETIF(runs_wanted(c, d_runs, runs_rows, d_row_start, d_n));
         if (hw == 0) {  // empty plane: no run, every row starts at 0
             if (d_n) HIPCHK(c, hipMemsetAsync(d_n, 0, 4, c->stream));
             if (d_row_start) HIPCHK(c, hipMemsetAsync(d_row_start, 0, ((size_t)h + 1) * 4, c->stream));
             return INFUR_OK;
         }
-        if (!d_plane) return fail(c, INFUR_E_INVALID_ARG, "a %ux%u plane and no plane pointer", w, h);
+        if (!d_plane) return no_plane(c, h, w);
         const size_t scratch = runs_scratch_bytes(hw);
         RETIF(ensure_private(c, c->st_runs, scratch > kRunsScratchFloor ? scratch : kRunsScratchFloor));
         ProfScope ps(c, "runs", "runs", 0, (double)hw * elem_bytes * ((d_runs && runs_rows) || d_row_start ? 2 : 1));
@@ -84,13 +85,13 @@ int32_t infur_runs(infur_ctx* c, const void* plane, uint32_t elem_bytes, uint32_
         RETIF(runs_check(c, elem_bytes, flags, skip_value));
         RETIF(plane_check(c, h, w, "a run"));
         const size_t hw = (size_t)h * w;
-        if (!(runs && runs_rows) && !row_start && !n_runs) return fail(c, INFUR_E_INVALID_ARG, "no output wanted: runs (with rows), row_start or n_runs");
+        RETIF(runs_wanted(c, runs, runs_rows, row_start, n_runs));
         if (hw == 0) {
             if (n_runs) *n_runs = 0;
             if (row_start) std::memset(row_start, 0, ((size_t)h + 1) * 4);
             return INFUR_OK;
         }
-        if (!plane) return fail(c, INFUR_E_INVALID_ARG, "a %ux%u plane and no plane pointer", w, h);
+        if (!plane) return no_plane(c, h, w);
         const RunStage st(hw, h, runs ? runs_rows : 0, 0, hw * elem_bytes);
         RETIF(ensure_private(c, c->st_runs_io, st.bytes));
         uint8_t* base = (uint8_t*)c->st_runs_io.p;
@@ -107,19 +108,11 @@ int32_t infur_frame_runs_dev(infur_ctx* c, const void* d_bgr, uint32_t w, uint32
     return abi_call(c, [&]() -> int32_t {
         if (!c || !ow || !oh) return INFUR_E_INVALID_ARG;
         RETIF(runs_check(c, 1, flags, skip_value));
-        uint32_t b = 0;
-        const size_t npix = scale_npix(w, h, factor, &b);
         void* kl = nullptr;
-        if (c->loaded && npix) {
-            if (!(d_runs && runs_rows) && !d_row_start && !d_n)
-                return fail(c, INFUR_E_INVALID_ARG, "no output wanted: runs (with rows), row_start or n_runs");
-            if (d_row_start && row_start_rows < (size_t)b + 1)
-                return fail(c, INFUR_E_CAPACITY, "the row index needs %zu words, buffer has %u", (size_t)b + 1, row_start_rows);
-            RETIF(ensure_private(c, c->st_runs_plane, npix));  // the class plane is decoded into scratch
-            kl = c->st_runs_plane.p;
-        }  // (otherwise the call below fails before it decodes: bad scale, empty frame or no model)
-        // scale -> model -> Segments decode, with that call's own checks, errors and MODEL_NOT_LOADED rule
-        RETIF(infur_frame_segments_dev(c, d_bgr, w, h, factor, mode, decode, kl, nullptr, npix, d_stats, stats_capacity, nullptr, 0, d_scaled, ow, oh));
+        RETIF(frame_class_plane(c, c->st_runs_plane, d_bgr, w, h, factor, mode, decode, d_stats, stats_capacity, d_scaled, ow, oh, &kl, [&](uint32_t rows) {
+            RETIF(runs_wanted(c, d_runs, runs_rows, d_row_start, d_n));
+            return row_index_check(c, d_row_start, row_start_rows, rows);
+        }));
         return infur_runs_dev(c, kl, 1, *oh, *ow, flags, skip_value, d_runs, runs_rows, d_row_start, d_n);
     });
 }
@@ -135,11 +128,8 @@ int32_t infur_frame_runs(infur_ctx* c, const uint8_t* bgr, uint32_t w, uint32_t 
         return frame_host(
             c, bgr, w, h, factor, scaled, ow, oh,
             [&](size_t npix) -> int32_t {
-                // (as the _dev form: checked only where a model is loaded, so that without one Scale still runs)
-                if (c->loaded && row_start && row_start_rows < (size_t)*oh + 1)
-                    return fail(c, INFUR_E_CAPACITY, "the row index needs %zu words, buffer has %u", (size_t)*oh + 1, row_start_rows);
-                st = RunStage(npix, *oh, runs ? runs_rows : 0,
-                              stats ? (stats_capacity < (uint32_t)kSegMaxClasses ? stats_capacity : (uint32_t)kSegMaxClasses) : 0, 0);
+                RETIF(row_index_check(c, row_start, row_start_rows, *oh));
+                st = RunStage(npix, *oh, runs ? runs_rows : 0, staged_classes(stats, stats_capacity), 0);
                 RETIF(ensure_private(c, c->st_runs_io, st.bytes));
                 base = (uint8_t*)c->st_runs_io.p;
                 return INFUR_OK;
@@ -150,7 +140,7 @@ int32_t infur_frame_runs(infur_ctx* c, const uint8_t* bgr, uint32_t w, uint32_t 
                                             stats ? base + st.stats : nullptr, stats_capacity, d_scaled, ow, oh);
             },
             [&](size_t) -> int32_t {
-                if (stats) HIPCHK(c, hipMemcpyAsync(stats, base + st.stats, (size_t)c->num_classes * INFUR_STAT_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
+                RETIF(stats_read_back(c, stats, base + st.stats));
                 return runs_read_back(c, base, st, *oh, runs, row_start, n_runs);
             });
     });

@@ -147,7 +147,7 @@ int32_t infur_frame_segments(infur_ctx* c, const uint8_t* bgr, uint32_t w, uint3
             [&](size_t npix) -> int32_t {
                 if ((klass || conf) && plane_cap < npix) return fail(c, INFUR_E_CAPACITY, "a plane needs %zu bytes, buffer has %zu", npix, plane_cap);
                 if (rgba && rgba_cap < npix * 4) return fail(c, INFUR_E_CAPACITY, "mask needs %zu bytes, buffer has %zu", npix * 4, rgba_cap);
-                st = SegStage(stats ? (stats_classes < (uint32_t)kSegMaxClasses ? stats_classes : (uint32_t)kSegMaxClasses) : 0, npix);
+                st = SegStage(staged_classes(stats, stats_classes), npix);
                 if (rgba) RETIF(ensure(c, c->st_rgba, npix ? npix * 4 : 1));
                 RETIF(ensure_private(c, c->st_seg, st.bytes ? st.bytes : 1));
                 base = (uint8_t*)c->st_seg.p;

@@ -1,74 +1,17 @@
 // infur_simplify.cpp -- Simplify, the stage behind Outlines (include/infur_hip.h): Douglas-Peucker on the loops Outlines left in
 // device memory, so that a host copies out polygons with a tolerance and not the pixel staircase.  Kernels: simplify.hip.
-// Everything is enqueued on the context's stream.  Like infur_outlines.cpp the frame path here always enqueues eagerly, and every
-// buffer of this file is private scratch no captured graph of the library can point into: growing it leaves mem_gen -- and with
-// it the graphs infur_frame_advance_dev has cached -- alone.
-#include <cstring>
-#include <new>
-
-#include "infur_ctx.h"
-#include "infur_rt.h"
-#include "kernels.h"
+// Everything is enqueued on the context's stream; the layout, checks, read-back, frame wrapper and the front half of the frame
+// call it shares with the other egress stages are infur_egress.h's, and so is the rule that its buffers are private scratch.
+#include "infur_egress.h"
 
 using namespace infur;
 
 namespace {
 
-constexpr uint32_t kMaxSide = 8191;  // every coordinate difference stays below 2^13: 256 * cross^2 < 2^62
-
 int32_t simplify_check(infur_ctx* c, uint32_t h, uint32_t w, uint32_t tol16) {
-    if (w == 0 || w > kMaxSide || h > kMaxSide) return fail(c, INFUR_E_INVALID_ARG, "%ux%u: a plane of width 1 to %u and height up to %u", w, h, kMaxSide, kMaxSide);
-    if (tol16 > 65535) return fail(c, INFUR_E_INVALID_ARG, "tol16 %u: at most 65535 (4095.9 pixels)", tol16);
-    return INFUR_OK;
+    RETIF(side_check(c, h, w, true));
+    return tol_check(c, tol16);
 }
-
-const char* const kNothingWanted = "no output wanted: loops_out (with rows), vertices_out (with rows) or counts_out";
-
-// st_simp_io: [counts_out][counts][statistics table k x 8 u64][records out][vertices out][records in][vertices in], on 256-byte
-// boundaries
-struct SimpStage {
-    size_t loops_rows, vertex_rows, counts_in, stats, loops, vertices, loops_in, vertices_in, bytes;
-    SimpStage(size_t loops_rows_, size_t vertex_rows_, uint32_t k, size_t loops_rows_in, size_t vertex_rows_in) {
-        loops_rows = loops_rows_;
-        vertex_rows = vertex_rows_;
-        counts_in = 256;
-        stats = 512;
-        loops = stats + align_up((size_t)k * INFUR_STAT_WORDS * 8, 256);
-        vertices = loops + align_up(loops_rows * INFUR_LOOP_WORDS * 4, 256);
-        loops_in = vertices + align_up(vertex_rows * 4, 256);
-        vertices_in = loops_in + align_up(loops_rows_in * INFUR_LOOP_WORDS * 4, 256);
-        bytes = vertices_in + align_up(vertex_rows_in * 4, 256);
-    }
-};
-
-// the counts first: they decide how many records and vertices there are to copy
-int32_t simplify_read_back(infur_ctx* c, const uint8_t* base, const SimpStage& st, uint32_t* loops, uint32_t* vertices, uint32_t* counts) {
-    uint32_t n[4] = {0, 0, 0, 0};
-    HIPCHK(c, hipMemcpyAsync(n, base, sizeof n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const bool truncated = (n[3] & INFUR_SIMPLIFY_TRUNCATED) != 0;  // nothing but the counts was written
-    const size_t nl = truncated ? 0 : (n[0] < st.loops_rows ? n[0] : st.loops_rows), nv = n[1] < st.vertex_rows ? n[1] : st.vertex_rows;
-    if (loops && nl) HIPCHK(c, hipMemcpy(loops, base + st.loops, nl * INFUR_LOOP_WORDS * 4, hipMemcpyDeviceToHost));
-    if (vertices && nv) HIPCHK(c, hipMemcpy(vertices, base + st.vertices, nv * 4, hipMemcpyDeviceToHost));
-    if (counts) std::memcpy(counts, n, sizeof n);
-    return INFUR_OK;
-}
-
-// the capacity of Outlines in edges (infur_outlines.cpp): 0 and anything above the worst case are the worst case
-size_t edge_capacity(size_t hw, uint32_t max_edges) { return max_edges && max_edges < hw * 4 ? max_edges : hw * 4; }
-
-// st_poly, what Outlines leaves for Simplify inside infur_frame_polygons_dev: [counts][records][vertices].  A loop has at least
-// four edges and a vertex is the tail of one
-struct PolyScratch {
-    size_t loops_rows, vertex_rows, loops, vertices, bytes;
-    explicit PolyScratch(size_t cap) {
-        loops_rows = cap / 4 ? cap / 4 : 1;
-        vertex_rows = cap;
-        loops = 256;
-        vertices = loops + align_up(loops_rows * INFUR_LOOP_WORDS * 4, 256);
-        bytes = vertices + align_up(vertex_rows * 4, 256);
-    }
-};
 
 }  // namespace
 
@@ -80,11 +23,8 @@ int32_t infur_simplify_dev(infur_ctx* c, const void* d_loops, uint32_t loops_row
     return abi_call(c, [&]() -> int32_t {
         if (!c) return INFUR_E_INVALID_ARG;
         RETIF(simplify_check(c, h, w, tol16));
-        if (!(d_loops_out && loops_rows_out) && !(d_vertices_out && vertex_rows_out) && !d_counts_out)
-            return fail(c, INFUR_E_INVALID_ARG, "%s", kNothingWanted);
-        if (!d_counts) return fail(c, INFUR_E_INVALID_ARG, "no counts: Outlines' {n_loops, n_vertices, ..} say how much of the input there is");
-        if ((!d_loops && loops_rows_in) || (!d_vertices && vertex_rows_in))
-            return fail(c, INFUR_E_INVALID_ARG, "%u records and %u vertices declared and no pointer to them", loops_rows_in, vertex_rows_in);
+        RETIF(wanted_check(c, d_loops_out, loops_rows_out, d_vertices_out, vertex_rows_out, d_counts_out, "_out"));
+        RETIF(input_check(c, d_loops, loops_rows_in, d_vertices, vertex_rows_in, d_counts));
         if (vertex_rows_in == 0xFFFFFFFFu) return fail(c, INFUR_E_INVALID_ARG, "vertex_rows_in: at most 2^32 - 2");
         RETIF(ensure_private(c, c->st_simp, simplify_scratch_bytes(loops_rows_in, vertex_rows_in)));
         ProfScope ps(c, "simplify", "simplify", 0, (double)vertex_rows_in * 4 + (double)loops_rows_in * 16);
@@ -102,14 +42,11 @@ int32_t infur_simplify(infur_ctx* c, const uint32_t* loops, uint32_t loops_rows_
     return abi_call(c, [&]() -> int32_t {
         if (!c) return INFUR_E_INVALID_ARG;
         RETIF(simplify_check(c, h, w, tol16));
-        if (!(loops_out && loops_rows_out) && !(vertices_out && vertex_rows_out) && !counts_out) return fail(c, INFUR_E_INVALID_ARG, "%s", kNothingWanted);
-        if (!counts) return fail(c, INFUR_E_INVALID_ARG, "no counts: Outlines' {n_loops, n_vertices, ..} say how much of the input there is");
-        if ((!loops && loops_rows_in) || (!vertices && vertex_rows_in))
-            return fail(c, INFUR_E_INVALID_ARG, "%u records and %u vertices declared and no pointer to them", loops_rows_in, vertex_rows_in);
+        RETIF(wanted_check(c, loops_out, loops_rows_out, vertices_out, vertex_rows_out, counts_out, "_out"));
+        RETIF(input_check(c, loops, loops_rows_in, vertices, vertex_rows_in, counts));
         // only what the counts say there is travels; an output is never longer than its input
-        const size_t nl = counts[0] < loops_rows_in ? counts[0] : loops_rows_in, nv = counts[1] < vertex_rows_in ? counts[1] : vertex_rows_in;
-        const size_t lrows = loops_out ? (loops_rows_out < nl ? loops_rows_out : nl) : 0, vrows = vertices_out ? (vertex_rows_out < nv ? vertex_rows_out : nv) : 0;
-        const SimpStage st(lrows, vrows, 0, nl, nv);
+        const size_t nl = copy_rows(counts[0], loops_rows_in), nv = copy_rows(counts[1], vertex_rows_in);
+        const PolyStage st(stage_rows(loops_out, loops_rows_out, nl), stage_rows(vertices_out, vertex_rows_out, nv), 0, nl, nv, 0);
         RETIF(ensure_private(c, c->st_simp_io, st.bytes));
         uint8_t* base = (uint8_t*)c->st_simp_io.p;
         HIPCHK(c, hipMemcpyAsync(base + st.counts_in, counts, 8, hipMemcpyHostToDevice, c->stream));
@@ -117,8 +54,9 @@ int32_t infur_simplify(infur_ctx* c, const uint32_t* loops, uint32_t loops_rows_
         if (nv) HIPCHK(c, hipMemcpyAsync(base + st.vertices_in, vertices, nv * 4, hipMemcpyHostToDevice, c->stream));
         // (the rows declared to the device are what was copied: truncated input stays truncated, counts[k] > rows)
         RETIF(infur_simplify_dev(c, base + st.loops_in, (uint32_t)nl, base + st.vertices_in, (uint32_t)nv, base + st.counts_in, h, w, tol16,
-                                 lrows ? base + st.loops : nullptr, (uint32_t)lrows, vrows ? base + st.vertices : nullptr, (uint32_t)vrows, base));
-        return simplify_read_back(c, base, st, loops_out, vertices_out, counts_out);
+                                 st.loops_rows ? base + st.loops : nullptr, (uint32_t)st.loops_rows, st.vertex_rows ? base + st.vertices : nullptr,
+                                 (uint32_t)st.vertex_rows, base));
+        return poly_read_back(c, base, st, INFUR_SIMPLIFY_COUNT_WORDS, INFUR_SIMPLIFY_TRUNCATED, loops_out, vertices_out, counts_out);
     });
 }
 
@@ -127,24 +65,11 @@ int32_t infur_frame_polygons_dev(infur_ctx* c, const void* d_bgr, uint32_t w, ui
                                  uint32_t vertex_rows, void* d_counts, void* d_stats, uint32_t stats_capacity, void* d_scaled, uint32_t* ow, uint32_t* oh) {
     return abi_call(c, [&]() -> int32_t {
         if (!c || !ow || !oh) return INFUR_E_INVALID_ARG;
-        RETIF(simplify_check(c, 0, 1, tol16));
-        const size_t npix = scale_npix(w, h, factor);
-        PolyScratch at(1);
-        uint8_t* base = nullptr;
-        uint32_t sw = 0, sh = 0;
-        if (npix && infur_scale_out_dims(w, h, factor, &sw, &sh) == INFUR_OK) RETIF(simplify_check(c, sh, sw, tol16));  // before the model runs
-        if (c->loaded && npix) {
-            if (!(d_loops && loops_rows) && !(d_vertices && vertex_rows) && !d_counts) return fail(c, INFUR_E_INVALID_ARG, "%s", kNothingWanted);
-            at = PolyScratch(edge_capacity(npix, max_edges));
-            RETIF(ensure_private(c, c->st_poly, at.bytes));
-            base = (uint8_t*)c->st_poly.p;
-        }  // (otherwise the call below fails before it decodes: bad scale, empty frame or no model)
-        // scale -> model -> Segments decode -> Outlines, with that call's own checks, errors and MODEL_NOT_LOADED rule
-        RETIF(infur_frame_outlines_dev(c, d_bgr, w, h, factor, mode, decode, flags, skip_value, max_edges, base ? base + at.loops : nullptr,
-                                       (uint32_t)at.loops_rows, base ? base + at.vertices : nullptr, (uint32_t)at.vertex_rows, base, d_stats,
-                                       stats_capacity, d_scaled, ow, oh));
-        return infur_simplify_dev(c, base + at.loops, (uint32_t)at.loops_rows, base + at.vertices, (uint32_t)at.vertex_rows, base, *oh, *ow, tol16, d_loops,
-                                  loops_rows, d_vertices, vertex_rows, d_counts);
+        PolyFront f;  // scale -> model -> Segments decode -> Outlines
+        RETIF(poly_frame_front(c, d_bgr, w, h, factor, mode, decode, flags, skip_value, max_edges, tol16, true, d_loops, loops_rows, d_vertices, vertex_rows,
+                               d_counts, d_stats, stats_capacity, d_scaled, ow, oh, &f));
+        return infur_simplify_dev(c, f.base + f.at.loops, (uint32_t)f.at.loops_rows, f.base + f.at.vertices, (uint32_t)f.at.vertex_rows, f.base, *oh, *ow,
+                                  tol16, d_loops, loops_rows, d_vertices, vertex_rows, d_counts);
     });
 }
 
@@ -153,27 +78,12 @@ int32_t infur_frame_polygons(infur_ctx* c, const uint8_t* bgr, uint32_t w, uint3
                              uint32_t vertex_rows, uint32_t* counts, uint64_t* stats, uint32_t stats_capacity, uint8_t* scaled, uint32_t* ow, uint32_t* oh) {
     return abi_call(c, [&]() -> int32_t {
         if (!c || !ow || !oh) return INFUR_E_INVALID_ARG;
-        SimpStage st(0, 0, 0, 0, 0);
-        uint8_t* base = nullptr;
-        const bool any = (loops && loops_rows) || (vertices && vertex_rows) || counts;
-        return frame_host(
-            c, bgr, w, h, factor, scaled, ow, oh,
-            [&](size_t npix) -> int32_t {
-                const size_t lr = loops ? (loops_rows < npix ? loops_rows : npix) : 0, vr = vertices ? (vertex_rows < npix * 4 ? vertex_rows : npix * 4) : 0;
-                st = SimpStage(lr, vr, stats ? (stats_capacity < (uint32_t)kSegMaxClasses ? stats_capacity : (uint32_t)kSegMaxClasses) : 0, 0, 0);
-                RETIF(ensure_private(c, c->st_simp_io, st.bytes));
-                base = (uint8_t*)c->st_simp_io.p;
-                return INFUR_OK;
-            },
-            [&](void* d_bgr, void* d_scaled) {
-                return infur_frame_polygons_dev(c, d_bgr, w, h, factor, mode, decode, flags, skip_value, max_edges, tol16, st.loops_rows ? base + st.loops : nullptr,
-                                                (uint32_t)st.loops_rows, st.vertex_rows ? base + st.vertices : nullptr, (uint32_t)st.vertex_rows,
-                                                any ? base : nullptr, stats ? base + st.stats : nullptr, stats_capacity, d_scaled, ow, oh);
-            },
-            [&](size_t) -> int32_t {
-                if (stats) HIPCHK(c, hipMemcpyAsync(stats, base + st.stats, (size_t)c->num_classes * INFUR_STAT_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
-                return simplify_read_back(c, base, st, loops, vertices, counts);
-            });
+        return poly_frame_host(c, c->st_simp_io, bgr, w, h, factor, scaled, ow, oh, {loops, loops_rows, vertices, vertex_rows, counts, stats, stats_capacity},
+                               INFUR_SIMPLIFY_COUNT_WORDS, INFUR_SIMPLIFY_TRUNCATED, false, [&](void* d_bgr, void* d_scaled, const PolyDevOut& d) {
+                                   return infur_frame_polygons_dev(c, d_bgr, w, h, factor, mode, decode, flags, skip_value, max_edges, tol16, d.loops,
+                                                                   d.loops_rows, d.vertices, d.vertex_rows, d.counts, d.stats, stats_capacity, d_scaled, ow,
+                                                                   oh);
+                               });
     });
 }
 

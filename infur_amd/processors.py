@@ -95,6 +95,16 @@ def _check_bgr(img: np.ndarray) -> np.ndarray:
     return np.ascontiguousarray(img)
 
 
+def _ptr(a: Optional[np.ndarray]):
+    """the address of an array, NULL for None"""
+    return a.ctypes.data if a is not None else None
+
+
+def _ptr_some(a: Optional[np.ndarray]):
+    """the address of an array that holds something, NULL for None and for an empty one"""
+    return a.ctypes.data if a is not None and a.size else None
+
+
 # --------------------------------------------------------------------------- #
 # context
 # --------------------------------------------------------------------------- #
@@ -925,6 +935,31 @@ def _outlines_flags(skip: Optional[int], connectivity: int) -> int:
     return (_lib.OUTLINES_SKIP if skip is not None else 0) | (_lib.OUTLINES_CONN8 if connectivity == 8 else 0)
 
 
+def _poly_alloc(loops_rows: int, most_loops: int, vertex_rows: int, most_vertices: int) -> tuple:
+    """The output arrays of a polygon call, the caller's rows clamped to what there can be -> (loops [lrows, 4] u32, vertices
+    [vrows] u32), None where no row is wanted."""
+    lrows, vrows = max(0, min(int(loops_rows), most_loops)), max(0, min(int(vertex_rows), most_vertices))
+    return np.empty((lrows, _lib.LOOP_WORDS), np.uint32) if lrows else None, np.empty(vrows, np.uint32) if vrows else None
+
+
+def _poly_rows(a: Optional[np.ndarray]) -> int:
+    return len(a) if a is not None else 0
+
+
+def _poly_slice(loops: Optional[np.ndarray], vertices: Optional[np.ndarray], counts, cut: bool = False) -> tuple:
+    """-> (loops[:min(n_loops, rows)], vertices[:min(n_vertices, rows)]); ``cut``: the status says that no record was written"""
+    nl, nv = int(counts[0]), int(counts[1])
+    return (loops[:0 if cut else min(nl, len(loops))] if loops is not None else None,
+            vertices[:min(nv, len(vertices))] if vertices is not None else None)
+
+
+def _poly_input(loops, vertices, counts) -> tuple:
+    """Outlines' results as the input of the stage behind it -> (loops [*, 4] u32, vertices [*] u32, {n_loops, n_vertices} u32)"""
+    loops = np.ascontiguousarray(loops if loops is not None else np.zeros((0, _lib.LOOP_WORDS)), np.uint32).reshape(-1, _lib.LOOP_WORDS)
+    vertices = np.ascontiguousarray(vertices if vertices is not None else np.zeros(0), np.uint32).reshape(-1)
+    return loops, vertices, np.array([int(counts[0]), int(counts[1])], np.uint32)
+
+
 class Outlines(Processor):
     """The polygon stage: the boundaries of the value-regions of a class plane (u8) or a label / track plane (u32) as closed loops.
 
@@ -958,16 +993,13 @@ class Outlines(Processor):
             raise InfurError(_lib.E_SHAPE, f"expected an [H,W] plane of 1- or 4-byte integers, got {inp.shape} {inp.dtype}")
         plane = np.ascontiguousarray(inp)
         h, w = plane.shape
-        lrows, vrows = max(0, min(int(out.loops_rows), h * w)), max(0, min(int(out.vertex_rows), 4 * h * w))
-        loops = np.empty((lrows, _lib.LOOP_WORDS), np.uint32) if lrows else None
-        vertices = np.empty(vrows, np.uint32) if vrows else None
+        loops, vertices = _poly_alloc(out.loops_rows, h * w, out.vertex_rows, 4 * h * w)
         counts = np.zeros(3, np.uint32)
-        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
-        self.ctx.check(self.ctx.L.infur_outlines(self.ctx.h, ptr(plane), plane.dtype.itemsize, h, w, _outlines_flags(self.skip, self.connectivity),
-                                                 self.skip or 0, self.max_edges, ptr(loops), lrows, ptr(vertices), vrows, counts.ctypes.data))
+        self.ctx.check(self.ctx.L.infur_outlines(self.ctx.h, _ptr_some(plane), plane.dtype.itemsize, h, w, _outlines_flags(self.skip, self.connectivity),
+                                                 self.skip or 0, self.max_edges, _ptr(loops), _poly_rows(loops), _ptr(vertices), _poly_rows(vertices),
+                                                 counts.ctypes.data))
         out.n_loops, out.n_vertices, out.n_edges = (int(v) for v in counts)
-        out.loops = loops[:min(out.n_loops, lrows)] if loops is not None else None
-        out.vertices = vertices[:min(out.n_vertices, vrows)] if vertices is not None else None
+        out.loops, out.vertices = _poly_slice(loops, vertices, counts)
 
 
 class OutlinesFrame(NamedTuple):
@@ -1079,20 +1111,13 @@ class Simplify(Processor):
     def advance(self, inp: tuple, out: SimplifyOut) -> None:
         self.dirty = False
         loops, vertices, counts, (h, w) = inp
-        loops = np.ascontiguousarray(loops if loops is not None else np.zeros((0, _lib.LOOP_WORDS)), np.uint32).reshape(-1, _lib.LOOP_WORDS)
-        vertices = np.ascontiguousarray(vertices if vertices is not None else np.zeros(0), np.uint32).reshape(-1)
-        cin = np.array([int(counts[0]), int(counts[1])], np.uint32)
-        lrows, vrows = max(0, min(int(out.loops_rows), len(loops))), max(0, min(int(out.vertex_rows), len(vertices)))
-        lo = np.empty((lrows, _lib.LOOP_WORDS), np.uint32) if lrows else None
-        vo = np.empty(vrows, np.uint32) if vrows else None
+        loops, vertices, cin = _poly_input(loops, vertices, counts)
+        lo, vo = _poly_alloc(out.loops_rows, len(loops), out.vertex_rows, len(vertices))
         cout = np.zeros(_lib.SIMPLIFY_COUNT_WORDS, np.uint32)
-        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
-        self.ctx.check(self.ctx.L.infur_simplify(self.ctx.h, ptr(loops), len(loops), ptr(vertices), len(vertices), cin.ctypes.data, h, w, self.tol16,
-                                                 ptr(lo), lrows, ptr(vo), vrows, cout.ctypes.data))
+        self.ctx.check(self.ctx.L.infur_simplify(self.ctx.h, _ptr_some(loops), len(loops), _ptr_some(vertices), len(vertices), cin.ctypes.data, h, w,
+                                                 self.tol16, _ptr(lo), _poly_rows(lo), _ptr(vo), _poly_rows(vo), cout.ctypes.data))
         out.n_loops, out.n_vertices, out.n_degenerate, out.status = (int(v) for v in cout)
-        cut = bool(out.status & _lib.SIMPLIFY_TRUNCATED)
-        out.loops = lo[:0 if cut else min(out.n_loops, lrows)] if lo is not None else None
-        out.vertices = vo[:min(out.n_vertices, vrows)] if vo is not None else None
+        out.loops, out.vertices = _poly_slice(lo, vo, cout, cut=bool(out.status & _lib.SIMPLIFY_TRUNCATED))
 
 
 class CoverageOut:
@@ -1145,22 +1170,15 @@ class Coverage(Processor):
         if plane.ndim != 2 or plane.dtype not in (np.uint8, np.uint32):
             raise InfurError(_lib.E_INVALID_ARG, "the plane: [h, w] of uint8 or uint32")
         h, w = plane.shape
-        loops = np.ascontiguousarray(loops if loops is not None else np.zeros((0, _lib.LOOP_WORDS)), np.uint32).reshape(-1, _lib.LOOP_WORDS)
-        vertices = np.ascontiguousarray(vertices if vertices is not None else np.zeros(0), np.uint32).reshape(-1)
-        cin = np.array([int(counts[0]), int(counts[1])], np.uint32)
-        most = len(vertices) + (h + 1) * (w + 1)  # junctions are inserted: the output may be longer than the input
-        lrows, vrows = max(0, min(int(out.loops_rows), len(loops))), max(0, min(int(out.vertex_rows), most))
-        lo = np.empty((lrows, _lib.LOOP_WORDS), np.uint32) if lrows else None
-        vo = np.empty(vrows, np.uint32) if vrows else None
+        loops, vertices, cin = _poly_input(loops, vertices, counts)
+        # junctions are inserted: the output may be longer than the input
+        lo, vo = _poly_alloc(out.loops_rows, len(loops), out.vertex_rows, len(vertices) + (h + 1) * (w + 1))
         cout = np.zeros(_lib.COVERAGE_COUNT_WORDS, np.uint32)
-        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
-        self.ctx.check(self.ctx.L.infur_coverage(self.ctx.h, ptr(plane), plane.itemsize, h, w, _lib.COVERAGE_SKIP if skip is not None else 0, skip or 0,
-                                                 ptr(loops), len(loops), ptr(vertices), len(vertices), cin.ctypes.data, self.tol16, self.aug_rows,
-                                                 ptr(lo), lrows, ptr(vo), vrows, cout.ctypes.data))
+        self.ctx.check(self.ctx.L.infur_coverage(self.ctx.h, _ptr_some(plane), plane.itemsize, h, w, _lib.COVERAGE_SKIP if skip is not None else 0,
+                                                 skip or 0, _ptr_some(loops), len(loops), _ptr_some(vertices), len(vertices), cin.ctypes.data, self.tol16,
+                                                 self.aug_rows, _ptr(lo), _poly_rows(lo), _ptr(vo), _poly_rows(vo), cout.ctypes.data))
         out.n_loops, out.n_vertices, out.n_degenerate, out.status, out.n_aug, out.n_arcs = (int(v) for v in cout)
-        cut = bool(out.status & (_lib.COVERAGE_TRUNCATED | _lib.COVERAGE_OVERFLOW))
-        out.loops = lo[:0 if cut else min(out.n_loops, lrows)] if lo is not None else None
-        out.vertices = vo[:min(out.n_vertices, vrows)] if vo is not None else None
+        out.loops, out.vertices = _poly_slice(lo, vo, cout, cut=bool(out.status & (_lib.COVERAGE_TRUNCATED | _lib.COVERAGE_OVERFLOW)))
 
 
 class PolygonsFrame(NamedTuple):
@@ -1194,58 +1212,68 @@ class FramePath:
         self.ctx = ctx
         self.scale_mode = scale_mode
 
-    def advance(self, img: np.ndarray, factor: float = 1.0, want_scaled: bool = False):
-        """-> (rgba [oh,ow,4] u8 or None when no model is loaded, scaled BGR or None)."""
+    # ---- what every fused call shares ----
+    def _front(self, img: np.ndarray, factor: float):
+        """The checked frame, its width and height, the factor as the float32 the library sees, and the scaled dimensions (two
+        ``c_uint32``, which the call then writes) -> (img, w, h, f, ow, oh)."""
         img = _check_bgr(img)
         h, w = img.shape[:2]
-        L = self.ctx.L
-        rc = L.infur_scale_validate(float(np.float32(factor)))
+        f = float(np.float32(factor))
+        rc = self.ctx.L.infur_scale_validate(f)
         if rc:
             raise ValidScaleError(rc)
         ow, oh = C.c_uint32(0), C.c_uint32(0)
-        rc = L.infur_scale_out_dims(w, h, float(np.float32(factor)), C.byref(ow), C.byref(oh))
+        rc = self.ctx.L.infur_scale_out_dims(w, h, f, C.byref(ow), C.byref(oh))
         if rc:
             raise ScaleProcError(rc)
-        rgba = np.empty((oh.value, ow.value, 4), np.uint8)
-        scaled = np.empty((oh.value, ow.value, 3), np.uint8) if want_scaled else None
-        rc = L.infur_frame_advance(self.ctx.h, img.ctypes.data, w, h, float(np.float32(factor)), self.scale_mode,
-                                   rgba.ctypes.data, rgba.nbytes, scaled.ctypes.data if want_scaled else None,
-                                   C.byref(ow), C.byref(oh))
+        return img, w, h, f, ow, oh
+
+    def _num_classes(self) -> int:
+        """the loaded model's class count, 0 without a model"""
+        mi = _lib.ModelInfoC()
+        return mi.num_classes if self.ctx.L.infur_model_info_get(self.ctx.h, C.byref(mi)) == _lib.OK else 0
+
+    @staticmethod
+    def _plane(ow, oh, want: bool, dtype=np.uint8, channels: int = 0) -> Optional[np.ndarray]:
+        """an optional output of the scaled frame's size: [oh, ow] or [oh, ow, channels]"""
+        return np.empty((oh.value, ow.value) + ((channels,) if channels else ()), dtype) if want else None
+
+    @staticmethod
+    def _stats(k: int, want: bool) -> Optional[np.ndarray]:
+        return np.zeros((k, _lib.STAT_WORDS), np.uint64) if want else None
+
+    def _loaded(self, rc: int) -> bool:
+        """The no-model rule: False when the call found no model -- the Scale stage has run, every result but ``scaled`` is None
+        (the mask is cleared, app.rs:127-129); any other failure raises."""
         if rc == _lib.E_MODEL_NOT_LOADED:
-            return None, scaled  # mask cleared (app.rs:127-129)
+            return False
         self.ctx.check(rc)
-        return rgba, scaled
+        return True
+
+    def advance(self, img: np.ndarray, factor: float = 1.0, want_scaled: bool = False):
+        """-> (rgba [oh,ow,4] u8 or None when no model is loaded, scaled BGR or None)."""
+        img, w, h, f, ow, oh = self._front(img, factor)
+        rgba = self._plane(ow, oh, True, channels=4)
+        scaled = self._plane(ow, oh, want_scaled, channels=3)
+        rc = self.ctx.L.infur_frame_advance(self.ctx.h, img.ctypes.data, w, h, f, self.scale_mode, rgba.ctypes.data, rgba.nbytes, _ptr(scaled),
+                                            C.byref(ow), C.byref(oh))
+        return (rgba if self._loaded(rc) else None), scaled
 
     def advance_segments(self, img: np.ndarray, factor: float = 1.0, decode: int = _lib.DECODE_RAW, want_rgba: bool = False,
                          want_scaled: bool = False, want_klass: bool = True, want_conf: bool = True,
                          want_stats: bool = True) -> SegmentsFrame:
         """The same fused path with the Segments decode instead of ColorCode -> ``SegmentsFrame``; every result field is None
         when no model is loaded (``scaled`` is still produced)."""
-        img = _check_bgr(img)
-        h, w = img.shape[:2]
-        L = self.ctx.L
-        f = float(np.float32(factor))
-        rc = L.infur_scale_validate(f)
-        if rc:
-            raise ValidScaleError(rc)
-        ow, oh = C.c_uint32(0), C.c_uint32(0)
-        rc = L.infur_scale_out_dims(w, h, f, C.byref(ow), C.byref(oh))
-        if rc:
-            raise ScaleProcError(rc)
-        mi = _lib.ModelInfoC()
-        k = mi.num_classes if L.infur_model_info_get(self.ctx.h, C.byref(mi)) == _lib.OK else 0
-        klass = np.empty((oh.value, ow.value), np.uint8) if want_klass else None
-        conf = np.empty((oh.value, ow.value), np.uint8) if want_conf else None
-        stats = np.zeros((k, _lib.STAT_WORDS), np.uint64) if want_stats else None
-        rgba = np.empty((oh.value, ow.value, 4), np.uint8) if want_rgba else None
-        scaled = np.empty((oh.value, ow.value, 3), np.uint8) if want_scaled else None
-        ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
-        rc = L.infur_frame_segments(self.ctx.h, img.ctypes.data, w, h, f, self.scale_mode, decode, ptr(klass), ptr(conf),
-                                    oh.value * ow.value, ptr(stats), k, ptr(rgba), rgba.nbytes if want_rgba else 0, ptr(scaled),
-                                    C.byref(ow), C.byref(oh))
-        if rc == _lib.E_MODEL_NOT_LOADED:
+        img, w, h, f, ow, oh = self._front(img, factor)
+        k = self._num_classes()
+        klass, conf = self._plane(ow, oh, want_klass), self._plane(ow, oh, want_conf)
+        stats = self._stats(k, want_stats)
+        rgba, scaled = self._plane(ow, oh, want_rgba, channels=4), self._plane(ow, oh, want_scaled, channels=3)
+        rc = self.ctx.L.infur_frame_segments(self.ctx.h, img.ctypes.data, w, h, f, self.scale_mode, decode, _ptr(klass), _ptr(conf),
+                                             oh.value * ow.value, _ptr(stats), k, _ptr(rgba), rgba.nbytes if want_rgba else 0, _ptr(scaled),
+                                             C.byref(ow), C.byref(oh))
+        if not self._loaded(rc):
             return SegmentsFrame(None, None, None, None, scaled)
-        self.ctx.check(rc)
         return SegmentsFrame(klass, conf, stats, rgba, scaled)
 
     def advance_regions(self, img: np.ndarray, factor: float = 1.0, decode: int = _lib.DECODE_RAW, connectivity: int = _lib.CONNECT_8,
@@ -1253,32 +1281,19 @@ class FramePath:
                         want_conf: bool = True, want_scaled: bool = False) -> RegionsFrame:
         """The fused path with both decode stages, scale -> model -> Segments decode -> Regions, in one call -> ``RegionsFrame``;
         every result field is None when no model is loaded (``scaled`` is still produced)."""
-        img = _check_bgr(img)
-        h, w = img.shape[:2]
-        L = self.ctx.L
-        f = float(np.float32(factor))
-        rc = L.infur_scale_validate(f)
-        if rc:
-            raise ValidScaleError(rc)
-        ow, oh = C.c_uint32(0), C.c_uint32(0)
-        rc = L.infur_scale_out_dims(w, h, f, C.byref(ow), C.byref(oh))
-        if rc:
-            raise ScaleProcError(rc)
+        img, w, h, f, ow, oh = self._front(img, factor)
         npix = oh.value * ow.value
         rows = max(0, min(int(table_rows), npix))
-        klass = np.empty((oh.value, ow.value), np.uint8) if want_klass else None
-        conf = np.empty((oh.value, ow.value), np.uint8) if want_conf else None
-        labels = np.empty((oh.value, ow.value), np.uint32) if want_labels else None
+        klass, conf = self._plane(ow, oh, want_klass), self._plane(ow, oh, want_conf)
+        labels = self._plane(ow, oh, want_labels, np.uint32)
         table = np.zeros((rows, _lib.REGION_WORDS), np.uint64) if rows else None
-        scaled = np.empty((oh.value, ow.value, 3), np.uint8) if want_scaled else None
+        scaled = self._plane(ow, oh, want_scaled, channels=3)
         n = C.c_uint32(0)
-        ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
-        rc = L.infur_frame_regions(self.ctx.h, img.ctypes.data, w, h, f, self.scale_mode, decode, connectivity, min_pixels, flags,
-                                   ptr(klass), ptr(conf), npix, ptr(labels), npix * 4, ptr(table), rows, C.addressof(n), ptr(scaled),
-                                   C.byref(ow), C.byref(oh))
-        if rc == _lib.E_MODEL_NOT_LOADED:
+        rc = self.ctx.L.infur_frame_regions(self.ctx.h, img.ctypes.data, w, h, f, self.scale_mode, decode, connectivity, min_pixels, flags,
+                                            _ptr(klass), _ptr(conf), npix, _ptr(labels), npix * 4, _ptr(table), rows, C.addressof(n), _ptr(scaled),
+                                            C.byref(ow), C.byref(oh))
+        if not self._loaded(rc):
             return RegionsFrame(None, None, None, None, None, scaled)
-        self.ctx.check(rc)
         return RegionsFrame(klass, conf, labels, table[:min(n.value, rows)] if table is not None else None, n.value, scaled)
 
     def advance_tracks(self, tracks: "Tracks", img: np.ndarray, factor: float = 1.0, decode: int = _lib.DECODE_RAW,
@@ -1287,37 +1302,24 @@ class FramePath:
                        want_plane: bool = False) -> TracksFrame:
         """The fused path with all three decode stages, scale -> model -> Segments decode -> Regions -> Tracks, in one call ->
         ``TracksFrame``; every result field is None when no model is loaded (``scaled`` is still produced)."""
-        img = _check_bgr(img)
-        h, w = img.shape[:2]
-        L = self.ctx.L
-        f = float(np.float32(factor))
-        rc = L.infur_scale_validate(f)
-        if rc:
-            raise ValidScaleError(rc)
-        ow, oh = C.c_uint32(0), C.c_uint32(0)
-        rc = L.infur_scale_out_dims(w, h, f, C.byref(ow), C.byref(oh))
-        if rc:
-            raise ScaleProcError(rc)
+        img, w, h, f, ow, oh = self._front(img, factor)
         npix = oh.value * ow.value
         rows = max(0, min(int(table_rows), npix))
-        klass = np.empty((oh.value, ow.value), np.uint8) if want_klass else None
-        conf = np.empty((oh.value, ow.value), np.uint8) if want_conf else None
-        labels = np.empty((oh.value, ow.value), np.uint32) if want_labels else None
+        klass, conf = self._plane(ow, oh, want_klass), self._plane(ow, oh, want_conf)
+        labels = self._plane(ow, oh, want_labels, np.uint32)
         table = np.zeros((rows, _lib.REGION_WORDS), np.uint64) if rows else None
-        scaled = np.empty((oh.value, ow.value, 3), np.uint8) if want_scaled else None
+        scaled = self._plane(ow, oh, want_scaled, channels=3)
         tor = np.empty(rows, np.uint32) if rows else None
         ttab = np.empty((rows, _lib.TRACK_WORDS), np.uint64) if rows else None
-        plane = np.empty((oh.value, ow.value), np.uint32) if want_plane else None
+        plane = self._plane(ow, oh, want_plane, np.uint32)
         summary = np.zeros(_lib.TRACKS_SUMMARY_WORDS, np.uint32)
         n = C.c_uint32(0)
-        ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
-        rc = L.infur_frame_tracks(self.ctx.h, img.ctypes.data, w, h, f, self.scale_mode, decode, connectivity, min_pixels, flags,
-                                  ptr(klass), ptr(conf), npix, ptr(labels), npix * 4, ptr(table), rows, C.addressof(n), ptr(scaled),
-                                  C.byref(ow), C.byref(oh), tracks.t, tracks.min_overlap, ptr(tor), ptr(plane), ptr(ttab),
-                                  summary.ctypes.data)
-        if rc == _lib.E_MODEL_NOT_LOADED:
+        rc = self.ctx.L.infur_frame_tracks(self.ctx.h, img.ctypes.data, w, h, f, self.scale_mode, decode, connectivity, min_pixels, flags,
+                                           _ptr(klass), _ptr(conf), npix, _ptr(labels), npix * 4, _ptr(table), rows, C.addressof(n), _ptr(scaled),
+                                           C.byref(ow), C.byref(oh), tracks.t, tracks.min_overlap, _ptr(tor), _ptr(plane), _ptr(ttab),
+                                           summary.ctypes.data)
+        if not self._loaded(rc):
             return TracksFrame(None, None, None, None, None, scaled, None, None, None, None)
-        self.ctx.check(rc)
         k = min(n.value, rows)
         return TracksFrame(klass, conf, labels, table[:k] if table is not None else None, n.value, scaled,
                            tor[:k] if tor is not None else None, ttab[:k] if ttab is not None else None, plane, summary)
@@ -1328,32 +1330,18 @@ class FramePath:
         """The fused path with the class plane run-length encoded, scale -> model -> Segments decode -> Runs, in one call ->
         ``RunsFrame``: no dense plane crosses PCIe.  Every result field is None when no model is loaded (``scaled`` is still
         produced)."""
-        img = _check_bgr(img)
-        h, w = img.shape[:2]
-        L = self.ctx.L
-        f = float(np.float32(factor))
-        rc = L.infur_scale_validate(f)
-        if rc:
-            raise ValidScaleError(rc)
-        ow, oh = C.c_uint32(0), C.c_uint32(0)
-        rc = L.infur_scale_out_dims(w, h, f, C.byref(ow), C.byref(oh))
-        if rc:
-            raise ScaleProcError(rc)
-        mi = _lib.ModelInfoC()
-        k = mi.num_classes if L.infur_model_info_get(self.ctx.h, C.byref(mi)) == _lib.OK else 0
+        img, w, h, f, ow, oh = self._front(img, factor)
+        k = self._num_classes()
         rows = max(0, min(int(runs_rows), oh.value * ow.value))
         runs = np.empty((rows, _lib.RUN_WORDS), np.uint32) if rows else None
         row_start = np.empty(oh.value + 1, np.uint32) if want_row_start else None
-        stats = np.zeros((k, _lib.STAT_WORDS), np.uint64) if want_stats else None
-        scaled = np.empty((oh.value, ow.value, 3), np.uint8) if want_scaled else None
+        stats, scaled = self._stats(k, want_stats), self._plane(ow, oh, want_scaled, channels=3)
         n = C.c_uint32(0)
-        ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
-        rc = L.infur_frame_runs(self.ctx.h, img.ctypes.data, w, h, f, self.scale_mode, decode, _lib.RUNS_SKIP if skip is not None else 0,
-                                skip or 0, ptr(runs), rows, ptr(row_start), oh.value + 1, C.addressof(n), ptr(stats), k, ptr(scaled),
-                                C.byref(ow), C.byref(oh))
-        if rc == _lib.E_MODEL_NOT_LOADED:
+        rc = self.ctx.L.infur_frame_runs(self.ctx.h, img.ctypes.data, w, h, f, self.scale_mode, decode, _lib.RUNS_SKIP if skip is not None else 0,
+                                         skip or 0, _ptr(runs), rows, _ptr(row_start), oh.value + 1, C.addressof(n), _ptr(stats), k, _ptr(scaled),
+                                         C.byref(ow), C.byref(oh))
+        if not self._loaded(rc):
             return RunsFrame(None, None, None, None, scaled)
-        self.ctx.check(rc)
         return RunsFrame(runs[:min(n.value, rows)] if runs is not None else None, row_start, n.value, stats, scaled)
 
     def advance_outlines(self, img: np.ndarray, factor: float = 1.0, decode: int = _lib.DECODE_RAW, skip: Optional[int] = None,
@@ -1362,36 +1350,26 @@ class FramePath:
         """The fused path with the class plane outlined, scale -> model -> Segments decode -> Outlines, in one call ->
         ``OutlinesFrame``: no dense plane crosses PCIe.  Every result field is None when no model is loaded (``scaled`` is still
         produced)."""
-        img = _check_bgr(img)
-        h, w = img.shape[:2]
-        L = self.ctx.L
-        f = float(np.float32(factor))
-        rc = L.infur_scale_validate(f)
-        if rc:
-            raise ValidScaleError(rc)
-        ow, oh = C.c_uint32(0), C.c_uint32(0)
-        rc = L.infur_scale_out_dims(w, h, f, C.byref(ow), C.byref(oh))
-        if rc:
-            raise ScaleProcError(rc)
-        mi = _lib.ModelInfoC()
-        k = mi.num_classes if L.infur_model_info_get(self.ctx.h, C.byref(mi)) == _lib.OK else 0
+        return self._advance_poly("infur_frame_outlines", OutlinesFrame, 3, False, (), img, factor, decode, skip, connectivity, max_edges, loops_rows,
+                                  vertex_rows, want_stats, want_scaled)
+
+    def _advance_poly(self, symbol: str, result, count_words: int, lattice: bool, tol: tuple, img, factor, decode, skip, connectivity, max_edges,
+                      loops_rows, vertex_rows, want_stats, want_scaled):
+        """The body of the three polygon calls: ``symbol`` with ``count_words`` counts -> ``result``.  ``lattice``: the vertices may
+        include the lattice's junctions (Coverage); ``tol``: the arguments between ``max_edges`` and the outputs.  The slices
+        follow the counts alone, whatever the status word says."""
+        img, w, h, f, ow, oh = self._front(img, factor)
+        k = self._num_classes()
         npix = oh.value * ow.value
-        lrows, vrows = max(0, min(int(loops_rows), npix)), max(0, min(int(vertex_rows), 4 * npix))
-        loops = np.empty((lrows, _lib.LOOP_WORDS), np.uint32) if lrows else None
-        vertices = np.empty(vrows, np.uint32) if vrows else None
-        counts = np.zeros(3, np.uint32)
-        stats = np.zeros((k, _lib.STAT_WORDS), np.uint64) if want_stats else None
-        scaled = np.empty((oh.value, ow.value, 3), np.uint8) if want_scaled else None
-        ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
-        rc = L.infur_frame_outlines(self.ctx.h, img.ctypes.data, w, h, f, self.scale_mode, decode, _outlines_flags(skip, connectivity), skip or 0,
-                                    max_edges, ptr(loops), lrows, ptr(vertices), vrows, counts.ctypes.data, ptr(stats), k, ptr(scaled),
-                                    C.byref(ow), C.byref(oh))
-        if rc == _lib.E_MODEL_NOT_LOADED:
-            return OutlinesFrame(None, None, None, None, scaled, (oh.value, ow.value))
-        self.ctx.check(rc)
-        nl, nv, ne = (int(v) for v in counts)
-        return OutlinesFrame(loops[:min(nl, lrows)] if loops is not None else None, vertices[:min(nv, vrows)] if vertices is not None else None,
-                             (nl, nv, ne), stats, scaled, (oh.value, ow.value))
+        loops, vertices = _poly_alloc(loops_rows, npix, vertex_rows, 4 * npix + ((oh.value + 1) * (ow.value + 1) if lattice else 0))
+        counts = np.zeros(count_words, np.uint32)
+        stats, scaled = self._stats(k, want_stats), self._plane(ow, oh, want_scaled, channels=3)
+        rc = getattr(self.ctx.L, symbol)(self.ctx.h, img.ctypes.data, w, h, f, self.scale_mode, decode, _outlines_flags(skip, connectivity), skip or 0,
+                                         max_edges, *tol, _ptr(loops), _poly_rows(loops), _ptr(vertices), _poly_rows(vertices), counts.ctypes.data,
+                                         _ptr(stats), k, _ptr(scaled), C.byref(ow), C.byref(oh))
+        if not self._loaded(rc):
+            return result(None, None, None, None, scaled, (oh.value, ow.value))
+        return result(*_poly_slice(loops, vertices, counts), tuple(int(v) for v in counts), stats, scaled, (oh.value, ow.value))
 
     def advance_polygons(self, img: np.ndarray, factor: float = 1.0, decode: int = _lib.DECODE_RAW, tol16: int = 16, skip: Optional[int] = None,
                          connectivity: int = 4, max_edges: int = 0, loops_rows: int = 1 << 16, vertex_rows: int = 1 << 20,
@@ -1399,36 +1377,8 @@ class FramePath:
         """The fused path with simplified polygons, scale -> model -> Segments decode -> Outlines -> Simplify within ``tol16``
         sixteenths of a pixel, in one call -> ``PolygonsFrame``.  Every result field is None when no model is loaded (``scaled`` is
         still produced)."""
-        img = _check_bgr(img)
-        h, w = img.shape[:2]
-        L = self.ctx.L
-        f = float(np.float32(factor))
-        rc = L.infur_scale_validate(f)
-        if rc:
-            raise ValidScaleError(rc)
-        ow, oh = C.c_uint32(0), C.c_uint32(0)
-        rc = L.infur_scale_out_dims(w, h, f, C.byref(ow), C.byref(oh))
-        if rc:
-            raise ScaleProcError(rc)
-        mi = _lib.ModelInfoC()
-        k = mi.num_classes if L.infur_model_info_get(self.ctx.h, C.byref(mi)) == _lib.OK else 0
-        npix = oh.value * ow.value
-        lrows, vrows = max(0, min(int(loops_rows), npix)), max(0, min(int(vertex_rows), 4 * npix))
-        loops = np.empty((lrows, _lib.LOOP_WORDS), np.uint32) if lrows else None
-        vertices = np.empty(vrows, np.uint32) if vrows else None
-        counts = np.zeros(_lib.SIMPLIFY_COUNT_WORDS, np.uint32)
-        stats = np.zeros((k, _lib.STAT_WORDS), np.uint64) if want_stats else None
-        scaled = np.empty((oh.value, ow.value, 3), np.uint8) if want_scaled else None
-        ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
-        rc = L.infur_frame_polygons(self.ctx.h, img.ctypes.data, w, h, f, self.scale_mode, decode, _outlines_flags(skip, connectivity), skip or 0,
-                                    max_edges, tol16, ptr(loops), lrows, ptr(vertices), vrows, counts.ctypes.data, ptr(stats), k, ptr(scaled),
-                                    C.byref(ow), C.byref(oh))
-        if rc == _lib.E_MODEL_NOT_LOADED:
-            return PolygonsFrame(None, None, None, None, scaled, (oh.value, ow.value))
-        self.ctx.check(rc)
-        nl, nv = int(counts[0]), int(counts[1])
-        return PolygonsFrame(loops[:min(nl, lrows)] if loops is not None else None, vertices[:min(nv, vrows)] if vertices is not None else None,
-                             tuple(int(v) for v in counts), stats, scaled, (oh.value, ow.value))
+        return self._advance_poly("infur_frame_polygons", PolygonsFrame, _lib.SIMPLIFY_COUNT_WORDS, False, (tol16,), img, factor, decode, skip,
+                                  connectivity, max_edges, loops_rows, vertex_rows, want_stats, want_scaled)
 
     def advance_coverage(self, img: np.ndarray, factor: float = 1.0, decode: int = _lib.DECODE_RAW, tol16: int = 16, skip: Optional[int] = None,
                          connectivity: int = 4, max_edges: int = 0, loops_rows: int = 1 << 16, vertex_rows: int = 1 << 20,
@@ -1436,36 +1386,8 @@ class FramePath:
         """The fused path with polygons that fit, scale -> model -> Segments decode -> Outlines -> Coverage within ``tol16``
         sixteenths of a pixel, in one call -> ``PolygonsFrame`` whose counts are Coverage's six (n_loops, n_vertices, n_degenerate,
         status, n_aug, n_arcs).  Every result field is None when no model is loaded (``scaled`` is still produced)."""
-        img = _check_bgr(img)
-        h, w = img.shape[:2]
-        L = self.ctx.L
-        f = float(np.float32(factor))
-        rc = L.infur_scale_validate(f)
-        if rc:
-            raise ValidScaleError(rc)
-        ow, oh = C.c_uint32(0), C.c_uint32(0)
-        rc = L.infur_scale_out_dims(w, h, f, C.byref(ow), C.byref(oh))
-        if rc:
-            raise ScaleProcError(rc)
-        mi = _lib.ModelInfoC()
-        k = mi.num_classes if L.infur_model_info_get(self.ctx.h, C.byref(mi)) == _lib.OK else 0
-        npix = oh.value * ow.value
-        lrows, vrows = max(0, min(int(loops_rows), npix)), max(0, min(int(vertex_rows), 4 * npix + (oh.value + 1) * (ow.value + 1)))
-        loops = np.empty((lrows, _lib.LOOP_WORDS), np.uint32) if lrows else None
-        vertices = np.empty(vrows, np.uint32) if vrows else None
-        counts = np.zeros(_lib.COVERAGE_COUNT_WORDS, np.uint32)
-        stats = np.zeros((k, _lib.STAT_WORDS), np.uint64) if want_stats else None
-        scaled = np.empty((oh.value, ow.value, 3), np.uint8) if want_scaled else None
-        ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
-        rc = L.infur_frame_coverage(self.ctx.h, img.ctypes.data, w, h, f, self.scale_mode, decode, _outlines_flags(skip, connectivity), skip or 0,
-                                    max_edges, tol16, ptr(loops), lrows, ptr(vertices), vrows, counts.ctypes.data, ptr(stats), k, ptr(scaled),
-                                    C.byref(ow), C.byref(oh))
-        if rc == _lib.E_MODEL_NOT_LOADED:
-            return PolygonsFrame(None, None, None, None, scaled, (oh.value, ow.value))
-        self.ctx.check(rc)
-        nl, nv = int(counts[0]), int(counts[1])
-        return PolygonsFrame(loops[:min(nl, lrows)] if loops is not None else None, vertices[:min(nv, vrows)] if vertices is not None else None,
-                             tuple(int(v) for v in counts), stats, scaled, (oh.value, ow.value))
+        return self._advance_poly("infur_frame_coverage", PolygonsFrame, _lib.COVERAGE_COUNT_WORDS, True, (tol16,), img, factor, decode, skip,
+                                  connectivity, max_edges, loops_rows, vertex_rows, want_stats, want_scaled)
 
     def advance_batch(self, imgs, factor: float = 1.0, outs=None):
         """A batch of independent frames (BASELINE configs[3]) -> list of masks, in order.  ``outs``: caller-owned mask arrays to fill
