@@ -74,10 +74,12 @@ def test_fused_pair_is_bit_identical_to_two_launches(tmp_path, depth, pairs, for
 ORACLE_SCRIPT = r"""
 import sys, ctypes as C, numpy as np
 sys.path.insert(0, sys.argv[1])
+sys.path.insert(0, sys.argv[1] + "/tests")
+import accuracy as A
 from infur_amd import weights as W
 from infur_amd.processors import Context, Model, ModelCmd
 from oracle.infur_oracle import COracle, TorchModel
-F16_TOL = 5e-3  # the f16 mode's stated tolerance against the f32 oracle (tests/test_gpu_f16_r101.py)
+F16_TOL = A.WAS[("f16", "friendly/layer")][0]  # 5e-3: the f16 mode's stated tolerance against the f32 oracle before tests/accuracy.py's table
 blob = W.synth_blob()
 co, tm = COracle(), TorchModel(blob)
 c = Context(device=0, dtype="f16", keep_activations=True, profile=True)
@@ -95,7 +97,7 @@ for i, spec in enumerate(W.graph(50)):
     cc, hh, ww = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
     c.check(c.L.infur_debug_read_activation(c.h, i, buf.ctypes.data, buf.size, C.byref(cc), C.byref(hh), C.byref(ww)))
     assert (cc.value, hh.value, ww.value) == ref.shape, spec.name
-    e = float(np.abs(buf.astype(np.float64) - ref).max() / max(np.abs(ref).max(), 1e-30))
+    e = A.grade(buf, ref, "f16", "friendly/layer", "241x135 fused pairs " + spec.name)[0]  # (four readings, the table's bars)
     worst = max(worst, e)
     assert e < F16_TOL, (spec.name, e)
 print("f16 + fused pairs: per-layer worst rel err", worst)

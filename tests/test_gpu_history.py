@@ -17,6 +17,7 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 if HERE not in sys.path:
     sys.path.insert(0, HERE)
+import accuracy as A  # noqa: E402
 import history as H  # noqa: E402
 from test_gpu_f16_r101 import F16_TOL  # noqa: E402
 from test_gpu_hl import HL_TOL  # noqa: E402
@@ -28,6 +29,7 @@ from infur_amd import weights as W  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
+# the old bars; the comparison itself is graded by tests/accuracy.py (four readings, scope "edge")
 ORACLE_TOL = {"f32": REL_TOL, "f32s": SPLIT_TOL, "f32x": FP8X_TOL, "f16hl": HL_TOL, "f16": F16_TOL}  # i8: bit-exact (Q.qforward)
 T0 = H.FULL_TARGET  # (75, 109)
 
@@ -40,8 +42,7 @@ def target_frame(size):
     return W.synth_frame(size[0], size[1], index=H.target_index(size))
 
 
-def rel_err(a, b):
-    return float(np.abs(a.astype(np.float64) - b).max() / max(np.abs(b).max(), 1e-30))
+rel_err = A.rel_err  # (one definition: tests/accuracy.py::readings)
 
 
 @pytest.fixture(scope="module")
@@ -130,8 +131,11 @@ def test_outputs_do_not_depend_on_history(mode, target, blobs, fresh, oracle):
         from oracle.infur_oracle import TorchModel
 
         tl, ta = TorchModel(blob).forward_lowres(oracle.pack_normalize(fr))
-        e_out, e_aux = rel_err(ref["lo"], tl.numpy()), rel_err(ref["la"], ta.numpy())
-        print(f"{mode} {tag(target)}: fresh logits rel err out={e_out:.2e} aux={e_aux:.2e} (bar {ORACLE_TOL[mode]:g})")
+        cap = (ORACLE_TOL[mode], None, None, None)
+        r_out = A.grade(ref["lo"], tl.numpy(), mode, "edge", f"{tag(target)} fresh out", cap=cap)
+        r_aux = A.grade(ref["la"], ta.numpy(), mode, "edge", f"{tag(target)} fresh aux", cap=cap)
+        e_out, e_aux = r_out[0], r_aux[0]
+        print(f"{mode} {tag(target)}: fresh logits rel err out={e_out:.2e} aux={e_aux:.2e} (old bar {ORACLE_TOL[mode]:g}); (max_rel, elem, rms, bias) out {A.fmt(r_out)} aux {A.fmt(r_aux)}")
         assert e_out < ORACLE_TOL[mode] and e_aux < ORACLE_TOL[mode]
         assert (ref["out"].view(np.uint32) == oracle.upsample_bilinear(ref["lo"], h, w).view(np.uint32)).all()
     assert (ref["rgba"] == oracle.colorcode(oracle.upsample_bilinear(ref["lo"], h, w))).all()

@@ -57,6 +57,7 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 if HERE not in sys.path:
     sys.path.insert(0, HERE)
+import accuracy as A  # noqa: E402
 import forms as F  # noqa: E402
 import test_gpu_forms as TF  # noqa: E402
 from test_gpu_forms import mode_bars, rel_err  # noqa: E402
@@ -158,16 +159,18 @@ class _Grader(dict):
     """what TorchModel.forward_lowres is given as `taps`: grades each layer as its float64 reference arrives and keeps the error only
     (the references of a 777x897 frame are 2.9 GB)"""
 
-    def __init__(self, run, size):
+    def __init__(self, run, size, mode, what, cap):
         super().__init__()
-        self.run, self.size, self.err = run, size, {}
+        self.mode, self.what, self.cap = mode, what, cap
+        self.run, self.size, self.err, self.readings = run, size, {}, {}
 
     def __setitem__(self, name, ref):
         ref = ref.numpy() if hasattr(ref, "numpy") else ref
         got = self.run[f"L/{F.tag(self.size)}/{name}"]
         assert got.shape == ref.shape, (self.size, name, got.shape, ref.shape)
         assert np.abs(ref).max() > 0.1, (self.size, name)  # (the denominator is never degenerate: test_gpu_forms.py)
-        self.err[name] = rel_err(got, ref)
+        self.readings[name] = A.grade(got, ref, self.mode, "edge", f"{self.what} {F.tag(self.size)} {name}", cap=self.cap, check=False)
+        self.err[name] = self.readings[name][0]
 
 
 def reference_logits(oracle, size):
@@ -189,14 +192,15 @@ def grade_baseline(run, case, oracle):
     tm = TorchModel(W.synth_blob(), float64=True)
     for size in F.SIZE_SETS[case.sizes]:
         h, w = size
-        g = _Grader(run, size)
+        cap = (bar, None, None, None)
+        g = _Grader(run, size, case.mode, case.id, cap)
         lo, la = tm.forward_lowres(oracle.pack_normalize(W.synth_frame(h, w, index=h + w)), taps=g)
         g["out_low"], g["aux_low"] = lo, la
         assert len(g.err) == 59, len(g.err)
         worst = max(g.err, key=g.err.get)
         print(f"{case.id} {F.tag(size)}: worst layer {g.err[worst]:.2e} ({worst}), bar {bar:g}")
-        over = [(n, e) for n, e in g.err.items() if not e < bar]
-        assert not over, f"{case.id} {F.tag(size)}: (layer, error) over the bar {bar:g}: {over}"
+        over = [A.message(r, case.mode, "edge", f"{case.id} {F.tag(size)} {n}", cap) for n, r in g.readings.items() if A.failures(r, case.mode, "edge", cap)]
+        assert not over, "over the bar:\n" + "\n".join(over)
         assert (run[f"P/{F.tag(size)}/rgba"] == oracle.colorcode(oracle.upsample_bilinear(run[f"P/{F.tag(size)}/out_low"], h, w))).all(), (case.id, size)
 
 
@@ -207,7 +211,9 @@ def grade_product_logits(run, case, oracle, refs):
         h, w = size
         if size not in refs:
             refs[size] = reference_logits(oracle, size)
-        e_out, e_aux = rel_err(run[f"P/{F.tag(size)}/out_low"], refs[size][0]), rel_err(run[f"P/{F.tag(size)}/aux_low"], refs[size][1])
+        cap = (bar, None, None, None)
+        e_out = A.grade(run[f"P/{F.tag(size)}/out_low"], refs[size][0], case.mode, "edge", f"{case.id} {F.tag(size)} product path out_low", cap=cap)[0]
+        e_aux = A.grade(run[f"P/{F.tag(size)}/aux_low"], refs[size][1], case.mode, "edge", f"{case.id} {F.tag(size)} product path aux_low", cap=cap)[0]
         print(f"{case.id} {F.tag(size)}: product path logits out {e_out:.2e} aux {e_aux:.2e}, bar {bar:g}")
         assert e_out < bar and e_aux < bar, (case.id, size, e_out, e_aux, bar)
         assert (run[f"P/{F.tag(size)}/rgba"] == oracle.colorcode(oracle.upsample_bilinear(run[f"P/{F.tag(size)}/out_low"], h, w))).all(), (case.id, size)
@@ -236,7 +242,7 @@ def test_subform_ran_and_gives_configuration_0s_bits(shared, oracle, case):
         else:  # "layers": every layer at every size against the float64 reference, at the mode's stated bar
             assert case.sizes == "edge" and sorted(base.keys()) == sorted(run.keys())
             print(f"{case.id}: tensors that differ from the baseline's bytes: L/ {len(F.byte_differences(base, run, 'L/'))}, P/ {len(F.byte_differences(base, run, 'P/'))}")
-            TF.grade_float(run, case.mode, shared.forms.float_taps(oracle), oracle)
+            TF.grade_float(run, case.mode, shared.forms.float_taps(oracle), oracle, what=case.id + " ")
     finally:
         if not case.baseline:
             run.discard()
