@@ -263,10 +263,16 @@ class TorchModel:
         if float64:
             self.params = [(w.double(), b.double()) for w, b in self.params]
 
-    def forward_lowres(self, chw: np.ndarray, taps=None):
+    def forward_lowres(self, chw: np.ndarray, taps=None, forced=None):
         """[3,h,w] f32 -> (out_low [K,lh,lw], aux_low or None) as torch tensors.
 
         ``taps``: optional dict filled with per-conv outputs (name -> tensor [C,H,W]).
+        ``forced``: optional dict name -> [C,H,W] array.  Every conv's output is computed and tapped as without it; what is
+        handed DOWNSTREAM -- to the max-pool, the next conv, the add of a downsample branch, the residual of later blocks,
+        the aux head, the returned logits -- is ``forced[name]`` in the model's dtype instead (a conv the dict does not name
+        hands on what it computed).  With an entry for every conv, taps[name] is that one layer's result (bias, residual,
+        ReLU as in the graph) on the inputs of ``forced``: with the tensors a device stored, the layer's own arithmetic with
+        the upstream error taken out (tests/own_error.py).  None changes nothing.
         """
         torch = self.torch
         F = torch.nn.functional
@@ -274,6 +280,14 @@ class TorchModel:
         if self.float64:
             x = x.double()
         it = iter(zip(self.specs, self.params))
+
+        def give(name, y):
+            """the tensor the consumers of conv `name` see"""
+            if forced is None or name not in forced:
+                return y
+            f = torch.from_numpy(np.ascontiguousarray(forced[name])).to(y.dtype)[None]
+            assert f.shape == y.shape, (name, tuple(f.shape), tuple(y.shape))
+            return f
 
         def conv(x, residual=None):
             s, (w, b) = next(it)
@@ -284,7 +298,7 @@ class TorchModel:
                 y = F.relu(y)
             if taps is not None:
                 taps[s.name] = y[0]
-            return y, s
+            return give(s.name, y), s
 
         with torch.no_grad():
             x, _ = conv(x)
@@ -303,9 +317,10 @@ class TorchModel:
                     idt = F.conv2d(x, wd, bd, stride=sd.stride)
                     if taps is not None:
                         taps[sd.name] = idt[0]
-                    y = F.relu(F.conv2d(t, p3[0], p3[1]) + idt)
+                    y = F.relu(F.conv2d(t, p3[0], p3[1]) + give(sd.name, idt))
                     if taps is not None:
                         taps[s3.name] = y[0]
+                    y = give(s3.name, y)
                     i += 4
                 else:
                     y, s3 = conv(t, residual=x)

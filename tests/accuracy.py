@@ -25,6 +25,12 @@ Scopes (the sizes are the existing tests'; MEASURED is the worst over everything
                       modes' own logit tests
   edge                forms.SIZES, NATURAL_SIZES, GEOM_SIZES, the history.TARGETS size that meets an oracle and the tiny / ragged
                       lists: layers and logits
+  own/<kind>          tests/test_gpu_own_error.py: each conv layer ALONE, against the float64 evaluation of that layer on the inputs the
+                      device itself stored (tests/own_error.py) -- the kernel's own arithmetic, the error of the layers upstream taken
+                      out.  <kind> is the kernel family that ran the layer, read off the profile: 1x1, direct, wino2 / wino4 / wino6,
+                      head (the f32-output classifiers).  No bar existed before (WAS: none): the bar is 1.3 x MEASURED
+  own16/<kind>        f16 only: the same, the reference's conv weights rounded to f16 first -- the f32 accumulation and one rounding of
+                      the output remain (elem: 2^-11 = 4.88e-4 measured on the f16-output layers)
 The quantised model is bit-exact and has no row.
 
 MEASURED, on one MI355X against the float64 / f32 references the tests use (see LAB_NOTES.md for the bars next to the old ones):
@@ -57,6 +63,32 @@ f32s  edge               | 1.0e-05 6.0e-04 3.5e-06 7.0e-07 | 1.4e-05 7.8e-04 4.5
 f32x  edge               | 5.8e-04 2.6e-02 2.4e-04 1.5e-05 | 7.6e-04 3.5e-02 3.2e-04 2.0e-05 | 1.0e-03 -       -       -      
 f16   edge               | 2.1e-03 1.4e-01 1.2e-03 2.1e-04 | 2.7e-03 1.9e-01 1.6e-03 2.8e-04 | 5.0e-03 -       -       -      
 f16hl edge               | 5.6e-04 2.7e-02 2.6e-04 2.7e-05 | 7.4e-04 3.6e-02 3.4e-04 3.5e-05 | 1.0e-03 -       -       -      
+f32   own/1x1            | 2.3e-06 7.2e-05 6.9e-07 6.3e-09 | 3.1e-06 9.4e-05 9.1e-07 8.3e-09 | -       -       -       -      
+f32s  own/1x1            | 2.0e-06 3.7e-05 5.3e-07 3.4e-08 | 2.6e-06 4.8e-05 7.0e-07 4.5e-08 | -       -       -       -      
+f32x  own/1x1            | 8.4e-05 2.2e-03 3.2e-05 2.0e-06 | 1.1e-04 2.9e-03 4.2e-05 2.6e-06 | -       -       -       -      
+f16   own/1x1            | 6.6e-04 2.5e-02 3.8e-04 3.4e-05 | 8.6e-04 3.3e-02 5.0e-04 4.4e-05 | -       -       -       -      
+f16hl own/1x1            | 7.9e-05 1.9e-03 2.8e-05 1.9e-06 | 1.1e-04 2.5e-03 3.7e-05 2.5e-06 | -       -       -       -      
+f32   own/direct         | 4.0e-06 1.1e-04 2.0e-06 2.6e-08 | 5.2e-06 1.5e-04 2.6e-06 3.5e-08 | -       -       -       -      
+f32s  own/direct         | 3.0e-06 8.8e-05 1.5e-06 2.5e-07 | 3.9e-06 1.2e-04 2.0e-06 3.4e-07 | -       -       -       -      
+f32x  own/direct         | 4.1e-05 2.3e-03 2.7e-05 2.0e-06 | 5.4e-05 3.0e-03 3.6e-05 2.6e-06 | -       -       -       -      
+f16   own/direct         | 6.3e-04 3.2e-02 4.2e-04 5.0e-05 | 8.2e-04 4.2e-02 5.5e-04 6.5e-05 | -       -       -       -      
+f16hl own/direct         | 6.2e-05 2.6e-03 3.4e-05 2.6e-06 | 8.1e-05 3.4e-03 4.5e-05 3.4e-06 | -       -       -       -      
+f32   own/wino2          | 1.8e-06 7.3e-05 9.4e-07 1.0e-08 | 2.4e-06 9.6e-05 1.3e-06 1.4e-08 | -       -       -       -      
+f32   own/wino4          | 7.2e-06 2.4e-04 1.7e-06 4.3e-08 | 9.3e-06 3.1e-04 2.2e-06 5.6e-08 | -       -       -       -      
+f32x  own/wino4          | 3.0e-04 1.5e-02 7.9e-05 2.7e-06 | 4.0e-04 1.9e-02 1.1e-04 3.6e-06 | -       -       -       -      
+f16hl own/wino4          | 3.7e-04 1.8e-02 8.1e-05 2.0e-06 | 4.8e-04 2.3e-02 1.1e-04 2.6e-06 | -       -       -       -      
+f32   own/wino6          | 1.9e-05 4.3e-04 4.7e-06 3.7e-08 | 2.5e-05 5.6e-04 6.2e-06 4.9e-08 | -       -       -       -      
+f32s  own/wino6          | 2.1e-05 3.0e-04 4.2e-06 2.0e-07 | 2.7e-05 3.9e-04 5.5e-06 2.6e-07 | -       -       -       -      
+f32x  own/wino6          | 6.2e-04 2.6e-02 2.9e-04 4.3e-06 | 8.1e-04 3.5e-02 3.8e-04 5.6e-06 | -       -       -       -      
+f16hl own/wino6          | 7.7e-04 4.6e-02 3.0e-04 3.6e-06 | 1.1e-03 6.1e-02 4.0e-04 4.7e-06 | -       -       -       -      
+f32   own/head           | 6.2e-07 1.6e-05 2.8e-07 1.2e-08 | 8.1e-07 2.2e-05 3.7e-07 1.7e-08 | -       -       -       -      
+f32s  own/head           | 6.6e-07 1.4e-05 2.4e-07 2.5e-08 | 8.6e-07 1.9e-05 3.2e-07 3.2e-08 | -       -       -       -      
+f32x  own/head           | 2.9e-05 1.8e-03 2.1e-05 1.7e-06 | 3.8e-05 2.4e-03 2.8e-05 2.3e-06 | -       -       -       -      
+f16   own/head           | 2.4e-04 1.6e-02 2.2e-04 4.1e-05 | 3.2e-04 2.1e-02 2.9e-04 5.3e-05 | -       -       -       -      
+f16hl own/head           | 2.6e-05 1.8e-03 1.9e-05 3.1e-06 | 3.5e-05 2.3e-03 2.5e-05 4.1e-06 | -       -       -       -      
+f16   own16/1x1          | 4.3e-04 4.9e-04 2.2e-04 3.2e-06 | 5.7e-04 6.4e-04 2.9e-04 4.2e-06 | -       -       -       -      
+f16   own16/direct       | 4.6e-04 4.9e-04 2.2e-04 3.7e-06 | 6.0e-04 6.4e-04 2.9e-04 4.9e-06 | -       -       -       -      
+f16   own16/head         | 3.9e-07 1.1e-05 1.4e-07 4.1e-09 | 5.1e-07 1.4e-05 1.9e-07 5.4e-09 | -       -       -       -      
 """
 import json
 import math
@@ -66,7 +98,8 @@ import numpy as np
 
 NAMES = ("max_rel", "elem", "rms", "bias")
 MODES = ("f32", "f32s", "f32x", "f16", "f16hl")
-SCOPES = ("hostile/layer", "hostile/logits1080", "hostile/seeds", "friendly/layer", "friendly/logits", "edge")
+SCOPES = ("hostile/layer", "hostile/logits1080", "hostile/seeds", "friendly/layer", "friendly/logits", "edge",
+          "own/1x1", "own/direct", "own/wino2", "own/wino4", "own/wino6", "own/head", "own16/1x1", "own16/direct", "own16/head")
 HEADROOM = 1.3  # VERDICT round 6, "Next round" item 2 (ii)
 
 # every (mode, scope) a GPU test asks for (tests/test_accuracy_cpu.py holds the table against this and the GPU files against SCOPES)
@@ -77,6 +110,16 @@ ASKED = {
     "friendly/layer": ("f32", "f32s", "f16", "f16hl"),  # (f32x has no per-layer test on the friendly weights: its layers are "edge"'s)
     "friendly/logits": MODES,
     "edge": MODES,
+    # tests/own_error.py: the scope is the kernel family that ran the layer; the modes are those whose forced variants reach it
+    "own/1x1": MODES,
+    "own/direct": MODES,
+    "own/wino2": ("f32",),
+    "own/wino4": ("f32", "f32x", "f16hl"),
+    "own/wino6": ("f32", "f32s", "f32x", "f16hl"),
+    "own/head": MODES,
+    "own16/1x1": ("f16",),
+    "own16/direct": ("f16",),
+    "own16/head": ("f16",),
 }
 
 _ = None  # a reading that had no bar before this table
@@ -119,6 +162,8 @@ WAS = {
     ("f16", "edge"): (5e-3, _, _, _),
     ("f16hl", "edge"): (1e-3, _, _, _),
 }
+# the own-error scopes had no bar before their rows: the bar is 1.3 x MEASURED
+WAS.update({(m, s): (_, _, _, _) for s in SCOPES if s.startswith("own") for m in ASKED[s]})
 del _
 
 # measured on an MI355X at the commit that introduced this table: the worst value of each reading over everything the suite grades
@@ -152,6 +197,35 @@ MEASURED = {
     ("f32x", "edge"): (5.83e-04, 2.62e-02, 2.45e-04, 1.50e-05),
     ("f16", "edge"): (2.05e-03, 1.41e-01, 1.23e-03, 2.08e-04),
     ("f16hl", "edge"): (5.63e-04, 2.73e-02, 2.61e-04, 2.67e-05),
+    # tests/test_gpu_own_error.py, at the commit that introduced it: each layer against the float64 evaluation of THAT layer on the
+    # inputs the device stored (tests/own_error.py), the worst layer of every variant, both weight sets and the ResNet-101 case
+    ("f32", "own/1x1"): (2.31e-06, 7.16e-05, 6.93e-07, 6.34e-09),
+    ("f32s", "own/1x1"): (1.96e-06, 3.69e-05, 5.32e-07, 3.44e-08),
+    ("f32x", "own/1x1"): (8.42e-05, 2.17e-03, 3.21e-05, 1.96e-06),
+    ("f16", "own/1x1"): (6.56e-04, 2.47e-02, 3.78e-04, 3.36e-05),
+    ("f16hl", "own/1x1"): (7.88e-05, 1.89e-03, 2.81e-05, 1.91e-06),
+    ("f32", "own/direct"): (3.98e-06, 1.14e-04, 1.99e-06, 2.62e-08),
+    ("f32s", "own/direct"): (2.99e-06, 8.76e-05, 1.52e-06, 2.55e-07),
+    ("f32x", "own/direct"): (4.08e-05, 2.30e-03, 2.72e-05, 2.00e-06),
+    ("f16", "own/direct"): (6.27e-04, 3.19e-02, 4.20e-04, 4.97e-05),
+    ("f16hl", "own/direct"): (6.17e-05, 2.61e-03, 3.42e-05, 2.57e-06),
+    ("f32", "own/wino2"): (1.82e-06, 7.34e-05, 9.37e-07, 1.03e-08),
+    ("f32", "own/wino4"): (7.15e-06, 2.36e-04, 1.68e-06, 4.28e-08),
+    ("f32x", "own/wino4"): (3.02e-04, 1.45e-02, 7.87e-05, 2.74e-06),
+    ("f16hl", "own/wino4"): (3.66e-04, 1.76e-02, 8.06e-05, 1.97e-06),
+    ("f32", "own/wino6"): (1.90e-05, 4.26e-04, 4.73e-06, 3.73e-08),
+    ("f32s", "own/wino6"): (2.05e-05, 2.99e-04, 4.22e-06, 1.95e-07),
+    ("f32x", "own/wino6"): (6.17e-04, 2.63e-02, 2.88e-04, 4.29e-06),
+    ("f16hl", "own/wino6"): (7.70e-04, 4.62e-02, 3.04e-04, 3.56e-06),
+    ("f32", "own/head"): (6.16e-07, 1.64e-05, 2.78e-07, 1.24e-08),
+    ("f32s", "own/head"): (6.59e-07, 1.41e-05, 2.44e-07, 2.46e-08),
+    ("f32x", "own/head"): (2.87e-05, 1.82e-03, 2.09e-05, 1.71e-06),
+    ("f16", "own/head"): (2.39e-04, 1.58e-02, 2.23e-04, 4.05e-05),
+    ("f16hl", "own/head"): (2.64e-05, 1.76e-03, 1.92e-05, 3.14e-06),
+    # f16 against the reference whose conv weights are rounded to f16 first: the f32 accumulation and one rounding of the output
+    ("f16", "own16/1x1"): (4.34e-04, 4.88e-04, 2.22e-04, 3.21e-06),
+    ("f16", "own16/direct"): (4.58e-04, 4.89e-04, 2.23e-04, 3.71e-06),
+    ("f16", "own16/head"): (3.92e-07, 1.07e-05, 1.42e-07, 4.14e-09),
 }
 
 
@@ -219,6 +293,15 @@ def table_lines():
         for mode in ASKED[scope]:
             out.append(f"{mode:6s}{scope:19s}| {cells(MEASURED[(mode, scope)])} | {cells(bar(mode, scope))} | {cells(WAS[(mode, scope)])}")
     return out
+
+
+def own_design_lines():
+    """one table row per (mode, own-error scope) -- the four measured readings and the four bars"""
+    def cell(t):
+        return " ; ".join(f"{x:.1e}" for x in t)
+
+    return [f"| {mode} | `{scope}` | {cell(MEASURED[(mode, scope)])} | {cell(bar(mode, scope))} |"
+            for scope in SCOPES if scope.startswith("own") for mode in ASKED[scope]]
 
 
 DESIGN_ROWS = {"f32": "| `F32` ", "f32s": "| `F32_SPLIT` ", "f32x": "| `F32_SPLIT_FP8` ", "f16": "| `F16` ", "f16hl": "| **`F16_HL`** "}

@@ -89,6 +89,14 @@ def test_every_mode_and_scope_a_gpu_test_asks_for_is_in_the_table():
             for scope in re.findall(r'"((?:hostile|friendly)/[a-z0-9]+|edge)"', src):
                 assert scope in A.SCOPES, (name, scope)
                 used.add(scope)
+    # the own-error scopes are named by the classifier of tests/own_error.py (from the kernels that ran), through which
+    # tests/test_gpu_own_error.py grades every layer
+    import own_error as OE
+
+    src = open(os.path.join(HERE, "test_gpu_own_error.py")).read()
+    assert "OE.grade_own(" in src and "OE.assert_table(" in src
+    assert set(OE.OWN_SCOPES) | set(OE.OWN16_SCOPES) == {s for s in A.SCOPES if s.startswith("own")}
+    used |= set(OE.OWN_SCOPES) | set(OE.OWN16_SCOPES)
     assert used == set(A.SCOPES)
     # the modes the files run under a scope (parametrize lists and loops) are spelled out in ASKED; the sweep's are the test's own
     src = open(os.path.join(HERE, "test_gpu_hostile.py")).read()
@@ -115,6 +123,18 @@ def test_docstring_and_lab_notes_hold_the_table():
     for line in A.table_lines():
         assert line in A.__doc__, line
         assert line in notes, line
+
+
+def test_design_section_5_holds_the_own_error_rows():
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    sec = design[design.index("\n## 5. "):design.index("\n## 6. ")]
+    lines = A.own_design_lines()
+    assert len(lines) == sum(len(A.ASKED[s]) for s in A.SCOPES if s.startswith("own")) == 26
+    for line in lines:
+        assert line in sec, line
+    assert "| mode | scope | measured: max_rel ; elem ; rms ; bias | bar (1.3 × measured) |" in sec
+    # and no row of a (mode, scope) nobody asks for
+    assert sum(1 for ln in sec.splitlines() if re.match(r"\| \w+ \| `own(16)?/", ln)) == len(lines)
 
 
 def test_design_section_3_holds_the_tables_numbers():
