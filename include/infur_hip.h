@@ -407,7 +407,7 @@ int32_t infur_frame_regions_dev(infur_ctx* ctx, const void* d_bgr, uint32_t w, u
  *               region (rows as for untracked regions; CONTINUED = NEW = 0), leaves next_id alone and forgets the frame
  *   resets      on the first frame, after infur_tracker_reset, after an exhausted step, or when h or w differs from the
  *               remembered frame, every tracked region is new (and ENDED = 0).  Ids keep counting; the frame counter counts
- *               every step since the tracker was created.  There is no memory beyond one frame
+ *               every step since the tracker was created.  Memory beyond one frame is opt-in: "Tracks: memory" below
  *   overflow    the pair table has pair_slots slots.  R = the number of runs of equal tracked (c, p) along rows, rows cut
  *               every 64 columns: a function of the two planes alone that bounds the number of distinct pairs.  If
  *               2 R > pair_slots the step sets INFUR_TRACKS_OVERFLOW and every tracked region is new; it still remembers
@@ -481,6 +481,91 @@ int32_t infur_frame_tracks_dev(infur_ctx* ctx, const void* d_bgr, uint32_t w, ui
                                uint32_t table_rows, void* d_n_regions, void* d_scaled_bgr, uint32_t* ow, uint32_t* oh,
                                void* tracker, uint32_t min_overlap, void* d_track_of_region, void* d_track_plane,
                                void* d_track_table, void* d_summary);
+
+/* ---- Tracks: memory -- lost tracks are kept for a few frames, so a flicker keeps its id ----
+ * A per-frame argmax flickers: a region drops below min_pixels, changes class or merges with a neighbour for one frame, and the
+ * same object returns with a new id, AGE = 1 and a new BORN.  Memory is an opt-in GALLERY of lost tracks on the device: a track
+ * whose region vanished stays in it for up to max_lost steps, and a region that would start a new track takes a lost track of
+ * its class back when it appears where that track was last seen.  Presence of this group is announced by infur_features() &
+ * INFUR_FEATURE_TRACK_MEMORY (INFUR_ABI_VERSION does not move).  A tracker without memory does exactly what is described above.
+ * Integers throughout, a function of the sequence of planes alone.
+ *
+ * infur_tracker_set_memory(tracker, max_lost, reach, gallery_rows): max_lost == 0 turns memory off and frees its device memory
+ * (the other two arguments are ignored); gallery_rows: 0 = 4096, at most 65536 (more is INFUR_E_INVALID_ARG).  The call
+ * synchronises the context's stream before it frees or replaces memory, and forgets the remembered frame and the gallery as a
+ * reset does; next_id and the frame counter keep counting.  A failed allocation is INFUR_E_HIP and leaves the tracker as it was.
+ * (So does every other error of this call.)
+ *
+ * The gallery is an ordered list of at most gallery_rows entries of INFUR_LOST_WORDS words: ID, AGE, BORN, CLASS, PIXELS, SUM_X,
+ * SUM_Y, MIN_X, MIN_Y, MAX_X, MAX_Y of the track's last region, and SEEN, the value of the frame counter at the last step in
+ * which the track had a region.  A step at frame counter f (the value BORN uses) on a tracker with memory:
+ *   1 forget      a step that starts afresh (first frame, after infur_tracker_reset, after set_memory, after an exhausted
+ *                 step, another h x w) empties the gallery first.  An empty frame (h*w == 0) empties it too; its memory
+ *                 summary is all zero
+ *   2 expire      gap(e) = f - SEEN(e) - 1 is the number of steps in which the track had no region; entries with
+ *                 gap > max_lost are removed, EXPIRED counts them
+ *   3 match       exactly the match above: overlap table, choose, keep.  ORPHANS are the tracked regions c < T that no
+ *                 remembered region kept (those that start new tracks without memory)
+ *   4 candidates  (c, e) is a candidate iff c is an orphan, CLASS(c) == CLASS(e) and box(c) intersects
+ *                 grow(box(e), reach * gap(e)); grow moves each side outwards by that many pixels and clamps to
+ *                 [0, w-1] x [0, h-1]; the product is taken in 64 bits and clamped, so no reach can wrap.
+ *                 score = (x1 - x0 + 1)(y1 - y0 + 1) of the intersection (at most h*w)
+ *   5 revive      two-sided and greedy, with Tracks' own rule: every orphan chooses its candidate of largest score (ties:
+ *                 the smaller gallery index); every entry is kept by its chooser of largest score (ties: the smaller c); a
+ *                 loser does not fall back.  A kept orphan c is REVIVED: ID and BORN from e, AGE = AGE(e) + 1; its
+ *                 track-table row has PREV_REGION = INFUR_REGION_NONE, OVERLAP = 0 and PREV_PIXELS / PREV_SUM_X /
+ *                 PREV_SUM_Y from e, so a centroid step is still one subtraction.  gap_of_region[c] = gap(e) for a revived c
+ *                 and 0 for every other region
+ *   6 new ids     next_id + rank over the orphans that were not revived, in ascending region id.  next_id + new >
+ *                 0xFFFFFFFE is INFUR_TRACKS_IDS_EXHAUSTED as above; in addition the gallery is emptied and the memory
+ *                 summary is all zero.  (A step that would exhaust the ids without memory may therefore pass with it.)
+ *   7 summary     CONTINUED and ENDED mean what they mean above; NEW counts only the tracks that got a new id, so
+ *                 CONTINUED + NEW + REVIVED = T on a step that is not exhausted
+ *   8 gallery     the revived entries leave the gallery.  The remembered regions that no current region inherited (the ones
+ *                 ENDED counts) are appended in ascending region id with SEEN = f - 1 -- none on a step that started afresh;
+ *                 LOST counts them.  If the list is now longer than gallery_rows, entries are dropped from the front (the
+ *                 longest lost) and the status bit INFUR_TRACKS_GALLERY_FULL is set.  HELD is the length afterwards.  An
+ *                 OVERFLOW step is not special: all its tracked regions are orphans, all remembered regions end.
+ *                 The bit is reported in the step's summary only: a caller that passes no summary does not see it (in the
+ *                 memory summary HELD == gallery_rows says that the gallery is full, not whether entries were dropped)
+ * The gallery's order is a function of the history: survivors in their old order, then the newly ended regions in ascending
+ * region id.  infur_tracker_reset empties the gallery.  Memory costs 2 * 60 + 8 bytes per gallery row and 28 per region. */
+enum { INFUR_FEATURE_TRACK_MEMORY = 128 };
+enum { INFUR_TRACKS_GALLERY_FULL = 8 };
+enum {
+    INFUR_LOST_ID = 0,
+    INFUR_LOST_AGE = 1,
+    INFUR_LOST_BORN = 2,
+    INFUR_LOST_CLASS = 3,
+    INFUR_LOST_PIXELS = 4,
+    INFUR_LOST_SUM_X = 5,
+    INFUR_LOST_SUM_Y = 6,
+    INFUR_LOST_MIN_X = 7,
+    INFUR_LOST_MIN_Y = 8,
+    INFUR_LOST_MAX_X = 9,
+    INFUR_LOST_MAX_Y = 10,
+    INFUR_LOST_SEEN = 11,
+    INFUR_LOST_WORDS = 12
+};
+enum {
+    INFUR_TRACK_MEMORY_REVIVED = 0,
+    INFUR_TRACK_MEMORY_LOST = 1,
+    INFUR_TRACK_MEMORY_EXPIRED = 2,
+    INFUR_TRACK_MEMORY_HELD = 3,
+    INFUR_TRACK_MEMORY_WORDS = 4
+};
+int32_t infur_tracker_set_memory(void* tracker, uint32_t max_lost, uint32_t reach, uint32_t gallery_rows);
+/* What the last step left.  Each output is optional (all NULL is INFUR_E_INVALID_ARG), none needs initialisation:
+ *   gap_of_region   exactly `rows` uint32_t are written; a word at or beyond the last step's T is 0
+ *   memory_summary  INFUR_TRACK_MEMORY_WORDS uint32_t: REVIVED, LOST, EXPIRED, HELD
+ *   lost_table      the first min(HELD, lost_rows) gallery entries in gallery order, INFUR_LOST_WORDS uint64_t each; rows
+ *                   beyond that are left alone
+ * On a tracker without memory, or a null or orphaned tracker, both calls are INFUR_E_INVALID_ARG with no output touched. */
+int32_t infur_tracker_memory(void* tracker, uint32_t* gap_of_region, uint32_t rows, uint32_t* memory_summary,
+                             uint64_t* lost_table, uint32_t lost_rows);
+/* device pointers; stream-ordered, no synchronisation */
+int32_t infur_tracker_memory_dev(void* tracker, void* d_gap_of_region, uint32_t rows, void* d_memory_summary,
+                                 void* d_lost_table, uint32_t lost_rows);
 
 /* ---- Runs: a class, label or track plane as run-length records ----
  * The four decode stages end in dense planes: at 1080p a 2 MB class plane, an 8 MB label plane, an 8 MB track plane.  A

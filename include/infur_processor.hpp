@@ -317,6 +317,16 @@ struct TracksOut {
     uint64_t word(uint32_t id, uint32_t w) const { return table[(size_t)id * INFUR_TRACK_WORDS + w]; }
 };
 
+/// What `Tracks::memory` reads of a tracker with memory: `gap_of_region` (as many words as asked for; 0 for a region that was
+/// not revived), the four INFUR_TRACK_MEMORY_* words and the gallery's first rows of INFUR_LOST_WORDS words, in gallery order.
+struct TracksMemory {
+    std::vector<uint32_t> gap_of_region;
+    uint32_t summary[INFUR_TRACK_MEMORY_WORDS] = {0, 0, 0, 0};
+    std::vector<uint64_t> lost;
+    uint32_t held() const { return summary[INFUR_TRACK_MEMORY_HELD]; }
+    uint64_t word(uint32_t entry, uint32_t w) const { return lost[(size_t)entry * INFUR_LOST_WORDS + w]; }
+};
+
 /// The fourth decode stage: region identities carried from frame to frame.  Owns its tracker -- one remembered frame on the
 /// device -- and must not outlive its context.  A region inherits the track of the remembered region of its class it overlaps
 /// most (when that region prefers it too), otherwise it starts a new one.  Integer results, identical from run to run.
@@ -346,6 +356,22 @@ public:
         }
     }
     bool is_dirty() const { return dirty_; }
+    /// Keep lost tracks for up to `max_lost` steps (0: memory off); forgets the remembered frame and the gallery.
+    Status set_memory(uint32_t max_lost, uint32_t reach = 0, uint32_t gallery_rows = 0) {
+        dirty_ = true;
+        return infur_tracker_set_memory(t_, max_lost, reach, gallery_rows);
+    }
+    /// What the last step left: `rows` words of gap_of_region, the memory summary, at most `lost_rows` gallery rows.
+    /// INFUR_E_INVALID_ARG on a tracker without memory.
+    Status memory(TracksMemory& out, uint32_t rows, uint32_t lost_rows = 0) const {
+        out.gap_of_region.assign(rows, 0);
+        out.lost.assign((size_t)lost_rows * INFUR_LOST_WORDS, 0);
+        const Status s = infur_tracker_memory(t_, rows ? out.gap_of_region.data() : nullptr, rows, out.summary,
+                                              lost_rows ? out.lost.data() : nullptr, lost_rows);
+        const uint32_t got = out.held() < lost_rows ? out.held() : lost_rows;  // the rows the call wrote
+        out.lost.resize(s == INFUR_OK ? (size_t)got * INFUR_LOST_WORDS : 0);
+        return s;
+    }
     Status advance(const RegionsOut& inp, TracksOut& out) {
         dirty_ = false;
         const size_t hw = (size_t)inp.width * inp.height;

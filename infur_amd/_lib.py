@@ -54,6 +54,14 @@ TRACKS_TRUNCATED, TRACKS_OVERFLOW, TRACKS_IDS_EXHAUSTED = 1, 2, 4
 TRACKS_SUMMARY_STATUS, TRACKS_SUMMARY_CONTINUED, TRACKS_SUMMARY_NEW, TRACKS_SUMMARY_ENDED = range(4)
 TRACKS_SUMMARY_WORDS = 4
 FEATURE_TRACKS = 4
+# Tracks' memory (infur_tracker_set_memory / infur_tracker_memory): the status bit, the words of a gallery entry and of the memory summary
+TRACKS_GALLERY_FULL = 8
+(LOST_ID, LOST_AGE, LOST_BORN, LOST_CLASS, LOST_PIXELS, LOST_SUM_X, LOST_SUM_Y, LOST_MIN_X, LOST_MIN_Y, LOST_MAX_X, LOST_MAX_Y,
+ LOST_SEEN) = range(12)
+LOST_WORDS = 12
+TRACK_MEMORY_REVIVED, TRACK_MEMORY_LOST, TRACK_MEMORY_EXPIRED, TRACK_MEMORY_HELD = range(4)
+TRACK_MEMORY_WORDS = 4
+FEATURE_TRACK_MEMORY = 128
 # Runs (infur_runs / infur_frame_runs): the flag, the words of a record, the feature bit
 RUNS_SKIP = 1
 RUN_START, RUN_END, RUN_VALUE, RUN_WORDS = 0, 1, 2, 3
@@ -178,6 +186,9 @@ SIGNATURES = {
     "infur_tracker_create": (C.c_int32, [_vp, _u32, _u32, C.POINTER(_vp)]),
     "infur_tracker_destroy": (None, [_vp]),
     "infur_tracker_reset": (C.c_int32, [_vp, _u32]),
+    "infur_tracker_set_memory": (C.c_int32, [_vp, _u32, _u32, _u32]),
+    "infur_tracker_memory": (C.c_int32, [_vp, _vp, _u32, _vp, _vp, _u32]),
+    "infur_tracker_memory_dev": (C.c_int32, [_vp, _vp, _u32, _vp, _vp, _u32]),
     "infur_tracks": (C.c_int32, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),
     "infur_tracks_dev": (C.c_int32, [_vp, _vp, _vp, _u32, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),
     "infur_frame_tracks": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp, _vp,

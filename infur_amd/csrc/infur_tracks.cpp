@@ -21,22 +21,33 @@ struct infur_tracker {
     Buf prev;   // the remembered label plane
     Buf io;     // staging of the host-pointer calls
     Buf frame;  // the label plane, table and count the frame calls keep when the caller does not want them
+    void* gmem = nullptr;  // memory (infur_tracker_set_memory): the gallery and everything it needs, an allocation of its own
+    TrkGal g{};
+    Buf mio;  // staging of infur_tracker_memory
 };
 
 namespace {
 
 static_assert(kTrkWords == INFUR_TRACK_WORDS, "tracks.hip and the header disagree about the row");
+static_assert(kLostWords == INFUR_LOST_WORDS && kTrkGalleryFull == INFUR_TRACKS_GALLERY_FULL, "tracks.hip and the header disagree about memory");
 static_assert(kTrkTruncated == INFUR_TRACKS_TRUNCATED && kTrkOverflow == INFUR_TRACKS_OVERFLOW && kTrkExhausted == INFUR_TRACKS_IDS_EXHAUSTED,
               "tracks.hip and the header disagree about the status bits");
 
-constexpr uint32_t kTrkMaxRegions = 1u << 24, kTrkMaxSlots = 1u << 28;
+constexpr uint32_t kTrkMaxRegions = 1u << 24, kTrkMaxSlots = 1u << 28, kTrkGalleryRows = 4096, kTrkMaxGalleryRows = 65536;
 
 void tracker_release(infur_tracker* t) {
     if (t->mem) (void)hipFree(t->mem);
-    for (Buf* b : {&t->prev, &t->io, &t->frame})
+    if (t->gmem) (void)hipFree(t->gmem);
+    for (Buf* b : {&t->prev, &t->io, &t->frame, &t->mio})
         if (b->p) (void)hipFree(b->p);
-    t->mem = t->prev.p = t->io.p = t->frame.p = nullptr;
-    t->prev.bytes = t->io.bytes = t->frame.bytes = 0;
+    t->mem = t->gmem = t->prev.p = t->io.p = t->frame.p = t->mio.p = nullptr;
+    t->prev.bytes = t->io.bytes = t->frame.bytes = t->mio.bytes = 0;
+}
+
+// forget the remembered frame and, on a tracker with memory, the gallery
+hipError_t tracker_forget(infur_tracker* t, int step, int set_id, uint32_t first_id, unsigned* summary, hipStream_t s) {
+    const hipError_t e = launch_tracks_forget(t->m.st, step, set_id, first_id, summary, s);
+    return e != hipSuccess || !t->gmem ? e : launch_tracks_memory_forget(t->g, s);
 }
 
 void tracker_detach(infur_tracker* t) {
@@ -167,7 +178,100 @@ int32_t infur_tracker_reset(void* tracker, uint32_t first_id) {
     infur_ctx* c = trk_ctx(tracker);
     return abi_call(c, [&]() -> int32_t {
         if (!c) return INFUR_E_INVALID_ARG;
-        HIPCHK(c, launch_tracks_forget(((infur_tracker*)tracker)->m.st, 0, 1, first_id, nullptr, c->stream));
+        HIPCHK(c, tracker_forget((infur_tracker*)tracker, 0, 1, first_id, nullptr, c->stream));
+        return INFUR_OK;
+    });
+}
+
+int32_t infur_tracker_set_memory(void* tracker, uint32_t max_lost, uint32_t reach, uint32_t gallery_rows) {
+    infur_ctx* c = trk_ctx(tracker);
+    return abi_call(c, [&]() -> int32_t {
+        if (!c) return INFUR_E_INVALID_ARG;
+        infur_tracker* t = (infur_tracker*)tracker;
+        const uint32_t G = gallery_rows ? gallery_rows : kTrkGalleryRows;
+        if (max_lost && G > kTrkMaxGalleryRows) return fail(c, INFUR_E_INVALID_ARG, "gallery_rows %u: at most %u", G, kTrkMaxGalleryRows);
+        HIPCHK(c, hipStreamSynchronize(c->stream));  // no launch still reads what is freed or replaced below
+        void* mem = nullptr;
+        TrkGal g{};
+        if (max_lost) {
+            const size_t M = t->max_regions;
+            const size_t m8 = align_up(M * 8, 256), m4 = align_up(M * 4, 256), g8 = align_up((size_t)G * 8, 256), g4 = align_up((size_t)G * 4, 256);
+            const size_t rpart = align_up((M / kScanBlock + 1) * 4, 256), gpart = align_up(scan_blocks((size_t)G + M) * 4, 256);
+            const size_t bytes = 256 + 2 * (3 * g8 + 9 * g4) + 5 * m4 + m8 + g8 + rpart + gpart;
+            if (hipMalloc(&mem, bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(c, INFUR_E_HIP, "hipMalloc of %zu bytes for a tracker's memory failed", bytes);
+            }
+            uint8_t* p = (uint8_t*)mem;
+            auto take = [&](size_t n) {
+                uint8_t* q = p;
+                p += n;
+                return q;
+            };
+            g.gs = (TrkGalState*)take(256);
+            for (TrkLost& b : g.buf) {
+                b.pix = (unsigned long long*)take(g8);
+                b.sx = (unsigned long long*)take(g8);
+                b.sy = (unsigned long long*)take(g8);
+                for (unsigned** a : {&b.id, &b.age, &b.born, &b.klass, &b.x0, &b.y0, &b.x1, &b.y1, &b.seen}) *a = (unsigned*)take(g4);
+            }
+            for (unsigned** a : {&g.px0, &g.py0, &g.px1, &g.py1, &g.cgap}) *a = (unsigned*)take(m4);
+            g.rbest = (unsigned long long*)take(m8);
+            g.rclaim = (unsigned long long*)take(g8);
+            g.rpart = (unsigned*)take(rpart);
+            g.gpart = (unsigned*)take(gpart);
+            g.max_lost = max_lost;
+            g.reach = reach;
+            g.G = G;
+            // (as at creation: every array word is written before a step reads it, the state words start at zero)
+            if (hipMemsetAsync(g.gs, 0, 256, c->stream) != hipSuccess) {
+                (void)hipGetLastError();
+                (void)hipFree(mem);
+                return fail(c, INFUR_E_HIP, "hipMemsetAsync of the tracker's memory state failed");
+            }
+        }
+        // the last step that can fail comes before the swap (it touches the tracker's state words only): an error leaves the tracker as it was
+        const hipError_t e = launch_tracks_forget(t->m.st, 0, 0, 0, nullptr, c->stream);
+        if (e != hipSuccess) {
+            if (mem) (void)hipFree(mem);
+            return fail(c, INFUR_E_HIP, "forgetting the remembered frame failed: %s", hipGetErrorString(e));
+        }
+        if (t->gmem) (void)hipFree(t->gmem);
+        t->gmem = mem;
+        t->g = g;
+        return INFUR_OK;
+    });
+}
+
+int32_t infur_tracker_memory_dev(void* tracker, void* d_gap, uint32_t rows, void* d_msum, void* d_lost, uint32_t lost_rows) {
+    infur_ctx* c = trk_ctx(tracker);
+    return abi_call(c, [&]() -> int32_t {
+        if (!c || !((infur_tracker*)tracker)->gmem) return INFUR_E_INVALID_ARG;
+        if (!d_gap && !d_msum && !d_lost) return INFUR_E_INVALID_ARG;
+        HIPCHK(c, launch_tracks_memory_read(((infur_tracker*)tracker)->g, (unsigned*)d_gap, rows, (unsigned*)d_msum, (unsigned long long*)d_lost, lost_rows,
+                                            c->stream));
+        return INFUR_OK;
+    });
+}
+
+int32_t infur_tracker_memory(void* tracker, uint32_t* gap, uint32_t rows, uint32_t* msum, uint64_t* lost, uint32_t lost_rows) {
+    infur_ctx* c = trk_ctx(tracker);
+    return abi_call(c, [&]() -> int32_t {
+        if (!c || !((infur_tracker*)tracker)->gmem) return INFUR_E_INVALID_ARG;
+        if (!gap && !msum && !lost) return INFUR_E_INVALID_ARG;
+        infur_tracker* t = (infur_tracker*)tracker;
+        const size_t lr = lost_rows < t->g.G ? lost_rows : t->g.G;  // the gallery holds no more
+        const size_t o_gap = 256, o_lost = o_gap + align_up((size_t)rows * 4, 256), bytes = o_lost + align_up(lr * INFUR_LOST_WORDS * 8, 256);
+        RETIF(ensure_private(c, t->mio, bytes));
+        uint8_t* base = (uint8_t*)t->mio.p;
+        RETIF(infur_tracker_memory_dev(t, gap ? base + o_gap : nullptr, rows, base, lost ? base + o_lost : nullptr, (uint32_t)lr));
+        uint32_t sum[INFUR_TRACK_MEMORY_WORDS];
+        HIPCHK(c, hipMemcpyAsync(sum, base, sizeof sum, hipMemcpyDeviceToHost, c->stream));
+        if (gap && rows) HIPCHK(c, hipMemcpyAsync(gap, base + o_gap, (size_t)rows * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        const size_t held = sum[INFUR_TRACK_MEMORY_HELD] < lr ? sum[INFUR_TRACK_MEMORY_HELD] : lr;  // the count decides how many rows there are to copy
+        if (lost && held) HIPCHK(c, hipMemcpy(lost, base + o_lost, held * INFUR_LOST_WORDS * 8, hipMemcpyDeviceToHost));
+        if (msum) memcpy(msum, sum, sizeof sum);
         return INFUR_OK;
     });
 }
@@ -182,7 +286,7 @@ int32_t infur_tracks_dev(void* tracker, const void* d_labels, const void* d_tabl
         const size_t hw = (size_t)h * w;
         if (!d_tor && !d_plane && !d_ttab && !d_summary) return INFUR_E_INVALID_ARG;
         if (hw == 0) {  // empty frame: nothing to track, nothing remembered
-            HIPCHK(c, launch_tracks_forget(t->m.st, 1, 0, 0, (unsigned*)d_summary, c->stream));
+            HIPCHK(c, tracker_forget(t, 1, 0, 0, (unsigned*)d_summary, c->stream));
             return INFUR_OK;
         }
         if (!d_labels || !d_table || !d_n) return INFUR_E_INVALID_ARG;
@@ -190,8 +294,13 @@ int32_t infur_tracks_dev(void* tracker, const void* d_labels, const void* d_tabl
         RETIF(ensure_private(c, t->prev, hw * 4));
         t->m.prev = (unsigned*)t->prev.p;
         ProfScope ps(c, "tracks", "tracks", 0, (double)hw * (12 + (d_plane ? 4 : 0)) + (double)t->pair_slots * 12);
-        HIPCHK(c, launch_tracks(t->m, (const unsigned*)d_labels, (const unsigned long long*)d_table, table_rows, (const unsigned*)d_n, h, w, min_overlap,
-                                (unsigned*)d_tor, (unsigned*)d_plane, (unsigned long long*)d_ttab, (unsigned*)d_summary, c->stream));
+        if (t->gmem)
+            HIPCHK(c, launch_tracks_memory(t->m, t->g, (const unsigned*)d_labels, (const unsigned long long*)d_table, table_rows, (const unsigned*)d_n, h,
+                                           w, min_overlap, (unsigned*)d_tor, (unsigned*)d_plane, (unsigned long long*)d_ttab, (unsigned*)d_summary,
+                                           c->stream));
+        else
+            HIPCHK(c, launch_tracks(t->m, (const unsigned*)d_labels, (const unsigned long long*)d_table, table_rows, (const unsigned*)d_n, h, w,
+                                    min_overlap, (unsigned*)d_tor, (unsigned*)d_plane, (unsigned long long*)d_ttab, (unsigned*)d_summary, c->stream));
         return INFUR_OK;
     });
 }

@@ -315,6 +315,40 @@ hipError_t launch_tracks(const TrkMem& m, const unsigned* labels, const unsigned
 // forget the remembered frame; step: advance the frame counter (an empty frame); set_id: next_id = first_id; summary (optional) zeroed
 hipError_t launch_tracks_forget(TrkState* st, int step, int set_id, unsigned first_id, unsigned* summary, hipStream_t s);
 
+// Tracks' memory (tracks.hip, DESIGN 4c'): a gallery of lost tracks, an allocation of its own made by infur_tracker_set_memory.
+// The gallery is a list of at most G entries in structure-of-arrays form, held twice: a step compacts buf[cur] into
+// buf[cur ^ 1] and its last launch flips cur.
+constexpr int kLostWords = 12;
+constexpr unsigned kTrkGalleryFull = 8;
+struct TrkGalState {
+    unsigned held, cur, T;                        // across steps: entries in buf[cur]; the last step's tracked regions
+    unsigned revived, ended, drop, new_held;      // of the running step
+    unsigned sum[4];                              // the last step's memory summary: REVIVED, LOST, EXPIRED, HELD
+};
+struct TrkLost {
+    unsigned long long *pix, *sx, *sy;
+    unsigned *id, *age, *born, *klass, *x0, *y0, *x1, *y1, *seen;
+};
+struct TrkGal {
+    TrkGalState* gs;
+    TrkLost buf[2];
+    unsigned *px0, *py0, *px1, *py1;     // remembered regions: bounding box (M words each)
+    unsigned* cgap;                      // current regions: gap_of_region
+    unsigned long long *rbest, *rclaim;  // per current region / per entry: (score << 32) | (0xFFFFFFFF - partner)
+    unsigned *rpart, *gpart;             // block sums: revived regions (as TrkMem::partial); the gallery scan over G + M flags
+    unsigned max_lost, reach, G;
+};
+// launch_tracks on a tracker with memory: the same step, with the revival launches between keep and assign and the gallery
+// update before save.  g.gs is zeroed by whoever allocates it
+hipError_t launch_tracks_memory(const TrkMem& m, const TrkGal& g, const unsigned* labels, const unsigned long long* table, unsigned rows,
+                                const unsigned* d_n, unsigned H, unsigned W, unsigned min_overlap, unsigned* track_of_region, unsigned* track_plane,
+                                unsigned long long* track_table, unsigned* summary, hipStream_t s);
+// empty the gallery (reset, empty frame): the memory summary reads all zero, gap_of_region too
+hipError_t launch_tracks_memory_forget(const TrkGal& g, hipStream_t s);
+// what the last step left, each output optional: gap_of_region[rows], memory summary[4], the first min(HELD, lost_rows) entries
+hipError_t launch_tracks_memory_read(const TrkGal& g, unsigned* gap_of_region, unsigned rows, unsigned* memory_summary,
+                                     unsigned long long* lost_table, unsigned lost_rows, hipStream_t s);
+
 // Runs (runs.hip): an H x W plane of 1- or 4-byte elements as raster-ordered runs -- rows x kRunWords u32 records (START, END,
 // VALUE), the per-row index row_start[H + 1] and the count (each optional; d_n is a device word).  skip: runs of skip_value are
 // neither emitted nor counted.  scratch: runs_scratch_bytes(H * W) bytes the launches own for the call.  Stream-ordered; no

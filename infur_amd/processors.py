@@ -678,11 +678,13 @@ class TracksOut:
     """``Tracks``' ``&mut Output``: what to produce (``want_plane``) and, after ``advance``, the results -- ``track_of_region``
     [min(n, rows)] u32 (``_lib.TRACK_NONE``: not tracked), ``table`` [min(n, rows), 8] uint64 (columns ``_lib.TRACK_*``),
     ``plane`` [H, W] u32 or None, ``summary`` [4] u32 (``_lib.TRACKS_SUMMARY_*``) and its fields ``status`` (``_lib.TRACKS_*``
-    bits), ``continued``, ``new``, ``ended``."""
+    bits), ``continued``, ``new``, ``ended``.  On a tracker with memory also ``gap_of_region`` [min(n, rows)] u32 and ``memory``
+    [4] u32 (``_lib.TRACK_MEMORY_*``: revived, lost, expired, held); both are None without memory."""
 
     def __init__(self, want_plane: bool = False):
         self.want_plane = want_plane
         self.track_of_region = self.table = self.plane = self.summary = None
+        self.gap_of_region = self.memory = None
         self.status = self.continued = self.new = self.ended = 0
 
     def _set(self, tor, table, plane, summary, n):
@@ -701,13 +703,48 @@ class Tracks(Processor):
     region prefers it too), otherwise it starts a new one; integers throughout, identical from run to run.
     """
 
-    def __init__(self, ctx: Context, max_regions: int = 0, pair_slots: int = 0, min_overlap: int = 1):
+    def __init__(self, ctx: Context, max_regions: int = 0, pair_slots: int = 0, min_overlap: int = 1, max_lost: int = 0, reach: int = 0,
+                 gallery_rows: int = 0):
         self.ctx = ctx
         self.min_overlap = min_overlap
         self.dirty = True
+        self.max_lost = 0
         t = C.c_void_p()
         ctx.check(ctx.L.infur_tracker_create(ctx.h, max_regions, pair_slots, C.byref(t)))
         self.t = t
+        if max_lost:
+            self.set_memory(max_lost, reach, gallery_rows)
+
+    def set_memory(self, max_lost: int, reach: int = 0, gallery_rows: int = 0) -> "Tracks":
+        """Keep lost tracks for up to ``max_lost`` steps (0: memory off): a region that would start a new track takes a lost
+        track of its class back when its box meets that track's last box grown by ``reach`` pixels per step of absence.  Forgets
+        the remembered frame and the gallery."""
+        self.ctx.check(self.ctx.L.infur_tracker_set_memory(self.t, max_lost, reach, gallery_rows))
+        self.max_lost = max_lost
+        self.dirty = True
+        return self
+
+    def memory(self, rows: int):
+        """-> (gap_of_region [rows] u32, memory summary [4] u32) of the last step, or (None, None) without memory"""
+        if not getattr(self, "max_lost", 0):
+            return None, None
+        gap, msum = np.zeros(rows, np.uint32), np.zeros(_lib.TRACK_MEMORY_WORDS, np.uint32)
+        self.ctx.check(self.ctx.L.infur_tracker_memory(self.t, gap.ctypes.data if rows else None, rows, msum.ctypes.data, None, 0))
+        return gap, msum
+
+    def lost(self, lost_rows: Optional[int] = None) -> Optional[np.ndarray]:
+        """-> the gallery as the last step left it, [min(HELD, lost_rows), 12] uint64 (columns ``_lib.LOST_*``) in gallery
+        order; None without memory"""
+        if not getattr(self, "max_lost", 0):
+            return None
+        msum = np.zeros(_lib.TRACK_MEMORY_WORDS, np.uint32)
+        self.ctx.check(self.ctx.L.infur_tracker_memory(self.t, None, 0, msum.ctypes.data, None, 0))
+        held = int(msum[_lib.TRACK_MEMORY_HELD])
+        rows = held if lost_rows is None else min(held, int(lost_rows))
+        table = np.zeros((rows, _lib.LOST_WORDS), np.uint64)
+        if rows:
+            self.ctx.check(self.ctx.L.infur_tracker_memory(self.t, None, 0, None, table.ctypes.data, rows))
+        return table
 
     def control(self, cmd: TracksCmd) -> "Tracks":
         given = [v for v in (cmd.min_overlap, cmd.reset) if v is not None]
@@ -740,7 +777,9 @@ class Tracks(Processor):
         ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
         self.ctx.check(self.ctx.L.infur_tracks(self.t, ptr(labels), ptr(table), rows, int(n), h, w, self.min_overlap, ptr(tor), ptr(plane),
                                                ptr(ttab), summary.ctypes.data))
-        out._set(tor, ttab, plane, summary, min(int(n), rows) if h * w else 0)
+        k = min(int(n), rows) if h * w else 0
+        out._set(tor, ttab, plane, summary, k)
+        out.gap_of_region, out.memory = self.memory(k)
 
     def close(self):
         if getattr(self, "t", None):
@@ -756,7 +795,8 @@ class Tracks(Processor):
 
 class TracksFrame(NamedTuple):
     """``FramePath.advance_tracks``: the fields of ``RegionsFrame``, then ``track_of_region`` [min(n, table_rows)] u32, the track
-    table [min(n, table_rows), 8] uint64, the track plane [oh, ow] u32 or None and the summary [4] u32"""
+    table [min(n, table_rows), 8] uint64, the track plane [oh, ow] u32 or None and the summary [4] u32; on a tracker with memory
+    also ``gap_of_region`` [min(n, table_rows)] u32 and the memory summary [4] u32 (None without memory)"""
 
     klass: Optional[np.ndarray]
     conf: Optional[np.ndarray]
@@ -768,9 +808,11 @@ class TracksFrame(NamedTuple):
     track_table: Optional[np.ndarray]
     track_plane: Optional[np.ndarray]
     summary: Optional[np.ndarray]
+    gap_of_region: Optional[np.ndarray] = None
+    memory: Optional[np.ndarray] = None
 
 
-def track_summary(table: np.ndarray, track_table: np.ndarray, n: int, ow: int, oh: int, names=None) -> List[dict]:
+def track_summary(table: np.ndarray, track_table: np.ndarray, n: int, ow: int, oh: int, names=None, gap=None) -> List[dict]:
     """``region_summary``'s records joined with the track table, one dict per row both tables hold, in region order: added are
     ``track`` (None for an untracked region), ``age``, ``born``, ``prev_region`` (None for a new track), ``overlap`` and
     ``step`` -- this frame's centroid minus the inherited region's, (dx, dy), or None for a new or untracked region."""
@@ -787,6 +829,9 @@ def track_summary(table: np.ndarray, track_table: np.ndarray, n: int, ow: int, o
         if rec["prev_region"] is not None and ppx:
             cx, cy = rec["centroid"]
             rec["step"] = (cx - int(row[_lib.TRACK_PREV_SUM_X]) / ppx, cy - int(row[_lib.TRACK_PREV_SUM_Y]) / ppx)
+    if gap is not None:  # a tracker with memory: the steps a revived track was absent (0 for every other region)
+        for rec, g in zip(recs, gap):
+            rec["gap"] = int(g)
     return recs
 
 
@@ -1321,8 +1366,9 @@ class FramePath:
         if not self._loaded(rc):
             return TracksFrame(None, None, None, None, None, scaled, None, None, None, None)
         k = min(n.value, rows)
+        gap, memory = tracks.memory(k)
         return TracksFrame(klass, conf, labels, table[:k] if table is not None else None, n.value, scaled,
-                           tor[:k] if tor is not None else None, ttab[:k] if ttab is not None else None, plane, summary)
+                           tor[:k] if tor is not None else None, ttab[:k] if ttab is not None else None, plane, summary, gap, memory)
 
     def advance_runs(self, img: np.ndarray, factor: float = 1.0, decode: int = _lib.DECODE_RAW, skip: Optional[int] = None,
                      runs_rows: int = 1 << 16, want_row_start: bool = True, want_stats: bool = True,

@@ -24,6 +24,9 @@ gains ``"track"`` (stable while the object overlaps itself from one frame to the
 ``"age"`` in frames and ``"dx"``, ``"dy"``, the step of its centroid since the previous frame (null for a new track), and every
 line ``"tracks": {"status", "continued", "new", "ended"}``.  ``--min-overlap N`` is the least number of common pixels that
 continues a track; ``--tracks-out`` receives the u32 track planes back to back (0xFFFFFFFF: not tracked).
+``--tracks-memory N`` keeps a lost track for N frames, so that a region absent for a frame or two returns with its id
+(``--tracks-reach PX``: how far per frame of absence it may have moved); ``"tracks"`` then gains ``"revived"``, ``"lost"``,
+``"expired"``, ``"held"`` and every region record ``"gap"``, the frames a revived track was absent (0 otherwise).
 
 ``--runs-out FILE`` receives a plane run-length encoded on the device: per frame a u32 count n followed by n records of three
 u32 (START = y*ow + x of the run's first pixel, END one past its last, VALUE), runs never crossing a row, in raster order, and
@@ -77,6 +80,10 @@ def main(argv=None) -> int:
     ap.add_argument("--tracks", action="store_true", help="carry region identities from frame to frame (implies --regions)")
     ap.add_argument("--min-overlap", type=int, default=1, help="common pixels a track needs to continue")
     ap.add_argument("--tracks-out", default="", help="raw u32 track planes, four bytes per pixel (needs --tracks)")
+    ap.add_argument("--tracks-memory", type=int, default=0, metavar="N",
+                    help="keep a lost track for N frames, so that a region that flickers returns with its id (needs --tracks; 0: off)")
+    ap.add_argument("--tracks-reach", type=int, default=0, metavar="PX",
+                    help="pixels per frame of absence by which a lost track's box grows when a region looks for it (needs --tracks)")
     ap.add_argument("--runs-out", default="", help="run-length records of a plane: per frame a u32 count, then count x 3 u32")
     ap.add_argument("--runs-plane", default="class", choices=["class", "labels", "tracks"], help="the plane --runs-out encodes")
     ap.add_argument("--runs-skip", type=int, default=None, help="leave out the runs of this value")
@@ -90,6 +97,10 @@ def main(argv=None) -> int:
         ap.error("--outlines-shared needs --outlines-tolerance")
     if a.tracks_out and not a.tracks:
         ap.error("--tracks-out needs --tracks")
+    if (a.tracks_memory or a.tracks_reach) and not a.tracks:
+        ap.error("--tracks-memory and --tracks-reach need --tracks")
+    if a.tracks_memory < 0 or a.tracks_reach < 0:
+        ap.error("--tracks-memory and --tracks-reach are not negative")
     a.regions = a.regions or a.tracks
     if a.regions_out and not a.regions:
         ap.error("--regions-out needs --regions")
@@ -145,7 +156,8 @@ def main(argv=None) -> int:
     if a.regions:
         oh, ow = _out_dims(ctx, a.width, a.height, a.scale)
         rpath = _RegionsPath(ctx, a.width, a.height, ow, oh, a.scale, fp.scale_mode, model.get_info().num_classes, max(0, a.max_regions),
-                             tracks=a.tracks, runs=fruns is not None, outlines=foutl is not None, simplify=tol16 is not None, shared=a.outlines_shared)
+                             tracks=a.tracks, memory=(a.tracks_memory, a.tracks_reach),
+                             runs=fruns is not None, outlines=foutl is not None, simplify=tol16 is not None, shared=a.outlines_shared)
         flags = _lib.REGIONS_SKIP_BACKGROUND if a.skip_background else 0
     n, t0 = 0, time.perf_counter()
     while True:
@@ -205,6 +217,11 @@ def main(argv=None) -> int:
                     r["track"], r["age"] = t["track"], t["age"]
                     r["dx"], r["dy"] = t["step"] if t["step"] is not None else (None, None)
                 rec["tracks"] = {"status": int(tsum[0]), "continued": int(tsum[1]), "new": int(tsum[2]), "ended": int(tsum[3])}
+                if a.tracks_memory:
+                    gap, msum = rpath.memory()
+                    for r, g in zip(rec["regions"], gap):
+                        r["gap"] = int(g)
+                    rec["tracks"].update(zip(("revived", "lost", "expired", "held"), (int(v) for v in msum)))
                 if ftrk is not None:
                     ftrk.write(memoryview(tplane).cast("B"))
             if freg is not None:
@@ -237,7 +254,8 @@ class _RegionsPath:
     writes class plane, confidence plane and per-class table into device buffers, infur_regions_dev labels those planes where
     they are; the tables, the count and the planes that are written out are all that is copied back."""
 
-    def __init__(self, ctx, w, h, ow, oh, factor, scale_mode, classes, rows, tracks=False, runs=False, outlines=False, simplify=False, shared=False):
+    def __init__(self, ctx, w, h, ow, oh, factor, scale_mode, classes, rows, tracks=False, memory=(0, 0), runs=False, outlines=False, simplify=False,
+                 shared=False):
         import ctypes as C
 
         self.ctx, self.w, self.h, self.ow, self.oh, self.factor, self.mode = ctx, w, h, ow, oh, float(factor), scale_mode
@@ -257,6 +275,8 @@ class _RegionsPath:
         if tracks:  # --tracks: the label plane stays on the device for the tracker whether it is written out or not
             self.tracker = C.c_void_p(None)
             ctx.check(ctx.L.infur_tracker_create(ctx.h, 0, 0, C.byref(self.tracker)))
+            if memory[0]:  # --tracks-memory N [--tracks-reach PX]
+                ctx.check(ctx.L.infur_tracker_set_memory(self.tracker, min(memory[0], 0xFFFFFFFF), min(memory[1], 0xFFFFFFFF), 0))
 
     def _read(self, name, shape, dtype):
         import numpy as np
@@ -300,6 +320,15 @@ class _RegionsPath:
                                      d["tplane"] if want_plane or keep_plane else None, d["ttab"] if self.rows else None, d["tsum"]))
         return (self._read("ttab", (min(self.n, self.rows), _TRACK_BYTES // 8), np.uint64),
                 self._read("tplane", (self.oh, self.ow), np.uint32) if want_plane else None, self._read("tsum", (4,), np.uint32))
+
+    def memory(self):
+        """infur_tracker_memory after `track` -> (gap_of_region of the table's rows, memory summary): --tracks-memory"""
+        import numpy as np
+
+        k = min(self.n, self.rows)
+        gap, msum = np.zeros(k, np.uint32), np.zeros(4, np.uint32)
+        self.ctx.check(self.ctx.L.infur_tracker_memory(self.tracker, gap.ctypes.data if k else None, k, msum.ctypes.data, None, 0))
+        return gap, msum
 
     def runs(self, plane, skip):
         """infur_runs_dev on a plane `advance` / `track` left on the device -> (records [n, 3] u32, n): every run, no dense plane"""

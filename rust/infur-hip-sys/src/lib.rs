@@ -129,6 +129,28 @@ pub const INFUR_TRACKS_SUMMARY_WORDS: u32 = 4;
 pub const INFUR_TRACK_NONE: u32 = 0xFFFF_FFFF;
 /// bit of `infur_features()`: the Tracks calls below exist
 pub const INFUR_FEATURE_TRACKS: u32 = 4;
+/// Tracks' memory: the status bit, the words of a gallery entry (`INFUR_LOST_WORDS` u64 each) and of the memory summary
+pub const INFUR_TRACKS_GALLERY_FULL: u32 = 8;
+pub const INFUR_LOST_ID: u32 = 0;
+pub const INFUR_LOST_AGE: u32 = 1;
+pub const INFUR_LOST_BORN: u32 = 2;
+pub const INFUR_LOST_CLASS: u32 = 3;
+pub const INFUR_LOST_PIXELS: u32 = 4;
+pub const INFUR_LOST_SUM_X: u32 = 5;
+pub const INFUR_LOST_SUM_Y: u32 = 6;
+pub const INFUR_LOST_MIN_X: u32 = 7;
+pub const INFUR_LOST_MIN_Y: u32 = 8;
+pub const INFUR_LOST_MAX_X: u32 = 9;
+pub const INFUR_LOST_MAX_Y: u32 = 10;
+pub const INFUR_LOST_SEEN: u32 = 11;
+pub const INFUR_LOST_WORDS: u32 = 12;
+pub const INFUR_TRACK_MEMORY_REVIVED: u32 = 0;
+pub const INFUR_TRACK_MEMORY_LOST: u32 = 1;
+pub const INFUR_TRACK_MEMORY_EXPIRED: u32 = 2;
+pub const INFUR_TRACK_MEMORY_HELD: u32 = 3;
+pub const INFUR_TRACK_MEMORY_WORDS: u32 = 4;
+/// bit of `infur_features()`: the memory calls of a tracker exist
+pub const INFUR_FEATURE_TRACK_MEMORY: u32 = 128;
 /// Runs: the flag, the words of a record (`INFUR_RUN_WORDS` u32 each)
 pub const INFUR_RUNS_SKIP: u32 = 1;
 pub const INFUR_RUN_START: u32 = 0;
@@ -318,6 +340,11 @@ extern "C" {
     pub fn infur_tracker_create(c: *mut infur_ctx, max_regions: u32, pair_slots: u32, tracker: *mut *mut c_void) -> i32;
     pub fn infur_tracker_destroy(tracker: *mut c_void);
     pub fn infur_tracker_reset(tracker: *mut c_void, first_id: u32) -> i32;
+    pub fn infur_tracker_set_memory(tracker: *mut c_void, max_lost: u32, reach: u32, gallery_rows: u32) -> i32;
+    pub fn infur_tracker_memory(tracker: *mut c_void, gap_of_region: *mut u32, rows: u32, memory_summary: *mut u32,
+                                lost_table: *mut u64, lost_rows: u32) -> i32;
+    pub fn infur_tracker_memory_dev(tracker: *mut c_void, d_gap_of_region: *mut c_void, rows: u32, d_memory_summary: *mut c_void,
+                                    d_lost_table: *mut c_void, lost_rows: u32) -> i32;
     pub fn infur_tracks(tracker: *mut c_void, labels: *const u32, table: *const u64, table_rows: u32, n_regions: u32, h: u32, w: u32,
                         min_overlap: u32, track_of_region: *mut u32, track_plane: *mut u32, track_table: *mut u64,
                         summary: *mut u32) -> i32;

@@ -511,6 +511,34 @@ impl HipTracks {
         if rc != sys::INFUR_OK { return Err(HipError::from_ctx(&ctx, rc)); }
         Ok(Self { raw, ctx, min_overlap: 1, dirty: true })
     }
+    /// Keep lost tracks for up to `max_lost` steps (0: memory off, the other two are ignored): a region that would start a new track
+    /// takes a lost track of its class back when its box meets that track's last box grown by `reach` pixels per step of absence.
+    /// `gallery_rows`: 0 = 4096, at most 65536.  Forgets the remembered frame and the gallery.
+    pub fn set_memory(&mut self, max_lost: u32, reach: u32, gallery_rows: u32) -> Result<(), HipError> {
+        let rc = unsafe { sys::infur_tracker_set_memory(self.raw, max_lost, reach, gallery_rows) };
+        if rc != sys::INFUR_OK { return Err(HipError::from_ctx(&self.ctx, rc)); }
+        self.dirty = true;
+        Ok(())
+    }
+    /// What the last step left on a tracker with memory: `rows` words of gap_of_region, the four `INFUR_TRACK_MEMORY_*` words and
+    /// the first `min(HELD, lost_rows)` gallery entries (`INFUR_LOST_WORDS` words each, in gallery order).
+    pub fn memory(&self, rows: usize, lost_rows: usize) -> Result<TracksMemory, HipError> {
+        let mut out = TracksMemory { gap_of_region: vec![0; rows], summary: [0; 4], lost: vec![0; lost_rows * sys::INFUR_LOST_WORDS as usize] };
+        let rc = unsafe {
+            sys::infur_tracker_memory(self.raw, if rows > 0 { out.gap_of_region.as_mut_ptr() } else { std::ptr::null_mut() }, rows as u32,
+                                      out.summary.as_mut_ptr(), if lost_rows > 0 { out.lost.as_mut_ptr() } else { std::ptr::null_mut() },
+                                      lost_rows as u32)
+        };
+        if rc != sys::INFUR_OK { return Err(HipError::from_ctx(&self.ctx, rc)); }
+        out.lost.truncate(out.held().min(lost_rows) * sys::INFUR_LOST_WORDS as usize);
+        Ok(out)
+    }
+}
+/// What `HipTracks::memory` reads: see `infur_tracker_memory`.
+pub struct TracksMemory { pub gap_of_region: Vec<u32>, pub summary: [u32; 4], pub lost: Vec<u64> }
+impl TracksMemory {
+    pub fn held(&self) -> usize { self.summary[sys::INFUR_TRACK_MEMORY_HELD as usize] as usize }
+    pub fn word(&self, entry: usize, word: u32) -> u64 { self.lost[entry * sys::INFUR_LOST_WORDS as usize + word as usize] }
 }
 impl Drop for HipTracks {
     fn drop(&mut self) { unsafe { sys::infur_tracker_destroy(self.raw) } }
