@@ -46,7 +46,7 @@ class Tracker(T.Tracker):
         """forgets the remembered frame and the gallery; next_id and the frame counter keep counting"""
         self.max_lost, self.reach = max_lost, reach
         self.G = gallery_rows or DEFAULT_ROWS
-        assert self.G <= MAX_ROWS
+        assert self.G <= MAX_ROWS or not max_lost  # (memory off: the other two arguments are ignored)
         self.valid = False
         self.gallery = np.zeros((0, L_WORDS), np.uint64)
 
