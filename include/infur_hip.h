@@ -887,6 +887,66 @@ int32_t infur_frame_coverage_dev(infur_ctx* ctx, const void* d_bgr, uint32_t w, 
                                  void* d_loops, uint32_t loops_rows, void* d_vertices, uint32_t vertex_rows, void* d_counts,
                                  void* d_stats, uint32_t stats_capacity, void* d_scaled_bgr, uint32_t* ow, uint32_t* oh);
 
+/* ---- Anchors: a distance transform and one interior label point per region ----
+ * A table row places its object at a centroid or a box corner, and neither has to lie on the object: the centroid of a "C", a
+ * ring or a horseshoe is a pixel of something else.  The point a caption, a click target or a "where is it" answer needs is the
+ * region's most interior pixel, with the radius of the largest disc that fits there: the argmax of a distance transform.  Anchors
+ * computes both on the device.  Presence of this group is announced by infur_features() & INFUR_FEATURE_ANCHORS
+ * (INFUR_ABI_VERSION does not move).
+ *
+ * The input is a plane of h x w elements of elem_bytes = 1 (a class plane) or 4 (a label or track plane), h and w at most 65535.
+ * Runs' rules hold for elem_bytes, for a NULL plane, for unknown flag bits and for skip_value.
+ *   flags & INFUR_ANCHORS_SKIP   pixels whose value equals skip_value belong to no region (typically class 0, INFUR_REGION_NONE,
+ *                                INFUR_TRACK_NONE)
+ * Outputs, each optional (NULL = not wanted, and so is anchors with rows == 0; nothing wanted is INFUR_E_INVALID_ARG), none needs
+ * initialisation:
+ *   dist2     h*w uint32_t: for a pixel p of value v, the squared Euclidean distance between pixel centres from p to the nearest
+ *             position whose value differs from v.  Positions outside the frame count as differing -- the frame is a border, so an
+ *             anchor and its disc lie inside the picture -- and so do skipped pixels.  Every pixel that is not skipped has
+ *             dist2 >= 1, and exactly 1 where it touches a border; a skipped pixel has 0.  The distance is by VALUE, not by
+ *             connected component: on a label plane the two coincide, on a class plane two touching objects of one class share
+ *             one interior
+ *   anchors   rows rows of INFUR_ANCHOR_WORDS uint32_t, one per value v < rows: INFUR_ANCHOR_PIXEL the linear index y*w + x of the
+ *             pixel of value v with the largest dist2, ties to the smallest index, INFUR_ANCHOR_DIST2 that dist2.  A value no
+ *             pixel holds, and the skipped value, read (INFUR_ANCHOR_NONE, 0).  Every one of the rows is written, whatever the
+ *             plane holds; a pixel whose value is at or above rows still gets its dist2 and touches no row
+ * h*w == 0 writes the NONE rows and nothing else; h or w above 65535 and a NULL plane with h*w > 0 are INFUR_E_INVALID_ARG.  No
+ * output is touched when a call is rejected.  Everything is an integer, exact, and a function of the plane alone: identical bytes
+ * from run to run. */
+#define INFUR_ANCHOR_NONE 0xFFFFFFFFu
+enum { INFUR_ANCHORS_SKIP = 1 };
+enum { INFUR_ANCHOR_PIXEL = 0, INFUR_ANCHOR_DIST2 = 1, INFUR_ANCHOR_WORDS = 2 };
+enum { INFUR_FEATURE_ANCHORS = 256 };
+
+/* on a given plane, host pointers */
+int32_t infur_anchors(infur_ctx* ctx, const void* plane, uint32_t elem_bytes, uint32_t h, uint32_t w, uint32_t flags,
+                      uint32_t skip_value, uint32_t* dist2, uint32_t* anchors, uint32_t rows);
+/* device pointers throughout; enqueued on the context's stream as one memset and three launches, never synchronises, capturable
+ * after one call outside the capture (which allocates the scratch: two bytes per pixel and eight per row, owned by the context;
+ * it grows only with a request larger than any before, and a graph captured around the call is re-captured after that).  This is
+ * the call that composes on the device: infur_frame_regions_dev or infur_frame_tracks_dev, then infur_anchors_dev on the label or
+ * track plane they left in device memory.  The outputs must not overlap the plane. */
+int32_t infur_anchors_dev(infur_ctx* ctx, const void* d_plane, uint32_t elem_bytes, uint32_t h, uint32_t w, uint32_t flags,
+                          uint32_t skip_value, void* d_dist2, void* d_anchors, uint32_t rows);
+/* The fused frame path with an anchor per object: scale -> model -> Segments decode(out[0]) -> Regions -> Anchors of the label
+ * plane with INFUR_REGION_NONE skipped, in one call.  The arguments are infur_frame_regions' own, then dist2 (dist2_capacity in
+ * bytes, ow*oh*4 needed; less is INFUR_E_CAPACITY, checked, like the other capacities, once a model is loaded) and anchors, which
+ * has table_rows rows: row i belongs to region i, table or no table.  Every output is optional, and at least one of labels,
+ * table, n_regions, dist2 and anchors (with table_rows) must be given; the label plane goes to scratch of the library's own when
+ * the caller does not want it.  The calls inherit infur_frame_regions' checks and errors: with no model loaded the Scale stage
+ * still runs and the call returns INFUR_E_MODEL_NOT_LOADED.  They always enqueue eagerly and leave the graphs cached for
+ * infur_frame_advance_dev alone.  (The stream ring, batch and group calls produce RGBA only.) */
+int32_t infur_frame_anchors(infur_ctx* ctx, const uint8_t* bgr, uint32_t w, uint32_t h, float factor, uint32_t scale_mode,
+                            uint32_t decode, uint32_t connectivity, uint32_t min_pixels, uint32_t flags, uint8_t* klass,
+                            uint8_t* conf, size_t plane_capacity, uint32_t* labels, size_t labels_capacity, uint64_t* table,
+                            uint32_t table_rows, uint32_t* n_regions, uint8_t* scaled_bgr, uint32_t* ow, uint32_t* oh,
+                            uint32_t* dist2, size_t dist2_capacity, uint32_t* anchors);
+int32_t infur_frame_anchors_dev(infur_ctx* ctx, const void* d_bgr, uint32_t w, uint32_t h, float factor, uint32_t scale_mode,
+                                uint32_t decode, uint32_t connectivity, uint32_t min_pixels, uint32_t flags, void* d_klass,
+                                void* d_conf, size_t plane_capacity, void* d_labels, size_t labels_capacity, void* d_table,
+                                uint32_t table_rows, void* d_n_regions, void* d_scaled_bgr, uint32_t* ow, uint32_t* oh,
+                                void* d_dist2, size_t dist2_capacity, void* d_anchors);
+
 /* ---- streaming (infur/src/main.rs:27-99,105): bounded queue, copies overlapped with compute ----
  * The reference back-pressures its producer with sync_channel(2) (main.rs:105); a stream
  * here is a ring of `depth` pinned + device slots.  submit() copies the caller's frame into a

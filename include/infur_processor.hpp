@@ -452,6 +452,63 @@ private:
     bool dirty_ = true;
 };
 
+/// What `Anchors` produces: `dist2` holds the width * height squared distances to the nearest pixel of another value or to the
+/// frame (0: a skipped pixel), `anchors` `rows` rows of INFUR_ANCHOR_WORDS words, one per value below `rows`;
+/// (INFUR_ANCHOR_NONE, 0): no pixel holds the value.
+struct AnchorsOut {
+    uint32_t rows = 256;
+    bool want_dist2 = true;
+    uint32_t width = 0, height = 0;
+    std::vector<uint32_t> dist2, anchors;
+    uint32_t word(uint32_t row, uint32_t w) const { return anchors[(size_t)row * INFUR_ANCHOR_WORDS + w]; }
+    bool has(uint32_t row) const { return word(row, INFUR_ANCHOR_PIXEL) != INFUR_ANCHOR_NONE; }
+    uint32_t x(uint32_t row) const { return word(row, INFUR_ANCHOR_PIXEL) % width; }
+    uint32_t y(uint32_t row) const { return word(row, INFUR_ANCHOR_PIXEL) / width; }
+};
+
+/// The stage that measures how thick a region is: the exact squared distance transform of a byte plane (class) or a u32 plane
+/// (labels, tracks) by value, the frame counting as a border, and per value its most interior pixel (ties to the smallest index).
+/// Integer results, identical from run to run.
+/// Command = skip (the pixels of `value` belong to no region) or not; Input = a plane of uint8_t or uint32_t, Output = AnchorsOut.
+class Anchors {
+public:
+    struct Cmd {
+        enum Kind { Skip, NoSkip } kind;
+        uint32_t value;
+    };
+    explicit Anchors(Context& c) : c_(c) {}
+    Status control(Cmd cmd) {
+        const uint32_t flags = cmd.kind == Cmd::Skip ? (uint32_t)INFUR_ANCHORS_SKIP : 0u, value = cmd.kind == Cmd::Skip ? cmd.value : 0u;
+        if (cmd.kind != Cmd::Skip && cmd.kind != Cmd::NoSkip) return INFUR_E_INVALID_ARG;
+        dirty_ = dirty_ || flags != flags_ || value != skip_value_;
+        flags_ = flags;
+        skip_value_ = value;
+        return INFUR_OK;
+    }
+    bool is_dirty() const { return dirty_; }
+    Status advance(const std::vector<uint8_t>& plane, uint32_t height, uint32_t width, AnchorsOut& out) {
+        return run(plane.data(), plane.size(), 1, height, width, out);
+    }
+    Status advance(const std::vector<uint32_t>& plane, uint32_t height, uint32_t width, AnchorsOut& out) {
+        return run(plane.data(), plane.size(), 4, height, width, out);
+    }
+
+private:
+    Status run(const void* plane, size_t elems, uint32_t elem_bytes, uint32_t height, uint32_t width, AnchorsOut& out) {
+        dirty_ = false;
+        if (elems != (size_t)width * height) return INFUR_E_SHAPE;
+        out.width = width;
+        out.height = height;
+        out.dist2.assign(out.want_dist2 ? elems : 0, 0);
+        out.anchors.assign((size_t)out.rows * INFUR_ANCHOR_WORDS, 0);
+        return infur_anchors(c_.get(), plane, elem_bytes, height, width, flags_, skip_value_, out.want_dist2 ? out.dist2.data() : nullptr,
+                             out.rows ? out.anchors.data() : nullptr, out.rows);
+    }
+    Context& c_;
+    uint32_t flags_ = 0, skip_value_ = 0;
+    bool dirty_ = true;
+};
+
 /// What `Outlines` produces: `loops` holds min(n_loops, loops_rows) records of INFUR_LOOP_WORDS words, `vertices` the first
 /// min(n_vertices, vertex_rows) vertex ids Y*(width+1) + X, loops back to back; the three counts are complete whatever the rows
 /// are (n_loops == 0 with n_edges > 0: the edges exceeded the capacity).

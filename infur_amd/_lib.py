@@ -79,6 +79,11 @@ COVERAGE_SKIP = 1
 COVERAGE_LOOPS, COVERAGE_VERTICES, COVERAGE_DEGENERATE, COVERAGE_STATUS, COVERAGE_AUG, COVERAGE_ARCS, COVERAGE_COUNT_WORDS = 0, 1, 2, 3, 4, 5, 6
 COVERAGE_TRUNCATED, COVERAGE_MALFORMED, COVERAGE_OVERFLOW = 1, 2, 4
 FEATURE_COVERAGE = 64
+# Anchors (infur_anchors / infur_frame_anchors): the flag, the words of a row, the "no pixel" index, the feature bit
+ANCHORS_SKIP = 1
+ANCHOR_PIXEL, ANCHOR_DIST2, ANCHOR_WORDS = 0, 1, 2
+ANCHOR_NONE = 0xFFFFFFFF
+FEATURE_ANCHORS = 256
 
 
 class Options(C.Structure):
@@ -219,6 +224,12 @@ SIGNATURES = {
                                          _vp, _u32p, _u32p]),
     "infur_frame_coverage_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _vp,
                                              _u32, _vp, _u32p, _u32p]),
+    "infur_anchors": (C.c_int32, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _u32]),
+    "infur_anchors_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _u32]),
+    "infur_frame_anchors": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp, _vp,
+                                        _u32p, _u32p, _vp, _sz, _vp]),
+    "infur_frame_anchors_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp,
+                                            _vp, _u32p, _u32p, _vp, _sz, _vp]),
     "infur_stream_create": (C.c_int32, [_vp, _u32, C.POINTER(_vp)]),
     "infur_stream_destroy": (None, [_vp]),
     "infur_stream_add_lane": (C.c_int32, [_vp, _vp]),

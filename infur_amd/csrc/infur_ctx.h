@@ -185,6 +185,9 @@ struct infur_ctx {
     // Coverage (infur_coverage.cpp): the junction bitmaps, augmented loops, arc table, keep flags, ranks and scan sums, and the
     // host-pointer calls' staging.  Private like the above.
     infur::Buf st_cov, st_cov_io;
+    // Anchors (infur_anchors.cpp): the u16 row-distance plane and the u64 key row per value, the label plane the frame calls let
+    // Regions write when the caller does not want it, and the host-pointer calls' staging.  Private like the above.
+    infur::Buf st_anch, st_anch_plane, st_anch_io;
     // Tracks (infur_tracks.cpp): the live trackers of this context; infur_ctx_destroy releases their device memory and orphans them
     std::vector<infur_tracker*> trackers;
 

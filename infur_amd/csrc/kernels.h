@@ -358,6 +358,17 @@ size_t runs_scratch_bytes(size_t npix);
 hipError_t launch_runs(const void* plane, int elem_bytes, unsigned H, unsigned W, int skip, unsigned skip_value, void* scratch, unsigned* runs,
                        unsigned rows, unsigned* row_start, unsigned* d_n, hipStream_t s);
 
+// Anchors (anchors.hip): the exact squared Euclidean distance transform by value of an H x W plane (both at most 65535) of 1- or
+// 4-byte elements, the frame counting as a differing value -- dist2[H * W] u32 -- and per value v < rows the pixel of largest dist2,
+// ties to the smallest index -- anchors[rows x kAnchorWords] u32 (PIXEL, DIST2), (0xFFFFFFFF, 0) where no pixel holds v (each
+// optional; device memory; every one of the rows is written).  skip: pixels of skip_value belong to no region and read dist2 = 0.
+// scratch: anchors_scratch_bytes(H * W, rows) bytes the launches own for the call.  Stream-ordered; one memset and three launches,
+// no workgroup waits for another.  H * W == 0 writes the NONE rows and needs no scratch.
+constexpr int kAnchorWords = 2;
+size_t anchors_scratch_bytes(size_t npix, unsigned rows);
+hipError_t launch_anchors(const void* plane, int elem_bytes, unsigned H, unsigned W, int skip, unsigned skip_value, void* scratch, unsigned* dist2,
+                          unsigned* anchors, unsigned rows, hipStream_t s);
+
 // Outlines (outlines.hip): the boundaries of the value-regions of an H x W plane of 1- or 4-byte elements as closed loops --
 // loops_rows x kLoopWords u32 records (OFFSET, COUNT, VALUE, START), vertex_rows u32 vertex ids Y * (W + 1) + X, and counts[3] =
 // {n_loops, n_vertices, n_edges} (each optional; device memory).  skip: pixels of skip_value belong to no region; conn8: the

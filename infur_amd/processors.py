@@ -15,6 +15,7 @@ exceptions carrying the status code of include/infur_hip.h.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from dataclasses import dataclass
 from typing import Generic, List, NamedTuple, Optional, TypeVar
@@ -628,11 +629,13 @@ class RegionsFrame(NamedTuple):
     scaled: Optional[np.ndarray]
 
 
-def region_summary(table: np.ndarray, n: int, ow: int, oh: int, names=None) -> List[dict]:
+def region_summary(table: np.ndarray, n: int, ow: int, oh: int, names=None, anchors=None) -> List[dict]:
     """The caption records of a frame's objects: one dict per table row, in id order -- ``id``, ``klass``, ``name``, ``pixels``,
     ``share`` of the ow x oh mask, ``centroid`` (x, y), ``box`` (min_x, min_y, max_x, max_y; inclusive), ``mean_confidence``
     in [0, 1] and ``first`` (x, y), the region's first pixel in raster order.  ``n`` may exceed the rows the table holds (a
-    truncated table): the rows there are are summarised.  ``names`` as in ``class_summary``."""
+    truncated table): the rows there are are summarised.  ``names`` as in ``class_summary``.  ``anchors`` (Anchors' rows, row i
+    for region i) adds ``anchor`` [x, y], the region's most interior pixel, and ``radius``, the distance from there to the nearest
+    pixel of anything else, to two decimals; both are None for a row without an anchor."""
     if names is None:
         L = _lib.load()
         names = lambda k: voc_class_name(L, k)  # noqa: E731
@@ -655,6 +658,13 @@ def region_summary(table: np.ndarray, n: int, ow: int, oh: int, names=None) -> L
             "mean_confidence": int(row[_lib.STAT_SUM_CONF]) / (255.0 * px),
             "first": (first % ow, first // ow) if ow else (0, 0),
         })
+    if anchors is not None:
+        arows = np.asarray(anchors, np.uint32).reshape(-1, _lib.ANCHOR_WORDS)
+        for i, rec in enumerate(recs):
+            at = int(arows[i, _lib.ANCHOR_PIXEL]) if i < len(arows) else _lib.ANCHOR_NONE
+            have = at != _lib.ANCHOR_NONE and ow
+            rec["anchor"] = [at % ow, at // ow] if have else None
+            rec["radius"] = round(math.sqrt(int(arows[i, _lib.ANCHOR_DIST2])), 2) if have else None
     return recs
 
 
@@ -905,6 +915,80 @@ class RunsFrame(NamedTuple):
     n: Optional[int]
     stats: Optional[np.ndarray]
     scaled: Optional[np.ndarray]
+
+
+@dataclass
+class AnchorsCmd:
+    """``Anchors``' command: ``Skip(value)`` takes the pixels of that value out of every region (``Skip(None)``: every value is
+    a region again)."""
+
+    skip: Optional[int] = None
+
+    @staticmethod
+    def Skip(v: Optional[int]) -> "AnchorsCmd":
+        return AnchorsCmd(skip=v)
+
+
+class AnchorsOut:
+    """``Anchors``' ``&mut Output``: what to produce (``rows`` anchor rows, ``want_dist2``) and, after ``advance``, the results --
+    ``dist2`` [H, W] u32 or None, ``anchors`` [rows, 2] u32 (columns ``_lib.ANCHOR_PIXEL``, ``_lib.ANCHOR_DIST2``; a value no
+    pixel holds reads ``(_lib.ANCHOR_NONE, 0)``) or None."""
+
+    def __init__(self, rows: int = 256, want_dist2: bool = True):
+        self.rows, self.want_dist2 = rows, want_dist2
+        self.dist2 = self.anchors = None
+
+
+class Anchors(Processor):
+    """The stage that measures how thick a region is: the exact squared distance transform of a class plane (u8) or a label /
+    track plane (u32) by value, the frame counting as a border, and per value its most interior pixel.
+
+    Command = ``AnchorsCmd``.  Input = a plane [H, W] of u8 or u32; Output = ``AnchorsOut``.  Integers throughout, identical
+    from run to run.
+    """
+
+    def __init__(self, ctx: Context, skip: Optional[int] = None):
+        self.ctx = ctx
+        self.skip = skip
+        self.dirty = True
+
+    def control(self, cmd: AnchorsCmd) -> "Anchors":
+        if cmd.skip is not None and not 0 <= cmd.skip <= 0xFFFFFFFF:
+            raise InfurError(_lib.E_INVALID_ARG, f"skip value {cmd.skip}: a u32")
+        self.dirty = self.dirty or cmd.skip != self.skip
+        self.skip = cmd.skip
+        return self
+
+    def is_dirty(self) -> bool:
+        return self.dirty
+
+    def advance(self, inp: np.ndarray, out: AnchorsOut) -> None:
+        self.dirty = False
+        if inp.ndim != 2 or inp.dtype.itemsize not in (1, 4) or inp.dtype.kind not in "ui":
+            raise InfurError(_lib.E_SHAPE, f"expected an [H,W] plane of 1- or 4-byte integers, got {inp.shape} {inp.dtype}")
+        plane = np.ascontiguousarray(inp)
+        h, w = plane.shape
+        rows = max(0, int(out.rows))
+        dist2 = np.empty((h, w), np.uint32) if out.want_dist2 else None
+        anchors = np.empty((rows, _lib.ANCHOR_WORDS), np.uint32) if rows else None
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        self.ctx.check(self.ctx.L.infur_anchors(self.ctx.h, ptr(plane), plane.dtype.itemsize, h, w, _lib.ANCHORS_SKIP if self.skip is not None else 0,
+                                                self.skip or 0, _ptr(dist2), ptr(anchors), rows))
+        out.dist2, out.anchors = dist2, anchors
+
+
+class AnchorsFrame(NamedTuple):
+    """``FramePath.advance_anchors``: ``RegionsFrame``'s fields, then the squared distances [oh, ow] u32 of the label plane (None
+    where not wanted) and the anchor rows [min(n, table_rows), 2] u32, row i for region i"""
+
+    klass: Optional[np.ndarray]
+    conf: Optional[np.ndarray]
+    labels: Optional[np.ndarray]
+    table: Optional[np.ndarray]
+    n: Optional[int]
+    scaled: Optional[np.ndarray]
+    dist2: Optional[np.ndarray]
+    anchors: Optional[np.ndarray]
 
 
 def runs_decode(runs: np.ndarray, n: int, h: int, w: int, fill: int = 0, dtype=None) -> np.ndarray:
@@ -1340,6 +1424,30 @@ class FramePath:
         if not self._loaded(rc):
             return RegionsFrame(None, None, None, None, None, scaled)
         return RegionsFrame(klass, conf, labels, table[:min(n.value, rows)] if table is not None else None, n.value, scaled)
+
+    def advance_anchors(self, img: np.ndarray, factor: float = 1.0, decode: int = _lib.DECODE_RAW, connectivity: int = _lib.CONNECT_8,
+                        min_pixels: int = 0, flags: int = 0, table_rows: int = 1024, want_labels: bool = True, want_klass: bool = True,
+                        want_conf: bool = True, want_scaled: bool = False, want_dist2: bool = True) -> AnchorsFrame:
+        """The fused path with an anchor per object, scale -> model -> Segments decode -> Regions -> Anchors of the label plane, in
+        one call -> ``AnchorsFrame``; every result field is None when no model is loaded (``scaled`` is still produced)."""
+        img, w, h, f, ow, oh = self._front(img, factor)
+        npix = oh.value * ow.value
+        rows = max(0, min(int(table_rows), npix))
+        klass, conf = self._plane(ow, oh, want_klass), self._plane(ow, oh, want_conf)
+        labels = self._plane(ow, oh, want_labels, np.uint32)
+        table = np.zeros((rows, _lib.REGION_WORDS), np.uint64) if rows else None
+        scaled = self._plane(ow, oh, want_scaled, channels=3)
+        dist2 = self._plane(ow, oh, want_dist2, np.uint32)
+        anchors = np.empty((rows, _lib.ANCHOR_WORDS), np.uint32) if rows else None
+        n = C.c_uint32(0)
+        rc = self.ctx.L.infur_frame_anchors(self.ctx.h, img.ctypes.data, w, h, f, self.scale_mode, decode, connectivity, min_pixels, flags,
+                                            _ptr(klass), _ptr(conf), npix, _ptr(labels), npix * 4, _ptr(table), rows, C.addressof(n), _ptr(scaled),
+                                            C.byref(ow), C.byref(oh), _ptr(dist2), npix * 4, _ptr(anchors))
+        if not self._loaded(rc):
+            return AnchorsFrame(None, None, None, None, None, scaled, None, None)
+        k = min(n.value, rows)
+        return AnchorsFrame(klass, conf, labels, table[:k] if table is not None else None, n.value, scaled, dist2,
+                            anchors[:k] if anchors is not None else None)
 
     def advance_tracks(self, tracks: "Tracks", img: np.ndarray, factor: float = 1.0, decode: int = _lib.DECODE_RAW,
                        connectivity: int = _lib.CONNECT_8, min_pixels: int = 0, flags: int = 0, table_rows: int = 1024,

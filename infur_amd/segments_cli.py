@@ -47,6 +47,12 @@ the simplified arrays in the same per-frame layout, its three counts being n_loo
 degenerate loops (COUNT below 3: a thin region collapsed to two points; skip them), and every line gains ``"n_degenerate"``.
 ``--outlines-shared`` (with ``--outlines-tolerance``) simplifies every border between two regions once (``infur_coverage``), so that
 the polygons of neighbours still fit: same file layout, and junction vertices may be added to a loop.
+
+``--anchors`` (needs ``--regions`` or ``--tracks``) places every object: the label plane goes through the distance transform where
+Regions left it on the device (``infur_anchors_dev``, pixels of no region skipped), and every region record gains ``"anchor"``
+[x, y], its most interior pixel -- on the object, which its centroid need not be -- and ``"radius"``, the distance from there to the
+nearest pixel of anything else or to the frame.  ``--dist-out FILE`` (needs ``--anchors``) receives the u32 planes of squared
+distances back to back (0: a pixel of no region).
 """
 from __future__ import annotations
 
@@ -92,6 +98,8 @@ def main(argv=None) -> int:
     ap.add_argument("--outlines-tolerance", type=float, default=None, help="simplify the loops within this many pixels (needs --outlines-out)")
     ap.add_argument("--outlines-shared", action="store_true",
                     help="simplify every shared border once, so that neighbouring polygons still fit (needs --outlines-tolerance)")
+    ap.add_argument("--anchors", action="store_true", help="add every region's most interior pixel and its radius (needs --regions or --tracks)")
+    ap.add_argument("--dist-out", default="", help="raw u32 planes of squared distances, four bytes per pixel (needs --anchors)")
     a = ap.parse_args(argv)
     if a.outlines_shared and a.outlines_tolerance is None:
         ap.error("--outlines-shared needs --outlines-tolerance")
@@ -104,6 +112,10 @@ def main(argv=None) -> int:
     a.regions = a.regions or a.tracks
     if a.regions_out and not a.regions:
         ap.error("--regions-out needs --regions")
+    if a.anchors and not a.regions:
+        ap.error("--anchors needs --regions or --tracks")
+    if a.dist_out and not a.anchors:
+        ap.error("--dist-out needs --anchors")
 
     if a.runs_out and a.runs_plane == "labels" and not a.regions:
         ap.error("--runs-plane labels needs --regions")
@@ -152,12 +164,14 @@ def main(argv=None) -> int:
     ftrk = open(a.tracks_out, "wb") if a.tracks_out else None
     fruns = open(a.runs_out, "wb") if a.runs_out else None
     foutl = open(a.outlines_out, "wb") if a.outlines_out else None
+    fdist = open(a.dist_out, "wb") if a.dist_out else None
     rpath = None
     if a.regions:
         oh, ow = _out_dims(ctx, a.width, a.height, a.scale)
         rpath = _RegionsPath(ctx, a.width, a.height, ow, oh, a.scale, fp.scale_mode, model.get_info().num_classes, max(0, a.max_regions),
                              tracks=a.tracks, memory=(a.tracks_memory, a.tracks_reach),
-                             runs=fruns is not None, outlines=foutl is not None, simplify=tol16 is not None, shared=a.outlines_shared)
+                             runs=fruns is not None, outlines=foutl is not None, simplify=tol16 is not None, shared=a.outlines_shared,
+                             anchors=a.anchors)
         flags = _lib.REGIONS_SKIP_BACKGROUND if a.skip_background else 0
     n, t0 = 0, time.perf_counter()
     while True:
@@ -169,13 +183,15 @@ def main(argv=None) -> int:
             raise
         if rpath is not None:
             s, labels, table, nreg = rpath.advance(img, decode, a.connectivity, a.min_pixels, flags, flab is not None, fconf is not None,
-                                                   freg is not None, keep_labels=(fruns is not None and a.runs_plane == "labels") or foutl is not None)
+                                                   freg is not None, keep_labels=(fruns is not None and a.runs_plane == "labels") or foutl is not None or a.anchors)
             if a.tracks:
                 ttab, tplane, tsum = rpath.track(max(0, a.min_overlap), ftrk is not None, keep_plane=fruns is not None and a.runs_plane == "tracks")
             if fruns is not None:
                 runs, nruns = rpath.runs(a.runs_plane, a.runs_skip)
             if foutl is not None:
                 outl = rpath.outlines(a.outlines_skip, a.connectivity, tol16, a.outlines_shared)
+            if a.anchors:
+                anch, dist2 = rpath.anchors(fdist is not None)
         elif foutl is not None and fruns is None and flab is None and fconf is None:  # polygons, counts and captions: no dense plane
             if tol16 is None:
                 r = fp.advance_outlines(img, a.scale, decode, skip=a.outlines_skip, connectivity=a.connectivity, loops_rows=1 << 32, vertex_rows=1 << 32)
@@ -211,7 +227,7 @@ def main(argv=None) -> int:
         rec = {"frame": fid, "width": ow, "height": oh, "classes": class_summary(s.stats, ow, oh)}
         if rpath is not None:
             rec["n_regions"] = nreg
-            rec["regions"] = region_summary(table, nreg, ow, oh)
+            rec["regions"] = region_summary(table, nreg, ow, oh, anchors=anch) if a.anchors else region_summary(table, nreg, ow, oh)
             if a.tracks:
                 for r, t in zip(rec["regions"], track_summary(table, ttab, nreg, ow, oh)):
                     r["track"], r["age"] = t["track"], t["age"]
@@ -226,6 +242,8 @@ def main(argv=None) -> int:
                     ftrk.write(memoryview(tplane).cast("B"))
             if freg is not None:
                 freg.write(memoryview(labels).cast("B"))
+            if fdist is not None:
+                fdist.write(memoryview(dist2).cast("B"))
         if fruns is not None:
             rec["n_runs"] = nruns
             fruns.write(int(nruns).to_bytes(4, "little"))
@@ -238,7 +256,7 @@ def main(argv=None) -> int:
                 foutl.write(memoryview(np.ascontiguousarray(part)).cast("B"))
         fst.write(json.dumps(rec) + "\n")
         n += 1
-    for f in (flab, fconf, freg, ftrk, fruns, foutl, fst):
+    for f in (flab, fconf, freg, ftrk, fruns, foutl, fdist, fst):
         if f is not None:
             f.flush()
     el = time.perf_counter() - t0
@@ -255,7 +273,7 @@ class _RegionsPath:
     they are; the tables, the count and the planes that are written out are all that is copied back."""
 
     def __init__(self, ctx, w, h, ow, oh, factor, scale_mode, classes, rows, tracks=False, memory=(0, 0), runs=False, outlines=False, simplify=False,
-                 shared=False):
+                 shared=False, anchors=False):
         import ctypes as C
 
         self.ctx, self.w, self.h, self.ow, self.oh, self.factor, self.mode = ctx, w, h, ow, oh, float(factor), scale_mode
@@ -267,7 +285,8 @@ class _RegionsPath:
                 ((("runs", ow * oh * _RUN_BYTES), ("nruns", 4)) if runs else ()) + \
                 ((("loops", ow * oh * _LOOP_BYTES), ("vertices", ow * oh * 16), ("ocounts", 12)) if outlines else ()) + \
                 ((("sloops", ow * oh * _LOOP_BYTES), ("svertices", ow * oh * 16 + (4 * (ow + 1) * (oh + 1) if shared else 0)), ("scounts", 24))
-                 if outlines and simplify else ()):
+                 if outlines and simplify else ()) + \
+                ((("anch", self.rows * _ANCHOR_BYTES), ("dist2", ow * oh * 4)) if anchors else ()):
             p = C.c_void_p(None)
             ctx.check(ctx.L.infur_dev_alloc(ctx.h, max(n, 4), C.byref(p)))
             self.d[name] = p
@@ -341,6 +360,19 @@ class _RegionsPath:
         n = int(self._read("nruns", (1,), np.uint32)[0])
         return self._read("runs", (n, _RUN_BYTES // 4), np.uint32), n
 
+    def anchors(self, want_dist2):
+        """infur_anchors_dev on the label plane `advance` left on the device, pixels of no region skipped -> (anchor rows of the
+        table's rows [min(n, rows), 2] u32, squared distances [oh, ow] u32 or None)"""
+        import numpy as np
+
+        c, d = self.ctx, self.d
+        if not (self.rows or want_dist2):
+            return np.zeros((0, _ANCHOR_BYTES // 4), np.uint32), None
+        c.check(c.L.infur_anchors_dev(c.h, d["labels"], 4, self.oh, self.ow, 1, 0xFFFFFFFF, d["dist2"] if want_dist2 else None,
+                                      d["anch"] if self.rows else None, self.rows))
+        return (self._read("anch", (min(self.n, self.rows), _ANCHOR_BYTES // 4), np.uint32),
+                self._read("dist2", (self.oh, self.ow), np.uint32) if want_dist2 else None)
+
     def outlines(self, skip, connectivity, tol16=None, shared=False):
         """infur_outlines_dev on the label plane `advance` left on the device -> (counts [3], loops [n_loops, 4], vertices
         [n_vertices]) u32: every object's polygon, no dense plane.  tol16: infur_simplify_dev behind it, on the device too; the
@@ -380,6 +412,7 @@ _ROW_BYTES = 10 * 8    # INFUR_REGION_WORDS u64 per region
 _TRACK_BYTES = 8 * 8   # INFUR_TRACK_WORDS u64 per region
 _RUN_BYTES = 3 * 4     # INFUR_RUN_WORDS u32 per run
 _LOOP_BYTES = 4 * 4    # INFUR_LOOP_WORDS u32 per loop
+_ANCHOR_BYTES = 2 * 4  # INFUR_ANCHOR_WORDS u32 per region
 
 
 def _out_dims(ctx, w, h, factor):

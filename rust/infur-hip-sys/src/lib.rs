@@ -193,6 +193,14 @@ pub const INFUR_COVERAGE_MALFORMED: u32 = 2;
 pub const INFUR_COVERAGE_OVERFLOW: u32 = 4;
 /// bit of `infur_features()`: the Coverage calls below exist
 pub const INFUR_FEATURE_COVERAGE: u32 = 64;
+/// Anchors: the flag, the words of a row (`INFUR_ANCHOR_WORDS` u32 each), the index of a row no pixel reached
+pub const INFUR_ANCHORS_SKIP: u32 = 1;
+pub const INFUR_ANCHOR_PIXEL: u32 = 0;
+pub const INFUR_ANCHOR_DIST2: u32 = 1;
+pub const INFUR_ANCHOR_WORDS: u32 = 2;
+pub const INFUR_ANCHOR_NONE: u32 = 0xFFFF_FFFF;
+/// bit of `infur_features()`: the Anchors calls below exist
+pub const INFUR_FEATURE_ANCHORS: u32 = 256;
 
 extern "C" {
     pub fn infur_abi_version() -> u32;
@@ -427,4 +435,19 @@ extern "C" {
                                     loops_rows: u32, d_vertices: *mut c_void, vertex_rows: u32, d_counts: *mut c_void,
                                     d_stats: *mut c_void, stats_capacity: u32, d_scaled_bgr: *mut c_void, ow: *mut u32,
                                     oh: *mut u32) -> i32;
+    // Anchors: the squared distance transform of a byte or u32 plane by value, one interior point per value
+    pub fn infur_anchors(c: *mut infur_ctx, plane: *const c_void, elem_bytes: u32, h: u32, w: u32, flags: u32, skip_value: u32,
+                         dist2: *mut u32, anchors: *mut u32, rows: u32) -> i32;
+    pub fn infur_anchors_dev(c: *mut infur_ctx, d_plane: *const c_void, elem_bytes: u32, h: u32, w: u32, flags: u32, skip_value: u32,
+                             d_dist2: *mut c_void, d_anchors: *mut c_void, rows: u32) -> i32;
+    pub fn infur_frame_anchors(c: *mut infur_ctx, bgr: *const u8, w: u32, h: u32, factor: f32, scale_mode: u32, decode: u32,
+                               connectivity: u32, min_pixels: u32, flags: u32, klass: *mut u8, conf: *mut u8, plane_capacity: usize,
+                               labels: *mut u32, labels_capacity: usize, table: *mut u64, table_rows: u32, n_regions: *mut u32,
+                               scaled_bgr: *mut u8, ow: *mut u32, oh: *mut u32, dist2: *mut u32, dist2_capacity: usize,
+                               anchors: *mut u32) -> i32;
+    pub fn infur_frame_anchors_dev(c: *mut infur_ctx, d_bgr: *const c_void, w: u32, h: u32, factor: f32, scale_mode: u32, decode: u32,
+                                   connectivity: u32, min_pixels: u32, flags: u32, d_klass: *mut c_void, d_conf: *mut c_void,
+                                   plane_capacity: usize, d_labels: *mut c_void, labels_capacity: usize, d_table: *mut c_void,
+                                   table_rows: u32, d_n_regions: *mut c_void, d_scaled_bgr: *mut c_void, ow: *mut u32, oh: *mut u32,
+                                   d_dist2: *mut c_void, dist2_capacity: usize, d_anchors: *mut c_void) -> i32;
 }

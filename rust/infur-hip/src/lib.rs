@@ -639,6 +639,63 @@ impl Processor for HipRuns {
     }
 }
 
+// ---------------------------------------------------------------- Anchors (a distance transform, one interior point per value)
+/// What `HipAnchors` produces: `dist2` holds the `w * h` squared distances to the nearest pixel of another value or to the frame
+/// (0: a skipped pixel), `anchors` `rows` rows of `INFUR_ANCHOR_WORDS` words (PIXEL, DIST2), one per value below `rows`;
+/// `(INFUR_ANCHOR_NONE, 0)`: no pixel holds the value.
+pub struct Anchors { pub rows: usize, pub want_dist2: bool, pub dist2: Vec<u32>, pub anchors: Vec<u32> }
+impl Default for Anchors {
+    fn default() -> Self { Self { rows: 256, want_dist2: true, dist2: Vec::new(), anchors: Vec::new() } }
+}
+impl Anchors {
+    pub fn word(&self, row: usize, word: u32) -> u32 { self.anchors[row * sys::INFUR_ANCHOR_WORDS as usize + word as usize] }
+    /// the anchor of value `row` as (x, y) in a plane of width `w`, `None` where no pixel holds it
+    pub fn point(&self, row: usize, w: usize) -> Option<(usize, usize)> {
+        let at = self.word(row, sys::INFUR_ANCHOR_PIXEL);
+        if at == sys::INFUR_ANCHOR_NONE || w == 0 { None } else { Some((at as usize % w, at as usize / w)) }
+    }
+}
+pub enum AnchorsCmd { Skip(u32), NoSkip }
+/// The stage that measures how thick a region is: exact squared distances by value, the frame counting as a border, and per
+/// value the most interior pixel (ties to the smallest index).  Integer results, identical from run to run.
+pub struct HipAnchors { ctx: Rc<Ctx>, skip: Option<u32>, dirty: bool }
+impl HipAnchors {
+    pub fn new(ctx: Rc<Ctx>) -> Self { Self { ctx, skip: None, dirty: true } }
+}
+impl Processor for HipAnchors {
+    type Command = AnchorsCmd;
+    type ControlError = HipError;
+    type Input = RunsPlane;
+    type Output = Anchors;
+    type ProcessResult = Result<(), HipError>;
+
+    fn control(&mut self, cmd: AnchorsCmd) -> Result<&mut Self, HipError> {
+        let skip = match cmd { AnchorsCmd::Skip(v) => Some(v), AnchorsCmd::NoSkip => None };
+        self.dirty |= skip != self.skip;
+        self.skip = skip;
+        Ok(self)
+    }
+    fn is_dirty(&self) -> bool { self.dirty }
+    fn advance(&mut self, inp: &RunsPlane, out: &mut Anchors) -> Result<(), HipError> {
+        self.dirty = false;
+        let [w, h] = inp.size;
+        let (ptr, len, elem_bytes) = match &inp.data {
+            RunsPlaneData::U8(p) => (p.as_ptr() as *const std::ffi::c_void, p.len(), 1u32),
+            RunsPlaneData::U32(p) => (p.as_ptr() as *const std::ffi::c_void, p.len(), 4u32),
+        };
+        if len != w * h { return Err(HipError::status(sys::INFUR_E_SHAPE)); }
+        out.dist2.resize(if out.want_dist2 { w * h } else { 0 }, 0);
+        out.anchors.resize(out.rows * sys::INFUR_ANCHOR_WORDS as usize, 0);
+        let rc = unsafe {
+            sys::infur_anchors(self.ctx.0, ptr, elem_bytes, h as u32, w as u32, if self.skip.is_some() { sys::INFUR_ANCHORS_SKIP } else { 0 },
+                               self.skip.unwrap_or(0), if out.want_dist2 { out.dist2.as_mut_ptr() } else { std::ptr::null_mut() },
+                               if out.rows > 0 { out.anchors.as_mut_ptr() } else { std::ptr::null_mut() }, out.rows as u32)
+        };
+        if rc != sys::INFUR_OK { return Err(HipError::from_ctx(&self.ctx, rc)); }
+        Ok(())
+    }
+}
+
 // ---------------------------------------------------------------- Outlines (region boundaries as polygon loops)
 /// What `HipOutlines` produces: `loops` holds `min(n_loops, loops_rows)` records of `INFUR_LOOP_WORDS` words (OFFSET, COUNT, VALUE,
 /// START), `vertices` the first `min(n_vertices, vertex_rows)` vertex ids `Y*(w+1) + X`, loops back to back; the three counts are
