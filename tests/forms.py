@@ -12,7 +12,8 @@ size of SIZES, writes
                       launch, the fused stem + pool, a reused arena -- after one frame of ANOTHER size through the same context, so
                       that stale bytes of other tensors lie behind every ragged tile
 
-into one .npz, and the product path's (layer, kernel, variant) profile records per size into a .json next to it.  With "digest" in
+into one .npz, and the product path's (layer, kernel, variant) profile records per size into a .json next to it ("records" in its
+options: also the records of the per-layer launches, with their flops and bytes, into a .records.json).  With "digest" in
 its options the child keeps a SHA-1 of every array ("D/<key>") instead of the array: the forced forms of a size whose 57 layers are
 1.5 GB.
 """
@@ -110,6 +111,13 @@ GEOM_SIZES = [(64, 256)]
 SIZE_SETS = {"edge": SIZES, "natural": NATURAL_SIZES, "geom": GEOM_SIZES}
 for _s in NATURAL_SIZES + GEOM_SIZES:
     PRE_FRAME[_s] = (97, 61)
+# the sizes that reach the edge classes the three lists above leave out: derived and held by tests/edge_cover.py (which imports this
+# module: the import stands here, after everything it reads), run by tests/test_gpu_edge_cover.py
+from edge_cover import COVER_SIZES  # noqa: E402
+
+SIZE_SETS["cover"] = COVER_SIZES
+for _s in COVER_SIZES:
+    PRE_FRAME[_s] = (97, 61)
 
 
 class SubformCase:
@@ -199,6 +207,7 @@ def child_main(argv):
     opts = json.loads(argv[3]) if len(argv) > 3 else {}
     sizes = [tuple(s) for s in opts.get("sizes", SIZES)]
     tile, digest = int(opts.get("tile", 0)), bool(opts.get("digest", False))
+    records = bool(opts.get("records", False))  # also keep the profile of the launches that made the L/ arrays (own_error.scope_of)
     sys.path.insert(0, ROOT)
     import ctypes as C
 
@@ -226,8 +235,9 @@ def child_main(argv):
         else:
             res[key] = a.copy()
 
-    c = Context(device=0, dtype=dtype, keep_activations=True, winograd_tile=tile)
+    c = Context(device=0, dtype=dtype, keep_activations=True, profile=records, winograd_tile=tile)
     m = Model(c).control(ModelCmd.LoadBlob(blob))
+    layer_records = {}
     for size in sizes:
         h, w = size
         fr = W.synth_frame(h, w, index=h + w)
@@ -242,6 +252,8 @@ def child_main(argv):
         lo, la = m.lowres()
         keep(f"L/{tag(size)}/out_low", lo)
         keep(f"L/{tag(size)}/aux_low", la)
+        if records:
+            layer_records[tag(size)] = [{k: r[k] for k in ("name", "kernel", "variant", "flops", "bytes")} for r in c.profile()]
     c.close()
 
     kernels = {}
@@ -263,6 +275,9 @@ def child_main(argv):
     np.savez(out_path, **res)
     with open(out_path + ".json", "w") as f:
         json.dump(kernels, f)
+    if records:
+        with open(out_path + ".records.json", "w") as f:
+            json.dump(layer_records, f)
     print("FORMS CHILD OK")
 
 
@@ -297,6 +312,10 @@ class Run:
             recs = json.load(f)
         self.kernels = {k: [(r[0], r[1]) for r in v] for k, v in recs.items()}  # size -> (layer, kernel)
         self.variants = {k: [tuple(r) for r in v] for k, v in recs.items()}  # size -> (layer, kernel, variant)
+        self.layer_records = None  # size -> the per-layer launches' records (a child run with records=True)
+        if os.path.exists(path + ".records.json"):
+            with open(path + ".records.json") as f:
+                self.layer_records = json.load(f)
 
     def keys(self):
         return self.npz.files
@@ -307,15 +326,16 @@ class Run:
     def discard(self):
         """the arrays of a form that has been compared are not needed again"""
         self.npz.close()
-        for p in (self.path, self.path + ".json"):
+        for p in (self.path, self.path + ".json", self.path + ".records.json"):
             if os.path.exists(p):
                 os.remove(p)
 
 
-def run_child(mode, cfg, plain, out_path, qblob_path="", extra_env=None, tile=0, sizes=None, digest=False, timeout=None):
+def run_child(mode, cfg, plain, out_path, qblob_path="", extra_env=None, tile=0, sizes=None, digest=False, timeout=None, records=False):
     """One child process for (mode, cfg, K loop) -> Run.  Raises ChildFailed; sets FATAL when the way the child ended says the GPU
     may be in trouble.  extra_env: hooks besides INFUR_CONV_CFG / INFUR_HL_PIPE; tile: the contexts' Winograd tile (0: default);
-    sizes: instead of SIZES; digest: keep a digest of every array instead of the array; timeout: instead of CHILD_TIMEOUT."""
+    sizes: instead of SIZES; digest: keep a digest of every array instead of the array; timeout: instead of CHILD_TIMEOUT; records:
+    the profile of the per-layer launches too (Run.layer_records)."""
     timeout = timeout or CHILD_TIMEOUT
     if FATAL:
         raise ChildFailed(f"not started: an earlier child of this module ended badly ({FATAL[0]})")
@@ -330,6 +350,8 @@ def run_child(mode, cfg, plain, out_path, qblob_path="", extra_env=None, tile=0,
     what = f"{mode} cfg {cfg}{' plain' if plain else ''}" + "".join(f" {k}={v}" for k, v in sorted((extra_env or {}).items())) + \
            (f" F({tile}x{tile})" if tile else "") + (f" at {[tag(s) for s in sizes]}" if sizes else "")
     opts = {"tile": tile, "digest": digest}
+    if records:
+        opts["records"] = True
     if sizes:
         opts["sizes"] = [list(s) for s in sizes]
     try:

@@ -97,6 +97,14 @@ def test_every_mode_and_scope_a_gpu_test_asks_for_is_in_the_table():
     assert "OE.grade_own(" in src and "OE.assert_table(" in src
     assert set(OE.OWN_SCOPES) | set(OE.OWN16_SCOPES) == {s for s in A.SCOPES if s.startswith("own")}
     used |= set(OE.OWN_SCOPES) | set(OE.OWN16_SCOPES)
+    # the rows of the own-error scopes at the derived cover sizes: tests/test_gpu_edge_cover.py grades a layer under cover/<kind> where
+    # the (mode, kind) has such a row and under own/<kind> where it has none; every cover row stands beside an own row of its mode
+    src = open(os.path.join(HERE, "test_gpu_edge_cover.py")).read()
+    assert 'scope.replace("own", "cover", 1)' in src
+    cover = {s for s in A.SCOPES if s.startswith("cover")}
+    for s in cover:
+        assert s.replace("cover", "own", 1) in A.SCOPES and set(A.ASKED[s]) <= set(A.ASKED[s.replace("cover", "own", 1)]), s
+    used |= cover
     assert used == set(A.SCOPES)
     # the modes the files run under a scope (parametrize lists and loops) are spelled out in ASKED; the sweep's are the test's own
     src = open(os.path.join(HERE, "test_gpu_hostile.py")).read()
