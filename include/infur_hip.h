@@ -947,6 +947,104 @@ int32_t infur_frame_anchors_dev(infur_ctx* ctx, const void* d_bgr, uint32_t w, u
                                 uint32_t table_rows, void* d_n_regions, void* d_scaled_bgr, uint32_t* ow, uint32_t* oh,
                                 void* d_dist2, size_t dist2_capacity, void* d_anchors);
 
+/* ---- Compare: the confusion matrix and the per-object IoU between two planes ----
+ * The stages above say what is in a frame; Compare says how good that answer is.  It takes two planes that lie in device memory
+ * -- a class plane and ground truth, the class planes of two arithmetic modes, a label plane and ground-truth instances -- and
+ * returns the integers every segmentation measure is made of: the confusion matrix (pixel accuracy, IoU per class, mIoU), and
+ * per value of either plane its best partner in the other with intersection and union (IoU per object, panoptic quality).
+ * Presence of this group is announced by infur_features() & INFUR_FEATURE_COMPARE (INFUR_ABI_VERSION does not move).
+ *
+ * The inputs are two planes a and b of the same h x w elements, h and w at most 65535, each with its own element size elem_a,
+ * elem_b = 1 (a class plane) or 4 (a label or track plane).  Runs' rules hold for the element sizes, for unknown flag bits, for
+ * an ignore value no 1-byte element can hold and for a NULL plane.
+ *   flags & INFUR_COMPARE_IGNORE_A   pixels with a == ignore_a are not compared
+ *   flags & INFUR_COMPARE_IGNORE_B   pixels with b == ignore_b are not compared (typically a "void" label such as 255 in ground
+ *                                    truth, INFUR_REGION_NONE, INFUR_TRACK_NONE)
+ * rows_a and rows_b are the number of values on each side.  A pixel is IGNORED or COMPARED; a compared pixel with a >= rows_a or
+ * b >= rows_b is OUTSIDE: it is counted and takes part in nothing else.  The rest are INSIDE.
+ * Outputs, each optional (NULL = not wanted, and so are a matrix with rows_a * rows_b == 0 and a row table of 0 rows; nothing
+ * wanted is INFUR_E_INVALID_ARG), none needs initialisation:
+ *   matrix      rows_a x rows_b uint32_t, row-major: matrix[i][j] is the number of inside pixels with a == i and b == j.  Every
+ *               entry is written.  Wanting it with rows_a * rows_b above 2^20 is INFUR_E_INVALID_ARG
+ *   rows_a_out  rows_a rows of INFUR_COMPARE_WORDS uint32_t, one per value i of a: INFUR_COMPARE_PIXELS the inside pixels of
+ *               value i, INFUR_COMPARE_PARTNER the value j of b with the largest intersection, ties to the smallest j,
+ *               INFUR_COMPARE_INTER that intersection, INFUR_COMPARE_UNION PIXELS + the partner's PIXELS - INTER.  IoU is
+ *               INTER / UNION, and the pair is MATCHED iff 2 * INTER > UNION -- the rule of panoptic quality: an IoU above one
+ *               half makes the match unique and mutual.  A value no inside pixel holds reads (0, INFUR_COMPARE_NONE, 0, 0)
+ *   rows_b_out  the mirror image: rows_b rows, the partner a value of a
+ *   counts      INFUR_COMPARE_COUNT_WORDS uint32_t: INFUR_COMPARE_COMPARED, INFUR_COMPARE_EQUAL (inside pixels with a == b),
+ *               INFUR_COMPARE_IGNORED, INFUR_COMPARE_OUTSIDE, INFUR_COMPARE_PAIRS (distinct (i, j) with a non-zero
+ *               intersection), INFUR_COMPARE_MATCHED (matched rows of a, which is the number of matched rows of b),
+ *               INFUR_COMPARE_RUNS (R, below), INFUR_COMPARE_STATUS.  COMPARED + IGNORED == h * w
+ * h * w == 0 writes zeros and NONE rows, and nothing else (STATUS 0).
+ *
+ * Two forms, chosen by the arguments alone.  With rows_a * rows_b <= 4096 the matrix is counted in LDS (the dense form): there is
+ * no table and nothing can overflow.  Everything larger goes through an open-addressing table of (i, j) pairs of pair_slots
+ * slots (the table form; INFUR_COMPARE_TABLE in STATUS): pair_slots is a power of two >= 64, 0 means 2^20, anything else is
+ * INFUR_E_INVALID_ARG in either form.  R is the number of runs of equal inside (i, j) along rows cut every 64 columns, reported in
+ * both forms; it bounds the distinct pairs.  In the table form 2 * R > pair_slots sets INFUR_COMPARE_OVERFLOW in STATUS: every
+ * PARTNER / INTER / UNION then reads (INFUR_COMPARE_NONE, 0, 0) and PAIRS = MATCHED = 0, while PIXELS, the matrix and the other
+ * counts are still exact.  The overflow is visible and is not an error.
+ *
+ * Example: a = [[0,0,1,1],[0,1,1,2]], b = [[0,0,0,1],[0,1,1,1]], rows 3 x 3, nothing ignored: matrix [[3,0,0],[1,3,0],[0,1,0]],
+ * rows_a_out (3,0,3,4) (4,1,3,5) (1,1,1,4), rows_b_out (4,0,3,4) (4,1,3,5) (0,NONE,0,0), counts COMPARED 8, EQUAL 6, IGNORED 0,
+ * OUTSIDE 0, PAIRS 4, MATCHED 2, RUNS 6, STATUS 0.  Pixel accuracy is 6/8, the class IoUs from the diagonal 3/4, 3/5 and 0/1.
+ *
+ * Checks, in this order, each INFUR_E_INVALID_ARG: the context; elem_a, then elem_b (1 or 4); unknown flag bits; ignore_a, then
+ * ignore_b, above 255 on a 1-byte plane; h or w above 65535; pair_slots; nothing wanted; a wanted matrix above 2^20 entries; a
+ * NULL plane with h * w > 0.  No output is touched when a call is rejected.  Everything is an integer, exact, and a function of the
+ * two planes alone: identical bytes from run to run. */
+#define INFUR_COMPARE_NONE 0xFFFFFFFFu
+enum { INFUR_COMPARE_IGNORE_A = 1, INFUR_COMPARE_IGNORE_B = 2 };
+enum { INFUR_COMPARE_PIXELS = 0, INFUR_COMPARE_PARTNER = 1, INFUR_COMPARE_INTER = 2, INFUR_COMPARE_UNION = 3, INFUR_COMPARE_WORDS = 4 };
+enum {
+    INFUR_COMPARE_COMPARED = 0,
+    INFUR_COMPARE_EQUAL = 1,
+    INFUR_COMPARE_IGNORED = 2,
+    INFUR_COMPARE_OUTSIDE = 3,
+    INFUR_COMPARE_PAIRS = 4,
+    INFUR_COMPARE_MATCHED = 5,
+    INFUR_COMPARE_RUNS = 6,
+    INFUR_COMPARE_STATUS = 7,
+    INFUR_COMPARE_COUNT_WORDS = 8
+};
+enum { INFUR_COMPARE_OVERFLOW = 1, INFUR_COMPARE_TABLE = 2 };
+enum { INFUR_FEATURE_COMPARE = 512 };
+
+/* on two given planes, host pointers */
+int32_t infur_compare(infur_ctx* ctx, const void* a, uint32_t elem_a, const void* b, uint32_t elem_b, uint32_t h, uint32_t w,
+                      uint32_t flags, uint32_t ignore_a, uint32_t ignore_b, uint32_t* matrix, uint32_t rows_a, uint32_t rows_b,
+                      uint32_t* rows_a_out, uint32_t* rows_b_out, uint32_t* counts, uint32_t pair_slots);
+/* device pointers throughout; enqueued on the context's stream, never synchronises.  The number of memsets and launches is fixed
+ * by the arguments: the dense form is one memset and four launches, the table form two memsets -- three when the matrix is
+ * wanted -- and five launches; without counts each is one launch fewer; an empty plane is at most two memsets and one launch.
+ * Capturable after one call outside the capture (which allocates the scratch, owned by the context: 12 bytes per row of either
+ * side, and four per matrix entry or twelve per slot; it grows only with a request larger than any before, and a graph captured
+ * around the call is re-captured after that).  This is the call that composes on the device: infur_frame_regions_dev or
+ * infur_frame_tracks_dev, then infur_compare_dev of the label or track plane they left in device memory against a ground-truth
+ * instance plane, with INFUR_REGION_NONE ignored.  The outputs must not overlap the planes or each other. */
+int32_t infur_compare_dev(infur_ctx* ctx, const void* d_a, uint32_t elem_a, const void* d_b, uint32_t elem_b, uint32_t h,
+                          uint32_t w, uint32_t flags, uint32_t ignore_a, uint32_t ignore_b, void* d_matrix, uint32_t rows_a,
+                          uint32_t rows_b, void* d_rows_a_out, void* d_rows_b_out, void* d_counts, uint32_t pair_slots);
+/* The fused frame path with a grade: scale -> model -> Segments decode(out[0]) -> Compare of the class plane (a, one byte per
+ * pixel) against the caller's uint8_t truth plane of ow x oh (b), in one call.  Of the flags only INFUR_COMPARE_IGNORE_B (with
+ * ignore_b) is meaningful, and INFUR_COMPARE_IGNORE_A is INFUR_E_INVALID_ARG.  truth_capacity is in bytes, ow * oh needed; less
+ * is INFUR_E_CAPACITY, checked, like plane_capacity for klass and conf, once a model is loaded.  klass, conf and scaled_bgr are
+ * optional outputs as in infur_frame_segments; at least one of matrix, rows_a_out, rows_b_out and counts must be wanted.  The
+ * calls inherit infur_frame_segments' checks and errors: with no model loaded the Scale stage still runs and the call returns
+ * INFUR_E_MODEL_NOT_LOADED.  They always enqueue eagerly and leave the graphs cached for infur_frame_advance_dev alone.  (The
+ * stream ring, batch and group calls produce RGBA only.) */
+int32_t infur_frame_compare(infur_ctx* ctx, const uint8_t* bgr, uint32_t w, uint32_t h, float factor, uint32_t scale_mode,
+                            uint32_t decode, uint32_t flags, uint32_t ignore_b, const uint8_t* truth, size_t truth_capacity,
+                            uint8_t* klass, uint8_t* conf, size_t plane_capacity, uint32_t* matrix, uint32_t rows_a,
+                            uint32_t rows_b, uint32_t* rows_a_out, uint32_t* rows_b_out, uint32_t* counts, uint32_t pair_slots,
+                            uint8_t* scaled_bgr, uint32_t* ow, uint32_t* oh);
+int32_t infur_frame_compare_dev(infur_ctx* ctx, const void* d_bgr, uint32_t w, uint32_t h, float factor, uint32_t scale_mode,
+                                uint32_t decode, uint32_t flags, uint32_t ignore_b, const void* d_truth, size_t truth_capacity,
+                                void* d_klass, void* d_conf, size_t plane_capacity, void* d_matrix, uint32_t rows_a,
+                                uint32_t rows_b, void* d_rows_a_out, void* d_rows_b_out, void* d_counts, uint32_t pair_slots,
+                                void* d_scaled_bgr, uint32_t* ow, uint32_t* oh);
+
 /* ---- streaming (infur/src/main.rs:27-99,105): bounded queue, copies overlapped with compute ----
  * The reference back-pressures its producer with sync_channel(2) (main.rs:105); a stream
  * here is a ring of `depth` pinned + device slots.  submit() copies the caller's frame into a

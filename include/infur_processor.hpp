@@ -509,6 +509,72 @@ private:
     bool dirty_ = true;
 };
 
+/// What `Compare` produces for `rows_a` x `rows_b` values: `matrix` row-major (pixels with a == i and b == j), `a` and `b` rows of
+/// INFUR_COMPARE_WORDS words per value of either plane ((0, INFUR_COMPARE_NONE, 0, 0): no compared pixel holds the value) and the
+/// INFUR_COMPARE_COUNT_WORDS counts.
+struct CompareOut {
+    uint32_t rows_a = 21, rows_b = 21;
+    bool want_matrix = true;
+    std::vector<uint32_t> matrix, a, b, counts;
+    uint32_t at(uint32_t i, uint32_t j) const { return matrix[(size_t)i * rows_b + j]; }
+    uint32_t count(uint32_t word) const { return counts[word]; }
+    /// row i of a's table is matched: 2 INTER > UNION, the rule of panoptic quality
+    bool matched_a(uint32_t i) const {
+        return 2ull * a[(size_t)i * INFUR_COMPARE_WORDS + INFUR_COMPARE_INTER] > a[(size_t)i * INFUR_COMPARE_WORDS + INFUR_COMPARE_UNION];
+    }
+    /// the share of the pixels that take part on which the planes agree; -1 when there is none
+    double pixel_accuracy() const {
+        const uint32_t n = count(INFUR_COMPARE_COMPARED) - count(INFUR_COMPARE_OUTSIDE);
+        return n ? (double)count(INFUR_COMPARE_EQUAL) / n : -1.0;
+    }
+};
+
+/// The stage that grades a result: the confusion matrix of two planes -- byte planes (class) or u32 planes (labels, tracks), in
+/// any combination -- and per value of either its best partner in the other with intersection and union.  Integer results,
+/// identical from run to run.
+/// Command = which value of either plane is not compared, and the pair table's slots; Input = two planes of one size,
+/// Output = CompareOut.
+class Compare {
+public:
+    struct Cmd {
+        enum Kind { IgnoreA, IgnoreB, IgnoreNone, PairSlots } kind;
+        uint32_t value;
+    };
+    explicit Compare(Context& c) : c_(c) {}
+    Status control(Cmd cmd) {
+        uint32_t flags = flags_, ia = ignore_a_, ib = ignore_b_, slots = pair_slots_;
+        switch (cmd.kind) {
+        case Cmd::IgnoreA: flags |= INFUR_COMPARE_IGNORE_A, ia = cmd.value; break;
+        case Cmd::IgnoreB: flags |= INFUR_COMPARE_IGNORE_B, ib = cmd.value; break;
+        case Cmd::IgnoreNone: flags = ia = ib = 0; break;
+        case Cmd::PairSlots: slots = cmd.value; break;
+        default: return INFUR_E_INVALID_ARG;
+        }
+        dirty_ = dirty_ || flags != flags_ || ia != ignore_a_ || ib != ignore_b_ || slots != pair_slots_;
+        flags_ = flags, ignore_a_ = ia, ignore_b_ = ib, pair_slots_ = slots;
+        return INFUR_OK;
+    }
+    bool is_dirty() const { return dirty_; }
+    template <class A, class B>
+    Status advance(const std::vector<A>& a, const std::vector<B>& b, uint32_t height, uint32_t width, CompareOut& out) {
+        static_assert((sizeof(A) == 1 || sizeof(A) == 4) && (sizeof(B) == 1 || sizeof(B) == 4), "planes of uint8_t or uint32_t");
+        dirty_ = false;
+        if (a.size() != (size_t)width * height || b.size() != a.size()) return INFUR_E_SHAPE;
+        out.matrix.assign(out.want_matrix ? (size_t)out.rows_a * out.rows_b : 0, 0);
+        out.a.assign((size_t)out.rows_a * INFUR_COMPARE_WORDS, 0);
+        out.b.assign((size_t)out.rows_b * INFUR_COMPARE_WORDS, 0);
+        out.counts.assign(INFUR_COMPARE_COUNT_WORDS, 0);
+        return infur_compare(c_.get(), a.data(), sizeof(A), b.data(), sizeof(B), height, width, flags_, ignore_a_, ignore_b_,
+                             out.matrix.empty() ? nullptr : out.matrix.data(), out.rows_a, out.rows_b, out.a.empty() ? nullptr : out.a.data(),
+                             out.b.empty() ? nullptr : out.b.data(), out.counts.data(), pair_slots_);
+    }
+
+private:
+    Context& c_;
+    uint32_t flags_ = 0, ignore_a_ = 0, ignore_b_ = 0, pair_slots_ = 0;
+    bool dirty_ = true;
+};
+
 /// What `Outlines` produces: `loops` holds min(n_loops, loops_rows) records of INFUR_LOOP_WORDS words, `vertices` the first
 /// min(n_vertices, vertex_rows) vertex ids Y*(width+1) + X, loops back to back; the three counts are complete whatever the rows
 /// are (n_loops == 0 with n_edges > 0: the edges exceeded the capacity).

@@ -84,6 +84,14 @@ ANCHORS_SKIP = 1
 ANCHOR_PIXEL, ANCHOR_DIST2, ANCHOR_WORDS = 0, 1, 2
 ANCHOR_NONE = 0xFFFFFFFF
 FEATURE_ANCHORS = 256
+# Compare (infur_compare / infur_frame_compare): the flags, the words of a row and of the counts, the status bits, the feature bit
+COMPARE_IGNORE_A, COMPARE_IGNORE_B = 1, 2
+COMPARE_PIXELS, COMPARE_PARTNER, COMPARE_INTER, COMPARE_UNION, COMPARE_WORDS = 0, 1, 2, 3, 4
+(COMPARE_COMPARED, COMPARE_EQUAL, COMPARE_IGNORED, COMPARE_OUTSIDE, COMPARE_PAIRS, COMPARE_MATCHED, COMPARE_RUNS, COMPARE_STATUS,
+ COMPARE_COUNT_WORDS) = 0, 1, 2, 3, 4, 5, 6, 7, 8
+COMPARE_OVERFLOW, COMPARE_TABLE = 1, 2
+COMPARE_NONE = 0xFFFFFFFF
+FEATURE_COMPARE = 512
 
 
 class Options(C.Structure):
@@ -230,6 +238,12 @@ SIGNATURES = {
                                         _u32p, _u32p, _vp, _sz, _vp]),
     "infur_frame_anchors_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp,
                                             _vp, _u32p, _u32p, _vp, _sz, _vp]),
+    "infur_compare": (C.c_int32, [_vp, _vp, _u32, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _u32]),
+    "infur_compare_dev": (C.c_int32, [_vp, _vp, _u32, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _u32]),
+    "infur_frame_compare": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _vp, _sz, _vp, _vp, _sz, _vp, _u32, _u32, _vp, _vp, _vp,
+                                        _u32, _vp, _u32p, _u32p]),
+    "infur_frame_compare_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _vp, _sz, _vp, _vp, _sz, _vp, _u32, _u32, _vp, _vp,
+                                            _vp, _u32, _vp, _u32p, _u32p]),
     "infur_stream_create": (C.c_int32, [_vp, _u32, C.POINTER(_vp)]),
     "infur_stream_destroy": (None, [_vp]),
     "infur_stream_add_lane": (C.c_int32, [_vp, _vp]),

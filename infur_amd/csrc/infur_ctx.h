@@ -188,6 +188,9 @@ struct infur_ctx {
     // Anchors (infur_anchors.cpp): the u16 row-distance plane and the u64 key row per value, the label plane the frame calls let
     // Regions write when the caller does not want it, and the host-pointer calls' staging.  Private like the above.
     infur::Buf st_anch, st_anch_plane, st_anch_io;
+    // Compare (infur_compare.cpp): the accumulators, per-value sums and maxima and the matrix or the pair table, the class plane of
+    // the frame calls when the caller does not want it, and the host-pointer calls' staging.  Private like the above.
+    infur::Buf st_cmp, st_cmp_plane, st_cmp_io;
     // Tracks (infur_tracks.cpp): the live trackers of this context; infur_ctx_destroy releases their device memory and orphans them
     std::vector<infur_tracker*> trackers;
 

@@ -369,6 +369,27 @@ size_t anchors_scratch_bytes(size_t npix, unsigned rows);
 hipError_t launch_anchors(const void* plane, int elem_bytes, unsigned H, unsigned W, int skip, unsigned skip_value, void* scratch, unsigned* dist2,
                           unsigned* anchors, unsigned rows, hipStream_t s);
 
+// Compare (compare.hip): two H x W planes (both sides at most 65535) of 1- or 4-byte elements against each other.  A pixel whose
+// a equals ignore_a (ign_a set) or whose b equals ignore_b (ign_b set) is ignored; a compared pixel with a >= rows_a or
+// b >= rows_b is outside; the rest are inside.  matrix[rows_a x rows_b] u32 counts the inside pixels per (a, b); rows_a_out and
+// rows_b_out hold kCompareWords u32 per value (PIXELS, PARTNER, INTER, UNION), (0, 0xFFFFFFFF, 0, 0) where no inside pixel holds
+// it; counts[kCompareCountWords] = {COMPARED, EQUAL, IGNORED, OUTSIDE, PAIRS, MATCHED, RUNS, STATUS} (each optional; device
+// memory; everything wanted is written in full).  compare_dense(rows_a, rows_b) says which form runs: the matrix in LDS, or an
+// open-addressing pair table of pair_slots slots (a power of two >= 64; kCmpOverflow in STATUS when 2 * RUNS exceeds it: then
+// no partner is reported and PIXELS, the matrix and the other counts are still exact).  scratch: compare_scratch_bytes(..)
+// bytes the launches own for the call.  Stream-ordered; dense: one memset and four launches, table: two memsets (three with a
+// matrix) and five launches, one launch fewer without counts; no workgroup waits for another.  H * W == 0 writes zeros and
+// NONE rows and needs no scratch.
+constexpr int kCompareWords = 4;
+constexpr int kCompareCountWords = 8;
+constexpr unsigned kCmpDenseMax = 4096;
+constexpr unsigned kCmpOverflow = 1u, kCmpTable = 2u;
+bool compare_dense(unsigned rows_a, unsigned rows_b);
+size_t compare_scratch_bytes(unsigned rows_a, unsigned rows_b, unsigned pair_slots);
+hipError_t launch_compare(const void* a, int elem_a, const void* b, int elem_b, unsigned H, unsigned W, int ign_a, unsigned ignore_a, int ign_b,
+                          unsigned ignore_b, unsigned rows_a, unsigned rows_b, void* scratch, unsigned pair_slots, unsigned* matrix, unsigned* rows_a_out,
+                          unsigned* rows_b_out, unsigned* counts, hipStream_t s);
+
 // Outlines (outlines.hip): the boundaries of the value-regions of an H x W plane of 1- or 4-byte elements as closed loops --
 // loops_rows x kLoopWords u32 records (OFFSET, COUNT, VALUE, START), vertex_rows u32 vertex ids Y * (W + 1) + X, and counts[3] =
 // {n_loops, n_vertices, n_edges} (each optional; device memory).  skip: pixels of skip_value belong to no region; conn8: the

@@ -991,6 +991,168 @@ class AnchorsFrame(NamedTuple):
     anchors: Optional[np.ndarray]
 
 
+@dataclass
+class CompareCmd:
+    """``Compare``'s command: ``Ignore(a, b)`` takes the pixels whose ``a`` (``b``) plane holds that value out of the comparison
+    (None: every value is compared); ``pair_slots`` sizes the pair table of the table form (0: the library's 2^20)."""
+
+    ignore_a: Optional[int] = None
+    ignore_b: Optional[int] = None
+    pair_slots: int = 0
+
+    @staticmethod
+    def Ignore(a: Optional[int] = None, b: Optional[int] = None, pair_slots: int = 0) -> "CompareCmd":
+        return CompareCmd(ignore_a=a, ignore_b=b, pair_slots=pair_slots)
+
+
+class CompareOut:
+    """``Compare``'s ``&mut Output``: what to produce (``rows_a``, ``rows_b`` values on each side, ``want_matrix``,
+    ``want_rows``, ``want_counts``) and, after ``advance``, the results -- ``matrix`` [rows_a, rows_b] u32, ``a`` [rows_a, 4] and
+    ``b`` [rows_b, 4] u32 (columns ``_lib.COMPARE_PIXELS`` .. ``_lib.COMPARE_UNION``; a value no compared pixel holds reads
+    ``(0, _lib.COMPARE_NONE, 0, 0)``), ``counts`` [8] u32 (``_lib.COMPARE_COMPARED`` .. ``_lib.COMPARE_STATUS``); None for what
+    was not wanted."""
+
+    def __init__(self, rows_a: int = 21, rows_b: int = 21, want_matrix: bool = True, want_rows: bool = True, want_counts: bool = True):
+        self.rows_a, self.rows_b = rows_a, rows_b
+        self.want_matrix, self.want_rows, self.want_counts = want_matrix, want_rows, want_counts
+        self.matrix = self.a = self.b = self.counts = None
+
+
+def _compare_alloc(rows_a: int, rows_b: int, want_matrix: bool, want_rows: bool, want_counts: bool) -> tuple:
+    """-> (matrix, rows of a, rows of b, counts): the arrays a compare call fills, None for what is not wanted or has no rows"""
+    return (np.empty((rows_a, rows_b), np.uint32) if want_matrix and rows_a * rows_b else None,
+            np.empty((rows_a, _lib.COMPARE_WORDS), np.uint32) if want_rows and rows_a else None,
+            np.empty((rows_b, _lib.COMPARE_WORDS), np.uint32) if want_rows and rows_b else None,
+            np.empty(_lib.COMPARE_COUNT_WORDS, np.uint32) if want_counts else None)
+
+
+class Compare(Processor):
+    """The stage that grades a result: the confusion matrix of two planes -- class planes (u8), label or track planes (u32), in
+    any combination -- and per value of either plane its best partner in the other with intersection and union.
+
+    Command = ``CompareCmd``.  Input = a pair of planes (a, b) of one [H, W]; Output = ``CompareOut``.  Integers throughout,
+    identical from run to run; ``confusion_summary`` and ``panoptic_summary`` turn them into the usual measures.
+    """
+
+    def __init__(self, ctx: Context, ignore_a: Optional[int] = None, ignore_b: Optional[int] = None, pair_slots: int = 0):
+        self.ctx = ctx
+        self.ignore_a, self.ignore_b, self.pair_slots = ignore_a, ignore_b, pair_slots
+        self.dirty = True
+
+    def control(self, cmd: CompareCmd) -> "Compare":
+        for v in (cmd.ignore_a, cmd.ignore_b):
+            if v is not None and not 0 <= v <= 0xFFFFFFFF:
+                raise InfurError(_lib.E_INVALID_ARG, f"ignore value {v}: a u32")
+        if not 0 <= cmd.pair_slots <= 0xFFFFFFFF:
+            raise InfurError(_lib.E_INVALID_ARG, f"pair_slots {cmd.pair_slots}: a u32")
+        new = (cmd.ignore_a, cmd.ignore_b, cmd.pair_slots)
+        self.dirty = self.dirty or new != (self.ignore_a, self.ignore_b, self.pair_slots)
+        self.ignore_a, self.ignore_b, self.pair_slots = new
+        return self
+
+    def is_dirty(self) -> bool:
+        return self.dirty
+
+    def flags(self) -> int:
+        return (_lib.COMPARE_IGNORE_A if self.ignore_a is not None else 0) | (_lib.COMPARE_IGNORE_B if self.ignore_b is not None else 0)
+
+    def advance(self, inp, out: CompareOut) -> None:
+        self.dirty = False
+        a, b = inp
+        for p in (a, b):
+            if p.ndim != 2 or p.dtype.itemsize not in (1, 4) or p.dtype.kind not in "ui":
+                raise InfurError(_lib.E_SHAPE, f"expected an [H,W] plane of 1- or 4-byte integers, got {p.shape} {p.dtype}")
+        if a.shape != b.shape:
+            raise InfurError(_lib.E_SHAPE, f"two planes of one size, got {a.shape} and {b.shape}")
+        a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+        h, w = a.shape
+        rows_a, rows_b = max(0, int(out.rows_a)), max(0, int(out.rows_b))
+        matrix, ra, rb, counts = _compare_alloc(rows_a, rows_b, out.want_matrix, out.want_rows, out.want_counts)
+        ptr = lambda p: p.ctypes.data if p.size else None  # noqa: E731
+        self.ctx.check(self.ctx.L.infur_compare(self.ctx.h, ptr(a), a.dtype.itemsize, ptr(b), b.dtype.itemsize, h, w, self.flags(), self.ignore_a or 0,
+                                                self.ignore_b or 0, _ptr(matrix), rows_a, rows_b, _ptr(ra), _ptr(rb), _ptr(counts), self.pair_slots))
+        out.matrix, out.a, out.b, out.counts = matrix, ra, rb, counts
+
+
+class CompareFrame(NamedTuple):
+    """``FramePath.advance_compare``: the class and confidence planes [oh, ow] u8 and the scaled frame (None where not wanted),
+    then ``CompareOut``'s four results of the class plane (a) against the caller's truth plane (b)"""
+
+    klass: Optional[np.ndarray]
+    conf: Optional[np.ndarray]
+    scaled: Optional[np.ndarray]
+    matrix: Optional[np.ndarray]
+    a: Optional[np.ndarray]
+    b: Optional[np.ndarray]
+    counts: Optional[np.ndarray]
+
+
+def confusion_summary(matrix: np.ndarray, names=None) -> dict:
+    """The usual measures of a confusion matrix (``matrix[i][j]``: pixels the first plane calls i and the second j; a matrix that
+    is not square is read as padded with zeros): ``pixel_accuracy`` (None for an empty matrix), ``classes`` -- one dict per class
+    with ``klass``, ``name``, ``intersection``, ``union`` and ``iou`` (None where the union is 0) --, ``miou`` over the classes
+    with a non-zero union (None when there is none) and ``fwiou``, the IoUs weighted by the second plane's class frequencies.
+    The host adds the matrices of several frames before it asks.  ``names`` as in ``class_summary``."""
+    if names is None:
+        L = _lib.load()
+        names = lambda k: voc_class_name(L, k)  # noqa: E731
+    elif not callable(names):
+        table = list(names)
+        names = lambda k: table[k] if k < len(table) else None  # noqa: E731
+    m = np.asarray(matrix, np.uint64)
+    k = max(m.shape) if m.size else 0
+    sq = np.zeros((k, k), np.uint64)
+    if m.size:
+        sq[:m.shape[0], :m.shape[1]] = m
+    total = int(sq.sum())
+    inter = [int(v) for v in np.diag(sq)]
+    row, col = [int(v) for v in sq.sum(axis=1)], [int(v) for v in sq.sum(axis=0)]
+    classes, ious, fw = [], [], 0.0
+    for c in range(k):
+        union = row[c] + col[c] - inter[c]
+        iou = inter[c] / union if union else None
+        classes.append({"klass": c, "name": names(c) or f"class{c}", "intersection": inter[c], "union": union, "iou": iou})
+        if union:
+            ious.append(iou)
+            fw += col[c] * iou
+    return {"pixel_accuracy": sum(inter) / total if total else None, "classes": classes, "miou": sum(ious) / len(ious) if ious else None,
+            "fwiou": fw / total if total else None}
+
+
+def panoptic_summary(rows_a: np.ndarray, rows_b: np.ndarray, class_of_a, class_of_b) -> dict:
+    """Panoptic quality from ``Compare``'s two row tables of a predicted label plane (a) against a ground-truth one (b).
+    ``class_of_a[i]`` and ``class_of_b[j]`` are the classes of the segments (Regions' table column ``_lib.REGION_CLASS``).  A
+    segment is one with PIXELS > 0; a pair is a true positive iff it is matched (2 INTER > UNION, which makes it unique and
+    mutual) and the classes agree; every other segment of a is a false positive of its class, every other segment of b a false
+    negative of its.  -> ``classes``: {class: {tp, fp, fn, sum_iou, pq, sq, rq}} for the classes that occur, and ``pq``, ``sq``,
+    ``rq`` averaged over them (None when there is none)."""
+    ra = np.asarray(rows_a, np.uint32).reshape(-1, _lib.COMPARE_WORDS)
+    rb = np.asarray(rows_b, np.uint32).reshape(-1, _lib.COMPARE_WORDS)
+    acc: dict = {}
+    slot = lambda c: acc.setdefault(int(c), {"tp": 0, "fp": 0, "fn": 0, "sum_iou": 0.0})  # noqa: E731
+    taken = set()
+    for i, (pix, partner, inter, union) in enumerate(ra.tolist()):
+        if not pix:
+            continue
+        if 2 * inter > union and int(class_of_a[i]) == int(class_of_b[partner]):
+            s = slot(class_of_a[i])
+            s["tp"] += 1
+            s["sum_iou"] += inter / union
+            taken.add(partner)
+        else:
+            slot(class_of_a[i])["fp"] += 1
+    for j, (pix, _, _, _) in enumerate(rb.tolist()):
+        if pix and j not in taken:
+            slot(class_of_b[j])["fn"] += 1
+    for s in acc.values():
+        den = s["tp"] + 0.5 * s["fp"] + 0.5 * s["fn"]
+        s["pq"] = s["sum_iou"] / den
+        s["sq"] = s["sum_iou"] / s["tp"] if s["tp"] else 0.0
+        s["rq"] = s["tp"] / den
+    mean = lambda f: sum(s[f] for s in acc.values()) / len(acc) if acc else None  # noqa: E731
+    return {"classes": dict(sorted(acc.items())), "pq": mean("pq"), "sq": mean("sq"), "rq": mean("rq")}
+
+
 def runs_decode(runs: np.ndarray, n: int, h: int, w: int, fill: int = 0, dtype=None) -> np.ndarray:
     """The dense [h, w] plane of the first ``min(n, len(runs))`` records; pixels no record covers (skipped or truncated runs) read
     ``fill``.  ``dtype``: uint8 when every value and ``fill`` fit a byte, else uint32."""
@@ -1448,6 +1610,30 @@ class FramePath:
         k = min(n.value, rows)
         return AnchorsFrame(klass, conf, labels, table[:k] if table is not None else None, n.value, scaled, dist2,
                             anchors[:k] if anchors is not None else None)
+
+    def advance_compare(self, img: np.ndarray, truth: np.ndarray, factor: float = 1.0, decode: int = _lib.DECODE_RAW,
+                        ignore: Optional[int] = None, rows_a: Optional[int] = None, rows_b: Optional[int] = None, pair_slots: int = 0,
+                        want_matrix: bool = True, want_rows: bool = True, want_counts: bool = True, want_klass: bool = False,
+                        want_conf: bool = False, want_scaled: bool = False) -> CompareFrame:
+        """The fused path with a grade, scale -> model -> Segments decode -> Compare of the class plane against ``truth`` ([oh, ow]
+        u8; pixels of ``ignore`` are not compared), in one call -> ``CompareFrame``; ``rows_a`` and ``rows_b`` default to the
+        model's class count.  Every result field is None when no model is loaded (``scaled`` is still produced)."""
+        img, w, h, f, ow, oh = self._front(img, factor)
+        npix = oh.value * ow.value
+        truth = np.ascontiguousarray(truth)
+        if truth.dtype != np.uint8 or truth.shape != (oh.value, ow.value):
+            raise InfurError(_lib.E_SHAPE, f"expected a [{oh.value},{ow.value}] uint8 truth plane, got {truth.shape} {truth.dtype}")
+        k = self._num_classes()
+        rows_a, rows_b = k if rows_a is None else max(0, int(rows_a)), k if rows_b is None else max(0, int(rows_b))
+        klass, conf = self._plane(ow, oh, want_klass), self._plane(ow, oh, want_conf)
+        scaled = self._plane(ow, oh, want_scaled, channels=3)
+        matrix, ra, rb, counts = _compare_alloc(rows_a, rows_b, want_matrix, want_rows, want_counts)
+        rc = self.ctx.L.infur_frame_compare(self.ctx.h, img.ctypes.data, w, h, f, self.scale_mode, decode, _lib.COMPARE_IGNORE_B if ignore is not None else 0,
+                                            ignore or 0, _ptr(truth), truth.size, _ptr(klass), _ptr(conf), npix, _ptr(matrix), rows_a, rows_b, _ptr(ra),
+                                            _ptr(rb), _ptr(counts), pair_slots, _ptr(scaled), C.byref(ow), C.byref(oh))
+        if not self._loaded(rc):
+            return CompareFrame(None, None, scaled, None, None, None, None)
+        return CompareFrame(klass, conf, scaled, matrix, ra, rb, counts)
 
     def advance_tracks(self, tracks: "Tracks", img: np.ndarray, factor: float = 1.0, decode: int = _lib.DECODE_RAW,
                        connectivity: int = _lib.CONNECT_8, min_pixels: int = 0, flags: int = 0, table_rows: int = 1024,

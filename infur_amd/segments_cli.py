@@ -53,6 +53,11 @@ Regions left it on the device (``infur_anchors_dev``, pixels of no region skippe
 [x, y], its most interior pixel -- on the object, which its centroid need not be -- and ``"radius"``, the distance from there to the
 nearest pixel of anything else or to the frame.  ``--dist-out FILE`` (needs ``--anchors``) receives the u32 planes of squared
 distances back to back (0: a pixel of no region).
+
+``--truth FILE`` grades every frame: FILE holds one u8 ground-truth class plane of the scaled frame's size per frame, back to back;
+the class plane is compared with it (``infur_compare``; ``--truth-ignore V`` leaves the pixels whose truth is V, a "void" label,
+out), every line gains ``"pixel_accuracy"`` and ``"miou"``, and one last line holds the totals of the confusion matrices added up
+over the frames: ``"frames"``, ``"pixel_accuracy"``, ``"miou"``, ``"fwiou"``, the per-class IoUs and the matrix itself.
 """
 from __future__ import annotations
 
@@ -100,7 +105,13 @@ def main(argv=None) -> int:
                     help="simplify every shared border once, so that neighbouring polygons still fit (needs --outlines-tolerance)")
     ap.add_argument("--anchors", action="store_true", help="add every region's most interior pixel and its radius (needs --regions or --tracks)")
     ap.add_argument("--dist-out", default="", help="raw u32 planes of squared distances, four bytes per pixel (needs --anchors)")
+    ap.add_argument("--truth", default="", help="raw u8 ground-truth class planes, one per frame: adds pixel_accuracy and miou, and a line of totals")
+    ap.add_argument("--truth-ignore", type=int, default=None, metavar="V", help="truth pixels of this value are not compared (needs --truth)")
     a = ap.parse_args(argv)
+    if a.truth_ignore is not None and not a.truth:
+        ap.error("--truth-ignore needs --truth")
+    if a.truth_ignore is not None and not 0 <= a.truth_ignore <= 255:
+        ap.error("--truth-ignore: a value of the truth plane, a byte")
     if a.outlines_shared and a.outlines_tolerance is None:
         ap.error("--outlines-shared needs --outlines-tolerance")
     if a.tracks_out and not a.tracks:
@@ -136,7 +147,7 @@ def main(argv=None) -> int:
 
     from . import _lib
     from .app import RawVideoSource, VideoProcError
-    from .processors import (Context, Coverage, CoverageOut, FramePath, Model, ModelCmd, Outlines, OutlinesOut, Runs, RunsOut, SegmentsFrame, Simplify, SimplifyOut,
+    from .processors import (Compare, CompareOut, confusion_summary, Context, Coverage, CoverageOut, FramePath, Model, ModelCmd, Outlines, OutlinesOut, Runs, RunsOut, SegmentsFrame, Simplify, SimplifyOut,
                              class_summary, region_summary, tolerance_to_tol16, track_summary)
 
     tol16 = tolerance_to_tol16(a.outlines_tolerance) if a.outlines_tolerance is not None else None
@@ -165,6 +176,10 @@ def main(argv=None) -> int:
     fruns = open(a.runs_out, "wb") if a.runs_out else None
     foutl = open(a.outlines_out, "wb") if a.outlines_out else None
     fdist = open(a.dist_out, "wb") if a.dist_out else None
+    ftruth = open(a.truth, "rb") if a.truth else None
+    if ftruth is not None:
+        classes = model.get_info().num_classes
+        grader, total = Compare(ctx, ignore_b=a.truth_ignore), np.zeros((classes, classes), np.uint64)
     rpath = None
     if a.regions:
         oh, ow = _out_dims(ctx, a.width, a.height, a.scale)
@@ -182,7 +197,7 @@ def main(argv=None) -> int:
                 break
             raise
         if rpath is not None:
-            s, labels, table, nreg = rpath.advance(img, decode, a.connectivity, a.min_pixels, flags, flab is not None, fconf is not None,
+            s, labels, table, nreg = rpath.advance(img, decode, a.connectivity, a.min_pixels, flags, flab is not None or ftruth is not None, fconf is not None,
                                                    freg is not None, keep_labels=(fruns is not None and a.runs_plane == "labels") or foutl is not None or a.anchors)
             if a.tracks:
                 ttab, tplane, tsum = rpath.track(max(0, a.min_overlap), ftrk is not None, keep_plane=fruns is not None and a.runs_plane == "tracks")
@@ -192,18 +207,18 @@ def main(argv=None) -> int:
                 outl = rpath.outlines(a.outlines_skip, a.connectivity, tol16, a.outlines_shared)
             if a.anchors:
                 anch, dist2 = rpath.anchors(fdist is not None)
-        elif foutl is not None and fruns is None and flab is None and fconf is None:  # polygons, counts and captions: no dense plane
+        elif foutl is not None and fruns is None and flab is None and fconf is None and ftruth is None:  # polygons, counts and captions: no dense plane
             if tol16 is None:
                 r = fp.advance_outlines(img, a.scale, decode, skip=a.outlines_skip, connectivity=a.connectivity, loops_rows=1 << 32, vertex_rows=1 << 32)
             else:
                 fused = fp.advance_coverage if a.outlines_shared else fp.advance_polygons
                 r = fused(img, a.scale, decode, tol16, skip=a.outlines_skip, connectivity=a.connectivity, loops_rows=1 << 32, vertex_rows=1 << 32)
             s, outl = SegmentsFrame(None, None, r.stats, None, None), (np.array(r.counts[:3], np.uint32), r.loops, r.vertices)
-        elif fruns is not None and flab is None and fconf is None and foutl is None:  # records, count and captions: no dense plane comes back
+        elif fruns is not None and flab is None and fconf is None and foutl is None and ftruth is None:  # records, count and captions: no dense plane comes back
             r = fp.advance_runs(img, a.scale, decode, skip=a.runs_skip, runs_rows=1 << 32, want_row_start=False)
             s, runs, nruns = SegmentsFrame(None, None, r.stats, None, None), r.runs, r.n
         else:
-            s = fp.advance_segments(img, a.scale, decode, want_klass=flab is not None or fruns is not None or foutl is not None, want_conf=fconf is not None)
+            s = fp.advance_segments(img, a.scale, decode, want_klass=flab is not None or fruns is not None or foutl is not None or ftruth is not None, want_conf=fconf is not None)
             if foutl is not None:  # the class plane is on the host anyway
                 oo = OutlinesOut(loops_rows=1 << 32, vertex_rows=1 << 32)
                 Outlines(ctx, skip=a.outlines_skip, connectivity=a.connectivity).advance(s.klass, oo)
@@ -225,6 +240,15 @@ def main(argv=None) -> int:
         if fconf is not None:
             fconf.write(memoryview(s.conf).cast("B"))
         rec = {"frame": fid, "width": ow, "height": oh, "classes": class_summary(s.stats, ow, oh)}
+        if ftruth is not None:  # the class plane is on the host anyway
+            truth = np.frombuffer(ftruth.read(ow * oh), np.uint8)
+            if truth.size != ow * oh:
+                raise SystemExit(f"--truth: {a.truth} ends inside frame {fid} ({truth.size} of {ow * oh} bytes)")
+            graded = CompareOut(rows_a=classes, rows_b=classes, want_rows=False, want_counts=False)
+            grader.advance((s.klass, truth.reshape(oh, ow)), graded)
+            total += graded.matrix
+            grade = confusion_summary(graded.matrix)
+            rec["pixel_accuracy"], rec["miou"] = grade["pixel_accuracy"], grade["miou"]
         if rpath is not None:
             rec["n_regions"] = nreg
             rec["regions"] = region_summary(table, nreg, ow, oh, anchors=anch) if a.anchors else region_summary(table, nreg, ow, oh)
@@ -256,6 +280,12 @@ def main(argv=None) -> int:
                 foutl.write(memoryview(np.ascontiguousarray(part)).cast("B"))
         fst.write(json.dumps(rec) + "\n")
         n += 1
+    if ftruth is not None:
+        grade = confusion_summary(total)
+        fst.write(json.dumps({"frames": n, "pixel_accuracy": grade["pixel_accuracy"], "miou": grade["miou"], "fwiou": grade["fwiou"],
+                              "classes": [{"klass": c["klass"], "name": c["name"], "iou": c["iou"]} for c in grade["classes"] if c["union"]],
+                              "matrix": total.tolist()}) + "\n")
+        ftruth.close()
     for f in (flab, fconf, freg, ftrk, fruns, foutl, fdist, fst):
         if f is not None:
             f.flush()

@@ -201,6 +201,28 @@ pub const INFUR_ANCHOR_WORDS: u32 = 2;
 pub const INFUR_ANCHOR_NONE: u32 = 0xFFFF_FFFF;
 /// bit of `infur_features()`: the Anchors calls below exist
 pub const INFUR_FEATURE_ANCHORS: u32 = 256;
+/// Compare: the flags, the words of a row (`INFUR_COMPARE_WORDS` u32 each) and of the counts, the status bits, "no partner"
+pub const INFUR_COMPARE_IGNORE_A: u32 = 1;
+pub const INFUR_COMPARE_IGNORE_B: u32 = 2;
+pub const INFUR_COMPARE_PIXELS: u32 = 0;
+pub const INFUR_COMPARE_PARTNER: u32 = 1;
+pub const INFUR_COMPARE_INTER: u32 = 2;
+pub const INFUR_COMPARE_UNION: u32 = 3;
+pub const INFUR_COMPARE_WORDS: u32 = 4;
+pub const INFUR_COMPARE_COMPARED: u32 = 0;
+pub const INFUR_COMPARE_EQUAL: u32 = 1;
+pub const INFUR_COMPARE_IGNORED: u32 = 2;
+pub const INFUR_COMPARE_OUTSIDE: u32 = 3;
+pub const INFUR_COMPARE_PAIRS: u32 = 4;
+pub const INFUR_COMPARE_MATCHED: u32 = 5;
+pub const INFUR_COMPARE_RUNS: u32 = 6;
+pub const INFUR_COMPARE_STATUS: u32 = 7;
+pub const INFUR_COMPARE_COUNT_WORDS: u32 = 8;
+pub const INFUR_COMPARE_OVERFLOW: u32 = 1;
+pub const INFUR_COMPARE_TABLE: u32 = 2;
+pub const INFUR_COMPARE_NONE: u32 = 0xFFFF_FFFF;
+/// bit of `infur_features()`: the Compare calls below exist
+pub const INFUR_FEATURE_COMPARE: u32 = 512;
 
 extern "C" {
     pub fn infur_abi_version() -> u32;
@@ -450,4 +472,21 @@ extern "C" {
                                    plane_capacity: usize, d_labels: *mut c_void, labels_capacity: usize, d_table: *mut c_void,
                                    table_rows: u32, d_n_regions: *mut c_void, d_scaled_bgr: *mut c_void, ow: *mut u32, oh: *mut u32,
                                    d_dist2: *mut c_void, dist2_capacity: usize, d_anchors: *mut c_void) -> i32;
+    // Compare: the confusion matrix of two byte or u32 planes and the best partner per value of either
+    pub fn infur_compare(c: *mut infur_ctx, a: *const c_void, elem_a: u32, b: *const c_void, elem_b: u32, h: u32, w: u32, flags: u32,
+                         ignore_a: u32, ignore_b: u32, matrix: *mut u32, rows_a: u32, rows_b: u32, rows_a_out: *mut u32,
+                         rows_b_out: *mut u32, counts: *mut u32, pair_slots: u32) -> i32;
+    pub fn infur_compare_dev(c: *mut infur_ctx, d_a: *const c_void, elem_a: u32, d_b: *const c_void, elem_b: u32, h: u32, w: u32,
+                             flags: u32, ignore_a: u32, ignore_b: u32, d_matrix: *mut c_void, rows_a: u32, rows_b: u32,
+                             d_rows_a_out: *mut c_void, d_rows_b_out: *mut c_void, d_counts: *mut c_void, pair_slots: u32) -> i32;
+    pub fn infur_frame_compare(c: *mut infur_ctx, bgr: *const u8, w: u32, h: u32, factor: f32, scale_mode: u32, decode: u32, flags: u32,
+                               ignore_b: u32, truth: *const u8, truth_capacity: usize, klass: *mut u8, conf: *mut u8,
+                               plane_capacity: usize, matrix: *mut u32, rows_a: u32, rows_b: u32, rows_a_out: *mut u32,
+                               rows_b_out: *mut u32, counts: *mut u32, pair_slots: u32, scaled_bgr: *mut u8, ow: *mut u32,
+                               oh: *mut u32) -> i32;
+    pub fn infur_frame_compare_dev(c: *mut infur_ctx, d_bgr: *const c_void, w: u32, h: u32, factor: f32, scale_mode: u32, decode: u32,
+                                   flags: u32, ignore_b: u32, d_truth: *const c_void, truth_capacity: usize, d_klass: *mut c_void,
+                                   d_conf: *mut c_void, plane_capacity: usize, d_matrix: *mut c_void, rows_a: u32, rows_b: u32,
+                                   d_rows_a_out: *mut c_void, d_rows_b_out: *mut c_void, d_counts: *mut c_void, pair_slots: u32,
+                                   d_scaled_bgr: *mut c_void, ow: *mut u32, oh: *mut u32) -> i32;
 }

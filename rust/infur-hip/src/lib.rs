@@ -696,6 +696,88 @@ impl Processor for HipAnchors {
     }
 }
 
+// ---------------------------------------------------------------- Compare (confusion matrix, best partner per value)
+/// What `HipCompare` produces for `rows_a` x `rows_b` values: `matrix` row-major (`matrix[i * rows_b + j]`: the pixels with a == i
+/// and b == j), `a` and `b` rows of `INFUR_COMPARE_WORDS` words (PIXELS, PARTNER, INTER, UNION) per value of either plane --
+/// `(0, INFUR_COMPARE_NONE, 0, 0)`: no compared pixel holds the value -- and the `INFUR_COMPARE_COUNT_WORDS` counts.
+pub struct Compared { pub rows_a: usize, pub rows_b: usize, pub want_matrix: bool, pub matrix: Vec<u32>, pub a: Vec<u32>, pub b: Vec<u32>,
+                      pub counts: [u32; sys::INFUR_COMPARE_COUNT_WORDS as usize] }
+impl Default for Compared {
+    fn default() -> Self {
+        Self { rows_a: 21, rows_b: 21, want_matrix: true, matrix: Vec::new(), a: Vec::new(), b: Vec::new(),
+               counts: [0; sys::INFUR_COMPARE_COUNT_WORDS as usize] }
+    }
+}
+impl Compared {
+    pub fn count(&self, word: u32) -> u32 { self.counts[word as usize] }
+    /// the share of compared pixels on which the planes agree
+    pub fn pixel_accuracy(&self) -> Option<f64> {
+        let n = self.count(sys::INFUR_COMPARE_COMPARED) - self.count(sys::INFUR_COMPARE_OUTSIDE);
+        if n == 0 { None } else { Some(self.count(sys::INFUR_COMPARE_EQUAL) as f64 / n as f64) }
+    }
+    /// row `i` of a's table is matched: 2 INTER > UNION, the rule of panoptic quality
+    pub fn matched_a(&self, i: usize) -> bool {
+        let r = &self.a[i * sys::INFUR_COMPARE_WORDS as usize..];
+        2 * r[sys::INFUR_COMPARE_INTER as usize] as u64 > r[sys::INFUR_COMPARE_UNION as usize] as u64
+    }
+}
+pub enum CompareCmd { Ignore { a: Option<u32>, b: Option<u32> }, PairSlots(u32) }
+/// The stage that grades a result: two planes (class, label or track, in any combination) against each other.  Integer results,
+/// identical from run to run.
+pub struct HipCompare { ctx: Rc<Ctx>, ignore_a: Option<u32>, ignore_b: Option<u32>, pair_slots: u32, dirty: bool }
+impl HipCompare {
+    pub fn new(ctx: Rc<Ctx>) -> Self { Self { ctx, ignore_a: None, ignore_b: None, pair_slots: 0, dirty: true } }
+}
+impl Processor for HipCompare {
+    type Command = CompareCmd;
+    type ControlError = HipError;
+    type Input = (RunsPlane, RunsPlane);
+    type Output = Compared;
+    type ProcessResult = Result<(), HipError>;
+
+    fn control(&mut self, cmd: CompareCmd) -> Result<&mut Self, HipError> {
+        match cmd {
+            CompareCmd::Ignore { a, b } => {
+                self.dirty |= a != self.ignore_a || b != self.ignore_b;
+                self.ignore_a = a;
+                self.ignore_b = b;
+            }
+            CompareCmd::PairSlots(n) => {
+                self.dirty |= n != self.pair_slots;
+                self.pair_slots = n;
+            }
+        }
+        Ok(self)
+    }
+    fn is_dirty(&self) -> bool { self.dirty }
+    fn advance(&mut self, inp: &(RunsPlane, RunsPlane), out: &mut Compared) -> Result<(), HipError> {
+        self.dirty = false;
+        let [w, h] = inp.0.size;
+        if inp.1.size != inp.0.size { return Err(HipError::status(sys::INFUR_E_SHAPE)); }
+        let raw = |p: &RunsPlane| match &p.data {
+            RunsPlaneData::U8(d) => (d.as_ptr() as *const std::ffi::c_void, d.len(), 1u32),
+            RunsPlaneData::U32(d) => (d.as_ptr() as *const std::ffi::c_void, d.len(), 4u32),
+        };
+        let (pa, la, ea) = raw(&inp.0);
+        let (pb, lb, eb) = raw(&inp.1);
+        if la != w * h || lb != w * h { return Err(HipError::status(sys::INFUR_E_SHAPE)); }
+        let words = sys::INFUR_COMPARE_WORDS as usize;
+        out.matrix.resize(if out.want_matrix { out.rows_a * out.rows_b } else { 0 }, 0);
+        out.a.resize(out.rows_a * words, 0);
+        out.b.resize(out.rows_b * words, 0);
+        let flags = (if self.ignore_a.is_some() { sys::INFUR_COMPARE_IGNORE_A } else { 0 })
+            | (if self.ignore_b.is_some() { sys::INFUR_COMPARE_IGNORE_B } else { 0 });
+        let ptr = |v: &mut Vec<u32>| if v.is_empty() { std::ptr::null_mut() } else { v.as_mut_ptr() };
+        let rc = unsafe {
+            sys::infur_compare(self.ctx.0, pa, ea, pb, eb, h as u32, w as u32, flags, self.ignore_a.unwrap_or(0), self.ignore_b.unwrap_or(0),
+                               ptr(&mut out.matrix), out.rows_a as u32, out.rows_b as u32, ptr(&mut out.a), ptr(&mut out.b),
+                               out.counts.as_mut_ptr(), self.pair_slots)
+        };
+        if rc != sys::INFUR_OK { return Err(HipError::from_ctx(&self.ctx, rc)); }
+        Ok(())
+    }
+}
+
 // ---------------------------------------------------------------- Outlines (region boundaries as polygon loops)
 /// What `HipOutlines` produces: `loops` holds `min(n_loops, loops_rows)` records of `INFUR_LOOP_WORDS` words (OFFSET, COUNT, VALUE,
 /// START), `vertices` the first `min(n_vertices, vertex_rows)` vertex ids `Y*(w+1) + X`, loops back to back; the three counts are
