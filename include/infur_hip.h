@@ -1045,6 +1045,166 @@ int32_t infur_frame_compare_dev(infur_ctx* ctx, const void* d_bgr, uint32_t w, u
                                 uint32_t rows_b, void* d_rows_a_out, void* d_rows_b_out, void* d_counts, uint32_t pair_slots,
                                 void* d_scaled_bgr, uint32_t* ow, uint32_t* oh);
 
+/* ---- Adjacency: which regions touch, and along how many pixel edges ----
+ * The region adjacency graph of a class, label or track plane in device memory: "person touches bicycle", the perimeter and the
+ * degree of every object, and the graph Sieve (below) merges speckle along.  Presence of this group and of Sieve is announced by
+ * infur_features() & INFUR_FEATURE_SIEVE (INFUR_ABI_VERSION does not move).
+ *
+ * The input is a plane of h x w elements of elem = 1 or 4 bytes, h and w at most 65535 and h * w below 2^31.  Runs' rules hold for
+ * the element size, for unknown flag bits, for a skip value no 1-byte element can hold and for a NULL plane.
+ *   flags & INFUR_ADJ_SKIP   pixels whose value equals skip_value belong to no region (class 0, INFUR_REGION_NONE, INFUR_TRACK_NONE)
+ * rows is the number of values.  A pixel is INSIDE when its value is below rows and is not the skipped value; the others are
+ * SKIPPED or OUTSIDE: they are counted and take part in nothing else.  A border edge is a pixel edge between two 4-neighbours
+ * that are both inside and have different values.  Diagonal contact has length 0 and is no adjacency, whatever connectivity made
+ * the labels.  The edge between (x, y) and (x+1, y) has id 2 * (y*w + x), the edge between (x, y) and (x, y+1) id 2 * (y*w + x) + 1.
+ * Outputs, each optional (NULL = not wanted, and so is a row table of 0 rows; nothing wanted is INFUR_E_INVALID_ARG), none needs
+ * initialisation:
+ *   pairs     pair_rows records of INFUR_ADJ_PAIR_WORDS uint32_t, one per unordered pair of values that share at least one border
+ *             edge: INFUR_ADJ_A < INFUR_ADJ_B the two values, INFUR_ADJ_BORDER the number of border edges between them,
+ *             INFUR_ADJ_FIRST the smallest of their ids.  The records are in ascending order of FIRST -- Regions' numbering rule
+ *             carried over to edges -- and min(PAIRS, pair_rows) of them are written; the rest is left alone
+ *   rows_out  rows records of INFUR_ADJ_ROW_WORDS uint32_t, one per value: INFUR_ADJ_DEGREE the number of distinct neighbours,
+ *             INFUR_ADJ_LONGEST the neighbour with the longest shared border, ties to the smallest value (INFUR_ADJ_NONE without a
+ *             neighbour), INFUR_ADJ_ROW_BORDER that border's length, INFUR_ADJ_PERIMETER every pixel edge of the value against
+ *             anything that is not the value: other values, skipped and outside pixels, and the frame
+ *   counts    INFUR_ADJ_COUNT_WORDS uint32_t: INFUR_ADJ_PAIRS, INFUR_ADJ_EDGES (the sum of all BORDER words), INFUR_ADJ_SKIPPED
+ *             and INFUR_ADJ_OUTSIDE pixels, INFUR_ADJ_RUNS (R, below), INFUR_ADJ_WRITTEN (the records written: 0 when pairs is
+ *             NULL), one reserved word written as 0, INFUR_ADJ_STATUS
+ * h * w == 0 writes zero counts and rows (0, INFUR_ADJ_NONE, 0, 0), and nothing else.
+ *
+ * The pairs are collected in an open-addressing table of pair_slots slots: a power of two >= 64, 0 means 2^20, anything else is
+ * INFUR_E_INVALID_ARG.  R is the number of border runs: the maximal sequences of border edges between rows y and y+1 that are
+ * consecutive in x and have the same ordered (top, bottom) pair, and of border edges between columns x and x+1 that are consecutive
+ * in y and have the same ordered (left, right) pair.  R bounds the distinct pairs and is a function of the plane.  2 * R > pair_slots
+ * sets INFUR_ADJ_OVERFLOW in STATUS: no pair record is written, every row reads (0, INFUR_ADJ_NONE, 0, PERIMETER) and PAIRS = EDGES
+ * = WRITTEN = 0.  With pairs wanted, PAIRS > pair_rows sets INFUR_ADJ_TRUNCATED.  Neither is an error.
+ *
+ * Example (used by Sieve below): the label plane [[0,0,0,1,1,1],[0,2,0,1,1,1],[0,0,0,1,3,3],[0,0,0,1,3,4]], rows 5, nothing skipped:
+ * pairs (0,2,4,3) (0,1,4,4) (1,3,4,21) (3,4,2,35); rows_out (2,1,4,18) (2,0,4,14) (1,0,4,4) (2,1,4,8) (1,3,2,4); counts PAIRS 4,
+ * EDGES 14, SKIPPED 0, OUTSIDE 0, RUNS 9, WRITTEN 4, 0, STATUS 0.
+ *
+ * Checks, in this order, each INFUR_E_INVALID_ARG: the context; elem (1 or 4); unknown flag bits; skip_value above 255 on a 1-byte
+ * plane; h or w above 65535 or h * w >= 2^31; pair_slots; nothing wanted; a NULL plane with h * w > 0.  No output is touched when a
+ * call is rejected.  Everything is an integer, exact, and a function of the plane alone: identical bytes from run to run. */
+#define INFUR_ADJ_NONE 0xFFFFFFFFu
+enum { INFUR_ADJ_SKIP = 1 };
+enum { INFUR_ADJ_A = 0, INFUR_ADJ_B = 1, INFUR_ADJ_BORDER = 2, INFUR_ADJ_FIRST = 3, INFUR_ADJ_PAIR_WORDS = 4 };
+enum { INFUR_ADJ_DEGREE = 0, INFUR_ADJ_LONGEST = 1, INFUR_ADJ_ROW_BORDER = 2, INFUR_ADJ_PERIMETER = 3, INFUR_ADJ_ROW_WORDS = 4 };
+enum {
+    INFUR_ADJ_PAIRS = 0,
+    INFUR_ADJ_EDGES = 1,
+    INFUR_ADJ_SKIPPED = 2,
+    INFUR_ADJ_OUTSIDE = 3,
+    INFUR_ADJ_RUNS = 4,
+    INFUR_ADJ_WRITTEN = 5,
+    INFUR_ADJ_STATUS = 7,
+    INFUR_ADJ_COUNT_WORDS = 8
+};
+enum { INFUR_ADJ_OVERFLOW = 1, INFUR_ADJ_TRUNCATED = 2 };
+enum { INFUR_FEATURE_SIEVE = 1024 };
+
+/* on a given plane, host pointers */
+int32_t infur_adjacency(infur_ctx* ctx, const void* plane, uint32_t elem, uint32_t h, uint32_t w, uint32_t flags,
+                        uint32_t skip_value, uint32_t rows, uint32_t* pairs, uint32_t pair_rows, uint32_t* rows_out,
+                        uint32_t* counts, uint32_t pair_slots);
+/* device pointers throughout; enqueued on the context's stream, never synchronises: two memsets and at most nine launches, fixed by
+ * the arguments.  The scratch is owned by the context (twelve bytes per slot, sixteen per row, a quarter of a byte per pixel for
+ * ordered records) and grows only with a request larger than any before.  The outputs must not overlap the plane or each other. */
+int32_t infur_adjacency_dev(infur_ctx* ctx, const void* d_plane, uint32_t elem, uint32_t h, uint32_t w, uint32_t flags,
+                            uint32_t skip_value, uint32_t rows, void* d_pairs, uint32_t pair_rows, void* d_rows_out,
+                            void* d_counts, uint32_t pair_slots);
+
+/* ---- Sieve: merge speckle regions into their neighbours ----
+ * A decoded class plane has speckle: islands of a few pixels of the wrong class, pin-holes inside objects.  Regions' min_pixels
+ * drops them from the label plane and leaves the class plane as it is.  Sieve is the standard remedy (GDAL's gdal_sieve): a region
+ * below a size threshold takes the class of the neighbour it shares the longest border with.  The result is again a complete
+ * class plane, so Regions, Tracks, Runs, Outlines, Coverage, Anchors and Compare run on it unchanged.  Announced by
+ * infur_features() & INFUR_FEATURE_SIEVE.
+ *
+ * infur_sieve_dev takes what infur_regions_dev (infur_frame_regions_dev) leaves in device memory after a run with min_pixels = 0
+ * and without INFUR_REGIONS_SKIP_BACKGROUND: the h x w uint8_t class plane, the uint32_t label plane, the region table
+ * (table_rows rows of INFUR_REGION_WORDS uint64_t) and the device word n_regions; h and w at most 65535, h * w below 2^31.
+ *   n = min(n_regions, table_rows).  A pixel whose label is >= n, or is INFUR_REGION_NONE, is FIXED: it keeps its class and is
+ *   neither a source nor a target.
+ *   Region r is SMALL when PIXELS(r) < min_pixels; every other region is KEPT.
+ *   Round 0: the kept regions are resolved with their own CLASS.
+ *   Round t >= 1, over every region still unresolved after round t-1: among its neighbours that were resolved after round t-1
+ *   take the one with the largest BORDER, ties to the smallest region id.  The neighbours are the Adjacency pairs of the label
+ *   plane as given; borders are never re-evaluated after a merger.  If such a neighbour q exists, r becomes resolved with q's
+ *   class, INTO(r) = INTO(q) and ROUND(r) = t.  A kept region's INTO is itself.
+ *   The loop ends after the first round that resolves nothing, or after max_rounds rounds (0 means 8; above 64 is
+ *   INFUR_E_INVALID_ARG).  What is still unresolved is STRANDED and keeps its class.
+ * Outputs, each optional (all NULL is INFUR_E_INVALID_ARG), none needs initialisation; they must not overlap the inputs or each other:
+ *   klass_out  h*w uint8_t: the final class of the pixel's region; fixed pixels are copied
+ *   rows_out   n records of INFUR_SIEVE_ROW_WORDS uint32_t: INFUR_SIEVE_CLASS the final class, INFUR_SIEVE_INTO the kept region it
+ *              was absorbed into (itself for kept and stranded regions), INFUR_SIEVE_ROUND (0 for kept, INFUR_SIEVE_NONE for
+ *              stranded), INFUR_SIEVE_BORDER the winning border (0 for kept and stranded)
+ *   counts     INFUR_SIEVE_COUNT_WORDS uint32_t: INFUR_SIEVE_REGIONS (n), INFUR_SIEVE_SMALL, INFUR_SIEVE_ABSORBED,
+ *              INFUR_SIEVE_STRANDED, INFUR_SIEVE_ROUNDS (the last round that resolved something), INFUR_SIEVE_PIXELS_CHANGED,
+ *              INFUR_SIEVE_PAIRS, INFUR_SIEVE_STATUS
+ * STATUS bits: INFUR_SIEVE_OVERFLOW -- Adjacency's overflow rule fired for pair_slots (as above): klass_out is the input, every
+ * small region is stranded and PAIRS = 0; INFUR_SIEVE_ROUNDS_EXHAUSTED -- round max_rounds still resolved something and unresolved
+ * regions remain; INFUR_SIEVE_TABLE_SHORT -- n_regions > table_rows.  None is an error.  h * w == 0 writes zero counts and nothing else.
+ *
+ * A small region only ever joins a neighbour across a shared pixel edge.  So with STRANDED == 0 and no fixed pixels every region of
+ * klass_out holds at least min_pixels pixels, whichever of the two connectivities made the labels (counted under that connectivity),
+ * and the pixels of kept regions are unchanged.
+ *
+ * Example: the class plane [[1,1,1,2,2,2],[1,3,1,2,2,2],[1,1,1,2,4,4],[1,1,1,2,4,5]] has the label plane of the example above and
+ * the regions 0 (class 1, 11 pixels), 1 (class 2, 8), 2 (class 3, 1), 3 (class 4, 3), 4 (class 5, 1).  With min_pixels = 4 regions
+ * 2, 3 and 4 are small.  Round 1: 2 joins 0 (border 4), 3 joins 1 (border 4); 4 touches only 3, which was unresolved.  Round 2: 4
+ * joins 3 (border 2) and with it region 1.  rows_out (1,0,0,0) (2,1,0,0) (1,0,1,4) (2,1,1,4) (2,1,2,2); klass_out has three columns
+ * of 1 and three of 2; counts REGIONS 5, SMALL 3, ABSORBED 3, STRANDED 0, ROUNDS 2, PIXELS_CHANGED 5, PAIRS 4, STATUS 0.
+ *
+ * Checks, in this order, each INFUR_E_INVALID_ARG: the context; h or w above 65535 or h * w >= 2^31; max_rounds; pair_slots;
+ * nothing wanted; a NULL input with h * w > 0.  Everything is an integer and a function of the inputs alone: identical bytes from
+ * run to run. */
+#define INFUR_SIEVE_NONE 0xFFFFFFFFu
+enum { INFUR_SIEVE_CLASS = 0, INFUR_SIEVE_INTO = 1, INFUR_SIEVE_ROUND = 2, INFUR_SIEVE_BORDER = 3, INFUR_SIEVE_ROW_WORDS = 4 };
+enum {
+    INFUR_SIEVE_REGIONS = 0,
+    INFUR_SIEVE_SMALL = 1,
+    INFUR_SIEVE_ABSORBED = 2,
+    INFUR_SIEVE_STRANDED = 3,
+    INFUR_SIEVE_ROUNDS = 4,
+    INFUR_SIEVE_PIXELS_CHANGED = 5,
+    INFUR_SIEVE_PAIRS = 6,
+    INFUR_SIEVE_STATUS = 7,
+    INFUR_SIEVE_COUNT_WORDS = 8
+};
+enum { INFUR_SIEVE_OVERFLOW = 1, INFUR_SIEVE_ROUNDS_EXHAUSTED = 2, INFUR_SIEVE_TABLE_SHORT = 4 };
+
+/* host pointers: klass and labels h*w, table min(n_regions, table_rows) rows, n_regions by value */
+int32_t infur_sieve(infur_ctx* ctx, const uint8_t* klass, const uint32_t* labels, const uint64_t* table, uint32_t table_rows,
+                    uint32_t n_regions, uint32_t h, uint32_t w, uint32_t min_pixels, uint32_t max_rounds, uint32_t pair_slots,
+                    uint8_t* klass_out, uint32_t* rows_out, uint32_t* counts);
+/* device pointers throughout, d_n_regions included (one device uint32_t); enqueued on the context's stream, never synchronises and
+ * reads nothing back: three memsets, 4 + 2 * max_rounds launches (a choose launch over the pair slots and an apply launch over the
+ * regions per round; a round behind one that resolved nothing exits at once on a device flag) and one launch per wanted output.
+ * The scratch is owned by the context (twelve bytes per slot, twenty-four per table row). */
+int32_t infur_sieve_dev(infur_ctx* ctx, const void* d_klass, const void* d_labels, const void* d_table, uint32_t table_rows,
+                        const void* d_n_regions, uint32_t h, uint32_t w, uint32_t min_pixels, uint32_t max_rounds,
+                        uint32_t pair_slots, void* d_klass_out, void* d_rows_out, void* d_counts);
+/* The fused frame path with a cleaned class plane: scale -> model -> Segments decode(out[0]) -> Regions (the caller's connectivity,
+ * min_pixels = 0, no skip) -> Sieve (min_pixels), in one call.  The arguments are infur_frame_regions' own, then max_rounds,
+ * pair_slots, klass_out (plane_capacity bytes, like klass and conf) and the sieve counts.  klass and conf are the planes as decoded;
+ * klass_out is the cleaned plane.  When labels, table or n_regions is wanted Regions runs a second time, on the cleaned plane, with
+ * the caller's flags and min_pixels = 0: they describe the cleaned plane.  At least one of labels, table, n_regions, klass_out and
+ * counts must be wanted.  The library's own region table holds 2^20 rows: a frame with more regions has INFUR_SIEVE_TABLE_SHORT in
+ * its status and the regions beyond stay as they are.  The calls inherit infur_frame_regions' checks, errors and check order
+ * (max_rounds and pair_slots are checked behind connectivity and flags); they always enqueue eagerly and leave the graphs cached
+ * for infur_frame_advance_dev alone.  (The stream ring, batch and group calls produce RGBA only.) */
+int32_t infur_frame_sieve(infur_ctx* ctx, const uint8_t* bgr, uint32_t w, uint32_t h, float factor, uint32_t scale_mode,
+                          uint32_t decode, uint32_t connectivity, uint32_t min_pixels, uint32_t flags, uint8_t* klass, uint8_t* conf,
+                          size_t plane_capacity, uint32_t* labels, size_t labels_capacity, uint64_t* table, uint32_t table_rows,
+                          uint32_t* n_regions, uint8_t* scaled_bgr, uint32_t* ow, uint32_t* oh, uint32_t max_rounds,
+                          uint32_t pair_slots, uint8_t* klass_out, uint32_t* counts);
+int32_t infur_frame_sieve_dev(infur_ctx* ctx, const void* d_bgr, uint32_t w, uint32_t h, float factor, uint32_t scale_mode,
+                              uint32_t decode, uint32_t connectivity, uint32_t min_pixels, uint32_t flags, void* d_klass,
+                              void* d_conf, size_t plane_capacity, void* d_labels, size_t labels_capacity, void* d_table,
+                              uint32_t table_rows, void* d_n_regions, void* d_scaled_bgr, uint32_t* ow, uint32_t* oh,
+                              uint32_t max_rounds, uint32_t pair_slots, void* d_klass_out, void* d_counts);
+
 /* ---- streaming (infur/src/main.rs:27-99,105): bounded queue, copies overlapped with compute ----
  * The reference back-pressures its producer with sync_channel(2) (main.rs:105); a stream
  * here is a ring of `depth` pinned + device slots.  submit() copies the caller's frame into a

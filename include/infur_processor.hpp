@@ -575,6 +575,125 @@ private:
     bool dirty_ = true;
 };
 
+/// What `Adjacency` produces for `rows` values: `pairs` holds the WRITTEN = min(PAIRS, pair_rows) records of INFUR_ADJ_PAIR_WORDS
+/// words (A < B, BORDER, FIRST) in ascending FIRST, `table` INFUR_ADJ_ROW_WORDS words per value (DEGREE, LONGEST, BORDER,
+/// PERIMETER; LONGEST == INFUR_ADJ_NONE: no neighbour) and the INFUR_ADJ_COUNT_WORDS counts.
+struct AdjacencyOut {
+    uint32_t rows = 21, pair_rows = 4096;
+    std::vector<uint32_t> pairs, table, counts;
+    uint32_t count(uint32_t word) const { return counts[word]; }
+    uint32_t n_pairs() const { return (uint32_t)(pairs.size() / INFUR_ADJ_PAIR_WORDS); }
+    /// the border edges between the values a and b: 0 when they do not touch (or the record was not written)
+    uint32_t border(uint32_t a, uint32_t b) const {
+        if (a > b) { const uint32_t t = a; a = b, b = t; }
+        for (size_t i = 0; i + INFUR_ADJ_PAIR_WORDS <= pairs.size(); i += INFUR_ADJ_PAIR_WORDS)
+            if (pairs[i + INFUR_ADJ_A] == a && pairs[i + INFUR_ADJ_B] == b) return pairs[i + INFUR_ADJ_BORDER];
+        return 0;
+    }
+};
+
+/// The region adjacency graph of a plane -- a byte plane (class) or a u32 plane (labels, tracks): which values touch along how
+/// many pixel edges.  Integer results, identical from run to run.
+/// Command = the value that belongs to no region, and the pair table's slots; Input = a plane, Output = AdjacencyOut.
+class Adjacency {
+public:
+    struct Cmd {
+        enum Kind { Skip, SkipNone, PairSlots } kind;
+        uint32_t value;
+    };
+    explicit Adjacency(Context& c) : c_(c) {}
+    Status control(Cmd cmd) {
+        uint32_t flags = flags_, skip = skip_, slots = pair_slots_;
+        switch (cmd.kind) {
+        case Cmd::Skip: flags = INFUR_ADJ_SKIP, skip = cmd.value; break;
+        case Cmd::SkipNone: flags = skip = 0; break;
+        case Cmd::PairSlots: slots = cmd.value; break;
+        default: return INFUR_E_INVALID_ARG;
+        }
+        dirty_ = dirty_ || flags != flags_ || skip != skip_ || slots != pair_slots_;
+        flags_ = flags, skip_ = skip, pair_slots_ = slots;
+        return INFUR_OK;
+    }
+    bool is_dirty() const { return dirty_; }
+    template <class T>
+    Status advance(const std::vector<T>& plane, uint32_t height, uint32_t width, AdjacencyOut& out) {
+        static_assert(sizeof(T) == 1 || sizeof(T) == 4, "a plane of uint8_t or uint32_t");
+        dirty_ = false;
+        if (plane.size() != (size_t)width * height) return INFUR_E_SHAPE;
+        out.pairs.assign((size_t)out.pair_rows * INFUR_ADJ_PAIR_WORDS, 0);
+        out.table.assign((size_t)out.rows * INFUR_ADJ_ROW_WORDS, 0);
+        out.counts.assign(INFUR_ADJ_COUNT_WORDS, 0);
+        uint32_t none = 0;  // (a pointer for zero records: they are wanted, and none fits)
+        const Status rc = infur_adjacency(c_.get(), plane.data(), sizeof(T), height, width, flags_, skip_, out.rows,
+                                          out.pairs.empty() ? &none : out.pairs.data(), out.pair_rows, out.table.empty() ? nullptr : out.table.data(),
+                                          out.counts.data(), pair_slots_);
+        out.pairs.resize(rc == INFUR_OK ? (size_t)out.counts[INFUR_ADJ_WRITTEN] * INFUR_ADJ_PAIR_WORDS : 0);
+        return rc;
+    }
+
+private:
+    Context& c_;
+    uint32_t flags_ = 0, skip_ = 0, pair_slots_ = 0;
+    bool dirty_ = true;
+};
+
+/// What `Sieve` produces: `klass` the cleaned h * w class plane, `rows` INFUR_SIEVE_ROW_WORDS words per region (CLASS, INTO, ROUND,
+/// BORDER; ROUND == INFUR_SIEVE_NONE: stranded) and the INFUR_SIEVE_COUNT_WORDS counts.
+struct SieveOut {
+    uint32_t width = 0, height = 0;
+    std::vector<uint8_t> klass;
+    std::vector<uint32_t> rows, counts;
+    uint32_t count(uint32_t word) const { return counts[word]; }
+    uint32_t word(uint32_t region, uint32_t w) const { return rows[(size_t)region * INFUR_SIEVE_ROW_WORDS + w]; }
+};
+
+/// The stage that removes speckle: every region of fewer than `min_pixels` pixels takes the class of the neighbour it shares the
+/// longest border with, round by round.  Integer results, identical from run to run.
+/// Command = one of min_pixels / max_rounds / pair_slots; Input = the class plane and what Regions made of it (min_pixels 0, no
+/// background skip, want_labels), Output = SieveOut.
+class Sieve {
+public:
+    struct Cmd {
+        enum Kind { MinPixels, MaxRounds, PairSlots } kind;
+        uint32_t value;
+    };
+    explicit Sieve(Context& c, uint32_t min_pixels = 0) : c_(c), min_pixels_(min_pixels) {}
+    Status control(Cmd cmd) {
+        uint32_t minpx = min_pixels_, rounds = max_rounds_, slots = pair_slots_;
+        switch (cmd.kind) {
+        case Cmd::MinPixels: minpx = cmd.value; break;
+        case Cmd::MaxRounds:
+            if (cmd.value > 64) return INFUR_E_INVALID_ARG;  // state untouched
+            rounds = cmd.value;
+            break;
+        case Cmd::PairSlots: slots = cmd.value; break;
+        default: return INFUR_E_INVALID_ARG;
+        }
+        dirty_ = dirty_ || minpx != min_pixels_ || rounds != max_rounds_ || slots != pair_slots_;
+        min_pixels_ = minpx, max_rounds_ = rounds, pair_slots_ = slots;
+        return INFUR_OK;
+    }
+    bool is_dirty() const { return dirty_; }
+    Status advance(const std::vector<uint8_t>& klass, const RegionsOut& regions, SieveOut& out) {
+        dirty_ = false;
+        const size_t hw = (size_t)regions.width * regions.height;
+        if (klass.size() != hw || regions.labels.size() != hw) return INFUR_E_SHAPE;  // (a RegionsOut made with want_labels)
+        out.width = regions.width;
+        out.height = regions.height;
+        out.klass.assign(hw, 0);
+        out.rows.assign((size_t)regions.rows() * INFUR_SIEVE_ROW_WORDS, 0);
+        out.counts.assign(INFUR_SIEVE_COUNT_WORDS, 0);
+        return infur_sieve(c_.get(), klass.data(), regions.labels.data(), regions.table.data(), regions.table_rows, regions.n, regions.height,
+                           regions.width, min_pixels_, max_rounds_, pair_slots_, hw ? out.klass.data() : nullptr,
+                           out.rows.empty() ? nullptr : out.rows.data(), out.counts.data());
+    }
+
+private:
+    Context& c_;
+    uint32_t min_pixels_, max_rounds_ = 0, pair_slots_ = 0;
+    bool dirty_ = true;
+};
+
 /// What `Outlines` produces: `loops` holds min(n_loops, loops_rows) records of INFUR_LOOP_WORDS words, `vertices` the first
 /// min(n_vertices, vertex_rows) vertex ids Y*(width+1) + X, loops back to back; the three counts are complete whatever the rows
 /// are (n_loops == 0 with n_edges > 0: the edges exceeded the capacity).

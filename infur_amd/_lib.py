@@ -92,6 +92,20 @@ COMPARE_PIXELS, COMPARE_PARTNER, COMPARE_INTER, COMPARE_UNION, COMPARE_WORDS = 0
 COMPARE_OVERFLOW, COMPARE_TABLE = 1, 2
 COMPARE_NONE = 0xFFFFFFFF
 FEATURE_COMPARE = 512
+# Adjacency and Sieve (infur_adjacency / infur_sieve / infur_frame_sieve): the flag, the words of a pair record, of a row and of the
+# counts, the status bits, the feature bit both groups share
+ADJ_SKIP = 1
+ADJ_A, ADJ_B, ADJ_BORDER, ADJ_FIRST, ADJ_PAIR_WORDS = 0, 1, 2, 3, 4
+ADJ_DEGREE, ADJ_LONGEST, ADJ_ROW_BORDER, ADJ_PERIMETER, ADJ_ROW_WORDS = 0, 1, 2, 3, 4
+ADJ_PAIRS, ADJ_EDGES, ADJ_SKIPPED, ADJ_OUTSIDE, ADJ_RUNS, ADJ_WRITTEN, ADJ_STATUS, ADJ_COUNT_WORDS = 0, 1, 2, 3, 4, 5, 7, 8
+ADJ_OVERFLOW, ADJ_TRUNCATED = 1, 2
+ADJ_NONE = 0xFFFFFFFF
+SIEVE_CLASS, SIEVE_INTO, SIEVE_ROUND, SIEVE_BORDER, SIEVE_ROW_WORDS = 0, 1, 2, 3, 4
+(SIEVE_REGIONS, SIEVE_SMALL, SIEVE_ABSORBED, SIEVE_STRANDED, SIEVE_ROUNDS, SIEVE_PIXELS_CHANGED, SIEVE_PAIRS, SIEVE_STATUS,
+ SIEVE_COUNT_WORDS) = 0, 1, 2, 3, 4, 5, 6, 7, 8
+SIEVE_OVERFLOW, SIEVE_ROUNDS_EXHAUSTED, SIEVE_TABLE_SHORT = 1, 2, 4
+SIEVE_NONE = 0xFFFFFFFF
+FEATURE_SIEVE = 1024
 
 
 class Options(C.Structure):
@@ -244,6 +258,14 @@ SIGNATURES = {
                                         _u32, _vp, _u32p, _u32p]),
     "infur_frame_compare_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _vp, _sz, _vp, _vp, _sz, _vp, _u32, _u32, _vp, _vp,
                                             _vp, _u32, _vp, _u32p, _u32p]),
+    "infur_adjacency": (C.c_int32, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _vp, _u32]),
+    "infur_adjacency_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _vp, _u32]),
+    "infur_sieve": (C.c_int32, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
+    "infur_sieve_dev": (C.c_int32, [_vp, _vp, _vp, _vp, _u32, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
+    "infur_frame_sieve": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp, _vp,
+                                      _u32p, _u32p, _u32, _u32, _vp, _vp]),
+    "infur_frame_sieve_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp, _vp,
+                                          _u32p, _u32p, _u32, _u32, _vp, _vp]),
     "infur_stream_create": (C.c_int32, [_vp, _u32, C.POINTER(_vp)]),
     "infur_stream_destroy": (None, [_vp]),
     "infur_stream_add_lane": (C.c_int32, [_vp, _vp]),

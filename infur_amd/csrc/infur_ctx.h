@@ -191,6 +191,9 @@ struct infur_ctx {
     // Compare (infur_compare.cpp): the accumulators, per-value sums and maxima and the matrix or the pair table, the class plane of
     // the frame calls when the caller does not want it, and the host-pointer calls' staging.  Private like the above.
     infur::Buf st_cmp, st_cmp_plane, st_cmp_io;
+    // Adjacency and Sieve (infur_sieve.cpp): the accumulators, the pair table, the bitmap of first edges and the per-region state of
+    // the rounds; the planes, labels and region table of the frame calls; the host-pointer calls' staging.  Private like the above.
+    infur::Buf st_sieve, st_sieve_frame, st_sieve_io;
     // Tracks (infur_tracks.cpp): the live trackers of this context; infur_ctx_destroy releases their device memory and orphans them
     std::vector<infur_tracker*> trackers;
 

@@ -390,6 +390,36 @@ hipError_t launch_compare(const void* a, int elem_a, const void* b, int elem_b, 
                           unsigned ignore_b, unsigned rows_a, unsigned rows_b, void* scratch, unsigned pair_slots, unsigned* matrix, unsigned* rows_a_out,
                           unsigned* rows_b_out, unsigned* counts, hipStream_t s);
 
+// Adjacency (sieve.hip): which values of an H x W plane (H * W below 2^31) of 1- or 4-byte elements touch, and along how many pixel
+// edges.  A pixel is inside when its value is below `rows` and is not skip_value (skip set).  pairs: pair_rows x kAdjPairWords u32
+// (A, B, BORDER, FIRST) in ascending FIRST, min(PAIRS, pair_rows) of them; rows_out: rows x kAdjRowWords u32 (DEGREE, LONGEST,
+// BORDER, PERIMETER); counts[kAdjCountWords] = {PAIRS, EDGES, SKIPPED, OUTSIDE, RUNS, WRITTEN, 0, STATUS} (each optional; device
+// memory).  pair_slots: a power of two >= 64; 2 * RUNS above it sets kAdjOverflow: no record, rows (0, NONE, 0, PERIMETER).
+// scratch: adjacency_scratch_bytes(..) bytes the launches own for the call (want_pairs: pairs wanted with pair_rows > 0).
+// Stream-ordered; two memsets and at most nine launches; no workgroup waits for another.
+constexpr int kAdjPairWords = 4;
+constexpr int kAdjRowWords = 4;
+constexpr int kAdjCountWords = 8;
+constexpr unsigned kAdjOverflow = 1u, kAdjTruncated = 2u;
+size_t adjacency_scratch_bytes(size_t npix, unsigned rows, unsigned pair_slots, bool want_rows, bool want_pairs);
+hipError_t launch_adjacency(const void* plane, int elem_bytes, unsigned H, unsigned W, int skip, unsigned skip_value, unsigned rows, void* scratch,
+                            unsigned pair_slots, unsigned* pairs, unsigned pair_rows, unsigned* rows_out, unsigned* counts, hipStream_t s);
+
+// Sieve (sieve.hip): every region of fewer than min_pixels pixels takes the class of the resolved neighbour with the longest
+// border, round by round (max_rounds of 1 to 64), over the adjacency pairs of the label plane.  klass, labels, table (table_rows
+// rows of kRegWords u64) and the device word d_n are what launch_regions left; n = min(*d_n, table_rows), a pixel with a label
+// >= n keeps its class.  klass_out: H * W bytes; rows_out: n x kSieveRowWords u32 (CLASS, INTO, ROUND, BORDER); counts
+// [kSieveCountWords] = {REGIONS, SMALL, ABSORBED, STRANDED, ROUNDS, PIXELS_CHANGED, PAIRS, STATUS} (each optional).  scratch:
+// sieve_scratch_bytes(..).  Stream-ordered; three memsets, 4 + 2 * max_rounds launches and one per wanted output; a round behind
+// one that resolved nothing exits on a device flag; nothing is read back.
+constexpr int kSieveRowWords = 4;
+constexpr int kSieveCountWords = 8;
+constexpr unsigned kSieveOverflow = 1u, kSieveRoundsExhausted = 2u, kSieveTableShort = 4u;
+size_t sieve_scratch_bytes(size_t npix, unsigned table_rows, unsigned pair_slots);
+hipError_t launch_sieve(const uint8_t* klass, const unsigned* labels, const unsigned long long* table, unsigned table_rows, const unsigned* d_n, unsigned H,
+                        unsigned W, unsigned min_pixels, unsigned max_rounds, void* scratch, unsigned pair_slots, uint8_t* klass_out, unsigned* rows_out,
+                        unsigned* counts, hipStream_t s);
+
 // Outlines (outlines.hip): the boundaries of the value-regions of an H x W plane of 1- or 4-byte elements as closed loops --
 // loops_rows x kLoopWords u32 records (OFFSET, COUNT, VALUE, START), vertex_rows u32 vertex ids Y * (W + 1) + X, and counts[3] =
 // {n_loops, n_vertices, n_edges} (each optional; device memory).  skip: pixels of skip_value belong to no region; conn8: the

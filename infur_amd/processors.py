@@ -1153,6 +1153,177 @@ def panoptic_summary(rows_a: np.ndarray, rows_b: np.ndarray, class_of_a, class_o
     return {"classes": dict(sorted(acc.items())), "pq": mean("pq"), "sq": mean("sq"), "rq": mean("rq")}
 
 
+@dataclass
+class AdjacencyCmd:
+    """``Adjacency``'s command: ``Skip(value)`` takes the pixels of that value out of every region (None: none are skipped);
+    ``pair_slots`` sizes the pair table (0: the library's 2^20)."""
+
+    skip_value: Optional[int] = None
+    pair_slots: int = 0
+
+    @staticmethod
+    def Skip(value: Optional[int] = None, pair_slots: int = 0) -> "AdjacencyCmd":
+        return AdjacencyCmd(skip_value=value, pair_slots=pair_slots)
+
+
+class AdjacencyOut:
+    """``Adjacency``'s ``&mut Output``: what to produce (``rows`` values, ``pair_rows`` records at most, ``want_pairs``,
+    ``want_rows``, ``want_counts``) and, after ``advance``, the results -- ``pairs`` [WRITTEN, 4] u32 (columns ``_lib.ADJ_A`` ..
+    ``_lib.ADJ_FIRST``, in ascending FIRST), ``table`` [rows, 4] u32 (``_lib.ADJ_DEGREE`` .. ``_lib.ADJ_PERIMETER``), ``counts``
+    [8] u32 (``_lib.ADJ_PAIRS`` .. ``_lib.ADJ_STATUS``); None for what was not wanted."""
+
+    def __init__(self, rows: int = 21, pair_rows: int = 4096, want_pairs: bool = True, want_rows: bool = True, want_counts: bool = True):
+        self.rows, self.pair_rows = rows, pair_rows
+        self.want_pairs, self.want_rows, self.want_counts = want_pairs, want_rows, want_counts
+        self.pairs = self.table = self.counts = None
+
+
+class Adjacency(Processor):
+    """The region adjacency graph of a plane -- a class plane (u8), a label or track plane (u32): which values touch along how
+    many pixel edges, and per value its degree, longest neighbour and perimeter.
+
+    Command = ``AdjacencyCmd``.  Input = an [H, W] plane; Output = ``AdjacencyOut``.  Integers throughout, identical from run to
+    run; ``adjacency_graph`` turns the records into neighbour lists.
+    """
+
+    def __init__(self, ctx: Context, skip_value: Optional[int] = None, pair_slots: int = 0):
+        self.ctx = ctx
+        self.skip_value, self.pair_slots = skip_value, pair_slots
+        self.dirty = True
+
+    def control(self, cmd: AdjacencyCmd) -> "Adjacency":
+        if cmd.skip_value is not None and not 0 <= cmd.skip_value <= 0xFFFFFFFF:
+            raise InfurError(_lib.E_INVALID_ARG, f"skip value {cmd.skip_value}: a u32")
+        if not 0 <= cmd.pair_slots <= 0xFFFFFFFF:
+            raise InfurError(_lib.E_INVALID_ARG, f"pair_slots {cmd.pair_slots}: a u32")
+        new = (cmd.skip_value, cmd.pair_slots)
+        self.dirty = self.dirty or new != (self.skip_value, self.pair_slots)
+        self.skip_value, self.pair_slots = new
+        return self
+
+    def is_dirty(self) -> bool:
+        return self.dirty
+
+    def advance(self, inp: np.ndarray, out: AdjacencyOut) -> None:
+        self.dirty = False
+        if inp.ndim != 2 or inp.dtype.itemsize not in (1, 4) or inp.dtype.kind not in "ui":
+            raise InfurError(_lib.E_SHAPE, f"expected an [H,W] plane of 1- or 4-byte integers, got {inp.shape} {inp.dtype}")
+        plane = np.ascontiguousarray(inp)
+        h, w = plane.shape
+        rows, pair_rows = max(0, int(out.rows)), max(0, int(out.pair_rows))
+        pairs = np.empty((pair_rows, _lib.ADJ_PAIR_WORDS), np.uint32) if out.want_pairs else None
+        table = np.empty((rows, _lib.ADJ_ROW_WORDS), np.uint32) if out.want_rows and rows else None
+        counts = np.zeros(_lib.ADJ_COUNT_WORDS, np.uint32)
+        self.ctx.check(self.ctx.L.infur_adjacency(self.ctx.h, plane.ctypes.data if plane.size else None, plane.dtype.itemsize, h, w,
+                                                  _lib.ADJ_SKIP if self.skip_value is not None else 0, self.skip_value or 0, rows,
+                                                  pairs.ctypes.data if pairs is not None else None, pair_rows, _ptr(table), counts.ctypes.data,
+                                                  self.pair_slots))
+        out.pairs = pairs[:int(counts[_lib.ADJ_WRITTEN])] if pairs is not None else None
+        out.table, out.counts = table, counts if out.want_counts else None
+
+
+def adjacency_graph(pairs: np.ndarray, rows: int) -> dict:
+    """``Adjacency``'s pair records as neighbour lists: {value: [(neighbour, border), ..]} for every value below ``rows``, each list
+    in descending border and then ascending neighbour -- its head is the row table's LONGEST.  A value without a neighbour has an
+    empty list."""
+    graph: dict = {v: [] for v in range(int(rows))}
+    for a, b, border, _ in np.asarray(pairs, np.uint32).reshape(-1, _lib.ADJ_PAIR_WORDS).tolist():
+        graph.setdefault(a, []).append((b, border))
+        graph.setdefault(b, []).append((a, border))
+    for v in graph.values():
+        v.sort(key=lambda nb: (-nb[1], nb[0]))
+    return graph
+
+
+@dataclass
+class SieveCmd:
+    """``Sieve``'s command: regions of fewer than ``min_pixels`` pixels are merged; ``max_rounds`` (0: the library's 8, at most
+    64); ``pair_slots`` (0: the library's 2^20)."""
+
+    min_pixels: int = 0
+    max_rounds: int = 0
+    pair_slots: int = 0
+
+
+class SieveOut:
+    """``Sieve``'s ``&mut Output``: what to produce and, after ``advance``, ``klass`` [H, W] u8 (the cleaned plane), ``rows`` [n, 4]
+    u32 (``_lib.SIEVE_CLASS`` .. ``_lib.SIEVE_BORDER``), ``counts`` [8] u32 (``_lib.SIEVE_REGIONS`` .. ``_lib.SIEVE_STATUS``); None
+    for what was not wanted."""
+
+    def __init__(self, want_klass: bool = True, want_rows: bool = True, want_counts: bool = True):
+        self.want_klass, self.want_rows, self.want_counts = want_klass, want_rows, want_counts
+        self.klass = self.rows = self.counts = None
+
+
+class Sieve(Processor):
+    """The stage that removes speckle: every region below ``min_pixels`` takes the class of the neighbour it shares the longest
+    border with, round by round.
+
+    Command = ``SieveCmd``.  Input = (klass [H, W] u8, labels [H, W] u32, table [rows, 10] u64, n) as ``Regions`` gives them with
+    ``min_pixels = 0`` and no background skip; Output = ``SieveOut``.  ``sieve_summary`` names the counts.
+    """
+
+    def __init__(self, ctx: Context, min_pixels: int = 0, max_rounds: int = 0, pair_slots: int = 0):
+        self.ctx = ctx
+        self.min_pixels, self.max_rounds, self.pair_slots = min_pixels, max_rounds, pair_slots
+        self.dirty = True
+
+    def control(self, cmd: SieveCmd) -> "Sieve":
+        for name in ("min_pixels", "max_rounds", "pair_slots"):
+            if not 0 <= getattr(cmd, name) <= 0xFFFFFFFF:
+                raise InfurError(_lib.E_INVALID_ARG, f"{name} {getattr(cmd, name)}: a u32")
+        new = (cmd.min_pixels, cmd.max_rounds, cmd.pair_slots)
+        self.dirty = self.dirty or new != (self.min_pixels, self.max_rounds, self.pair_slots)
+        self.min_pixels, self.max_rounds, self.pair_slots = new
+        return self
+
+    def is_dirty(self) -> bool:
+        return self.dirty
+
+    def advance(self, inp, out: SieveOut) -> None:
+        self.dirty = False
+        klass, labels, table, n = inp
+        if klass.ndim != 2 or klass.dtype != np.uint8 or labels.shape != klass.shape or labels.dtype != np.uint32:
+            raise InfurError(_lib.E_SHAPE, f"expected an [H,W] uint8 class plane and a uint32 label plane of one size, got {klass.shape} "
+                                           f"{klass.dtype} and {labels.shape} {labels.dtype}")
+        klass, labels = np.ascontiguousarray(klass), np.ascontiguousarray(labels)
+        table = np.ascontiguousarray(table, np.uint64).reshape(-1, _lib.REGION_WORDS)
+        h, w = klass.shape
+        rows = min(int(n), len(table))
+        cleaned = np.empty((h, w), np.uint8) if out.want_klass else None
+        sieved = np.empty((rows, _lib.SIEVE_ROW_WORDS), np.uint32) if out.want_rows else None
+        counts = np.zeros(_lib.SIEVE_COUNT_WORDS, np.uint32) if out.want_counts else None
+        ptr = lambda p: p.ctypes.data if p is not None and p.size else None  # noqa: E731
+        self.ctx.check(self.ctx.L.infur_sieve(self.ctx.h, ptr(klass), ptr(labels), ptr(table), len(table), int(n), h, w, self.min_pixels,
+                                              self.max_rounds, self.pair_slots, ptr(cleaned), ptr(sieved), _ptr(counts)))
+        out.klass, out.rows, out.counts = cleaned, sieved, counts
+
+
+def sieve_summary(counts: np.ndarray) -> dict:
+    """``Sieve``'s eight counts by name: ``regions``, ``small``, ``absorbed``, ``stranded``, ``rounds``, ``pixels_changed``,
+    ``pairs``, ``status``, and the status bits as ``overflow``, ``rounds_exhausted`` and ``table_short``."""
+    c = [int(v) for v in np.asarray(counts).ravel()[:_lib.SIEVE_COUNT_WORDS]]
+    status = c[_lib.SIEVE_STATUS]
+    return {"regions": c[_lib.SIEVE_REGIONS], "small": c[_lib.SIEVE_SMALL], "absorbed": c[_lib.SIEVE_ABSORBED], "stranded": c[_lib.SIEVE_STRANDED],
+            "rounds": c[_lib.SIEVE_ROUNDS], "pixels_changed": c[_lib.SIEVE_PIXELS_CHANGED], "pairs": c[_lib.SIEVE_PAIRS], "status": status,
+            "overflow": bool(status & _lib.SIEVE_OVERFLOW), "rounds_exhausted": bool(status & _lib.SIEVE_ROUNDS_EXHAUSTED),
+            "table_short": bool(status & _lib.SIEVE_TABLE_SHORT)}
+
+
+class SieveFrame(NamedTuple):
+    """``FramePath.advance_sieve``: the class and confidence planes as decoded and the cleaned class plane [oh, ow] u8 (None where
+    not wanted), the label plane, region table and region count of the cleaned plane, Sieve's counts [8] u32, the scaled frame"""
+
+    klass: Optional[np.ndarray]
+    conf: Optional[np.ndarray]
+    cleaned: Optional[np.ndarray]
+    labels: Optional[np.ndarray]
+    table: Optional[np.ndarray]
+    n: Optional[int]
+    counts: Optional[np.ndarray]
+    scaled: Optional[np.ndarray]
+
+
 def runs_decode(runs: np.ndarray, n: int, h: int, w: int, fill: int = 0, dtype=None) -> np.ndarray:
     """The dense [h, w] plane of the first ``min(n, len(runs))`` records; pixels no record covers (skipped or truncated runs) read
     ``fill``.  ``dtype``: uint8 when every value and ``fill`` fit a byte, else uint32."""
@@ -1634,6 +1805,32 @@ class FramePath:
         if not self._loaded(rc):
             return CompareFrame(None, None, scaled, None, None, None, None)
         return CompareFrame(klass, conf, scaled, matrix, ra, rb, counts)
+
+    def advance_sieve(self, img: np.ndarray, min_pixels: int, factor: float = 1.0, decode: int = _lib.DECODE_RAW,
+                      connectivity: int = _lib.CONNECT_8, flags: int = 0, table_rows: int = 1024, max_rounds: int = 0, pair_slots: int = 0,
+                      want_labels: bool = True, want_klass: bool = False, want_conf: bool = True, want_cleaned: bool = True,
+                      want_scaled: bool = False) -> SieveFrame:
+        """The fused path with a cleaned class plane, scale -> model -> Segments decode -> Regions -> Sieve (regions below
+        ``min_pixels`` merged into their neighbours) -> Regions of the cleaned plane (``flags``; only with ``want_labels`` or
+        ``table_rows``, ``n`` is None otherwise), in one call -> ``SieveFrame``; every result field is None when no model is
+        loaded (``scaled`` is still produced)."""
+        img, w, h, f, ow, oh = self._front(img, factor)
+        npix = oh.value * ow.value
+        rows = max(0, min(int(table_rows), npix))
+        klass, conf, cleaned = self._plane(ow, oh, want_klass), self._plane(ow, oh, want_conf), self._plane(ow, oh, want_cleaned)
+        labels = self._plane(ow, oh, want_labels, np.uint32)
+        table = np.zeros((rows, _lib.REGION_WORDS), np.uint64) if rows else None
+        scaled = self._plane(ow, oh, want_scaled, channels=3)
+        counts = np.zeros(_lib.SIEVE_COUNT_WORDS, np.uint32)
+        n = C.c_uint32(0)
+        again = want_labels or rows > 0  # the regions of the cleaned plane: a second Regions pass, only when something of it is wanted
+        rc = self.ctx.L.infur_frame_sieve(self.ctx.h, img.ctypes.data, w, h, f, self.scale_mode, decode, connectivity, min_pixels, flags, _ptr(klass),
+                                          _ptr(conf), npix, _ptr(labels), npix * 4, _ptr(table), rows, C.addressof(n) if again else None, _ptr(scaled),
+                                          C.byref(ow), C.byref(oh), max_rounds, pair_slots, _ptr(cleaned), counts.ctypes.data)
+        if not self._loaded(rc):
+            return SieveFrame(None, None, None, None, None, None, None, scaled)
+        return SieveFrame(klass, conf, cleaned, labels, table[:min(n.value, rows)] if table is not None else None, n.value if again else None, counts,
+                          scaled)
 
     def advance_tracks(self, tracks: "Tracks", img: np.ndarray, factor: float = 1.0, decode: int = _lib.DECODE_RAW,
                        connectivity: int = _lib.CONNECT_8, min_pixels: int = 0, flags: int = 0, table_rows: int = 1024,

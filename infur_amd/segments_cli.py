@@ -58,6 +58,14 @@ distances back to back (0: a pixel of no region).
 the class plane is compared with it (``infur_compare``; ``--truth-ignore V`` leaves the pixels whose truth is V, a "void" label,
 out), every line gains ``"pixel_accuracy"`` and ``"miou"``, and one last line holds the totals of the confusion matrices added up
 over the frames: ``"frames"``, ``"pixel_accuracy"``, ``"miou"``, ``"fwiou"``, the per-class IoUs and the matrix itself.
+
+``--sieve N`` removes speckle on the device: the frame goes through ``infur_frame_sieve`` (and with it ``infur_frame_sieve_dev``),
+every region of fewer than N pixels takes the class of the neighbour it shares the longest border with (``--sieve-rounds R``: at
+most R rounds, 1 to 64; the library's 8 by default), and every line gains ``"sieve": {small, absorbed, stranded, rounds,
+pixels_changed, status}``.  ``--labels-out``, ``--regions`` and ``--regions-out`` see the cleaned plane (``--connectivity`` and
+``--skip-background`` apply; the regions are those of the cleaned plane, none is dropped), ``"classes"`` is summarised from the
+cleaned class plane and the confidence plane as decoded.  ``--sieve`` is refused together with ``--min-pixels``, ``--tracks``,
+``--runs-out``, ``--outlines-out``, ``--anchors`` and ``--truth``: those paths read planes this one does not leave on the device.
 """
 from __future__ import annotations
 
@@ -107,7 +115,20 @@ def main(argv=None) -> int:
     ap.add_argument("--dist-out", default="", help="raw u32 planes of squared distances, four bytes per pixel (needs --anchors)")
     ap.add_argument("--truth", default="", help="raw u8 ground-truth class planes, one per frame: adds pixel_accuracy and miou, and a line of totals")
     ap.add_argument("--truth-ignore", type=int, default=None, metavar="V", help="truth pixels of this value are not compared (needs --truth)")
+    ap.add_argument("--sieve", type=int, default=None, metavar="N", help="merge regions of fewer than N pixels into their neighbours on the device")
+    ap.add_argument("--sieve-rounds", type=int, default=None, metavar="R", help="at most R rounds of merging, 1 to 64 (needs --sieve)")
     a = ap.parse_args(argv)
+    if a.sieve_rounds is not None and a.sieve is None:
+        ap.error("--sieve-rounds needs --sieve")
+    if a.sieve is not None and not 1 <= a.sieve <= 0xFFFFFFFF:
+        ap.error("--sieve: a number of pixels, at least 1")
+    if a.sieve_rounds is not None and not 1 <= a.sieve_rounds <= 64:
+        ap.error("--sieve-rounds: 1 to 64")
+    if a.sieve is not None:
+        for given, name in ((a.min_pixels, "--min-pixels"), (a.tracks, "--tracks"), (a.runs_out, "--runs-out"), (a.outlines_out, "--outlines-out"),
+                            (a.anchors, "--anchors"), (a.truth, "--truth")):
+            if given:
+                ap.error(f"--sieve does not combine with {name}: that path reads planes the sieve call does not leave on the device")
     if a.truth_ignore is not None and not a.truth:
         ap.error("--truth-ignore needs --truth")
     if a.truth_ignore is not None and not 0 <= a.truth_ignore <= 255:
@@ -147,7 +168,7 @@ def main(argv=None) -> int:
 
     from . import _lib
     from .app import RawVideoSource, VideoProcError
-    from .processors import (Compare, CompareOut, confusion_summary, Context, Coverage, CoverageOut, FramePath, Model, ModelCmd, Outlines, OutlinesOut, Runs, RunsOut, SegmentsFrame, Simplify, SimplifyOut,
+    from .processors import (Compare, CompareOut, confusion_summary, sieve_summary, Context, Coverage, CoverageOut, FramePath, Model, ModelCmd, Outlines, OutlinesOut, Runs, RunsOut, SegmentsFrame, Simplify, SimplifyOut,
                              class_summary, region_summary, tolerance_to_tol16, track_summary)
 
     tol16 = tolerance_to_tol16(a.outlines_tolerance) if a.outlines_tolerance is not None else None
@@ -181,7 +202,9 @@ def main(argv=None) -> int:
         classes = model.get_info().num_classes
         grader, total = Compare(ctx, ignore_b=a.truth_ignore), np.zeros((classes, classes), np.uint64)
     rpath = None
-    if a.regions:
+    if a.regions and a.sieve is not None:
+        flags = _lib.REGIONS_SKIP_BACKGROUND if a.skip_background else 0
+    elif a.regions:
         oh, ow = _out_dims(ctx, a.width, a.height, a.scale)
         rpath = _RegionsPath(ctx, a.width, a.height, ow, oh, a.scale, fp.scale_mode, model.get_info().num_classes, max(0, a.max_regions),
                              tracks=a.tracks, memory=(a.tracks_memory, a.tracks_reach),
@@ -196,7 +219,12 @@ def main(argv=None) -> int:
             if e.kind == "FinishedNormally":
                 break
             raise
-        if rpath is not None:
+        if a.sieve is not None:  # scale -> model -> decode -> Regions -> Sieve -> Regions of the cleaned plane, in one call
+            r = fp.advance_sieve(img, a.sieve, a.scale, decode, a.connectivity, flags if a.regions else 0, table_rows=max(0, a.max_regions) if a.regions else 0,
+                                 max_rounds=a.sieve_rounds or 0, want_labels=freg is not None)
+            s = SegmentsFrame(r.cleaned, r.conf, _class_stats(r.cleaned, r.conf, model.get_info().num_classes), None, None)
+            labels, table, nreg = r.labels, r.table, r.n
+        elif rpath is not None:
             s, labels, table, nreg = rpath.advance(img, decode, a.connectivity, a.min_pixels, flags, flab is not None or ftruth is not None, fconf is not None,
                                                    freg is not None, keep_labels=(fruns is not None and a.runs_plane == "labels") or foutl is not None or a.anchors)
             if a.tracks:
@@ -249,6 +277,14 @@ def main(argv=None) -> int:
             total += graded.matrix
             grade = confusion_summary(graded.matrix)
             rec["pixel_accuracy"], rec["miou"] = grade["pixel_accuracy"], grade["miou"]
+        if a.sieve is not None:
+            sv = sieve_summary(r.counts)
+            rec["sieve"] = {k: sv[k] for k in ("small", "absorbed", "stranded", "rounds", "pixels_changed", "status")}
+            if a.regions:
+                rec["n_regions"] = nreg
+                rec["regions"] = region_summary(table, nreg, ow, oh)
+                if freg is not None:
+                    freg.write(memoryview(labels).cast("B"))
         if rpath is not None:
             rec["n_regions"] = nreg
             rec["regions"] = region_summary(table, nreg, ow, oh, anchors=anch) if a.anchors else region_summary(table, nreg, ow, oh)
@@ -435,6 +471,25 @@ class _RegionsPath:
         for p in self.d.values():
             self.ctx.L.infur_dev_free(self.ctx.h, p)
         self.d = {}
+
+
+def _class_stats(klass, conf, classes):
+    """--sieve: the per-class table (INFUR_STAT_WORDS u64 per class) of a cleaned class plane and the confidence plane, on the host"""
+    import numpy as np
+
+    h, w = klass.shape
+    st = np.zeros((classes, _STAT_BYTES // 8), np.uint64)
+    k = klass.ravel().astype(np.int64)
+    ys, xs = np.divmod(np.arange(h * w, dtype=np.int64), w)
+    ok = k < classes
+    k, ys, xs, cf = k[ok], ys[ok], xs[ok], conf.ravel()[ok].astype(np.int64)
+    for col, wt in ((0, None), (1, xs), (2, ys), (3, cf)):
+        st[:, col] = np.bincount(k, weights=wt, minlength=classes).astype(np.uint64)  # < 2^53: exact
+    for col, v, fn, init in ((4, xs, np.minimum, h * w), (5, ys, np.minimum, h * w), (6, xs, np.maximum, 0), (7, ys, np.maximum, 0)):
+        acc = np.full(classes, init, np.int64)
+        fn.at(acc, k, v)
+        st[:, col] = acc.astype(np.uint64)
+    return st
 
 
 _STAT_BYTES = 8 * 8    # INFUR_STAT_WORDS u64 per class

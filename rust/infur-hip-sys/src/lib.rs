@@ -223,6 +223,50 @@ pub const INFUR_COMPARE_TABLE: u32 = 2;
 pub const INFUR_COMPARE_NONE: u32 = 0xFFFF_FFFF;
 /// bit of `infur_features()`: the Compare calls below exist
 pub const INFUR_FEATURE_COMPARE: u32 = 512;
+/// Adjacency: the flag, the words of a pair record, of a row and of the counts, the status bits, "no neighbour"
+pub const INFUR_ADJ_SKIP: u32 = 1;
+pub const INFUR_ADJ_A: u32 = 0;
+pub const INFUR_ADJ_B: u32 = 1;
+pub const INFUR_ADJ_BORDER: u32 = 2;
+pub const INFUR_ADJ_FIRST: u32 = 3;
+pub const INFUR_ADJ_PAIR_WORDS: u32 = 4;
+pub const INFUR_ADJ_DEGREE: u32 = 0;
+pub const INFUR_ADJ_LONGEST: u32 = 1;
+pub const INFUR_ADJ_ROW_BORDER: u32 = 2;
+pub const INFUR_ADJ_PERIMETER: u32 = 3;
+pub const INFUR_ADJ_ROW_WORDS: u32 = 4;
+pub const INFUR_ADJ_PAIRS: u32 = 0;
+pub const INFUR_ADJ_EDGES: u32 = 1;
+pub const INFUR_ADJ_SKIPPED: u32 = 2;
+pub const INFUR_ADJ_OUTSIDE: u32 = 3;
+pub const INFUR_ADJ_RUNS: u32 = 4;
+pub const INFUR_ADJ_WRITTEN: u32 = 5;
+pub const INFUR_ADJ_STATUS: u32 = 7;
+pub const INFUR_ADJ_COUNT_WORDS: u32 = 8;
+pub const INFUR_ADJ_OVERFLOW: u32 = 1;
+pub const INFUR_ADJ_TRUNCATED: u32 = 2;
+pub const INFUR_ADJ_NONE: u32 = 0xFFFF_FFFF;
+/// Sieve: the words of a row and of the counts, the status bits, "stranded"
+pub const INFUR_SIEVE_CLASS: u32 = 0;
+pub const INFUR_SIEVE_INTO: u32 = 1;
+pub const INFUR_SIEVE_ROUND: u32 = 2;
+pub const INFUR_SIEVE_BORDER: u32 = 3;
+pub const INFUR_SIEVE_ROW_WORDS: u32 = 4;
+pub const INFUR_SIEVE_REGIONS: u32 = 0;
+pub const INFUR_SIEVE_SMALL: u32 = 1;
+pub const INFUR_SIEVE_ABSORBED: u32 = 2;
+pub const INFUR_SIEVE_STRANDED: u32 = 3;
+pub const INFUR_SIEVE_ROUNDS: u32 = 4;
+pub const INFUR_SIEVE_PIXELS_CHANGED: u32 = 5;
+pub const INFUR_SIEVE_PAIRS: u32 = 6;
+pub const INFUR_SIEVE_STATUS: u32 = 7;
+pub const INFUR_SIEVE_COUNT_WORDS: u32 = 8;
+pub const INFUR_SIEVE_OVERFLOW: u32 = 1;
+pub const INFUR_SIEVE_ROUNDS_EXHAUSTED: u32 = 2;
+pub const INFUR_SIEVE_TABLE_SHORT: u32 = 4;
+pub const INFUR_SIEVE_NONE: u32 = 0xFFFF_FFFF;
+/// bit of `infur_features()`: the Adjacency and Sieve calls below exist
+pub const INFUR_FEATURE_SIEVE: u32 = 1024;
 
 extern "C" {
     pub fn infur_abi_version() -> u32;
@@ -489,4 +533,26 @@ extern "C" {
                                    d_conf: *mut c_void, plane_capacity: usize, d_matrix: *mut c_void, rows_a: u32, rows_b: u32,
                                    d_rows_a_out: *mut c_void, d_rows_b_out: *mut c_void, d_counts: *mut c_void, pair_slots: u32,
                                    d_scaled_bgr: *mut c_void, ow: *mut u32, oh: *mut u32) -> i32;
+    // Adjacency: which values of a plane touch, along how many pixel edges; Sieve: speckle regions merged into their neighbours
+    pub fn infur_adjacency(c: *mut infur_ctx, plane: *const c_void, elem: u32, h: u32, w: u32, flags: u32, skip_value: u32, rows: u32,
+                           pairs: *mut u32, pair_rows: u32, rows_out: *mut u32, counts: *mut u32, pair_slots: u32) -> i32;
+    pub fn infur_adjacency_dev(c: *mut infur_ctx, d_plane: *const c_void, elem: u32, h: u32, w: u32, flags: u32, skip_value: u32,
+                               rows: u32, d_pairs: *mut c_void, pair_rows: u32, d_rows_out: *mut c_void, d_counts: *mut c_void,
+                               pair_slots: u32) -> i32;
+    pub fn infur_sieve(c: *mut infur_ctx, klass: *const u8, labels: *const u32, table: *const u64, table_rows: u32, n_regions: u32,
+                       h: u32, w: u32, min_pixels: u32, max_rounds: u32, pair_slots: u32, klass_out: *mut u8, rows_out: *mut u32,
+                       counts: *mut u32) -> i32;
+    pub fn infur_sieve_dev(c: *mut infur_ctx, d_klass: *const c_void, d_labels: *const c_void, d_table: *const c_void, table_rows: u32,
+                           d_n_regions: *const c_void, h: u32, w: u32, min_pixels: u32, max_rounds: u32, pair_slots: u32,
+                           d_klass_out: *mut c_void, d_rows_out: *mut c_void, d_counts: *mut c_void) -> i32;
+    pub fn infur_frame_sieve(c: *mut infur_ctx, bgr: *const u8, w: u32, h: u32, factor: f32, scale_mode: u32, decode: u32,
+                             connectivity: u32, min_pixels: u32, flags: u32, klass: *mut u8, conf: *mut u8, plane_capacity: usize,
+                             labels: *mut u32, labels_capacity: usize, table: *mut u64, table_rows: u32, n_regions: *mut u32,
+                             scaled_bgr: *mut u8, ow: *mut u32, oh: *mut u32, max_rounds: u32, pair_slots: u32, klass_out: *mut u8,
+                             counts: *mut u32) -> i32;
+    pub fn infur_frame_sieve_dev(c: *mut infur_ctx, d_bgr: *const c_void, w: u32, h: u32, factor: f32, scale_mode: u32, decode: u32,
+                                 connectivity: u32, min_pixels: u32, flags: u32, d_klass: *mut c_void, d_conf: *mut c_void,
+                                 plane_capacity: usize, d_labels: *mut c_void, labels_capacity: usize, d_table: *mut c_void,
+                                 table_rows: u32, d_n_regions: *mut c_void, d_scaled_bgr: *mut c_void, ow: *mut u32, oh: *mut u32,
+                                 max_rounds: u32, pair_slots: u32, d_klass_out: *mut c_void, d_counts: *mut c_void) -> i32;
 }

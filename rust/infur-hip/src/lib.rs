@@ -778,6 +778,136 @@ impl Processor for HipCompare {
     }
 }
 
+// ---------------------------------------------------------------- Adjacency (which values touch, along how many pixel edges)
+/// What `HipAdjacency` produces for `rows` values: `pairs` holds the `min(PAIRS, pair_rows)` records of `INFUR_ADJ_PAIR_WORDS` words
+/// (A < B, BORDER, FIRST) in ascending FIRST, `table` `INFUR_ADJ_ROW_WORDS` words per value (DEGREE, LONGEST, BORDER, PERIMETER;
+/// LONGEST == `INFUR_ADJ_NONE`: no neighbour) and the `INFUR_ADJ_COUNT_WORDS` counts.
+pub struct Adjacent { pub rows: usize, pub pair_rows: usize, pub pairs: Vec<u32>, pub table: Vec<u32>,
+                      pub counts: [u32; sys::INFUR_ADJ_COUNT_WORDS as usize] }
+impl Default for Adjacent {
+    fn default() -> Self {
+        Self { rows: 21, pair_rows: 4096, pairs: Vec::new(), table: Vec::new(), counts: [0; sys::INFUR_ADJ_COUNT_WORDS as usize] }
+    }
+}
+impl Adjacent {
+    pub fn count(&self, word: u32) -> u32 { self.counts[word as usize] }
+    /// the neighbours of `value` with their borders, longest first and then by value: the head is the row table's LONGEST
+    pub fn neighbours(&self, value: u32) -> Vec<(u32, u32)> {
+        let mut v: Vec<(u32, u32)> = self.pairs.chunks_exact(sys::INFUR_ADJ_PAIR_WORDS as usize).filter_map(|p| {
+            if p[0] == value { Some((p[1], p[2])) } else if p[1] == value { Some((p[0], p[2])) } else { None }
+        }).collect();
+        v.sort_by(|x, y| y.1.cmp(&x.1).then(x.0.cmp(&y.0)));
+        v
+    }
+}
+pub enum AdjacencyCmd { Skip(u32), NoSkip, PairSlots(u32) }
+/// The region adjacency graph of a class, label or track plane.  Integer results, identical from run to run.
+pub struct HipAdjacency { ctx: Rc<Ctx>, skip: Option<u32>, pair_slots: u32, dirty: bool }
+impl HipAdjacency {
+    pub fn new(ctx: Rc<Ctx>) -> Self { Self { ctx, skip: None, pair_slots: 0, dirty: true } }
+}
+impl Processor for HipAdjacency {
+    type Command = AdjacencyCmd;
+    type ControlError = HipError;
+    type Input = RunsPlane;
+    type Output = Adjacent;
+    type ProcessResult = Result<(), HipError>;
+
+    fn control(&mut self, cmd: AdjacencyCmd) -> Result<&mut Self, HipError> {
+        let (skip, slots) = match cmd {
+            AdjacencyCmd::Skip(v) => (Some(v), self.pair_slots),
+            AdjacencyCmd::NoSkip => (None, self.pair_slots),
+            AdjacencyCmd::PairSlots(n) => (self.skip, n),
+        };
+        self.dirty |= skip != self.skip || slots != self.pair_slots;
+        self.skip = skip;
+        self.pair_slots = slots;
+        Ok(self)
+    }
+    fn is_dirty(&self) -> bool { self.dirty }
+    fn advance(&mut self, inp: &RunsPlane, out: &mut Adjacent) -> Result<(), HipError> {
+        self.dirty = false;
+        let [w, h] = inp.size;
+        let (ptr, len, elem) = match &inp.data {
+            RunsPlaneData::U8(d) => (d.as_ptr() as *const std::ffi::c_void, d.len(), 1u32),
+            RunsPlaneData::U32(d) => (d.as_ptr() as *const std::ffi::c_void, d.len(), 4u32),
+        };
+        if len != w * h { return Err(HipError::status(sys::INFUR_E_SHAPE)); }
+        out.pairs.clear();
+        out.pairs.resize(out.pair_rows.max(1) * sys::INFUR_ADJ_PAIR_WORDS as usize, 0);  // (a pointer also for zero records)
+        out.table.resize(out.rows * sys::INFUR_ADJ_ROW_WORDS as usize, 0);
+        let rc = unsafe {
+            sys::infur_adjacency(self.ctx.0, ptr, elem, h as u32, w as u32, if self.skip.is_some() { sys::INFUR_ADJ_SKIP } else { 0 },
+                                 self.skip.unwrap_or(0), out.rows as u32, out.pairs.as_mut_ptr(), out.pair_rows as u32,
+                                 if out.table.is_empty() { std::ptr::null_mut() } else { out.table.as_mut_ptr() }, out.counts.as_mut_ptr(),
+                                 self.pair_slots)
+        };
+        if rc != sys::INFUR_OK { out.pairs.clear(); return Err(HipError::from_ctx(&self.ctx, rc)); }
+        out.pairs.truncate(out.counts[sys::INFUR_ADJ_WRITTEN as usize] as usize * sys::INFUR_ADJ_PAIR_WORDS as usize);
+        Ok(())
+    }
+}
+
+// ---------------------------------------------------------------- Sieve (speckle regions merged into their neighbours)
+/// What `HipSieve` consumes: the class plane and what `HipRegions` made of it with `min_pixels` 0, no background skip and
+/// `want_labels`.
+pub struct SieveInput { pub klass: Vec<u8>, pub regions: Regions }
+/// What `HipSieve` produces: `klass` the cleaned `h * w` class plane, `rows` `INFUR_SIEVE_ROW_WORDS` words per region (CLASS, INTO,
+/// ROUND, BORDER; ROUND == `INFUR_SIEVE_NONE`: stranded) and the `INFUR_SIEVE_COUNT_WORDS` counts.
+#[derive(Default)]
+pub struct Sieved { pub size: [usize; 2], pub klass: Vec<u8>, pub rows: Vec<u32>, pub counts: [u32; sys::INFUR_SIEVE_COUNT_WORDS as usize] }
+impl Sieved {
+    pub fn count(&self, word: u32) -> u32 { self.counts[word as usize] }
+    pub fn word(&self, region: usize, word: u32) -> u32 { self.rows[region * sys::INFUR_SIEVE_ROW_WORDS as usize + word as usize] }
+}
+pub enum SieveCmd { MinPixels(u32), MaxRounds(u32), PairSlots(u32) }
+/// The stage that removes speckle: every region of fewer than `min_pixels` pixels takes the class of the neighbour it shares the
+/// longest border with, round by round.  Integer results, identical from run to run.
+pub struct HipSieve { ctx: Rc<Ctx>, min_pixels: u32, max_rounds: u32, pair_slots: u32, dirty: bool }
+impl HipSieve {
+    pub fn new(ctx: Rc<Ctx>) -> Self { Self { ctx, min_pixels: 0, max_rounds: 0, pair_slots: 0, dirty: true } }
+}
+impl Processor for HipSieve {
+    type Command = SieveCmd;
+    type ControlError = HipError;
+    type Input = SieveInput;
+    type Output = Sieved;
+    type ProcessResult = Result<(), HipError>;
+
+    fn control(&mut self, cmd: SieveCmd) -> Result<&mut Self, HipError> {
+        let (minpx, rounds, slots) = match cmd {
+            SieveCmd::MinPixels(n) => (n, self.max_rounds, self.pair_slots),
+            SieveCmd::MaxRounds(n) => {
+                if n > 64 { return Err(HipError::status(sys::INFUR_E_INVALID_ARG)); }  // state untouched
+                (self.min_pixels, n, self.pair_slots)
+            }
+            SieveCmd::PairSlots(n) => (self.min_pixels, self.max_rounds, n),
+        };
+        self.dirty |= (minpx, rounds, slots) != (self.min_pixels, self.max_rounds, self.pair_slots);
+        self.min_pixels = minpx;
+        self.max_rounds = rounds;
+        self.pair_slots = slots;
+        Ok(self)
+    }
+    fn is_dirty(&self) -> bool { self.dirty }
+    fn advance(&mut self, inp: &SieveInput, out: &mut Sieved) -> Result<(), HipError> {
+        self.dirty = false;
+        let [w, h] = inp.regions.size;
+        if inp.klass.len() != w * h || inp.regions.labels.len() != w * h { return Err(HipError::status(sys::INFUR_E_SHAPE)); }
+        out.size = inp.regions.size;
+        out.klass.resize(w * h, 0);
+        out.rows.resize(inp.regions.rows() * sys::INFUR_SIEVE_ROW_WORDS as usize, 0);
+        let rc = unsafe {
+            sys::infur_sieve(self.ctx.0, inp.klass.as_ptr(), inp.regions.labels.as_ptr(), inp.regions.table.as_ptr(), inp.regions.table_rows as u32,
+                             inp.regions.n, h as u32, w as u32, self.min_pixels, self.max_rounds, self.pair_slots,
+                             if out.klass.is_empty() { std::ptr::null_mut() } else { out.klass.as_mut_ptr() },
+                             if out.rows.is_empty() { std::ptr::null_mut() } else { out.rows.as_mut_ptr() }, out.counts.as_mut_ptr())
+        };
+        if rc != sys::INFUR_OK { return Err(HipError::from_ctx(&self.ctx, rc)); }
+        Ok(())
+    }
+}
+
 // ---------------------------------------------------------------- Outlines (region boundaries as polygon loops)
 /// What `HipOutlines` produces: `loops` holds `min(n_loops, loops_rows)` records of `INFUR_LOOP_WORDS` words (OFFSET, COUNT, VALUE,
 /// START), `vertices` the first `min(n_vertices, vertex_rows)` vertex ids `Y*(w+1) + X`, loops back to back; the three counts are
