@@ -1205,6 +1205,125 @@ int32_t infur_frame_sieve_dev(infur_ctx* ctx, const void* d_bgr, uint32_t w, uin
                               uint32_t table_rows, void* d_n_regions, void* d_scaled_bgr, uint32_t* ow, uint32_t* oh,
                               uint32_t max_rounds, uint32_t pair_slots, void* d_klass_out, void* d_counts);
 
+/* ---- Shapes: convex hull, moments and minimum rectangle per outline loop ----
+ * The stages above say where an object is and where its edge runs; none says what shape it has: elongated or round, lying or
+ * standing, solid or ragged.  Shapes takes what Outlines left in device memory and computes, loop by loop, the area, perimeter and
+ * second-order moments, the convex hull, and the smallest rectangle around the hull; per value it sums them.  Every quantity is an
+ * exact integer function of a loop: identical bytes from run to run and no tolerance anywhere.  Presence of this group is announced
+ * by infur_features() & INFUR_FEATURE_SHAPES (INFUR_ABI_VERSION does not move).
+ *
+ * INPUT.  Simplify's exactly: Outlines' `loops`, `vertices` and `counts` for a plane of width w, with loops_rows_in and
+ * vertex_rows_in; w in 1 .. 8191 and h at most 8191, otherwise INFUR_E_INVALID_ARG; a NULL counts, or a NULL array with rows
+ * declared, is INFUR_E_INVALID_ARG.  No plane is read.
+ * PER LOOP with vertices v_0 .. v_{n-1}, v_n := v_0, and c_i = x_i * y_{i+1} - x_{i+1} * y_i.  Every word is a signed 64-bit
+ * integer (the arrays are declared uint64_t: read them as two's complement); the sums are formed modulo 2^64, intermediates may
+ * wrap, the true values fit (24 * integral of xy < 2^57 with coordinates up to 8191).  A record has INFUR_SHAPE_WORDS words:
+ *   INFUR_SHAPE_AREA2       sum c_i                                                  twice the area; negative for a hole
+ *   INFUR_SHAPE_PERIMETER   sum |x_{i+1} - x_i| + |y_{i+1} - y_i|                    the lattice length
+ *   INFUR_SHAPE_M10_6       sum c_i (x_i + x_{i+1})                                  6 * integral of x
+ *   INFUR_SHAPE_M01_6       sum c_i (y_i + y_{i+1})                                  6 * integral of y
+ *   INFUR_SHAPE_M20_12      sum c_i (x_i^2 + x_i x_{i+1} + x_{i+1}^2)                12 * integral of x^2
+ *   INFUR_SHAPE_M02_12      sum c_i (y_i^2 + y_i y_{i+1} + y_{i+1}^2)                12 * integral of y^2
+ *   INFUR_SHAPE_M11_24      sum c_i (x_i y_{i+1} + 2 x_i y_i + 2 x_{i+1} y_{i+1} + x_{i+1} y_i)   24 * integral of xy
+ *   INFUR_SHAPE_HULL_AREA2  the shoelace sum of the hull's vertices: it has the loop's sign
+ *   INFUR_SHAPE_RECT_EDGE, _RECT_W, _RECT_H, _RECT_L   the minimum rectangle, below
+ * The integrals run over the union of pixel squares, pixel (x, y) being [x, x+1] x [y, y+1]; summed over the loops of a value
+ * (holes are negative) AREA2 = 2 * pixels, M10_6 = 3 * sum(2x + 1), M20_12 = 2 * sum(6x^2 + 6x + 2), M11_24 = 6 * sum(2x + 1)(2y + 1),
+ * and likewise in y.
+ * HULL.  The kept set is the set of strictly extreme points of the loop's vertices: collinear points on a hull edge are dropped.
+ * It is written in the loop's own order in Simplify's output layout: loops_out record i is (OFFSET', COUNT', VALUE, START) for
+ * input loop i, vertices_out holds the kept ids back to back, with Simplify's truncation rules.  The set is defined mathematically
+ * and does not depend on how it is found.  (This holds for every loop that is a polygon's boundary, which is every loop Outlines
+ * writes: the kernel walks index ranges and relies on the hull's vertices appearing in the loop's order.  For other vertex lists
+ * the output is some subset of the vertices, a function of the list alone and inside the buffers.  When all vertices are one point,
+ * COUNT' = 1.)
+ * MINIMUM RECTANGLE over the hull's edges j (kept vertex j -> j+1, vector e, L = |e|^2): W_j = max_p e.p - min_p e.p and
+ * H_j = max_p |e x (p - v_j)| over the hull's vertices p; the rectangle on edge j has the sides sqrt(W^2 / L) along e and
+ * sqrt(H^2 / L) across it, and the area W * H / L.  RECT_EDGE is the j that minimises the area, compared exactly as
+ * W_a H_a L_b < W_b H_b L_a in 128 bits, on a tie the smallest j; RECT_W, RECT_H, RECT_L are that edge's.  COUNT' = 1 gives zeros.
+ * PER VALUE, `value_rows` rows of INFUR_SHAPE_WORDS words, optional: for every loop with VALUE < value_rows, the row of its value
+ * receives the sums of the seven measures (so AREA2 / 2 is the value's pixel count and the moments are the region's);
+ * INFUR_SHAPE_HULL_AREA2 is summed over the outer loops (AREA2 > 0); INFUR_SHAPE_OUTER and INFUR_SHAPE_HOLES count the loops with
+ * AREA2 > 0 and AREA2 < 0 (their difference is the Euler number); INFUR_SHAPE_LOOP is the index of the value's outer loop with the
+ * largest AREA2, on a tie the smallest index, and -1 for a value without one: the region's hull and rectangle are that loop's.
+ * Word 11 is 0.  Every one of the value_rows rows is written.
+ * OUTPUTS, each optional (NULL or no rows = not wanted; nothing wanted is INFUR_E_INVALID_ARG), none needs initialisation; a
+ * rejected call touches no output: loops_out and vertices_out as above; `shapes`, the first min(n_loops, shape_rows) per-loop
+ * records; `values`; counts_out, INFUR_SHAPES_COUNT_WORDS uint32_t {n_loops, n_hull_vertices, status, largest COUNT'}, always
+ * complete.
+ * STATUS.  INFUR_SHAPES_TRUNCATED: counts[0] > loops_rows_in or counts[1] > vertex_rows_in.  Only counts_out, as {counts[0], 0,
+ * 1, 0}, and the per-value table, as for a plane without loops, are written.  INFUR_SHAPES_MALFORMED: some record had COUNT < 2 or
+ * OFFSET + COUNT > counts[1].  Such a loop gets COUNT' = 0, a record of zeros, and adds nothing to its value.  Every read is
+ * clamped to the rows the caller declared: no value held in the input buffers can take a load or a store outside them.
+ * EXAMPLE 1, the "C": a 24 x 24 plane, class 1 = [2:22, 2:22] minus [7:17, 7:22], class 0 skipped.  One loop of 8 vertices (2,2)
+ * (22,2) (22,7) (7,7) (7,17) (22,17) (22,22) (2,22): AREA2 500, PERIMETER 110, M10_6 15750, M01_6 18000, M20_12 439000, M02_12
+ * 577000, M11_24 756000.  The hull is (2,2) (22,2) (22,22) (2,22), HULL_AREA2 800 (solidity 0.625); the rectangle is edge 0 with
+ * W = H = L = 400.  The centroid in pixel centres is 15750 / (3 * 500) - 1/2 = 10.0.
+ * EXAMPLE 2, a slanted bar: a 12 x 16 plane, value 2 where |(x - 8) - (y - 6)| <= 1, 1 <= y <= 10 and 1 <= x <= 14, value 0
+ * skipped.  One loop of 40 vertices: AREA2 60, PERIMETER 44, M10_6 1440, M01_6 1080, M20_12 26280, M02_12 15960, M11_24 40500.
+ * The hull is (2,1) (5,1) (14,10) (14,11) (11,11) (2,2), HULL_AREA2 78; the rectangle is edge 1 with W 198, H 36, L 162: 15.56 x
+ * 2.83 pixels, area 44.
+ * COST.  A wave owns a loop: the measures read it once, the hull reads a range once per level of the recursion below it, 64
+ * vertices a step; the rectangle is O(k^2 / 64) steps for a hull of k vertices (88 for a disc of radius 120).
+ * WHAT IT DOES NOT DO.  No hull of a value with several outer loops, no Hu invariants, no least-squares ellipse, no Feret
+ * diameters other than the rectangle's, no confidence-weighted moments, no input above 8191.  The stream ring, batch and group
+ * calls produce RGBA only. */
+enum {
+    INFUR_SHAPE_AREA2 = 0,
+    INFUR_SHAPE_PERIMETER = 1,
+    INFUR_SHAPE_M10_6 = 2,
+    INFUR_SHAPE_M01_6 = 3,
+    INFUR_SHAPE_M20_12 = 4,
+    INFUR_SHAPE_M02_12 = 5,
+    INFUR_SHAPE_M11_24 = 6,
+    INFUR_SHAPE_HULL_AREA2 = 7,
+    INFUR_SHAPE_RECT_EDGE = 8,
+    INFUR_SHAPE_RECT_W = 9,
+    INFUR_SHAPE_RECT_H = 10,
+    INFUR_SHAPE_RECT_L = 11,
+    INFUR_SHAPE_WORDS = 12
+};
+enum { INFUR_SHAPE_OUTER = 8, INFUR_SHAPE_HOLES = 9, INFUR_SHAPE_LOOP = 10 }; /* words 8 .. 10 of a per-value row */
+enum { INFUR_SHAPES_LOOPS = 0, INFUR_SHAPES_VERTICES = 1, INFUR_SHAPES_STATUS = 2, INFUR_SHAPES_LARGEST = 3, INFUR_SHAPES_COUNT_WORDS = 4 };
+enum { INFUR_SHAPES_TRUNCATED = 1, INFUR_SHAPES_MALFORMED = 2 };
+enum { INFUR_FEATURE_SHAPES = 2048 };
+
+/* host pointers, with Simplify's copy rules: counts is read first, min(counts[0], loops_rows_in) records and min(counts[1],
+ * vertex_rows_in) vertices travel to the device; then counts_out is read and what it says there is comes back */
+int32_t infur_shapes(infur_ctx* ctx, const uint32_t* loops, uint32_t loops_rows_in, const uint32_t* vertices,
+                     uint32_t vertex_rows_in, const uint32_t* counts, uint32_t h, uint32_t w, uint32_t* loops_out,
+                     uint32_t loops_rows_out, uint32_t* vertices_out, uint32_t vertex_rows_out, uint64_t* shapes,
+                     uint32_t shape_rows, uint64_t* values, uint32_t value_rows, uint32_t* counts_out);
+/* device pointers throughout; enqueued on the context's stream as at most two memsets and 6 launches, a number fixed by the
+ * arguments: the call never synchronises, so its grids are sized by loops_rows_in and vertex_rows_in -- declare the rows Outlines
+ * was given, not more.  Capturable after one call outside the capture, which allocates the scratch: 9 bytes per vertex row, one
+ * per loop row and the scan's sums, owned by the context.  The outputs must not overlap the inputs. */
+int32_t infur_shapes_dev(infur_ctx* ctx, const void* d_loops, uint32_t loops_rows_in, const void* d_vertices,
+                         uint32_t vertex_rows_in, const void* d_counts, uint32_t h, uint32_t w, void* d_loops_out,
+                         uint32_t loops_rows_out, void* d_vertices_out, uint32_t vertex_rows_out, void* d_shapes,
+                         uint32_t shape_rows, void* d_values, uint32_t value_rows, void* d_counts_out);
+/* The fused frame path with a descriptor per object: scale -> model -> Segments decode(out[0]) -> Regions -> Outlines of the label
+ * plane (INFUR_REGION_NONE skipped, the caller's connectivity) -> Shapes, in one call.  The arguments are infur_frame_regions'
+ * own, then Outlines' max_edges and Shapes' outputs; `values` has table_rows rows and row i is region i, table or no table.
+ * Every output is optional, and at least one must be given; the label plane goes to scratch of the library's own when the caller
+ * does not want it.  When a Shapes output is wanted the scaled frame must be at most 8191 x 8191 (INFUR_E_INVALID_ARG, before the
+ * model runs).  A plane with more edges than max_edges (0: the worst case) reads counts = {0, 0, 0, 0} and a per-value table
+ * without loops.  The calls inherit infur_frame_regions' checks, errors and order: with no model loaded the Scale stage still
+ * runs and the call returns INFUR_E_MODEL_NOT_LOADED.  They always enqueue eagerly and leave the graphs cached for
+ * infur_frame_advance_dev alone. */
+int32_t infur_frame_shapes(infur_ctx* ctx, const uint8_t* bgr, uint32_t w, uint32_t h, float factor, uint32_t scale_mode,
+                           uint32_t decode, uint32_t connectivity, uint32_t min_pixels, uint32_t flags, uint8_t* klass, uint8_t* conf,
+                           size_t plane_capacity, uint32_t* labels, size_t labels_capacity, uint64_t* table, uint32_t table_rows,
+                           uint32_t* n_regions, uint8_t* scaled_bgr, uint32_t* ow, uint32_t* oh, uint32_t max_edges,
+                           uint32_t* loops_out, uint32_t loops_rows_out, uint32_t* vertices_out, uint32_t vertex_rows_out,
+                           uint64_t* shapes, uint32_t shape_rows, uint64_t* values, uint32_t* counts_out);
+int32_t infur_frame_shapes_dev(infur_ctx* ctx, const void* d_bgr, uint32_t w, uint32_t h, float factor, uint32_t scale_mode,
+                               uint32_t decode, uint32_t connectivity, uint32_t min_pixels, uint32_t flags, void* d_klass,
+                               void* d_conf, size_t plane_capacity, void* d_labels, size_t labels_capacity, void* d_table,
+                               uint32_t table_rows, void* d_n_regions, void* d_scaled_bgr, uint32_t* ow, uint32_t* oh,
+                               uint32_t max_edges, void* d_loops_out, uint32_t loops_rows_out, void* d_vertices_out,
+                               uint32_t vertex_rows_out, void* d_shapes, uint32_t shape_rows, void* d_values, void* d_counts_out);
+
 /* ---- streaming (infur/src/main.rs:27-99,105): bounded queue, copies overlapped with compute ----
  * The reference back-pressures its producer with sync_channel(2) (main.rs:105); a stream
  * here is a ring of `depth` pinned + device slots.  submit() copies the caller's frame into a

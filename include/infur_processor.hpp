@@ -829,6 +829,61 @@ private:
     bool dirty_ = true;
 };
 
+/// What `Shapes` produces: the hulls in Outlines' layout (`loops`, `vertices`), `shapes` with INFUR_SHAPE_WORDS signed words per
+/// loop (INFUR_SHAPE_AREA2 .. INFUR_SHAPE_RECT_L) and `values` with as many per value (words 8 .. 10: INFUR_SHAPE_OUTER,
+/// INFUR_SHAPE_HOLES, INFUR_SHAPE_LOOP), every one of value_rows written; status: INFUR_SHAPES_TRUNCATED (the input was cut off),
+/// INFUR_SHAPES_MALFORMED; largest: the largest COUNT'.
+struct ShapesOut {
+    uint32_t loops_rows = 1u << 16, vertex_rows = 1u << 20, shape_rows = 1u << 16, value_rows = 0;
+    uint32_t width = 0, height = 0, n_loops = 0, n_vertices = 0, status = 0, largest = 0;
+    std::vector<uint32_t> loops, vertices;
+    std::vector<int64_t> shapes, values;
+    uint32_t word(uint32_t loop, uint32_t w) const { return loops[(size_t)loop * INFUR_LOOP_WORDS + w]; }
+    int64_t shape(uint32_t loop, uint32_t w) const { return shapes[(size_t)loop * INFUR_SHAPE_WORDS + w]; }
+    int64_t value(uint32_t v, uint32_t w) const { return values[(size_t)v * INFUR_SHAPE_WORDS + w]; }
+    uint32_t x(uint32_t vertex) const { return vertices[vertex] % (width + 1); }
+    uint32_t y(uint32_t vertex) const { return vertices[vertex] / (width + 1); }
+};
+
+/// The descriptor stage behind Outlines: per loop the area, perimeter and moments, the convex hull and the minimum rectangle, per
+/// value the sums.  Integer results, identical from run to run.  No command; Input = an OutlinesOut, Output = ShapesOut.
+class Shapes {
+public:
+    explicit Shapes(Context& c) : c_(c) {}
+    bool is_dirty() const { return dirty_; }
+    Status advance(const OutlinesOut& in, ShapesOut& out) {
+        dirty_ = false;
+        out.width = in.width;
+        out.height = in.height;
+        const uint32_t rows_in = (uint32_t)(in.loops.size() / INFUR_LOOP_WORDS), verts_in = (uint32_t)in.vertices.size();
+        const uint32_t lrows = out.loops_rows < rows_in ? out.loops_rows : rows_in, vrows = out.vertex_rows < verts_in ? out.vertex_rows : verts_in;
+        const uint32_t srows = out.shape_rows < rows_in ? out.shape_rows : rows_in;
+        out.loops.assign((size_t)lrows * INFUR_LOOP_WORDS, 0);
+        out.vertices.assign(vrows, 0);
+        out.shapes.assign((size_t)srows * INFUR_SHAPE_WORDS, 0);
+        out.values.assign((size_t)out.value_rows * INFUR_SHAPE_WORDS, 0);
+        const uint32_t counts_in[2] = {in.n_loops, in.n_vertices};
+        uint32_t counts[INFUR_SHAPES_COUNT_WORDS] = {0, 0, 0, 0};
+        const Status s = infur_shapes(c_.get(), rows_in ? in.loops.data() : nullptr, rows_in, verts_in ? in.vertices.data() : nullptr, verts_in, counts_in,
+                                      in.height, in.width, lrows ? out.loops.data() : nullptr, lrows, vrows ? out.vertices.data() : nullptr, vrows,
+                                      srows ? (uint64_t*)out.shapes.data() : nullptr, srows, out.value_rows ? (uint64_t*)out.values.data() : nullptr,
+                                      out.value_rows, counts);
+        out.n_loops = counts[INFUR_SHAPES_LOOPS];
+        out.n_vertices = counts[INFUR_SHAPES_VERTICES];
+        out.status = counts[INFUR_SHAPES_STATUS];
+        out.largest = counts[INFUR_SHAPES_LARGEST];
+        const bool cut = (out.status & INFUR_SHAPES_TRUNCATED) != 0;
+        out.loops.resize((size_t)(cut ? 0 : (out.n_loops < lrows ? out.n_loops : lrows)) * INFUR_LOOP_WORDS);
+        out.vertices.resize(out.n_vertices < vrows ? out.n_vertices : vrows);
+        out.shapes.resize((size_t)(cut ? 0 : (out.n_loops < srows ? out.n_loops : srows)) * INFUR_SHAPE_WORDS);
+        return s;
+    }
+
+private:
+    Context& c_;
+    bool dirty_ = true;
+};
+
 /// What `Coverage` produces, in Outlines' layout: `loops` holds min(n_loops, loops_rows) records (OFFSET', COUNT', VALUE, START),
 /// `vertices` the first min(n_vertices, vertex_rows) kept vertex ids; n_degenerate counts the loops with COUNT' < 3 (skip them);
 /// status: INFUR_COVERAGE_TRUNCATED and INFUR_COVERAGE_OVERFLOW (nothing was produced), INFUR_COVERAGE_MALFORMED; n_aug: the

@@ -106,6 +106,14 @@ SIEVE_CLASS, SIEVE_INTO, SIEVE_ROUND, SIEVE_BORDER, SIEVE_ROW_WORDS = 0, 1, 2, 3
 SIEVE_OVERFLOW, SIEVE_ROUNDS_EXHAUSTED, SIEVE_TABLE_SHORT = 1, 2, 4
 SIEVE_NONE = 0xFFFFFFFF
 FEATURE_SIEVE = 1024
+# Shapes (infur_shapes / infur_frame_shapes): the words of a per-loop record, of a per-value row (8 .. 10 differ) and of the counts,
+# the status bits, the feature bit
+(SHAPE_AREA2, SHAPE_PERIMETER, SHAPE_M10_6, SHAPE_M01_6, SHAPE_M20_12, SHAPE_M02_12, SHAPE_M11_24, SHAPE_HULL_AREA2, SHAPE_RECT_EDGE,
+ SHAPE_RECT_W, SHAPE_RECT_H, SHAPE_RECT_L, SHAPE_WORDS) = range(13)
+SHAPE_OUTER, SHAPE_HOLES, SHAPE_LOOP = 8, 9, 10
+SHAPES_LOOPS, SHAPES_VERTICES, SHAPES_STATUS, SHAPES_LARGEST, SHAPES_COUNT_WORDS = 0, 1, 2, 3, 4
+SHAPES_TRUNCATED, SHAPES_MALFORMED = 1, 2
+FEATURE_SHAPES = 2048
 
 
 class Options(C.Structure):
@@ -266,6 +274,12 @@ SIGNATURES = {
                                       _u32p, _u32p, _u32, _u32, _vp, _vp]),
     "infur_frame_sieve_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp, _vp,
                                           _u32p, _u32p, _u32, _u32, _vp, _vp]),
+    "infur_shapes": (C.c_int32, [_vp, _vp, _u32, _vp, _u32, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp]),
+    "infur_shapes_dev": (C.c_int32, [_vp, _vp, _u32, _vp, _u32, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp]),
+    "infur_frame_shapes": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp, _vp,
+                                       _u32p, _u32p, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _vp]),
+    "infur_frame_shapes_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp, _vp,
+                                           _u32p, _u32p, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _vp]),
     "infur_stream_create": (C.c_int32, [_vp, _u32, C.POINTER(_vp)]),
     "infur_stream_destroy": (None, [_vp]),
     "infur_stream_add_lane": (C.c_int32, [_vp, _vp]),

@@ -194,6 +194,9 @@ struct infur_ctx {
     // Adjacency and Sieve (infur_sieve.cpp): the accumulators, the pair table, the bitmap of first edges and the per-region state of
     // the rounds; the planes, labels and region table of the frame calls; the host-pointer calls' staging.  Private like the above.
     infur::Buf st_sieve, st_sieve_frame, st_sieve_io;
+    // Shapes (infur_shapes.cpp): the keep flags, ranks, hull ids and scan sums; the label plane and what Outlines leaves for Shapes
+    // inside the frame calls; the host-pointer calls' staging.  Private like the above.
+    infur::Buf st_shapes, st_shapes_plane, st_shapes_poly, st_shapes_io;
     // Tracks (infur_tracks.cpp): the live trackers of this context; infur_ctx_destroy releases their device memory and orphans them
     std::vector<infur_tracker*> trackers;
 

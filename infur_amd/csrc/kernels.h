@@ -443,6 +443,22 @@ hipError_t launch_simplify(const unsigned* loops, unsigned loops_rows_in, const 
                            unsigned W, unsigned tol16, void* scratch, unsigned* loops_out, unsigned loops_rows_out, unsigned* vertices_out,
                            unsigned vertex_rows_out, unsigned* counts_out, hipStream_t s);
 
+// Shapes (shapes.hip): per loop of launch_simplify's input its measures (AREA2, PERIMETER and five moment sums), its convex hull in
+// Simplify's output layout, the hull's area and the minimum rectangle over the hull's edges; per value the sums.  Outputs, each
+// optional: loops_rows_out records (OFFSET', COUNT', VALUE, START), vertex_rows_out hull vertex ids, shape_rows x kShapeWords
+// signed 64-bit words per loop, value_rows x kShapeWords per value (every row written) and counts_out[4] = {n_loops,
+// n_hull_vertices, status, largest COUNT'}.  scratch: shapes_scratch_bytes(loops_rows_in, vertex_rows_in) bytes.  Stream-ordered;
+// two memsets and at most 6 launches, no workgroup waits for another.  No value held in the input buffers takes a load or a
+// store outside the declared rows.
+constexpr int kShapeMeasures = 7;
+constexpr int kShapeWords = 12;
+constexpr int kShapesCountWords = 4;
+constexpr unsigned kShapesTruncated = 1u, kShapesMalformed = 2u;
+size_t shapes_scratch_bytes(size_t loops_rows, size_t vertex_rows);
+hipError_t launch_shapes(const unsigned* loops, unsigned loops_rows_in, const unsigned* vertices, unsigned vertex_rows_in, const unsigned* counts,
+                         unsigned W, void* scratch, unsigned* loops_out, unsigned loops_rows_out, unsigned* vertices_out, unsigned vertex_rows_out,
+                         long long* shapes, unsigned shape_rows, long long* values, unsigned value_rows, unsigned* counts_out, hipStream_t s);
+
 // Coverage (coverage.hip): Outlines' loops of an H x W plane (both in [1, 8191]) of 1- or 4-byte elements, simplified within
 // tol16 / 16 pixels so that neighbouring polygons still fit: the loops are cut at the plane's junctions and every arc between
 // two of them is simplified by a rule that does not depend on the direction of travel.  Inputs as launch_simplify's plus the

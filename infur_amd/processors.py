@@ -1643,6 +1643,123 @@ class Coverage(Processor):
         out.loops, out.vertices = _poly_slice(lo, vo, cout, cut=bool(out.status & (_lib.COVERAGE_TRUNCATED | _lib.COVERAGE_OVERFLOW)))
 
 
+class ShapesOut:
+    """``Shapes``' ``&mut Output``: what to produce (``loops_rows`` hull records, ``vertex_rows`` hull vertices, ``shape_rows`` per-loop
+    records and ``value_rows`` per-value rows at most; 0 = not wanted) and, after ``advance``, the results -- ``loops`` and
+    ``vertices``, the hulls in Outlines' layout; ``shapes`` [min(n_loops, shape_rows), ``_lib.SHAPE_WORDS``] int64 (columns
+    ``_lib.SHAPE_AREA2`` .. ``SHAPE_RECT_L``); ``values`` [value_rows, ``_lib.SHAPE_WORDS``] int64 (columns 8 .. 10 are
+    ``SHAPE_OUTER``, ``SHAPE_HOLES``, ``SHAPE_LOOP``), every row written -- and the counts ``n_loops``, ``n_vertices`` (hull
+    vertices), ``status`` (``_lib.SHAPES_TRUNCATED``: the input was cut off; ``SHAPES_MALFORMED``) and ``largest`` (the largest
+    COUNT')."""
+
+    def __init__(self, loops_rows: int = 1 << 16, vertex_rows: int = 1 << 20, shape_rows: int = 1 << 16, value_rows: int = 0):
+        self.loops_rows, self.vertex_rows, self.shape_rows, self.value_rows = loops_rows, vertex_rows, shape_rows, value_rows
+        self.loops = self.vertices = self.shapes = self.values = None
+        self.n_loops = self.n_vertices = self.status = self.largest = 0
+
+
+def _shape_rows(rows: int) -> Optional[np.ndarray]:
+    return np.empty((rows, _lib.SHAPE_WORDS), np.int64) if rows > 0 else None
+
+
+class Shapes(Processor):
+    """The descriptor stage behind Outlines: per loop the area, perimeter and moments, the convex hull and the minimum rectangle;
+    per value the sums.
+
+    No command (``control(None)``).  Input = ``(loops, vertices, counts, (h, w))`` as ``Outlines`` left them
+    (``Shapes.input_of(out, shape)``); Output = ``ShapesOut``.  ``outlines_polygons`` reads the hulls as it reads Outlines' loops;
+    ``shape_summary`` turns a row into floats.  Integers throughout, identical from run to run.
+    """
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+        self.dirty = True
+
+    @staticmethod
+    def input_of(out: "OutlinesOut", shape: tuple) -> tuple:
+        return out.loops, out.vertices, (out.n_loops, out.n_vertices), shape
+
+    def control(self, cmd=None) -> "Shapes":
+        return self
+
+    def is_dirty(self) -> bool:
+        return self.dirty
+
+    def advance(self, inp: tuple, out: ShapesOut) -> None:
+        self.dirty = False
+        loops, vertices, counts, (h, w) = inp
+        loops, vertices, cin = _poly_input(loops, vertices, counts)
+        lo, vo = _poly_alloc(out.loops_rows, len(loops), out.vertex_rows, len(vertices))
+        shapes, values = _shape_rows(min(int(out.shape_rows), len(loops))), _shape_rows(int(out.value_rows))
+        cout = np.zeros(_lib.SHAPES_COUNT_WORDS, np.uint32)
+        self.ctx.check(self.ctx.L.infur_shapes(self.ctx.h, _ptr_some(loops), len(loops), _ptr_some(vertices), len(vertices), cin.ctypes.data, h, w,
+                                               _ptr(lo), _poly_rows(lo), _ptr(vo), _poly_rows(vo), _ptr(shapes), _poly_rows(shapes), _ptr(values),
+                                               _poly_rows(values), cout.ctypes.data))
+        out.n_loops, out.n_vertices, out.status, out.largest = (int(v) for v in cout)
+        cut = bool(out.status & _lib.SHAPES_TRUNCATED)
+        out.loops, out.vertices = _poly_slice(lo, vo, cout, cut=cut)
+        out.shapes = shapes[:0 if cut else min(out.n_loops, len(shapes))] if shapes is not None else None
+        out.values = values
+
+
+def shape_summary(measures, rect=None, hull=None) -> dict:
+    """Floats on the host from the integers of Shapes.  ``measures``: a per-loop record or a per-value row (their first eight words
+    agree).  -> ``area`` (pixels), ``perimeter``, ``centroid`` (x, y) in pixel-centre coordinates, ``orientation`` (radians from
+    the x axis towards y, 1/2 atan2(2 mu11, mu20 - mu02)), ``major`` and ``minor`` (the axes of the ellipse with the same second
+    moments), ``eccentricity``, ``solidity`` (AREA2 / HULL_AREA2) and ``compactness`` (4 pi A / P^2; 1 for a disc in the continuum).
+    ``rect``: a per-loop record (for a value: ``shapes[row[SHAPE_LOOP]]``) adds ``rect_sides`` (along the edge, across it) and
+    ``rect_angle`` (of the edge); with ``hull`` as well, the xy [k, 2] of that loop's hull, also ``rect_centre`` in pixel-centre
+    coordinates.  The central moments are formed in exact integers and divided once.  None for a row without area."""
+    m = [int(v) for v in np.asarray(measures).reshape(-1)[:8]]
+    a2, per, m10, m01, m20, m02, m11, hull2 = m
+    if a2 == 0:
+        return None
+    mu20 = (3 * m20 * a2 - 2 * m10 * m10) / (36 * a2)
+    mu02 = (3 * m02 * a2 - 2 * m01 * m01) / (36 * a2)
+    mu11 = (3 * m11 * a2 - 4 * m10 * m01) / (72 * a2)
+    area = a2 / 2
+    root = float(np.hypot(mu20 - mu02, 2 * mu11))
+    big, small = (mu20 + mu02 + root) / (2 * area), max((mu20 + mu02 - root) / (2 * area), 0.0)
+    out = {"area": area, "perimeter": float(per), "centroid": (m10 / (3 * a2) - 0.5, m01 / (3 * a2) - 0.5),
+           "orientation": 0.5 * float(np.arctan2(2 * mu11, mu20 - mu02)), "major": 4 * float(np.sqrt(big)), "minor": 4 * float(np.sqrt(small)),
+           "eccentricity": float(np.sqrt(1 - small / big)) if big > 0 else 0.0, "solidity": a2 / hull2 if hull2 else None,
+           "compactness": 4 * float(np.pi) * abs(area) / (per * per) if per else None}
+    if rect is not None:
+        r = [int(v) for v in np.asarray(rect).reshape(-1)]
+        j, rw, rh, rl = (r[k] for k in (_lib.SHAPE_RECT_EDGE, _lib.SHAPE_RECT_W, _lib.SHAPE_RECT_H, _lib.SHAPE_RECT_L))
+        if rl:
+            out["rect_sides"] = (rw / float(np.sqrt(rl)), rh / float(np.sqrt(rl)))
+            if hull is not None:
+                xy = np.asarray(hull, np.float64).reshape(-1, 2)
+                e = xy[(j + 1) % len(xy)] - xy[j]
+                u = e / np.sqrt(rl)
+                n = np.array([-u[1], u[0]])
+                along, across = xy[:, 0] * u[0] + xy[:, 1] * u[1], xy[:, 0] * n[0] + xy[:, 1] * n[1]  # (elementwise: no layout-dependent summation)
+                c = u * (along.min() + along.max()) / 2 + n * (across.min() + across.max()) / 2 - 0.5
+                out["rect_angle"] = float(np.arctan2(e[1], e[0]))
+                out["rect_centre"] = (float(c[0]), float(c[1]))
+    return out
+
+
+class ShapesFrame(NamedTuple):
+    """``FramePath.advance_shapes``: ``RegionsFrame``'s fields, then the hull records and vertex ids in Outlines' layout, the
+    per-loop records [min(n_loops, shape_rows), 12] int64, the per-region rows [table_rows, 12] int64 (row i is region i), the
+    counts (n_loops, n_hull_vertices, status, largest COUNT') and the plane's (height, width)"""
+
+    klass: Optional[np.ndarray]
+    conf: Optional[np.ndarray]
+    labels: Optional[np.ndarray]
+    table: Optional[np.ndarray]
+    n_regions: Optional[int]
+    scaled: Optional[np.ndarray]
+    loops: Optional[np.ndarray]
+    vertices: Optional[np.ndarray]
+    shapes: Optional[np.ndarray]
+    values: Optional[np.ndarray]
+    counts: Optional[tuple]
+    shape: tuple
+
+
 class PolygonsFrame(NamedTuple):
     """``FramePath.advance_polygons``: ``OutlinesFrame`` with simplified loops, and the counts (n_loops, n_vertices, n_degenerate,
     status)"""
@@ -1781,6 +1898,36 @@ class FramePath:
         k = min(n.value, rows)
         return AnchorsFrame(klass, conf, labels, table[:k] if table is not None else None, n.value, scaled, dist2,
                             anchors[:k] if anchors is not None else None)
+
+    def advance_shapes(self, img: np.ndarray, factor: float = 1.0, decode: int = _lib.DECODE_RAW, connectivity: int = _lib.CONNECT_8,
+                       min_pixels: int = 0, flags: int = 0, table_rows: int = 1024, max_edges: int = 0, loops_rows: int = 1 << 16,
+                       vertex_rows: int = 1 << 20, shape_rows: int = 1 << 16, want_labels: bool = False, want_klass: bool = False,
+                       want_conf: bool = False, want_scaled: bool = False) -> ShapesFrame:
+        """The fused path with a descriptor per object, scale -> model -> Segments decode -> Regions -> Outlines of the label plane
+        -> Shapes, in one call -> ``ShapesFrame``; every result field is None when no model is loaded (``scaled`` is still
+        produced).  No dense plane crosses PCIe unless it is asked for."""
+        img, w, h, f, ow, oh = self._front(img, factor)
+        npix = oh.value * ow.value
+        rows = max(0, min(int(table_rows), npix))
+        klass, conf = self._plane(ow, oh, want_klass), self._plane(ow, oh, want_conf)
+        labels = self._plane(ow, oh, want_labels, np.uint32)
+        table = np.zeros((rows, _lib.REGION_WORDS), np.uint64) if rows else None
+        scaled = self._plane(ow, oh, want_scaled, channels=3)
+        lo, vo = _poly_alloc(loops_rows, npix, vertex_rows, 4 * npix)
+        shapes, values = _shape_rows(max(0, min(int(shape_rows), npix))), _shape_rows(rows)
+        counts = np.zeros(_lib.SHAPES_COUNT_WORDS, np.uint32)
+        n = C.c_uint32(0)
+        rc = self.ctx.L.infur_frame_shapes(self.ctx.h, img.ctypes.data, w, h, f, self.scale_mode, decode, connectivity, min_pixels, flags,
+                                           _ptr(klass), _ptr(conf), npix, _ptr(labels), npix * 4, _ptr(table), rows, C.addressof(n), _ptr(scaled),
+                                           C.byref(ow), C.byref(oh), max_edges, _ptr(lo), _poly_rows(lo), _ptr(vo), _poly_rows(vo), _ptr(shapes),
+                                           _poly_rows(shapes), _ptr(values), counts.ctypes.data)
+        shape = (oh.value, ow.value)
+        if not self._loaded(rc):
+            return ShapesFrame(None, None, None, None, None, scaled, None, None, None, None, None, shape)
+        k = min(n.value, rows)
+        lo, vo = _poly_slice(lo, vo, counts)
+        return ShapesFrame(klass, conf, labels, table[:k] if table is not None else None, n.value, scaled, lo, vo,
+                           shapes[:min(int(counts[0]), len(shapes))] if shapes is not None else None, values, tuple(int(v) for v in counts), shape)
 
     def advance_compare(self, img: np.ndarray, truth: np.ndarray, factor: float = 1.0, decode: int = _lib.DECODE_RAW,
                         ignore: Optional[int] = None, rows_a: Optional[int] = None, rows_b: Optional[int] = None, pair_slots: int = 0,

@@ -66,6 +66,14 @@ pixels_changed, status}``.  ``--labels-out``, ``--regions`` and ``--regions-out`
 ``--skip-background`` apply; the regions are those of the cleaned plane, none is dropped), ``"classes"`` is summarised from the
 cleaned class plane and the confidence plane as decoded.  ``--sieve`` is refused together with ``--min-pixels``, ``--tracks``,
 ``--runs-out``, ``--outlines-out``, ``--anchors`` and ``--truth``: those paths read planes this one does not leave on the device.
+
+``--shapes`` (needs ``--regions``) describes every object: the frame goes through ``infur_frame_shapes`` (scale -> model -> decode ->
+Regions -> Outlines of the label plane -> Shapes, all on the device), and every region record gains ``"shape"``, the
+``shape_summary`` of its row (area, perimeter, centroid, orientation, equivalent-ellipse axes, eccentricity, solidity,
+compactness, and the minimum rectangle of its largest outer loop: sides, angle, centre); every line gains ``"n_hull_vertices"``.
+``--hulls-out FILE`` (needs ``--shapes``) receives the convex hulls in the layout of ``--outlines-out``: per frame 4 u32 counts
+(n_loops, n_hull_vertices, status, largest), then n_loops x 4 u32, then n_hull_vertices u32.  ``--shapes`` is refused together
+with ``--sieve``, ``--tracks``, ``--runs-out``, ``--outlines-out``, ``--anchors`` and ``--truth``.
 """
 from __future__ import annotations
 
@@ -117,7 +125,18 @@ def main(argv=None) -> int:
     ap.add_argument("--truth-ignore", type=int, default=None, metavar="V", help="truth pixels of this value are not compared (needs --truth)")
     ap.add_argument("--sieve", type=int, default=None, metavar="N", help="merge regions of fewer than N pixels into their neighbours on the device")
     ap.add_argument("--sieve-rounds", type=int, default=None, metavar="R", help="at most R rounds of merging, 1 to 64 (needs --sieve)")
+    ap.add_argument("--shapes", action="store_true", help="add every region's shape descriptors (needs --regions)")
+    ap.add_argument("--hulls-out", default="", help="convex hulls: per frame 4 u32 counts, then n_loops x 4 u32, then n_hull_vertices u32 (needs --shapes)")
     a = ap.parse_args(argv)
+    if a.hulls_out and not a.shapes:
+        ap.error("--hulls-out needs --shapes")
+    if a.shapes:
+        if not a.regions:
+            ap.error("--shapes needs --regions")
+        for given, name in ((a.sieve is not None, "--sieve"), (a.tracks, "--tracks"), (a.runs_out, "--runs-out"), (a.outlines_out, "--outlines-out"),
+                            (a.anchors, "--anchors"), (a.truth, "--truth")):
+            if given:
+                ap.error(f"--shapes does not combine with {name}: the fused shapes call leaves no plane on the device for it")
     if a.sieve_rounds is not None and a.sieve is None:
         ap.error("--sieve-rounds needs --sieve")
     if a.sieve is not None and not 1 <= a.sieve <= 0xFFFFFFFF:
@@ -169,7 +188,7 @@ def main(argv=None) -> int:
     from . import _lib
     from .app import RawVideoSource, VideoProcError
     from .processors import (Compare, CompareOut, confusion_summary, sieve_summary, Context, Coverage, CoverageOut, FramePath, Model, ModelCmd, Outlines, OutlinesOut, Runs, RunsOut, SegmentsFrame, Simplify, SimplifyOut,
-                             class_summary, region_summary, tolerance_to_tol16, track_summary)
+                             class_summary, outlines_polygons, region_summary, shape_summary, tolerance_to_tol16, track_summary)
 
     tol16 = tolerance_to_tol16(a.outlines_tolerance) if a.outlines_tolerance is not None else None
 
@@ -202,7 +221,8 @@ def main(argv=None) -> int:
         classes = model.get_info().num_classes
         grader, total = Compare(ctx, ignore_b=a.truth_ignore), np.zeros((classes, classes), np.uint64)
     rpath = None
-    if a.regions and a.sieve is not None:
+    fhull = open(a.hulls_out, "wb") if a.hulls_out else None
+    if a.regions and (a.sieve is not None or a.shapes):
         flags = _lib.REGIONS_SKIP_BACKGROUND if a.skip_background else 0
     elif a.regions:
         oh, ow = _out_dims(ctx, a.width, a.height, a.scale)
@@ -224,6 +244,11 @@ def main(argv=None) -> int:
                                  max_rounds=a.sieve_rounds or 0, want_labels=freg is not None)
             s = SegmentsFrame(r.cleaned, r.conf, _class_stats(r.cleaned, r.conf, model.get_info().num_classes), None, None)
             labels, table, nreg = r.labels, r.table, r.n
+        elif a.shapes:  # scale -> model -> decode -> Regions -> Outlines of the label plane -> Shapes, in one call
+            r = fp.advance_shapes(img, a.scale, decode, a.connectivity, a.min_pixels, flags, table_rows=max(0, a.max_regions), loops_rows=1 << 32,
+                                  vertex_rows=1 << 32, shape_rows=1 << 32, want_labels=freg is not None, want_klass=True, want_conf=True)
+            s = SegmentsFrame(r.klass, r.conf, _class_stats(r.klass, r.conf, model.get_info().num_classes), None, None)
+            labels, table, nreg = r.labels, r.table, r.n_regions
         elif rpath is not None:
             s, labels, table, nreg = rpath.advance(img, decode, a.connectivity, a.min_pixels, flags, flab is not None or ftruth is not None, fconf is not None,
                                                    freg is not None, keep_labels=(fruns is not None and a.runs_plane == "labels") or foutl is not None or a.anchors)
@@ -285,6 +310,18 @@ def main(argv=None) -> int:
                 rec["regions"] = region_summary(table, nreg, ow, oh)
                 if freg is not None:
                     freg.write(memoryview(labels).cast("B"))
+        if a.shapes:
+            rec["n_regions"], rec["n_hull_vertices"] = nreg, r.counts[1]
+            rec["regions"] = region_summary(table, nreg, ow, oh)
+            hulls = outlines_polygons(r.loops, r.vertices, ow)
+            for region, row in zip(rec["regions"], r.values):
+                at = int(row[_lib.SHAPE_LOOP])
+                region["shape"] = shape_summary(row, r.shapes[at], hulls[at][2]) if 0 <= at < len(r.shapes) else None
+            if freg is not None:
+                freg.write(memoryview(labels).cast("B"))
+            if fhull is not None:
+                for part in (np.array(r.counts, np.uint32), r.loops, r.vertices):
+                    fhull.write(memoryview(np.ascontiguousarray(part)).cast("B"))
         if rpath is not None:
             rec["n_regions"] = nreg
             rec["regions"] = region_summary(table, nreg, ow, oh, anchors=anch) if a.anchors else region_summary(table, nreg, ow, oh)
@@ -322,7 +359,7 @@ def main(argv=None) -> int:
                               "classes": [{"klass": c["klass"], "name": c["name"], "iou": c["iou"]} for c in grade["classes"] if c["union"]],
                               "matrix": total.tolist()}) + "\n")
         ftruth.close()
-    for f in (flab, fconf, freg, ftrk, fruns, foutl, fdist, fst):
+    for f in (flab, fconf, freg, ftrk, fruns, foutl, fdist, fhull, fst):
         if f is not None:
             f.flush()
     el = time.perf_counter() - t0

@@ -267,6 +267,32 @@ pub const INFUR_SIEVE_TABLE_SHORT: u32 = 4;
 pub const INFUR_SIEVE_NONE: u32 = 0xFFFF_FFFF;
 /// bit of `infur_features()`: the Adjacency and Sieve calls below exist
 pub const INFUR_FEATURE_SIEVE: u32 = 1024;
+/// Shapes: the words of a per-loop record and of a per-value row (words 8 .. 10 differ), of the counts, the status bits
+pub const INFUR_SHAPE_AREA2: u32 = 0;
+pub const INFUR_SHAPE_PERIMETER: u32 = 1;
+pub const INFUR_SHAPE_M10_6: u32 = 2;
+pub const INFUR_SHAPE_M01_6: u32 = 3;
+pub const INFUR_SHAPE_M20_12: u32 = 4;
+pub const INFUR_SHAPE_M02_12: u32 = 5;
+pub const INFUR_SHAPE_M11_24: u32 = 6;
+pub const INFUR_SHAPE_HULL_AREA2: u32 = 7;
+pub const INFUR_SHAPE_RECT_EDGE: u32 = 8;
+pub const INFUR_SHAPE_RECT_W: u32 = 9;
+pub const INFUR_SHAPE_RECT_H: u32 = 10;
+pub const INFUR_SHAPE_RECT_L: u32 = 11;
+pub const INFUR_SHAPE_WORDS: u32 = 12;
+pub const INFUR_SHAPE_OUTER: u32 = 8;
+pub const INFUR_SHAPE_HOLES: u32 = 9;
+pub const INFUR_SHAPE_LOOP: u32 = 10;
+pub const INFUR_SHAPES_LOOPS: u32 = 0;
+pub const INFUR_SHAPES_VERTICES: u32 = 1;
+pub const INFUR_SHAPES_STATUS: u32 = 2;
+pub const INFUR_SHAPES_LARGEST: u32 = 3;
+pub const INFUR_SHAPES_COUNT_WORDS: u32 = 4;
+pub const INFUR_SHAPES_TRUNCATED: u32 = 1;
+pub const INFUR_SHAPES_MALFORMED: u32 = 2;
+/// bit of `infur_features()`: the Shapes calls below exist
+pub const INFUR_FEATURE_SHAPES: u32 = 2048;
 
 extern "C" {
     pub fn infur_abi_version() -> u32;
@@ -555,4 +581,27 @@ extern "C" {
                                  plane_capacity: usize, d_labels: *mut c_void, labels_capacity: usize, d_table: *mut c_void,
                                  table_rows: u32, d_n_regions: *mut c_void, d_scaled_bgr: *mut c_void, ow: *mut u32, oh: *mut u32,
                                  max_rounds: u32, pair_slots: u32, d_klass_out: *mut c_void, d_counts: *mut c_void) -> i32;
+    // Shapes: area, moments, convex hull and minimum rectangle per outline loop, and the frame path that ends in it.  The 64-bit
+    // words are signed (two's complement)
+    pub fn infur_shapes(c: *mut infur_ctx, loops: *const u32, loops_rows_in: u32, vertices: *const u32, vertex_rows_in: u32,
+                        counts: *const u32, h: u32, w: u32, loops_out: *mut u32, loops_rows_out: u32, vertices_out: *mut u32,
+                        vertex_rows_out: u32, shapes: *mut u64, shape_rows: u32, values: *mut u64, value_rows: u32,
+                        counts_out: *mut u32) -> i32;
+    pub fn infur_shapes_dev(c: *mut infur_ctx, d_loops: *const c_void, loops_rows_in: u32, d_vertices: *const c_void,
+                            vertex_rows_in: u32, d_counts: *const c_void, h: u32, w: u32, d_loops_out: *mut c_void,
+                            loops_rows_out: u32, d_vertices_out: *mut c_void, vertex_rows_out: u32, d_shapes: *mut c_void,
+                            shape_rows: u32, d_values: *mut c_void, value_rows: u32, d_counts_out: *mut c_void) -> i32;
+    pub fn infur_frame_shapes(c: *mut infur_ctx, bgr: *const u8, w: u32, h: u32, factor: f32, scale_mode: u32, decode: u32,
+                              connectivity: u32, min_pixels: u32, flags: u32, klass: *mut u8, conf: *mut u8, plane_capacity: usize,
+                              labels: *mut u32, labels_capacity: usize, table: *mut u64, table_rows: u32, n_regions: *mut u32,
+                              scaled_bgr: *mut u8, ow: *mut u32, oh: *mut u32, max_edges: u32, loops_out: *mut u32,
+                              loops_rows_out: u32, vertices_out: *mut u32, vertex_rows_out: u32, shapes: *mut u64, shape_rows: u32,
+                              values: *mut u64, counts_out: *mut u32) -> i32;
+    pub fn infur_frame_shapes_dev(c: *mut infur_ctx, d_bgr: *const c_void, w: u32, h: u32, factor: f32, scale_mode: u32, decode: u32,
+                                  connectivity: u32, min_pixels: u32, flags: u32, d_klass: *mut c_void, d_conf: *mut c_void,
+                                  plane_capacity: usize, d_labels: *mut c_void, labels_capacity: usize, d_table: *mut c_void,
+                                  table_rows: u32, d_n_regions: *mut c_void, d_scaled_bgr: *mut c_void, ow: *mut u32, oh: *mut u32,
+                                  max_edges: u32, d_loops_out: *mut c_void, loops_rows_out: u32, d_vertices_out: *mut c_void,
+                                  vertex_rows_out: u32, d_shapes: *mut c_void, shape_rows: u32, d_values: *mut c_void,
+                                  d_counts_out: *mut c_void) -> i32;
 }

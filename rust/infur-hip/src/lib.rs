@@ -1056,6 +1056,75 @@ impl Processor for HipSimplify {
     }
 }
 
+// ---------------------------------------------------------------- Shapes (hull, moments and rectangle per loop)
+/// What `HipShapes` produces: the hulls in `Outlines`' layout (`loops`, `vertices`), `shapes` with `INFUR_SHAPE_WORDS` signed words
+/// per loop (AREA2 .. RECT_L) and `values` with as many per value (words 8 .. 10: OUTER, HOLES, LOOP), every one of `value_rows`
+/// written; `status`: `INFUR_SHAPES_TRUNCATED` (the input was cut off), `INFUR_SHAPES_MALFORMED`; `largest`: the largest COUNT'.
+pub struct Shaped { pub loops_rows: usize, pub vertex_rows: usize, pub shape_rows: usize, pub value_rows: usize, pub n_loops: u32,
+                    pub n_vertices: u32, pub status: u32, pub largest: u32, pub loops: Vec<u32>, pub vertices: Vec<u32>, pub shapes: Vec<i64>,
+                    pub values: Vec<i64> }
+impl Default for Shaped {
+    fn default() -> Self {
+        Self { loops_rows: 1 << 16, vertex_rows: 1 << 20, shape_rows: 1 << 16, value_rows: 0, n_loops: 0, n_vertices: 0, status: 0, largest: 0,
+               loops: Vec::new(), vertices: Vec::new(), shapes: Vec::new(), values: Vec::new() }
+    }
+}
+impl Shaped {
+    pub fn shape_word(&self, l: usize, word: u32) -> i64 { self.shapes[l * sys::INFUR_SHAPE_WORDS as usize + word as usize] }
+    pub fn value_word(&self, v: usize, word: u32) -> i64 { self.values[v * sys::INFUR_SHAPE_WORDS as usize + word as usize] }
+}
+/// The descriptor stage behind `HipOutlines`; its input is `HipSimplify`'s.  No command.  Integer results, identical from run to run.
+pub struct HipShapes { ctx: Rc<Ctx>, dirty: bool }
+impl HipShapes {
+    pub fn new(ctx: Rc<Ctx>) -> Self { Self { ctx, dirty: true } }
+}
+impl Processor for HipShapes {
+    type Command = ();
+    type ControlError = HipError;
+    type Input = SimplifyInput;
+    type Output = Shaped;
+    type ProcessResult = Result<(), HipError>;
+
+    fn control(&mut self, _cmd: ()) -> Result<&mut Self, HipError> { Ok(self) }
+    fn is_dirty(&self) -> bool { self.dirty }
+    fn advance(&mut self, inp: &SimplifyInput, out: &mut Shaped) -> Result<(), HipError> {
+        self.dirty = false;
+        let [w, h] = inp.size;
+        let o = &inp.outlines;
+        let words = sys::INFUR_SHAPE_WORDS as usize;
+        let rows_in = o.loops.len() / sys::INFUR_LOOP_WORDS as usize;
+        let lrows = out.loops_rows.min(rows_in);
+        let vrows = out.vertex_rows.min(o.vertices.len());
+        let srows = out.shape_rows.min(rows_in);
+        out.loops.resize(lrows * sys::INFUR_LOOP_WORDS as usize, 0);
+        out.vertices.resize(vrows, 0);
+        out.shapes.resize(srows * words, 0);
+        out.values.resize(out.value_rows * words, 0);
+        let counts_in = [o.n_loops, o.n_vertices];
+        let mut counts = [0u32; 4];
+        let rc = unsafe {
+            sys::infur_shapes(self.ctx.0, if rows_in > 0 { o.loops.as_ptr() } else { std::ptr::null() }, rows_in as u32,
+                              if !o.vertices.is_empty() { o.vertices.as_ptr() } else { std::ptr::null() }, o.vertices.len() as u32,
+                              counts_in.as_ptr(), h as u32, w as u32,
+                              if lrows > 0 { out.loops.as_mut_ptr() } else { std::ptr::null_mut() }, lrows as u32,
+                              if vrows > 0 { out.vertices.as_mut_ptr() } else { std::ptr::null_mut() }, vrows as u32,
+                              if srows > 0 { out.shapes.as_mut_ptr() as *mut u64 } else { std::ptr::null_mut() }, srows as u32,
+                              if out.value_rows > 0 { out.values.as_mut_ptr() as *mut u64 } else { std::ptr::null_mut() }, out.value_rows as u32,
+                              counts.as_mut_ptr())
+        };
+        if rc != sys::INFUR_OK { return Err(HipError::from_ctx(&self.ctx, rc)); }
+        out.n_loops = counts[sys::INFUR_SHAPES_LOOPS as usize];
+        out.n_vertices = counts[sys::INFUR_SHAPES_VERTICES as usize];
+        out.status = counts[sys::INFUR_SHAPES_STATUS as usize];
+        out.largest = counts[sys::INFUR_SHAPES_LARGEST as usize];
+        let cut = out.status & sys::INFUR_SHAPES_TRUNCATED != 0;
+        out.loops.truncate(if cut { 0 } else { (out.n_loops as usize).min(lrows) } * sys::INFUR_LOOP_WORDS as usize);
+        out.vertices.truncate((out.n_vertices as usize).min(vrows));
+        out.shapes.truncate(if cut { 0 } else { (out.n_loops as usize).min(srows) } * words);
+        Ok(())
+    }
+}
+
 // ---------------------------------------------------------------- Coverage (shared borders simplified once)
 /// What `HipCoverage` produces, in `Outlines`' layout: `loops` holds `min(n_loops, loops_rows)` records (OFFSET', COUNT', VALUE,
 /// START), `vertices` the first `min(n_vertices, vertex_rows)` kept vertex ids; `n_degenerate` counts the loops with COUNT' < 3
