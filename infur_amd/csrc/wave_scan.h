@@ -39,8 +39,11 @@ __device__ __forceinline__ unsigned flag_rank(const bool flag, const unsigned bl
 }
 
 // One workgroup of kScanBlock lanes: partial[0, NB) -> its exclusive prefix sums in place; -> the total, in every thread.
-// More than kScanBlock sums take further passes of the loop: Runs' test_more_than_1024_block_sums and Regions' 1080p planes
-// execute them, also for Tracks, which no test can give the million regions its own second pass would need.
+// More than kScanBlock sums take further passes of the loop: Runs' test_more_than_1024_block_sums, Regions' 1080p planes,
+// Outlines' million-edge checkerboard and Simplify's comb execute them with sums in every pass; tests/test_gpu_stage_limits.py
+// executes them for Shapes' vertex scan and Coverage's scan over the augmented rows with zeros beyond the first pass (the carry
+// into the total).  They stand in for Tracks too, which no test can give the million regions its own second pass would need
+// (tests/stage_limits.py lists every such crossing and the test that reaches it).
 __device__ __forceinline__ unsigned scan_block_sums(unsigned* __restrict__ partial, const size_t NB, unsigned* wsum) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     unsigned carry = 0;
