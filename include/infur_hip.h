@@ -1324,6 +1324,80 @@ int32_t infur_frame_shapes_dev(infur_ctx* ctx, const void* d_bgr, uint32_t w, ui
                                uint32_t max_edges, void* d_loops_out, uint32_t loops_rows_out, void* d_vertices_out,
                                uint32_t vertex_rows_out, void* d_shapes, uint32_t shape_rows, void* d_values, void* d_counts_out);
 
+/* ---- Raster: polygon loops and run-length records filled back into a plane ----
+ * Every stage above turns a dense plane into something smaller; Raster goes the other way, on the device: the loops Outlines,
+ * Simplify, Coverage or Shapes (its hulls) left in device memory, or the records Runs left, become a class, label or track plane
+ * again, so that Compare can grade against ground truth that exists as polygons or run-length records, and so that what a
+ * tolerance costs can be counted in pixels.  Everything is an exact integer function of the input: identical bytes from run to
+ * run and no tolerance anywhere.  Raster(Outlines(plane)) == plane and RasterRuns(Runs(plane)) == plane, byte for byte, for any
+ * plane, connectivity and skip value (fill_value = skip_value).  Presence of this group is announced by infur_features() &
+ * INFUR_FEATURE_RASTER (INFUR_ABI_VERSION does not move).
+ *
+ * THE PLANE is h x w, both in 1 .. 8191 (otherwise INFUR_E_INVALID_ARG), of elem_bytes 1 or 4; fill_value > 255 on a byte plane is
+ * INFUR_E_INVALID_ARG.  Pixel (x, y) has its centre at (x + 1/2, y + 1/2).
+ * INPUT, LOOPS.  Simplify's exactly: `loops`, `vertices` and `counts` with loops_rows_in and vertex_rows_in; a NULL counts, or a
+ * NULL array with rows declared, is INFUR_E_INVALID_ARG.  A record (OFFSET, COUNT, VALUE, START) with lattice vertices v_0 ..
+ * v_{n-1}, v_n := v_0, is a closed polygon of value V.
+ * CROSSINGS.  Take a segment a -> b with y_a != y_b and each row y with min(y_a, y_b) <= y < max(y_a, y_b).  The segment crosses
+ * the centre line of that row at x* = x_a + (x_b - x_a)(2y + 1 - 2 y_a) / (2 (y_b - y_a)); the CROSSING COLUMN c is the smallest x
+ * with x + 1/2 >= x*: with the segment oriented so that dy > 0, c = ceil((num - dy) / (2 dy)), num = 2 x_0 dy + (x_1 - x_0)(2y + 1 -
+ * 2 y_0), clamped to 0 from below; a crossing with c >= w has no effect.  Horizontal segments contribute nothing.  Centres have
+ * half-integer y and vertices integer y: no vertex lies on a scan line.  The one tie, a centre exactly on a slanted segment, goes
+ * to the right-hand side for every loop alike, so a border two loops share with the same vertices gives each such pixel to
+ * exactly one of them.
+ * SIGN.  A segment heading north (y_b < y_a) adds +1 to the winding of the pixels x >= c of that row and +V to their value sum; a
+ * segment heading south adds -1 and -V.  This is Outlines' orientation: the pixel on the right hand, outer loops clockwise on a
+ * y-down screen, holes counter-clockwise.
+ * RESOLVE.  Pixel (x, y) then has a winding k and a value sum S modulo 2^32:
+ *   OUTSIDE    k = 0 and S = 0                                  fill_value is written
+ *   PAINTED    k = 1, and S <= 255 on a byte plane              S is written
+ *   CONFLICT   anything else                                    fill_value is written
+ * CONFLICT covers overlapping loops, a hole with no outer loop, crossed arcs, and a byte plane asked to hold more than 255.
+ * Three or more loops stacked so that k = 1 again (two outer loops and a hole, say) are PAINTED with their signed value sum: that
+ * is a property of the rule, not a defect.  There is no painter's order.
+ * INPUT, RUNS.  `runs` holds Runs' records (START, END, VALUE), runs_rows_in of them declared, n_runs of them there.  A record
+ * with START < END <= h*w and START / w == (END - 1) / w is +1, +V at START and -1, -V at END unless END is the end of its row:
+ * overlapping runs are CONFLICT, deterministically, not "whichever wrote last".  Any other record is skipped and sets MALFORMED.
+ * OUTPUTS, each optional (NULL = not wanted; neither wanted is INFUR_E_INVALID_ARG), neither needs initialisation; a rejected call
+ * touches no output: plane_out, h*w elements, every one written; counts_out, INFUR_RASTER_COUNT_WORDS uint32_t {n_loops (for
+ * runs: the number of records), PAINTED, CONFLICT, status}.  PAINTED + CONFLICT + the OUTSIDE pixels = h*w.
+ * STATUS.  INFUR_RASTER_TRUNCATED: counts[0] > loops_rows_in or counts[1] > vertex_rows_in (runs: n_runs > runs_rows_in).  Only
+ * counts_out is written, as {counts[0], 0, 0, INFUR_RASTER_TRUNCATED}; the plane is left alone.  INFUR_RASTER_MALFORMED: some
+ * loop record had COUNT < 2 or OFFSET + COUNT > counts[1], or some run record was not a run of one row; it was skipped.
+ * INFUR_RASTER_OUTSIDE: some vertex id had Y > h (X > w cannot be written as an id); it was clamped onto the lattice.  Every read
+ * is clamped to the rows the caller declared: no value held in the input buffers can take a load, a store or an atomic outside
+ * them, the library's scratch and the plane.
+ * EXAMPLE.  The diamond (4,0) (8,4) (4,8) (0,4) of value 7 on an 8 x 8 plane, fill 0: rows 0 .. 7 are painted from column 3, 2, 1,
+ * 0, 0, 1, 2, 3 up to but not including column 4, 5, 6, 7, 7, 6, 5, 4: every centre on the two left-hand sides belongs to the
+ * diamond, no centre on the two right-hand sides does, PAINTED = 32 = the area.
+ * COST.  8 bytes of accumulator per pixel, cleared on every call; one 64-bit atomic add per crossing (one per pixel side heading
+ * north or south: scattered, one address per row and segment); one pass over the accumulator that also writes the plane.
+ * WHAT IT DOES NOT DO.  No painter's order for overlapping instances, no anti-aliased coverage, no column-major COCO RLE, no frame,
+ * stream, batch or group call: the input is not a product of the frame, and the stage composes through the _dev calls. */
+enum { INFUR_RASTER_LOOPS = 0, INFUR_RASTER_PAINTED = 1, INFUR_RASTER_CONFLICT = 2, INFUR_RASTER_STATUS = 3, INFUR_RASTER_COUNT_WORDS = 4 };
+enum { INFUR_RASTER_TRUNCATED = 1, INFUR_RASTER_MALFORMED = 2, INFUR_RASTER_OUTSIDE = 4 };
+enum { INFUR_FEATURE_RASTER = 4096 };
+
+/* host pointers, with Simplify's copy rules: counts is read first, min(counts[0], loops_rows_in) records and min(counts[1],
+ * vertex_rows_in) vertices travel to the device; the plane comes back unless the status says INFUR_RASTER_TRUNCATED */
+int32_t infur_raster(infur_ctx* ctx, const uint32_t* loops, uint32_t loops_rows_in, const uint32_t* vertices,
+                     uint32_t vertex_rows_in, const uint32_t* counts, uint32_t h, uint32_t w, uint32_t elem_bytes,
+                     uint32_t fill_value, void* plane_out, uint32_t* counts_out);
+/* device pointers throughout; enqueued on the context's stream as one memset and at most 3 launches, a number fixed by the
+ * arguments: the call never synchronises, so its grid is sized by loops_rows_in -- declare the rows Outlines was given, not more.
+ * Capturable after one call outside the capture, which allocates the scratch: 8 bytes per pixel, owned by the context; it grows
+ * only with a larger plane than any before.  The outputs must not overlap the inputs. */
+int32_t infur_raster_dev(infur_ctx* ctx, const void* d_loops, uint32_t loops_rows_in, const void* d_vertices,
+                         uint32_t vertex_rows_in, const void* d_counts, uint32_t h, uint32_t w, uint32_t elem_bytes,
+                         uint32_t fill_value, void* d_plane_out, void* d_counts_out);
+/* the runs front end, host pointers: min(n_runs, runs_rows_in) records travel to the device */
+int32_t infur_raster_runs(infur_ctx* ctx, const uint32_t* runs, uint32_t runs_rows_in, uint32_t n_runs, uint32_t h, uint32_t w,
+                          uint32_t elem_bytes, uint32_t fill_value, void* plane_out, uint32_t* counts_out);
+/* device pointers throughout; d_n_runs is the device word Runs left (a NULL d_n_runs, or a NULL d_runs with rows declared, is
+ * INFUR_E_INVALID_ARG).  One memset and at most 3 launches, the grid sized by runs_rows_in; otherwise as infur_raster_dev. */
+int32_t infur_raster_runs_dev(infur_ctx* ctx, const void* d_runs, uint32_t runs_rows_in, const void* d_n_runs, uint32_t h,
+                              uint32_t w, uint32_t elem_bytes, uint32_t fill_value, void* d_plane_out, void* d_counts_out);
+
 /* ---- streaming (infur/src/main.rs:27-99,105): bounded queue, copies overlapped with compute ----
  * The reference back-pressures its producer with sync_channel(2) (main.rs:105); a stream
  * here is a ring of `depth` pinned + device slots.  submit() copies the caller's frame into a

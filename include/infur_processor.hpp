@@ -14,6 +14,7 @@
 // exactly where the reference reuses them.
 #pragma once
 #include <cstdint>
+#include <cstring>
 #include <optional>
 #include <string>
 #include <vector>
@@ -881,6 +882,81 @@ public:
 
 private:
     Context& c_;
+    bool dirty_ = true;
+};
+
+/// What `Raster` produces: `plane` holds height * width elements of elem_bytes bytes each (empty when the input was truncated);
+/// painted and conflict count the pixels exactly one loop claims and the pixels that were refused (overlapping loops, a hole
+/// alone, crossed arcs, a value a byte plane cannot hold: they read the fill value); status: INFUR_RASTER_TRUNCATED, _MALFORMED,
+/// _OUTSIDE; n: the loops or records read.
+struct RasterOut {
+    uint32_t width = 0, height = 0, elem_bytes = 1, n = 0, painted = 0, conflict = 0, status = 0;
+    std::vector<uint8_t> plane;
+    uint32_t at(uint32_t x, uint32_t y) const {
+        const size_t i = (size_t)y * width + x;
+        if (elem_bytes == 1) return plane[i];
+        uint32_t v;
+        std::memcpy(&v, plane.data() + i * 4, 4);
+        return v;
+    }
+};
+
+/// The stage that goes the other way: the loops of Outlines, Simplify, Coverage or Shapes (its hulls), or the records of Runs,
+/// filled back into a plane.  Winding 1 paints the loop's value; everything else reads the fill value.  Integer results,
+/// identical from run to run.  Command = the plane's element size and fill value; Input = an OutlinesOut or a RunsOut,
+/// Output = RasterOut.
+class Raster {
+public:
+    struct Cmd {
+        enum Kind { Fill } kind;
+        uint32_t elem_bytes, fill_value;
+    };
+    explicit Raster(Context& c) : c_(c) {}
+    Status control(Cmd cmd) {
+        if (cmd.kind != Cmd::Fill || (cmd.elem_bytes != 1 && cmd.elem_bytes != 4) || (cmd.elem_bytes == 1 && cmd.fill_value > 255))
+            return INFUR_E_INVALID_ARG;
+        dirty_ = dirty_ || cmd.elem_bytes != elem_bytes_ || cmd.fill_value != fill_value_;
+        elem_bytes_ = cmd.elem_bytes;
+        fill_value_ = cmd.fill_value;
+        return INFUR_OK;
+    }
+    bool is_dirty() const { return dirty_; }
+    Status advance(const OutlinesOut& in, RasterOut& out) {
+        begin(in.width, in.height, out);
+        const uint32_t rows_in = (uint32_t)(in.loops.size() / INFUR_LOOP_WORDS), verts_in = (uint32_t)in.vertices.size();
+        const uint32_t counts_in[2] = {in.n_loops, in.n_vertices};
+        uint32_t counts[INFUR_RASTER_COUNT_WORDS] = {0, 0, 0, 0};
+        const Status s = infur_raster(c_.get(), rows_in ? in.loops.data() : nullptr, rows_in, verts_in ? in.vertices.data() : nullptr, verts_in, counts_in,
+                                      in.height, in.width, elem_bytes_, fill_value_, out.plane.empty() ? nullptr : out.plane.data(), counts);
+        return end(s, counts, out);
+    }
+    Status advance(const RunsOut& in, RasterOut& out) {
+        begin(in.width, in.height, out);
+        const uint32_t rows_in = (uint32_t)(in.runs.size() / INFUR_RUN_WORDS);
+        uint32_t counts[INFUR_RASTER_COUNT_WORDS] = {0, 0, 0, 0};
+        const Status s = infur_raster_runs(c_.get(), rows_in ? in.runs.data() : nullptr, rows_in, in.n, in.height, in.width, elem_bytes_, fill_value_,
+                                           out.plane.empty() ? nullptr : out.plane.data(), counts);
+        return end(s, counts, out);
+    }
+
+private:
+    void begin(uint32_t w, uint32_t h, RasterOut& out) {
+        dirty_ = false;
+        out.width = w;
+        out.height = h;
+        out.elem_bytes = elem_bytes_;
+        out.plane.assign((size_t)w * h * elem_bytes_, 0);
+    }
+    static Status end(Status s, const uint32_t* counts, RasterOut& out) {
+        out.n = counts[INFUR_RASTER_LOOPS];
+        out.painted = counts[INFUR_RASTER_PAINTED];
+        out.conflict = counts[INFUR_RASTER_CONFLICT];
+        out.status = counts[INFUR_RASTER_STATUS];
+        if (out.status & INFUR_RASTER_TRUNCATED) out.plane.clear();
+        return s;
+    }
+    Context& c_;
+    uint32_t elem_bytes_ = 1, fill_value_ = 0;
     bool dirty_ = true;
 };
 

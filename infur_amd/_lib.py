@@ -114,6 +114,10 @@ SHAPE_OUTER, SHAPE_HOLES, SHAPE_LOOP = 8, 9, 10
 SHAPES_LOOPS, SHAPES_VERTICES, SHAPES_STATUS, SHAPES_LARGEST, SHAPES_COUNT_WORDS = 0, 1, 2, 3, 4
 SHAPES_TRUNCATED, SHAPES_MALFORMED = 1, 2
 FEATURE_SHAPES = 2048
+# Raster (infur_raster / infur_raster_runs): the words of the counts, the status bits, the feature bit
+RASTER_LOOPS, RASTER_PAINTED, RASTER_CONFLICT, RASTER_STATUS, RASTER_COUNT_WORDS = 0, 1, 2, 3, 4
+RASTER_TRUNCATED, RASTER_MALFORMED, RASTER_OUTSIDE = 1, 2, 4
+FEATURE_RASTER = 4096
 
 
 class Options(C.Structure):
@@ -280,6 +284,10 @@ SIGNATURES = {
                                        _u32p, _u32p, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _vp]),
     "infur_frame_shapes_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp, _vp,
                                            _u32p, _u32p, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _vp]),
+    "infur_raster": (C.c_int32, [_vp, _vp, _u32, _vp, _u32, _vp, _u32, _u32, _u32, _u32, _vp, _vp]),
+    "infur_raster_dev": (C.c_int32, [_vp, _vp, _u32, _vp, _u32, _vp, _u32, _u32, _u32, _u32, _vp, _vp]),
+    "infur_raster_runs": (C.c_int32, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp]),
+    "infur_raster_runs_dev": (C.c_int32, [_vp, _vp, _u32, _vp, _u32, _u32, _u32, _u32, _vp, _vp]),
     "infur_stream_create": (C.c_int32, [_vp, _u32, C.POINTER(_vp)]),
     "infur_stream_destroy": (None, [_vp]),
     "infur_stream_add_lane": (C.c_int32, [_vp, _vp]),

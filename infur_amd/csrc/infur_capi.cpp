@@ -1154,7 +1154,7 @@ void infur_ctx_destroy(infur_ctx* c) {
                    &c->st_reg_io, &c->st_runs, &c->st_runs_plane, &c->st_runs_io, &c->st_outl, &c->st_outl_plane, &c->st_outl_io,
                    &c->st_simp, &c->st_simp_io, &c->st_poly, &c->st_cov, &c->st_cov_io, &c->st_anch, &c->st_anch_plane, &c->st_anch_io,
                    &c->st_cmp, &c->st_cmp_plane, &c->st_cmp_io, &c->st_sieve, &c->st_sieve_frame, &c->st_sieve_io, &c->st_shapes,
-                   &c->st_shapes_plane, &c->st_shapes_poly, &c->st_shapes_io})
+                   &c->st_shapes_plane, &c->st_shapes_poly, &c->st_shapes_io, &c->st_raster, &c->st_raster_io})
         if (b->p) (void)hipFree(b->p);
     prof_reset(c);
     for (auto e : c->ev_free) (void)hipEventDestroy(e);

@@ -197,6 +197,9 @@ struct infur_ctx {
     // Shapes (infur_shapes.cpp): the keep flags, ranks, hull ids and scan sums; the label plane and what Outlines leaves for Shapes
     // inside the frame calls; the host-pointer calls' staging.  Private like the above.
     infur::Buf st_shapes, st_shapes_plane, st_shapes_poly, st_shapes_io;
+    // Raster (infur_raster.cpp): the head words and one 64-bit accumulator word per pixel; the host-pointer calls' staging.  Private
+    // like the above.
+    infur::Buf st_raster, st_raster_io;
     // Tracks (infur_tracks.cpp): the live trackers of this context; infur_ctx_destroy releases their device memory and orphans them
     std::vector<infur_tracker*> trackers;
 

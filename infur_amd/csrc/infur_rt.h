@@ -14,6 +14,7 @@
 //   infur_anchors.cpp       Anchors (distance transform of a class, label or track plane, one interior point per value): C entry points
 //   infur_compare.cpp       Compare (confusion matrix and best partner per value between two planes): C entry points
 //   infur_shapes.cpp        Shapes (area, moments, convex hull and minimum rectangle per outline loop, sums per value): C entry points
+//   infur_raster.cpp        Raster (polygon loops or run-length records filled back into a plane, with the pixels no loop or several claim): C entry points
 //   infur_sieve.cpp         Adjacency (which values of a plane touch, along how many edges) and Sieve (speckle regions merged into their neighbours): C entry points
 // (infur_egress.h, beside this header: what the last four share -- the argument checks with their messages, the read-back of a
 //  polygon stage, the host-pointer frame wrapper and the front halves of the _dev frame calls)

@@ -66,7 +66,8 @@ const char* const kVocNames[21] = {"__background__", "aeroplane", "bicycle", "bi
 extern "C" {
 
 uint32_t infur_features(void) { return INFUR_FEATURE_SEGMENTS | INFUR_FEATURE_REGIONS | INFUR_FEATURE_TRACKS | INFUR_FEATURE_RUNS | INFUR_FEATURE_OUTLINES |
-           INFUR_FEATURE_SIMPLIFY | INFUR_FEATURE_COVERAGE | INFUR_FEATURE_TRACK_MEMORY | INFUR_FEATURE_ANCHORS | INFUR_FEATURE_COMPARE | INFUR_FEATURE_SIEVE | INFUR_FEATURE_SHAPES;
+           INFUR_FEATURE_SIMPLIFY | INFUR_FEATURE_COVERAGE | INFUR_FEATURE_TRACK_MEMORY | INFUR_FEATURE_ANCHORS | INFUR_FEATURE_COMPARE | INFUR_FEATURE_SIEVE | INFUR_FEATURE_SHAPES |
+           INFUR_FEATURE_RASTER;
 }
 
 const char* infur_voc_class_name(uint32_t k) { return k < 21 ? kVocNames[k] : nullptr; }

@@ -459,6 +459,20 @@ hipError_t launch_shapes(const unsigned* loops, unsigned loops_rows_in, const un
                          unsigned W, void* scratch, unsigned* loops_out, unsigned loops_rows_out, unsigned* vertices_out, unsigned vertex_rows_out,
                          long long* shapes, unsigned shape_rows, long long* values, unsigned value_rows, unsigned* counts_out, hipStream_t s);
 
+// Raster (raster.hip): the way back -- launch_simplify's input (loops of any polygon stage), or launch_runs' records, filled into an
+// H x W plane (both in [1, 8191]) of 1- or 4-byte elements.  A pixel inside exactly one loop (winding 1) reads that loop's VALUE,
+// a pixel inside none reads fill_value, every other pixel is a CONFLICT and reads fill_value.  Outputs, each optional: the plane
+// (every pixel written) and counts_out[4] = {n_loops or n_runs, painted, conflict, status}.  scratch: raster_scratch_bytes(H * W)
+// bytes.  Stream-ordered; one memset and at most 3 launches, no workgroup waits for another.  No value held in the input buffers
+// takes a load, a store or an atomic outside the declared rows, the scratch and the plane.
+constexpr int kRasterCountWords = 4;
+constexpr unsigned kRasterTruncated = 1u, kRasterMalformed = 2u, kRasterOutside = 4u;
+size_t raster_scratch_bytes(size_t npix);
+hipError_t launch_raster(const unsigned* loops, unsigned loops_rows_in, const unsigned* vertices, unsigned vertex_rows_in, const unsigned* counts,
+                         unsigned H, unsigned W, int elem_bytes, unsigned fill_value, void* scratch, void* plane, unsigned* counts_out, hipStream_t s);
+hipError_t launch_raster_runs(const unsigned* runs, unsigned runs_rows_in, const unsigned* d_n, unsigned H, unsigned W, int elem_bytes,
+                              unsigned fill_value, void* scratch, void* plane, unsigned* counts_out, hipStream_t s);
+
 // Coverage (coverage.hip): Outlines' loops of an H x W plane (both in [1, 8191]) of 1- or 4-byte elements, simplified within
 // tol16 / 16 pixels so that neighbouring polygons still fit: the loops are cut at the plane's junctions and every arc between
 // two of them is simplified by a rule that does not depend on the direction of travel.  Inputs as launch_simplify's plus the

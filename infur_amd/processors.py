@@ -1643,6 +1643,139 @@ class Coverage(Processor):
         out.loops, out.vertices = _poly_slice(lo, vo, cout, cut=bool(out.status & (_lib.COVERAGE_TRUNCATED | _lib.COVERAGE_OVERFLOW)))
 
 
+class RasterCmd(NamedTuple):
+    """``Raster``'s command: the plane's element type (``np.uint8`` or ``np.uint32``) and the value of the pixels no loop paints"""
+
+    dtype: type = np.uint8
+    fill_value: int = 0
+
+
+class RasterOut:
+    """``Raster``'s ``&mut Output``: what to produce (``want_plane``) and, after ``advance``, the results -- ``plane`` [h, w] of the
+    command's dtype (None when not wanted or when the input was truncated) and the counts ``n`` (loops or records read),
+    ``painted`` (pixels exactly one loop claims), ``conflict`` (pixels that were refused and read the fill value: overlapping
+    loops, a hole alone, crossed arcs, a value a byte plane cannot hold) and ``status`` (``_lib.RASTER_TRUNCATED``,
+    ``RASTER_MALFORMED``, ``RASTER_OUTSIDE``)."""
+
+    def __init__(self, want_plane: bool = True):
+        self.want_plane = want_plane
+        self.plane = None
+        self.n = self.painted = self.conflict = self.status = 0
+
+
+class Raster(Processor):
+    """The stage that goes the other way: the loops of Outlines, Simplify, Coverage or Shapes (its hulls), or the records of Runs,
+    filled back into a plane.  A pixel of winding 1 reads its loop's value, every other pixel the fill value.
+
+    Command = ``RasterCmd``.  Input = ``(loops, vertices, counts, (h, w))`` (``Simplify.input_of``) or ``(runs, n, (h, w))``;
+    Output = ``RasterOut``.  ``Raster(Outlines(plane)) == plane`` and ``Raster(Runs(plane)) == plane`` with the fill value = the
+    skipped value.  Integers throughout, identical from run to run.
+    """
+
+    def __init__(self, ctx: Context, dtype=np.uint8, fill_value: int = 0):
+        self.ctx = ctx
+        self.dtype, self.fill_value = np.dtype(np.uint8), 0
+        self.dirty = True
+        self.control(RasterCmd(dtype, fill_value))
+
+    def control(self, cmd: RasterCmd) -> "Raster":
+        dtype = np.dtype(cmd.dtype)
+        if dtype not in (np.dtype(np.uint8), np.dtype(np.uint32)):
+            raise InfurError(_lib.E_INVALID_ARG, f"dtype {dtype}: uint8 or uint32")
+        if not 0 <= cmd.fill_value <= (255 if dtype.itemsize == 1 else 0xFFFFFFFF):
+            raise InfurError(_lib.E_INVALID_ARG, f"fill_value {cmd.fill_value}: a {dtype} plane cannot hold it")
+        self.dirty = self.dirty or (dtype, cmd.fill_value) != (self.dtype, self.fill_value)
+        self.dtype, self.fill_value = dtype, int(cmd.fill_value)
+        return self
+
+    def is_dirty(self) -> bool:
+        return self.dirty
+
+    def advance(self, inp: tuple, out: RasterOut) -> None:
+        self.dirty = False
+        (h, w) = inp[-1]
+        plane = np.empty((h, w), self.dtype) if out.want_plane else None
+        cout = np.zeros(_lib.RASTER_COUNT_WORDS, np.uint32)
+        if len(inp) == 4:
+            loops, vertices, cin = _poly_input(*inp[:3])
+            rc = self.ctx.L.infur_raster(self.ctx.h, _ptr_some(loops), len(loops), _ptr_some(vertices), len(vertices), cin.ctypes.data, h, w,
+                                         self.dtype.itemsize, self.fill_value, _ptr(plane), cout.ctypes.data)
+        else:
+            runs = np.ascontiguousarray(inp[0] if inp[0] is not None else np.zeros((0, _lib.RUN_WORDS)), np.uint32).reshape(-1, _lib.RUN_WORDS)
+            rc = self.ctx.L.infur_raster_runs(self.ctx.h, _ptr_some(runs), len(runs), int(inp[1]), h, w, self.dtype.itemsize, self.fill_value,
+                                              _ptr(plane), cout.ctypes.data)
+        self.ctx.check(rc)
+        out.n, out.painted, out.conflict, out.status = (int(v) for v in cout)
+        out.plane = None if out.status & _lib.RASTER_TRUNCATED else plane
+
+
+def polygon_fidelity(ctx: Context, plane: np.ndarray, tol16: int, shared: bool = False, connectivity: int = 4, skip: Optional[int] = None,
+                     rows: int = 21) -> dict:
+    """What a tolerance costs, in pixels: Outlines -> Simplify (``shared=False``) or Coverage (``shared=True``) at ``tol16`` -> Raster
+    -> Compare against ``plane`` itself, all through the ``_dev`` calls on device buffers: the plane goes up once and a few dozen
+    words come back.  ``skip``: the value that belongs to no region (Outlines' and Coverage's SKIP); it is Raster's fill value.
+    Without one the fill value is the largest the plane's type holds, which the plane should not use.  A diagnostic: every call
+    allocates and frees its twelve device buffers (about 48 bytes per pixel, 100 MB at 1080p) and synchronises once.  ``rows``: the values the
+    confusion matrix has room for.  ->
+
+    * ``vertices_in``, ``vertices_out``: the vertices Outlines wrote and the stage behind it kept;
+    * ``changed``: the pixels of the re-filled plane that differ from ``plane``;
+    * ``conflict``: the pixels several polygons claim, or a hole alone, or crossed arcs (Raster's CONFLICT);
+    * ``uncovered``: the pixels no polygon claims beyond those ``plane`` skips (Raster's OUTSIDE pixels less the skipped ones: a
+      skipped pixel that a simplified polygon paints counts against it);
+    * ``pixel_accuracy``, ``miou``: ``confusion_summary`` of the matrix plane (rows) against re-filled plane (columns).  A pixel
+      that reads the fill value lies outside the matrix when the fill value is at or above ``rows``: the two measures are then
+      over the painted pixels alone, and ``changed`` is the figure that counts every pixel."""
+    plane = np.ascontiguousarray(plane)
+    if plane.ndim != 2 or plane.dtype not in (np.dtype(np.uint8), np.dtype(np.uint32)) or not plane.size:
+        raise InfurError(_lib.E_SHAPE, f"expected a non-empty [H,W] plane of uint8 or uint32, got {plane.shape} {plane.dtype}")
+    L, h, w, elem = ctx.L, plane.shape[0], plane.shape[1], plane.dtype.itemsize
+    npix = h * w
+    flags = _outlines_flags(skip, connectivity)
+    fill = int(skip) if skip is not None else (255 if elem == 1 else 0xFFFFFFFF)
+    most_v = 4 * npix + (w + 1) * (h + 1)  # Coverage adds the lattice's junctions
+    sizes = {"plane": plane.nbytes, "loops": npix * 16, "vertices": 4 * npix * 4, "counts": 16, "loops2": npix * 16, "vertices2": most_v * 4,
+             "counts2": 32, "filled": plane.nbytes, "rcounts": 16, "matrix": max(rows * rows, 1) * 4, "ccounts": _lib.COMPARE_COUNT_WORDS * 4,
+             "icounts": _lib.COMPARE_COUNT_WORDS * 4}
+    d = {}
+    try:
+        for name, n in sizes.items():
+            p = C.c_void_p(None)
+            ctx.check(L.infur_dev_alloc(ctx.h, n, C.byref(p)))
+            d[name] = p
+        ctx.check(L.infur_memcpy_h2d(ctx.h, d["plane"], plane.ctypes.data, plane.nbytes))
+        ctx.check(L.infur_outlines_dev(ctx.h, d["plane"], elem, h, w, flags, skip or 0, 0, d["loops"], npix, d["vertices"], 4 * npix, d["counts"]))
+        if shared:
+            ctx.check(L.infur_coverage_dev(ctx.h, d["plane"], elem, h, w, _lib.COVERAGE_SKIP if skip is not None else 0, skip or 0, d["loops"], npix,
+                                           d["vertices"], 4 * npix, d["counts"], tol16, 0, d["loops2"], npix, d["vertices2"], most_v, d["counts2"]))
+        else:
+            ctx.check(L.infur_simplify_dev(ctx.h, d["loops"], npix, d["vertices"], 4 * npix, d["counts"], h, w, tol16, d["loops2"], npix,
+                                           d["vertices2"], most_v, d["counts2"]))
+        ctx.check(L.infur_raster_dev(ctx.h, d["loops2"], npix, d["vertices2"], most_v, d["counts2"], h, w, elem, fill, d["filled"], d["rcounts"]))
+        ctx.check(L.infur_compare_dev(ctx.h, d["plane"], elem, d["filled"], elem, h, w, 0, 0, 0, d["matrix"] if rows else None, rows, rows, None, None,
+                                      d["ccounts"], 0))
+        ctx.check(L.infur_compare_dev(ctx.h, d["plane"], elem, d["filled"], elem, h, w, _lib.COMPARE_IGNORE_A if skip is not None else 0, skip or 0, 0,
+                                      None, 0, 0, None, None, d["icounts"], 0))
+        ctx.synchronize()
+
+        def words(name, n):
+            out = np.empty(n, np.uint32)
+            ctx.check(L.infur_memcpy_d2h(ctx.h, out.ctypes.data, d[name], out.nbytes))
+            return out
+
+        cin, cout, rc = words("counts", 3), words("counts2", 4), words("rcounts", 4)
+        cc, ic = words("ccounts", _lib.COMPARE_COUNT_WORDS), words("icounts", _lib.COMPARE_COUNT_WORDS)
+        matrix = words("matrix", rows * rows).reshape(rows, rows) if rows else np.zeros((0, 0), np.uint32)
+    finally:
+        for p in d.values():
+            L.infur_dev_free(ctx.h, p)
+    summary = confusion_summary(matrix, names=lambda k: None)
+    painted, conflict = int(rc[_lib.RASTER_PAINTED]), int(rc[_lib.RASTER_CONFLICT])
+    return {"vertices_in": int(cin[1]), "vertices_out": int(cout[1]), "changed": int(cc[_lib.COMPARE_COMPARED]) - int(cc[_lib.COMPARE_EQUAL]),
+            "conflict": conflict, "uncovered": npix - painted - conflict - int(ic[_lib.COMPARE_IGNORED]), "status": int(rc[_lib.RASTER_STATUS]),
+            "pixel_accuracy": summary["pixel_accuracy"], "miou": summary["miou"]}
+
+
 class ShapesOut:
     """``Shapes``' ``&mut Output``: what to produce (``loops_rows`` hull records, ``vertex_rows`` hull vertices, ``shape_rows`` per-loop
     records and ``value_rows`` per-value rows at most; 0 = not wanted) and, after ``advance``, the results -- ``loops`` and

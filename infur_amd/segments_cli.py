@@ -74,6 +74,15 @@ compactness, and the minimum rectangle of its largest outer loop: sides, angle, 
 ``--hulls-out FILE`` (needs ``--shapes``) receives the convex hulls in the layout of ``--outlines-out``: per frame 4 u32 counts
 (n_loops, n_hull_vertices, status, largest), then n_loops x 4 u32, then n_hull_vertices u32.  ``--shapes`` is refused together
 with ``--sieve``, ``--tracks``, ``--runs-out``, ``--outlines-out``, ``--anchors`` and ``--truth``.
+
+``--outlines-fidelity`` (needs ``--outlines-tolerance``; ``--outlines-out`` is then optional) says what the tolerance costs in pixels:
+the class plane goes through ``polygon_fidelity`` -- Outlines -> Simplify (or Coverage with ``--outlines-shared``) -> Raster -> Compare
+against the plane itself, all on the device -- and every line gains ``"polygon_fidelity": {vertices_in, vertices_out, changed,
+conflict, uncovered, status, pixel_accuracy, miou}``; a last line carries the totals over the frames.  It is refused together with
+``--regions``, ``--tracks`` and ``--sieve``: it grades the class plane.  It is a diagnostic, not a fast path: it needs no output
+file of its own, with ``--outlines-out`` the Outlines and Simplify or Coverage chain runs twice per frame (once for the file, once
+inside ``polygon_fidelity``), and ``polygon_fidelity`` allocates and frees its twelve device buffers on every frame, about 100 MB
+at 1080p.
 """
 from __future__ import annotations
 
@@ -125,6 +134,8 @@ def main(argv=None) -> int:
     ap.add_argument("--truth-ignore", type=int, default=None, metavar="V", help="truth pixels of this value are not compared (needs --truth)")
     ap.add_argument("--sieve", type=int, default=None, metavar="N", help="merge regions of fewer than N pixels into their neighbours on the device")
     ap.add_argument("--sieve-rounds", type=int, default=None, metavar="R", help="at most R rounds of merging, 1 to 64 (needs --sieve)")
+    ap.add_argument("--outlines-fidelity", action="store_true",
+                    help="add what the tolerance costs in pixels: the polygons filled back into a plane and compared with the class plane (needs --outlines-tolerance)")
     ap.add_argument("--shapes", action="store_true", help="add every region's shape descriptors (needs --regions)")
     ap.add_argument("--hulls-out", default="", help="convex hulls: per frame 4 u32 counts, then n_loops x 4 u32, then n_hull_vertices u32 (needs --shapes)")
     a = ap.parse_args(argv)
@@ -178,8 +189,12 @@ def main(argv=None) -> int:
     if a.outlines_skip is not None and not 0 <= a.outlines_skip <= (0xFFFFFFFF if a.regions else 255):
         ap.error("--outlines-skip: a value of the plane (a byte for the class plane, a u32 for the label plane)")
 
-    if a.outlines_tolerance is not None and not a.outlines_out:
-        ap.error("--outlines-tolerance needs --outlines-out")
+    if a.outlines_fidelity and a.outlines_tolerance is None:
+        ap.error("--outlines-fidelity needs --outlines-tolerance")
+    if a.outlines_fidelity and (a.regions or a.sieve is not None):
+        ap.error("--outlines-fidelity does not combine with --regions, --tracks or --sieve: it grades the class plane")
+    if a.outlines_tolerance is not None and not a.outlines_out and not a.outlines_fidelity:
+        ap.error("--outlines-tolerance needs --outlines-out or --outlines-fidelity")
     if a.outlines_tolerance is not None and not 0 <= a.outlines_tolerance * 16 + 0.5 < 65536:
         ap.error("--outlines-tolerance: 0 to 4095.9 pixels")
 
@@ -188,7 +203,7 @@ def main(argv=None) -> int:
     from . import _lib
     from .app import RawVideoSource, VideoProcError
     from .processors import (Compare, CompareOut, confusion_summary, sieve_summary, Context, Coverage, CoverageOut, FramePath, Model, ModelCmd, Outlines, OutlinesOut, Runs, RunsOut, SegmentsFrame, Simplify, SimplifyOut,
-                             class_summary, outlines_polygons, region_summary, shape_summary, tolerance_to_tol16, track_summary)
+                             class_summary, outlines_polygons, polygon_fidelity, region_summary, shape_summary, tolerance_to_tol16, track_summary)
 
     tol16 = tolerance_to_tol16(a.outlines_tolerance) if a.outlines_tolerance is not None else None
 
@@ -231,6 +246,7 @@ def main(argv=None) -> int:
                              runs=fruns is not None, outlines=foutl is not None, simplify=tol16 is not None, shared=a.outlines_shared,
                              anchors=a.anchors)
         flags = _lib.REGIONS_SKIP_BACKGROUND if a.skip_background else 0
+    fid_total = {k: 0 for k in ("vertices_in", "vertices_out", "changed", "conflict", "uncovered")}
     n, t0 = 0, time.perf_counter()
     while True:
         try:
@@ -260,18 +276,18 @@ def main(argv=None) -> int:
                 outl = rpath.outlines(a.outlines_skip, a.connectivity, tol16, a.outlines_shared)
             if a.anchors:
                 anch, dist2 = rpath.anchors(fdist is not None)
-        elif foutl is not None and fruns is None and flab is None and fconf is None and ftruth is None:  # polygons, counts and captions: no dense plane
+        elif foutl is not None and fruns is None and flab is None and fconf is None and ftruth is None and not a.outlines_fidelity:  # polygons, counts and captions: no dense plane
             if tol16 is None:
                 r = fp.advance_outlines(img, a.scale, decode, skip=a.outlines_skip, connectivity=a.connectivity, loops_rows=1 << 32, vertex_rows=1 << 32)
             else:
                 fused = fp.advance_coverage if a.outlines_shared else fp.advance_polygons
                 r = fused(img, a.scale, decode, tol16, skip=a.outlines_skip, connectivity=a.connectivity, loops_rows=1 << 32, vertex_rows=1 << 32)
             s, outl = SegmentsFrame(None, None, r.stats, None, None), (np.array(r.counts[:3], np.uint32), r.loops, r.vertices)
-        elif fruns is not None and flab is None and fconf is None and foutl is None and ftruth is None:  # records, count and captions: no dense plane comes back
+        elif fruns is not None and flab is None and fconf is None and foutl is None and ftruth is None and not a.outlines_fidelity:  # records, count and captions: no dense plane comes back
             r = fp.advance_runs(img, a.scale, decode, skip=a.runs_skip, runs_rows=1 << 32, want_row_start=False)
             s, runs, nruns = SegmentsFrame(None, None, r.stats, None, None), r.runs, r.n
         else:
-            s = fp.advance_segments(img, a.scale, decode, want_klass=flab is not None or fruns is not None or foutl is not None or ftruth is not None, want_conf=fconf is not None)
+            s = fp.advance_segments(img, a.scale, decode, want_klass=flab is not None or fruns is not None or foutl is not None or ftruth is not None or a.outlines_fidelity, want_conf=fconf is not None)
             if foutl is not None:  # the class plane is on the host anyway
                 oo = OutlinesOut(loops_rows=1 << 32, vertex_rows=1 << 32)
                 Outlines(ctx, skip=a.outlines_skip, connectivity=a.connectivity).advance(s.klass, oo)
@@ -302,6 +318,12 @@ def main(argv=None) -> int:
             total += graded.matrix
             grade = confusion_summary(graded.matrix)
             rec["pixel_accuracy"], rec["miou"] = grade["pixel_accuracy"], grade["miou"]
+        if a.outlines_fidelity:  # the class plane is on the host anyway
+            fid_rec = polygon_fidelity(ctx, s.klass, tol16, shared=a.outlines_shared, connectivity=a.connectivity, skip=a.outlines_skip,
+                                       rows=model.get_info().num_classes)
+            rec["polygon_fidelity"] = fid_rec
+            for k in fid_total:
+                fid_total[k] += fid_rec[k]
         if a.sieve is not None:
             sv = sieve_summary(r.counts)
             rec["sieve"] = {k: sv[k] for k in ("small", "absorbed", "stranded", "rounds", "pixels_changed", "status")}
@@ -359,6 +381,8 @@ def main(argv=None) -> int:
                               "classes": [{"klass": c["klass"], "name": c["name"], "iou": c["iou"]} for c in grade["classes"] if c["union"]],
                               "matrix": total.tolist()}) + "\n")
         ftruth.close()
+    if a.outlines_fidelity:
+        fst.write(json.dumps({"frames": n, "polygon_fidelity": fid_total}) + "\n")
     for f in (flab, fconf, freg, ftrk, fruns, foutl, fdist, fhull, fst):
         if f is not None:
             f.flush()

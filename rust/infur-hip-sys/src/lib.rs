@@ -293,6 +293,17 @@ pub const INFUR_SHAPES_TRUNCATED: u32 = 1;
 pub const INFUR_SHAPES_MALFORMED: u32 = 2;
 /// bit of `infur_features()`: the Shapes calls below exist
 pub const INFUR_FEATURE_SHAPES: u32 = 2048;
+/// Raster: the words of the counts, the status bits
+pub const INFUR_RASTER_LOOPS: u32 = 0;
+pub const INFUR_RASTER_PAINTED: u32 = 1;
+pub const INFUR_RASTER_CONFLICT: u32 = 2;
+pub const INFUR_RASTER_STATUS: u32 = 3;
+pub const INFUR_RASTER_COUNT_WORDS: u32 = 4;
+pub const INFUR_RASTER_TRUNCATED: u32 = 1;
+pub const INFUR_RASTER_MALFORMED: u32 = 2;
+pub const INFUR_RASTER_OUTSIDE: u32 = 4;
+/// bit of `infur_features()`: the Raster calls below exist
+pub const INFUR_FEATURE_RASTER: u32 = 4096;
 
 extern "C" {
     pub fn infur_abi_version() -> u32;
@@ -604,4 +615,15 @@ extern "C" {
                                   max_edges: u32, d_loops_out: *mut c_void, loops_rows_out: u32, d_vertices_out: *mut c_void,
                                   vertex_rows_out: u32, d_shapes: *mut c_void, shape_rows: u32, d_values: *mut c_void,
                                   d_counts_out: *mut c_void) -> i32;
+    // Raster: polygon loops, or run-length records, filled back into a plane of 1- or 4-byte elements
+    pub fn infur_raster(c: *mut infur_ctx, loops: *const u32, loops_rows_in: u32, vertices: *const u32, vertex_rows_in: u32,
+                        counts: *const u32, h: u32, w: u32, elem_bytes: u32, fill_value: u32, plane_out: *mut c_void,
+                        counts_out: *mut u32) -> i32;
+    pub fn infur_raster_dev(c: *mut infur_ctx, d_loops: *const c_void, loops_rows_in: u32, d_vertices: *const c_void,
+                            vertex_rows_in: u32, d_counts: *const c_void, h: u32, w: u32, elem_bytes: u32, fill_value: u32,
+                            d_plane_out: *mut c_void, d_counts_out: *mut c_void) -> i32;
+    pub fn infur_raster_runs(c: *mut infur_ctx, runs: *const u32, runs_rows_in: u32, n_runs: u32, h: u32, w: u32, elem_bytes: u32,
+                             fill_value: u32, plane_out: *mut c_void, counts_out: *mut u32) -> i32;
+    pub fn infur_raster_runs_dev(c: *mut infur_ctx, d_runs: *const c_void, runs_rows_in: u32, d_n_runs: *const c_void, h: u32,
+                                 w: u32, elem_bytes: u32, fill_value: u32, d_plane_out: *mut c_void, d_counts_out: *mut c_void) -> i32;
 }

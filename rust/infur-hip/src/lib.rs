@@ -1125,6 +1125,75 @@ impl Processor for HipShapes {
     }
 }
 
+// ---------------------------------------------------------------- Raster (loops and runs back into a plane)
+/// What `HipRaster` reads: the loops of a polygon stage (`Loops`, `HipSimplify`'s input) or the records of `HipRuns` with the plane's
+/// `[w, h]`.
+pub enum RasterInput { Loops(SimplifyInput), Runs { runs: Runs, size: [usize; 2] } }
+/// What `HipRaster` produces: `plane` holds `h * w` elements of `elem_bytes` bytes each (empty when the input was truncated),
+/// `painted` and `conflict` count the pixels exactly one loop claims and the pixels that were refused (overlaps, a hole alone,
+/// crossed arcs, a value a byte plane cannot hold); `status`: `INFUR_RASTER_TRUNCATED`, `_MALFORMED`, `_OUTSIDE`.
+#[derive(Default)]
+pub struct Rastered { pub n: u32, pub painted: u32, pub conflict: u32, pub status: u32, pub plane: Vec<u8> }
+pub enum RasterCmd { Fill { elem_bytes: u32, fill_value: u32 } }
+/// The stage that goes the other way: polygon loops or run-length records filled into a plane.  Winding 1 paints the loop's value,
+/// everything else reads `fill_value`.  Integer results, identical from run to run.
+pub struct HipRaster { ctx: Rc<Ctx>, elem_bytes: u32, fill_value: u32, dirty: bool }
+impl HipRaster {
+    pub fn new(ctx: Rc<Ctx>) -> Self { Self { ctx, elem_bytes: 1, fill_value: 0, dirty: true } }
+}
+impl Processor for HipRaster {
+    type Command = RasterCmd;
+    type ControlError = HipError;
+    type Input = RasterInput;
+    type Output = Rastered;
+    type ProcessResult = Result<(), HipError>;
+
+    fn control(&mut self, cmd: RasterCmd) -> Result<&mut Self, HipError> {
+        let RasterCmd::Fill { elem_bytes, fill_value } = cmd;
+        if (elem_bytes != 1 && elem_bytes != 4) || (elem_bytes == 1 && fill_value > 255) {
+            return Err(HipError::status(sys::INFUR_E_INVALID_ARG));
+        }
+        self.dirty = self.dirty || elem_bytes != self.elem_bytes || fill_value != self.fill_value;
+        self.elem_bytes = elem_bytes;
+        self.fill_value = fill_value;
+        Ok(self)
+    }
+    fn is_dirty(&self) -> bool { self.dirty }
+    fn advance(&mut self, inp: &RasterInput, out: &mut Rastered) -> Result<(), HipError> {
+        self.dirty = false;
+        let [w, h] = match inp { RasterInput::Loops(l) => l.size, RasterInput::Runs { size, .. } => *size };
+        out.plane.resize(w * h * self.elem_bytes as usize, 0);
+        let mut counts = [0u32; 4];
+        let plane = if out.plane.is_empty() { std::ptr::null_mut() } else { out.plane.as_mut_ptr() as *mut std::ffi::c_void };
+        let rc = match inp {
+            RasterInput::Loops(l) => {
+                let o = &l.outlines;
+                let rows_in = o.loops.len() / sys::INFUR_LOOP_WORDS as usize;
+                let counts_in = [o.n_loops, o.n_vertices];
+                unsafe {
+                    sys::infur_raster(self.ctx.0, if rows_in > 0 { o.loops.as_ptr() } else { std::ptr::null() }, rows_in as u32,
+                                      if !o.vertices.is_empty() { o.vertices.as_ptr() } else { std::ptr::null() }, o.vertices.len() as u32,
+                                      counts_in.as_ptr(), h as u32, w as u32, self.elem_bytes, self.fill_value, plane, counts.as_mut_ptr())
+                }
+            }
+            RasterInput::Runs { runs, .. } => {
+                let rows_in = runs.runs.len() / sys::INFUR_RUN_WORDS as usize;
+                unsafe {
+                    sys::infur_raster_runs(self.ctx.0, if rows_in > 0 { runs.runs.as_ptr() } else { std::ptr::null() }, rows_in as u32, runs.n,
+                                           h as u32, w as u32, self.elem_bytes, self.fill_value, plane, counts.as_mut_ptr())
+                }
+            }
+        };
+        if rc != sys::INFUR_OK { return Err(HipError::from_ctx(&self.ctx, rc)); }
+        out.n = counts[sys::INFUR_RASTER_LOOPS as usize];
+        out.painted = counts[sys::INFUR_RASTER_PAINTED as usize];
+        out.conflict = counts[sys::INFUR_RASTER_CONFLICT as usize];
+        out.status = counts[sys::INFUR_RASTER_STATUS as usize];
+        if out.status & sys::INFUR_RASTER_TRUNCATED != 0 { out.plane.clear(); }
+        Ok(())
+    }
+}
+
 // ---------------------------------------------------------------- Coverage (shared borders simplified once)
 /// What `HipCoverage` produces, in `Outlines`' layout: `loops` holds `min(n_loops, loops_rows)` records (OFFSET', COUNT', VALUE,
 /// START), `vertices` the first `min(n_vertices, vertex_rows)` kept vertex ids; `n_degenerate` counts the loops with COUNT' < 3
