@@ -1398,6 +1398,99 @@ int32_t infur_raster_runs(infur_ctx* ctx, const uint32_t* runs, uint32_t runs_ro
 int32_t infur_raster_runs_dev(infur_ctx* ctx, const void* d_runs, uint32_t runs_rows_in, const void* d_n_runs, uint32_t h,
                               uint32_t w, uint32_t elem_bytes, uint32_t fill_value, void* d_plane_out, void* d_counts_out);
 
+/* ---- Split: touching objects of one value separated at their necks ----
+ * Regions gives one row per connected component of a class.  On a semantic model that is not one row per object: two people whose
+ * masks touch are one "person" region with one box, one anchor, one track and one polygon.  The textbook remedy is a marker
+ * watershed of the distance transform, and Anchors already leaves that transform (dist2) in device memory.  Split turns a plane
+ * and a height plane into a finer label plane on the device; its output is a label plane like Regions', so Tracks, Runs, Outlines,
+ * Anchors, Shapes and Compare run on it unchanged.  Everything is an exact integer function of the two planes and `core`:
+ * identical bytes from run to run.  Announced by infur_features() & INFUR_FEATURE_SPLIT (INFUR_ABI_VERSION does not move).
+ *
+ * INPUTS.  `plane`: h x w elements of elem_bytes = 1 or 4; Anchors' rules hold for the sizes (and h*w must stay below 2^31), for a
+ * NULL plane, for unknown flag bits and for flags & INFUR_SPLIT_SKIP with skip_value: skipped pixels belong to no segment, the
+ * others are KEPT.  `height`: h x w uint32_t, typically Anchors' dist2 of the same plane; the rule holds for any values and never
+ * assumes a distance transform.  `core`: with dist2 a squared half-width -- a neck narrower than 2 sqrt(core) pixels separates,
+ * a body has to be wider than that to count as an object of its own.
+ * 1 ORDER.  Pixels are totally ordered by (height, -index): of two pixels the higher is larger, of equal heights the one with the
+ *   smaller index y*w + x.
+ * 2 ASCENT.  A kept pixel points to the largest of its kept 4-neighbours of the same value if that neighbour is larger than the
+ *   pixel itself; otherwise it is a PEAK.  Following the pointers leads every kept pixel to a peak; the pixels of one peak are a
+ *   BASIN, named by the peak's index.
+ * 3 SADDLES.  Two basins A < B of the same value that share a pixel edge are a PAIR.  SADDLE(A, B) is the maximum over the shared
+ *   edges (p, q) of min(height p, height q); FIRST(A, B) the smallest id of a shared edge, where the edge from pixel i to x+1 has
+ *   id 2i and the edge to y+1 id 2i + 1 (Adjacency's ids).  Pairs are strictly ordered by (SADDLE descending, FIRST ascending).
+ * 4 MERGE.  A basin is MARKED when its peak's height is >= core, and a set of basins when it holds a marked one.  Walk the pairs in
+ *   their order with a union-find over the basins; unite the two sets of a pair when SADDLE >= core, or when they are not both
+ *   marked.  This is the marker watershed as a maximum spanning forest rooted in the markers: two cores joined only through a
+ *   neck lower than core stay apart; everything unmarked (limbs, bumps on a ridge) joins the marker it reaches over the highest
+ *   path; a region without any marked basin ends as one segment.
+ * 5 NUMBERING.  The final sets are the SEGMENTS, numbered in raster order of their first pixel, as Regions numbers regions.
+ * core = 0 and core = 0xFFFFFFFF with heights below it both give the 4-connected components of the plane.
+ * OUTPUTS, each optional (NULL = not wanted, and so is table with rows == 0; nothing wanted is INFUR_E_INVALID_ARG), none needs
+ * initialisation, and a rejected call touches none:
+ *   labels_out  h*w uint32_t: the segment of every kept pixel, INFUR_SPLIT_NONE on skipped pixels
+ *   table       the first min(SEGMENTS, rows) rows of INFUR_SPLIT_WORDS uint32_t: VALUE (of the plane), PIXELS, FIRST (its first
+ *               pixel), PEAK (the index of its largest peak, an anchor for the segment), HEIGHT (of that peak), NECK (the largest
+ *               SADDLE of a pair that leads into another segment, 0 when there is none)
+ *   counts      INFUR_SPLIT_COUNT_WORDS uint32_t, always complete: SEGMENTS, BASINS, PAIRS, RUNS (the edges between basins of one
+ *               value whose (basin, basin) differs from that of the edge one column to the left, for edges towards y+1, or one row
+ *               up, for edges towards x+1: what the pair table has to absorb), MARKED (basins), SPLIT_VALUES (the
+ *               values of the plane that end with more than one segment, touching or not), ROUNDS (the rounds of the device's
+ *               forest construction that joined something: every unmarked set picks its largest pair at once, sets that picked
+ *               each other and chains of picks merge, until nothing is picked) and STATUS
+ * pair_slots sizes the hash table of pairs: a power of two of at least 64, 0 = 2^20.  2 RUNS > pair_slots sets INFUR_SPLIT_OVERFLOW
+ * in STATUS; then SEGMENTS, PAIRS, MARKED, SPLIT_VALUES and ROUNDS read 0 and nothing but the counts is written -- visible, and not an
+ * error, as in Outlines and Sieve.  h*w == 0 writes zero counts and nothing else.
+ * EXAMPLE.  h = 1, w = 9, every pixel of value 1, height = 1 4 9 4 1 4 9 4 1.  Pixels 2 and 6 are peaks; pixel 4 sees 4 on both
+ * sides and points to the smaller index, 3: the basins are 2 = {0 .. 4} and 6 = {5 .. 8}.  Their one shared edge joins pixels 4
+ * and 5, so SADDLE = min(1, 4) = 1 and FIRST = 8.  With core = 4 both basins are marked and 1 < 4: labels 0 0 0 0 0 1 1 1 1, rows
+ * (1, 5, 0, 2, 9, 1) and (1, 4, 5, 6, 9, 1), counts (2, 2, 1, 1, 2, 1, 0, 0).  With core = 1 the pair unites at once: one
+ * segment, row (1, 9, 0, 2, 9, 0), counts (1, 2, 1, 1, 2, 0, 0, 0).  With core = 10 nothing is marked and the unmarked pair unites
+ * in the first round: the same row, counts (1, 2, 1, 1, 0, 0, 1, 0).
+ * WHAT IT DOES NOT DO.  No 8-neighbour ascent, no persistence (h-maxima) criterion, no stream, batch or group call, and no Tracks
+ * on the segments inside one call: a host chains the _dev calls. */
+#define INFUR_SPLIT_NONE 0xFFFFFFFFu
+enum { INFUR_SPLIT_SKIP = 1 };
+enum { INFUR_SPLIT_VALUE = 0, INFUR_SPLIT_PIXELS = 1, INFUR_SPLIT_FIRST = 2, INFUR_SPLIT_PEAK = 3, INFUR_SPLIT_HEIGHT = 4, INFUR_SPLIT_NECK = 5, INFUR_SPLIT_WORDS = 6 };
+enum { INFUR_SPLIT_SEGMENTS = 0, INFUR_SPLIT_BASINS = 1, INFUR_SPLIT_PAIRS = 2, INFUR_SPLIT_RUNS = 3, INFUR_SPLIT_MARKED = 4, INFUR_SPLIT_SPLIT_VALUES = 5,
+       INFUR_SPLIT_ROUNDS = 6, INFUR_SPLIT_STATUS = 7, INFUR_SPLIT_COUNT_WORDS = 8 };
+enum { INFUR_SPLIT_OVERFLOW = 1 };
+enum { INFUR_FEATURE_SPLIT = 8192 };
+
+/* on a given plane and height plane, host pointers */
+int32_t infur_split(infur_ctx* ctx, const void* plane, uint32_t elem_bytes, const uint32_t* height, uint32_t h, uint32_t w,
+                    uint32_t flags, uint32_t skip_value, uint32_t core, uint32_t pair_slots, uint32_t* labels_out, uint32_t* table,
+                    uint32_t rows, uint32_t* counts);
+/* device pointers throughout; enqueued on the context's stream as launches only -- no memset, 10 + ceil(log2(h*w)) +
+ * 3 (ceil(log2(min(h*w, pair_slots))) + 1) of them and one or two per wanted output, a number fixed by the arguments; the launches
+ * behind a pass that changed nothing exit at once.  The call never synchronises and is capturable after one call outside the
+ * capture, which allocates the scratch: 44 bytes per pixel, 16 per slot and 12 per slot of the table of values (the power of two
+ * from twice the pixels, or 512 for a byte plane), owned by the context; it grows only with a request larger than any before.  This is the call that composes on the device: infur_frame_regions_dev, infur_anchors_dev on its label
+ * plane, then infur_split_dev on both.  The outputs must not overlap the inputs. */
+int32_t infur_split_dev(infur_ctx* ctx, const void* d_plane, uint32_t elem_bytes, const void* d_height, uint32_t h, uint32_t w,
+                        uint32_t flags, uint32_t skip_value, uint32_t core, uint32_t pair_slots, void* d_labels_out, void* d_table,
+                        uint32_t rows, void* d_counts);
+/* The fused frame path with one row per object: scale -> model -> Segments decode(out[0]) -> Regions -> Anchors of the label plane
+ * with INFUR_REGION_NONE skipped -> Split of the label plane under dist2, INFUR_REGION_NONE skipped, in one call.  The arguments
+ * are infur_frame_anchors' own, then core, pair_slots and Split's outputs (split_labels_capacity in bytes, ow*oh*4 needed; less is
+ * INFUR_E_CAPACITY).  Every output is optional; the label and distance planes go to scratch of the library's own when the caller
+ * does not want them.  The calls inherit infur_frame_anchors' checks and errors and its rule for a context without a model, always
+ * enqueue eagerly and leave the graphs cached for infur_frame_advance_dev alone. */
+int32_t infur_frame_split(infur_ctx* ctx, const uint8_t* bgr, uint32_t w, uint32_t h, float factor, uint32_t scale_mode,
+                          uint32_t decode, uint32_t connectivity, uint32_t min_pixels, uint32_t flags, uint8_t* klass,
+                          uint8_t* conf, size_t plane_capacity, uint32_t* labels, size_t labels_capacity, uint64_t* table,
+                          uint32_t table_rows, uint32_t* n_regions, uint8_t* scaled_bgr, uint32_t* ow, uint32_t* oh,
+                          uint32_t* dist2, size_t dist2_capacity, uint32_t* anchors, uint32_t core, uint32_t pair_slots,
+                          uint32_t* split_labels, size_t split_labels_capacity, uint32_t* split_table, uint32_t split_rows,
+                          uint32_t* split_counts);
+int32_t infur_frame_split_dev(infur_ctx* ctx, const void* d_bgr, uint32_t w, uint32_t h, float factor, uint32_t scale_mode,
+                              uint32_t decode, uint32_t connectivity, uint32_t min_pixels, uint32_t flags, void* d_klass,
+                              void* d_conf, size_t plane_capacity, void* d_labels, size_t labels_capacity, void* d_table,
+                              uint32_t table_rows, void* d_n_regions, void* d_scaled_bgr, uint32_t* ow, uint32_t* oh,
+                              void* d_dist2, size_t dist2_capacity, void* d_anchors, uint32_t core, uint32_t pair_slots,
+                              void* d_split_labels, size_t split_labels_capacity, void* d_split_table, uint32_t split_rows,
+                              void* d_split_counts);
+
 /* ---- streaming (infur/src/main.rs:27-99,105): bounded queue, copies overlapped with compute ----
  * The reference back-pressures its producer with sync_channel(2) (main.rs:105); a stream
  * here is a ring of `depth` pinned + device slots.  submit() copies the caller's frame into a

@@ -960,6 +960,62 @@ private:
     bool dirty_ = true;
 };
 
+/// What `Split` produces: `labels` holds height * width segment ids (INFUR_SPLIT_NONE on skipped pixels), `table` the first
+/// min(segments, rows) rows of INFUR_SPLIT_WORDS words (VALUE, PIXELS, FIRST, PEAK, HEIGHT, NECK), `counts` the eight count words.
+/// After an overflow of the pair table (counts[INFUR_SPLIT_STATUS] & INFUR_SPLIT_OVERFLOW) only the counts hold anything.
+struct SplitOut {
+    uint32_t width = 0, height = 0, rows = 1024;  // rows: the table rows wanted
+    std::vector<uint32_t> labels, table;
+    uint32_t counts[INFUR_SPLIT_COUNT_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint32_t segments() const { return counts[INFUR_SPLIT_SEGMENTS]; }
+    const uint32_t* row(uint32_t i) const { return table.data() + (size_t)i * INFUR_SPLIT_WORDS; }
+};
+
+/// The stage that separates touching objects of one value at their necks: a marker watershed of a u32 height plane, typically
+/// Anchors' dist2, as a maximum spanning forest rooted in the basins whose peak reaches `core`.  Its output is a label plane like
+/// Regions'.  Integer results, identical from run to run.  Command = core, the skipped value and the size of the pair table;
+/// Input = a plane of 1- or 4-byte elements and a height plane of its size; Output = SplitOut.
+class Split {
+public:
+    struct Cmd {
+        enum Kind { Core } kind;
+        uint32_t core;
+        bool skip;
+        uint32_t skip_value, pair_slots;
+    };
+    explicit Split(Context& c) : c_(c) {}
+    Status control(Cmd cmd) {
+        if (cmd.kind != Cmd::Core || (cmd.pair_slots && (cmd.pair_slots < 64 || (cmd.pair_slots & (cmd.pair_slots - 1))))) return INFUR_E_INVALID_ARG;
+        dirty_ = dirty_ || cmd.core != cmd_.core || cmd.skip != cmd_.skip || cmd.skip_value != cmd_.skip_value || cmd.pair_slots != cmd_.pair_slots;
+        cmd_ = cmd;
+        return INFUR_OK;
+    }
+    bool is_dirty() const { return dirty_; }
+    Status advance(const void* plane, uint32_t elem_bytes, const uint32_t* height, uint32_t h, uint32_t w, SplitOut& out) {
+        dirty_ = false;
+        const size_t npix = (size_t)h * w, rows = out.rows < npix ? out.rows : npix;
+        out.width = w;
+        out.height = h;
+        out.labels.assign(npix, 0);
+        out.table.assign(rows * INFUR_SPLIT_WORDS, 0);
+        const Status s = infur_split(c_.get(), plane, elem_bytes, height, h, w, cmd_.skip ? INFUR_SPLIT_SKIP : 0, cmd_.skip_value, cmd_.core, cmd_.pair_slots,
+                                     npix ? out.labels.data() : nullptr, rows ? out.table.data() : nullptr, (uint32_t)rows, out.counts);
+        if (s != INFUR_OK) return s;
+        if (out.counts[INFUR_SPLIT_STATUS] & INFUR_SPLIT_OVERFLOW) {
+            out.labels.clear();
+            out.table.clear();
+        } else {
+            out.table.resize((out.segments() < rows ? out.segments() : rows) * INFUR_SPLIT_WORDS);
+        }
+        return s;
+    }
+
+private:
+    Context& c_;
+    Cmd cmd_{Cmd::Core, 0, false, 0, 0};
+    bool dirty_ = true;
+};
+
 /// What `Coverage` produces, in Outlines' layout: `loops` holds min(n_loops, loops_rows) records (OFFSET', COUNT', VALUE, START),
 /// `vertices` the first min(n_vertices, vertex_rows) kept vertex ids; n_degenerate counts the loops with COUNT' < 3 (skip them);
 /// status: INFUR_COVERAGE_TRUNCATED and INFUR_COVERAGE_OVERFLOW (nothing was produced), INFUR_COVERAGE_MALFORMED; n_aug: the

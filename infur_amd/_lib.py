@@ -118,6 +118,14 @@ FEATURE_SHAPES = 2048
 RASTER_LOOPS, RASTER_PAINTED, RASTER_CONFLICT, RASTER_STATUS, RASTER_COUNT_WORDS = 0, 1, 2, 3, 4
 RASTER_TRUNCATED, RASTER_MALFORMED, RASTER_OUTSIDE = 1, 2, 4
 FEATURE_RASTER = 4096
+# Split (infur_split / infur_frame_split): the flag, the words of a segment row and of the counts, the status bit, the feature bit
+SPLIT_SKIP = 1
+SPLIT_VALUE, SPLIT_PIXELS, SPLIT_FIRST, SPLIT_PEAK, SPLIT_HEIGHT, SPLIT_NECK, SPLIT_WORDS = 0, 1, 2, 3, 4, 5, 6
+(SPLIT_SEGMENTS, SPLIT_BASINS, SPLIT_PAIRS, SPLIT_RUNS, SPLIT_MARKED, SPLIT_SPLIT_VALUES, SPLIT_ROUNDS, SPLIT_STATUS,
+ SPLIT_COUNT_WORDS) = 0, 1, 2, 3, 4, 5, 6, 7, 8
+SPLIT_OVERFLOW = 1
+SPLIT_NONE = 0xFFFFFFFF
+FEATURE_SPLIT = 8192
 
 
 class Options(C.Structure):
@@ -288,6 +296,12 @@ SIGNATURES = {
     "infur_raster_dev": (C.c_int32, [_vp, _vp, _u32, _vp, _u32, _vp, _u32, _u32, _u32, _u32, _vp, _vp]),
     "infur_raster_runs": (C.c_int32, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp]),
     "infur_raster_runs_dev": (C.c_int32, [_vp, _vp, _u32, _vp, _u32, _u32, _u32, _u32, _vp, _vp]),
+    "infur_split": (C.c_int32, [_vp, _vp, _u32, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _u32, _vp]),
+    "infur_split_dev": (C.c_int32, [_vp, _vp, _u32, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _u32, _vp]),
+    "infur_frame_split": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp, _vp,
+                                      _u32p, _u32p, _vp, _sz, _vp, _u32, _u32, _vp, _sz, _vp, _u32, _vp]),
+    "infur_frame_split_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp, _vp,
+                                          _u32p, _u32p, _vp, _sz, _vp, _u32, _u32, _vp, _sz, _vp, _u32, _vp]),
     "infur_stream_create": (C.c_int32, [_vp, _u32, C.POINTER(_vp)]),
     "infur_stream_destroy": (None, [_vp]),
     "infur_stream_add_lane": (C.c_int32, [_vp, _vp]),

@@ -200,6 +200,9 @@ struct infur_ctx {
     // Raster (infur_raster.cpp): the head words and one 64-bit accumulator word per pixel; the host-pointer calls' staging.  Private
     // like the above.
     infur::Buf st_raster, st_raster_io;
+    // Split (infur_split.cpp): the ascent pointers, the union-find over basins, the saddle table and the per-root words; the label and
+    // distance planes the frame calls let the caller leave out; the host-pointer calls' staging.  Private like the above.
+    infur::Buf st_split, st_split_plane, st_split_io;
     // Tracks (infur_tracks.cpp): the live trackers of this context; infur_ctx_destroy releases their device memory and orphans them
     std::vector<infur_tracker*> trackers;
 

@@ -473,6 +473,22 @@ hipError_t launch_raster(const unsigned* loops, unsigned loops_rows_in, const un
 hipError_t launch_raster_runs(const unsigned* runs, unsigned runs_rows_in, const unsigned* d_n, unsigned H, unsigned W, int elem_bytes,
                               unsigned fill_value, void* scratch, void* plane, unsigned* counts_out, hipStream_t s);
 
+// Split (split.hip): the segments of an H x W plane (H * W below 2^31) of 1- or 4-byte elements under a u32 height plane: the marker
+// watershed of include/infur_hip.h.  labels: H * W u32 segment ids (0xFFFFFFFF on skipped pixels); table: the first min(n, rows)
+// rows of kSplitWords u32 (VALUE, PIXELS, FIRST, PEAK, HEIGHT, NECK); counts[kSplitCountWords] = {SEGMENTS, BASINS, PAIRS, RUNS,
+// MARKED, SPLIT_VALUES, ROUNDS, STATUS} (each optional).  pair_slots: a power of two of at least 64; 2 RUNS > pair_slots sets
+// kSplitOverflow and leaves everything but the counts alone.  scratch: split_scratch_bytes(..).  Stream-ordered, no memset;
+// split_launches(..) launches, a number fixed by the arguments; a doubling launch or a round behind one that changed nothing
+// exits on a device flag.
+constexpr int kSplitWords = 6;
+constexpr int kSplitCountWords = 8;
+constexpr unsigned kSplitOverflow = 1u;
+size_t split_scratch_bytes(size_t npix, unsigned pair_slots, int elem_bytes);
+unsigned split_rounds(size_t npix, unsigned pair_slots);
+unsigned split_launches(size_t npix, unsigned pair_slots, bool labels, bool table, bool counts);
+hipError_t launch_split(const void* plane, int elem_bytes, const unsigned* height, unsigned H, unsigned W, int skip, unsigned skip_value, unsigned core,
+                        void* scratch, unsigned pair_slots, unsigned* labels, unsigned* table, unsigned rows, unsigned* counts, hipStream_t s);
+
 // Coverage (coverage.hip): Outlines' loops of an H x W plane (both in [1, 8191]) of 1- or 4-byte elements, simplified within
 // tol16 / 16 pixels so that neighbouring polygons still fit: the loops are cut at the plane's junctions and every arc between
 // two of them is simplified by a rule that does not depend on the direction of travel.  Inputs as launch_simplify's plus the

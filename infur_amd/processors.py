@@ -1324,6 +1324,112 @@ class SieveFrame(NamedTuple):
     scaled: Optional[np.ndarray]
 
 
+@dataclass
+class SplitCmd:
+    """``Split``'s command: ``core``, the height a saddle must reach to join two objects and a peak to found one (with Anchors'
+    ``dist2`` a squared half-width; ``split_core(px)`` converts a width in pixels); ``skip``: the value that belongs to no segment
+    (None: every value is kept); ``pair_slots`` (0: the library's 2^20)."""
+
+    core: int = 0
+    skip: Optional[int] = None
+    pair_slots: int = 0
+
+
+def split_core(px: float) -> int:
+    """The ``core`` of a neck width in pixels: ceil(px / 2) squared, the squared half-width ``dist2`` is compared with."""
+    half = int(-(-max(0.0, float(px)) // 2))
+    return min(0xFFFFFFFF, half * half)
+
+
+class SplitOut:
+    """``Split``'s ``&mut Output``: what to produce (``want_labels``, ``rows`` table rows, ``want_counts``) and, after ``advance``,
+    ``labels`` [H, W] u32 (``_lib.SPLIT_NONE`` on skipped pixels), ``table`` [min(segments, rows), 6] u32 (``_lib.SPLIT_VALUE`` ..
+    ``_lib.SPLIT_NECK``), ``counts`` [8] u32 (``_lib.SPLIT_SEGMENTS`` .. ``_lib.SPLIT_STATUS``); None for what was not wanted, and
+    for the labels and the table of a call whose pair table overflowed."""
+
+    def __init__(self, want_labels: bool = True, rows: int = 1024, want_counts: bool = True):
+        self.want_labels, self.rows, self.want_counts = want_labels, rows, want_counts
+        self.labels = self.table = self.counts = None
+
+
+def _split_result(labels, table, counts) -> tuple:
+    """what a call left valid: nothing but the counts after an overflow, else the rows there are"""
+    if counts[_lib.SPLIT_STATUS] & _lib.SPLIT_OVERFLOW:
+        return None, None
+    return labels, table[:min(int(counts[_lib.SPLIT_SEGMENTS]), len(table))] if table is not None else None
+
+
+class Split(Processor):
+    """The stage that separates touching objects of one value at their necks: a marker watershed of a height plane, typically
+    ``Anchors``' ``dist2``, whose output is a label plane like ``Regions``'.
+
+    Command = ``SplitCmd``.  Input = (plane [H, W] u8 or u32, height [H, W] u32); Output = ``SplitOut``.  Integers throughout,
+    identical from run to run.  ``split_summary`` names the counts.
+    """
+
+    def __init__(self, ctx: Context, core: int = 0, skip: Optional[int] = None, pair_slots: int = 0):
+        self.ctx = ctx
+        self.core, self.skip, self.pair_slots = core, skip, pair_slots
+        self.dirty = True
+
+    def control(self, cmd: SplitCmd) -> "Split":
+        for name in ("core", "pair_slots", "skip"):
+            v = getattr(cmd, name)
+            if v is not None and not 0 <= v <= 0xFFFFFFFF:
+                raise InfurError(_lib.E_INVALID_ARG, f"{name} {v}: a u32")
+        new = (cmd.core, cmd.skip, cmd.pair_slots)
+        self.dirty = self.dirty or new != (self.core, self.skip, self.pair_slots)
+        self.core, self.skip, self.pair_slots = new
+        return self
+
+    def is_dirty(self) -> bool:
+        return self.dirty
+
+    def advance(self, inp, out: SplitOut) -> None:
+        self.dirty = False
+        plane, height = inp
+        if plane.ndim != 2 or plane.dtype.itemsize not in (1, 4) or plane.dtype.kind not in "ui" or height.shape != plane.shape:
+            raise InfurError(_lib.E_SHAPE, f"expected an [H,W] plane of 1- or 4-byte integers and a height plane of its size, got {plane.shape} "
+                                           f"{plane.dtype} and {height.shape}")
+        plane, height = np.ascontiguousarray(plane), np.ascontiguousarray(height, np.uint32)
+        h, w = plane.shape
+        rows = max(0, min(int(out.rows), h * w))
+        labels = np.empty((h, w), np.uint32) if out.want_labels else None
+        table = np.empty((rows, _lib.SPLIT_WORDS), np.uint32) if rows else None
+        counts = np.zeros(_lib.SPLIT_COUNT_WORDS, np.uint32)
+        self.ctx.check(self.ctx.L.infur_split(self.ctx.h, _ptr_some(plane), plane.dtype.itemsize, _ptr_some(height), h, w,
+                                              _lib.SPLIT_SKIP if self.skip is not None else 0, self.skip or 0, self.core, self.pair_slots, _ptr(labels),
+                                              _ptr_some(table), rows, counts.ctypes.data))
+        out.labels, out.table = _split_result(labels, table, counts)
+        out.counts = counts if out.want_counts else None
+
+
+def split_summary(counts: np.ndarray) -> dict:
+    """``Split``'s eight counts by name: ``segments``, ``basins``, ``pairs``, ``runs``, ``marked``, ``split_values``, ``rounds``, ``status``,
+    and the status bit as ``overflow``."""
+    c = [int(v) for v in np.asarray(counts).ravel()[:_lib.SPLIT_COUNT_WORDS]]
+    return {"segments": c[_lib.SPLIT_SEGMENTS], "basins": c[_lib.SPLIT_BASINS], "pairs": c[_lib.SPLIT_PAIRS], "runs": c[_lib.SPLIT_RUNS],
+            "marked": c[_lib.SPLIT_MARKED], "split_values": c[_lib.SPLIT_SPLIT_VALUES], "rounds": c[_lib.SPLIT_ROUNDS], "status": c[_lib.SPLIT_STATUS],
+            "overflow": bool(c[_lib.SPLIT_STATUS] & _lib.SPLIT_OVERFLOW)}
+
+
+class SplitFrame(NamedTuple):
+    """``FramePath.advance_split``: ``AnchorsFrame``'s fields, then the segment plane [oh, ow] u32, the segment rows
+    [min(segments, split_rows), 6] u32 and Split's counts [8] u32"""
+
+    klass: Optional[np.ndarray]
+    conf: Optional[np.ndarray]
+    labels: Optional[np.ndarray]
+    table: Optional[np.ndarray]
+    n: Optional[int]
+    scaled: Optional[np.ndarray]
+    dist2: Optional[np.ndarray]
+    anchors: Optional[np.ndarray]
+    segments: Optional[np.ndarray]
+    segment_table: Optional[np.ndarray]
+    counts: Optional[np.ndarray]
+
+
 def runs_decode(runs: np.ndarray, n: int, h: int, w: int, fill: int = 0, dtype=None) -> np.ndarray:
     """The dense [h, w] plane of the first ``min(n, len(runs))`` records; pixels no record covers (skipped or truncated runs) read
     ``fill``.  ``dtype``: uint8 when every value and ``fill`` fit a byte, else uint32."""
@@ -2031,6 +2137,37 @@ class FramePath:
         k = min(n.value, rows)
         return AnchorsFrame(klass, conf, labels, table[:k] if table is not None else None, n.value, scaled, dist2,
                             anchors[:k] if anchors is not None else None)
+
+    def advance_split(self, img: np.ndarray, core: int, factor: float = 1.0, decode: int = _lib.DECODE_RAW, connectivity: int = _lib.CONNECT_8,
+                      min_pixels: int = 0, flags: int = 0, table_rows: int = 1024, split_rows: int = 1024, pair_slots: int = 0,
+                      want_labels: bool = False, want_klass: bool = True, want_conf: bool = False, want_scaled: bool = False,
+                      want_dist2: bool = False, want_segments: bool = True) -> SplitFrame:
+        """The fused path with one row per object, scale -> model -> Segments decode -> Regions -> Anchors of the label plane ->
+        Split of the label plane under its ``dist2``, in one call -> ``SplitFrame``; every result field is None when no model is
+        loaded (``scaled`` is still produced)."""
+        img, w, h, f, ow, oh = self._front(img, factor)
+        npix = oh.value * ow.value
+        rows, srows = max(0, min(int(table_rows), npix)), max(0, min(int(split_rows), npix))
+        klass, conf = self._plane(ow, oh, want_klass), self._plane(ow, oh, want_conf)
+        labels = self._plane(ow, oh, want_labels, np.uint32)
+        table = np.zeros((rows, _lib.REGION_WORDS), np.uint64) if rows else None
+        scaled = self._plane(ow, oh, want_scaled, channels=3)
+        dist2 = self._plane(ow, oh, want_dist2, np.uint32)
+        anchors = np.empty((rows, _lib.ANCHOR_WORDS), np.uint32) if rows else None
+        segments = self._plane(ow, oh, want_segments, np.uint32)
+        stable = np.empty((srows, _lib.SPLIT_WORDS), np.uint32) if srows else None
+        counts = np.zeros(_lib.SPLIT_COUNT_WORDS, np.uint32)
+        n = C.c_uint32(0)
+        rc = self.ctx.L.infur_frame_split(self.ctx.h, img.ctypes.data, w, h, f, self.scale_mode, decode, connectivity, min_pixels, flags,
+                                          _ptr(klass), _ptr(conf), npix, _ptr(labels), npix * 4, _ptr(table), rows, C.addressof(n), _ptr(scaled),
+                                          C.byref(ow), C.byref(oh), _ptr(dist2), npix * 4, _ptr(anchors), core, pair_slots, _ptr(segments), npix * 4,
+                                          _ptr(stable), srows, counts.ctypes.data)
+        if not self._loaded(rc):
+            return SplitFrame(None, None, None, None, None, scaled, None, None, None, None, None)
+        k = min(n.value, rows)
+        segments, stable = _split_result(segments, stable, counts)
+        return SplitFrame(klass, conf, labels, table[:k] if table is not None else None, n.value, scaled, dist2,
+                          anchors[:k] if anchors is not None else None, segments, stable, counts)
 
     def advance_shapes(self, img: np.ndarray, factor: float = 1.0, decode: int = _lib.DECODE_RAW, connectivity: int = _lib.CONNECT_8,
                        min_pixels: int = 0, flags: int = 0, table_rows: int = 1024, max_edges: int = 0, loops_rows: int = 1 << 16,

@@ -54,6 +54,12 @@ Regions left it on the device (``infur_anchors_dev``, pixels of no region skippe
 nearest pixel of anything else or to the frame.  ``--dist-out FILE`` (needs ``--anchors``) receives the u32 planes of squared
 distances back to back (0: a pixel of no region).
 
+``--split PX`` (needs ``--regions``) separates the touching objects of a region where it is narrower than PX pixels: the frame goes
+through ``infur_frame_split`` (Regions -> Anchors -> Split with core = ceil(PX / 2) squared), every line gains ``"split"`` (the stage's
+counts) and ``"segments"``, one record per object with its ``"region"``, ``"pixels"``, ``"first"`` pixel, ``"anchor"`` [x, y] and
+``"radius"``, and ``"neck"``, the width of the widest passage into a neighbouring segment.  ``--split-out FILE`` receives the u32
+segment planes back to back (4294967295: a pixel of no region).
+
 ``--truth FILE`` grades every frame: FILE holds one u8 ground-truth class plane of the scaled frame's size per frame, back to back;
 the class plane is compared with it (``infur_compare``; ``--truth-ignore V`` leaves the pixels whose truth is V, a "void" label,
 out), every line gains ``"pixel_accuracy"`` and ``"miou"``, and one last line holds the totals of the confusion matrices added up
@@ -138,7 +144,21 @@ def main(argv=None) -> int:
                     help="add what the tolerance costs in pixels: the polygons filled back into a plane and compared with the class plane (needs --outlines-tolerance)")
     ap.add_argument("--shapes", action="store_true", help="add every region's shape descriptors (needs --regions)")
     ap.add_argument("--hulls-out", default="", help="convex hulls: per frame 4 u32 counts, then n_loops x 4 u32, then n_hull_vertices u32 (needs --shapes)")
+    ap.add_argument("--split", type=float, default=None, metavar="PX",
+                    help="separate touching objects of a region at necks narrower than PX pixels on the device (needs --regions)")
+    ap.add_argument("--split-out", default="", help="raw u32 segment planes, four bytes per pixel (needs --split)")
     a = ap.parse_args(argv)
+    if a.split_out and a.split is None:
+        ap.error("--split-out needs --split")
+    if a.split is not None:
+        if not a.regions:
+            ap.error("--split needs --regions")
+        if not 0 <= a.split <= 131070:
+            ap.error("--split: a width in pixels, 0 to 131070")
+        for given, name in ((a.sieve is not None, "--sieve"), (a.shapes, "--shapes"), (a.tracks, "--tracks"), (a.runs_out, "--runs-out"),
+                            (a.outlines_out, "--outlines-out"), (a.anchors, "--anchors"), (a.truth, "--truth")):
+            if given:
+                ap.error(f"--split does not combine with {name}: the fused split call leaves no plane on the device for it")
     if a.hulls_out and not a.shapes:
         ap.error("--hulls-out needs --shapes")
     if a.shapes:
@@ -203,7 +223,8 @@ def main(argv=None) -> int:
     from . import _lib
     from .app import RawVideoSource, VideoProcError
     from .processors import (Compare, CompareOut, confusion_summary, sieve_summary, Context, Coverage, CoverageOut, FramePath, Model, ModelCmd, Outlines, OutlinesOut, Runs, RunsOut, SegmentsFrame, Simplify, SimplifyOut,
-                             class_summary, outlines_polygons, polygon_fidelity, region_summary, shape_summary, tolerance_to_tol16, track_summary)
+                             class_summary, outlines_polygons, polygon_fidelity, region_summary, shape_summary, split_core, split_summary, tolerance_to_tol16,
+                             track_summary)
 
     tol16 = tolerance_to_tol16(a.outlines_tolerance) if a.outlines_tolerance is not None else None
 
@@ -237,7 +258,8 @@ def main(argv=None) -> int:
         grader, total = Compare(ctx, ignore_b=a.truth_ignore), np.zeros((classes, classes), np.uint64)
     rpath = None
     fhull = open(a.hulls_out, "wb") if a.hulls_out else None
-    if a.regions and (a.sieve is not None or a.shapes):
+    fsplit = open(a.split_out, "wb") if a.split_out else None
+    if a.regions and (a.sieve is not None or a.shapes or a.split is not None):
         flags = _lib.REGIONS_SKIP_BACKGROUND if a.skip_background else 0
     elif a.regions:
         oh, ow = _out_dims(ctx, a.width, a.height, a.scale)
@@ -265,6 +287,11 @@ def main(argv=None) -> int:
                                   vertex_rows=1 << 32, shape_rows=1 << 32, want_labels=freg is not None, want_klass=True, want_conf=True)
             s = SegmentsFrame(r.klass, r.conf, _class_stats(r.klass, r.conf, model.get_info().num_classes), None, None)
             labels, table, nreg = r.labels, r.table, r.n_regions
+        elif a.split is not None:  # scale -> model -> decode -> Regions -> Anchors -> Split of the label plane under its dist2, in one call
+            r = fp.advance_split(img, split_core(a.split), a.scale, decode, a.connectivity, a.min_pixels, flags, table_rows=max(0, a.max_regions),
+                                 split_rows=1 << 32, want_labels=freg is not None, want_klass=True, want_conf=True, want_segments=fsplit is not None)
+            s = SegmentsFrame(r.klass, r.conf, _class_stats(r.klass, r.conf, model.get_info().num_classes), None, None)
+            labels, table, nreg = r.labels, r.table, r.n
         elif rpath is not None:
             s, labels, table, nreg = rpath.advance(img, decode, a.connectivity, a.min_pixels, flags, flab is not None or ftruth is not None, fconf is not None,
                                                    freg is not None, keep_labels=(fruns is not None and a.runs_plane == "labels") or foutl is not None or a.anchors)
@@ -344,6 +371,19 @@ def main(argv=None) -> int:
             if fhull is not None:
                 for part in (np.array(r.counts, np.uint32), r.loops, r.vertices):
                     fhull.write(memoryview(np.ascontiguousarray(part)).cast("B"))
+        if a.split is not None:
+            sp = split_summary(r.counts)
+            rec["n_regions"], rec["regions"] = nreg, region_summary(table, nreg, ow, oh, anchors=r.anchors)
+            rec["split"] = {k: sp[k] for k in ("segments", "basins", "pairs", "marked", "split_values", "rounds", "status")}
+            rec["segments"] = [{"region": int(row[_lib.SPLIT_VALUE]), "pixels": int(row[_lib.SPLIT_PIXELS]),
+                                "first": [int(row[_lib.SPLIT_FIRST]) % ow, int(row[_lib.SPLIT_FIRST]) // ow],
+                                "anchor": [int(row[_lib.SPLIT_PEAK]) % ow, int(row[_lib.SPLIT_PEAK]) // ow],
+                                "radius": round(float(np.sqrt(row[_lib.SPLIT_HEIGHT])), 2), "neck": round(2 * float(np.sqrt(row[_lib.SPLIT_NECK])), 2)}
+                               for row in (r.segment_table if r.segment_table is not None else ())]
+            if freg is not None:
+                freg.write(memoryview(labels).cast("B"))
+            if fsplit is not None and r.segments is not None:
+                fsplit.write(memoryview(r.segments).cast("B"))
         if rpath is not None:
             rec["n_regions"] = nreg
             rec["regions"] = region_summary(table, nreg, ow, oh, anchors=anch) if a.anchors else region_summary(table, nreg, ow, oh)
@@ -383,7 +423,7 @@ def main(argv=None) -> int:
         ftruth.close()
     if a.outlines_fidelity:
         fst.write(json.dumps({"frames": n, "polygon_fidelity": fid_total}) + "\n")
-    for f in (flab, fconf, freg, ftrk, fruns, foutl, fdist, fhull, fst):
+    for f in (flab, fconf, freg, ftrk, fruns, foutl, fdist, fhull, fsplit, fst):
         if f is not None:
             f.flush()
     el = time.perf_counter() - t0

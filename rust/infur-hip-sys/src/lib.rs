@@ -304,6 +304,28 @@ pub const INFUR_RASTER_MALFORMED: u32 = 2;
 pub const INFUR_RASTER_OUTSIDE: u32 = 4;
 /// bit of `infur_features()`: the Raster calls below exist
 pub const INFUR_FEATURE_RASTER: u32 = 4096;
+/// Split: the flag, the words of a segment row and of the counts, the status bit
+pub const INFUR_SPLIT_NONE: u32 = 0xFFFF_FFFF;
+pub const INFUR_SPLIT_SKIP: u32 = 1;
+pub const INFUR_SPLIT_VALUE: u32 = 0;
+pub const INFUR_SPLIT_PIXELS: u32 = 1;
+pub const INFUR_SPLIT_FIRST: u32 = 2;
+pub const INFUR_SPLIT_PEAK: u32 = 3;
+pub const INFUR_SPLIT_HEIGHT: u32 = 4;
+pub const INFUR_SPLIT_NECK: u32 = 5;
+pub const INFUR_SPLIT_WORDS: u32 = 6;
+pub const INFUR_SPLIT_SEGMENTS: u32 = 0;
+pub const INFUR_SPLIT_BASINS: u32 = 1;
+pub const INFUR_SPLIT_PAIRS: u32 = 2;
+pub const INFUR_SPLIT_RUNS: u32 = 3;
+pub const INFUR_SPLIT_MARKED: u32 = 4;
+pub const INFUR_SPLIT_SPLIT_VALUES: u32 = 5;
+pub const INFUR_SPLIT_ROUNDS: u32 = 6;
+pub const INFUR_SPLIT_STATUS: u32 = 7;
+pub const INFUR_SPLIT_COUNT_WORDS: u32 = 8;
+pub const INFUR_SPLIT_OVERFLOW: u32 = 1;
+/// bit of `infur_features()`: the Split calls below exist
+pub const INFUR_FEATURE_SPLIT: u32 = 8192;
 
 extern "C" {
     pub fn infur_abi_version() -> u32;
@@ -626,4 +648,24 @@ extern "C" {
                              fill_value: u32, plane_out: *mut c_void, counts_out: *mut u32) -> i32;
     pub fn infur_raster_runs_dev(c: *mut infur_ctx, d_runs: *const c_void, runs_rows_in: u32, d_n_runs: *const c_void, h: u32,
                                  w: u32, elem_bytes: u32, fill_value: u32, d_plane_out: *mut c_void, d_counts_out: *mut c_void) -> i32;
+    // Split: touching objects of one value separated at their necks, a marker watershed of a u32 height plane
+    pub fn infur_split(c: *mut infur_ctx, plane: *const c_void, elem_bytes: u32, height: *const u32, h: u32, w: u32, flags: u32,
+                       skip_value: u32, core: u32, pair_slots: u32, labels_out: *mut u32, table: *mut u32, rows: u32,
+                       counts: *mut u32) -> i32;
+    pub fn infur_split_dev(c: *mut infur_ctx, d_plane: *const c_void, elem_bytes: u32, d_height: *const c_void, h: u32, w: u32,
+                           flags: u32, skip_value: u32, core: u32, pair_slots: u32, d_labels_out: *mut c_void, d_table: *mut c_void,
+                           rows: u32, d_counts: *mut c_void) -> i32;
+    pub fn infur_frame_split(c: *mut infur_ctx, bgr: *const u8, w: u32, h: u32, factor: f32, scale_mode: u32, decode: u32,
+                             connectivity: u32, min_pixels: u32, flags: u32, klass: *mut u8, conf: *mut u8, plane_capacity: usize,
+                             labels: *mut u32, labels_capacity: usize, table: *mut u64, table_rows: u32, n_regions: *mut u32,
+                             scaled_bgr: *mut u8, ow: *mut u32, oh: *mut u32, dist2: *mut u32, dist2_capacity: usize,
+                             anchors: *mut u32, core: u32, pair_slots: u32, split_labels: *mut u32, split_labels_capacity: usize,
+                             split_table: *mut u32, split_rows: u32, split_counts: *mut u32) -> i32;
+    pub fn infur_frame_split_dev(c: *mut infur_ctx, d_bgr: *const c_void, w: u32, h: u32, factor: f32, scale_mode: u32, decode: u32,
+                                 connectivity: u32, min_pixels: u32, flags: u32, d_klass: *mut c_void, d_conf: *mut c_void,
+                                 plane_capacity: usize, d_labels: *mut c_void, labels_capacity: usize, d_table: *mut c_void,
+                                 table_rows: u32, d_n_regions: *mut c_void, d_scaled_bgr: *mut c_void, ow: *mut u32, oh: *mut u32,
+                                 d_dist2: *mut c_void, dist2_capacity: usize, d_anchors: *mut c_void, core: u32, pair_slots: u32,
+                                 d_split_labels: *mut c_void, split_labels_capacity: usize, d_split_table: *mut c_void,
+                                 split_rows: u32, d_split_counts: *mut c_void) -> i32;
 }

@@ -1194,6 +1194,65 @@ impl Processor for HipRaster {
     }
 }
 
+// ---------------------------------------------------------------- Split (touching objects separated at their necks)
+/// What `HipSplit` reads: a plane of `elem_bytes` 1 or 4 with its `[w, h]` and a u32 height plane of the same size, typically
+/// `HipAnchors`' `dist2` of that plane.
+pub struct SplitInput { pub plane: Vec<u8>, pub elem_bytes: u32, pub height: Vec<u32>, pub size: [usize; 2] }
+/// What `HipSplit` produces: `labels` holds `h * w` segment ids (`INFUR_SPLIT_NONE` on skipped pixels), `table` the first
+/// `min(segments, rows)` rows of `INFUR_SPLIT_WORDS` words (VALUE, PIXELS, FIRST, PEAK, HEIGHT, NECK), `counts` the eight count
+/// words; after an overflow of the pair table (`counts[INFUR_SPLIT_STATUS] & INFUR_SPLIT_OVERFLOW`) only the counts hold anything.
+#[derive(Default)]
+pub struct Segmented { pub labels: Vec<u32>, pub table: Vec<u32>, pub counts: [u32; 8] }
+pub enum SplitCmd { Core { core: u32, skip: Option<u32>, rows: u32, pair_slots: u32 } }
+/// The stage that separates touching objects of one value at their necks: a marker watershed of the height plane as a maximum
+/// spanning forest rooted in the basins whose peak reaches `core`.  Integer results, identical from run to run.
+pub struct HipSplit { ctx: Rc<Ctx>, core: u32, skip: Option<u32>, rows: u32, pair_slots: u32, dirty: bool }
+impl HipSplit {
+    pub fn new(ctx: Rc<Ctx>) -> Self { Self { ctx, core: 0, skip: None, rows: 1024, pair_slots: 0, dirty: true } }
+}
+impl Processor for HipSplit {
+    type Command = SplitCmd;
+    type ControlError = HipError;
+    type Input = SplitInput;
+    type Output = Segmented;
+    type ProcessResult = Result<(), HipError>;
+
+    fn control(&mut self, cmd: SplitCmd) -> Result<&mut Self, HipError> {
+        let SplitCmd::Core { core, skip, rows, pair_slots } = cmd;
+        if pair_slots != 0 && (pair_slots < 64 || !pair_slots.is_power_of_two()) { return Err(HipError::status(sys::INFUR_E_INVALID_ARG)); }
+        self.dirty = self.dirty || (core, skip, rows, pair_slots) != (self.core, self.skip, self.rows, self.pair_slots);
+        self.core = core;
+        self.skip = skip;
+        self.rows = rows;
+        self.pair_slots = pair_slots;
+        Ok(self)
+    }
+    fn is_dirty(&self) -> bool { self.dirty }
+    fn advance(&mut self, inp: &SplitInput, out: &mut Segmented) -> Result<(), HipError> {
+        self.dirty = false;
+        let [w, h] = inp.size;
+        if inp.plane.len() != w * h * inp.elem_bytes as usize || inp.height.len() != w * h { return Err(HipError::status(sys::INFUR_E_SHAPE)); }
+        let rows = (self.rows as usize).min(w * h);
+        out.labels.resize(w * h, 0);
+        out.table.resize(rows * sys::INFUR_SPLIT_WORDS as usize, 0);
+        let rc = unsafe {
+            sys::infur_split(self.ctx.0, if w * h > 0 { inp.plane.as_ptr() as *const std::ffi::c_void } else { std::ptr::null() }, inp.elem_bytes,
+                             if w * h > 0 { inp.height.as_ptr() } else { std::ptr::null() }, h as u32, w as u32,
+                             if self.skip.is_some() { sys::INFUR_SPLIT_SKIP } else { 0 }, self.skip.unwrap_or(0), self.core, self.pair_slots,
+                             if w * h > 0 { out.labels.as_mut_ptr() } else { std::ptr::null_mut() },
+                             if rows > 0 { out.table.as_mut_ptr() } else { std::ptr::null_mut() }, rows as u32, out.counts.as_mut_ptr())
+        };
+        if rc != sys::INFUR_OK { return Err(HipError::from_ctx(&self.ctx, rc)); }
+        if out.counts[sys::INFUR_SPLIT_STATUS as usize] & sys::INFUR_SPLIT_OVERFLOW != 0 {
+            out.labels.clear();
+            out.table.clear();
+        } else {
+            out.table.truncate(rows.min(out.counts[sys::INFUR_SPLIT_SEGMENTS as usize] as usize) * sys::INFUR_SPLIT_WORDS as usize);
+        }
+        Ok(())
+    }
+}
+
 // ---------------------------------------------------------------- Coverage (shared borders simplified once)
 /// What `HipCoverage` produces, in `Outlines`' layout: `loops` holds `min(n_loops, loops_rows)` records (OFFSET', COUNT', VALUE,
 /// START), `vertices` the first `min(n_vertices, vertex_rows)` kept vertex ids; `n_degenerate` counts the loops with COUNT' < 3

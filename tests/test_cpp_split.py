@@ -1,0 +1,28 @@
+"""Builds tests/cpp/split_test.cpp against include/infur_processor.hpp + libinfur_hip.so with g++ and runs it."""
+import os
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def split_bin(tmp_path_factory):
+    out = str(tmp_path_factory.mktemp("cpp_split") / "split_test")
+    lib = os.path.join(ROOT, "infur_amd")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "cpp", "split_test.cpp"), "-o", out,
+                           "-L", lib, "-linfur_hip", f"-Wl,-rpath,{lib}", "-Wl,-rpath,/opt/rocm/lib"])
+    return out
+
+
+def test_cpp_split_cpu(split_bin):
+    r = subprocess.run([split_bin, "cpu"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "cpu ok" in r.stdout, r.stdout + r.stderr
+
+
+@pytest.mark.gpu
+def test_cpp_split_gpu(split_bin):
+    r = subprocess.run([split_bin, "gpu"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "gpu ok" in r.stdout, r.stdout + r.stderr
