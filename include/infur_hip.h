@@ -1491,6 +1491,95 @@ int32_t infur_frame_split_dev(infur_ctx* ctx, const void* d_bgr, uint32_t w, uin
                               void* d_split_labels, size_t split_labels_capacity, void* d_split_table, uint32_t split_rows,
                               void* d_split_counts);
 
+/* ---- Skeleton: every value of a plane thinned to one-pixel centrelines ----
+ * The stages above describe an object by its area.  For roads, lane markings, rails, cables, vessels, cracks, rivers and limbs the
+ * centreline is the object, and the questions are how long it is, where it branches, where it ends and how narrow it gets.
+ * Skeleton thins a plane on the device and measures what is left; what a host otherwise gets from skimage's skeletonize or
+ * OpenCV's thinning after pulling the plane across PCIe.  Everything is an exact integer function of the inputs: identical bytes
+ * from run to run.  Announced by infur_features() & INFUR_FEATURE_SKELETON (INFUR_ABI_VERSION does not move).
+ *
+ * INPUTS.  `plane`: h x w elements of elem_bytes = 1 or 4, h and w at most 65535; Runs' rules hold for elem_bytes, for a NULL
+ * plane, for unknown flag bits and for flags & INFUR_SKELETON_SKIP with skip_value.  `height`: NULL, or h x w uint32_t, typically
+ * Anchors' dist2 of the same plane; nothing assumes that.  `max_rounds`: at most INFUR_SKELETON_MAX_ROUNDS; 0 means min(h, w) + 2.
+ * 1 NEIGHBOURHOOD.  A pixel is SET FOR p when it lies inside the frame, is not skipped, is still alive and holds p's value.  Every
+ *   value is thinned as its own binary mask; the frame and all other values are background.  P2 .. P9 are p's neighbours N, NE, E,
+ *   SE, S, SW, W, NW, each 1 when set for p.
+ * 2 RULE (Guo and Hall 1989, algorithm A1; OpenCV's THINNING_GUOHALL).  With
+ *     C  = (!P2 & (P3|P4)) + (!P4 & (P5|P6)) + (!P6 & (P7|P8)) + (!P8 & (P9|P2))
+ *     N1 = (P9|P2) + (P3|P4) + (P5|P6) + (P7|P8),  N2 = (P2|P3) + (P4|P5) + (P6|P7) + (P8|P9),  N = min(N1, N2)
+ *     m  = (P6 | P7 | !P9) & P8 in sub-iterations 1, 3, 5, ..   and   (P2 | P3 | !P5) & P4 in sub-iterations 2, 4, 6, ..
+ *   an alive pixel dies in sub-iteration k iff C == 1 && 2 <= N && N <= 3 && !m.  At the start every pixel that is not skipped is
+ *   alive; all decisions of one sub-iteration read the state before it.
+ * 3 END.  The result is the state after sub-iteration max_rounds, or earlier once two consecutive sub-iterations removed nothing
+ *   (the state no longer changes then).  ROUNDS is the 1-based number of the last sub-iteration that removed a pixel anywhere, 0
+ *   when none did; STATUS has INFUR_SKELETON_UNFINISHED iff max_rounds < ROUNDS + 2 (with 0 replaced by its meaning).  A truncated
+ *   result is still exactly defined.  The pixels alive at the end are KEPT.
+ * OUTPUTS, each optional (NULL = not wanted, and so is table with rows == 0; nothing wanted is INFUR_E_INVALID_ARG), none needs
+ * initialisation, and a rejected call touches none:
+ *   kind_out  h*w uint8_t: 0 on a removed or skipped pixel, 1 + n on a kept one, n the number of its 8 neighbours that are kept
+ *             and of its value: 1 an isolated pixel, 2 an end, 3 a path pixel, 4 or more a junction
+ *   table     rows rows of INFUR_SKELETON_WORDS uint32_t, row v for value v < rows, all of them written: PIXELS, ENDS (n == 1),
+ *             JUNCTIONS (n >= 3), ORTHO (unordered pairs of 4-adjacent kept pixels of the value), DIAG (unordered diagonal pairs of
+ *             kept pixels of the value neither of whose two common 4-neighbours is a kept pixel of the value), FIRST (the smallest
+ *             kept index y*w + x), MIN_H and MAX_H (of the height plane over the kept pixels; 0 without one).  A value no kept
+ *             pixel holds reads (0, 0, 0, 0, 0, INFUR_SKELETON_NONE, 0, 0).  ORTHO + sqrt(2) DIAG is the length of the
+ *             centreline; MIN_H on dist2 is the squared half-width at its narrowest point
+ *   counts    INFUR_SKELETON_COUNT_WORDS uint32_t, always complete: KEPT, REMOVED, ROUNDS, ENDS, JUNCTIONS, ORTHO, DIAG, STATUS
+ * h*w == 0 writes the empty rows and zero counts.
+ * EXAMPLE.  h = 4, w = 7, flags = INFUR_SKELETON_SKIP, skip_value = 0, max_rounds = 0 (6), no height plane:
+ *     1 1 1 1 1 1 0                                  0 4 6 6 6 4 0                          0 0 0 0 0 0 0
+ *     1 1 1 1 1 1 0    after sub-iteration 1 the     0 4 6 6 6 4 0    and after 2, the      0 2 3 3 2 0 0
+ *     1 1 1 1 1 1 2    kinds would be                0 0 0 0 0 0 2    last that removes,    0 0 0 0 0 0 2
+ *     0 0 0 0 0 2 0                                  0 0 0 0 0 2 0    kind_out is           0 0 0 0 0 2 0
+ * The block of value 1 ends as a line of four pixels with three ORTHO links; the two pixels of value 2 are one DIAG link, because
+ * neither (5, 2), a removed pixel of value 1, nor (6, 3), which is skipped, is a kept pixel of value 2.  With rows = 3 the table
+ * is (0, 0, 0, 0, 0, NONE, 0, 0), (4, 2, 0, 3, 0, 8, 0, 0), (2, 2, 0, 0, 1, 20, 0, 0) and the counts are (6, 14, 2, 4, 0, 3, 1, 0).
+ * max_rounds = 2 gives the same result with STATUS = 1: two more sub-iterations would have had to confirm it.  max_rounds = 1 stops
+ * at the middle picture: counts (12, 8, 1, 2, 10, 13, 1, 1).
+ * WHAT IT DOES NOT DO.  No pruning of spurs, no Zhang-Suen or medial-axis variant, no polyline output, no stream, batch or group
+ * call. */
+#define INFUR_SKELETON_NONE 0xFFFFFFFFu
+enum { INFUR_SKELETON_SKIP = 1, INFUR_SKELETON_MAX_ROUNDS = 131072 };
+enum { INFUR_SKELETON_PIXELS = 0, INFUR_SKELETON_ENDS = 1, INFUR_SKELETON_JUNCTIONS = 2, INFUR_SKELETON_ORTHO = 3, INFUR_SKELETON_DIAG = 4,
+       INFUR_SKELETON_FIRST = 5, INFUR_SKELETON_MIN_H = 6, INFUR_SKELETON_MAX_H = 7, INFUR_SKELETON_WORDS = 8 };
+enum { INFUR_SKELETON_KEPT = 0, INFUR_SKELETON_REMOVED = 1, INFUR_SKELETON_ROUNDS = 2, INFUR_SKELETON_COUNT_ENDS = 3, INFUR_SKELETON_COUNT_JUNCTIONS = 4,
+       INFUR_SKELETON_COUNT_ORTHO = 5, INFUR_SKELETON_COUNT_DIAG = 6, INFUR_SKELETON_STATUS = 7, INFUR_SKELETON_COUNT_WORDS = 8 };
+enum { INFUR_SKELETON_UNFINISHED = 1 };
+enum { INFUR_FEATURE_SKELETON = 16384 };
+
+/* on a given plane and optional height plane, host pointers */
+int32_t infur_skeleton(infur_ctx* ctx, const void* plane, uint32_t elem_bytes, const uint32_t* height, uint32_t h, uint32_t w,
+                       uint32_t flags, uint32_t skip_value, uint32_t max_rounds, uint8_t* kind_out, uint32_t* table, uint32_t rows,
+                       uint32_t* counts);
+/* device pointers throughout; enqueued on the context's stream as launches only -- no memset, 3 + ceil(max_rounds / 8) of them
+ * (with 0 replaced by its meaning), a number fixed by the arguments: one that turns the plane into bitmaps, the thinning launches of
+ * eight sub-iterations each, one for the measures, one for the counts; a thinning launch behind one that removed nothing exits at
+ * once.  The call never synchronises and is capturable after one call outside the capture, which allocates the scratch: about one
+ * byte per pixel, owned by the context; it grows only with a request larger than any before.  This is the call that composes on the
+ * device: infur_frame_regions_dev, infur_anchors_dev on its label plane, then infur_skeleton_dev on both.  The outputs must not
+ * overlap the inputs. */
+int32_t infur_skeleton_dev(infur_ctx* ctx, const void* d_plane, uint32_t elem_bytes, const void* d_height, uint32_t h, uint32_t w,
+                           uint32_t flags, uint32_t skip_value, uint32_t max_rounds, void* d_kind_out, void* d_table, uint32_t rows,
+                           void* d_counts);
+/* The fused frame path with a centreline per object: scale -> model -> Segments decode(out[0]) -> Regions -> Anchors of the label
+ * plane with INFUR_REGION_NONE skipped -> Skeleton of the label plane under dist2, INFUR_REGION_NONE skipped, in one call: row i of
+ * skel_table belongs to region i.  The arguments are infur_frame_anchors' own, then max_rounds and Skeleton's outputs
+ * (kind_capacity in bytes, ow*oh needed; less is INFUR_E_CAPACITY).  Every output is optional; the label and distance planes go to
+ * scratch of the library's own when the caller does not want them.  The calls inherit infur_frame_anchors' checks and errors and
+ * its rule for a context without a model, always enqueue eagerly and leave the graphs cached for infur_frame_advance_dev alone. */
+int32_t infur_frame_skeleton(infur_ctx* ctx, const uint8_t* bgr, uint32_t w, uint32_t h, float factor, uint32_t scale_mode,
+                             uint32_t decode, uint32_t connectivity, uint32_t min_pixels, uint32_t flags, uint8_t* klass,
+                             uint8_t* conf, size_t plane_capacity, uint32_t* labels, size_t labels_capacity, uint64_t* table,
+                             uint32_t table_rows, uint32_t* n_regions, uint8_t* scaled_bgr, uint32_t* ow, uint32_t* oh,
+                             uint32_t* dist2, size_t dist2_capacity, uint32_t* anchors, uint32_t max_rounds, uint8_t* kind,
+                             size_t kind_capacity, uint32_t* skel_table, uint32_t skel_rows, uint32_t* skel_counts);
+int32_t infur_frame_skeleton_dev(infur_ctx* ctx, const void* d_bgr, uint32_t w, uint32_t h, float factor, uint32_t scale_mode,
+                                 uint32_t decode, uint32_t connectivity, uint32_t min_pixels, uint32_t flags, void* d_klass,
+                                 void* d_conf, size_t plane_capacity, void* d_labels, size_t labels_capacity, void* d_table,
+                                 uint32_t table_rows, void* d_n_regions, void* d_scaled_bgr, uint32_t* ow, uint32_t* oh,
+                                 void* d_dist2, size_t dist2_capacity, void* d_anchors, uint32_t max_rounds, void* d_kind,
+                                 size_t kind_capacity, void* d_skel_table, uint32_t skel_rows, void* d_skel_counts);
+
 /* ---- streaming (infur/src/main.rs:27-99,105): bounded queue, copies overlapped with compute ----
  * The reference back-pressures its producer with sync_channel(2) (main.rs:105); a stream
  * here is a ring of `depth` pinned + device slots.  submit() copies the caller's frame into a

@@ -1016,6 +1016,56 @@ private:
     bool dirty_ = true;
 };
 
+/// What `Skeleton` produces: `kind` holds height * width bytes (0 removed or skipped, 1 + kept neighbours of the value: 2 an end,
+/// 3 a path pixel, 4 or more a junction), `table` `rows` rows of INFUR_SKELETON_WORDS words, row v for value v (PIXELS, ENDS,
+/// JUNCTIONS, ORTHO, DIAG, FIRST, MIN_H, MAX_H), `counts` the eight count words.
+struct SkeletonOut {
+    uint32_t width = 0, height = 0, rows = 256;  // rows: the table rows wanted
+    std::vector<uint8_t> kind;
+    std::vector<uint32_t> table;
+    uint32_t counts[INFUR_SKELETON_COUNT_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
+    bool unfinished() const { return (counts[INFUR_SKELETON_STATUS] & INFUR_SKELETON_UNFINISHED) != 0; }
+    const uint32_t* row(uint32_t v) const { return table.data() + (size_t)v * INFUR_SKELETON_WORDS; }
+    /// ORTHO + sqrt(2) DIAG of value v, in pixels
+    double length(uint32_t v) const { return row(v)[INFUR_SKELETON_ORTHO] + 1.4142135623730951 * row(v)[INFUR_SKELETON_DIAG]; }
+};
+
+/// The stage that thins every value of a plane to one-pixel centrelines by Guo and Hall's rule and measures them.  Integer results,
+/// identical from run to run.  Command = the sub-iterations allowed (0: min(h, w) + 2) and the skipped value; Input = a plane of 1-
+/// or 4-byte elements and an optional height plane of its size (nullptr: none); Output = SkeletonOut.
+class Skeleton {
+public:
+    struct Cmd {
+        enum Kind { Rounds } kind;
+        uint32_t max_rounds;
+        bool skip;
+        uint32_t skip_value;
+    };
+    explicit Skeleton(Context& c) : c_(c) {}
+    Status control(Cmd cmd) {
+        if (cmd.kind != Cmd::Rounds || cmd.max_rounds > INFUR_SKELETON_MAX_ROUNDS) return INFUR_E_INVALID_ARG;
+        dirty_ = dirty_ || cmd.max_rounds != cmd_.max_rounds || cmd.skip != cmd_.skip || cmd.skip_value != cmd_.skip_value;
+        cmd_ = cmd;
+        return INFUR_OK;
+    }
+    bool is_dirty() const { return dirty_; }
+    Status advance(const void* plane, uint32_t elem_bytes, const uint32_t* height, uint32_t h, uint32_t w, SkeletonOut& out) {
+        dirty_ = false;
+        const size_t npix = (size_t)h * w;
+        out.width = w;
+        out.height = h;
+        out.kind.assign(npix, 0);
+        out.table.assign((size_t)out.rows * INFUR_SKELETON_WORDS, 0);
+        return infur_skeleton(c_.get(), plane, elem_bytes, height, h, w, cmd_.skip ? INFUR_SKELETON_SKIP : 0, cmd_.skip_value, cmd_.max_rounds,
+                              npix ? out.kind.data() : nullptr, out.rows ? out.table.data() : nullptr, out.rows, out.counts);
+    }
+
+private:
+    Context& c_;
+    Cmd cmd_{Cmd::Rounds, 0, false, 0};
+    bool dirty_ = true;
+};
+
 /// What `Coverage` produces, in Outlines' layout: `loops` holds min(n_loops, loops_rows) records (OFFSET', COUNT', VALUE, START),
 /// `vertices` the first min(n_vertices, vertex_rows) kept vertex ids; n_degenerate counts the loops with COUNT' < 3 (skip them);
 /// status: INFUR_COVERAGE_TRUNCATED and INFUR_COVERAGE_OVERFLOW (nothing was produced), INFUR_COVERAGE_MALFORMED; n_aug: the

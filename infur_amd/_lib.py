@@ -126,6 +126,16 @@ SPLIT_VALUE, SPLIT_PIXELS, SPLIT_FIRST, SPLIT_PEAK, SPLIT_HEIGHT, SPLIT_NECK, SP
 SPLIT_OVERFLOW = 1
 SPLIT_NONE = 0xFFFFFFFF
 FEATURE_SPLIT = 8192
+# Skeleton (infur_skeleton / infur_frame_skeleton): the flag, the words of a value's row and of the counts, the status bit, the feature bit
+SKELETON_SKIP = 1
+(SKELETON_PIXELS, SKELETON_ENDS, SKELETON_JUNCTIONS, SKELETON_ORTHO, SKELETON_DIAG, SKELETON_FIRST, SKELETON_MIN_H, SKELETON_MAX_H,
+ SKELETON_WORDS) = 0, 1, 2, 3, 4, 5, 6, 7, 8
+(SKELETON_KEPT, SKELETON_REMOVED, SKELETON_ROUNDS, SKELETON_COUNT_ENDS, SKELETON_COUNT_JUNCTIONS, SKELETON_COUNT_ORTHO, SKELETON_COUNT_DIAG,
+ SKELETON_STATUS, SKELETON_COUNT_WORDS) = 0, 1, 2, 3, 4, 5, 6, 7, 8
+SKELETON_UNFINISHED = 1
+SKELETON_NONE = 0xFFFFFFFF
+SKELETON_MAX_ROUNDS = 131072
+FEATURE_SKELETON = 16384
 
 
 class Options(C.Structure):
@@ -302,6 +312,12 @@ SIGNATURES = {
                                       _u32p, _u32p, _vp, _sz, _vp, _u32, _u32, _vp, _sz, _vp, _u32, _vp]),
     "infur_frame_split_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp, _vp,
                                           _u32p, _u32p, _vp, _sz, _vp, _u32, _u32, _vp, _sz, _vp, _u32, _vp]),
+    "infur_skeleton": (C.c_int32, [_vp, _vp, _u32, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _u32, _vp]),
+    "infur_skeleton_dev": (C.c_int32, [_vp, _vp, _u32, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _u32, _vp]),
+    "infur_frame_skeleton": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp, _vp,
+                                         _u32p, _u32p, _vp, _sz, _vp, _u32, _vp, _sz, _vp, _u32, _vp]),
+    "infur_frame_skeleton_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp, _vp,
+                                             _u32p, _u32p, _vp, _sz, _vp, _u32, _vp, _sz, _vp, _u32, _vp]),
     "infur_stream_create": (C.c_int32, [_vp, _u32, C.POINTER(_vp)]),
     "infur_stream_destroy": (None, [_vp]),
     "infur_stream_add_lane": (C.c_int32, [_vp, _vp]),

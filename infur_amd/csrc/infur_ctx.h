@@ -203,6 +203,9 @@ struct infur_ctx {
     // Split (infur_split.cpp): the ascent pointers, the union-find over basins, the saddle table and the per-root words; the label and
     // distance planes the frame calls let the caller leave out; the host-pointer calls' staging.  Private like the above.
     infur::Buf st_split, st_split_plane, st_split_io;
+    // Skeleton (infur_skeleton.cpp): the two alive bitmaps, the four relation planes and the tile flags; the label and distance planes
+    // of the frame calls; the host-pointer calls' staging.  Private like the above.
+    infur::Buf st_skel, st_skel_plane, st_skel_io;
     // Tracks (infur_tracks.cpp): the live trackers of this context; infur_ctx_destroy releases their device memory and orphans them
     std::vector<infur_tracker*> trackers;
 

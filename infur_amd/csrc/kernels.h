@@ -489,6 +489,23 @@ unsigned split_launches(size_t npix, unsigned pair_slots, bool labels, bool tabl
 hipError_t launch_split(const void* plane, int elem_bytes, const unsigned* height, unsigned H, unsigned W, int skip, unsigned skip_value, unsigned core,
                         void* scratch, unsigned pair_slots, unsigned* labels, unsigned* table, unsigned rows, unsigned* counts, hipStream_t s);
 
+// Skeleton (skeleton.hip): every value of an H x W plane (both at most 65535) of 1- or 4-byte elements thinned to one-pixel centrelines
+// by Guo and Hall's rule of include/infur_hip.h, for max_rounds (1 .. kSkeletonMaxRounds) sub-iterations.  height: a u32 plane or
+// null.  kind: H * W bytes (0 removed or skipped, 1 + kept neighbours of the value); table: rows rows of kSkeletonWords u32 (PIXELS,
+// ENDS, JUNCTIONS, ORTHO, DIAG, FIRST, MIN_H, MAX_H), row v for value v; counts[kSkeletonCountWords] = {KEPT, REMOVED, ROUNDS, ENDS,
+// JUNCTIONS, ORTHO, DIAG, STATUS} (each optional).  scratch: skeleton_scratch_bytes(..).  Stream-ordered, no memset;
+// 3 + skeleton_thin_launches(max_rounds) launches, kSkeletonK sub-iterations in each thin one; a thin launch behind one that removed
+// nothing exits on a device word.
+constexpr int kSkeletonWords = 8;
+constexpr int kSkeletonCountWords = 8;
+constexpr unsigned kSkeletonUnfinished = 1u;
+constexpr int kSkeletonK = 8;
+constexpr unsigned kSkeletonMaxRounds = 131072u;
+size_t skeleton_scratch_bytes(unsigned H, unsigned W);
+unsigned skeleton_thin_launches(unsigned max_rounds);
+hipError_t launch_skeleton(const void* plane, int elem_bytes, const unsigned* height, unsigned H, unsigned W, int skip, unsigned skip_value,
+                           unsigned max_rounds, void* scratch, uint8_t* kind, unsigned* table, unsigned rows, unsigned* counts, hipStream_t s);
+
 // Coverage (coverage.hip): Outlines' loops of an H x W plane (both in [1, 8191]) of 1- or 4-byte elements, simplified within
 // tol16 / 16 pixels so that neighbouring polygons still fit: the loops are cut at the plane's junctions and every arc between
 // two of them is simplified by a rule that does not depend on the direction of travel.  Inputs as launch_simplify's plus the

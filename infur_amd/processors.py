@@ -1430,6 +1430,109 @@ class SplitFrame(NamedTuple):
     counts: Optional[np.ndarray]
 
 
+@dataclass
+class SkeletonCmd:
+    """``Skeleton``'s command: ``max_rounds`` (0: the library's min(h, w) + 2) and ``skip``, the value that is background (None:
+    every value is thinned)."""
+
+    max_rounds: int = 0
+    skip: Optional[int] = None
+
+
+class SkeletonOut:
+    """``Skeleton``'s ``&mut Output``: what to produce (``want_kind``, ``rows`` table rows, ``want_counts``) and, after ``advance``,
+    ``kind`` [H, W] u8 (0 removed or skipped, 1 + kept neighbours of the value), ``table`` [rows, 8] u32 (``_lib.SKELETON_PIXELS`` ..
+    ``_lib.SKELETON_MAX_H``, row v for value v), ``counts`` [8] u32 (``_lib.SKELETON_KEPT`` .. ``_lib.SKELETON_STATUS``); None for
+    what was not wanted."""
+
+    def __init__(self, want_kind: bool = True, rows: int = 256, want_counts: bool = True):
+        self.want_kind, self.rows, self.want_counts = want_kind, rows, want_counts
+        self.kind = self.table = self.counts = None
+
+
+class Skeleton(Processor):
+    """The stage that thins every value of a plane to one-pixel centrelines (Guo and Hall's rule) and measures them: ends,
+    junctions and link counts per value, and the range of a height plane -- typically ``Anchors``' ``dist2`` -- along them.
+
+    Command = ``SkeletonCmd``.  Input = plane [H, W] u8 or u32, or (plane, height [H, W] u32); Output = ``SkeletonOut``.  Integers
+    throughout, identical from run to run.  ``skeleton_summary`` turns the rows into lengths and widths.
+    """
+
+    def __init__(self, ctx: Context, max_rounds: int = 0, skip: Optional[int] = None):
+        self.ctx = ctx
+        self.max_rounds, self.skip = max_rounds, skip
+        self.dirty = True
+
+    def control(self, cmd: SkeletonCmd) -> "Skeleton":
+        if not 0 <= cmd.max_rounds <= _lib.SKELETON_MAX_ROUNDS:
+            raise InfurError(_lib.E_INVALID_ARG, f"max_rounds {cmd.max_rounds}: 0 to {_lib.SKELETON_MAX_ROUNDS}")
+        if cmd.skip is not None and not 0 <= cmd.skip <= 0xFFFFFFFF:
+            raise InfurError(_lib.E_INVALID_ARG, f"skip {cmd.skip}: a u32")
+        self.dirty = self.dirty or (cmd.max_rounds, cmd.skip) != (self.max_rounds, self.skip)
+        self.max_rounds, self.skip = cmd.max_rounds, cmd.skip
+        return self
+
+    def is_dirty(self) -> bool:
+        return self.dirty
+
+    def advance(self, inp, out: SkeletonOut) -> None:
+        self.dirty = False
+        plane, height = inp if isinstance(inp, tuple) else (inp, None)
+        if plane.ndim != 2 or plane.dtype.itemsize not in (1, 4) or plane.dtype.kind not in "ui" or (height is not None and height.shape != plane.shape):
+            raise InfurError(_lib.E_SHAPE, f"expected an [H,W] plane of 1- or 4-byte integers and no height plane or one of its size, got {plane.shape} "
+                                           f"{plane.dtype}")
+        plane = np.ascontiguousarray(plane)
+        height = np.ascontiguousarray(height, np.uint32) if height is not None else None
+        h, w = plane.shape
+        rows = max(0, int(out.rows))
+        kind = np.empty((h, w), np.uint8) if out.want_kind else None
+        table = np.empty((rows, _lib.SKELETON_WORDS), np.uint32) if rows else None
+        counts = np.zeros(_lib.SKELETON_COUNT_WORDS, np.uint32)
+        self.ctx.check(self.ctx.L.infur_skeleton(self.ctx.h, _ptr_some(plane), plane.dtype.itemsize, _ptr_some(height) if height is not None else None, h, w,
+                                                 _lib.SKELETON_SKIP if self.skip is not None else 0, self.skip or 0, self.max_rounds, _ptr(kind),
+                                                 _ptr_some(table), rows, counts.ctypes.data))
+        out.kind, out.table = kind, table
+        out.counts = counts if out.want_counts else None
+
+
+def skeleton_summary(table: np.ndarray, counts: Optional[np.ndarray] = None) -> list:
+    """One record per row of ``Skeleton``'s table that holds kept pixels: ``value``, ``pixels``, ``length`` (ORTHO + sqrt(2) DIAG
+    pixels), ``ends``, ``junctions``, ``first`` (index), and ``narrowest`` / ``widest``: 2 sqrt of MIN_H / MAX_H, the widths of the
+    object at the narrowest and widest point of its centreline when the height plane was ``dist2``.  With ``counts`` the first
+    record is the frame's: ``kept``, ``removed``, ``rounds``, ``unfinished`` and the total ``length``."""
+    recs = []
+    if counts is not None:
+        c = [int(v) for v in np.asarray(counts).ravel()[:_lib.SKELETON_COUNT_WORDS]]
+        recs.append({"kept": c[_lib.SKELETON_KEPT], "removed": c[_lib.SKELETON_REMOVED], "rounds": c[_lib.SKELETON_ROUNDS],
+                     "ends": c[_lib.SKELETON_COUNT_ENDS], "junctions": c[_lib.SKELETON_COUNT_JUNCTIONS],
+                     "length": round(c[_lib.SKELETON_COUNT_ORTHO] + float(np.sqrt(2.0)) * c[_lib.SKELETON_COUNT_DIAG], 2),
+                     "unfinished": bool(c[_lib.SKELETON_STATUS] & _lib.SKELETON_UNFINISHED)})
+    for v, row in enumerate(np.asarray(table).reshape(-1, _lib.SKELETON_WORDS) if table is not None else ()):
+        if row[_lib.SKELETON_PIXELS]:
+            recs.append({"value": v, "pixels": int(row[_lib.SKELETON_PIXELS]),
+                         "length": round(int(row[_lib.SKELETON_ORTHO]) + float(np.sqrt(2.0)) * int(row[_lib.SKELETON_DIAG]), 2),
+                         "ends": int(row[_lib.SKELETON_ENDS]), "junctions": int(row[_lib.SKELETON_JUNCTIONS]), "first": int(row[_lib.SKELETON_FIRST]),
+                         "narrowest": round(2 * float(np.sqrt(row[_lib.SKELETON_MIN_H])), 2), "widest": round(2 * float(np.sqrt(row[_lib.SKELETON_MAX_H])), 2)})
+    return recs
+
+
+class SkeletonFrame(NamedTuple):
+    """``FramePath.advance_skeleton``: ``AnchorsFrame``'s fields, then the kind plane [oh, ow] u8, the centreline rows
+    [min(skeleton_rows, oh * ow), 8] u32, row i for region i, and Skeleton's counts [8] u32"""
+
+    klass: Optional[np.ndarray]
+    conf: Optional[np.ndarray]
+    labels: Optional[np.ndarray]
+    table: Optional[np.ndarray]
+    n: Optional[int]
+    scaled: Optional[np.ndarray]
+    dist2: Optional[np.ndarray]
+    anchors: Optional[np.ndarray]
+    kind: Optional[np.ndarray]
+    skeleton_table: Optional[np.ndarray]
+    counts: Optional[np.ndarray]
+
+
 def runs_decode(runs: np.ndarray, n: int, h: int, w: int, fill: int = 0, dtype=None) -> np.ndarray:
     """The dense [h, w] plane of the first ``min(n, len(runs))`` records; pixels no record covers (skipped or truncated runs) read
     ``fill``.  ``dtype``: uint8 when every value and ``fill`` fit a byte, else uint32."""
@@ -2168,6 +2271,36 @@ class FramePath:
         segments, stable = _split_result(segments, stable, counts)
         return SplitFrame(klass, conf, labels, table[:k] if table is not None else None, n.value, scaled, dist2,
                           anchors[:k] if anchors is not None else None, segments, stable, counts)
+
+    def advance_skeleton(self, img: np.ndarray, factor: float = 1.0, decode: int = _lib.DECODE_RAW, connectivity: int = _lib.CONNECT_8,
+                         min_pixels: int = 0, flags: int = 0, table_rows: int = 1024, skeleton_rows: int = 1024, max_rounds: int = 0,
+                         want_labels: bool = False, want_klass: bool = True, want_conf: bool = False, want_scaled: bool = False,
+                         want_dist2: bool = False, want_kind: bool = True) -> SkeletonFrame:
+        """The fused path with a centreline per object, scale -> model -> Segments decode -> Regions -> Anchors of the label plane
+        -> Skeleton of the label plane under its ``dist2``, in one call -> ``SkeletonFrame``; every result field is None when no
+        model is loaded (``scaled`` is still produced)."""
+        img, w, h, f, ow, oh = self._front(img, factor)
+        npix = oh.value * ow.value
+        rows, srows = max(0, min(int(table_rows), npix)), max(0, min(int(skeleton_rows), npix))
+        klass, conf = self._plane(ow, oh, want_klass), self._plane(ow, oh, want_conf)
+        labels = self._plane(ow, oh, want_labels, np.uint32)
+        table = np.zeros((rows, _lib.REGION_WORDS), np.uint64) if rows else None
+        scaled = self._plane(ow, oh, want_scaled, channels=3)
+        dist2 = self._plane(ow, oh, want_dist2, np.uint32)
+        anchors = np.empty((rows, _lib.ANCHOR_WORDS), np.uint32) if rows else None
+        kind = self._plane(ow, oh, want_kind)
+        stable = np.empty((srows, _lib.SKELETON_WORDS), np.uint32) if srows else None
+        counts = np.zeros(_lib.SKELETON_COUNT_WORDS, np.uint32)
+        n = C.c_uint32(0)
+        rc = self.ctx.L.infur_frame_skeleton(self.ctx.h, img.ctypes.data, w, h, f, self.scale_mode, decode, connectivity, min_pixels, flags,
+                                             _ptr(klass), _ptr(conf), npix, _ptr(labels), npix * 4, _ptr(table), rows, C.addressof(n), _ptr(scaled),
+                                             C.byref(ow), C.byref(oh), _ptr(dist2), npix * 4, _ptr(anchors), max_rounds, _ptr(kind), npix,
+                                             _ptr(stable), srows, counts.ctypes.data)
+        if not self._loaded(rc):
+            return SkeletonFrame(None, None, None, None, None, scaled, None, None, None, None, None)
+        k = min(n.value, rows)
+        return SkeletonFrame(klass, conf, labels, table[:k] if table is not None else None, n.value, scaled, dist2,
+                             anchors[:k] if anchors is not None else None, kind, stable, counts)
 
     def advance_shapes(self, img: np.ndarray, factor: float = 1.0, decode: int = _lib.DECODE_RAW, connectivity: int = _lib.CONNECT_8,
                        min_pixels: int = 0, flags: int = 0, table_rows: int = 1024, max_edges: int = 0, loops_rows: int = 1 << 16,

@@ -60,6 +60,12 @@ counts) and ``"segments"``, one record per object with its ``"region"``, ``"pixe
 ``"radius"``, and ``"neck"``, the width of the widest passage into a neighbouring segment.  ``--split-out FILE`` receives the u32
 segment planes back to back (4294967295: a pixel of no region).
 
+``--skeleton`` (needs ``--regions``) thins every region to its one-pixel centreline: the frame goes through ``infur_frame_skeleton``
+(Regions -> Anchors -> Skeleton), every line gains ``"skeleton"`` (the frame's kept and removed pixels, rounds, ends, junctions,
+length and whether ``--skeleton-rounds N`` ran out; 0: the library's bound) and ``"centrelines"``, one record per region with its
+``"length"``, ``"ends"``, ``"junctions"`` and the ``"narrowest"`` and ``"widest"`` width along the line.  ``--skeleton-out FILE``
+receives the u8 kind planes back to back (0: no centreline, 2: an end, 3: a path pixel, 4 or more: a junction).
+
 ``--truth FILE`` grades every frame: FILE holds one u8 ground-truth class plane of the scaled frame's size per frame, back to back;
 the class plane is compared with it (``infur_compare``; ``--truth-ignore V`` leaves the pixels whose truth is V, a "void" label,
 out), every line gains ``"pixel_accuracy"`` and ``"miou"``, and one last line holds the totals of the confusion matrices added up
@@ -147,7 +153,21 @@ def main(argv=None) -> int:
     ap.add_argument("--split", type=float, default=None, metavar="PX",
                     help="separate touching objects of a region at necks narrower than PX pixels on the device (needs --regions)")
     ap.add_argument("--split-out", default="", help="raw u32 segment planes, four bytes per pixel (needs --split)")
+    ap.add_argument("--skeleton", action="store_true", help="thin every region to its one-pixel centreline on the device (needs --regions)")
+    ap.add_argument("--skeleton-out", default="", help="raw u8 kind planes, one byte per pixel (needs --skeleton)")
+    ap.add_argument("--skeleton-rounds", type=int, default=0, metavar="N", help="at most N sub-iterations (0: the library's bound; needs --skeleton)")
     a = ap.parse_args(argv)
+    if (a.skeleton_out or a.skeleton_rounds) and not a.skeleton:
+        ap.error("--skeleton-out and --skeleton-rounds need --skeleton")
+    if a.skeleton:
+        if not a.regions:
+            ap.error("--skeleton needs --regions")
+        if not 0 <= a.skeleton_rounds <= 131072:
+            ap.error("--skeleton-rounds: 0 to 131072")
+        for given, name in ((a.sieve is not None, "--sieve"), (a.shapes, "--shapes"), (a.tracks, "--tracks"), (a.runs_out, "--runs-out"),
+                            (a.outlines_out, "--outlines-out"), (a.anchors, "--anchors"), (a.truth, "--truth"), (a.split is not None, "--split")):
+            if given:
+                ap.error(f"--skeleton does not combine with {name}: the fused skeleton call leaves no plane on the device for it")
     if a.split_out and a.split is None:
         ap.error("--split-out needs --split")
     if a.split is not None:
@@ -223,7 +243,7 @@ def main(argv=None) -> int:
     from . import _lib
     from .app import RawVideoSource, VideoProcError
     from .processors import (Compare, CompareOut, confusion_summary, sieve_summary, Context, Coverage, CoverageOut, FramePath, Model, ModelCmd, Outlines, OutlinesOut, Runs, RunsOut, SegmentsFrame, Simplify, SimplifyOut,
-                             class_summary, outlines_polygons, polygon_fidelity, region_summary, shape_summary, split_core, split_summary, tolerance_to_tol16,
+                             class_summary, outlines_polygons, polygon_fidelity, region_summary, shape_summary, skeleton_summary, split_core, split_summary, tolerance_to_tol16,
                              track_summary)
 
     tol16 = tolerance_to_tol16(a.outlines_tolerance) if a.outlines_tolerance is not None else None
@@ -259,7 +279,8 @@ def main(argv=None) -> int:
     rpath = None
     fhull = open(a.hulls_out, "wb") if a.hulls_out else None
     fsplit = open(a.split_out, "wb") if a.split_out else None
-    if a.regions and (a.sieve is not None or a.shapes or a.split is not None):
+    fskel = open(a.skeleton_out, "wb") if a.skeleton_out else None
+    if a.regions and (a.sieve is not None or a.shapes or a.split is not None or a.skeleton):
         flags = _lib.REGIONS_SKIP_BACKGROUND if a.skip_background else 0
     elif a.regions:
         oh, ow = _out_dims(ctx, a.width, a.height, a.scale)
@@ -290,6 +311,11 @@ def main(argv=None) -> int:
         elif a.split is not None:  # scale -> model -> decode -> Regions -> Anchors -> Split of the label plane under its dist2, in one call
             r = fp.advance_split(img, split_core(a.split), a.scale, decode, a.connectivity, a.min_pixels, flags, table_rows=max(0, a.max_regions),
                                  split_rows=1 << 32, want_labels=freg is not None, want_klass=True, want_conf=True, want_segments=fsplit is not None)
+            s = SegmentsFrame(r.klass, r.conf, _class_stats(r.klass, r.conf, model.get_info().num_classes), None, None)
+            labels, table, nreg = r.labels, r.table, r.n
+        elif a.skeleton:  # scale -> model -> decode -> Regions -> Anchors -> Skeleton of the label plane under its dist2, in one call
+            r = fp.advance_skeleton(img, a.scale, decode, a.connectivity, a.min_pixels, flags, table_rows=max(0, a.max_regions), skeleton_rows=max(0, a.max_regions),
+                                    max_rounds=a.skeleton_rounds, want_labels=freg is not None, want_klass=True, want_conf=True, want_kind=fskel is not None)
             s = SegmentsFrame(r.klass, r.conf, _class_stats(r.klass, r.conf, model.get_info().num_classes), None, None)
             labels, table, nreg = r.labels, r.table, r.n
         elif rpath is not None:
@@ -384,6 +410,14 @@ def main(argv=None) -> int:
                 freg.write(memoryview(labels).cast("B"))
             if fsplit is not None and r.segments is not None:
                 fsplit.write(memoryview(r.segments).cast("B"))
+        if a.skeleton:
+            sk = skeleton_summary(r.skeleton_table[:nreg] if r.skeleton_table is not None else None, r.counts)
+            rec["n_regions"], rec["regions"] = nreg, region_summary(table, nreg, ow, oh, anchors=r.anchors)
+            rec["skeleton"], rec["centrelines"] = sk[0], [dict(c, region=c.pop("value"), first=[c["first"] % ow, c["first"] // ow]) for c in sk[1:]]
+            if freg is not None:
+                freg.write(memoryview(labels).cast("B"))
+            if fskel is not None and r.kind is not None:
+                fskel.write(memoryview(r.kind).cast("B"))
         if rpath is not None:
             rec["n_regions"] = nreg
             rec["regions"] = region_summary(table, nreg, ow, oh, anchors=anch) if a.anchors else region_summary(table, nreg, ow, oh)
@@ -423,7 +457,7 @@ def main(argv=None) -> int:
         ftruth.close()
     if a.outlines_fidelity:
         fst.write(json.dumps({"frames": n, "polygon_fidelity": fid_total}) + "\n")
-    for f in (flab, fconf, freg, ftrk, fruns, foutl, fdist, fhull, fsplit, fst):
+    for f in (flab, fconf, freg, ftrk, fruns, foutl, fdist, fhull, fsplit, fskel, fst):
         if f is not None:
             f.flush()
     el = time.perf_counter() - t0

@@ -326,6 +326,31 @@ pub const INFUR_SPLIT_COUNT_WORDS: u32 = 8;
 pub const INFUR_SPLIT_OVERFLOW: u32 = 1;
 /// bit of `infur_features()`: the Split calls below exist
 pub const INFUR_FEATURE_SPLIT: u32 = 8192;
+/// Skeleton: the flag, the words of a value's row and of the counts, the status bit
+pub const INFUR_SKELETON_NONE: u32 = 0xFFFF_FFFF;
+pub const INFUR_SKELETON_MAX_ROUNDS: u32 = 131072;
+pub const INFUR_SKELETON_SKIP: u32 = 1;
+pub const INFUR_SKELETON_PIXELS: u32 = 0;
+pub const INFUR_SKELETON_ENDS: u32 = 1;
+pub const INFUR_SKELETON_JUNCTIONS: u32 = 2;
+pub const INFUR_SKELETON_ORTHO: u32 = 3;
+pub const INFUR_SKELETON_DIAG: u32 = 4;
+pub const INFUR_SKELETON_FIRST: u32 = 5;
+pub const INFUR_SKELETON_MIN_H: u32 = 6;
+pub const INFUR_SKELETON_MAX_H: u32 = 7;
+pub const INFUR_SKELETON_WORDS: u32 = 8;
+pub const INFUR_SKELETON_KEPT: u32 = 0;
+pub const INFUR_SKELETON_REMOVED: u32 = 1;
+pub const INFUR_SKELETON_ROUNDS: u32 = 2;
+pub const INFUR_SKELETON_COUNT_ENDS: u32 = 3;
+pub const INFUR_SKELETON_COUNT_JUNCTIONS: u32 = 4;
+pub const INFUR_SKELETON_COUNT_ORTHO: u32 = 5;
+pub const INFUR_SKELETON_COUNT_DIAG: u32 = 6;
+pub const INFUR_SKELETON_STATUS: u32 = 7;
+pub const INFUR_SKELETON_COUNT_WORDS: u32 = 8;
+pub const INFUR_SKELETON_UNFINISHED: u32 = 1;
+/// bit of `infur_features()`: the Skeleton calls below exist
+pub const INFUR_FEATURE_SKELETON: u32 = 16384;
 
 extern "C" {
     pub fn infur_abi_version() -> u32;
@@ -668,4 +693,23 @@ extern "C" {
                                  d_dist2: *mut c_void, dist2_capacity: usize, d_anchors: *mut c_void, core: u32, pair_slots: u32,
                                  d_split_labels: *mut c_void, split_labels_capacity: usize, d_split_table: *mut c_void,
                                  split_rows: u32, d_split_counts: *mut c_void) -> i32;
+    // Skeleton: every value of a plane thinned to one-pixel centrelines (Guo and Hall), with ends, junctions and lengths per value
+    pub fn infur_skeleton(c: *mut infur_ctx, plane: *const c_void, elem_bytes: u32, height: *const u32, h: u32, w: u32, flags: u32,
+                          skip_value: u32, max_rounds: u32, kind_out: *mut u8, table: *mut u32, rows: u32, counts: *mut u32) -> i32;
+    pub fn infur_skeleton_dev(c: *mut infur_ctx, d_plane: *const c_void, elem_bytes: u32, d_height: *const c_void, h: u32, w: u32,
+                              flags: u32, skip_value: u32, max_rounds: u32, d_kind_out: *mut c_void, d_table: *mut c_void, rows: u32,
+                              d_counts: *mut c_void) -> i32;
+    pub fn infur_frame_skeleton(c: *mut infur_ctx, bgr: *const u8, w: u32, h: u32, factor: f32, scale_mode: u32, decode: u32,
+                                connectivity: u32, min_pixels: u32, flags: u32, klass: *mut u8, conf: *mut u8, plane_capacity: usize,
+                                labels: *mut u32, labels_capacity: usize, table: *mut u64, table_rows: u32, n_regions: *mut u32,
+                                scaled_bgr: *mut u8, ow: *mut u32, oh: *mut u32, dist2: *mut u32, dist2_capacity: usize,
+                                anchors: *mut u32, max_rounds: u32, kind: *mut u8, kind_capacity: usize, skel_table: *mut u32,
+                                skel_rows: u32, skel_counts: *mut u32) -> i32;
+    pub fn infur_frame_skeleton_dev(c: *mut infur_ctx, d_bgr: *const c_void, w: u32, h: u32, factor: f32, scale_mode: u32, decode: u32,
+                                    connectivity: u32, min_pixels: u32, flags: u32, d_klass: *mut c_void, d_conf: *mut c_void,
+                                    plane_capacity: usize, d_labels: *mut c_void, labels_capacity: usize, d_table: *mut c_void,
+                                    table_rows: u32, d_n_regions: *mut c_void, d_scaled_bgr: *mut c_void, ow: *mut u32, oh: *mut u32,
+                                    d_dist2: *mut c_void, dist2_capacity: usize, d_anchors: *mut c_void, max_rounds: u32,
+                                    d_kind: *mut c_void, kind_capacity: usize, d_skel_table: *mut c_void, skel_rows: u32,
+                                    d_skel_counts: *mut c_void) -> i32;
 }

@@ -1253,6 +1253,59 @@ impl Processor for HipSplit {
     }
 }
 
+// ---------------------------------------------------------------- Skeleton (every value thinned to one-pixel centrelines)
+/// What `HipSkeleton` reads: a plane of `elem_bytes` 1 or 4 with its `[w, h]` and, optionally, a u32 height plane of the same
+/// size, typically `HipAnchors`' `dist2` of that plane.
+pub struct SkeletonInput { pub plane: Vec<u8>, pub elem_bytes: u32, pub height: Option<Vec<u32>>, pub size: [usize; 2] }
+/// What `HipSkeleton` produces: `kind` holds `h * w` bytes (0 removed or skipped, 1 + kept neighbours of the value), `table` `rows`
+/// rows of `INFUR_SKELETON_WORDS` words, row v for value v (PIXELS, ENDS, JUNCTIONS, ORTHO, DIAG, FIRST, MIN_H, MAX_H), `counts`
+/// the eight count words (`counts[INFUR_SKELETON_STATUS] & INFUR_SKELETON_UNFINISHED`: max_rounds ran out).
+#[derive(Default)]
+pub struct Centrelines { pub kind: Vec<u8>, pub table: Vec<u32>, pub counts: [u32; 8] }
+pub enum SkeletonCmd { Rounds { max_rounds: u32, skip: Option<u32>, rows: u32 } }
+/// The stage that thins every value of a plane by Guo and Hall's two-sub-iteration rule and measures the centrelines.  Integer
+/// results, identical from run to run.
+pub struct HipSkeleton { ctx: Rc<Ctx>, max_rounds: u32, skip: Option<u32>, rows: u32, dirty: bool }
+impl HipSkeleton {
+    pub fn new(ctx: Rc<Ctx>) -> Self { Self { ctx, max_rounds: 0, skip: None, rows: 256, dirty: true } }
+}
+impl Processor for HipSkeleton {
+    type Command = SkeletonCmd;
+    type ControlError = HipError;
+    type Input = SkeletonInput;
+    type Output = Centrelines;
+    type ProcessResult = Result<(), HipError>;
+
+    fn control(&mut self, cmd: SkeletonCmd) -> Result<&mut Self, HipError> {
+        let SkeletonCmd::Rounds { max_rounds, skip, rows } = cmd;
+        if max_rounds > sys::INFUR_SKELETON_MAX_ROUNDS { return Err(HipError::status(sys::INFUR_E_INVALID_ARG)); }
+        self.dirty = self.dirty || (max_rounds, skip, rows) != (self.max_rounds, self.skip, self.rows);
+        self.max_rounds = max_rounds;
+        self.skip = skip;
+        self.rows = rows;
+        Ok(self)
+    }
+    fn is_dirty(&self) -> bool { self.dirty }
+    fn advance(&mut self, inp: &SkeletonInput, out: &mut Centrelines) -> Result<(), HipError> {
+        self.dirty = false;
+        let [w, h] = inp.size;
+        if inp.plane.len() != w * h * inp.elem_bytes as usize || inp.height.as_ref().map_or(false, |v| v.len() != w * h) {
+            return Err(HipError::status(sys::INFUR_E_SHAPE));
+        }
+        out.kind.resize(w * h, 0);
+        out.table.resize(self.rows as usize * sys::INFUR_SKELETON_WORDS as usize, 0);
+        let rc = unsafe {
+            sys::infur_skeleton(self.ctx.0, if w * h > 0 { inp.plane.as_ptr() as *const std::ffi::c_void } else { std::ptr::null() }, inp.elem_bytes,
+                                match &inp.height { Some(v) if w * h > 0 => v.as_ptr(), _ => std::ptr::null() }, h as u32, w as u32,
+                                if self.skip.is_some() { sys::INFUR_SKELETON_SKIP } else { 0 }, self.skip.unwrap_or(0), self.max_rounds,
+                                if w * h > 0 { out.kind.as_mut_ptr() } else { std::ptr::null_mut() },
+                                if self.rows > 0 { out.table.as_mut_ptr() } else { std::ptr::null_mut() }, self.rows, out.counts.as_mut_ptr())
+        };
+        if rc != sys::INFUR_OK { return Err(HipError::from_ctx(&self.ctx, rc)); }
+        Ok(())
+    }
+}
+
 // ---------------------------------------------------------------- Coverage (shared borders simplified once)
 /// What `HipCoverage` produces, in `Outlines`' layout: `loops` holds `min(n_loops, loops_rows)` records (OFFSET', COUNT', VALUE,
 /// START), `vertices` the first `min(n_vertices, vertex_rows)` kept vertex ids; `n_degenerate` counts the loops with COUNT' < 3
