@@ -1580,6 +1580,96 @@ int32_t infur_frame_skeleton_dev(infur_ctx* ctx, const void* d_bgr, uint32_t w, 
                                  void* d_dist2, size_t dist2_capacity, void* d_anchors, uint32_t max_rounds, void* d_kind,
                                  size_t kind_capacity, void* d_skel_table, uint32_t skel_rows, void* d_skel_counts);
 
+/* ---- Centrelines: Skeleton's centrelines traced into polyline branches ----
+ * Skeleton returns a kind plane and sums per value.  What a host wants from the centreline of a road, rail, cable, vessel or crack
+ * is the line itself: one polyline per branch, from an end or junction to the next end or junction, with its length and narrowest
+ * point, and which branches meet where -- a GeoJSON LineString, a lane graph, a vessel tree.  Centrelines traces a plane and
+ * Skeleton's kind plane, both already in device memory, into branch records and vertex lists in Outlines' layout, instead of the
+ * kind and label planes crossing PCIe to be walked on the CPU.  Everything is an exact integer function of the inputs: identical
+ * bytes from run to run.  Announced by infur_features() & INFUR_FEATURE_CENTRELINES (INFUR_ABI_VERSION does not move).
+ *
+ * INPUTS.  `plane`: h x w elements of elem_bytes = 1 or 4, h and w at most 65535 and h*w below 2^30; Runs' rules hold for
+ * elem_bytes, for a NULL plane, for unknown flag bits and for flags & INFUR_CENTRELINES_SKIP with skip_value.  `kind`: NULL, or h x w
+ * bytes, typically Skeleton's kind_out of the same plane.  `height`: NULL, or h x w uint32_t, typically Anchors' dist2.
+ * 1 KEPT PIXELS AND LINKS.  A pixel is KEPT when it is not skipped and, with a kind plane, its kind byte is not 0; with kind ==
+ *   NULL every pixel that is not skipped is kept, so a hand-drawn thin plane is traced without Skeleton.  Neighbour k of p (k = 0 ..
+ *   7: N, NE, E, SE, S, SW, W, NW) is SET FOR p when it lies inside the frame, is kept and holds p's value.  The LINKS of p are the
+ *   pairs Skeleton counts as ORTHO and DIAG: every set 4-neighbour, and a set diagonal neighbour only when neither of the two
+ *   4-neighbours it shares with p is set for p.  The rule is symmetric and leaves no triangles; a pixel has at most four links, a
+ *   plane at most 2*h*w.  d(p) is the number of links of p; a NODE is a kept pixel with d != 2, every other kept pixel a PATH PIXEL.
+ *   A DART is a directed link (p, k) with the id 8*p + k, p = y*w + x.
+ * 2 BRANCHES.  A branch is a maximal walk along links whose interior pixels are all path pixels: from a node to a node (possibly
+ *   the same one), a RING of path pixels only, or a node with d = 0 alone (one vertex, no link).  A branch between nodes can be
+ *   walked from either end; it is listed once, from the end whose first dart has the smaller id (the other candidate is the dart
+ *   that leaves the far end back along the branch).  A ring starts at its smallest pixel along that pixel's smaller direction and
+ *   repeats that pixel at its end.  The branches are listed in ascending order of their first dart's id, an isolated pixel p
+ *   counting as dart 8*p.
+ * OUTPUTS, each optional (NULL or no rows = not wanted; nothing wanted is INFUR_E_INVALID_ARG), none needs initialisation, nothing
+ * beyond the declared rows is written, and a rejected call touches none:
+ *   records   INFUR_CENTRELINE_WORDS uint32_t per branch: OFFSET and COUNT (its vertices in `vertices`), VALUE, A and B (its first
+ *             and last pixel), ORTHO and DIAG (its links; ORTHO + sqrt(2) DIAG is its length), MIN_H (the smallest height over
+ *             its pixels, both ends included; 0 without a height plane: on dist2 the squared half-width at its narrowest point)
+ *   vertices  pixel ids, the branches back to back, each from A to B inclusive: COUNT = ORTHO + DIAG + 1.  With
+ *             INFUR_CENTRELINES_CORNERS an interior vertex whose incoming and outgoing directions are equal is dropped; the first
+ *             and the last vertex always stay, a ring's start included
+ *   counts    INFUR_CENTRELINES_COUNT_WORDS uint32_t, always complete: BRANCHES, VERTICES, LINKS, NODES, ENDS (d = 1), RINGS, DIAG
+ *             (the diagonal links), STATUS
+ * CAPACITY.  max_links bounds the scratch (about 200 bytes per link); 0 means 2*h*w, the most a plane can hold.  A plane with
+ * more links than max_links is reported in the counts, not as an error, exactly as Outlines treats max_edges: STATUS has
+ * INFUR_CENTRELINES_OVERFLOW, LINKS, NODES, ENDS and DIAG still hold the true numbers, BRANCHES = VERTICES = RINGS = 0 and nothing
+ * else is written.  h*w == 0 writes zero counts and nothing else.
+ * EXAMPLE.  The plane of Skeleton's example with the kind plane it gives there: h = 4, w = 7, flags = INFUR_CENTRELINES_SKIP,
+ * skip_value = 0.  Value 1 is kept at the pixels 8 .. 11, value 2 at 20 and 26.  records (0, 4, 1, 8, 11, 3, 0, 0) and
+ * (4, 2, 2, 20, 26, 0, 1, 0), vertices 8 9 10 11 20 26, counts (2, 6, 4, 4, 4, 0, 1, 0).  With INFUR_CENTRELINES_CORNERS: records
+ * (0, 2, 1, 8, 11, 3, 0, 0) and (2, 2, 2, 20, 26, 0, 1, 0), vertices 8 11 20 26.
+ * WHAT IT DOES NOT DO.  No pruning of spurs (a record carries what a host needs to prune: its length, its ends, MIN_H), no merging
+ * of adjacent junction pixels into one node, no Douglas-Peucker on open polylines, no stream, batch or group call. */
+enum { INFUR_CENTRELINES_SKIP = 1, INFUR_CENTRELINES_CORNERS = 2 };
+enum { INFUR_CENTRELINE_OFFSET = 0, INFUR_CENTRELINE_COUNT = 1, INFUR_CENTRELINE_VALUE = 2, INFUR_CENTRELINE_A = 3, INFUR_CENTRELINE_B = 4,
+       INFUR_CENTRELINE_ORTHO = 5, INFUR_CENTRELINE_DIAG = 6, INFUR_CENTRELINE_MIN_H = 7, INFUR_CENTRELINE_WORDS = 8 };
+enum { INFUR_CENTRELINES_BRANCHES = 0, INFUR_CENTRELINES_VERTICES = 1, INFUR_CENTRELINES_LINKS = 2, INFUR_CENTRELINES_NODES = 3,
+       INFUR_CENTRELINES_ENDS = 4, INFUR_CENTRELINES_RINGS = 5, INFUR_CENTRELINES_COUNT_DIAG = 6, INFUR_CENTRELINES_STATUS = 7,
+       INFUR_CENTRELINES_COUNT_WORDS = 8 };
+enum { INFUR_CENTRELINES_OVERFLOW = 1 };
+enum { INFUR_FEATURE_CENTRELINES = 32768 };
+
+/* on a given plane and optional kind and height planes, host pointers: the counts are read first, then min(count, rows) of each
+ * output */
+int32_t infur_centrelines(infur_ctx* ctx, const void* plane, uint32_t elem_bytes, const uint8_t* kind, const uint32_t* height, uint32_t h,
+                          uint32_t w, uint32_t flags, uint32_t skip_value, uint32_t max_links, uint32_t* records, uint32_t rows,
+                          uint32_t* vertices, uint32_t vertex_rows, uint32_t* counts);
+/* device pointers throughout; enqueued on the context's stream as launches only -- no memset, nothing read back; their number is
+ * fixed by the arguments: 9 + ceil(log2(2 * capacity)), and one or two more where records or vertices are wanted; a round of the
+ * list ranking behind one that met only finished darts exits at once.  The call never synchronises and is capturable after one call
+ * outside the capture, which allocates the scratch, owned by the context; it grows only with a request larger than any before.
+ * This is the call that composes on the device: infur_frame_regions_dev, infur_anchors_dev, infur_skeleton_dev, then
+ * infur_centrelines_dev on the label plane, the kind plane and dist2.  The outputs must not overlap the inputs. */
+int32_t infur_centrelines_dev(infur_ctx* ctx, const void* d_plane, uint32_t elem_bytes, const void* d_kind, const void* d_height, uint32_t h,
+                              uint32_t w, uint32_t flags, uint32_t skip_value, uint32_t max_links, void* d_records, uint32_t rows,
+                              void* d_vertices, uint32_t vertex_rows, void* d_counts);
+/* The fused frame path with the polylines of every object: infur_frame_skeleton_dev, then Centrelines of the label plane and the
+ * kind plane under dist2 with INFUR_REGION_NONE skipped, in one call: VALUE of a record is its region.  The arguments are
+ * infur_frame_skeleton's own, then cl_flags (INFUR_CENTRELINES_CORNERS or 0), max_links and Centrelines' outputs.  Every output is
+ * optional; the label, distance and kind planes go to scratch of the library's own when the caller does not want them.  The calls
+ * inherit infur_frame_skeleton's checks and errors and its rule for a context without a model, always enqueue eagerly and leave
+ * the graphs cached for infur_frame_advance_dev alone. */
+int32_t infur_frame_centrelines(infur_ctx* ctx, const uint8_t* bgr, uint32_t w, uint32_t h, float factor, uint32_t scale_mode,
+                                uint32_t decode, uint32_t connectivity, uint32_t min_pixels, uint32_t flags, uint8_t* klass,
+                                uint8_t* conf, size_t plane_capacity, uint32_t* labels, size_t labels_capacity, uint64_t* table,
+                                uint32_t table_rows, uint32_t* n_regions, uint8_t* scaled_bgr, uint32_t* ow, uint32_t* oh,
+                                uint32_t* dist2, size_t dist2_capacity, uint32_t* anchors, uint32_t max_rounds, uint8_t* kind,
+                                size_t kind_capacity, uint32_t* skel_table, uint32_t skel_rows, uint32_t* skel_counts,
+                                uint32_t cl_flags, uint32_t max_links, uint32_t* records, uint32_t record_rows, uint32_t* vertices,
+                                uint32_t vertex_rows, uint32_t* cl_counts);
+int32_t infur_frame_centrelines_dev(infur_ctx* ctx, const void* d_bgr, uint32_t w, uint32_t h, float factor, uint32_t scale_mode,
+                                    uint32_t decode, uint32_t connectivity, uint32_t min_pixels, uint32_t flags, void* d_klass,
+                                    void* d_conf, size_t plane_capacity, void* d_labels, size_t labels_capacity, void* d_table,
+                                    uint32_t table_rows, void* d_n_regions, void* d_scaled_bgr, uint32_t* ow, uint32_t* oh,
+                                    void* d_dist2, size_t dist2_capacity, void* d_anchors, uint32_t max_rounds, void* d_kind,
+                                    size_t kind_capacity, void* d_skel_table, uint32_t skel_rows, void* d_skel_counts,
+                                    uint32_t cl_flags, uint32_t max_links, void* d_records, uint32_t record_rows, void* d_vertices,
+                                    uint32_t vertex_rows, void* d_cl_counts);
+
 /* ---- streaming (infur/src/main.rs:27-99,105): bounded queue, copies overlapped with compute ----
  * The reference back-pressures its producer with sync_channel(2) (main.rs:105); a stream
  * here is a ring of `depth` pinned + device slots.  submit() copies the caller's frame into a

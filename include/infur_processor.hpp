@@ -13,6 +13,7 @@
 // structs; `&mut Option<T>` outputs become `std::optional<T>&`; buffers are reused across calls
 // exactly where the reference reuses them.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <optional>
@@ -1063,6 +1064,61 @@ public:
 private:
     Context& c_;
     Cmd cmd_{Cmd::Rounds, 0, false, 0};
+    bool dirty_ = true;
+};
+
+/// What `Centrelines` produces, in Outlines' layout: `records` holds min(BRANCHES, rows) records of INFUR_CENTRELINE_WORDS words
+/// (OFFSET, COUNT, VALUE, A, B, ORTHO, DIAG, MIN_H), `vertices` the first min(VERTICES, vertex_rows) pixel ids, `counts` the eight
+/// count words.
+struct CentrelinesOut {
+    uint32_t width = 0, height = 0, rows = 1u << 16, vertex_rows = 1u << 20;  // rows, vertex_rows: what to provide
+    std::vector<uint32_t> records, vertices;
+    uint32_t counts[INFUR_CENTRELINES_COUNT_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
+    bool overflow() const { return (counts[INFUR_CENTRELINES_STATUS] & INFUR_CENTRELINES_OVERFLOW) != 0; }
+    const uint32_t* record(uint32_t i) const { return records.data() + (size_t)i * INFUR_CENTRELINE_WORDS; }
+    /// ORTHO + sqrt(2) DIAG of branch i, in pixels
+    double length(uint32_t i) const { return record(i)[INFUR_CENTRELINE_ORTHO] + 1.4142135623730951 * record(i)[INFUR_CENTRELINE_DIAG]; }
+};
+
+/// The stage behind Skeleton that traces the one-pixel centrelines into polyline branches.  Integer results, identical from run to
+/// run.  Command = the skipped value, CORNERS and the capacity in links (0: the most the plane can hold); Input = a plane of 1- or
+/// 4-byte elements and optional kind and height planes of its size (nullptr: none); Output = CentrelinesOut.
+class Centrelines {
+public:
+    struct Cmd {
+        enum Kind { Trace } kind;
+        bool skip;
+        uint32_t skip_value;
+        bool corners;
+        uint32_t max_links;
+    };
+    explicit Centrelines(Context& c) : c_(c) {}
+    Status control(Cmd cmd) {
+        if (cmd.kind != Cmd::Trace) return INFUR_E_INVALID_ARG;
+        dirty_ = dirty_ || cmd.skip != cmd_.skip || cmd.skip_value != cmd_.skip_value || cmd.corners != cmd_.corners || cmd.max_links != cmd_.max_links;
+        cmd_ = cmd;
+        return INFUR_OK;
+    }
+    bool is_dirty() const { return dirty_; }
+    Status advance(const void* plane, uint32_t elem_bytes, const uint8_t* kind, const uint32_t* height, uint32_t h, uint32_t w, CentrelinesOut& out) {
+        dirty_ = false;
+        out.width = w;
+        out.height = h;
+        out.records.assign((size_t)out.rows * INFUR_CENTRELINE_WORDS, 0);
+        out.vertices.assign(out.vertex_rows, 0);
+        const Status rc = infur_centrelines(c_.get(), plane, elem_bytes, kind, height, h, w,
+                                            (cmd_.skip ? INFUR_CENTRELINES_SKIP : 0) | (cmd_.corners ? INFUR_CENTRELINES_CORNERS : 0), cmd_.skip_value,
+                                            cmd_.max_links, out.rows ? out.records.data() : nullptr, out.rows,
+                                            out.vertex_rows ? out.vertices.data() : nullptr, out.vertex_rows, out.counts);
+        if (rc != INFUR_OK) return rc;
+        out.records.resize((size_t)std::min(out.rows, out.counts[INFUR_CENTRELINES_BRANCHES]) * INFUR_CENTRELINE_WORDS);
+        out.vertices.resize(std::min(out.vertex_rows, out.counts[INFUR_CENTRELINES_VERTICES]));
+        return rc;
+    }
+
+private:
+    Context& c_;
+    Cmd cmd_{Cmd::Trace, false, 0, false, 0};
     bool dirty_ = true;
 };
 

@@ -136,6 +136,14 @@ SKELETON_UNFINISHED = 1
 SKELETON_NONE = 0xFFFFFFFF
 SKELETON_MAX_ROUNDS = 131072
 FEATURE_SKELETON = 16384
+# Centrelines (infur_centrelines / infur_frame_centrelines): the flags, the words of a branch's record and of the counts, the status bit
+CENTRELINES_SKIP, CENTRELINES_CORNERS = 1, 2
+(CENTRELINE_OFFSET, CENTRELINE_COUNT, CENTRELINE_VALUE, CENTRELINE_A, CENTRELINE_B, CENTRELINE_ORTHO, CENTRELINE_DIAG, CENTRELINE_MIN_H,
+ CENTRELINE_WORDS) = 0, 1, 2, 3, 4, 5, 6, 7, 8
+(CENTRELINES_BRANCHES, CENTRELINES_VERTICES, CENTRELINES_LINKS, CENTRELINES_NODES, CENTRELINES_ENDS, CENTRELINES_RINGS, CENTRELINES_COUNT_DIAG,
+ CENTRELINES_STATUS, CENTRELINES_COUNT_WORDS) = 0, 1, 2, 3, 4, 5, 6, 7, 8
+CENTRELINES_OVERFLOW = 1
+FEATURE_CENTRELINES = 32768
 
 
 class Options(C.Structure):
@@ -318,6 +326,12 @@ SIGNATURES = {
                                          _u32p, _u32p, _vp, _sz, _vp, _u32, _vp, _sz, _vp, _u32, _vp]),
     "infur_frame_skeleton_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp, _vp,
                                              _u32p, _u32p, _vp, _sz, _vp, _u32, _vp, _sz, _vp, _u32, _vp]),
+    "infur_centrelines": (C.c_int32, [_vp, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _vp]),
+    "infur_centrelines_dev": (C.c_int32, [_vp, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _vp]),
+    "infur_frame_centrelines": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp, _vp,
+                                            _u32p, _u32p, _vp, _sz, _vp, _u32, _vp, _sz, _vp, _u32, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp]),
+    "infur_frame_centrelines_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp, _vp,
+                                                _u32p, _u32p, _vp, _sz, _vp, _u32, _vp, _sz, _vp, _u32, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp]),
     "infur_stream_create": (C.c_int32, [_vp, _u32, C.POINTER(_vp)]),
     "infur_stream_destroy": (None, [_vp]),
     "infur_stream_add_lane": (C.c_int32, [_vp, _vp]),

@@ -206,6 +206,9 @@ struct infur_ctx {
     // Skeleton (infur_skeleton.cpp): the two alive bitmaps, the four relation planes and the tile flags; the label and distance planes
     // of the frame calls; the host-pointer calls' staging.  Private like the above.
     infur::Buf st_skel, st_skel_plane, st_skel_io;
+    // Centrelines (infur_centrelines.cpp): the link plane, the dart bases, the two buffers of dart records and the block sums; the label,
+    // distance and kind planes of the frame calls; the host-pointer calls' staging.  Private like the above.
+    infur::Buf st_cl, st_cl_plane, st_cl_io;
     // Tracks (infur_tracks.cpp): the live trackers of this context; infur_ctx_destroy releases their device memory and orphans them
     std::vector<infur_tracker*> trackers;
 

@@ -506,6 +506,22 @@ unsigned skeleton_thin_launches(unsigned max_rounds);
 hipError_t launch_skeleton(const void* plane, int elem_bytes, const unsigned* height, unsigned H, unsigned W, int skip, unsigned skip_value,
                            unsigned max_rounds, void* scratch, uint8_t* kind, unsigned* table, unsigned rows, unsigned* counts, hipStream_t s);
 
+// Centrelines (centrelines.hip): the kept pixels of an H x W plane (H * W below 2^30) of 1- or 4-byte elements -- not skipped and,
+// with a kind plane, of non-zero kind -- traced along their links into branches by the rules of include/infur_hip.h.  height: a u32
+// plane or null.  max_links: 1 .. 2 * H * W, the capacity in links.  records: rows rows of kCentrelineWords u32 (OFFSET, COUNT, VALUE,
+// A, B, ORTHO, DIAG, MIN_H); vertices: vertex_rows pixel ids; counts[kCentrelinesCountWords] = {BRANCHES, VERTICES, LINKS, NODES, ENDS,
+// RINGS, DIAG, STATUS} (each optional).  scratch: centrelines_scratch_bytes(..).  Stream-ordered, launches only:
+// 8 + centrelines_rounds(max_links), and 1 or 2 more where records or vertices are wanted; a round behind one that met only finished
+// darts exits on a device word.  An empty plane is one launch that clears the counts.
+constexpr int kCentrelineWords = 8;
+constexpr int kCentrelinesCountWords = 8;
+constexpr unsigned kCentrelinesOverflow = 1u;
+size_t centrelines_scratch_bytes(size_t npix, size_t max_links);
+unsigned centrelines_rounds(size_t max_links);
+hipError_t launch_centrelines(const void* plane, int elem_bytes, const uint8_t* kind, const unsigned* height, unsigned H, unsigned W, int skip, int corners,
+                              unsigned skip_value, size_t max_links, void* scratch, unsigned* records, unsigned rows, unsigned* vertices,
+                              unsigned vertex_rows, unsigned* counts, hipStream_t s);
+
 // Coverage (coverage.hip): Outlines' loops of an H x W plane (both in [1, 8191]) of 1- or 4-byte elements, simplified within
 // tol16 / 16 pixels so that neighbouring polygons still fit: the loops are cut at the plane's junctions and every arc between
 // two of them is simplified by a rule that does not depend on the direction of travel.  Inputs as launch_simplify's plus the

@@ -1533,6 +1533,110 @@ class SkeletonFrame(NamedTuple):
     counts: Optional[np.ndarray]
 
 
+@dataclass
+class CentrelinesCmd:
+    """``Centrelines``' command: ``skip``, the value that is background (None: every value is traced), ``corners`` (drop the interior
+    vertices at which a branch runs straight on) and ``max_links`` (0: the most the plane can hold)."""
+
+    skip: Optional[int] = None
+    corners: bool = False
+    max_links: int = 0
+
+
+class CentrelinesOut:
+    """``Centrelines``' ``&mut Output``: the rows to provide (``rows`` records, ``vertex_rows`` vertices) and, after ``advance``,
+    ``records`` [min(BRANCHES, rows), 8] u32 (``_lib.CENTRELINE_OFFSET`` .. ``_lib.CENTRELINE_MIN_H``), ``vertices`` [min(VERTICES,
+    vertex_rows)] u32 pixel ids and ``counts`` [8] u32 (``_lib.CENTRELINES_BRANCHES`` .. ``_lib.CENTRELINES_STATUS``)."""
+
+    def __init__(self, rows: int = 1 << 16, vertex_rows: int = 1 << 20):
+        self.rows, self.vertex_rows = rows, vertex_rows
+        self.records = self.vertices = self.counts = None
+
+
+class Centrelines(Processor):
+    """The stage behind ``Skeleton`` that traces the one-pixel centrelines into polyline branches: one record and one vertex list
+    per branch, from an end or junction to the next, with its links and the smallest height along it.
+
+    Command = ``CentrelinesCmd``.  Input = plane [H, W] u8 or u32, or (plane, kind [H, W] u8 or None, height [H, W] u32 or None);
+    Output = ``CentrelinesOut``.  Integers throughout, identical from run to run.  ``centreline_features`` turns the output into
+    polylines with lengths and widths.
+    """
+
+    def __init__(self, ctx: Context, skip: Optional[int] = None, corners: bool = False, max_links: int = 0):
+        self.ctx = ctx
+        self.skip, self.corners, self.max_links = skip, corners, max_links
+        self.dirty = True
+
+    def control(self, cmd: CentrelinesCmd) -> "Centrelines":
+        if not 0 <= cmd.max_links <= 0xFFFFFFFF or (cmd.skip is not None and not 0 <= cmd.skip <= 0xFFFFFFFF):
+            raise InfurError(_lib.E_INVALID_ARG, f"max_links {cmd.max_links}, skip {cmd.skip}: u32")
+        self.dirty = self.dirty or (cmd.skip, cmd.corners, cmd.max_links) != (self.skip, self.corners, self.max_links)
+        self.skip, self.corners, self.max_links = cmd.skip, cmd.corners, cmd.max_links
+        return self
+
+    def is_dirty(self) -> bool:
+        return self.dirty
+
+    def advance(self, inp, out: CentrelinesOut) -> None:
+        self.dirty = False
+        plane, kind, height = inp if isinstance(inp, tuple) else (inp, None, None)
+        if plane.ndim != 2 or plane.dtype.itemsize not in (1, 4) or plane.dtype.kind not in "ui" or any(
+                a is not None and a.shape != plane.shape for a in (kind, height)):
+            raise InfurError(_lib.E_SHAPE, f"expected an [H,W] plane of 1- or 4-byte integers and kind and height planes of its size or none, got "
+                                           f"{plane.shape} {plane.dtype}")
+        plane = np.ascontiguousarray(plane)
+        kind = np.ascontiguousarray(kind, np.uint8) if kind is not None else None
+        height = np.ascontiguousarray(height, np.uint32) if height is not None else None
+        h, w = plane.shape
+        rows, vrows = max(0, min(int(out.rows), 4 * h * w + 1)), max(0, min(int(out.vertex_rows), 8 * h * w + 1))
+        records = np.empty((rows, _lib.CENTRELINE_WORDS), np.uint32) if rows else None
+        vertices = np.empty(vrows, np.uint32) if vrows else None
+        counts = np.zeros(_lib.CENTRELINES_COUNT_WORDS, np.uint32)
+        flags = (_lib.CENTRELINES_SKIP if self.skip is not None else 0) | (_lib.CENTRELINES_CORNERS if self.corners else 0)
+        self.ctx.check(self.ctx.L.infur_centrelines(self.ctx.h, _ptr_some(plane), plane.dtype.itemsize, _ptr_some(kind) if kind is not None else None,
+                                                    _ptr_some(height) if height is not None else None, h, w, flags, self.skip or 0, self.max_links,
+                                                    _ptr_some(records), rows, _ptr_some(vertices), vrows, counts.ctypes.data))
+        out.records = records[:min(rows, int(counts[_lib.CENTRELINES_BRANCHES]))] if records is not None else None
+        out.vertices = vertices[:min(vrows, int(counts[_lib.CENTRELINES_VERTICES]))] if vertices is not None else None
+        out.counts = counts
+
+
+def centreline_features(records: np.ndarray, vertices: np.ndarray, width: int) -> list:
+    """One polyline per record of ``Centrelines`` whose vertices are all there: ``value``, ``vertices`` as (x, y) from A to B,
+    ``length`` (ORTHO + sqrt(2) DIAG pixels), ``narrowest`` (2 sqrt of MIN_H: the object's width at the narrowest point of the branch
+    when the height plane was ``dist2``) and ``closed`` (a ring, or a loop from a junction back to itself)."""
+    feats = []
+    for r in np.asarray(records).reshape(-1, _lib.CENTRELINE_WORDS):
+        o, n = int(r[_lib.CENTRELINE_OFFSET]), int(r[_lib.CENTRELINE_COUNT])
+        if o + n > len(vertices):
+            continue
+        feats.append({"value": int(r[_lib.CENTRELINE_VALUE]), "vertices": [(int(v) % width, int(v) // width) for v in vertices[o:o + n]],
+                      "length": round(int(r[_lib.CENTRELINE_ORTHO]) + float(np.sqrt(2.0)) * int(r[_lib.CENTRELINE_DIAG]), 2),
+                      "narrowest": round(2 * float(np.sqrt(r[_lib.CENTRELINE_MIN_H])), 2),
+                      "closed": bool(n > 1 and r[_lib.CENTRELINE_A] == r[_lib.CENTRELINE_B])})
+    return feats
+
+
+class CentrelinesFrame(NamedTuple):
+    """``FramePath.advance_centrelines``: ``SkeletonFrame``'s fields, then the branch records [min(BRANCHES, record_rows), 8] u32
+    (VALUE is the region), the vertices [min(VERTICES, vertex_rows)] u32 and Centrelines' counts [8] u32"""
+
+    klass: Optional[np.ndarray]
+    conf: Optional[np.ndarray]
+    labels: Optional[np.ndarray]
+    table: Optional[np.ndarray]
+    n: Optional[int]
+    scaled: Optional[np.ndarray]
+    dist2: Optional[np.ndarray]
+    anchors: Optional[np.ndarray]
+    kind: Optional[np.ndarray]
+    skeleton_table: Optional[np.ndarray]
+    counts: Optional[np.ndarray]
+    records: Optional[np.ndarray]
+    vertices: Optional[np.ndarray]
+    centreline_counts: Optional[np.ndarray]
+
+
 def runs_decode(runs: np.ndarray, n: int, h: int, w: int, fill: int = 0, dtype=None) -> np.ndarray:
     """The dense [h, w] plane of the first ``min(n, len(runs))`` records; pixels no record covers (skipped or truncated runs) read
     ``fill``.  ``dtype``: uint8 when every value and ``fill`` fit a byte, else uint32."""
@@ -2301,6 +2405,43 @@ class FramePath:
         k = min(n.value, rows)
         return SkeletonFrame(klass, conf, labels, table[:k] if table is not None else None, n.value, scaled, dist2,
                              anchors[:k] if anchors is not None else None, kind, stable, counts)
+
+    def advance_centrelines(self, img: np.ndarray, factor: float = 1.0, decode: int = _lib.DECODE_RAW, connectivity: int = _lib.CONNECT_8,
+                            min_pixels: int = 0, flags: int = 0, table_rows: int = 1024, skeleton_rows: int = 1024, max_rounds: int = 0,
+                            corners: bool = False, max_links: int = 0, record_rows: int = 1 << 16, vertex_rows: int = 1 << 20,
+                            want_labels: bool = False, want_klass: bool = True, want_conf: bool = False, want_scaled: bool = False,
+                            want_dist2: bool = False, want_kind: bool = True) -> CentrelinesFrame:
+        """The fused path with the polylines of every object, ``advance_skeleton``'s chain -> Centrelines of the label plane and the
+        kind plane under ``dist2``, in one call -> ``CentrelinesFrame``; every result field is None when no model is loaded
+        (``scaled`` is still produced)."""
+        img, w, h, f, ow, oh = self._front(img, factor)
+        npix = oh.value * ow.value
+        rows, srows = max(0, min(int(table_rows), npix)), max(0, min(int(skeleton_rows), npix))
+        rrows, vrows = max(0, min(int(record_rows), 4 * npix + 1)), max(0, min(int(vertex_rows), 8 * npix + 1))
+        klass, conf = self._plane(ow, oh, want_klass), self._plane(ow, oh, want_conf)
+        labels = self._plane(ow, oh, want_labels, np.uint32)
+        table = np.zeros((rows, _lib.REGION_WORDS), np.uint64) if rows else None
+        scaled = self._plane(ow, oh, want_scaled, channels=3)
+        dist2 = self._plane(ow, oh, want_dist2, np.uint32)
+        anchors = np.empty((rows, _lib.ANCHOR_WORDS), np.uint32) if rows else None
+        kind = self._plane(ow, oh, want_kind)
+        stable = np.empty((srows, _lib.SKELETON_WORDS), np.uint32) if srows else None
+        counts, ccounts = np.zeros(_lib.SKELETON_COUNT_WORDS, np.uint32), np.zeros(_lib.CENTRELINES_COUNT_WORDS, np.uint32)
+        records = np.empty((rrows, _lib.CENTRELINE_WORDS), np.uint32) if rrows else None
+        vertices = np.empty(vrows, np.uint32) if vrows else None
+        n = C.c_uint32(0)
+        rc = self.ctx.L.infur_frame_centrelines(self.ctx.h, img.ctypes.data, w, h, f, self.scale_mode, decode, connectivity, min_pixels, flags,
+                                                _ptr(klass), _ptr(conf), npix, _ptr(labels), npix * 4, _ptr(table), rows, C.addressof(n), _ptr(scaled),
+                                                C.byref(ow), C.byref(oh), _ptr(dist2), npix * 4, _ptr(anchors), max_rounds, _ptr(kind), npix,
+                                                _ptr(stable), srows, counts.ctypes.data, _lib.CENTRELINES_CORNERS if corners else 0, max_links,
+                                                _ptr(records), rrows, _ptr(vertices), vrows, ccounts.ctypes.data)
+        if not self._loaded(rc):
+            return CentrelinesFrame(None, None, None, None, None, scaled, None, None, None, None, None, None, None, None)
+        k = min(n.value, rows)
+        return CentrelinesFrame(klass, conf, labels, table[:k] if table is not None else None, n.value, scaled, dist2,
+                                anchors[:k] if anchors is not None else None, kind, stable, counts,
+                                records[:min(rrows, int(ccounts[_lib.CENTRELINES_BRANCHES]))] if records is not None else None,
+                                vertices[:min(vrows, int(ccounts[_lib.CENTRELINES_VERTICES]))] if vertices is not None else None, ccounts)
 
     def advance_shapes(self, img: np.ndarray, factor: float = 1.0, decode: int = _lib.DECODE_RAW, connectivity: int = _lib.CONNECT_8,
                        min_pixels: int = 0, flags: int = 0, table_rows: int = 1024, max_edges: int = 0, loops_rows: int = 1 << 16,

@@ -65,6 +65,10 @@ segment planes back to back (4294967295: a pixel of no region).
 length and whether ``--skeleton-rounds N`` ran out; 0: the library's bound) and ``"centrelines"``, one record per region with its
 ``"length"``, ``"ends"``, ``"junctions"`` and the ``"narrowest"`` and ``"widest"`` width along the line.  ``--skeleton-out FILE``
 receives the u8 kind planes back to back (0: no centreline, 2: an end, 3: a path pixel, 4 or more: a junction).
+``--centrelines-out FILE`` (needs ``--skeleton``) traces the centrelines into polylines on the device (``infur_frame_centrelines``):
+per frame FILE receives the eight u32 counts, then the records (eight u32 per branch: OFFSET, COUNT, VALUE = region, A, B, ORTHO,
+DIAG, MIN_H), then the vertices (u32 pixel ids); ``--centrelines-corners`` keeps only the vertices at which a branch turns.  Every
+line gains ``"branches"``: the frame's branches, vertices, links, nodes, ends and rings.
 
 ``--truth FILE`` grades every frame: FILE holds one u8 ground-truth class plane of the scaled frame's size per frame, back to back;
 the class plane is compared with it (``infur_compare``; ``--truth-ignore V`` leaves the pixels whose truth is V, a "void" label,
@@ -156,7 +160,13 @@ def main(argv=None) -> int:
     ap.add_argument("--skeleton", action="store_true", help="thin every region to its one-pixel centreline on the device (needs --regions)")
     ap.add_argument("--skeleton-out", default="", help="raw u8 kind planes, one byte per pixel (needs --skeleton)")
     ap.add_argument("--skeleton-rounds", type=int, default=0, metavar="N", help="at most N sub-iterations (0: the library's bound; needs --skeleton)")
+    ap.add_argument("--centrelines-out", default="", help="per frame 8 u32 counts, the branch records, the vertices (needs --skeleton)")
+    ap.add_argument("--centrelines-corners", action="store_true", help="keep only the vertices at which a branch turns (needs --centrelines-out)")
     a = ap.parse_args(argv)
+    if a.centrelines_out and not a.skeleton:
+        ap.error("--centrelines-out needs --skeleton")
+    if a.centrelines_corners and not a.centrelines_out:
+        ap.error("--centrelines-corners needs --centrelines-out")
     if (a.skeleton_out or a.skeleton_rounds) and not a.skeleton:
         ap.error("--skeleton-out and --skeleton-rounds need --skeleton")
     if a.skeleton:
@@ -280,6 +290,7 @@ def main(argv=None) -> int:
     fhull = open(a.hulls_out, "wb") if a.hulls_out else None
     fsplit = open(a.split_out, "wb") if a.split_out else None
     fskel = open(a.skeleton_out, "wb") if a.skeleton_out else None
+    fcl = open(a.centrelines_out, "wb") if a.centrelines_out else None
     if a.regions and (a.sieve is not None or a.shapes or a.split is not None or a.skeleton):
         flags = _lib.REGIONS_SKIP_BACKGROUND if a.skip_background else 0
     elif a.regions:
@@ -311,6 +322,12 @@ def main(argv=None) -> int:
         elif a.split is not None:  # scale -> model -> decode -> Regions -> Anchors -> Split of the label plane under its dist2, in one call
             r = fp.advance_split(img, split_core(a.split), a.scale, decode, a.connectivity, a.min_pixels, flags, table_rows=max(0, a.max_regions),
                                  split_rows=1 << 32, want_labels=freg is not None, want_klass=True, want_conf=True, want_segments=fsplit is not None)
+            s = SegmentsFrame(r.klass, r.conf, _class_stats(r.klass, r.conf, model.get_info().num_classes), None, None)
+            labels, table, nreg = r.labels, r.table, r.n
+        elif fcl is not None:  # the call below, then Centrelines of the label plane and the kind plane under dist2, in one call
+            r = fp.advance_centrelines(img, a.scale, decode, a.connectivity, a.min_pixels, flags, table_rows=max(0, a.max_regions),
+                                       skeleton_rows=max(0, a.max_regions), max_rounds=a.skeleton_rounds, corners=a.centrelines_corners, record_rows=1 << 20,
+                                       vertex_rows=1 << 22, want_labels=freg is not None, want_klass=True, want_conf=True, want_kind=fskel is not None)
             s = SegmentsFrame(r.klass, r.conf, _class_stats(r.klass, r.conf, model.get_info().num_classes), None, None)
             labels, table, nreg = r.labels, r.table, r.n
         elif a.skeleton:  # scale -> model -> decode -> Regions -> Anchors -> Skeleton of the label plane under its dist2, in one call
@@ -418,6 +435,13 @@ def main(argv=None) -> int:
                 freg.write(memoryview(labels).cast("B"))
             if fskel is not None and r.kind is not None:
                 fskel.write(memoryview(r.kind).cast("B"))
+            if fcl is not None and r.centreline_counts is not None:
+                cc = [int(v) for v in r.centreline_counts]
+                rec["branches"] = {"branches": cc[_lib.CENTRELINES_BRANCHES], "vertices": cc[_lib.CENTRELINES_VERTICES], "links": cc[_lib.CENTRELINES_LINKS],
+                                   "nodes": cc[_lib.CENTRELINES_NODES], "ends": cc[_lib.CENTRELINES_ENDS], "rings": cc[_lib.CENTRELINES_RINGS],
+                                   "overflow": bool(cc[_lib.CENTRELINES_STATUS] & _lib.CENTRELINES_OVERFLOW)}
+                for part in (r.centreline_counts, r.records, r.vertices):
+                    fcl.write(np.ascontiguousarray(part).tobytes())
         if rpath is not None:
             rec["n_regions"] = nreg
             rec["regions"] = region_summary(table, nreg, ow, oh, anchors=anch) if a.anchors else region_summary(table, nreg, ow, oh)
@@ -457,7 +481,7 @@ def main(argv=None) -> int:
         ftruth.close()
     if a.outlines_fidelity:
         fst.write(json.dumps({"frames": n, "polygon_fidelity": fid_total}) + "\n")
-    for f in (flab, fconf, freg, ftrk, fruns, foutl, fdist, fhull, fsplit, fskel, fst):
+    for f in (flab, fconf, freg, ftrk, fruns, foutl, fdist, fhull, fsplit, fskel, fcl, fst):
         if f is not None:
             f.flush()
     el = time.perf_counter() - t0

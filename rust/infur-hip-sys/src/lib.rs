@@ -351,6 +351,30 @@ pub const INFUR_SKELETON_COUNT_WORDS: u32 = 8;
 pub const INFUR_SKELETON_UNFINISHED: u32 = 1;
 /// bit of `infur_features()`: the Skeleton calls below exist
 pub const INFUR_FEATURE_SKELETON: u32 = 16384;
+/// Centrelines: the flags, the words of a branch's record and of the counts, the status bit
+pub const INFUR_CENTRELINES_SKIP: u32 = 1;
+pub const INFUR_CENTRELINES_CORNERS: u32 = 2;
+pub const INFUR_CENTRELINE_OFFSET: u32 = 0;
+pub const INFUR_CENTRELINE_COUNT: u32 = 1;
+pub const INFUR_CENTRELINE_VALUE: u32 = 2;
+pub const INFUR_CENTRELINE_A: u32 = 3;
+pub const INFUR_CENTRELINE_B: u32 = 4;
+pub const INFUR_CENTRELINE_ORTHO: u32 = 5;
+pub const INFUR_CENTRELINE_DIAG: u32 = 6;
+pub const INFUR_CENTRELINE_MIN_H: u32 = 7;
+pub const INFUR_CENTRELINE_WORDS: u32 = 8;
+pub const INFUR_CENTRELINES_BRANCHES: u32 = 0;
+pub const INFUR_CENTRELINES_VERTICES: u32 = 1;
+pub const INFUR_CENTRELINES_LINKS: u32 = 2;
+pub const INFUR_CENTRELINES_NODES: u32 = 3;
+pub const INFUR_CENTRELINES_ENDS: u32 = 4;
+pub const INFUR_CENTRELINES_RINGS: u32 = 5;
+pub const INFUR_CENTRELINES_COUNT_DIAG: u32 = 6;
+pub const INFUR_CENTRELINES_STATUS: u32 = 7;
+pub const INFUR_CENTRELINES_COUNT_WORDS: u32 = 8;
+pub const INFUR_CENTRELINES_OVERFLOW: u32 = 1;
+/// bit of `infur_features()`: the Centrelines calls below exist
+pub const INFUR_FEATURE_CENTRELINES: u32 = 32768;
 
 extern "C" {
     pub fn infur_abi_version() -> u32;
@@ -712,4 +736,26 @@ extern "C" {
                                     d_dist2: *mut c_void, dist2_capacity: usize, d_anchors: *mut c_void, max_rounds: u32,
                                     d_kind: *mut c_void, kind_capacity: usize, d_skel_table: *mut c_void, skel_rows: u32,
                                     d_skel_counts: *mut c_void) -> i32;
+    // Centrelines: Skeleton's centrelines traced into polyline branches, a record per branch and the vertex lists
+    pub fn infur_centrelines(c: *mut infur_ctx, plane: *const c_void, elem_bytes: u32, kind: *const u8, height: *const u32, h: u32, w: u32,
+                             flags: u32, skip_value: u32, max_links: u32, records: *mut u32, rows: u32, vertices: *mut u32,
+                             vertex_rows: u32, counts: *mut u32) -> i32;
+    pub fn infur_centrelines_dev(c: *mut infur_ctx, d_plane: *const c_void, elem_bytes: u32, d_kind: *const c_void, d_height: *const c_void,
+                                 h: u32, w: u32, flags: u32, skip_value: u32, max_links: u32, d_records: *mut c_void, rows: u32,
+                                 d_vertices: *mut c_void, vertex_rows: u32, d_counts: *mut c_void) -> i32;
+    pub fn infur_frame_centrelines(c: *mut infur_ctx, bgr: *const u8, w: u32, h: u32, factor: f32, scale_mode: u32, decode: u32,
+                                   connectivity: u32, min_pixels: u32, flags: u32, klass: *mut u8, conf: *mut u8, plane_capacity: usize,
+                                   labels: *mut u32, labels_capacity: usize, table: *mut u64, table_rows: u32, n_regions: *mut u32,
+                                   scaled_bgr: *mut u8, ow: *mut u32, oh: *mut u32, dist2: *mut u32, dist2_capacity: usize,
+                                   anchors: *mut u32, max_rounds: u32, kind: *mut u8, kind_capacity: usize, skel_table: *mut u32,
+                                   skel_rows: u32, skel_counts: *mut u32, cl_flags: u32, max_links: u32, records: *mut u32,
+                                   record_rows: u32, vertices: *mut u32, vertex_rows: u32, cl_counts: *mut u32) -> i32;
+    pub fn infur_frame_centrelines_dev(c: *mut infur_ctx, d_bgr: *const c_void, w: u32, h: u32, factor: f32, scale_mode: u32, decode: u32,
+                                       connectivity: u32, min_pixels: u32, flags: u32, d_klass: *mut c_void, d_conf: *mut c_void,
+                                       plane_capacity: usize, d_labels: *mut c_void, labels_capacity: usize, d_table: *mut c_void,
+                                       table_rows: u32, d_n_regions: *mut c_void, d_scaled_bgr: *mut c_void, ow: *mut u32, oh: *mut u32,
+                                       d_dist2: *mut c_void, dist2_capacity: usize, d_anchors: *mut c_void, max_rounds: u32,
+                                       d_kind: *mut c_void, kind_capacity: usize, d_skel_table: *mut c_void, skel_rows: u32,
+                                       d_skel_counts: *mut c_void, cl_flags: u32, max_links: u32, d_records: *mut c_void,
+                                       record_rows: u32, d_vertices: *mut c_void, vertex_rows: u32, d_cl_counts: *mut c_void) -> i32;
 }

@@ -1306,6 +1306,67 @@ impl Processor for HipSkeleton {
     }
 }
 
+// ---------------------------------------------------------------- Centrelines (Skeleton's centrelines traced into polyline branches)
+/// What `HipCentrelines` reads: a plane of `elem_bytes` 1 or 4 with its `[w, h]` and, optionally, a kind plane (typically
+/// `HipSkeleton`'s) and a u32 height plane of the same size.
+pub struct CentrelinesInput { pub plane: Vec<u8>, pub elem_bytes: u32, pub kind: Option<Vec<u8>>, pub height: Option<Vec<u32>>, pub size: [usize; 2] }
+/// What `HipCentrelines` produces, in `Outlines`' layout: `records` holds `min(BRANCHES, rows)` records of
+/// `INFUR_CENTRELINE_WORDS` words (OFFSET, COUNT, VALUE, A, B, ORTHO, DIAG, MIN_H), `vertices` the first `min(VERTICES,
+/// vertex_rows)` pixel ids, `counts` the eight count words (`counts[INFUR_CENTRELINES_STATUS] & INFUR_CENTRELINES_OVERFLOW`:
+/// more links than `max_links`, nothing was traced).
+#[derive(Default)]
+pub struct Polylines { pub records: Vec<u32>, pub vertices: Vec<u32>, pub counts: [u32; 8] }
+pub enum CentrelinesCmd { Trace { skip: Option<u32>, corners: bool, max_links: u32, rows: u32, vertex_rows: u32 } }
+/// The stage behind `HipSkeleton` that traces the centrelines into one polyline per branch.  Integer results, identical from run
+/// to run.
+pub struct HipCentrelines { ctx: Rc<Ctx>, skip: Option<u32>, corners: bool, max_links: u32, rows: u32, vertex_rows: u32, dirty: bool }
+impl HipCentrelines {
+    pub fn new(ctx: Rc<Ctx>) -> Self { Self { ctx, skip: None, corners: false, max_links: 0, rows: 1 << 16, vertex_rows: 1 << 20, dirty: true } }
+}
+impl Processor for HipCentrelines {
+    type Command = CentrelinesCmd;
+    type ControlError = HipError;
+    type Input = CentrelinesInput;
+    type Output = Polylines;
+    type ProcessResult = Result<(), HipError>;
+
+    fn control(&mut self, cmd: CentrelinesCmd) -> Result<&mut Self, HipError> {
+        let CentrelinesCmd::Trace { skip, corners, max_links, rows, vertex_rows } = cmd;
+        self.dirty = self.dirty || (skip, corners, max_links, rows, vertex_rows) != (self.skip, self.corners, self.max_links, self.rows, self.vertex_rows);
+        self.skip = skip;
+        self.corners = corners;
+        self.max_links = max_links;
+        self.rows = rows;
+        self.vertex_rows = vertex_rows;
+        Ok(self)
+    }
+    fn is_dirty(&self) -> bool { self.dirty }
+    fn advance(&mut self, inp: &CentrelinesInput, out: &mut Polylines) -> Result<(), HipError> {
+        self.dirty = false;
+        let [w, h] = inp.size;
+        if inp.plane.len() != w * h * inp.elem_bytes as usize || inp.kind.as_ref().map_or(false, |v| v.len() != w * h)
+            || inp.height.as_ref().map_or(false, |v| v.len() != w * h) {
+            return Err(HipError::status(sys::INFUR_E_SHAPE));
+        }
+        out.records.resize(self.rows as usize * sys::INFUR_CENTRELINE_WORDS as usize, 0);
+        out.vertices.resize(self.vertex_rows as usize, 0);
+        let flags = if self.skip.is_some() { sys::INFUR_CENTRELINES_SKIP } else { 0 } | if self.corners { sys::INFUR_CENTRELINES_CORNERS } else { 0 };
+        let rc = unsafe {
+            sys::infur_centrelines(self.ctx.0, if w * h > 0 { inp.plane.as_ptr() as *const std::ffi::c_void } else { std::ptr::null() }, inp.elem_bytes,
+                                   match &inp.kind { Some(v) if w * h > 0 => v.as_ptr(), _ => std::ptr::null() },
+                                   match &inp.height { Some(v) if w * h > 0 => v.as_ptr(), _ => std::ptr::null() }, h as u32, w as u32, flags,
+                                   self.skip.unwrap_or(0), self.max_links,
+                                   if self.rows > 0 { out.records.as_mut_ptr() } else { std::ptr::null_mut() }, self.rows,
+                                   if self.vertex_rows > 0 { out.vertices.as_mut_ptr() } else { std::ptr::null_mut() }, self.vertex_rows,
+                                   out.counts.as_mut_ptr())
+        };
+        if rc != sys::INFUR_OK { return Err(HipError::from_ctx(&self.ctx, rc)); }
+        out.records.truncate(self.rows.min(out.counts[sys::INFUR_CENTRELINES_BRANCHES as usize]) as usize * sys::INFUR_CENTRELINE_WORDS as usize);
+        out.vertices.truncate(self.vertex_rows.min(out.counts[sys::INFUR_CENTRELINES_VERTICES as usize]) as usize);
+        Ok(())
+    }
+}
+
 // ---------------------------------------------------------------- Coverage (shared borders simplified once)
 /// What `HipCoverage` produces, in `Outlines`' layout: `loops` holds `min(n_loops, loops_rows)` records (OFFSET', COUNT', VALUE,
 /// START), `vertices` the first `min(n_vertices, vertex_rows)` kept vertex ids; `n_degenerate` counts the loops with COUNT' < 3
