@@ -1670,6 +1670,88 @@ int32_t infur_frame_centrelines_dev(infur_ctx* ctx, const void* d_bgr, uint32_t 
                                     uint32_t cl_flags, uint32_t max_links, void* d_records, uint32_t record_rows, void* d_vertices,
                                     uint32_t vertex_rows, void* d_cl_counts);
 
+/* ---- Expand: grow labels into open pixels by exact nearest seed ----
+ * Every stage above describes pixels that have a value; none gives one to a pixel that has none: the INFUR_REGION_NONE holes
+ * min_pixels leaves, the background between the objects of a class plane.  Expand does: every open pixel takes the value of its
+ * nearest seed, within a reach.  That is a privacy or inpainting mask with an N-pixel margin (dilation by an exact disc),
+ * skimage's expand_labels, "which object is nearest to this click", and, with Adjacency on the grown plane, "which objects are
+ * within N pixels of each other" -- what a host otherwise gets from scipy's distance_transform_edt(return_indices=True) or
+ * cv2.dilate after pulling the plane across PCIe.  Announced by infur_features() & INFUR_FEATURE_EXPAND (INFUR_ABI_VERSION does not
+ * move).
+ *
+ * INPUTS.  `plane`: h x w elements of elem_bytes = 1 or 4, h and w at most INFUR_EXPAND_MAX_SIDE (every squared distance stays
+ * below 2^31).  `open_value`: a pixel that holds it is OPEN, every other pixel is a SEED (at most 255 on a byte plane).  `reach`:
+ * in pixels, 0 = unbounded.  `flags`: no bit is defined, a set bit is INFUR_E_INVALID_ARG.
+ *
+ * THE RULE.  The nearest seed q of an open pixel p minimises the squared Euclidean distance d2(p, q) between pixel centres; ties
+ * go to the smallest index y*w + x (smallest y first, then smallest x).  The result is a function of the plane alone, exact
+ * integers, identical bytes from run to run.
+ *
+ * OUTPUTS, each optional (NULL = not wanted, and so is table with rows == 0; nothing wanted is INFUR_E_INVALID_ARG), none needs
+ * initialisation:
+ *   out     h*w elements of the plane's size.  A seed keeps its value; an open pixel with d2(p, q) <= reach^2 (any distance when
+ *           reach is 0) takes q's value; every other open pixel keeps open_value.  out == plane (in place) is INFUR_E_INVALID_ARG,
+ *           and no output may overlap the plane
+ *   dist2   h*w uint32_t: 0 on a seed, otherwise d2(p, q), whatever reach is; INFUR_EXPAND_NONE where the plane holds no seed
+ *   source  h*w uint32_t: the index of q; a seed reads its own index; INFUR_EXPAND_NONE where the plane holds no seed
+ *   table   rows rows of INFUR_EXPAND_WORDS uint32_t, one per value v < rows: SEEDS the seed pixels of value v, GAINED the open
+ *           pixels that took v, MAX_D2 the largest d2 among those and MAX_PIXEL the index of that pixel, ties to the smallest
+ *           index -- (0, INFUR_EXPAND_NONE) when nothing was gained.  Every row is written; a value at or above rows touches no
+ *           row; the row of open_value reads (0, 0, 0, INFUR_EXPAND_NONE)
+ *   counts  INFUR_EXPAND_COUNT_WORDS uint32_t: SEEDS, OPEN, GAINED, LEFT (the open pixels that stay open), MAX_D2 (over all
+ *           open pixels, gained or not, of a plane that has a seed; 0 otherwise), two reserved zeros, STATUS (INFUR_EXPAND_NO_SEED:
+ *           the plane holds no seed, nothing was gained)
+ * h*w == 0 writes (0, 0, 0, INFUR_EXPAND_NONE) rows and eight zero counts and nothing else.  The checks come in Anchors' order:
+ * elem_bytes, flags, open_value against elem_bytes, the sides (INFUR_E_INVALID_ARG above INFUR_EXPAND_MAX_SIDE), nothing wanted, a
+ * NULL plane with h*w > 0, out == plane.  No output is touched when a call is rejected.
+ *
+ * EXAMPLE.  The 1 x 7 byte plane  0 0 5 0 0 0 7  with open_value 0 and reach 1.  Pixel 4 is two pixels from either seed and goes
+ * to the smaller index:
+ *   source  2 2 2 2 2 6 6      dist2  4 1 0 1 4 1 0      out  0 5 5 5 0 7 7
+ *   table   row 5 = (1, 2, 1, 1)   row 7 = (1, 1, 1, 5)   every other row (0, 0, 0, INFUR_EXPAND_NONE)
+ *   counts  SEEDS 2, OPEN 5, GAINED 3, LEFT 2, MAX_D2 4, 0, 0, STATUS 0
+ * Opening and closing by a disc compose with Anchors: dist2 <= r^2 here is the dilation, dist2 > r^2 there the erosion. */
+#define INFUR_EXPAND_NONE 0xFFFFFFFFu
+enum { INFUR_EXPAND_SEEDS = 0, INFUR_EXPAND_GAINED = 1, INFUR_EXPAND_MAX_D2 = 2, INFUR_EXPAND_MAX_PIXEL = 3, INFUR_EXPAND_WORDS = 4 };
+enum { INFUR_EXPAND_COUNT_SEEDS = 0, INFUR_EXPAND_COUNT_OPEN = 1, INFUR_EXPAND_COUNT_GAINED = 2, INFUR_EXPAND_COUNT_LEFT = 3,
+       INFUR_EXPAND_COUNT_MAX_D2 = 4, INFUR_EXPAND_COUNT_STATUS = 7, INFUR_EXPAND_COUNT_WORDS = 8 };
+enum { INFUR_EXPAND_NO_SEED = 1 };
+enum { INFUR_EXPAND_MAX_SIDE = 32768 };
+enum { INFUR_FEATURE_EXPAND = 65536 };
+
+/* on a given plane, host pointers */
+int32_t infur_expand(infur_ctx* ctx, const void* plane, uint32_t elem_bytes, uint32_t h, uint32_t w, uint32_t flags, uint32_t open_value,
+                     uint32_t reach, void* out, uint32_t* dist2, uint32_t* source, uint32_t* table, uint32_t rows, uint32_t* counts);
+/* device pointers throughout; enqueued on the context's stream as launches only -- no memset, nothing read back; their number is
+ * fixed by the arguments: a row pass, a coarse column pass, one refine pass for each of 32, 16, .. 1 that is below h, a finish pass,
+ * and a clear and a table pass where table or counts are wanted.  The call never synchronises and is capturable after one call
+ * outside the capture, which allocates the scratch (four bytes per pixel and sixteen per row, owned by the context; it grows only
+ * with a request larger than any before).  This is the call that composes on the device: infur_frame_regions_dev, then
+ * infur_expand_dev on the label plane it left in device memory. */
+int32_t infur_expand_dev(infur_ctx* ctx, const void* d_plane, uint32_t elem_bytes, uint32_t h, uint32_t w, uint32_t flags,
+                         uint32_t open_value, uint32_t reach, void* d_out, void* d_dist2, void* d_source, void* d_table, uint32_t rows,
+                         void* d_counts);
+/* The fused frame path with the grown label plane: scale -> model -> Segments decode(out[0]) -> Regions -> Expand of the label plane
+ * with open_value = INFUR_REGION_NONE, in one call.  The arguments are infur_frame_regions' own, then reach and Expand's outputs
+ * (the capacities in bytes, ow*oh*4 needed for each plane; less is INFUR_E_CAPACITY, checked, like the other capacities, once a model
+ * is loaded); expand_table has expand_rows rows, row i for region i.  Every output is optional, and at least one of labels, table,
+ * n_regions and Expand's outputs must be given; the label plane goes to scratch of the library's own when the caller does not want
+ * it.  Every check and error before Expand is infur_frame_regions' own: with no model loaded the Scale stage still runs and the call
+ * returns INFUR_E_MODEL_NOT_LOADED.  The calls always enqueue eagerly and leave the graphs cached for infur_frame_advance_dev
+ * alone.  The grown plane is a label plane: Tracks, Runs, Outlines, Adjacency and Compare run on it unchanged. */
+int32_t infur_frame_expand(infur_ctx* ctx, const uint8_t* bgr, uint32_t w, uint32_t h, float factor, uint32_t scale_mode,
+                           uint32_t decode, uint32_t connectivity, uint32_t min_pixels, uint32_t flags, uint8_t* klass, uint8_t* conf,
+                           size_t plane_capacity, uint32_t* labels, size_t labels_capacity, uint64_t* table, uint32_t table_rows,
+                           uint32_t* n_regions, uint8_t* scaled_bgr, uint32_t* ow, uint32_t* oh, uint32_t reach, uint32_t* grown,
+                           size_t grown_capacity, uint32_t* dist2, size_t dist2_capacity, uint32_t* source, size_t source_capacity,
+                           uint32_t* expand_table, uint32_t expand_rows, uint32_t* expand_counts);
+int32_t infur_frame_expand_dev(infur_ctx* ctx, const void* d_bgr, uint32_t w, uint32_t h, float factor, uint32_t scale_mode,
+                               uint32_t decode, uint32_t connectivity, uint32_t min_pixels, uint32_t flags, void* d_klass,
+                               void* d_conf, size_t plane_capacity, void* d_labels, size_t labels_capacity, void* d_table,
+                               uint32_t table_rows, void* d_n_regions, void* d_scaled_bgr, uint32_t* ow, uint32_t* oh, uint32_t reach,
+                               void* d_grown, size_t grown_capacity, void* d_dist2, size_t dist2_capacity, void* d_source,
+                               size_t source_capacity, void* d_expand_table, uint32_t expand_rows, void* d_expand_counts);
+
 /* ---- streaming (infur/src/main.rs:27-99,105): bounded queue, copies overlapped with compute ----
  * The reference back-pressures its producer with sync_channel(2) (main.rs:105); a stream
  * here is a ring of `depth` pinned + device slots.  submit() copies the caller's frame into a

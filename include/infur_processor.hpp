@@ -511,6 +511,68 @@ private:
     bool dirty_ = true;
 };
 
+/// What `Expand` produces: the grown plane in `out8` or `out32`, whichever the input's elements are; `dist2` the squared distance to
+/// the nearest seed (0 on a seed) and `source` that seed's index (INFUR_EXPAND_NONE throughout where the plane holds no seed);
+/// `table` rows of INFUR_EXPAND_WORDS words (SEEDS, GAINED, MAX_D2, MAX_PIXEL) per value below `rows`; the eight counts.
+struct ExpandOut {
+    uint32_t rows = 256;  // what to provide
+    bool want_out = true, want_dist2 = true, want_source = false;
+    uint32_t width = 0, height = 0;
+    std::vector<uint8_t> out8;
+    std::vector<uint32_t> out32, dist2, source, table;
+    uint32_t counts[INFUR_EXPAND_COUNT_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint32_t word(uint32_t row, uint32_t w) const { return table[(size_t)row * INFUR_EXPAND_WORDS + w]; }
+    bool no_seed() const { return (counts[INFUR_EXPAND_COUNT_STATUS] & INFUR_EXPAND_NO_SEED) != 0; }
+};
+
+/// The stage that gives a value to the pixels that have none: every open pixel (value == open_value) of a byte or u32 plane takes
+/// the value of its exact nearest seed, ties to the smallest index, where that lies within `reach` pixels (0: anywhere).  Integer
+/// results, identical from run to run.  Command = the open value and the reach; Input = a plane of uint8_t or uint32_t, Output =
+/// ExpandOut.
+class Expand {
+public:
+    struct Cmd {
+        enum Kind { Grow } kind;
+        uint32_t open_value, reach;
+    };
+    explicit Expand(Context& c) : c_(c) {}
+    Status control(Cmd cmd) {
+        if (cmd.kind != Cmd::Grow) return INFUR_E_INVALID_ARG;
+        dirty_ = dirty_ || cmd.open_value != open_value_ || cmd.reach != reach_;
+        open_value_ = cmd.open_value;
+        reach_ = cmd.reach;
+        return INFUR_OK;
+    }
+    bool is_dirty() const { return dirty_; }
+    Status advance(const std::vector<uint8_t>& plane, uint32_t height, uint32_t width, ExpandOut& out) {
+        out.out8.assign(out.want_out ? plane.size() : 0, 0);
+        out.out32.clear();
+        return run(plane.data(), plane.size(), 1, height, width, out.out8.data(), out);
+    }
+    Status advance(const std::vector<uint32_t>& plane, uint32_t height, uint32_t width, ExpandOut& out) {
+        out.out32.assign(out.want_out ? plane.size() : 0, 0);
+        out.out8.clear();
+        return run(plane.data(), plane.size(), 4, height, width, out.out32.data(), out);
+    }
+
+private:
+    Status run(const void* plane, size_t elems, uint32_t elem_bytes, uint32_t height, uint32_t width, void* grown, ExpandOut& out) {
+        dirty_ = false;
+        if (elems != (size_t)width * height) return INFUR_E_SHAPE;
+        out.width = width;
+        out.height = height;
+        out.dist2.assign(out.want_dist2 ? elems : 0, 0);
+        out.source.assign(out.want_source ? elems : 0, 0);
+        out.table.assign((size_t)out.rows * INFUR_EXPAND_WORDS, 0);
+        return infur_expand(c_.get(), elems ? plane : nullptr, elem_bytes, height, width, 0, open_value_, reach_, (out.want_out && elems) ? grown : nullptr,
+                            out.want_dist2 ? out.dist2.data() : nullptr, out.want_source ? out.source.data() : nullptr,
+                            out.rows ? out.table.data() : nullptr, out.rows, out.counts);
+    }
+    Context& c_;
+    uint32_t open_value_ = 0, reach_ = 0;
+    bool dirty_ = true;
+};
+
 /// What `Compare` produces for `rows_a` x `rows_b` values: `matrix` row-major (pixels with a == i and b == j), `a` and `b` rows of
 /// INFUR_COMPARE_WORDS words per value of either plane ((0, INFUR_COMPARE_NONE, 0, 0): no compared pixel holds the value) and the
 /// INFUR_COMPARE_COUNT_WORDS counts.

@@ -144,6 +144,14 @@ CENTRELINES_SKIP, CENTRELINES_CORNERS = 1, 2
  CENTRELINES_STATUS, CENTRELINES_COUNT_WORDS) = 0, 1, 2, 3, 4, 5, 6, 7, 8
 CENTRELINES_OVERFLOW = 1
 FEATURE_CENTRELINES = 32768
+# Expand (infur_expand / infur_frame_expand): the words of a table row and of the counts, the status bit, "no seed", the longest side
+EXPAND_SEEDS, EXPAND_GAINED, EXPAND_MAX_D2, EXPAND_MAX_PIXEL, EXPAND_WORDS = 0, 1, 2, 3, 4
+(EXPAND_COUNT_SEEDS, EXPAND_COUNT_OPEN, EXPAND_COUNT_GAINED, EXPAND_COUNT_LEFT, EXPAND_COUNT_MAX_D2, EXPAND_COUNT_STATUS,
+ EXPAND_COUNT_WORDS) = 0, 1, 2, 3, 4, 7, 8
+EXPAND_NO_SEED = 1
+EXPAND_NONE = 0xFFFFFFFF
+EXPAND_MAX_SIDE = 32768
+FEATURE_EXPAND = 65536
 
 
 class Options(C.Structure):
@@ -332,6 +340,12 @@ SIGNATURES = {
                                             _u32p, _u32p, _vp, _sz, _vp, _u32, _vp, _sz, _vp, _u32, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp]),
     "infur_frame_centrelines_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp, _vp,
                                                 _u32p, _u32p, _vp, _sz, _vp, _u32, _vp, _sz, _vp, _u32, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp]),
+    "infur_expand": (C.c_int32, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _u32, _vp]),
+    "infur_expand_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _u32, _vp]),
+    "infur_frame_expand": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp, _vp,
+                                       _u32p, _u32p, _u32, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _u32, _vp]),
+    "infur_frame_expand_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp, _vp,
+                                           _u32p, _u32p, _u32, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _u32, _vp]),
     "infur_stream_create": (C.c_int32, [_vp, _u32, C.POINTER(_vp)]),
     "infur_stream_destroy": (None, [_vp]),
     "infur_stream_add_lane": (C.c_int32, [_vp, _vp]),

@@ -209,6 +209,9 @@ struct infur_ctx {
     // Centrelines (infur_centrelines.cpp): the link plane, the dart bases, the two buffers of dart records and the block sums; the label,
     // distance and kind planes of the frame calls; the host-pointer calls' staging.  Private like the above.
     infur::Buf st_cl, st_cl_plane, st_cl_io;
+    // Expand (infur_expand.cpp): the two u16 planes (nearest seed column, best row) and the accumulator rows; the label plane the frame
+    // calls let Regions write when the caller does not want it; the host-pointer calls' staging.  Private like the above.
+    infur::Buf st_exp, st_exp_plane, st_exp_io;
     // Tracks (infur_tracks.cpp): the live trackers of this context; infur_ctx_destroy releases their device memory and orphans them
     std::vector<infur_tracker*> trackers;
 

@@ -369,6 +369,21 @@ size_t anchors_scratch_bytes(size_t npix, unsigned rows);
 hipError_t launch_anchors(const void* plane, int elem_bytes, unsigned H, unsigned W, int skip, unsigned skip_value, void* scratch, unsigned* dist2,
                           unsigned* anchors, unsigned rows, hipStream_t s);
 
+// Expand (expand.hip): every open pixel (value == open_value) of an H x W plane (both at most kExpandMaxSide) of 1- or 4-byte elements
+// takes the value of its exact nearest seed, ties to the smallest index, where that seed lies within `reach` pixels (0: anywhere) --
+// out[H * W] of the plane's element type, dist2[H * W] and source[H * W] u32 (0xFFFFFFFF where the plane holds no seed), table[rows x
+// kExpandWords] u32 (SEEDS, GAINED, MAX_D2, MAX_PIXEL) and counts[kExpandCountWords] (each optional; device memory; every one of the
+// rows is written).  scratch: expand_scratch_bytes(H * W, rows) bytes the launches own for the call.  Stream-ordered, launches only:
+// rows, coarse, a refine launch for every level 32, 16, .. 1 below H, finish, and clear and table where a table or counts are wanted.
+// No workgroup waits for another.  H * W == 0 writes zero rows and zero counts and needs no scratch.
+constexpr int kExpandWords = 4;
+constexpr int kExpandCountWords = 8;
+constexpr unsigned kExpandNoSeed = 1u;
+constexpr unsigned kExpandMaxSide = 32768;
+size_t expand_scratch_bytes(size_t npix, unsigned rows);
+hipError_t launch_expand(const void* plane, int elem_bytes, unsigned H, unsigned W, unsigned open_value, unsigned reach, void* scratch, void* out,
+                         unsigned* dist2, unsigned* source, unsigned* table, unsigned rows, unsigned* counts, hipStream_t s);
+
 // Compare (compare.hip): two H x W planes (both sides at most 65535) of 1- or 4-byte elements against each other.  A pixel whose
 // a equals ignore_a (ign_a set) or whose b equals ignore_b (ign_b set) is ignored; a compared pixel with a >= rows_a or
 // b >= rows_b is outside; the rest are inside.  matrix[rows_a x rows_b] u32 counts the inside pixels per (a, b); rows_a_out and

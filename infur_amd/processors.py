@@ -992,6 +992,105 @@ class AnchorsFrame(NamedTuple):
 
 
 @dataclass
+class ExpandCmd:
+    """``Expand``'s command: ``Grow(open_value, reach)`` -- the pixels that hold ``open_value`` are open, every other pixel is a
+    seed; an open pixel takes the value of its nearest seed where that lies within ``reach`` pixels (0: anywhere)."""
+
+    open_value: int = 0
+    reach: int = 0
+
+    @staticmethod
+    def Grow(open_value: int, reach: int = 0) -> "ExpandCmd":
+        return ExpandCmd(open_value=open_value, reach=reach)
+
+
+class ExpandOut:
+    """``Expand``'s ``&mut Output``: what to produce (``rows`` table rows, ``want_out``, ``want_dist2``, ``want_source``) and, after
+    ``advance``, the results -- ``out`` [H, W] of the plane's type, ``dist2`` and ``source`` [H, W] u32 (``_lib.EXPAND_NONE`` where
+    the plane holds no seed), ``table`` [rows, 4] u32 (columns ``_lib.EXPAND_SEEDS`` .. ``_lib.EXPAND_MAX_PIXEL``), each None where
+    not wanted, and ``counts`` [8] u32."""
+
+    def __init__(self, rows: int = 256, want_out: bool = True, want_dist2: bool = True, want_source: bool = False):
+        self.rows, self.want_out, self.want_dist2, self.want_source = rows, want_out, want_dist2, want_source
+        self.out = self.dist2 = self.source = self.table = self.counts = None
+
+
+class Expand(Processor):
+    """The stage that gives a value to the pixels that have none: every open pixel of a class plane (u8) or a label / track plane
+    (u32) takes the value of its exact nearest seed (squared Euclidean distance between pixel centres, ties to the smallest index),
+    within a reach: a mask with an N-pixel margin, ``expand_labels``, "which object is nearest".
+
+    Command = ``ExpandCmd``.  Input = a plane [H, W] of u8 or u32; Output = ``ExpandOut``.  Integers throughout, identical from run
+    to run.
+    """
+
+    def __init__(self, ctx: Context, open_value: int = 0, reach: int = 0):
+        self.ctx = ctx
+        self.open_value, self.reach = open_value, reach
+        self.dirty = True
+
+    def control(self, cmd: ExpandCmd) -> "Expand":
+        if not 0 <= cmd.open_value <= 0xFFFFFFFF or not 0 <= cmd.reach <= 0xFFFFFFFF:
+            raise InfurError(_lib.E_INVALID_ARG, f"open value {cmd.open_value}, reach {cmd.reach}: each a u32")
+        self.dirty = self.dirty or (cmd.open_value, cmd.reach) != (self.open_value, self.reach)
+        self.open_value, self.reach = cmd.open_value, cmd.reach
+        return self
+
+    def is_dirty(self) -> bool:
+        return self.dirty
+
+    def advance(self, inp: np.ndarray, out: ExpandOut) -> None:
+        self.dirty = False
+        if inp.ndim != 2 or inp.dtype.itemsize not in (1, 4) or inp.dtype.kind not in "ui":
+            raise InfurError(_lib.E_SHAPE, f"expected an [H,W] plane of 1- or 4-byte integers, got {inp.shape} {inp.dtype}")
+        plane = np.ascontiguousarray(inp)
+        h, w = plane.shape
+        rows = max(0, int(out.rows))
+        grown = np.empty_like(plane) if out.want_out else None
+        dist2 = np.empty((h, w), np.uint32) if out.want_dist2 else None
+        source = np.empty((h, w), np.uint32) if out.want_source else None
+        table = np.empty((rows, _lib.EXPAND_WORDS), np.uint32) if rows else None
+        counts = np.zeros(_lib.EXPAND_COUNT_WORDS, np.uint32)
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        self.ctx.check(self.ctx.L.infur_expand(self.ctx.h, ptr(plane), plane.dtype.itemsize, h, w, 0, self.open_value, self.reach, _ptr(grown),
+                                               _ptr(dist2), _ptr(source), ptr(table), rows, counts.ctypes.data))
+        out.out, out.dist2, out.source, out.table, out.counts = grown, dist2, source, table, counts
+
+
+class ExpandFrame(NamedTuple):
+    """``FramePath.advance_expand``: ``RegionsFrame``'s fields, then the grown label plane, the squared distances and the source
+    indices [oh, ow] u32 (None where not wanted), the rows [min(n, table_rows), 4] u32, row i for region i, and the eight counts"""
+
+    klass: Optional[np.ndarray]
+    conf: Optional[np.ndarray]
+    labels: Optional[np.ndarray]
+    table: Optional[np.ndarray]
+    n: Optional[int]
+    scaled: Optional[np.ndarray]
+    grown: Optional[np.ndarray]
+    dist2: Optional[np.ndarray]
+    source: Optional[np.ndarray]
+    expand_table: Optional[np.ndarray]
+    expand_counts: Optional[np.ndarray]
+
+
+def expand_summary(table: np.ndarray, names=None) -> List[dict]:
+    """Expand's rows as records, one per value that has a seed: ``value`` (and ``name`` with ``names``), ``seeds``, ``gained``,
+    and ``margin``, the distance in pixels the value actually grew (the square root of MAX_D2, to two decimals; 0.0 when it gained
+    nothing) with ``farthest`` the index of the pixel that lies that far out (None when it gained nothing)."""
+    recs = []
+    for v, row in enumerate(np.asarray(table, np.uint32).reshape(-1, _lib.EXPAND_WORDS).tolist()):
+        if not row[_lib.EXPAND_SEEDS]:
+            continue
+        rec = {"value": v, "seeds": row[_lib.EXPAND_SEEDS], "gained": row[_lib.EXPAND_GAINED], "margin": round(math.sqrt(row[_lib.EXPAND_MAX_D2]), 2),
+               "farthest": row[_lib.EXPAND_MAX_PIXEL] if row[_lib.EXPAND_GAINED] else None}
+        if names is not None and v < len(names):
+            rec["name"] = names[v]
+        recs.append(rec)
+    return recs
+
+
+@dataclass
 class CompareCmd:
     """``Compare``'s command: ``Ignore(a, b)`` takes the pixels whose ``a`` (``b``) plane holds that value out of the comparison
     (None: every value is compared); ``pair_slots`` sizes the pair table of the table form (0: the library's 2^20)."""
@@ -2344,6 +2443,34 @@ class FramePath:
         k = min(n.value, rows)
         return AnchorsFrame(klass, conf, labels, table[:k] if table is not None else None, n.value, scaled, dist2,
                             anchors[:k] if anchors is not None else None)
+
+    def advance_expand(self, img: np.ndarray, reach: int = 0, factor: float = 1.0, decode: int = _lib.DECODE_RAW, connectivity: int = _lib.CONNECT_8,
+                       min_pixels: int = 0, flags: int = 0, table_rows: int = 1024, want_labels: bool = True, want_klass: bool = True,
+                       want_conf: bool = True, want_scaled: bool = False, want_grown: bool = True, want_dist2: bool = True,
+                       want_source: bool = False) -> ExpandFrame:
+        """The fused path with the grown label plane, scale -> model -> Segments decode -> Regions -> Expand of the label plane with
+        the pixels of no region open, in one call -> ``ExpandFrame``; every result field is None when no model is loaded (``scaled``
+        is still produced)."""
+        img, w, h, f, ow, oh = self._front(img, factor)
+        npix = oh.value * ow.value
+        rows = max(0, min(int(table_rows), npix))
+        klass, conf = self._plane(ow, oh, want_klass), self._plane(ow, oh, want_conf)
+        labels = self._plane(ow, oh, want_labels, np.uint32)
+        table = np.zeros((rows, _lib.REGION_WORDS), np.uint64) if rows else None
+        scaled = self._plane(ow, oh, want_scaled, channels=3)
+        grown, dist2, source = (self._plane(ow, oh, want, np.uint32) for want in (want_grown, want_dist2, want_source))
+        etable = np.empty((rows, _lib.EXPAND_WORDS), np.uint32) if rows else None
+        counts = np.zeros(_lib.EXPAND_COUNT_WORDS, np.uint32)
+        n = C.c_uint32(0)
+        rc = self.ctx.L.infur_frame_expand(self.ctx.h, img.ctypes.data, w, h, f, self.scale_mode, decode, connectivity, min_pixels, flags,
+                                           _ptr(klass), _ptr(conf), npix, _ptr(labels), npix * 4, _ptr(table), rows, C.addressof(n), _ptr(scaled),
+                                           C.byref(ow), C.byref(oh), reach, _ptr(grown), npix * 4, _ptr(dist2), npix * 4, _ptr(source), npix * 4,
+                                           _ptr(etable), rows, counts.ctypes.data)
+        if not self._loaded(rc):
+            return ExpandFrame(None, None, None, None, None, scaled, None, None, None, None, None)
+        k = min(n.value, rows)
+        return ExpandFrame(klass, conf, labels, table[:k] if table is not None else None, n.value, scaled, grown, dist2, source,
+                           etable[:k] if etable is not None else None, counts)
 
     def advance_split(self, img: np.ndarray, core: int, factor: float = 1.0, decode: int = _lib.DECODE_RAW, connectivity: int = _lib.CONNECT_8,
                       min_pixels: int = 0, flags: int = 0, table_rows: int = 1024, split_rows: int = 1024, pair_slots: int = 0,

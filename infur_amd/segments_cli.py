@@ -70,6 +70,11 @@ per frame FILE receives the eight u32 counts, then the records (eight u32 per br
 DIAG, MIN_H), then the vertices (u32 pixel ids); ``--centrelines-corners`` keeps only the vertices at which a branch turns.  Every
 line gains ``"branches"``: the frame's branches, vertices, links, nodes, ends and rings.
 
+``--expand PX`` (needs ``--regions``) grows every region by up to PX pixels into the pixels of no region (``--min-pixels`` holes, a
+skipped background; 0: as far as it takes), each open pixel going to its exact nearest region (``infur_frame_expand``): every line
+gains ``"expand"`` (the frame's seeds, open, gained and left pixels and the largest distance to a region) and every region record
+``"gained"`` and ``"margin"``, the distance it actually grew.  ``--expand-out FILE`` receives the grown u32 label planes.
+
 ``--truth FILE`` grades every frame: FILE holds one u8 ground-truth class plane of the scaled frame's size per frame, back to back;
 the class plane is compared with it (``infur_compare``; ``--truth-ignore V`` leaves the pixels whose truth is V, a "void" label,
 out), every line gains ``"pixel_accuracy"`` and ``"miou"``, and one last line holds the totals of the confusion matrices added up
@@ -104,6 +109,7 @@ from __future__ import annotations
 
 import argparse
 import json
+import math
 import sys
 import time
 
@@ -160,6 +166,8 @@ def main(argv=None) -> int:
     ap.add_argument("--skeleton", action="store_true", help="thin every region to its one-pixel centreline on the device (needs --regions)")
     ap.add_argument("--skeleton-out", default="", help="raw u8 kind planes, one byte per pixel (needs --skeleton)")
     ap.add_argument("--skeleton-rounds", type=int, default=0, metavar="N", help="at most N sub-iterations (0: the library's bound; needs --skeleton)")
+    ap.add_argument("--expand", type=int, default=None, metavar="PX", help="grow every region by up to PX pixels into the pixels of no region, 0: unbounded (needs --regions)")
+    ap.add_argument("--expand-out", default="", help="raw u32 grown label planes, four bytes per pixel (needs --expand)")
     ap.add_argument("--centrelines-out", default="", help="per frame 8 u32 counts, the branch records, the vertices (needs --skeleton)")
     ap.add_argument("--centrelines-corners", action="store_true", help="keep only the vertices at which a branch turns (needs --centrelines-out)")
     a = ap.parse_args(argv)
@@ -178,6 +186,18 @@ def main(argv=None) -> int:
                             (a.outlines_out, "--outlines-out"), (a.anchors, "--anchors"), (a.truth, "--truth"), (a.split is not None, "--split")):
             if given:
                 ap.error(f"--skeleton does not combine with {name}: the fused skeleton call leaves no plane on the device for it")
+    if a.expand_out and a.expand is None:
+        ap.error("--expand-out needs --expand")
+    if a.expand is not None:
+        if not a.regions:
+            ap.error("--expand needs --regions")
+        if not 0 <= a.expand <= 0xFFFFFFFF:
+            ap.error("--expand: a reach in pixels, 0 (unbounded) or more")
+        for given, name in ((a.sieve is not None, "--sieve"), (a.shapes, "--shapes"), (a.tracks, "--tracks"), (a.runs_out, "--runs-out"),
+                            (a.outlines_out, "--outlines-out"), (a.anchors, "--anchors"), (a.truth, "--truth"), (a.split is not None, "--split"),
+                            (a.skeleton, "--skeleton")):
+            if given:
+                ap.error(f"--expand does not combine with {name}: the fused expand call leaves no plane on the device for it")
     if a.split_out and a.split is None:
         ap.error("--split-out needs --split")
     if a.split is not None:
@@ -253,7 +273,7 @@ def main(argv=None) -> int:
     from . import _lib
     from .app import RawVideoSource, VideoProcError
     from .processors import (Compare, CompareOut, confusion_summary, sieve_summary, Context, Coverage, CoverageOut, FramePath, Model, ModelCmd, Outlines, OutlinesOut, Runs, RunsOut, SegmentsFrame, Simplify, SimplifyOut,
-                             class_summary, outlines_polygons, polygon_fidelity, region_summary, shape_summary, skeleton_summary, split_core, split_summary, tolerance_to_tol16,
+                             class_summary, expand_summary, outlines_polygons, polygon_fidelity, region_summary, shape_summary, skeleton_summary, split_core, split_summary, tolerance_to_tol16,
                              track_summary)
 
     tol16 = tolerance_to_tol16(a.outlines_tolerance) if a.outlines_tolerance is not None else None
@@ -291,7 +311,8 @@ def main(argv=None) -> int:
     fsplit = open(a.split_out, "wb") if a.split_out else None
     fskel = open(a.skeleton_out, "wb") if a.skeleton_out else None
     fcl = open(a.centrelines_out, "wb") if a.centrelines_out else None
-    if a.regions and (a.sieve is not None or a.shapes or a.split is not None or a.skeleton):
+    fexp = open(a.expand_out, "wb") if a.expand_out else None
+    if a.regions and (a.sieve is not None or a.shapes or a.split is not None or a.skeleton or a.expand is not None):
         flags = _lib.REGIONS_SKIP_BACKGROUND if a.skip_background else 0
     elif a.regions:
         oh, ow = _out_dims(ctx, a.width, a.height, a.scale)
@@ -322,6 +343,11 @@ def main(argv=None) -> int:
         elif a.split is not None:  # scale -> model -> decode -> Regions -> Anchors -> Split of the label plane under its dist2, in one call
             r = fp.advance_split(img, split_core(a.split), a.scale, decode, a.connectivity, a.min_pixels, flags, table_rows=max(0, a.max_regions),
                                  split_rows=1 << 32, want_labels=freg is not None, want_klass=True, want_conf=True, want_segments=fsplit is not None)
+            s = SegmentsFrame(r.klass, r.conf, _class_stats(r.klass, r.conf, model.get_info().num_classes), None, None)
+            labels, table, nreg = r.labels, r.table, r.n
+        elif a.expand is not None:  # scale -> model -> decode -> Regions -> Expand of the label plane with the pixels of no region open, in one call
+            r = fp.advance_expand(img, a.expand, a.scale, decode, a.connectivity, a.min_pixels, flags, table_rows=max(0, a.max_regions),
+                                  want_labels=freg is not None, want_klass=True, want_conf=True, want_grown=fexp is not None, want_dist2=False)
             s = SegmentsFrame(r.klass, r.conf, _class_stats(r.klass, r.conf, model.get_info().num_classes), None, None)
             labels, table, nreg = r.labels, r.table, r.n
         elif fcl is not None:  # the call below, then Centrelines of the label plane and the kind plane under dist2, in one call
@@ -427,6 +453,19 @@ def main(argv=None) -> int:
                 freg.write(memoryview(labels).cast("B"))
             if fsplit is not None and r.segments is not None:
                 fsplit.write(memoryview(r.segments).cast("B"))
+        if a.expand is not None:
+            ec = [int(v) for v in r.expand_counts]
+            rec["n_regions"], rec["regions"] = nreg, region_summary(table, nreg, ow, oh)
+            rec["expand"] = {"seeds": ec[_lib.EXPAND_COUNT_SEEDS], "open": ec[_lib.EXPAND_COUNT_OPEN], "gained": ec[_lib.EXPAND_COUNT_GAINED],
+                             "left": ec[_lib.EXPAND_COUNT_LEFT], "farthest": round(math.sqrt(ec[_lib.EXPAND_COUNT_MAX_D2]), 2)}
+            grew = {e["value"]: e for e in expand_summary(r.expand_table if r.expand_table is not None else ())}
+            for region in rec["regions"]:
+                e = grew.get(region["id"])
+                region["gained"], region["margin"] = (e["gained"], e["margin"]) if e else (None, None)
+            if freg is not None:
+                freg.write(memoryview(labels).cast("B"))
+            if fexp is not None and r.grown is not None:
+                fexp.write(memoryview(r.grown).cast("B"))
         if a.skeleton:
             sk = skeleton_summary(r.skeleton_table[:nreg] if r.skeleton_table is not None else None, r.counts)
             rec["n_regions"], rec["regions"] = nreg, region_summary(table, nreg, ow, oh, anchors=r.anchors)
@@ -481,7 +520,7 @@ def main(argv=None) -> int:
         ftruth.close()
     if a.outlines_fidelity:
         fst.write(json.dumps({"frames": n, "polygon_fidelity": fid_total}) + "\n")
-    for f in (flab, fconf, freg, ftrk, fruns, foutl, fdist, fhull, fsplit, fskel, fcl, fst):
+    for f in (flab, fconf, freg, ftrk, fruns, foutl, fdist, fhull, fsplit, fskel, fcl, fexp, fst):
         if f is not None:
             f.flush()
     el = time.perf_counter() - t0

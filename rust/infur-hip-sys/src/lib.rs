@@ -375,6 +375,24 @@ pub const INFUR_CENTRELINES_COUNT_WORDS: u32 = 8;
 pub const INFUR_CENTRELINES_OVERFLOW: u32 = 1;
 /// bit of `infur_features()`: the Centrelines calls below exist
 pub const INFUR_FEATURE_CENTRELINES: u32 = 32768;
+/// Expand: the words of a table row and of the counts, the status bit, the longest side, "no seed / nothing gained"
+pub const INFUR_EXPAND_SEEDS: u32 = 0;
+pub const INFUR_EXPAND_GAINED: u32 = 1;
+pub const INFUR_EXPAND_MAX_D2: u32 = 2;
+pub const INFUR_EXPAND_MAX_PIXEL: u32 = 3;
+pub const INFUR_EXPAND_WORDS: u32 = 4;
+pub const INFUR_EXPAND_COUNT_SEEDS: u32 = 0;
+pub const INFUR_EXPAND_COUNT_OPEN: u32 = 1;
+pub const INFUR_EXPAND_COUNT_GAINED: u32 = 2;
+pub const INFUR_EXPAND_COUNT_LEFT: u32 = 3;
+pub const INFUR_EXPAND_COUNT_MAX_D2: u32 = 4;
+pub const INFUR_EXPAND_COUNT_STATUS: u32 = 7;
+pub const INFUR_EXPAND_COUNT_WORDS: u32 = 8;
+pub const INFUR_EXPAND_NO_SEED: u32 = 1;
+pub const INFUR_EXPAND_MAX_SIDE: u32 = 32768;
+pub const INFUR_EXPAND_NONE: u32 = 0xFFFF_FFFF;
+/// bit of `infur_features()`: the Expand calls below exist
+pub const INFUR_FEATURE_EXPAND: u32 = 65536;
 
 extern "C" {
     pub fn infur_abi_version() -> u32;
@@ -758,4 +776,23 @@ extern "C" {
                                        d_kind: *mut c_void, kind_capacity: usize, d_skel_table: *mut c_void, skel_rows: u32,
                                        d_skel_counts: *mut c_void, cl_flags: u32, max_links: u32, d_records: *mut c_void,
                                        record_rows: u32, d_vertices: *mut c_void, vertex_rows: u32, d_cl_counts: *mut c_void) -> i32;
+    // Expand: every open pixel takes the value of its exact nearest seed, within a reach
+    pub fn infur_expand(c: *mut infur_ctx, plane: *const c_void, elem_bytes: u32, h: u32, w: u32, flags: u32, open_value: u32, reach: u32,
+                        out: *mut c_void, dist2: *mut u32, source: *mut u32, table: *mut u32, rows: u32, counts: *mut u32) -> i32;
+    pub fn infur_expand_dev(c: *mut infur_ctx, d_plane: *const c_void, elem_bytes: u32, h: u32, w: u32, flags: u32, open_value: u32,
+                            reach: u32, d_out: *mut c_void, d_dist2: *mut c_void, d_source: *mut c_void, d_table: *mut c_void, rows: u32,
+                            d_counts: *mut c_void) -> i32;
+    pub fn infur_frame_expand(c: *mut infur_ctx, bgr: *const u8, w: u32, h: u32, factor: f32, scale_mode: u32, decode: u32,
+                              connectivity: u32, min_pixels: u32, flags: u32, klass: *mut u8, conf: *mut u8, plane_capacity: usize,
+                              labels: *mut u32, labels_capacity: usize, table: *mut u64, table_rows: u32, n_regions: *mut u32,
+                              scaled_bgr: *mut u8, ow: *mut u32, oh: *mut u32, reach: u32, grown: *mut u32, grown_capacity: usize,
+                              dist2: *mut u32, dist2_capacity: usize, source: *mut u32, source_capacity: usize, expand_table: *mut u32,
+                              expand_rows: u32, expand_counts: *mut u32) -> i32;
+    pub fn infur_frame_expand_dev(c: *mut infur_ctx, d_bgr: *const c_void, w: u32, h: u32, factor: f32, scale_mode: u32, decode: u32,
+                                  connectivity: u32, min_pixels: u32, flags: u32, d_klass: *mut c_void, d_conf: *mut c_void,
+                                  plane_capacity: usize, d_labels: *mut c_void, labels_capacity: usize, d_table: *mut c_void,
+                                  table_rows: u32, d_n_regions: *mut c_void, d_scaled_bgr: *mut c_void, ow: *mut u32, oh: *mut u32,
+                                  reach: u32, d_grown: *mut c_void, grown_capacity: usize, d_dist2: *mut c_void, dist2_capacity: usize,
+                                  d_source: *mut c_void, source_capacity: usize, d_expand_table: *mut c_void, expand_rows: u32,
+                                  d_expand_counts: *mut c_void) -> i32;
 }

@@ -696,6 +696,72 @@ impl Processor for HipAnchors {
     }
 }
 
+// ---------------------------------------------------------------- Expand (every open pixel takes the value of its nearest seed)
+/// What `HipExpand` produces: the grown plane in `out_u8` or `out_u32`, whichever the input's elements are; `dist2` the `w * h`
+/// squared distances to the nearest seed (0 on a seed) and `source` that seed's index, `INFUR_EXPAND_NONE` throughout where the
+/// plane holds no seed; `table` `rows` rows of `INFUR_EXPAND_WORDS` words (SEEDS, GAINED, MAX_D2, MAX_PIXEL), one per value below
+/// `rows`; `counts` the `INFUR_EXPAND_COUNT_WORDS` counts.
+pub struct Expanded { pub rows: usize, pub want_out: bool, pub want_dist2: bool, pub want_source: bool, pub out_u8: Vec<u8>, pub out_u32: Vec<u32>,
+                      pub dist2: Vec<u32>, pub source: Vec<u32>, pub table: Vec<u32>, pub counts: [u32; sys::INFUR_EXPAND_COUNT_WORDS as usize] }
+impl Default for Expanded {
+    fn default() -> Self {
+        Self { rows: 256, want_out: true, want_dist2: true, want_source: false, out_u8: Vec::new(), out_u32: Vec::new(), dist2: Vec::new(),
+               source: Vec::new(), table: Vec::new(), counts: [0; sys::INFUR_EXPAND_COUNT_WORDS as usize] }
+    }
+}
+impl Expanded {
+    pub fn word(&self, row: usize, word: u32) -> u32 { self.table[row * sys::INFUR_EXPAND_WORDS as usize + word as usize] }
+    /// the plane holds no seed: nothing was gained
+    pub fn no_seed(&self) -> bool { self.counts[sys::INFUR_EXPAND_COUNT_STATUS as usize] & sys::INFUR_EXPAND_NO_SEED != 0 }
+}
+pub enum ExpandCmd { Grow { open_value: u32, reach: u32 } }
+/// The stage that gives a value to the pixels that have none: every open pixel takes the value of its exact nearest seed (ties to
+/// the smallest index) where that lies within `reach` pixels (0: anywhere).  Integer results, identical from run to run.
+pub struct HipExpand { ctx: Rc<Ctx>, open_value: u32, reach: u32, dirty: bool }
+impl HipExpand {
+    pub fn new(ctx: Rc<Ctx>) -> Self { Self { ctx, open_value: 0, reach: 0, dirty: true } }
+}
+impl Processor for HipExpand {
+    type Command = ExpandCmd;
+    type ControlError = HipError;
+    type Input = RunsPlane;
+    type Output = Expanded;
+    type ProcessResult = Result<(), HipError>;
+
+    fn control(&mut self, cmd: ExpandCmd) -> Result<&mut Self, HipError> {
+        let ExpandCmd::Grow { open_value, reach } = cmd;
+        self.dirty |= (open_value, reach) != (self.open_value, self.reach);
+        self.open_value = open_value;
+        self.reach = reach;
+        Ok(self)
+    }
+    fn is_dirty(&self) -> bool { self.dirty }
+    fn advance(&mut self, inp: &RunsPlane, out: &mut Expanded) -> Result<(), HipError> {
+        self.dirty = false;
+        let [w, h] = inp.size;
+        let (ptr, len, elem_bytes) = match &inp.data {
+            RunsPlaneData::U8(p) => (p.as_ptr() as *const std::ffi::c_void, p.len(), 1u32),
+            RunsPlaneData::U32(p) => (p.as_ptr() as *const std::ffi::c_void, p.len(), 4u32),
+        };
+        if len != w * h { return Err(HipError::status(sys::INFUR_E_SHAPE)); }
+        out.out_u8.resize(if out.want_out && elem_bytes == 1 { w * h } else { 0 }, 0);
+        out.out_u32.resize(if out.want_out && elem_bytes == 4 { w * h } else { 0 }, 0);
+        out.dist2.resize(if out.want_dist2 { w * h } else { 0 }, 0);
+        out.source.resize(if out.want_source { w * h } else { 0 }, 0);
+        out.table.resize(out.rows * sys::INFUR_EXPAND_WORDS as usize, 0);
+        let grown = if !out.want_out || w * h == 0 { std::ptr::null_mut() }
+                    else if elem_bytes == 1 { out.out_u8.as_mut_ptr() as *mut std::ffi::c_void } else { out.out_u32.as_mut_ptr() as *mut std::ffi::c_void };
+        let rc = unsafe {
+            sys::infur_expand(self.ctx.0, if w * h > 0 { ptr } else { std::ptr::null() }, elem_bytes, h as u32, w as u32, 0, self.open_value, self.reach, grown,
+                              if out.want_dist2 { out.dist2.as_mut_ptr() } else { std::ptr::null_mut() },
+                              if out.want_source { out.source.as_mut_ptr() } else { std::ptr::null_mut() },
+                              if out.rows > 0 { out.table.as_mut_ptr() } else { std::ptr::null_mut() }, out.rows as u32, out.counts.as_mut_ptr())
+        };
+        if rc != sys::INFUR_OK { return Err(HipError::from_ctx(&self.ctx, rc)); }
+        Ok(())
+    }
+}
+
 // ---------------------------------------------------------------- Compare (confusion matrix, best partner per value)
 /// What `HipCompare` produces for `rows_a` x `rows_b` values: `matrix` row-major (`matrix[i * rows_b + j]`: the pixels with a == i
 /// and b == j), `a` and `b` rows of `INFUR_COMPARE_WORDS` words (PIXELS, PARTNER, INTER, UNION) per value of either plane --
