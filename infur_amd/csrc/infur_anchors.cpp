@@ -1,9 +1,10 @@
 // infur_anchors.cpp -- Anchors, the stage behind Regions and Tracks that measures how thick a region is (include/infur_hip.h): the
 // exact squared distance transform of a byte or u32 plane by value, and per value its most interior pixel, so that a host places a
 // caption on the object and not at a centroid beside it.  Kernels: anchors.hip.  Everything is enqueued on the context's stream;
-// the element checks and the frame wrapper are the egress stages' (infur_egress.h, infur_rt.h), and so is the rule that its
+// the element checks are the egress stages' (infur_egress.h), the frame calls' staging, capacity checks and read-back the ones the
+// stages behind Regions share (infur_region_frames.h) around frame_host (infur_rt.h), and so is the rule that its
 // buffers are private scratch: growing them leaves mem_gen -- and with it the graphs infur_frame_advance_dev has cached -- alone.
-#include "infur_egress.h"
+#include "infur_region_frames.h"
 
 using namespace infur;
 
@@ -32,22 +33,6 @@ struct AnchStage {
         dist2 = align_up(rows * INFUR_ANCHOR_WORDS * 4, 256);
         plane = dist2 + align_up(npix * 4, 256);
         bytes = plane + align_up(plane_bytes, 256) + 256;
-    }
-};
-
-// st_anch_io of infur_frame_anchors: [count][table, at most one row per pixel][label plane][class plane][confidence plane][dist2]
-// [anchors, table_rows x 2 words], on 256-byte boundaries
-struct AnchFrameStage {
-    size_t rows, table, labels, klass, conf, dist2, anchors, bytes;
-    AnchFrameStage(size_t npix, uint32_t table_rows, uint32_t anchor_rows) {
-        rows = table_rows < npix ? table_rows : npix;
-        table = 256;
-        labels = table + align_up(rows * INFUR_REGION_WORDS * 8, 256);
-        klass = labels + align_up(npix * 4, 256);
-        conf = klass + align_up(npix, 256);
-        dist2 = conf + align_up(npix, 256);
-        anchors = dist2 + align_up(npix * 4, 256);
-        bytes = anchors + align_up((size_t)anchor_rows * INFUR_ANCHOR_WORDS * 4, 256);
     }
 };
 
@@ -110,13 +95,9 @@ int32_t infur_frame_anchors_dev(infur_ctx* c, const void* d_bgr, uint32_t w, uin
         size_t lb_cap = labels_cap;
         if (c->loaded && npix) {
             if (!d_labels && !d_table && !d_n && !anch) return INFUR_E_INVALID_ARG;
-            if (d_labels && labels_cap < npix * 4) return fail(c, INFUR_E_CAPACITY, "the label plane needs %zu bytes, buffer has %zu", npix * 4, labels_cap);
-            if (d_dist2 && dist2_cap < npix * 4) return fail(c, INFUR_E_CAPACITY, "the distance plane needs %zu bytes, buffer has %zu", npix * 4, dist2_cap);
-            if (!lb && anch) {  // the label plane Anchors reads, when the caller does not want it
-                RETIF(ensure_private(c, c->st_anch_plane, npix * 4));
-                lb = c->st_anch_plane.p;
-                lb_cap = npix * 4;
-            }
+            RETIF(cap_check(c, "label", true, d_labels, labels_cap, npix * 4));
+            RETIF(cap_check(c, "distance", true, d_dist2, dist2_cap, npix * 4));
+            if (anch) RETIF(borrow_planes(c, c->st_anch_plane, npix, &lb, &lb_cap));  // the label plane Anchors reads
         }  // (otherwise the call below fails before it decodes: bad scale, empty frame or no model)
         // scale -> model -> Segments decode -> Regions, with that call's own checks, errors and MODEL_NOT_LOADED rule
         RETIF(infur_frame_regions_dev(c, d_bgr, w, h, factor, mode, decode, connectivity, min_pixels, flags, d_klass, d_conf, plane_cap, lb, lb_cap,
@@ -133,44 +114,24 @@ int32_t infur_frame_anchors(infur_ctx* c, const uint8_t* bgr, uint32_t w, uint32
     return abi_call(c, [&]() -> int32_t {
         if (!c || !ow || !oh) return INFUR_E_INVALID_ARG;
         RETIF(reg_check(c, connectivity, flags));
-        AnchFrameStage st(0, 0, 0);
+        const RegHostOut o{klass, conf, plane_cap, labels, labels_cap, table, table_rows, n_regions, dist2, dist2_cap, anchors};
+        RegAnchLayout st(0, 0, 0, 0);  // st_anch_io: Regions' and Anchors' products and nothing else
         uint8_t* base = nullptr;
-        const uint32_t arows = anchors ? table_rows : 0;
         return frame_host(
             c, bgr, w, h, factor, scaled, ow, oh,
             [&](size_t npix) -> int32_t {
-                if ((klass || conf) && plane_cap < npix) return fail(c, INFUR_E_CAPACITY, "a plane needs %zu bytes, buffer has %zu", npix, plane_cap);
-                if (labels && labels_cap < npix * 4) return fail(c, INFUR_E_CAPACITY, "the label plane needs %zu bytes, buffer has %zu", npix * 4, labels_cap);
-                if (c->loaded && dist2 && dist2_cap < npix * 4)
-                    return fail(c, INFUR_E_CAPACITY, "the distance plane needs %zu bytes, buffer has %zu", npix * 4, dist2_cap);
-                st = AnchFrameStage(npix, table ? table_rows : 0, arows);
-                RETIF(ensure_private(c, c->st_anch_io, st.bytes));
+                RETIF(reg_caps_check(c, o, npix));
+                st = RegAnchLayout(0, npix, o.staged_rows(), o.anchor_rows());
+                RETIF(ensure_private(c, c->st_anch_io, st.end));
                 base = (uint8_t*)c->st_anch_io.p;
                 return INFUR_OK;
             },
             [&](void* d_bgr, void* d_scaled) {
-                const size_t npix = (size_t)*ow * *oh;
-                // (table_rows reaches the device call as given when anchors are wanted: its rows are all written)
-                return infur_frame_anchors_dev(c, d_bgr, w, h, factor, mode, decode, connectivity, min_pixels, flags, base + st.klass,
-                                               (conf || table) ? base + st.conf : nullptr, npix, (labels || dist2 || arows) ? base + st.labels : nullptr,
-                                               npix * 4, (table && st.rows) ? base + st.table : nullptr, arows ? table_rows : (uint32_t)st.rows,
-                                               (labels || table || n_regions) ? base : nullptr, d_scaled, ow, oh, dist2 ? base + st.dist2 : nullptr,
-                                               npix * 4, arows ? base + st.anchors : nullptr);
+                const RegDevArgs a = reg_dev_args(o, base, st, (size_t)*ow * *oh, false);
+                return infur_frame_anchors_dev(c, d_bgr, w, h, factor, mode, decode, connectivity, min_pixels, flags, a.klass, a.conf, a.plane_cap,
+                                               a.labels, a.labels_cap, a.table, a.table_rows, a.n, d_scaled, ow, oh, a.dist2, a.dist2_cap, a.anchors);
             },
-            [&](size_t npix) -> int32_t {
-                if (klass) HIPCHK(c, hipMemcpyAsync(klass, base + st.klass, npix, hipMemcpyDeviceToHost, c->stream));
-                if (conf) HIPCHK(c, hipMemcpyAsync(conf, base + st.conf, npix, hipMemcpyDeviceToHost, c->stream));
-                if (dist2) HIPCHK(c, hipMemcpyAsync(dist2, base + st.dist2, npix * 4, hipMemcpyDeviceToHost, c->stream));
-                if (arows) HIPCHK(c, hipMemcpyAsync(anchors, base + st.anchors, (size_t)arows * INFUR_ANCHOR_WORDS * 4, hipMemcpyDeviceToHost, c->stream));
-                uint32_t n = 0;
-                HIPCHK(c, hipMemcpyAsync(&n, base, 4, hipMemcpyDeviceToHost, c->stream));
-                if (labels) HIPCHK(c, hipMemcpyAsync(labels, base + st.labels, npix * 4, hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                const size_t rows = n < st.rows ? n : st.rows;
-                if (table && rows) HIPCHK(c, hipMemcpy(table, base + st.table, rows * INFUR_REGION_WORDS * 8, hipMemcpyDeviceToHost));
-                if (n_regions) *n_regions = n;
-                return INFUR_OK;
-            });
+            [&](size_t npix) { return reg_read_back(c, base, st, npix, o); });
     });
 }
 

@@ -1,9 +1,10 @@
 // infur_centrelines.cpp -- Centrelines, the stage behind Skeleton that traces the one-pixel centrelines into polyline branches
 // (include/infur_hip.h): a record per branch and the vertex lists in Outlines' layout, and eight counts.  Kernels: centrelines.hip.
-// Everything is enqueued on the context's stream; the element checks and the frame wrapper are the egress stages' (infur_egress.h,
-// infur_rt.h), and so is the rule that its buffers are private scratch: growing them leaves mem_gen -- and with it the graphs
+// Everything is enqueued on the context's stream; the element checks are the egress stages' (infur_egress.h), the host-pointer frame
+// call's staging of Regions' and Anchors' products, their capacity checks and read-back the ones the stages behind Regions share
+// (infur_region_frames.h), and so is the rule that its buffers are private scratch: growing them leaves mem_gen -- and with it the graphs
 // infur_frame_advance_dev has cached -- alone.
-#include "infur_egress.h"
+#include "infur_region_frames.h"
 
 using namespace infur;
 
@@ -58,23 +59,16 @@ int32_t centrelines_read_back(infur_ctx* c, const uint8_t* base, const Centrelin
     return INFUR_OK;
 }
 
-// st_cl_io of infur_frame_centrelines: Centrelines' own staging as above (no input planes), then what the calls before it produce:
-// [n_regions][region table][label plane][class plane][confidence plane][dist2][anchors][kind][skeleton table][skeleton counts]
+// st_cl_io of infur_frame_centrelines: Centrelines' own staging as above, then Regions' and Anchors' products from its kind slot on
+// (no kind, height or plane travels: the slots behind the vertices are free), then Skeleton's: [kind][skeleton table][skeleton counts]
 struct CentrelinesFrameStage {
     CentrelinesStage cl;
-    size_t rrows, srows, n, rtable, rlabels, klass, conf, dist2, anchors, kind, stable, scounts, bytes;
-    CentrelinesFrameStage(size_t npix, uint32_t table_rows, uint32_t anchor_rows, size_t skel_rows, size_t record_rows, size_t vrows)
-        : cl(npix, record_rows, vrows, false, false, 0) {
-        rrows = table_rows < npix ? table_rows : npix;
+    RegAnchLayout r;
+    size_t srows, kind, stable, scounts, bytes;
+    CentrelinesFrameStage(size_t npix, const RegHostOut& o, size_t skel_rows, size_t record_rows, size_t vrows)
+        : cl(npix, record_rows, vrows, false, false, 0), r(cl.kind, npix, o.staged_rows(), o.anchor_rows()) {
         srows = skel_rows;
-        n = cl.kind;  // (no kind, height or plane travels: the slots behind the vertices are free)
-        rtable = n + 256;
-        rlabels = rtable + align_up(rrows * INFUR_REGION_WORDS * 8, 256);
-        klass = rlabels + align_up(npix * 4, 256);
-        conf = klass + align_up(npix, 256);
-        dist2 = conf + align_up(npix, 256);
-        anchors = dist2 + align_up(npix * 4, 256);
-        kind = anchors + align_up((size_t)anchor_rows * INFUR_ANCHOR_WORDS * 4, 256);
+        kind = r.end;
         stable = kind + align_up(npix, 256);
         scounts = stable + align_up(srows * INFUR_SKELETON_WORDS * 4, 256);
         bytes = scounts + 256;
@@ -166,50 +160,35 @@ int32_t infur_frame_centrelines(infur_ctx* c, const uint8_t* bgr, uint32_t w, ui
                                 uint32_t* vertices, uint32_t vertex_rows, uint32_t* cl_counts) {
     return abi_call(c, [&]() -> int32_t {
         if (!c || !ow || !oh) return INFUR_E_INVALID_ARG;
-        CentrelinesFrameStage st(0, 0, 0, 0, 0, 0);
+        const RegHostOut o{klass, conf, plane_cap, labels, labels_cap, table, table_rows, n_regions, dist2, dist2_cap, anchors};
+        CentrelinesFrameStage st(0, o, 0, 0, 0);
         uint8_t* base = nullptr;
-        const uint32_t arows = anchors ? table_rows : 0;
         const bool cl = (records && record_rows) || (vertices && vertex_rows) || cl_counts;
         const bool skel = kind || (skel_table && skel_rows) || skel_counts;
         return frame_host(
             c, bgr, w, h, factor, scaled, ow, oh,
             [&](size_t npix) -> int32_t {
-                if ((klass || conf) && plane_cap < npix) return fail(c, INFUR_E_CAPACITY, "a plane needs %zu bytes, buffer has %zu", npix, plane_cap);
-                if (labels && labels_cap < npix * 4) return fail(c, INFUR_E_CAPACITY, "the label plane needs %zu bytes, buffer has %zu", npix * 4, labels_cap);
-                if (c->loaded && dist2 && dist2_cap < npix * 4)
-                    return fail(c, INFUR_E_CAPACITY, "the distance plane needs %zu bytes, buffer has %zu", npix * 4, dist2_cap);
-                if (c->loaded && kind && kind_cap < npix) return fail(c, INFUR_E_CAPACITY, "the kind plane needs %zu bytes, buffer has %zu", npix, kind_cap);
-                st = CentrelinesFrameStage(npix, table ? table_rows : 0, arows, skel_table ? skel_rows : 0, records ? record_rows : 0, vertices ? vertex_rows : 0);
+                RETIF(reg_caps_check(c, o, npix));
+                RETIF(cap_check(c, "kind", c->loaded, kind, kind_cap, npix));
+                st = CentrelinesFrameStage(npix, o, skel_table ? skel_rows : 0, records ? record_rows : 0, vertices ? vertex_rows : 0);
                 RETIF(ensure_private(c, c->st_cl_io, st.bytes));
                 base = (uint8_t*)c->st_cl_io.p;
                 return INFUR_OK;
             },
             [&](void* d_bgr, void* d_scaled) {
                 const size_t npix = (size_t)*ow * *oh;
+                const RegDevArgs a = reg_dev_args(o, base, st.r, npix, skel || cl);
                 return infur_frame_centrelines_dev(
-                    c, d_bgr, w, h, factor, mode, decode, connectivity, min_pixels, flags, base + st.klass, (conf || table) ? base + st.conf : nullptr, npix,
-                    (labels || dist2 || arows || skel || cl) ? base + st.rlabels : nullptr, npix * 4, (table && st.rrows) ? base + st.rtable : nullptr,
-                    arows ? table_rows : (uint32_t)st.rrows, (labels || table || n_regions) ? base + st.n : nullptr, d_scaled, ow, oh,
-                    (dist2 || skel || cl) ? base + st.dist2 : nullptr, npix * 4, arows ? base + st.anchors : nullptr, max_rounds,
-                    (kind || cl) ? base + st.kind : nullptr, npix, st.srows ? base + st.stable : nullptr, (uint32_t)st.srows,
+                    c, d_bgr, w, h, factor, mode, decode, connectivity, min_pixels, flags, a.klass, a.conf, a.plane_cap, a.labels, a.labels_cap, a.table,
+                    a.table_rows, a.n, d_scaled, ow, oh, a.dist2, a.dist2_cap, a.anchors, max_rounds, (kind || cl) ? base + st.kind : nullptr, npix, st.srows ? base + st.stable : nullptr, (uint32_t)st.srows,
                     skel_counts ? base + st.scounts : nullptr, cl_flags, max_links, st.cl.rows ? base + st.cl.records : nullptr, (uint32_t)st.cl.rows,
                     st.cl.vertex_rows ? base + st.cl.vertices : nullptr, (uint32_t)st.cl.vertex_rows, cl ? base : nullptr);
             },
             [&](size_t npix) -> int32_t {
-                if (klass) HIPCHK(c, hipMemcpyAsync(klass, base + st.klass, npix, hipMemcpyDeviceToHost, c->stream));
-                if (conf) HIPCHK(c, hipMemcpyAsync(conf, base + st.conf, npix, hipMemcpyDeviceToHost, c->stream));
-                if (dist2) HIPCHK(c, hipMemcpyAsync(dist2, base + st.dist2, npix * 4, hipMemcpyDeviceToHost, c->stream));
-                if (arows) HIPCHK(c, hipMemcpyAsync(anchors, base + st.anchors, (size_t)arows * INFUR_ANCHOR_WORDS * 4, hipMemcpyDeviceToHost, c->stream));
                 if (kind) HIPCHK(c, hipMemcpyAsync(kind, base + st.kind, npix, hipMemcpyDeviceToHost, c->stream));
                 if (st.srows) HIPCHK(c, hipMemcpyAsync(skel_table, base + st.stable, st.srows * INFUR_SKELETON_WORDS * 4, hipMemcpyDeviceToHost, c->stream));
                 if (skel_counts) HIPCHK(c, hipMemcpyAsync(skel_counts, base + st.scounts, INFUR_SKELETON_COUNT_WORDS * 4, hipMemcpyDeviceToHost, c->stream));
-                uint32_t n = 0;
-                HIPCHK(c, hipMemcpyAsync(&n, base + st.n, 4, hipMemcpyDeviceToHost, c->stream));
-                if (labels) HIPCHK(c, hipMemcpyAsync(labels, base + st.rlabels, npix * 4, hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                const size_t rows = n < st.rrows ? n : st.rrows;
-                if (table && rows) HIPCHK(c, hipMemcpy(table, base + st.rtable, rows * INFUR_REGION_WORDS * 8, hipMemcpyDeviceToHost));
-                if (n_regions) *n_regions = n;
+                RETIF(reg_read_back(c, base, st.r, npix, o));
                 if (!cl) return INFUR_OK;
                 return centrelines_read_back(c, base, st.cl, records, vertices, cl_counts);
             });

@@ -1,9 +1,10 @@
 // infur_expand.cpp -- Expand, the stage that gives a value to the pixels that have none (include/infur_hip.h): every open pixel of a
 // byte or u32 plane takes the value of its exact nearest seed, within a reach, with the squared distance, the seed's index, a row per
-// value and eight counts.  Kernels: expand.hip.  Everything is enqueued on the context's stream; the frame wrapper is the egress
-// stages' (infur_rt.h), and so is the rule that its buffers are private scratch: growing them leaves mem_gen -- and with it the
+// value and eight counts.  Kernels: expand.hip.  Everything is enqueued on the context's stream; the frame calls' staging of Regions'
+// products, their capacity checks and read-back are the ones the stages behind Regions share (infur_region_frames.h), and so is
+// the rule that its buffers are private scratch: growing them leaves mem_gen -- and with it the
 // graphs infur_frame_advance_dev has cached -- alone.
-#include "infur_egress.h"
+#include "infur_region_frames.h"
 
 using namespace infur;
 
@@ -44,18 +45,13 @@ struct ExpStage {
     }
 };
 
-// st_exp_io of infur_frame_expand: [count][counts][table, at most one row per pixel][label plane][class plane][confidence plane]
-// [grown][dist2][source][expand table], on 256-byte boundaries
+// st_exp_io of infur_frame_expand: [counts], Regions' products, then [grown][dist2][source][expand table], on 256-byte boundaries
 struct ExpFrameStage {
-    size_t rows, counts, table, labels, klass, conf, grown, dist2, source, etable, bytes;
-    ExpFrameStage(size_t npix, uint32_t table_rows, uint32_t expand_rows) {
-        rows = table_rows < npix ? table_rows : npix;
-        counts = 256;
-        table = 512;
-        labels = table + align_up(rows * INFUR_REGION_WORDS * 8, 256);
-        klass = labels + align_up(npix * 4, 256);
-        conf = klass + align_up(npix, 256);
-        grown = conf + align_up(npix, 256);
+    size_t counts;
+    RegLayout r;
+    size_t grown, dist2, source, etable, bytes;
+    ExpFrameStage(size_t npix, uint32_t table_rows, uint32_t expand_rows) : counts(0), r(256, npix, table_rows) {
+        grown = r.end;
         dist2 = grown + align_up(npix * 4, 256);
         source = dist2 + align_up(npix * 4, 256);
         etable = source + align_up(npix * 4, 256);
@@ -125,15 +121,11 @@ int32_t infur_frame_expand_dev(infur_ctx* c, const void* d_bgr, uint32_t w, uint
         size_t lb_cap = labels_cap;
         if (c->loaded && npix) {
             if (!d_labels && !d_table && !d_n && !exp) return INFUR_E_INVALID_ARG;
-            if (d_labels && labels_cap < npix * 4) return fail(c, INFUR_E_CAPACITY, "the label plane needs %zu bytes, buffer has %zu", npix * 4, labels_cap);
-            if (d_grown && grown_cap < npix * 4) return fail(c, INFUR_E_CAPACITY, "the grown plane needs %zu bytes, buffer has %zu", npix * 4, grown_cap);
-            if (d_dist2 && dist2_cap < npix * 4) return fail(c, INFUR_E_CAPACITY, "the distance plane needs %zu bytes, buffer has %zu", npix * 4, dist2_cap);
-            if (d_source && source_cap < npix * 4) return fail(c, INFUR_E_CAPACITY, "the source plane needs %zu bytes, buffer has %zu", npix * 4, source_cap);
-            if (!lb && exp) {  // the label plane Expand reads, when the caller does not want it
-                RETIF(ensure_private(c, c->st_exp_plane, npix * 4));
-                lb = c->st_exp_plane.p;
-                lb_cap = npix * 4;
-            }
+            RETIF(cap_check(c, "label", true, d_labels, labels_cap, npix * 4));
+            RETIF(cap_check(c, "grown", true, d_grown, grown_cap, npix * 4));
+            RETIF(cap_check(c, "distance", true, d_dist2, dist2_cap, npix * 4));
+            RETIF(cap_check(c, "source", true, d_source, source_cap, npix * 4));
+            if (exp) RETIF(borrow_planes(c, c->st_exp_plane, npix, &lb, &lb_cap));  // the label plane Expand reads
         }  // (otherwise the call below fails before it decodes: bad scale, empty frame or no model)
         // scale -> model -> Segments decode -> Regions, with that call's own checks, errors and MODEL_NOT_LOADED rule
         RETIF(infur_frame_regions_dev(c, d_bgr, w, h, factor, mode, decode, connectivity, min_pixels, flags, d_klass, d_conf, plane_cap, lb, lb_cap,
@@ -151,6 +143,7 @@ int32_t infur_frame_expand(infur_ctx* c, const uint8_t* bgr, uint32_t w, uint32_
     return abi_call(c, [&]() -> int32_t {
         if (!c || !ow || !oh) return INFUR_E_INVALID_ARG;
         RETIF(reg_check(c, connectivity, flags));
+        const RegHostOut o{klass, conf, plane_cap, labels, labels_cap, table, table_rows, n_regions};  // (dist2 here is Expand's own)
         ExpFrameStage st(0, 0, 0);
         uint8_t* base = nullptr;
         const uint32_t erows = etable ? expand_rows : 0;
@@ -158,44 +151,30 @@ int32_t infur_frame_expand(infur_ctx* c, const uint8_t* bgr, uint32_t w, uint32_
         return frame_host(
             c, bgr, w, h, factor, scaled, ow, oh,
             [&](size_t npix) -> int32_t {
-                if ((klass || conf) && plane_cap < npix) return fail(c, INFUR_E_CAPACITY, "a plane needs %zu bytes, buffer has %zu", npix, plane_cap);
-                if (labels && labels_cap < npix * 4) return fail(c, INFUR_E_CAPACITY, "the label plane needs %zu bytes, buffer has %zu", npix * 4, labels_cap);
-                if (c->loaded && grown && grown_cap < npix * 4)
-                    return fail(c, INFUR_E_CAPACITY, "the grown plane needs %zu bytes, buffer has %zu", npix * 4, grown_cap);
-                if (c->loaded && dist2 && dist2_cap < npix * 4)
-                    return fail(c, INFUR_E_CAPACITY, "the distance plane needs %zu bytes, buffer has %zu", npix * 4, dist2_cap);
-                if (c->loaded && source && source_cap < npix * 4)
-                    return fail(c, INFUR_E_CAPACITY, "the source plane needs %zu bytes, buffer has %zu", npix * 4, source_cap);
-                st = ExpFrameStage(npix, table ? table_rows : 0, erows);
+                RETIF(reg_caps_check(c, o, npix));
+                RETIF(cap_check(c, "grown", c->loaded, grown, grown_cap, npix * 4));
+                RETIF(cap_check(c, "distance", c->loaded, dist2, dist2_cap, npix * 4));
+                RETIF(cap_check(c, "source", c->loaded, source, source_cap, npix * 4));
+                st = ExpFrameStage(npix, o.staged_rows(), erows);
                 RETIF(ensure_private(c, c->st_exp_io, st.bytes));
                 base = (uint8_t*)c->st_exp_io.p;
                 return INFUR_OK;
             },
             [&](void* d_bgr, void* d_scaled) {
                 const size_t npix = (size_t)*ow * *oh;
-                return infur_frame_expand_dev(c, d_bgr, w, h, factor, mode, decode, connectivity, min_pixels, flags, base + st.klass,
-                                              (conf || table) ? base + st.conf : nullptr, npix, (labels || exp) ? base + st.labels : nullptr, npix * 4,
-                                              (table && st.rows) ? base + st.table : nullptr, (uint32_t)st.rows,
-                                              (labels || table || n_regions) ? base : nullptr, d_scaled, ow, oh, reach, grown ? base + st.grown : nullptr,
+                const RegDevArgs a = reg_dev_args(o, base, st.r, npix, exp);
+                return infur_frame_expand_dev(c, d_bgr, w, h, factor, mode, decode, connectivity, min_pixels, flags, a.klass, a.conf, a.plane_cap, a.labels,
+                                              a.labels_cap, a.table, a.table_rows, a.n, d_scaled, ow, oh, reach, grown ? base + st.grown : nullptr,
                                               npix * 4, dist2 ? base + st.dist2 : nullptr, npix * 4, source ? base + st.source : nullptr, npix * 4,
                                               erows ? base + st.etable : nullptr, erows, ecounts ? base + st.counts : nullptr);
             },
             [&](size_t npix) -> int32_t {
-                if (klass) HIPCHK(c, hipMemcpyAsync(klass, base + st.klass, npix, hipMemcpyDeviceToHost, c->stream));
-                if (conf) HIPCHK(c, hipMemcpyAsync(conf, base + st.conf, npix, hipMemcpyDeviceToHost, c->stream));
                 if (grown) HIPCHK(c, hipMemcpyAsync(grown, base + st.grown, npix * 4, hipMemcpyDeviceToHost, c->stream));
                 if (dist2) HIPCHK(c, hipMemcpyAsync(dist2, base + st.dist2, npix * 4, hipMemcpyDeviceToHost, c->stream));
                 if (source) HIPCHK(c, hipMemcpyAsync(source, base + st.source, npix * 4, hipMemcpyDeviceToHost, c->stream));
                 if (erows) HIPCHK(c, hipMemcpyAsync(etable, base + st.etable, (size_t)erows * INFUR_EXPAND_WORDS * 4, hipMemcpyDeviceToHost, c->stream));
                 if (ecounts) HIPCHK(c, hipMemcpyAsync(ecounts, base + st.counts, INFUR_EXPAND_COUNT_WORDS * 4, hipMemcpyDeviceToHost, c->stream));
-                uint32_t n = 0;
-                HIPCHK(c, hipMemcpyAsync(&n, base, 4, hipMemcpyDeviceToHost, c->stream));
-                if (labels) HIPCHK(c, hipMemcpyAsync(labels, base + st.labels, npix * 4, hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                const size_t rows = n < st.rows ? n : st.rows;
-                if (table && rows) HIPCHK(c, hipMemcpy(table, base + st.table, rows * INFUR_REGION_WORDS * 8, hipMemcpyDeviceToHost));
-                if (n_regions) *n_regions = n;
-                return INFUR_OK;
+                return reg_read_back(c, base, st.r, npix, o);
             });
     });
 }

@@ -3,45 +3,11 @@
 // classes.  Kernels: regions.hip.  Everything is enqueued on the context's stream.  Like infur_segments.cpp the frame path
 // here always enqueues eagerly, and every buffer of this file is private scratch no captured graph can point into: growing it
 // leaves mem_gen -- and with it the graphs infur_frame_advance_dev has cached -- alone.
-#include <cstring>
-#include <new>
-
-#include "infur_ctx.h"
-#include "infur_rt.h"
-#include "kernels.h"
+#include "infur_region_frames.h"
 
 using namespace infur;
 
-namespace {
-
 static_assert(kRegWords == INFUR_REGION_WORDS, "regions.hip and the header disagree about the row");
-
-// st_reg_io: [count][table, at most one row per pixel][label plane][class plane][confidence plane], on 256-byte boundaries
-struct RegStage {
-    size_t rows, table, labels, klass, conf, bytes;
-    RegStage(size_t npix, uint32_t table_rows) {
-        rows = table_rows < npix ? table_rows : npix;
-        table = 256;
-        labels = table + align_up(rows * INFUR_REGION_WORDS * 8, 256);
-        klass = labels + align_up(npix * 4, 256);
-        conf = klass + align_up(npix, 256);
-        bytes = conf + align_up(npix, 256);
-    }
-};
-
-// count and the written rows of the table to the host: the count decides how many rows there are to copy
-int32_t reg_read_back(infur_ctx* c, const uint8_t* base, const RegStage& st, size_t npix, uint32_t* labels, uint64_t* table, uint32_t* n_regions) {
-    uint32_t n = 0;
-    HIPCHK(c, hipMemcpyAsync(&n, base, 4, hipMemcpyDeviceToHost, c->stream));
-    if (labels) HIPCHK(c, hipMemcpyAsync(labels, base + st.labels, npix * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const size_t rows = n < st.rows ? n : st.rows;
-    if (table && rows) HIPCHK(c, hipMemcpy(table, base + st.table, rows * INFUR_REGION_WORDS * 8, hipMemcpyDeviceToHost));
-    if (n_regions) *n_regions = n;
-    return INFUR_OK;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -80,14 +46,15 @@ int32_t infur_regions(infur_ctx* c, const uint8_t* klass, const uint8_t* conf, u
             return INFUR_OK;
         }
         if (!klass) return INFUR_E_INVALID_ARG;
-        const RegStage st(hw, table ? table_rows : 0);
-        RETIF(ensure_private(c, c->st_reg_io, st.bytes));
+        const RegHostOut o{nullptr, nullptr, 0, labels, 0, table, table_rows, n_regions};  // (the planes are inputs here)
+        const RegLayout st(0, hw, o.staged_rows());
+        RETIF(ensure_private(c, c->st_reg_io, st.end));
         uint8_t* base = (uint8_t*)c->st_reg_io.p;
         HIPCHK(c, hipMemcpyAsync(base + st.klass, klass, hw, hipMemcpyHostToDevice, c->stream));
         if (conf) HIPCHK(c, hipMemcpyAsync(base + st.conf, conf, hw, hipMemcpyHostToDevice, c->stream));
         RETIF(infur_regions_dev(c, base + st.klass, conf ? base + st.conf : nullptr, h, w, connectivity, min_pixels, flags,
                                 labels ? base + st.labels : nullptr, (table && st.rows) ? base + st.table : nullptr, (uint32_t)st.rows, base));
-        return reg_read_back(c, base, st, hw, labels, table, n_regions);
+        return reg_read_back(c, base, st, hw, o);
     });
 }
 
@@ -103,7 +70,7 @@ int32_t infur_frame_regions_dev(infur_ctx* c, const void* d_bgr, uint32_t w, uin
         void* cf = d_conf;
         if (c->loaded && npix) {
             if (!d_labels && !d_table && !d_n) return INFUR_E_INVALID_ARG;
-            if (d_labels && labels_cap < npix * 4) return fail(c, INFUR_E_CAPACITY, "the label plane needs %zu bytes, buffer has %zu", npix * 4, labels_cap);
+            RETIF(cap_check(c, "label", true, d_labels, labels_cap, npix * 4));
             // the planes the caller does not want are decoded into scratch: the class plane always, the confidences for a table
             if (!kl || (!cf && d_table)) {
                 RETIF(ensure_private(c, c->st_reg_planes, 2 * align_up(npix, 256)));
@@ -125,30 +92,24 @@ int32_t infur_frame_regions(infur_ctx* c, const uint8_t* bgr, uint32_t w, uint32
     return abi_call(c, [&]() -> int32_t {
         if (!c || !ow || !oh) return INFUR_E_INVALID_ARG;
         RETIF(reg_check(c, connectivity, flags));
-        RegStage st(0, 0);
+        const RegHostOut o{klass, conf, plane_cap, labels, labels_cap, table, table_rows, n_regions};
+        RegLayout st(0, 0, 0);
         uint8_t* base = nullptr;
         return frame_host(
             c, bgr, w, h, factor, scaled, ow, oh,
             [&](size_t npix) -> int32_t {
-                if ((klass || conf) && plane_cap < npix) return fail(c, INFUR_E_CAPACITY, "a plane needs %zu bytes, buffer has %zu", npix, plane_cap);
-                if (labels && labels_cap < npix * 4) return fail(c, INFUR_E_CAPACITY, "the label plane needs %zu bytes, buffer has %zu", npix * 4, labels_cap);
-                st = RegStage(npix, table ? table_rows : 0);
-                RETIF(ensure_private(c, c->st_reg_io, st.bytes));
+                RETIF(reg_caps_check(c, o, npix));
+                st = RegLayout(0, npix, o.staged_rows());
+                RETIF(ensure_private(c, c->st_reg_io, st.end));
                 base = (uint8_t*)c->st_reg_io.p;
                 return INFUR_OK;
             },
             [&](void* d_bgr, void* d_scaled) {
-                const size_t npix = (size_t)*ow * *oh;
-                return infur_frame_regions_dev(c, d_bgr, w, h, factor, mode, decode, connectivity, min_pixels, flags, base + st.klass,
-                                               (conf || table) ? base + st.conf : nullptr, npix, labels ? base + st.labels : nullptr, npix * 4,
-                                               (table && st.rows) ? base + st.table : nullptr, (uint32_t)st.rows,
-                                               (labels || table || n_regions) ? base : nullptr, d_scaled, ow, oh);
+                const RegDevArgs a = reg_dev_args(o, base, st, (size_t)*ow * *oh, false);
+                return infur_frame_regions_dev(c, d_bgr, w, h, factor, mode, decode, connectivity, min_pixels, flags, a.klass, a.conf, a.plane_cap,
+                                               a.labels, a.labels_cap, a.table, a.table_rows, a.n, d_scaled, ow, oh);
             },
-            [&](size_t npix) -> int32_t {
-                if (klass) HIPCHK(c, hipMemcpyAsync(klass, base + st.klass, npix, hipMemcpyDeviceToHost, c->stream));
-                if (conf) HIPCHK(c, hipMemcpyAsync(conf, base + st.conf, npix, hipMemcpyDeviceToHost, c->stream));
-                return reg_read_back(c, base, st, npix, labels, table, n_regions);
-            });
+            [&](size_t npix) { return reg_read_back(c, base, st, npix, o); });
     });
 }
 

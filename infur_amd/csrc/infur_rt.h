@@ -24,6 +24,9 @@
 //  polygon stage, the host-pointer frame wrapper and the front halves of the _dev frame calls)
 // (egress_layout.h, HIP-free and included here: align_up, which moved there, the polygon stages' staging layout PolyStage, what
 //  Outlines leaves behind it PolyScratch, edge_capacity, kMaxSide, the statistics-class clamp and the row rules of the copies)
+// (infur_region_frames.h, beside infur_egress.h: what the frame calls of the nine stages behind Regions share -- the capacity checks
+//  with their messages, the caller's arrays for Regions' and Anchors' products with the device arguments and the read-back made of
+//  them, the planes a _dev form borrows; region_layout.h, HIP-free like egress_layout.h: where those products are staged)
 // (conv_forms.h, the table of conv modes, configurations and forms, comes with kernels.h)
 // (wave_scan.h, the device code regions.hip, tracks.hip and runs.hip share, also holds kScanBlock, which sizes their block sums)
 // Everything here lives in namespace infur and is NOT part of the public ABI.

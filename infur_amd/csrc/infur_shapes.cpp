@@ -1,9 +1,10 @@
 // infur_shapes.cpp -- Shapes, the descriptor stage behind Outlines (include/infur_hip.h): per loop its area, perimeter, moments,
 // convex hull and minimum rectangle, per value the sums, so that a host learns what shape an object has without pulling its
 // polygon across PCIe.  Kernels: shapes.hip.  Everything is enqueued on the context's stream; the checks and row rules are the
-// egress stages' (infur_egress.h), and so is the rule that its buffers are private scratch: growing them leaves mem_gen -- and
+// egress stages' (infur_egress.h), the frame calls' staging of Regions' products, their capacity checks and read-back the ones the
+// stages behind Regions share (infur_region_frames.h), and so is the rule that its buffers are private scratch: growing them leaves mem_gen -- and
 // with it the graphs infur_frame_advance_dev has cached -- alone.
-#include "infur_egress.h"
+#include "infur_region_frames.h"
 
 using namespace infur;
 
@@ -151,13 +152,9 @@ int32_t infur_frame_shapes_dev(infur_ctx* c, const void* d_bgr, uint32_t w, uint
         PolyScratch at(1);
         if (c->loaded && npix) {
             if (!d_labels && !d_table && !d_n && !shp) return INFUR_E_INVALID_ARG;
-            if (d_labels && labels_cap < npix * 4) return fail(c, INFUR_E_CAPACITY, "the label plane needs %zu bytes, buffer has %zu", npix * 4, labels_cap);
-            if (!lb && shp) {  // the label plane Outlines reads, when the caller does not want it
-                RETIF(ensure_private(c, c->st_shapes_plane, npix * 4));
-                lb = c->st_shapes_plane.p;
-                lb_cap = npix * 4;
-            }
+            RETIF(cap_check(c, "label", true, d_labels, labels_cap, npix * 4));
             if (shp) {
+                RETIF(borrow_planes(c, c->st_shapes_plane, npix, &lb, &lb_cap));  // the label plane Outlines reads
                 at = PolyScratch(edge_capacity(npix, max_edges));
                 RETIF(ensure_private(c, c->st_shapes_poly, at.bytes));
             }
@@ -184,46 +181,30 @@ int32_t infur_frame_shapes(infur_ctx* c, const uint8_t* bgr, uint32_t w, uint32_
         RETIF(reg_check(c, connectivity, flags));
         const ShapesOut o = {loops_out, loops_rows_out, vertices_out, vertex_rows_out, shapes, shape_rows, values, table_rows, counts_out};
         const bool shp = o.any();  // whether there is anything to do behind Regions
-        // st_shapes_io: [n][table, at most one row per pixel][label plane][class plane][confidence plane], then the outputs
-        size_t rows = 0, at_table = 256, at_labels = 0, at_klass = 0, at_conf = 0;
+        const RegHostOut ro{klass, conf, plane_cap, labels, labels_cap, table, table_rows, n_regions};
+        RegLayout r(0, 0, 0);  // st_shapes_io: Regions' products, then the outputs
         OutStage st(0, ShapesOut{}, 0, 0);
         uint8_t* base = nullptr;
         return frame_host(
             c, bgr, w, h, factor, scaled, ow, oh,
             [&](size_t npix) -> int32_t {
-                if ((klass || conf) && plane_cap < npix) return fail(c, INFUR_E_CAPACITY, "a plane needs %zu bytes, buffer has %zu", npix, plane_cap);
-                if (labels && labels_cap < npix * 4) return fail(c, INFUR_E_CAPACITY, "the label plane needs %zu bytes, buffer has %zu", npix * 4, labels_cap);
-                rows = table ? min_rows(table_rows, npix) : 0;
-                at_labels = at_table + align_up(rows * INFUR_REGION_WORDS * 8, 256);
-                at_klass = at_labels + align_up(npix * 4, 256);
-                at_conf = at_klass + align_up(npix, 256);
-                st = OutStage(at_conf + align_up(npix, 256), o, frame_max_loops(npix), frame_max_vertices(npix));
+                RETIF(reg_caps_check(c, ro, npix));
+                r = RegLayout(0, npix, ro.staged_rows());
+                st = OutStage(r.end, o, frame_max_loops(npix), frame_max_vertices(npix));
                 RETIF(ensure_private(c, c->st_shapes_io, st.bytes));
                 base = (uint8_t*)c->st_shapes_io.p;
                 return INFUR_OK;
             },
             [&](void* d_bgr, void* d_scaled) {
-                const size_t npix = (size_t)*ow * *oh;
                 const ShapesOut d = st.dev(base, shp);
-                // (table_rows reaches the device call as given when the per-value table is wanted: its rows are all written)
-                return infur_frame_shapes_dev(c, d_bgr, w, h, factor, mode, decode, connectivity, min_pixels, flags, base + at_klass,
-                                              (conf || table) ? base + at_conf : nullptr, npix, (labels || shp) ? base + at_labels : nullptr, npix * 4,
-                                              (table && rows) ? base + at_table : nullptr, values ? table_rows : (uint32_t)rows,
-                                              (labels || table || n_regions) ? base : nullptr, d_scaled, ow, oh, max_edges, d.loops, d.loops_rows,
-                                              d.vertices, d.vertex_rows, d.shapes, d.shape_rows, d.values, d.counts);
+                const RegDevArgs a = reg_dev_args(ro, base, r, (size_t)*ow * *oh, shp, values != nullptr);
+                return infur_frame_shapes_dev(c, d_bgr, w, h, factor, mode, decode, connectivity, min_pixels, flags, a.klass, a.conf, a.plane_cap, a.labels,
+                                              a.labels_cap, a.table, a.table_rows, a.n, d_scaled, ow, oh, max_edges, d.loops, d.loops_rows, d.vertices,
+                                              d.vertex_rows, d.shapes, d.shape_rows, d.values, d.counts);
             },
             [&](size_t npix) -> int32_t {
-                if (klass) HIPCHK(c, hipMemcpyAsync(klass, base + at_klass, npix, hipMemcpyDeviceToHost, c->stream));
-                if (conf) HIPCHK(c, hipMemcpyAsync(conf, base + at_conf, npix, hipMemcpyDeviceToHost, c->stream));
-                uint32_t n = 0;
-                HIPCHK(c, hipMemcpyAsync(&n, base, 4, hipMemcpyDeviceToHost, c->stream));
-                if (labels) HIPCHK(c, hipMemcpyAsync(labels, base + at_labels, npix * 4, hipMemcpyDeviceToHost, c->stream));
                 if (shp) RETIF(shapes_read_back(c, base, st, o));  // (synchronises)
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                const size_t nr = n < rows ? n : rows;
-                if (table && nr) HIPCHK(c, hipMemcpy(table, base + at_table, nr * INFUR_REGION_WORDS * 8, hipMemcpyDeviceToHost));
-                if (n_regions) *n_regions = n;
-                return INFUR_OK;
+                return reg_read_back(c, base, r, npix, ro);
             });
     });
 }

@@ -1,9 +1,10 @@
 // infur_sieve.cpp -- Adjacency and Sieve (include/infur_hip.h): the region adjacency graph of a class, label or track plane, and the
 // stage that merges every region below a size threshold into the neighbour it shares the longest border with, so that the stages
-// behind it see a class plane without speckle.  Kernels: sieve.hip.  Everything is enqueued on the context's stream; the frame
-// wrapper is the egress stages' (infur_rt.h), and so is the rule that the buffers of this file are private scratch: growing them
+// behind it see a class plane without speckle.  Kernels: sieve.hip.  Everything is enqueued on the context's stream; the host-pointer
+// frame call's staging of Regions' products, the capacity checks and the read-back are the ones the stages behind Regions share
+// (infur_region_frames.h), and so is the rule that the buffers of this file are private scratch: growing them
 // leaves mem_gen -- and with it the graphs infur_frame_advance_dev has cached -- alone.
-#include "infur_egress.h"
+#include "infur_region_frames.h"
 
 using namespace infur;
 
@@ -187,8 +188,8 @@ int32_t infur_frame_sieve_dev(infur_ctx* c, const void* d_bgr, uint32_t w, uint3
         uint8_t* base = nullptr;
         if (c->loaded && npix) {
             if (!again && !d_klass_out && !d_counts) return INFUR_E_INVALID_ARG;
-            if (d_labels && labels_cap < npix * 4) return fail(c, INFUR_E_CAPACITY, "the label plane needs %zu bytes, buffer has %zu", npix * 4, labels_cap);
-            if (d_klass_out && plane_cap < npix) return fail(c, INFUR_E_CAPACITY, "a plane needs %zu bytes, buffer has %zu", npix, plane_cap);
+            RETIF(cap_check(c, "label", true, d_labels, labels_cap, npix * 4));
+            RETIF(byte_planes_check(c, d_klass_out != nullptr, plane_cap, npix));
             RETIF(ensure_private(c, c->st_sieve_frame, o_table + align_up(rows1 * INFUR_REGION_WORDS * 8, 256)));
             base = (uint8_t*)c->st_sieve_frame.p;
             if (!kl) kl = base + o_klass;
@@ -214,45 +215,31 @@ int32_t infur_frame_sieve(infur_ctx* c, const uint8_t* bgr, uint32_t w, uint32_t
     return abi_call(c, [&]() -> int32_t {
         if (!c || !ow || !oh) return INFUR_E_INVALID_ARG;
         RETIF(reg_check(c, connectivity, flags));
-        // st_sieve_io: [n_regions, counts][table][label plane][class plane][confidence plane][cleaned plane]
-        size_t rows = 0, o_table = 256, o_labels = 0, o_klass = 0, o_conf = 0, o_out = 0;
+        const RegHostOut o{klass, conf, plane_cap, labels, labels_cap, table, table_rows, n_regions};
+        RegLayout r(0, 0, 0);  // st_sieve_io: Regions' products with the counts at 128, then [cleaned plane]
         uint8_t* base = nullptr;
-        const bool again = labels || table || n_regions;
         return frame_host(
             c, bgr, w, h, factor, scaled, ow, oh,
             [&](size_t npix) -> int32_t {
-                if ((klass || conf || klass_out) && plane_cap < npix) return fail(c, INFUR_E_CAPACITY, "a plane needs %zu bytes, buffer has %zu", npix, plane_cap);
-                if (labels && labels_cap < npix * 4) return fail(c, INFUR_E_CAPACITY, "the label plane needs %zu bytes, buffer has %zu", npix * 4, labels_cap);
-                rows = table ? (table_rows < npix ? table_rows : npix) : 0;
-                o_labels = o_table + align_up(rows * INFUR_REGION_WORDS * 8, 256);
-                o_klass = o_labels + align_up(npix * 4, 256);
-                o_conf = o_klass + align_up(npix, 256);
-                o_out = o_conf + align_up(npix, 256);
-                RETIF(ensure_private(c, c->st_sieve_io, o_out + align_up(npix, 256)));
+                RETIF(reg_caps_check(c, o, npix, klass_out != nullptr));
+                r = RegLayout(0, npix, o.staged_rows());
+                RETIF(ensure_private(c, c->st_sieve_io, r.end + align_up(npix, kSlotAlign)));
                 base = (uint8_t*)c->st_sieve_io.p;
                 return INFUR_OK;
             },
             [&](void* d_bgr, void* d_scaled) {
-                const size_t npix = (size_t)*ow * *oh;
-                return infur_frame_sieve_dev(c, d_bgr, w, h, factor, mode, decode, connectivity, min_pixels, flags, klass ? base + o_klass : nullptr,
-                                             conf ? base + o_conf : nullptr, npix, labels ? base + o_labels : nullptr, npix * 4,
-                                             (table && rows) ? base + o_table : nullptr, (uint32_t)rows, again ? base : nullptr, d_scaled, ow, oh,
-                                             max_rounds, pair_slots, klass_out ? base + o_out : nullptr, counts ? base + 128 : nullptr);
+                RegDevArgs a = reg_dev_args(o, base, r, (size_t)*ow * *oh, false);
+                // (Sieve decodes the planes the caller does not want into its own scratch: null here, not staged)
+                if (!klass) a.klass = nullptr;
+                if (!conf) a.conf = nullptr;
+                return infur_frame_sieve_dev(c, d_bgr, w, h, factor, mode, decode, connectivity, min_pixels, flags, a.klass, a.conf, a.plane_cap, a.labels,
+                                             a.labels_cap, a.table, a.table_rows, a.n, d_scaled, ow, oh, max_rounds, pair_slots,
+                                             klass_out ? base + r.end : nullptr, counts ? base + 128 : nullptr);
             },
             [&](size_t npix) -> int32_t {
-                if (klass) HIPCHK(c, hipMemcpyAsync(klass, base + o_klass, npix, hipMemcpyDeviceToHost, c->stream));
-                if (conf) HIPCHK(c, hipMemcpyAsync(conf, base + o_conf, npix, hipMemcpyDeviceToHost, c->stream));
-                if (klass_out) HIPCHK(c, hipMemcpyAsync(klass_out, base + o_out, npix, hipMemcpyDeviceToHost, c->stream));
+                if (klass_out) HIPCHK(c, hipMemcpyAsync(klass_out, base + r.end, npix, hipMemcpyDeviceToHost, c->stream));
                 if (counts) HIPCHK(c, hipMemcpyAsync(counts, base + 128, INFUR_SIEVE_COUNT_WORDS * 4, hipMemcpyDeviceToHost, c->stream));
-                if (!again) return INFUR_OK;
-                uint32_t n = 0;
-                HIPCHK(c, hipMemcpyAsync(&n, base, 4, hipMemcpyDeviceToHost, c->stream));
-                if (labels) HIPCHK(c, hipMemcpyAsync(labels, base + o_labels, npix * 4, hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                const size_t got = n < rows ? n : rows;
-                if (table && got) HIPCHK(c, hipMemcpy(table, base + o_table, got * INFUR_REGION_WORDS * 8, hipMemcpyDeviceToHost));
-                if (n_regions) *n_regions = n;
-                return INFUR_OK;
+                return reg_read_back(c, base, r, npix, o);  // (Regions of the cleaned plane, where anything of it is wanted)
             });
     });
 }

@@ -1,9 +1,10 @@
 // infur_skeleton.cpp -- Skeleton, the stage behind Regions and Anchors that thins every value of a plane to one-pixel centrelines
 // (include/infur_hip.h): Guo and Hall's two-sub-iteration rule on device bitmaps, then kind_out, a row per value and eight counts.
-// Kernels: skeleton.hip.  Everything is enqueued on the context's stream; the element checks and the frame wrapper are the egress
-// stages' (infur_egress.h, infur_rt.h), and so is the rule that its buffers are private scratch: growing them leaves mem_gen -- and
+// Kernels: skeleton.hip.  Everything is enqueued on the context's stream; the element checks are the egress stages' (infur_egress.h),
+// the frame calls' staging of Regions' and Anchors' products, their capacity checks and read-back the ones the stages behind Regions
+// share (infur_region_frames.h), and so is the rule that its buffers are private scratch: growing them leaves mem_gen -- and
 // with it the graphs infur_frame_advance_dev has cached -- alone.
-#include "infur_egress.h"
+#include "infur_region_frames.h"
 
 using namespace infur;
 
@@ -48,22 +49,13 @@ int32_t skeleton_read_back(infur_ctx* c, const uint8_t* base, const SkeletonStag
     return INFUR_OK;
 }
 
-// st_skel_io of infur_frame_skeleton: Skeleton's own staging as above (no input planes), then Regions' and Anchors' products:
-// [n_regions][region table][label plane][class plane][confidence plane][dist2][anchors]
+// st_skel_io of infur_frame_skeleton: Skeleton's own staging as above, then Regions' and Anchors' products from its height slot on
+// (no height or plane travels: the slots behind kind are free)
 struct SkeletonFrameStage {
     SkeletonStage sk;
-    size_t rrows, n, rtable, rlabels, klass, conf, dist2, anchors, bytes;
-    SkeletonFrameStage(size_t npix, uint32_t table_rows, uint32_t anchor_rows, size_t skel_rows, bool want_kind) : sk(npix, skel_rows, want_kind, false, 0) {
-        rrows = table_rows < npix ? table_rows : npix;
-        n = sk.height;  // (no height or plane travels: the slots behind kind are free)
-        rtable = n + 256;
-        rlabels = rtable + align_up(rrows * INFUR_REGION_WORDS * 8, 256);
-        klass = rlabels + align_up(npix * 4, 256);
-        conf = klass + align_up(npix, 256);
-        dist2 = conf + align_up(npix, 256);
-        anchors = dist2 + align_up(npix * 4, 256);
-        bytes = anchors + align_up((size_t)anchor_rows * INFUR_ANCHOR_WORDS * 4, 256);
-    }
+    RegAnchLayout r;
+    SkeletonFrameStage(size_t npix, const RegHostOut& o, size_t skel_rows, bool want_kind)
+        : sk(npix, skel_rows, want_kind, false, 0), r(sk.height, npix, o.staged_rows(), o.anchor_rows()) {}
 };
 
 }  // namespace
@@ -121,15 +113,10 @@ int32_t infur_frame_skeleton_dev(infur_ctx* c, const void* d_bgr, uint32_t w, ui
         if (c->loaded && npix) {
             uint32_t rounds = 0;
             if (skel) RETIF(skeleton_check(c, 4, 1, 1, INFUR_SKELETON_SKIP, INFUR_REGION_NONE, max_rounds, d_kind, d_skel_table, skel_rows, d_skel_counts, &rounds));
-            if (d_kind && kind_cap < npix) return fail(c, INFUR_E_CAPACITY, "the kind plane needs %zu bytes, buffer has %zu", npix, kind_cap);
-            if (d_labels && labels_cap < npix * 4) return fail(c, INFUR_E_CAPACITY, "the label plane needs %zu bytes, buffer has %zu", npix * 4, labels_cap);
-            if (d_dist2 && dist2_cap < npix * 4) return fail(c, INFUR_E_CAPACITY, "the distance plane needs %zu bytes, buffer has %zu", npix * 4, dist2_cap);
-            if (skel && (!lb || !d2)) {  // the planes Skeleton reads, when the caller does not want them: [labels][dist2]
-                const size_t one = align_up(npix * 4, 256);
-                RETIF(ensure_private(c, c->st_skel_plane, 2 * one));
-                if (!lb) lb = c->st_skel_plane.p, lb_cap = npix * 4;
-                if (!d2) d2 = (uint8_t*)c->st_skel_plane.p + one, d2_cap = npix * 4;
-            }
+            RETIF(cap_check(c, "kind", true, d_kind, kind_cap, npix));
+            RETIF(cap_check(c, "label", true, d_labels, labels_cap, npix * 4));
+            RETIF(cap_check(c, "distance", true, d_dist2, dist2_cap, npix * 4));
+            if (skel) RETIF(borrow_planes(c, c->st_skel_plane, npix, &lb, &lb_cap, &d2, &d2_cap));  // the planes Skeleton reads
         }  // (otherwise the call below fails before it decodes: bad scale, empty frame or no model)
         // scale -> model -> Segments decode -> Regions -> Anchors, with that call's own checks, errors and MODEL_NOT_LOADED rule
         RETIF(infur_frame_anchors_dev(c, d_bgr, w, h, factor, mode, decode, connectivity, min_pixels, flags, d_klass, d_conf, plane_cap, lb, lb_cap, d_table,
@@ -147,45 +134,30 @@ int32_t infur_frame_skeleton(infur_ctx* c, const uint8_t* bgr, uint32_t w, uint3
     return abi_call(c, [&]() -> int32_t {
         if (!c || !ow || !oh) return INFUR_E_INVALID_ARG;
         RETIF(reg_check(c, connectivity, flags));
-        SkeletonFrameStage st(0, 0, 0, 0, false);
+        const RegHostOut o{klass, conf, plane_cap, labels, labels_cap, table, table_rows, n_regions, dist2, dist2_cap, anchors};
+        SkeletonFrameStage st(0, o, 0, false);
         uint8_t* base = nullptr;
-        const uint32_t arows = anchors ? table_rows : 0;
         const bool skel = kind || (skel_table && skel_rows) || skel_counts;
         return frame_host(
             c, bgr, w, h, factor, scaled, ow, oh,
             [&](size_t npix) -> int32_t {
-                if ((klass || conf) && plane_cap < npix) return fail(c, INFUR_E_CAPACITY, "a plane needs %zu bytes, buffer has %zu", npix, plane_cap);
-                if (labels && labels_cap < npix * 4) return fail(c, INFUR_E_CAPACITY, "the label plane needs %zu bytes, buffer has %zu", npix * 4, labels_cap);
-                if (c->loaded && dist2 && dist2_cap < npix * 4)
-                    return fail(c, INFUR_E_CAPACITY, "the distance plane needs %zu bytes, buffer has %zu", npix * 4, dist2_cap);
-                if (c->loaded && kind && kind_cap < npix) return fail(c, INFUR_E_CAPACITY, "the kind plane needs %zu bytes, buffer has %zu", npix, kind_cap);
-                st = SkeletonFrameStage(npix, table ? table_rows : 0, arows, skel_table ? skel_rows : 0, kind != nullptr);
-                RETIF(ensure_private(c, c->st_skel_io, st.bytes));
+                RETIF(reg_caps_check(c, o, npix));
+                RETIF(cap_check(c, "kind", c->loaded, kind, kind_cap, npix));
+                st = SkeletonFrameStage(npix, o, skel_table ? skel_rows : 0, kind != nullptr);
+                RETIF(ensure_private(c, c->st_skel_io, st.r.end));
                 base = (uint8_t*)c->st_skel_io.p;
                 return INFUR_OK;
             },
             [&](void* d_bgr, void* d_scaled) {
                 const size_t npix = (size_t)*ow * *oh;
-                return infur_frame_skeleton_dev(c, d_bgr, w, h, factor, mode, decode, connectivity, min_pixels, flags, base + st.klass,
-                                                (conf || table) ? base + st.conf : nullptr, npix, (labels || dist2 || arows || skel) ? base + st.rlabels : nullptr,
-                                                npix * 4, (table && st.rrows) ? base + st.rtable : nullptr, arows ? table_rows : (uint32_t)st.rrows,
-                                                (labels || table || n_regions) ? base + st.n : nullptr, d_scaled, ow, oh,
-                                                (dist2 || skel) ? base + st.dist2 : nullptr, npix * 4, arows ? base + st.anchors : nullptr, max_rounds,
-                                                kind ? base + st.sk.kind : nullptr, npix, st.sk.rows ? base + st.sk.table : nullptr, (uint32_t)st.sk.rows,
-                                                skel ? base : nullptr);
+                const RegDevArgs a = reg_dev_args(o, base, st.r, npix, skel);
+                return infur_frame_skeleton_dev(c, d_bgr, w, h, factor, mode, decode, connectivity, min_pixels, flags, a.klass, a.conf, a.plane_cap,
+                                                a.labels, a.labels_cap, a.table, a.table_rows, a.n, d_scaled, ow, oh, a.dist2, a.dist2_cap, a.anchors,
+                                                max_rounds, kind ? base + st.sk.kind : nullptr, npix, st.sk.rows ? base + st.sk.table : nullptr,
+                                                (uint32_t)st.sk.rows, skel ? base : nullptr);
             },
             [&](size_t npix) -> int32_t {
-                if (klass) HIPCHK(c, hipMemcpyAsync(klass, base + st.klass, npix, hipMemcpyDeviceToHost, c->stream));
-                if (conf) HIPCHK(c, hipMemcpyAsync(conf, base + st.conf, npix, hipMemcpyDeviceToHost, c->stream));
-                if (dist2) HIPCHK(c, hipMemcpyAsync(dist2, base + st.dist2, npix * 4, hipMemcpyDeviceToHost, c->stream));
-                if (arows) HIPCHK(c, hipMemcpyAsync(anchors, base + st.anchors, (size_t)arows * INFUR_ANCHOR_WORDS * 4, hipMemcpyDeviceToHost, c->stream));
-                uint32_t n = 0;
-                HIPCHK(c, hipMemcpyAsync(&n, base + st.n, 4, hipMemcpyDeviceToHost, c->stream));
-                if (labels) HIPCHK(c, hipMemcpyAsync(labels, base + st.rlabels, npix * 4, hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                const size_t rows = n < st.rrows ? n : st.rrows;
-                if (table && rows) HIPCHK(c, hipMemcpy(table, base + st.rtable, rows * INFUR_REGION_WORDS * 8, hipMemcpyDeviceToHost));
-                if (n_regions) *n_regions = n;
+                RETIF(reg_read_back(c, base, st.r, npix, o));
                 if (!skel) return INFUR_OK;
                 return skeleton_read_back(c, base, st.sk, npix, kind, skel_table, skel_counts);
             });

@@ -1,9 +1,10 @@
 // infur_split.cpp -- Split, the stage behind Regions and Anchors that separates touching objects of one value at their necks
 // (include/infur_hip.h): a marker watershed of a u32 height plane, typically Anchors' dist2, whose output is a label plane again.
-// Kernels: split.hip.  Everything is enqueued on the context's stream; the element checks and the frame wrapper are the egress
-// stages' (infur_egress.h, infur_rt.h), and so is the rule that its buffers are private scratch: growing them leaves mem_gen -- and
+// Kernels: split.hip.  Everything is enqueued on the context's stream; the element checks are the egress stages' (infur_egress.h),
+// the frame calls' staging of Regions' and Anchors' products, their capacity checks and read-back the ones the stages behind Regions
+// share (infur_region_frames.h), and so is the rule that its buffers are private scratch: growing them leaves mem_gen -- and
 // with it the graphs infur_frame_advance_dev has cached -- alone.
-#include "infur_egress.h"
+#include "infur_region_frames.h"
 
 using namespace infur;
 
@@ -54,22 +55,13 @@ int32_t split_read_back(infur_ctx* c, const uint8_t* base, const SplitStage& st,
     return INFUR_OK;
 }
 
-// st_split_io of infur_frame_split: Split's own staging as above (no input planes), then Regions' and Anchors' products:
-// [n_regions][region table][label plane][class plane][confidence plane][dist2][anchors]
+// st_split_io of infur_frame_split: Split's own staging as above, then Regions' and Anchors' products from its height slot on
+// (no height or plane travels: the slots behind Split's labels are free)
 struct SplitFrameStage {
     SplitStage sp;
-    size_t rrows, n, rtable, rlabels, klass, conf, dist2, anchors, bytes;
-    SplitFrameStage(size_t npix, uint32_t table_rows, uint32_t anchor_rows, size_t split_rows, bool want_labels) : sp(npix, split_rows, want_labels, 0) {
-        rrows = table_rows < npix ? table_rows : npix;
-        n = sp.height;  // (no height or plane travels: the slots behind Split's labels are free)
-        rtable = n + 256;
-        rlabels = rtable + align_up(rrows * INFUR_REGION_WORDS * 8, 256);
-        klass = rlabels + align_up(npix * 4, 256);
-        conf = klass + align_up(npix, 256);
-        dist2 = conf + align_up(npix, 256);
-        anchors = dist2 + align_up(npix * 4, 256);
-        bytes = anchors + align_up((size_t)anchor_rows * INFUR_ANCHOR_WORDS * 4, 256);
-    }
+    RegAnchLayout r;
+    SplitFrameStage(size_t npix, const RegHostOut& o, size_t split_rows, bool want_labels)
+        : sp(npix, split_rows, want_labels, 0), r(sp.height, npix, o.staged_rows(), o.anchor_rows()) {}
 };
 
 }  // namespace
@@ -135,16 +127,10 @@ int32_t infur_frame_split_dev(infur_ctx* c, const void* d_bgr, uint32_t w, uint3
             if (split)
                 RETIF(split_check(c, 4, 1, 1, INFUR_SPLIT_SKIP, INFUR_REGION_NONE, pair_slots, d_split_labels, d_split_table, split_rows, d_split_counts,
                                   &slots));
-            if (d_split_labels && split_labels_cap < npix * 4)
-                return fail(c, INFUR_E_CAPACITY, "the segment plane needs %zu bytes, buffer has %zu", npix * 4, split_labels_cap);
-            if (d_labels && labels_cap < npix * 4) return fail(c, INFUR_E_CAPACITY, "the label plane needs %zu bytes, buffer has %zu", npix * 4, labels_cap);
-            if (d_dist2 && dist2_cap < npix * 4) return fail(c, INFUR_E_CAPACITY, "the distance plane needs %zu bytes, buffer has %zu", npix * 4, dist2_cap);
-            if (split && (!lb || !d2)) {  // the planes Split reads, when the caller does not want them: [labels][dist2]
-                const size_t one = align_up(npix * 4, 256);
-                RETIF(ensure_private(c, c->st_split_plane, 2 * one));
-                if (!lb) lb = c->st_split_plane.p, lb_cap = npix * 4;
-                if (!d2) d2 = (uint8_t*)c->st_split_plane.p + one, d2_cap = npix * 4;
-            }
+            RETIF(cap_check(c, "segment", true, d_split_labels, split_labels_cap, npix * 4));
+            RETIF(cap_check(c, "label", true, d_labels, labels_cap, npix * 4));
+            RETIF(cap_check(c, "distance", true, d_dist2, dist2_cap, npix * 4));
+            if (split) RETIF(borrow_planes(c, c->st_split_plane, npix, &lb, &lb_cap, &d2, &d2_cap));  // the planes Split reads
         }  // (otherwise the call below fails before it decodes: bad scale, empty frame or no model)
         // scale -> model -> Segments decode -> Regions -> Anchors, with that call's own checks, errors and MODEL_NOT_LOADED rule
         RETIF(infur_frame_anchors_dev(c, d_bgr, w, h, factor, mode, decode, connectivity, min_pixels, flags, d_klass, d_conf, plane_cap, lb, lb_cap, d_table,
@@ -163,46 +149,30 @@ int32_t infur_frame_split(infur_ctx* c, const uint8_t* bgr, uint32_t w, uint32_t
     return abi_call(c, [&]() -> int32_t {
         if (!c || !ow || !oh) return INFUR_E_INVALID_ARG;
         RETIF(reg_check(c, connectivity, flags));
-        SplitFrameStage st(0, 0, 0, 0, false);
+        const RegHostOut o{klass, conf, plane_cap, labels, labels_cap, table, table_rows, n_regions, dist2, dist2_cap, anchors};
+        SplitFrameStage st(0, o, 0, false);
         uint8_t* base = nullptr;
-        const uint32_t arows = anchors ? table_rows : 0;
         const bool split = split_labels || (split_table && split_rows) || split_counts;
         return frame_host(
             c, bgr, w, h, factor, scaled, ow, oh,
             [&](size_t npix) -> int32_t {
-                if ((klass || conf) && plane_cap < npix) return fail(c, INFUR_E_CAPACITY, "a plane needs %zu bytes, buffer has %zu", npix, plane_cap);
-                if (labels && labels_cap < npix * 4) return fail(c, INFUR_E_CAPACITY, "the label plane needs %zu bytes, buffer has %zu", npix * 4, labels_cap);
-                if (c->loaded && dist2 && dist2_cap < npix * 4)
-                    return fail(c, INFUR_E_CAPACITY, "the distance plane needs %zu bytes, buffer has %zu", npix * 4, dist2_cap);
-                if (c->loaded && split_labels && split_labels_cap < npix * 4)
-                    return fail(c, INFUR_E_CAPACITY, "the segment plane needs %zu bytes, buffer has %zu", npix * 4, split_labels_cap);
-                st = SplitFrameStage(npix, table ? table_rows : 0, arows, split_table ? split_rows : 0, split_labels != nullptr);
-                RETIF(ensure_private(c, c->st_split_io, st.bytes));
+                RETIF(reg_caps_check(c, o, npix));
+                RETIF(cap_check(c, "segment", c->loaded, split_labels, split_labels_cap, npix * 4));
+                st = SplitFrameStage(npix, o, split_table ? split_rows : 0, split_labels != nullptr);
+                RETIF(ensure_private(c, c->st_split_io, st.r.end));
                 base = (uint8_t*)c->st_split_io.p;
                 return INFUR_OK;
             },
             [&](void* d_bgr, void* d_scaled) {
                 const size_t npix = (size_t)*ow * *oh;
-                return infur_frame_split_dev(c, d_bgr, w, h, factor, mode, decode, connectivity, min_pixels, flags, base + st.klass,
-                                             (conf || table) ? base + st.conf : nullptr, npix, (labels || dist2 || arows || split) ? base + st.rlabels : nullptr,
-                                             npix * 4, (table && st.rrows) ? base + st.rtable : nullptr, arows ? table_rows : (uint32_t)st.rrows,
-                                             (labels || table || n_regions) ? base + st.n : nullptr, d_scaled, ow, oh,
-                                             (dist2 || split) ? base + st.dist2 : nullptr, npix * 4, arows ? base + st.anchors : nullptr, core, pair_slots,
+                const RegDevArgs a = reg_dev_args(o, base, st.r, npix, split);
+                return infur_frame_split_dev(c, d_bgr, w, h, factor, mode, decode, connectivity, min_pixels, flags, a.klass, a.conf, a.plane_cap, a.labels,
+                                             a.labels_cap, a.table, a.table_rows, a.n, d_scaled, ow, oh, a.dist2, a.dist2_cap, a.anchors, core, pair_slots,
                                              split_labels ? base + st.sp.labels : nullptr, npix * 4, st.sp.rows ? base + st.sp.table : nullptr,
                                              (uint32_t)st.sp.rows, split ? base : nullptr);
             },
             [&](size_t npix) -> int32_t {
-                if (klass) HIPCHK(c, hipMemcpyAsync(klass, base + st.klass, npix, hipMemcpyDeviceToHost, c->stream));
-                if (conf) HIPCHK(c, hipMemcpyAsync(conf, base + st.conf, npix, hipMemcpyDeviceToHost, c->stream));
-                if (dist2) HIPCHK(c, hipMemcpyAsync(dist2, base + st.dist2, npix * 4, hipMemcpyDeviceToHost, c->stream));
-                if (arows) HIPCHK(c, hipMemcpyAsync(anchors, base + st.anchors, (size_t)arows * INFUR_ANCHOR_WORDS * 4, hipMemcpyDeviceToHost, c->stream));
-                uint32_t n = 0;
-                HIPCHK(c, hipMemcpyAsync(&n, base + st.n, 4, hipMemcpyDeviceToHost, c->stream));
-                if (labels) HIPCHK(c, hipMemcpyAsync(labels, base + st.rlabels, npix * 4, hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                const size_t rows = n < st.rrows ? n : st.rrows;
-                if (table && rows) HIPCHK(c, hipMemcpy(table, base + st.rtable, rows * INFUR_REGION_WORDS * 8, hipMemcpyDeviceToHost));
-                if (n_regions) *n_regions = n;
+                RETIF(reg_read_back(c, base, st.r, npix, o));
                 if (!split) return INFUR_OK;
                 return split_read_back(c, base, st.sp, npix, split_labels, split_table, split_counts);
             });

@@ -7,7 +7,7 @@
 #include <new>
 
 #include "infur_ctx.h"
-#include "infur_rt.h"
+#include "infur_region_frames.h"
 #include "kernels.h"
 #include "wave_scan.h"
 
@@ -62,17 +62,13 @@ void tracker_detach(infur_tracker* t) {
 
 inline infur_ctx* trk_ctx(void* tracker) { return tracker ? ((infur_tracker*)tracker)->ctx : nullptr; }
 
-// staging of the host-pointer calls, on 256-byte boundaries: [count][summary] [table][labels][class][confidence] and the outputs
-struct TrkStage {
-    size_t rows, summary, table, labels, klass, conf, tor, plane, ttab, bytes;
-    TrkStage(size_t npix, uint32_t table_rows, bool planes) {
-        rows = table_rows < npix ? table_rows : npix;  // there are at most npix regions
+// staging of the host-pointer calls, on 256-byte boundaries: Regions' products with the summary at 128, then the outputs.  Without
+// `planes` (infur_tracks, which stages no class or confidence plane) the outputs start where those two would lie.
+struct TrkStage : RegLayout {
+    size_t summary, tor, plane, ttab, bytes;
+    TrkStage(size_t npix, uint32_t table_rows, bool planes) : RegLayout(0, npix, table_rows) {
         summary = 128;
-        table = 256;
-        labels = table + align_up(rows * INFUR_REGION_WORDS * 8, 256);
-        klass = labels + align_up(npix * 4, 256);
-        conf = klass + (planes ? align_up(npix, 256) : 0);
-        tor = conf + (planes ? align_up(npix, 256) : 0);
+        tor = planes ? end : klass;
         plane = tor + align_up(rows * 4, 256);
         ttab = plane + align_up(npix * 4, 256);
         bytes = ttab + align_up(rows * INFUR_TRACK_WORDS * 8, 256);
@@ -370,13 +366,14 @@ int32_t infur_frame_tracks(infur_ctx* c, const uint8_t* bgr, uint32_t w, uint32_
         RETIF(reg_check(c, connectivity, flags));
         if (!tor && !plane && !ttab && !summary) return INFUR_E_INVALID_ARG;
         infur_tracker* t = (infur_tracker*)tracker;
+        uint32_t n = 0;  // the count is always read: it decides how many rows of the tracker's outputs there are to copy, too
+        const RegHostOut o{klass, conf, plane_cap, labels, labels_cap, table, table_rows, &n};
         TrkStage st(0, 0, true);
         uint8_t* base = nullptr;
         return frame_host(
             c, bgr, w, h, factor, scaled, ow, oh,
             [&](size_t npix) -> int32_t {
-                if ((klass || conf) && plane_cap < npix) return fail(c, INFUR_E_CAPACITY, "a plane needs %zu bytes, buffer has %zu", npix, plane_cap);
-                if (labels && labels_cap < npix * 4) return fail(c, INFUR_E_CAPACITY, "the label plane needs %zu bytes, buffer has %zu", npix * 4, labels_cap);
+                RETIF(reg_caps_check(c, o, npix));
                 st = TrkStage(npix, table_rows, true);
                 RETIF(ensure_private(c, t->io, st.bytes));
                 base = (uint8_t*)t->io.p;
@@ -390,14 +387,7 @@ int32_t infur_frame_tracks(infur_ctx* c, const uint8_t* bgr, uint32_t w, uint32_
                                               base + st.summary);
             },
             [&](size_t npix) -> int32_t {
-                uint32_t n = 0;  // the count decides how many rows there are to copy
-                HIPCHK(c, hipMemcpyAsync(&n, base, 4, hipMemcpyDeviceToHost, c->stream));
-                if (klass) HIPCHK(c, hipMemcpyAsync(klass, base + st.klass, npix, hipMemcpyDeviceToHost, c->stream));
-                if (conf) HIPCHK(c, hipMemcpyAsync(conf, base + st.conf, npix, hipMemcpyDeviceToHost, c->stream));
-                if (labels) HIPCHK(c, hipMemcpyAsync(labels, base + st.labels, npix * 4, hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                const size_t rows = n < st.rows ? n : st.rows;
-                if (table && rows) HIPCHK(c, hipMemcpy(table, base + st.table, rows * INFUR_REGION_WORDS * 8, hipMemcpyDeviceToHost));
+                RETIF(reg_read_back(c, base, st, npix, o));
                 if (n_regions) *n_regions = n;
                 return trk_read_back(c, base, st, npix, n, tor, plane, ttab, summary);
             });
