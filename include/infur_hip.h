@@ -1752,6 +1752,84 @@ int32_t infur_frame_expand_dev(infur_ctx* ctx, const void* d_bgr, uint32_t w, ui
                                void* d_grown, size_t grown_capacity, void* d_dist2, size_t dist2_capacity, void* d_source,
                                size_t source_capacity, void* d_expand_table, uint32_t expand_rows, void* d_expand_counts);
 
+/* ---- Redact: fill, pixelate or blur the pixels of chosen values ----
+ * Every stage above describes the frame; none changes the picture.  Redact does: the pixels a plane selects are hidden in the packed
+ * BGR frame -- one tracked person, every licence plate, or with INFUR_REDACT_INVERT everything else (background blur) -- where a host
+ * otherwise pulls the plane across PCIe, blurs the frame on the CPU and pushes it back.  A margin is Expand followed by Redact.
+ * Announced by infur_features() & INFUR_FEATURE_REDACT (INFUR_ABI_VERSION does not move).
+ *
+ * INPUTS.  `frame`: h x w x 3 bytes, B G R.  `plane`: h x w elements of elem_bytes = 1 or 4 (a class, label or track plane); h and w
+ * 1 to INFUR_REDACT_MAX_SIDE.  `select`: select_rows bytes.  A pixel with value v is SELECTED iff v < select_rows && select[v] != 0;
+ * with INFUR_REDACT_INVERT in `flags` the answer is flipped, so that INFUR_REGION_NONE, INFUR_TRACK_NONE and every value beyond the
+ * table are selected (any other flag bit is INFUR_E_INVALID_ARG).  select may be NULL when select_rows is 0.
+ *
+ * THE RULE.  Unselected pixels of `out` equal the frame, byte for byte, and never contribute to a selected pixel's result: no halo
+ * of the foreground in a blurred background, nothing of the hidden object leaking the other way.  Throughout,
+ * mean(S, n) = (2 S + n) / (2 n) in unsigned integer division (round half up); n >= 1, because the pixel itself is selected.
+ *   INFUR_REDACT_FILL      a selected pixel reads `colour` (B = bits 0-7, G = bits 8-15, R = bits 16-23)
+ *   INFUR_REDACT_PIXELATE  size = B in 2..256: cells of B x B pixels, aligned to the origin and clipped at the frame; a selected pixel
+ *                          reads, per channel, mean over the selected pixels of its cell
+ *   INFUR_REDACT_BLUR      size = r in 1..255, passes in 1..3: one pass gives a selected pixel, per channel, mean over the selected
+ *                          pixels of the (2r+1) x (2r+1) window around it, clipped at the frame; pass k+1 reads pass k's picture; the
+ *                          selection is the same in every pass.  Three passes approximate a Gaussian
+ * size and passes are checked only in the modes that use them.  The two averaging modes take at most INFUR_REDACT_MAX_PIXELS
+ * pixels (4K fits): every running sum then fits 32 bits; more is INFUR_E_INVALID_ARG.  Exact integers, a function of the inputs
+ * alone, identical bytes from run to run.
+ *
+ * OUTPUTS, each optional (NULL = not wanted; neither is INFUR_E_INVALID_ARG), none needs initialisation:
+ *   out     h*w*3 bytes.  out may be the frame itself (in place); any other overlap of the two is INFUR_E_INVALID_ARG.  Neither may
+ *           overlap the plane or the table
+ *   counts  INFUR_REDACT_COUNT_WORDS uint32_t: SELECTED, OUTSIDE (the pixels whose value is >= select_rows, counted before INVERT),
+ *           PASSES (0 for FILL, 1 for PIXELATE, passes for BLUR), four reserved zeros, STATUS (INFUR_REDACT_NOTHING: nothing is
+ *           selected and out is the frame)
+ * The checks come in this order: elem_bytes, flags, mode, size and passes, the sides, the pixels, a NULL select with rows, nothing
+ * wanted, a NULL plane or frame, the overlap.  No output is touched when a call is rejected.
+ *
+ * EXAMPLE.  The 1 x 6 frame with B = 10 20 90 40 50 61 (G = R = 0), the byte plane 1 1 0 1 1 1 and select = {0, 1}:
+ *   PIXELATE 2       cells {0,1} {2,3} {4,5}: 15 15 90 40 56 56   (the cell {2,3} holds one selected pixel; (2*111 + 2) / 4 = 56)
+ *   BLUR r = 1       (10+20)/2, (10+20)/2, 90, (40+50)/2, (40+50+61)/3, (50+61)/2  =  15 15 90 45 50 56
+ *   BLUR r = 1, two  from 15 15 90 45 50 56:  15 15 90 48 50 53
+ *   with INVERT      pixel 2 alone is selected and keeps 90 in either mode; FILL with colour 7 writes 10 20 7 40 50 61
+ *   counts           SELECTED 5, OUTSIDE 0, PASSES 1 (2 for two passes), 0, 0, 0, 0, STATUS 0 */
+enum { INFUR_REDACT_FILL = 0, INFUR_REDACT_PIXELATE = 1, INFUR_REDACT_BLUR = 2 };
+enum { INFUR_REDACT_INVERT = 1 };
+enum { INFUR_REDACT_COUNT_SELECTED = 0, INFUR_REDACT_COUNT_OUTSIDE = 1, INFUR_REDACT_COUNT_PASSES = 2, INFUR_REDACT_COUNT_STATUS = 7,
+       INFUR_REDACT_COUNT_WORDS = 8 };
+enum { INFUR_REDACT_NOTHING = 1 };
+enum { INFUR_REDACT_MAX_SIDE = 32768, INFUR_REDACT_MAX_PIXELS = 16777216 };
+enum { INFUR_FEATURE_REDACT = 131072 };
+
+/* on a given frame and plane, host pointers */
+int32_t infur_redact(infur_ctx* ctx, const uint8_t* frame, const void* plane, uint32_t elem_bytes, uint32_t h, uint32_t w,
+                     const uint8_t* select, uint32_t select_rows, uint32_t flags, uint32_t mode, uint32_t size, uint32_t passes,
+                     uint32_t colour, uint8_t* out, uint32_t* counts);
+/* device pointers throughout, the table included; enqueued on the context's stream as launches only -- no memset, nothing read
+ * back; their number is fixed by the arguments: FILL one; PIXELATE and each pass of BLUR a row pass, a band pass, above 64 rows a
+ * totals and an add pass, and a resolve pass; a clear and a counts launch where counts are wanted.  The call never synchronises and
+ * is capturable after one call outside the capture, which allocates the scratch (sixteen bytes per pixel in the averaging modes,
+ * owned by the context; it grows only with a request larger than any before).  This is the call that composes on the device:
+ * infur_frame_tracks_dev then infur_redact_dev hides one tracked person, infur_frame_expand_dev then infur_redact_dev hides a region
+ * with a margin. */
+int32_t infur_redact_dev(infur_ctx* ctx, const void* d_frame, const void* d_plane, uint32_t elem_bytes, uint32_t h, uint32_t w,
+                         const void* d_select, uint32_t select_rows, uint32_t flags, uint32_t mode, uint32_t size, uint32_t passes,
+                         uint32_t colour, void* d_out, void* d_counts);
+/* The fused frame path with the redacted picture: scale -> model -> Segments decode(out[0]) -> Redact of the scaled frame by the class
+ * plane, in one call.  `redacted` takes ow*oh*3 bytes (less is INFUR_E_CAPACITY, checked once a model is loaded); klass, conf
+ * (plane_capacity bytes each), counts and scaled_bgr are optional, and so is redacted; at least one of redacted, klass, conf and
+ * counts must be given.  The class plane goes to scratch of the library's own when the caller does not want it; d_redacted may be
+ * d_scaled_bgr (in place).  Every check and error behind Redact's own argument checks is infur_frame_segments' own: with no model
+ * loaded the Scale stage still runs and the call returns INFUR_E_MODEL_NOT_LOADED.  The calls always enqueue eagerly and leave the
+ * graphs cached for infur_frame_advance_dev alone. */
+int32_t infur_frame_redact(infur_ctx* ctx, const uint8_t* bgr, uint32_t w, uint32_t h, float factor, uint32_t scale_mode,
+                           uint32_t decode, const uint8_t* select, uint32_t select_rows, uint32_t redact_flags, uint32_t redact_mode,
+                           uint32_t size, uint32_t passes, uint32_t colour, uint8_t* redacted, size_t redacted_capacity, uint8_t* klass,
+                           uint8_t* conf, size_t plane_capacity, uint32_t* counts, uint8_t* scaled_bgr, uint32_t* ow, uint32_t* oh);
+int32_t infur_frame_redact_dev(infur_ctx* ctx, const void* d_bgr, uint32_t w, uint32_t h, float factor, uint32_t scale_mode,
+                               uint32_t decode, const void* d_select, uint32_t select_rows, uint32_t redact_flags, uint32_t redact_mode,
+                               uint32_t size, uint32_t passes, uint32_t colour, void* d_redacted, size_t redacted_capacity,
+                               void* d_klass, void* d_conf, size_t plane_capacity, void* d_counts, void* d_scaled_bgr, uint32_t* ow,
+                               uint32_t* oh);
+
 /* ---- streaming (infur/src/main.rs:27-99,105): bounded queue, copies overlapped with compute ----
  * The reference back-pressures its producer with sync_channel(2) (main.rs:105); a stream
  * here is a ring of `depth` pinned + device slots.  submit() copies the caller's frame into a

@@ -573,6 +573,56 @@ private:
     bool dirty_ = true;
 };
 
+/// What `Redact` produces: the redacted frame (`width * height * 3` bytes, B G R; empty with `want_out` false) and the eight counts.
+struct RedactOut {
+    bool want_out = true;  // what to provide
+    uint32_t width = 0, height = 0;
+    std::vector<uint8_t> out;
+    uint32_t counts[INFUR_REDACT_COUNT_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
+    bool nothing() const { return (counts[INFUR_REDACT_COUNT_STATUS] & INFUR_REDACT_NOTHING) != 0; }
+};
+
+/// The stage that writes the frame: the pixels a plane selects (value v is selected iff v < select.size() && select[v] != 0; the
+/// opposite with `invert`) are filled, pixelated or blurred in the packed BGR frame.  Unselected pixels keep their bytes and never
+/// contribute to a hidden pixel.  Integer results, identical from run to run.  Command = what to hide and how; Input = a frame and a
+/// plane of uint8_t or uint32_t, Output = RedactOut.
+class Redact {
+public:
+    struct Cmd {
+        std::vector<uint8_t> select;
+        uint32_t mode = INFUR_REDACT_BLUR, size = 8, passes = 1, colour = 0;
+        bool invert = false;
+    };
+    explicit Redact(Context& c) : c_(c) {}
+    Status control(Cmd cmd) {
+        cmd_ = std::move(cmd);
+        dirty_ = true;
+        return INFUR_OK;
+    }
+    bool is_dirty() const { return dirty_; }
+    Status advance(const std::vector<uint8_t>& frame, const std::vector<uint8_t>& plane, uint32_t height, uint32_t width, RedactOut& out) {
+        return run(frame, plane.data(), plane.size(), 1, height, width, out);
+    }
+    Status advance(const std::vector<uint8_t>& frame, const std::vector<uint32_t>& plane, uint32_t height, uint32_t width, RedactOut& out) {
+        return run(frame, plane.data(), plane.size(), 4, height, width, out);
+    }
+
+private:
+    Status run(const std::vector<uint8_t>& frame, const void* plane, size_t elems, uint32_t elem_bytes, uint32_t height, uint32_t width, RedactOut& out) {
+        dirty_ = false;
+        if (elems != (size_t)width * height || frame.size() != elems * 3) return INFUR_E_SHAPE;
+        out.width = width;
+        out.height = height;
+        out.out.assign(out.want_out ? frame.size() : 0, 0);
+        return infur_redact(c_.get(), frame.data(), plane, elem_bytes, height, width, cmd_.select.empty() ? nullptr : cmd_.select.data(),
+                            (uint32_t)cmd_.select.size(), cmd_.invert ? INFUR_REDACT_INVERT : 0, cmd_.mode, cmd_.size, cmd_.passes, cmd_.colour,
+                            out.want_out ? out.out.data() : nullptr, out.counts);
+    }
+    Context& c_;
+    Cmd cmd_;
+    bool dirty_ = true;
+};
+
 /// What `Compare` produces for `rows_a` x `rows_b` values: `matrix` row-major (pixels with a == i and b == j), `a` and `b` rows of
 /// INFUR_COMPARE_WORDS words per value of either plane ((0, INFUR_COMPARE_NONE, 0, 0): no compared pixel holds the value) and the
 /// INFUR_COMPARE_COUNT_WORDS counts.

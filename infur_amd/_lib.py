@@ -152,6 +152,13 @@ EXPAND_NO_SEED = 1
 EXPAND_NONE = 0xFFFFFFFF
 EXPAND_MAX_SIDE = 32768
 FEATURE_EXPAND = 65536
+# Redact (infur_redact / infur_frame_redact): the modes, the flag, the words of the counts, the status bit, the limits
+REDACT_FILL, REDACT_PIXELATE, REDACT_BLUR = 0, 1, 2
+REDACT_INVERT = 1
+REDACT_COUNT_SELECTED, REDACT_COUNT_OUTSIDE, REDACT_COUNT_PASSES, REDACT_COUNT_STATUS, REDACT_COUNT_WORDS = 0, 1, 2, 7, 8
+REDACT_NOTHING = 1
+REDACT_MAX_SIDE, REDACT_MAX_PIXELS = 32768, 1 << 24
+FEATURE_REDACT = 131072
 
 
 class Options(C.Structure):
@@ -346,7 +353,13 @@ SIGNATURES = {
                                        _u32p, _u32p, _u32, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _u32, _vp]),
     "infur_frame_expand_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp, _vp,
                                            _u32p, _u32p, _u32, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _u32, _vp]),
-    "infur_stream_create": (C.c_int32, [_vp, _u32, C.POINTER(_vp)]),
+    "infur_redact": (C.c_int32, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp]),
+    "infur_redact_dev": (C.c_int32, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp]),
+    "infur_frame_redact": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _sz, _vp, _vp, _sz, _vp, _vp,
+                                       _u32p, _u32p]),
+    "infur_frame_redact_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _sz, _vp, _vp, _sz, _vp,
+                                           _vp, _u32p, _u32p]),
+    "infur_stream_create":(C.c_int32, [_vp, _u32, C.POINTER(_vp)]),
     "infur_stream_destroy": (None, [_vp]),
     "infur_stream_add_lane": (C.c_int32, [_vp, _vp]),
     "infur_stream_submit": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, C.c_uint64]),

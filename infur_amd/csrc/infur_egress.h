@@ -26,11 +26,12 @@ inline int32_t tol_check(infur_ctx* c, uint32_t tol16) {
     if (tol16 > 65535) return fail(c, INFUR_E_INVALID_ARG, "tol16 %u: at most 65535 (4095.9 pixels)", tol16);
     return INFUR_OK;
 }
-// sides of at most kMaxSide; Simplify, which reads no plane, lets a height of 0 pass
-inline int32_t side_check(infur_ctx* c, uint32_t h, uint32_t w, bool empty_ok) {
-    if (w != 0 && w <= kMaxSide && h <= kMaxSide && (h != 0 || empty_ok)) return INFUR_OK;
-    if (empty_ok) return fail(c, INFUR_E_INVALID_ARG, "%ux%u: a plane of width 1 to %u and height up to %u", w, h, kMaxSide, kMaxSide);
-    return fail(c, INFUR_E_INVALID_ARG, "%ux%u: a plane of width and height 1 to %u", w, h, kMaxSide);
+// sides of at most `most` (kMaxSide for the polygon stages; Redact, which holds no coordinate differences, passes its own);
+// Simplify, which reads no plane, lets a height of 0 pass
+inline int32_t side_check(infur_ctx* c, uint32_t h, uint32_t w, bool empty_ok, uint32_t most = kMaxSide) {
+    if (w != 0 && w <= most && h <= most && (h != 0 || empty_ok)) return INFUR_OK;
+    if (empty_ok) return fail(c, INFUR_E_INVALID_ARG, "%ux%u: a plane of width 1 to %u and height up to %u", w, h, most, most);
+    return fail(c, INFUR_E_INVALID_ARG, "%ux%u: a plane of width and height 1 to %u", w, h, most);
 }
 // `sfx`: "" where the arguments are loops, vertices, counts (Outlines), "_out" behind Outlines
 inline int32_t wanted_check(infur_ctx* c, const void* loops, uint32_t loops_rows, const void* vertices, uint32_t vertex_rows, const void* counts,

@@ -384,6 +384,24 @@ size_t expand_scratch_bytes(size_t npix, unsigned rows);
 hipError_t launch_expand(const void* plane, int elem_bytes, unsigned H, unsigned W, unsigned open_value, unsigned reach, void* scratch, void* out,
                          unsigned* dist2, unsigned* source, unsigned* table, unsigned rows, unsigned* counts, hipStream_t s);
 
+// Redact (redact.hip): the selected pixels of a packed BGR frame[H * W * 3] are filled with `colour`, pixelated (cells of size x
+// size) or blurred (`passes` box passes of radius size) into out[H * W * 3], which may be the frame itself; only selected pixels
+// contribute and only selected pixels change.  A pixel of the H x W plane (1- or 4-byte elements) is selected when its value v is
+// below select_rows and select[v] is not zero -- the opposite with invert.  counts[kRedactCountWords] = {SELECTED, OUTSIDE, PASSES,
+// 0, 0, 0, 0, STATUS} (out and counts each optional; device memory).  Sides 1 to kRedactMaxSide; the averaging modes take at most
+// kRedactMaxPixels pixels.  scratch: redact_scratch_bytes(H * W, mode) bytes the launches own for the call.  Stream-ordered,
+// launches only: FILL one; an averaging pass three (five above 64 rows: rows, bands, totals, add, resolve); a clear and a counts
+// launch where counts are wanted.  No workgroup waits for another.
+constexpr int kRedactCountWords = 8;
+constexpr unsigned kRedactFill = 0u, kRedactPixelate = 1u, kRedactBlur = 2u;
+constexpr unsigned kRedactNothing = 1u;
+constexpr unsigned kRedactMaxSide = 32768;
+constexpr size_t kRedactMaxPixels = (size_t)1 << 24;
+size_t redact_scratch_bytes(size_t npix, unsigned mode);
+hipError_t launch_redact(const uint8_t* frame, const void* plane, int elem_bytes, unsigned H, unsigned W, const uint8_t* select, unsigned select_rows,
+                         int invert, unsigned mode, unsigned size, unsigned passes, unsigned colour, void* scratch, uint8_t* out, unsigned* counts,
+                         hipStream_t s);
+
 // Compare (compare.hip): two H x W planes (both sides at most 65535) of 1- or 4-byte elements against each other.  A pixel whose
 // a equals ignore_a (ign_a set) or whose b equals ignore_b (ign_b set) is ignored; a compared pixel with a >= rows_a or
 // b >= rows_b is outside; the rest are inside.  matrix[rows_a x rows_b] u32 counts the inside pixels per (a, b); rows_a_out and

@@ -18,7 +18,7 @@ import ctypes as C
 import math
 import os
 from dataclasses import dataclass
-from typing import Generic, List, NamedTuple, Optional, TypeVar
+from typing import Generic, List, NamedTuple, Optional, Sequence, Tuple, TypeVar
 
 import numpy as np
 
@@ -1088,6 +1088,118 @@ def expand_summary(table: np.ndarray, names=None) -> List[dict]:
             rec["name"] = names[v]
         recs.append(rec)
     return recs
+
+
+def _select_table(values, rows: int = 0) -> np.ndarray:
+    """the selection table that selects exactly ``values``: one byte per value, ``max(values) + 1`` of them or ``rows`` if more"""
+    values = sorted({int(v) for v in values})
+    if values and values[0] < 0:
+        raise InfurError(_lib.E_INVALID_ARG, f"selected value {values[0]}: a plane holds no negative value")
+    table = np.zeros(max(rows, values[-1] + 1 if values else 0), np.uint8)
+    table[values] = 1
+    return table
+
+
+@dataclass
+class RedactCmd:
+    """``Redact``'s command: which values to hide and how.  ``select`` lists the values (or is a ready table of bytes, one per
+    value, as a ``np.uint8`` array); ``invert`` hides everything else instead.  ``Fill(colour)`` paints ``colour`` = (B, G, R);
+    ``Pixelate(size)`` averages the selected pixels of each ``size`` x ``size`` cell; ``Blur(radius, passes)`` averages those of the
+    window of that radius, ``passes`` times (three approximate a Gaussian)."""
+
+    select: Sequence[int] = ()
+    mode: int = _lib.REDACT_BLUR
+    size: int = 8
+    passes: int = 1
+    colour: Tuple[int, int, int] = (0, 0, 0)
+    invert: bool = False
+
+    @staticmethod
+    def Fill(select, colour=(0, 0, 0), invert: bool = False) -> "RedactCmd":
+        return RedactCmd(select=select, mode=_lib.REDACT_FILL, colour=tuple(colour), invert=invert)
+
+    @staticmethod
+    def Pixelate(select, size: int, invert: bool = False) -> "RedactCmd":
+        return RedactCmd(select=select, mode=_lib.REDACT_PIXELATE, size=size, invert=invert)
+
+    @staticmethod
+    def Blur(select, radius: int, passes: int = 1, invert: bool = False) -> "RedactCmd":
+        return RedactCmd(select=select, mode=_lib.REDACT_BLUR, size=radius, passes=passes, invert=invert)
+
+    def table(self) -> np.ndarray:
+        if isinstance(self.select, np.ndarray) and self.select.dtype == np.uint8:
+            return np.ascontiguousarray(self.select.ravel())
+        return _select_table(self.select)
+
+    def colour_word(self) -> int:
+        b, g, r = (int(v) & 255 for v in self.colour)
+        return b | (g << 8) | (r << 16)
+
+    def flags(self) -> int:
+        return _lib.REDACT_INVERT if self.invert else 0
+
+
+class RedactOut:
+    """``Redact``'s ``&mut Output``: after ``advance`` the redacted frame ``out`` [H, W, 3] u8 (None with ``want_out=False``) and
+    ``counts`` [8] u32 (``_lib.REDACT_COUNT_SELECTED`` ..); ``nothing`` says that no pixel was selected and ``out`` is the frame."""
+
+    def __init__(self, want_out: bool = True):
+        self.want_out = want_out
+        self.out = self.counts = None
+
+    @property
+    def nothing(self) -> bool:
+        return bool(self.counts is not None and self.counts[_lib.REDACT_COUNT_STATUS] & _lib.REDACT_NOTHING)
+
+
+class Redact(Processor):
+    """The stage that writes the frame: the pixels a class plane (u8) or a label / track plane (u32) selects are filled, pixelated
+    or blurred in the packed BGR frame; unselected pixels keep their bytes and never contribute to a hidden pixel, nor the other
+    way round.
+
+    Command = ``RedactCmd``.  Input = (frame [H, W, 3] u8, plane [H, W] of u8 or u32); Output = ``RedactOut``.  Integers throughout,
+    identical from run to run.
+    """
+
+    def __init__(self, ctx: Context, cmd: Optional[RedactCmd] = None):
+        self.ctx = ctx
+        self.cmd = cmd or RedactCmd()
+        self.dirty = True
+
+    def control(self, cmd: RedactCmd) -> "Redact":
+        key = lambda c: (c.table().tobytes(), c.mode, c.size, c.passes, c.colour_word(), c.invert)  # noqa: E731
+        self.dirty = self.dirty or key(cmd) != key(self.cmd)
+        self.cmd = cmd
+        return self
+
+    def is_dirty(self) -> bool:
+        return self.dirty
+
+    def advance(self, inp: Tuple[np.ndarray, np.ndarray], out: RedactOut) -> None:
+        self.dirty = False
+        frame, plane = inp
+        frame = _check_bgr(frame)
+        if plane.ndim != 2 or plane.dtype.itemsize not in (1, 4) or plane.dtype.kind not in "ui" or plane.shape != frame.shape[:2]:
+            raise InfurError(_lib.E_SHAPE, f"expected an [H,W] plane of 1- or 4-byte integers for a {frame.shape} frame, got {plane.shape} {plane.dtype}")
+        plane = np.ascontiguousarray(plane)
+        h, w = plane.shape
+        cmd, table = self.cmd, self.cmd.table()
+        res = np.empty_like(frame) if out.want_out else None
+        counts = np.zeros(_lib.REDACT_COUNT_WORDS, np.uint32)
+        self.ctx.check(self.ctx.L.infur_redact(self.ctx.h, frame.ctypes.data, plane.ctypes.data, plane.dtype.itemsize, h, w, _ptr_some(table), table.size,
+                                               cmd.flags(), cmd.mode, cmd.size, cmd.passes, cmd.colour_word(), _ptr(res), counts.ctypes.data))
+        out.out, out.counts = res, counts
+
+
+class RedactFrame(NamedTuple):
+    """``FramePath.advance_redact``: the redacted scaled frame [oh, ow, 3] u8, the class and confidence planes and the scaled frame
+    (None where not wanted) and the eight counts"""
+
+    redacted: Optional[np.ndarray]
+    klass: Optional[np.ndarray]
+    conf: Optional[np.ndarray]
+    counts: Optional[np.ndarray]
+    scaled: Optional[np.ndarray]
 
 
 @dataclass
@@ -2471,6 +2583,24 @@ class FramePath:
         k = min(n.value, rows)
         return ExpandFrame(klass, conf, labels, table[:k] if table is not None else None, n.value, scaled, grown, dist2, source,
                            etable[:k] if etable is not None else None, counts)
+
+    def advance_redact(self, img: np.ndarray, cmd: RedactCmd, factor: float = 1.0, decode: int = _lib.DECODE_RAW, want_klass: bool = False,
+                       want_conf: bool = False, want_scaled: bool = False) -> RedactFrame:
+        """The fused path with the redacted picture, scale -> model -> Segments decode -> Redact of the scaled frame by the class
+        plane, in one call -> ``RedactFrame``; every result field is None when no model is loaded (``scaled`` is still produced)."""
+        img, w, h, f, ow, oh = self._front(img, factor)
+        npix = oh.value * ow.value
+        table = cmd.table()
+        redacted = self._plane(ow, oh, True, channels=3)
+        klass, conf = self._plane(ow, oh, want_klass), self._plane(ow, oh, want_conf)
+        scaled = self._plane(ow, oh, want_scaled, channels=3)
+        counts = np.zeros(_lib.REDACT_COUNT_WORDS, np.uint32)
+        rc = self.ctx.L.infur_frame_redact(self.ctx.h, img.ctypes.data, w, h, f, self.scale_mode, decode, _ptr_some(table), table.size, cmd.flags(),
+                                           cmd.mode, cmd.size, cmd.passes, cmd.colour_word(), redacted.ctypes.data, npix * 3, _ptr(klass), _ptr(conf),
+                                           npix, counts.ctypes.data, _ptr(scaled), C.byref(ow), C.byref(oh))
+        if not self._loaded(rc):
+            return RedactFrame(None, None, None, None, scaled)
+        return RedactFrame(redacted, klass, conf, counts, scaled)
 
     def advance_split(self, img: np.ndarray, core: int, factor: float = 1.0, decode: int = _lib.DECODE_RAW, connectivity: int = _lib.CONNECT_8,
                       min_pixels: int = 0, flags: int = 0, table_rows: int = 1024, split_rows: int = 1024, pair_slots: int = 0,

@@ -75,6 +75,12 @@ skipped background; 0: as far as it takes), each open pixel going to its exact n
 gains ``"expand"`` (the frame's seeds, open, gained and left pixels and the largest distance to a region) and every region record
 ``"gained"`` and ``"margin"``, the distance it actually grew.  ``--expand-out FILE`` receives the grown u32 label planes.
 
+``--redact-out FILE`` hides the pixels of the classes ``--redact-classes 15[,2,..]`` in the scaled frame on the device
+(``infur_frame_redact``) and writes the bgr24 frames to FILE, so that the output pipes back into ffmpeg: ``--redact-mode blur``
+(``--redact-size`` the radius, ``--redact-passes`` 1 to 3), ``pixelate`` (``--redact-size`` the cell) or ``fill`` (``--redact-colour
+BBGGRR``); ``--redact-invert`` hides everything else instead (background blur).  Every line gains ``"redact"``: the frame's selected
+pixels.
+
 ``--truth FILE`` grades every frame: FILE holds one u8 ground-truth class plane of the scaled frame's size per frame, back to back;
 the class plane is compared with it (``infur_compare``; ``--truth-ignore V`` leaves the pixels whose truth is V, a "void" label,
 out), every line gains ``"pixel_accuracy"`` and ``"miou"``, and one last line holds the totals of the confusion matrices added up
@@ -170,7 +176,29 @@ def main(argv=None) -> int:
     ap.add_argument("--expand-out", default="", help="raw u32 grown label planes, four bytes per pixel (needs --expand)")
     ap.add_argument("--centrelines-out", default="", help="per frame 8 u32 counts, the branch records, the vertices (needs --skeleton)")
     ap.add_argument("--centrelines-corners", action="store_true", help="keep only the vertices at which a branch turns (needs --centrelines-out)")
+    ap.add_argument("--redact-out", default="", help="raw bgr24 frames with the pixels of --redact-classes hidden on the device")
+    ap.add_argument("--redact-classes", default="", metavar="K[,K..]", help="the classes to hide (needs --redact-out)")
+    ap.add_argument("--redact-mode", default="blur", choices=["blur", "pixelate", "fill"])
+    ap.add_argument("--redact-size", type=int, default=8, metavar="N", help="blur: the radius, 1 to 255; pixelate: the cell, 2 to 256")
+    ap.add_argument("--redact-passes", type=int, default=3, metavar="K", help="blur passes, 1 to 3 (three approximate a Gaussian)")
+    ap.add_argument("--redact-invert", action="store_true", help="hide everything but --redact-classes")
+    ap.add_argument("--redact-colour", default="000000", metavar="BBGGRR", help="the colour of --redact-mode fill")
     a = ap.parse_args(argv)
+    redact_classes = []
+    if a.redact_out:
+        try:
+            redact_classes = [int(v) for v in a.redact_classes.split(",") if v != ""]
+            redact_colour = int(a.redact_colour, 16)
+        except ValueError:
+            ap.error("--redact-classes: class numbers separated by commas; --redact-colour: six hexadecimal digits BBGGRR")
+        if not redact_classes or min(redact_classes) < 0 or max(redact_classes) > 255:
+            ap.error("--redact-out needs --redact-classes, each 0 to 255")
+        for given, name in ((a.regions, "--regions"), (a.runs_out, "--runs-out"), (a.outlines_out, "--outlines-out"), (a.truth, "--truth"),
+                            (a.outlines_fidelity, "--outlines-fidelity")):
+            if given:
+                ap.error(f"--redact-out does not combine with {name}: the fused redact call returns the picture and the two planes")
+    elif a.redact_classes or a.redact_invert:
+        ap.error("--redact-classes and --redact-invert need --redact-out")
     if a.centrelines_out and not a.skeleton:
         ap.error("--centrelines-out needs --skeleton")
     if a.centrelines_corners and not a.centrelines_out:
@@ -312,6 +340,14 @@ def main(argv=None) -> int:
     fskel = open(a.skeleton_out, "wb") if a.skeleton_out else None
     fcl = open(a.centrelines_out, "wb") if a.centrelines_out else None
     fexp = open(a.expand_out, "wb") if a.expand_out else None
+    fred = open(a.redact_out, "wb") if a.redact_out else None
+    if fred is not None:
+        from .processors import RedactCmd
+
+        colour = (redact_colour >> 16 & 255, redact_colour >> 8 & 255, redact_colour & 255)  # BBGGRR -> (B, G, R)
+        redact_cmd = {"blur": RedactCmd.Blur(redact_classes, a.redact_size, a.redact_passes, a.redact_invert),
+                      "pixelate": RedactCmd.Pixelate(redact_classes, a.redact_size, a.redact_invert),
+                      "fill": RedactCmd.Fill(redact_classes, colour, a.redact_invert)}[a.redact_mode]
     if a.regions and (a.sieve is not None or a.shapes or a.split is not None or a.skeleton or a.expand is not None):
         flags = _lib.REGIONS_SKIP_BACKGROUND if a.skip_background else 0
     elif a.regions:
@@ -350,6 +386,9 @@ def main(argv=None) -> int:
                                   want_labels=freg is not None, want_klass=True, want_conf=True, want_grown=fexp is not None, want_dist2=False)
             s = SegmentsFrame(r.klass, r.conf, _class_stats(r.klass, r.conf, model.get_info().num_classes), None, None)
             labels, table, nreg = r.labels, r.table, r.n
+        elif fred is not None:  # scale -> model -> decode -> Redact of the scaled frame by the class plane, in one call
+            r = fp.advance_redact(img, redact_cmd, a.scale, decode, want_klass=True, want_conf=True)
+            s = SegmentsFrame(r.klass, r.conf, _class_stats(r.klass, r.conf, model.get_info().num_classes), None, None)
         elif fcl is not None:  # the call below, then Centrelines of the label plane and the kind plane under dist2, in one call
             r = fp.advance_centrelines(img, a.scale, decode, a.connectivity, a.min_pixels, flags, table_rows=max(0, a.max_regions),
                                        skeleton_rows=max(0, a.max_regions), max_rounds=a.skeleton_rounds, corners=a.centrelines_corners, record_rows=1 << 20,
@@ -453,6 +492,9 @@ def main(argv=None) -> int:
                 freg.write(memoryview(labels).cast("B"))
             if fsplit is not None and r.segments is not None:
                 fsplit.write(memoryview(r.segments).cast("B"))
+        if fred is not None:
+            rec["redact"] = {"selected": int(r.counts[_lib.REDACT_COUNT_SELECTED]), "mode": a.redact_mode}
+            fred.write(memoryview(r.redacted).cast("B"))
         if a.expand is not None:
             ec = [int(v) for v in r.expand_counts]
             rec["n_regions"], rec["regions"] = nreg, region_summary(table, nreg, ow, oh)
@@ -520,7 +562,7 @@ def main(argv=None) -> int:
         ftruth.close()
     if a.outlines_fidelity:
         fst.write(json.dumps({"frames": n, "polygon_fidelity": fid_total}) + "\n")
-    for f in (flab, fconf, freg, ftrk, fruns, foutl, fdist, fhull, fsplit, fskel, fcl, fexp, fst):
+    for f in (flab, fconf, freg, ftrk, fruns, foutl, fdist, fhull, fsplit, fskel, fcl, fexp, fred, fst):
         if f is not None:
             f.flush()
     el = time.perf_counter() - t0

@@ -393,6 +393,21 @@ pub const INFUR_EXPAND_MAX_SIDE: u32 = 32768;
 pub const INFUR_EXPAND_NONE: u32 = 0xFFFF_FFFF;
 /// bit of `infur_features()`: the Expand calls below exist
 pub const INFUR_FEATURE_EXPAND: u32 = 65536;
+/// Redact: the modes, the flag, the words of the counts, the status bit, the limits
+pub const INFUR_REDACT_FILL: u32 = 0;
+pub const INFUR_REDACT_PIXELATE: u32 = 1;
+pub const INFUR_REDACT_BLUR: u32 = 2;
+pub const INFUR_REDACT_INVERT: u32 = 1;
+pub const INFUR_REDACT_COUNT_SELECTED: u32 = 0;
+pub const INFUR_REDACT_COUNT_OUTSIDE: u32 = 1;
+pub const INFUR_REDACT_COUNT_PASSES: u32 = 2;
+pub const INFUR_REDACT_COUNT_STATUS: u32 = 7;
+pub const INFUR_REDACT_COUNT_WORDS: u32 = 8;
+pub const INFUR_REDACT_NOTHING: u32 = 1;
+pub const INFUR_REDACT_MAX_SIDE: u32 = 32768;
+pub const INFUR_REDACT_MAX_PIXELS: u32 = 16777216;
+/// bit of `infur_features()`: the Redact calls below exist
+pub const INFUR_FEATURE_REDACT: u32 = 131072;
 
 extern "C" {
     pub fn infur_abi_version() -> u32;
@@ -795,4 +810,18 @@ extern "C" {
                                   reach: u32, d_grown: *mut c_void, grown_capacity: usize, d_dist2: *mut c_void, dist2_capacity: usize,
                                   d_source: *mut c_void, source_capacity: usize, d_expand_table: *mut c_void, expand_rows: u32,
                                   d_expand_counts: *mut c_void) -> i32;
+    // Redact: the pixels a plane selects filled, pixelated or blurred in the BGR frame
+    pub fn infur_redact(c: *mut infur_ctx, frame: *const u8, plane: *const c_void, elem_bytes: u32, h: u32, w: u32, select: *const u8,
+                        select_rows: u32, flags: u32, mode: u32, size: u32, passes: u32, colour: u32, out: *mut u8, counts: *mut u32) -> i32;
+    pub fn infur_redact_dev(c: *mut infur_ctx, d_frame: *const c_void, d_plane: *const c_void, elem_bytes: u32, h: u32, w: u32,
+                            d_select: *const c_void, select_rows: u32, flags: u32, mode: u32, size: u32, passes: u32, colour: u32,
+                            d_out: *mut c_void, d_counts: *mut c_void) -> i32;
+    pub fn infur_frame_redact(c: *mut infur_ctx, bgr: *const u8, w: u32, h: u32, factor: f32, scale_mode: u32, decode: u32,
+                              select: *const u8, select_rows: u32, redact_flags: u32, redact_mode: u32, size: u32, passes: u32, colour: u32,
+                              redacted: *mut u8, redacted_capacity: usize, klass: *mut u8, conf: *mut u8, plane_capacity: usize,
+                              counts: *mut u32, scaled_bgr: *mut u8, ow: *mut u32, oh: *mut u32) -> i32;
+    pub fn infur_frame_redact_dev(c: *mut infur_ctx, d_bgr: *const c_void, w: u32, h: u32, factor: f32, scale_mode: u32, decode: u32,
+                                  d_select: *const c_void, select_rows: u32, redact_flags: u32, redact_mode: u32, size: u32, passes: u32,
+                                  colour: u32, d_redacted: *mut c_void, redacted_capacity: usize, d_klass: *mut c_void, d_conf: *mut c_void,
+                                  plane_capacity: usize, d_counts: *mut c_void, d_scaled_bgr: *mut c_void, ow: *mut u32, oh: *mut u32) -> i32;
 }

@@ -762,6 +762,71 @@ impl Processor for HipExpand {
     }
 }
 
+// ---------------------------------------------------------------- Redact (the pixels a plane selects filled, pixelated or blurred)
+/// What `HipRedact` produces: the redacted frame (`w * h * 3` bytes, B G R; empty with `want_out` false) and the
+/// `INFUR_REDACT_COUNT_WORDS` counts.
+pub struct Redacted { pub want_out: bool, pub out: Vec<u8>, pub counts: [u32; sys::INFUR_REDACT_COUNT_WORDS as usize] }
+impl Default for Redacted {
+    fn default() -> Self { Self { want_out: true, out: Vec::new(), counts: [0; sys::INFUR_REDACT_COUNT_WORDS as usize] } }
+}
+impl Redacted {
+    /// nothing was selected: `out` is the frame
+    pub fn nothing(&self) -> bool { self.counts[sys::INFUR_REDACT_COUNT_STATUS as usize] & sys::INFUR_REDACT_NOTHING != 0 }
+}
+/// `select[v] != 0` selects value `v`; `invert` hides everything else instead.  `colour` is B | G << 8 | R << 16.
+pub enum RedactCmd {
+    Fill { select: Vec<u8>, invert: bool, colour: u32 },
+    Pixelate { select: Vec<u8>, invert: bool, size: u32 },
+    Blur { select: Vec<u8>, invert: bool, radius: u32, passes: u32 },
+}
+/// The frame and the plane that selects its pixels, both `size` = [w, h]
+pub struct RedactInput { pub frame: Vec<u8>, pub plane: RunsPlane }
+/// The stage that writes the frame: the selected pixels are filled, pixelated or blurred; unselected pixels keep their bytes and
+/// never contribute to a hidden pixel.  Integer results, identical from run to run.
+pub struct HipRedact { ctx: Rc<Ctx>, select: Vec<u8>, flags: u32, mode: u32, size: u32, passes: u32, colour: u32, dirty: bool }
+impl HipRedact {
+    pub fn new(ctx: Rc<Ctx>) -> Self { Self { ctx, select: Vec::new(), flags: 0, mode: sys::INFUR_REDACT_FILL, size: 0, passes: 0, colour: 0, dirty: true } }
+}
+impl Processor for HipRedact {
+    type Command = RedactCmd;
+    type ControlError = HipError;
+    type Input = RedactInput;
+    type Output = Redacted;
+    type ProcessResult = Result<(), HipError>;
+
+    fn control(&mut self, cmd: RedactCmd) -> Result<&mut Self, HipError> {
+        let (select, invert, mode, size, passes, colour) = match cmd {
+            RedactCmd::Fill { select, invert, colour } => (select, invert, sys::INFUR_REDACT_FILL, 0, 0, colour),
+            RedactCmd::Pixelate { select, invert, size } => (select, invert, sys::INFUR_REDACT_PIXELATE, size, 0, 0),
+            RedactCmd::Blur { select, invert, radius, passes } => (select, invert, sys::INFUR_REDACT_BLUR, radius, passes, 0),
+        };
+        self.select = select;
+        self.flags = if invert { sys::INFUR_REDACT_INVERT } else { 0 };
+        (self.mode, self.size, self.passes, self.colour) = (mode, size, passes, colour);
+        self.dirty = true;
+        Ok(self)
+    }
+    fn is_dirty(&self) -> bool { self.dirty }
+    fn advance(&mut self, inp: &RedactInput, out: &mut Redacted) -> Result<(), HipError> {
+        self.dirty = false;
+        let [w, h] = inp.plane.size;
+        let (ptr, len, elem_bytes) = match &inp.plane.data {
+            RunsPlaneData::U8(p) => (p.as_ptr() as *const std::ffi::c_void, p.len(), 1u32),
+            RunsPlaneData::U32(p) => (p.as_ptr() as *const std::ffi::c_void, p.len(), 4u32),
+        };
+        if len != w * h || inp.frame.len() != w * h * 3 { return Err(HipError::status(sys::INFUR_E_SHAPE)); }
+        out.out.resize(if out.want_out { w * h * 3 } else { 0 }, 0);
+        let rc = unsafe {
+            sys::infur_redact(self.ctx.0, inp.frame.as_ptr(), ptr, elem_bytes, h as u32, w as u32,
+                              if self.select.is_empty() { std::ptr::null() } else { self.select.as_ptr() }, self.select.len() as u32, self.flags,
+                              self.mode, self.size, self.passes, self.colour,
+                              if out.want_out { out.out.as_mut_ptr() } else { std::ptr::null_mut() }, out.counts.as_mut_ptr())
+        };
+        if rc != sys::INFUR_OK { return Err(HipError::from_ctx(&self.ctx, rc)); }
+        Ok(())
+    }
+}
+
 // ---------------------------------------------------------------- Compare (confusion matrix, best partner per value)
 /// What `HipCompare` produces for `rows_a` x `rows_b` values: `matrix` row-major (`matrix[i * rows_b + j]`: the pixels with a == i
 /// and b == j), `a` and `b` rows of `INFUR_COMPARE_WORDS` words (PIXELS, PARTNER, INTER, UNION) per value of either plane --
