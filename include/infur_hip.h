@@ -1830,6 +1830,77 @@ int32_t infur_frame_redact_dev(infur_ctx* ctx, const void* d_bgr, uint32_t w, ui
                                void* d_klass, void* d_conf, size_t plane_capacity, void* d_counts, void* d_scaled_bgr, uint32_t* ow,
                                uint32_t* oh);
 
+/* ---- Appearance: per-object colour sums and histogram from the frame ----
+ * Every stage behind Segments reads the planes; only Redact reads the picture, and it only writes it back.  Appearance says what an
+ * object looks like: a mean colour for a caption ("red car") or a readable label colour, a covariance, and a colour histogram to find
+ * an object again across a gap or across cameras -- where a host otherwise pulls the frame and the label plane across PCIe and runs
+ * np.bincount or cv2.calcHist with a mask, once per object.  Announced by infur_features() & INFUR_FEATURE_APPEARANCE
+ * (INFUR_ABI_VERSION does not move).
+ *
+ * INPUTS.  `frame`: h x w x 3 bytes, B G R, packed as Redact takes it.  `plane`: h x w elements of elem_bytes = 1 or 4 (a class, label,
+ * track, split or grown plane); h and w 1 to INFUR_APPEARANCE_MAX_SIDE.  `flags`: INFUR_APPEARANCE_SKIP leaves the pixels whose value
+ * equals skip_value uncounted (class 0, INFUR_REGION_NONE, INFUR_TRACK_NONE); any other bit is INFUR_E_INVALID_ARG.
+ *
+ * THE RULE.  A pixel with value v that is not skipped counts towards row v when v < table_rows, otherwise only in OUTSIDE.
+ *
+ * OUTPUTS, each optional (NULL = not wanted; none at all is INFUR_E_INVALID_ARG), none needs initialisation, every row below table_rows
+ * is written and a value with no pixels has an all-zero row:
+ *   table   table_rows x INFUR_APPEARANCE_WORDS uint64_t: PIXELS, SUM_B, SUM_G, SUM_R, SUM_BB, SUM_GG, SUM_RR, SUM_BG, SUM_BR, SUM_GR,
+ *           MODE_BIN (the most frequent histogram bin, ties to the smallest bin), MODE_COUNT.  Mean and covariance follow exactly
+ *           from the ten sums
+ *   hist    table_rows x INFUR_APPEARANCE_BINS uint32_t, the joint histogram on the top two bits of each channel:
+ *           bin = (R >> 6) << 4 | (G >> 6) << 2 | (B >> 6)
+ *   counts  INFUR_APPEARANCE_COUNT_WORDS uint32_t: COUNTED (the pixels that reached a row), SKIPPED, OUTSIDE (the three add up to
+ *           h * w), VALUES (the rows with PIXELS > 0), three reserved zeros, STATUS (INFUR_APPEARANCE_NOTHING: COUNTED is 0)
+ * Exact integers, a function of the inputs alone, identical bytes from run to run.  The checks come in this order: elem_bytes, flags,
+ * the sides, nothing wanted, a NULL plane or frame, an output that overlaps an input.  No output is touched when a call is rejected.
+ *
+ * EXAMPLE.  The 1 x 6 frame with B = 10 20 90 40 50 61 (G = R = 0), the byte plane 1 1 0 1 1 1, table_rows 2 and no flags:
+ *   row 0   PIXELS 1, SUM_B 90, SUM_BB 8100, MODE_BIN 1, MODE_COUNT 1;   row 1   PIXELS 5, SUM_B 181, SUM_BB 8321, MODE_BIN 0,
+ *   MODE_COUNT 5; every other sum is 0; hist[0][1] = 1 and hist[1][0] = 5; counts 6, 0, 0, 2, 0, 0, 0, 0
+ *   with SKIP and skip_value 0     row 0 is zero and the counts are 5, 1, 0, 1, 0, 0, 0, 0
+ *   with table_rows 1, no flags    row 0 as above and the counts are 1, 0, 5, 1, 0, 0, 0, 0 */
+enum { INFUR_APPEARANCE_SKIP = 1 };
+enum { INFUR_APPEARANCE_PIXELS = 0, INFUR_APPEARANCE_SUM_B = 1, INFUR_APPEARANCE_SUM_G = 2, INFUR_APPEARANCE_SUM_R = 3, INFUR_APPEARANCE_SUM_BB = 4,
+       INFUR_APPEARANCE_SUM_GG = 5, INFUR_APPEARANCE_SUM_RR = 6, INFUR_APPEARANCE_SUM_BG = 7, INFUR_APPEARANCE_SUM_BR = 8, INFUR_APPEARANCE_SUM_GR = 9,
+       INFUR_APPEARANCE_MODE_BIN = 10, INFUR_APPEARANCE_MODE_COUNT = 11, INFUR_APPEARANCE_WORDS = 12 };
+enum { INFUR_APPEARANCE_BINS = 64 };
+enum { INFUR_APPEARANCE_COUNT_COUNTED = 0, INFUR_APPEARANCE_COUNT_SKIPPED = 1, INFUR_APPEARANCE_COUNT_OUTSIDE = 2, INFUR_APPEARANCE_COUNT_VALUES = 3,
+       INFUR_APPEARANCE_COUNT_STATUS = 7, INFUR_APPEARANCE_COUNT_WORDS = 8 };
+enum { INFUR_APPEARANCE_NOTHING = 1 };
+enum { INFUR_APPEARANCE_MAX_SIDE = 32768 };
+enum { INFUR_FEATURE_APPEARANCE = 262144 };
+
+/* on a given frame and plane, host pointers */
+int32_t infur_appearance(infur_ctx* ctx, const uint8_t* frame, const void* plane, uint32_t elem_bytes, uint32_t h, uint32_t w,
+                         uint32_t flags, uint32_t skip_value, uint64_t* table, uint32_t table_rows, uint32_t* hist, uint32_t* counts);
+/* device pointers throughout; enqueued on the context's stream as three launches -- a clear, the tiles, a finish -- with no memset and
+ * nothing read back.  The call never synchronises and is capturable after one call outside the capture, which allocates the scratch
+ * (the count words, and a histogram of table_rows rows where the caller wants none; owned by the context, it grows only with a
+ * request larger than any before).  This is the call that composes on the device: infur_frame_tracks_dev then infur_appearance_dev
+ * describes every tracked object. */
+int32_t infur_appearance_dev(infur_ctx* ctx, const void* d_frame, const void* d_plane, uint32_t elem_bytes, uint32_t h, uint32_t w,
+                             uint32_t flags, uint32_t skip_value, void* d_table, uint32_t table_rows, void* d_hist, void* d_counts);
+/* The fused frame path with the appearance of every region: scale -> model -> Segments decode(out[0]) -> Regions -> Appearance of the
+ * scaled frame by the label plane, in one call.  Row i is region i and the pixels of no region are skipped.  The arguments are
+ * infur_frame_regions' followed by Appearance's outputs, each optional; at least one of labels, table, n_regions and the three must be
+ * given.  The label plane goes to scratch of the library's own when the caller does not want it, and the scaled frame is read where
+ * the Scale stage left it whether or not the caller wants scaled_bgr.  Every check and error is infur_frame_regions' own: with no model
+ * loaded the Scale stage still runs and the call returns INFUR_E_MODEL_NOT_LOADED; unwanted buffers are not touched.  The calls
+ * always enqueue eagerly and leave the graphs cached for infur_frame_advance_dev alone. */
+int32_t infur_frame_appearance(infur_ctx* ctx, const uint8_t* bgr, uint32_t w, uint32_t h, float factor, uint32_t scale_mode,
+                               uint32_t decode, uint32_t connectivity, uint32_t min_pixels, uint32_t region_flags, uint8_t* klass,
+                               uint8_t* conf, size_t plane_capacity, uint32_t* labels, size_t labels_capacity, uint64_t* table,
+                               uint32_t table_rows, uint32_t* n_regions, uint8_t* scaled_bgr, uint32_t* ow, uint32_t* oh,
+                               uint64_t* appearance_table, uint32_t appearance_rows, uint32_t* appearance_hist,
+                               uint32_t* appearance_counts);
+int32_t infur_frame_appearance_dev(infur_ctx* ctx, const void* d_bgr, uint32_t w, uint32_t h, float factor, uint32_t scale_mode,
+                                   uint32_t decode, uint32_t connectivity, uint32_t min_pixels, uint32_t region_flags, void* d_klass,
+                                   void* d_conf, size_t plane_capacity, void* d_labels, size_t labels_capacity, void* d_table,
+                                   uint32_t table_rows, void* d_n_regions, void* d_scaled_bgr, uint32_t* ow, uint32_t* oh,
+                                   void* d_appearance_table, uint32_t appearance_rows, void* d_appearance_hist,
+                                   void* d_appearance_counts);
+
 /* ---- streaming (infur/src/main.rs:27-99,105): bounded queue, copies overlapped with compute ----
  * The reference back-pressures its producer with sync_channel(2) (main.rs:105); a stream
  * here is a ring of `depth` pinned + device slots.  submit() copies the caller's frame into a

@@ -623,6 +623,62 @@ private:
     bool dirty_ = true;
 };
 
+/// What `Appearance` produces for `rows` values: `table` rows of INFUR_APPEARANCE_WORDS words (PIXELS, the three colour sums, the six
+/// second moments, MODE_BIN, MODE_COUNT), `hist` rows of INFUR_APPEARANCE_BINS bins (either empty when not wanted) and the eight counts.
+struct AppearanceOut {
+    bool want_table = true, want_hist = true;  // what to provide
+    uint32_t rows = 0;
+    std::vector<uint64_t> table;
+    std::vector<uint32_t> hist;
+    uint32_t counts[INFUR_APPEARANCE_COUNT_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
+    bool nothing() const { return (counts[INFUR_APPEARANCE_COUNT_STATUS] & INFUR_APPEARANCE_NOTHING) != 0; }
+    uint64_t pixels(uint32_t v) const { return table[(size_t)v * INFUR_APPEARANCE_WORDS + INFUR_APPEARANCE_PIXELS]; }
+    /// the mean of channel ch (0 B, 1 G, 2 R) of value v; 0 where it has no pixel
+    double mean(uint32_t v, int ch) const {
+        return pixels(v) ? (double)table[(size_t)v * INFUR_APPEARANCE_WORDS + INFUR_APPEARANCE_SUM_B + ch] / (double)pixels(v) : 0.0;
+    }
+};
+
+/// What every value of a plane looks like in the packed BGR frame: pixel count, colour sums, second moments and the joint 64-bin
+/// histogram per value.  Integer results, identical from run to run.  Command = the rows and what to skip; Input = a frame and a plane
+/// of uint8_t or uint32_t, Output = AppearanceOut.
+class Appearance {
+public:
+    struct Cmd {
+        uint32_t rows = 256;
+        bool skip = false;  // leave the pixels whose value is skip_value uncounted
+        uint32_t skip_value = 0;
+    };
+    explicit Appearance(Context& c) : c_(c) {}
+    Status control(Cmd cmd) {
+        cmd_ = cmd;
+        dirty_ = true;
+        return INFUR_OK;
+    }
+    bool is_dirty() const { return dirty_; }
+    Status advance(const std::vector<uint8_t>& frame, const std::vector<uint8_t>& plane, uint32_t height, uint32_t width, AppearanceOut& out) {
+        return run(frame, plane.data(), plane.size(), 1, height, width, out);
+    }
+    Status advance(const std::vector<uint8_t>& frame, const std::vector<uint32_t>& plane, uint32_t height, uint32_t width, AppearanceOut& out) {
+        return run(frame, plane.data(), plane.size(), 4, height, width, out);
+    }
+
+private:
+    Status run(const std::vector<uint8_t>& frame, const void* plane, size_t elems, uint32_t elem_bytes, uint32_t height, uint32_t width,
+               AppearanceOut& out) {
+        dirty_ = false;
+        if (elems != (size_t)width * height || frame.size() != elems * 3) return INFUR_E_SHAPE;
+        out.rows = cmd_.rows;
+        out.table.assign(out.want_table ? (size_t)cmd_.rows * INFUR_APPEARANCE_WORDS : 0, 0);
+        out.hist.assign(out.want_hist ? (size_t)cmd_.rows * INFUR_APPEARANCE_BINS : 0, 0);
+        return infur_appearance(c_.get(), frame.data(), plane, elem_bytes, height, width, cmd_.skip ? INFUR_APPEARANCE_SKIP : 0, cmd_.skip_value,
+                                out.want_table ? out.table.data() : nullptr, cmd_.rows, out.want_hist ? out.hist.data() : nullptr, out.counts);
+    }
+    Context& c_;
+    Cmd cmd_;
+    bool dirty_ = true;
+};
+
 /// What `Compare` produces for `rows_a` x `rows_b` values: `matrix` row-major (pixels with a == i and b == j), `a` and `b` rows of
 /// INFUR_COMPARE_WORDS words per value of either plane ((0, INFUR_COMPARE_NONE, 0, 0): no compared pixel holds the value) and the
 /// INFUR_COMPARE_COUNT_WORDS counts.

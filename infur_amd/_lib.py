@@ -159,6 +159,16 @@ REDACT_COUNT_SELECTED, REDACT_COUNT_OUTSIDE, REDACT_COUNT_PASSES, REDACT_COUNT_S
 REDACT_NOTHING = 1
 REDACT_MAX_SIDE, REDACT_MAX_PIXELS = 32768, 1 << 24
 FEATURE_REDACT = 131072
+# Appearance (infur_appearance / infur_frame_appearance): the flag, the words of a row, the bins, the words of the counts, the status bit
+APPEARANCE_SKIP = 1
+(APPEARANCE_PIXELS, APPEARANCE_SUM_B, APPEARANCE_SUM_G, APPEARANCE_SUM_R, APPEARANCE_SUM_BB, APPEARANCE_SUM_GG, APPEARANCE_SUM_RR, APPEARANCE_SUM_BG,
+ APPEARANCE_SUM_BR, APPEARANCE_SUM_GR, APPEARANCE_MODE_BIN, APPEARANCE_MODE_COUNT, APPEARANCE_WORDS) = range(13)
+APPEARANCE_BINS = 64
+(APPEARANCE_COUNT_COUNTED, APPEARANCE_COUNT_SKIPPED, APPEARANCE_COUNT_OUTSIDE, APPEARANCE_COUNT_VALUES, APPEARANCE_COUNT_STATUS,
+ APPEARANCE_COUNT_WORDS) = 0, 1, 2, 3, 7, 8
+APPEARANCE_NOTHING = 1
+APPEARANCE_MAX_SIDE = 32768
+FEATURE_APPEARANCE = 262144
 
 
 class Options(C.Structure):
@@ -359,6 +369,12 @@ SIGNATURES = {
                                        _u32p, _u32p]),
     "infur_frame_redact_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _sz, _vp, _vp, _sz, _vp,
                                            _vp, _u32p, _u32p]),
+    "infur_appearance": (C.c_int32, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _vp]),
+    "infur_appearance_dev": (C.c_int32, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _vp]),
+    "infur_frame_appearance": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp, _vp,
+                                           _u32p, _u32p, _vp, _u32, _vp, _vp]),
+    "infur_frame_appearance_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp, _vp,
+                                               _u32p, _u32p, _vp, _u32, _vp, _vp]),
     "infur_stream_create":(C.c_int32, [_vp, _u32, C.POINTER(_vp)]),
     "infur_stream_destroy": (None, [_vp]),
     "infur_stream_add_lane": (C.c_int32, [_vp, _vp]),

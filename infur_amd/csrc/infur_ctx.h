@@ -215,6 +215,9 @@ struct infur_ctx {
     // Redact (infur_redact.cpp): the two count words and the summed-area table, sixteen bytes a pixel; the class plane the frame calls
     // let Segments write when the caller does not want it; the host-pointer calls' staging.  Private like the above.
     infur::Buf st_redact, st_redact_plane, st_redact_io;
+    // Appearance (infur_appearance.cpp): the count words and the histogram of a call that wants none; the label plane the frame calls
+    // let Regions write when the caller does not want it; the host-pointer calls' staging.  Private like the above.
+    infur::Buf st_app, st_app_plane, st_app_io;
     // Tracks (infur_tracks.cpp): the live trackers of this context; infur_ctx_destroy releases their device memory and orphans them
     std::vector<infur_tracker*> trackers;
 

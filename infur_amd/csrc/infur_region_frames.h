@@ -1,5 +1,5 @@
 // infur_region_frames.h -- the host side the frame calls behind Regions share (Regions, Tracks, Anchors, Sieve, Shapes, Split,
-// Skeleton, Centrelines, Expand; internal, beside infur_egress.h): the capacity checks with their messages, the caller's arrays
+// Skeleton, Centrelines, Expand, Appearance; internal, beside infur_egress.h): the capacity checks with their messages, the caller's arrays
 // for Regions' and Anchors' products with the device arguments made of them and their read-back, and the planes a _dev form
 // borrows when the caller does not want what the stage behind reads.  The offsets are region_layout.h's.  Every frame path here
 // enqueues eagerly on the context's stream, and every buffer is private scratch no captured graph of the library can point into.

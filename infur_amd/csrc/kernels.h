@@ -402,6 +402,20 @@ hipError_t launch_redact(const uint8_t* frame, const void* plane, int elem_bytes
                          int invert, unsigned mode, unsigned size, unsigned passes, unsigned colour, void* scratch, uint8_t* out, unsigned* counts,
                          hipStream_t s);
 
+// Appearance (appearance.hip): what every value of the H x W plane (1- or 4-byte elements) looks like in the packed BGR frame[H * W * 3].
+// A pixel whose value equals skip_value (with skip) is skipped; a counted pixel with value v < rows adds to row v, any other only to
+// OUTSIDE.  table[rows x kAppearanceWords] u64 = {PIXELS, SUM_B, SUM_G, SUM_R, SUM_BB, SUM_GG, SUM_RR, SUM_BG, SUM_BR, SUM_GR, MODE_BIN,
+// MODE_COUNT}; hist[rows x kAppearanceBins] u32, bin = (R >> 6) << 4 | (G >> 6) << 2 | (B >> 6); counts[kAppearanceCountWords] =
+// {COUNTED, SKIPPED, OUTSIDE, VALUES, 0, 0, 0, STATUS} (each optional; device memory; none needs initialisation).  Sides 1 to
+// kAppearanceMaxSide.  scratch: appearance_scratch_bytes(rows, hist != nullptr) bytes the launches own for the call.  Stream-ordered,
+// three launches (clear, tiles, finish), no memset; no workgroup waits for another.
+constexpr int kAppearanceWords = 12, kAppearanceBins = 64, kAppearanceCountWords = 8;
+constexpr unsigned kAppearanceNothing = 1u;
+constexpr unsigned kAppearanceMaxSide = 32768;
+size_t appearance_scratch_bytes(unsigned rows, bool own_hist);
+hipError_t launch_appearance(const uint8_t* frame, const void* plane, int elem_bytes, unsigned H, unsigned W, int skip, unsigned skip_value, void* scratch,
+                             unsigned long long* table, unsigned rows, unsigned* hist, unsigned* counts, hipStream_t s);
+
 // Compare (compare.hip): two H x W planes (both sides at most 65535) of 1- or 4-byte elements against each other.  A pixel whose
 // a equals ignore_a (ign_a set) or whose b equals ignore_b (ign_b set) is ignored; a compared pixel with a >= rows_a or
 // b >= rows_b is outside; the rest are inside.  matrix[rows_a x rows_b] u32 counts the inside pixels per (a, b); rows_a_out and

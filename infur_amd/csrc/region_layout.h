@@ -1,6 +1,6 @@
 // region_layout.h -- the staging arithmetic the frame calls behind Regions share (infur_regions.cpp, infur_tracks.cpp,
 // infur_anchors.cpp, infur_sieve.cpp, infur_shapes.cpp, infur_split.cpp, infur_skeleton.cpp, infur_centrelines.cpp,
-// infur_expand.cpp): where Regions' products lie in a stage's staging buffer, and Anchors' behind them.  No HIP and no project
+// infur_expand.cpp, infur_appearance.cpp): where Regions' products lie in a stage's staging buffer, and Anchors' behind them.  No HIP and no project
 // header but egress_layout.h: plain g++ compiles it (tests/cpp/region_layout_test.cpp sweeps it under the sanitizers).
 // infur_region_frames.h ties the row constants to the public header's.
 #pragma once

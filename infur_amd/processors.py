@@ -1203,6 +1203,110 @@ class RedactFrame(NamedTuple):
 
 
 @dataclass
+class AppearanceCmd:
+    """``Appearance``'s command: ``rows`` rows of the table and the histogram (values at or above it count only as OUTSIDE), and the
+    value whose pixels are left out (``skip``: class 0, ``_lib.REGION_NONE``, ``_lib.TRACK_NONE``; None: every pixel counts)."""
+
+    rows: int = 256
+    skip: Optional[int] = None
+
+
+class AppearanceOut:
+    """``Appearance``'s ``&mut Output``: after ``advance`` ``table`` [rows, 12] u64 (``_lib.APPEARANCE_PIXELS`` ..), ``hist``
+    [rows, 64] u32 and ``counts`` [8] u32 (``_lib.APPEARANCE_COUNT_COUNTED`` ..), None where not wanted; ``nothing`` says that no
+    pixel was counted."""
+
+    def __init__(self, want_table: bool = True, want_hist: bool = True):
+        self.want_table, self.want_hist = want_table, want_hist
+        self.table = self.hist = self.counts = None
+
+    @property
+    def nothing(self) -> bool:
+        return bool(self.counts is not None and self.counts[_lib.APPEARANCE_COUNT_STATUS] & _lib.APPEARANCE_NOTHING)
+
+
+class Appearance(Processor):
+    """What every value of a plane looks like in the frame: per value of a class plane (u8) or a label / track plane (u32) the
+    pixel count, the colour sums and second moments of the packed BGR frame and its 64-bin joint colour histogram with its mode.
+
+    Command = ``AppearanceCmd``.  Input = (frame [H, W, 3] u8, plane [H, W] of u8 or u32); Output = ``AppearanceOut``.  Integers
+    throughout, identical from run to run; ``appearance_summary`` turns the rows into means, deviations and colours.
+    """
+
+    def __init__(self, ctx: Context, cmd: Optional[AppearanceCmd] = None):
+        self.ctx = ctx
+        self.cmd = cmd or AppearanceCmd()
+        self.dirty = True
+
+    def control(self, cmd: AppearanceCmd) -> "Appearance":
+        self.dirty = self.dirty or cmd != self.cmd
+        self.cmd = cmd
+        return self
+
+    def is_dirty(self) -> bool:
+        return self.dirty
+
+    def advance(self, inp: Tuple[np.ndarray, np.ndarray], out: AppearanceOut) -> None:
+        self.dirty = False
+        frame, plane = inp
+        frame = _check_bgr(frame)
+        if plane.ndim != 2 or plane.dtype.itemsize not in (1, 4) or plane.dtype.kind not in "ui" or plane.shape != frame.shape[:2]:
+            raise InfurError(_lib.E_SHAPE, f"expected an [H,W] plane of 1- or 4-byte integers for a {frame.shape} frame, got {plane.shape} {plane.dtype}")
+        plane = np.ascontiguousarray(plane)
+        h, w = plane.shape
+        rows = max(0, int(self.cmd.rows))
+        table = np.zeros((rows, _lib.APPEARANCE_WORDS), np.uint64) if out.want_table else None
+        hist = np.zeros((rows, _lib.APPEARANCE_BINS), np.uint32) if out.want_hist else None
+        counts = np.zeros(_lib.APPEARANCE_COUNT_WORDS, np.uint32)
+        skip = self.cmd.skip is not None
+        self.ctx.check(self.ctx.L.infur_appearance(self.ctx.h, frame.ctypes.data, plane.ctypes.data, plane.dtype.itemsize, h, w,
+                                                   _lib.APPEARANCE_SKIP if skip else 0, int(self.cmd.skip) if skip else 0, _ptr(table), rows, _ptr(hist),
+                                                   counts.ctypes.data))
+        out.table, out.hist, out.counts = table, hist, counts
+
+
+class AppearanceFrame(NamedTuple):
+    """``FramePath.advance_appearance``: ``RegionsFrame``'s fields, then Appearance's table [min(n, table_rows), 12] u64 and
+    histogram [min(n, table_rows), 64] u32, row i for region i (None where not wanted), and the eight counts"""
+
+    klass: Optional[np.ndarray]
+    conf: Optional[np.ndarray]
+    labels: Optional[np.ndarray]
+    table: Optional[np.ndarray]
+    n: Optional[int]
+    scaled: Optional[np.ndarray]
+    appearance_table: Optional[np.ndarray]
+    appearance_hist: Optional[np.ndarray]
+    appearance_counts: Optional[np.ndarray]
+
+
+def appearance_bin_colour(b: int) -> Tuple[int, int, int]:
+    """the centre colour (B, G, R) of histogram bin ``b``: each channel's two bits select a quarter of 0..255"""
+    return ((b & 3) * 64 + 32, (b >> 2 & 3) * 64 + 32, (b >> 4 & 3) * 64 + 32)
+
+
+def appearance_summary(table: np.ndarray, hist: Optional[np.ndarray] = None, names=None) -> List[dict]:
+    """Appearance's rows as records, one per value that has pixels: ``value`` (and ``name`` with ``names``), ``pixels``, ``mean``
+    and ``std`` (B, G, R; the population deviation, from the exact sums), ``dominant`` (the centre colour of the most frequent bin)
+    and, with ``hist``, ``histogram``: the 64 bins divided by the pixels."""
+    recs = []
+    for v, row in enumerate(np.asarray(table, np.uint64).reshape(-1, _lib.APPEARANCE_WORDS).tolist()):
+        n = row[_lib.APPEARANCE_PIXELS]
+        if not n:
+            continue
+        s, ss = row[_lib.APPEARANCE_SUM_B:_lib.APPEARANCE_SUM_R + 1], row[_lib.APPEARANCE_SUM_BB:_lib.APPEARANCE_SUM_RR + 1]
+        rec = {"value": v, "pixels": n, "mean": [round(x / n, 2) for x in s],
+               "std": [round(math.sqrt(max(n * q - x * x, 0)) / n, 2) for x, q in zip(s, ss)],  # (integers until the root)
+               "dominant": list(appearance_bin_colour(row[_lib.APPEARANCE_MODE_BIN]))}
+        if hist is not None:
+            rec["histogram"] = (np.asarray(hist[v], np.float64) / n).tolist()
+        if names is not None and v < len(names):
+            rec["name"] = names[v]
+        recs.append(rec)
+    return recs
+
+
+@dataclass
 class CompareCmd:
     """``Compare``'s command: ``Ignore(a, b)`` takes the pixels whose ``a`` (``b``) plane holds that value out of the comparison
     (None: every value is compared); ``pair_slots`` sizes the pair table of the table form (0: the library's 2^20)."""
@@ -2601,6 +2705,32 @@ class FramePath:
         if not self._loaded(rc):
             return RedactFrame(None, None, None, None, scaled)
         return RedactFrame(redacted, klass, conf, counts, scaled)
+
+    def advance_appearance(self, img: np.ndarray, factor: float = 1.0, decode: int = _lib.DECODE_RAW, connectivity: int = _lib.CONNECT_8,
+                           min_pixels: int = 0, flags: int = 0, table_rows: int = 1024, want_labels: bool = True, want_klass: bool = True,
+                           want_conf: bool = True, want_scaled: bool = False, want_hist: bool = True) -> AppearanceFrame:
+        """The fused path with every region's appearance, scale -> model -> Segments decode -> Regions -> Appearance of the scaled
+        frame by the label plane, in one call -> ``AppearanceFrame``; every result field is None when no model is loaded (``scaled``
+        is still produced)."""
+        img, w, h, f, ow, oh = self._front(img, factor)
+        npix = oh.value * ow.value
+        rows = max(0, min(int(table_rows), npix))
+        klass, conf = self._plane(ow, oh, want_klass), self._plane(ow, oh, want_conf)
+        labels = self._plane(ow, oh, want_labels, np.uint32)
+        table = np.zeros((rows, _lib.REGION_WORDS), np.uint64) if rows else None
+        scaled = self._plane(ow, oh, want_scaled, channels=3)
+        atable = np.zeros((rows, _lib.APPEARANCE_WORDS), np.uint64)
+        ahist = np.zeros((rows, _lib.APPEARANCE_BINS), np.uint32) if want_hist else None
+        counts = np.zeros(_lib.APPEARANCE_COUNT_WORDS, np.uint32)
+        n = C.c_uint32(0)
+        rc = self.ctx.L.infur_frame_appearance(self.ctx.h, img.ctypes.data, w, h, f, self.scale_mode, decode, connectivity, min_pixels, flags,
+                                               _ptr(klass), _ptr(conf), npix, _ptr(labels), npix * 4, _ptr(table), rows, C.addressof(n), _ptr(scaled),
+                                               C.byref(ow), C.byref(oh), atable.ctypes.data, rows, _ptr(ahist), counts.ctypes.data)
+        if not self._loaded(rc):
+            return AppearanceFrame(None, None, None, None, None, scaled, None, None, None)
+        k = min(n.value, rows)
+        return AppearanceFrame(klass, conf, labels, table[:k] if table is not None else None, n.value, scaled, atable[:k],
+                               ahist[:k] if ahist is not None else None, counts)
 
     def advance_split(self, img: np.ndarray, core: int, factor: float = 1.0, decode: int = _lib.DECODE_RAW, connectivity: int = _lib.CONNECT_8,
                       min_pixels: int = 0, flags: int = 0, table_rows: int = 1024, split_rows: int = 1024, pair_slots: int = 0,

@@ -75,6 +75,9 @@ skipped background; 0: as far as it takes), each open pixel going to its exact n
 gains ``"expand"`` (the frame's seeds, open, gained and left pixels and the largest distance to a region) and every region record
 ``"gained"`` and ``"margin"``, the distance it actually grew.  ``--expand-out FILE`` receives the grown u32 label planes.
 
+``--appearance`` (needs ``--regions``) describes every region by the pixels of the scaled frame under it (``infur_frame_appearance``):
+every region record gains ``"colour"``, its mean [b, g, r], and ``"dominant"``, the centre [b, g, r] of its most frequent colour bin.
+
 ``--redact-out FILE`` hides the pixels of the classes ``--redact-classes 15[,2,..]`` in the scaled frame on the device
 (``infur_frame_redact``) and writes the bgr24 frames to FILE, so that the output pipes back into ffmpeg: ``--redact-mode blur``
 (``--redact-size`` the radius, ``--redact-passes`` 1 to 3), ``pixelate`` (``--redact-size`` the cell) or ``fill`` (``--redact-colour
@@ -176,6 +179,7 @@ def main(argv=None) -> int:
     ap.add_argument("--expand-out", default="", help="raw u32 grown label planes, four bytes per pixel (needs --expand)")
     ap.add_argument("--centrelines-out", default="", help="per frame 8 u32 counts, the branch records, the vertices (needs --skeleton)")
     ap.add_argument("--centrelines-corners", action="store_true", help="keep only the vertices at which a branch turns (needs --centrelines-out)")
+    ap.add_argument("--appearance", action="store_true", help="add every region's mean and dominant colour, [b, g, r] (needs --regions)")
     ap.add_argument("--redact-out", default="", help="raw bgr24 frames with the pixels of --redact-classes hidden on the device")
     ap.add_argument("--redact-classes", default="", metavar="K[,K..]", help="the classes to hide (needs --redact-out)")
     ap.add_argument("--redact-mode", default="blur", choices=["blur", "pixelate", "fill"])
@@ -226,6 +230,14 @@ def main(argv=None) -> int:
                             (a.skeleton, "--skeleton")):
             if given:
                 ap.error(f"--expand does not combine with {name}: the fused expand call leaves no plane on the device for it")
+    if a.appearance:
+        if not a.regions:
+            ap.error("--appearance needs --regions")
+        for given, name in ((a.sieve is not None, "--sieve"), (a.shapes, "--shapes"), (a.tracks, "--tracks"), (a.runs_out, "--runs-out"),
+                            (a.outlines_out, "--outlines-out"), (a.anchors, "--anchors"), (a.truth, "--truth"), (a.split is not None, "--split"),
+                            (a.skeleton, "--skeleton"), (a.expand is not None, "--expand")):
+            if given:
+                ap.error(f"--appearance does not combine with {name}: the fused appearance call returns Regions' products and the colours")
     if a.split_out and a.split is None:
         ap.error("--split-out needs --split")
     if a.split is not None:
@@ -301,7 +313,7 @@ def main(argv=None) -> int:
     from . import _lib
     from .app import RawVideoSource, VideoProcError
     from .processors import (Compare, CompareOut, confusion_summary, sieve_summary, Context, Coverage, CoverageOut, FramePath, Model, ModelCmd, Outlines, OutlinesOut, Runs, RunsOut, SegmentsFrame, Simplify, SimplifyOut,
-                             class_summary, expand_summary, outlines_polygons, polygon_fidelity, region_summary, shape_summary, skeleton_summary, split_core, split_summary, tolerance_to_tol16,
+                             appearance_summary, class_summary, expand_summary, outlines_polygons, polygon_fidelity, region_summary, shape_summary, skeleton_summary, split_core, split_summary, tolerance_to_tol16,
                              track_summary)
 
     tol16 = tolerance_to_tol16(a.outlines_tolerance) if a.outlines_tolerance is not None else None
@@ -348,7 +360,7 @@ def main(argv=None) -> int:
         redact_cmd = {"blur": RedactCmd.Blur(redact_classes, a.redact_size, a.redact_passes, a.redact_invert),
                       "pixelate": RedactCmd.Pixelate(redact_classes, a.redact_size, a.redact_invert),
                       "fill": RedactCmd.Fill(redact_classes, colour, a.redact_invert)}[a.redact_mode]
-    if a.regions and (a.sieve is not None or a.shapes or a.split is not None or a.skeleton or a.expand is not None):
+    if a.regions and (a.sieve is not None or a.shapes or a.split is not None or a.skeleton or a.expand is not None or a.appearance):
         flags = _lib.REGIONS_SKIP_BACKGROUND if a.skip_background else 0
     elif a.regions:
         oh, ow = _out_dims(ctx, a.width, a.height, a.scale)
@@ -384,6 +396,11 @@ def main(argv=None) -> int:
         elif a.expand is not None:  # scale -> model -> decode -> Regions -> Expand of the label plane with the pixels of no region open, in one call
             r = fp.advance_expand(img, a.expand, a.scale, decode, a.connectivity, a.min_pixels, flags, table_rows=max(0, a.max_regions),
                                   want_labels=freg is not None, want_klass=True, want_conf=True, want_grown=fexp is not None, want_dist2=False)
+            s = SegmentsFrame(r.klass, r.conf, _class_stats(r.klass, r.conf, model.get_info().num_classes), None, None)
+            labels, table, nreg = r.labels, r.table, r.n
+        elif a.appearance:  # scale -> model -> decode -> Regions -> Appearance of the scaled frame by the label plane, in one call
+            r = fp.advance_appearance(img, a.scale, decode, a.connectivity, a.min_pixels, flags, table_rows=max(0, a.max_regions),
+                                      want_labels=freg is not None, want_klass=True, want_conf=True, want_hist=False)
             s = SegmentsFrame(r.klass, r.conf, _class_stats(r.klass, r.conf, model.get_info().num_classes), None, None)
             labels, table, nreg = r.labels, r.table, r.n
         elif fred is not None:  # scale -> model -> decode -> Redact of the scaled frame by the class plane, in one call
@@ -495,6 +512,14 @@ def main(argv=None) -> int:
         if fred is not None:
             rec["redact"] = {"selected": int(r.counts[_lib.REDACT_COUNT_SELECTED]), "mode": a.redact_mode}
             fred.write(memoryview(r.redacted).cast("B"))
+        if a.appearance:
+            rec["n_regions"], rec["regions"] = nreg, region_summary(table, nreg, ow, oh)
+            looks = {e["value"]: e for e in appearance_summary(r.appearance_table if r.appearance_table is not None else ())}
+            for region in rec["regions"]:
+                e = looks.get(region["id"])
+                region["colour"], region["dominant"] = ([int(round(v)) for v in e["mean"]], e["dominant"]) if e else (None, None)
+            if freg is not None:
+                freg.write(memoryview(labels).cast("B"))
         if a.expand is not None:
             ec = [int(v) for v in r.expand_counts]
             rec["n_regions"], rec["regions"] = nreg, region_summary(table, nreg, ow, oh)

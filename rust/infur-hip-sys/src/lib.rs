@@ -408,6 +408,32 @@ pub const INFUR_REDACT_MAX_SIDE: u32 = 32768;
 pub const INFUR_REDACT_MAX_PIXELS: u32 = 16777216;
 /// bit of `infur_features()`: the Redact calls below exist
 pub const INFUR_FEATURE_REDACT: u32 = 131072;
+/// Appearance: the flag, the words of a row, the bins, the words of the counts, the status bit, the limit
+pub const INFUR_APPEARANCE_SKIP: u32 = 1;
+pub const INFUR_APPEARANCE_PIXELS: u32 = 0;
+pub const INFUR_APPEARANCE_SUM_B: u32 = 1;
+pub const INFUR_APPEARANCE_SUM_G: u32 = 2;
+pub const INFUR_APPEARANCE_SUM_R: u32 = 3;
+pub const INFUR_APPEARANCE_SUM_BB: u32 = 4;
+pub const INFUR_APPEARANCE_SUM_GG: u32 = 5;
+pub const INFUR_APPEARANCE_SUM_RR: u32 = 6;
+pub const INFUR_APPEARANCE_SUM_BG: u32 = 7;
+pub const INFUR_APPEARANCE_SUM_BR: u32 = 8;
+pub const INFUR_APPEARANCE_SUM_GR: u32 = 9;
+pub const INFUR_APPEARANCE_MODE_BIN: u32 = 10;
+pub const INFUR_APPEARANCE_MODE_COUNT: u32 = 11;
+pub const INFUR_APPEARANCE_WORDS: u32 = 12;
+pub const INFUR_APPEARANCE_BINS: u32 = 64;
+pub const INFUR_APPEARANCE_COUNT_COUNTED: u32 = 0;
+pub const INFUR_APPEARANCE_COUNT_SKIPPED: u32 = 1;
+pub const INFUR_APPEARANCE_COUNT_OUTSIDE: u32 = 2;
+pub const INFUR_APPEARANCE_COUNT_VALUES: u32 = 3;
+pub const INFUR_APPEARANCE_COUNT_STATUS: u32 = 7;
+pub const INFUR_APPEARANCE_COUNT_WORDS: u32 = 8;
+pub const INFUR_APPEARANCE_NOTHING: u32 = 1;
+pub const INFUR_APPEARANCE_MAX_SIDE: u32 = 32768;
+/// bit of `infur_features()`: the Appearance calls below exist
+pub const INFUR_FEATURE_APPEARANCE: u32 = 262144;
 
 extern "C" {
     pub fn infur_abi_version() -> u32;
@@ -824,4 +850,21 @@ extern "C" {
                                   d_select: *const c_void, select_rows: u32, redact_flags: u32, redact_mode: u32, size: u32, passes: u32,
                                   colour: u32, d_redacted: *mut c_void, redacted_capacity: usize, d_klass: *mut c_void, d_conf: *mut c_void,
                                   plane_capacity: usize, d_counts: *mut c_void, d_scaled_bgr: *mut c_void, ow: *mut u32, oh: *mut u32) -> i32;
+    // Appearance: per value of a plane the colour sums, second moments and joint histogram of the BGR frame
+    pub fn infur_appearance(c: *mut infur_ctx, frame: *const u8, plane: *const c_void, elem_bytes: u32, h: u32, w: u32, flags: u32,
+                            skip_value: u32, table: *mut u64, table_rows: u32, hist: *mut u32, counts: *mut u32) -> i32;
+    pub fn infur_appearance_dev(c: *mut infur_ctx, d_frame: *const c_void, d_plane: *const c_void, elem_bytes: u32, h: u32, w: u32,
+                                flags: u32, skip_value: u32, d_table: *mut c_void, table_rows: u32, d_hist: *mut c_void,
+                                d_counts: *mut c_void) -> i32;
+    pub fn infur_frame_appearance(c: *mut infur_ctx, bgr: *const u8, w: u32, h: u32, factor: f32, scale_mode: u32, decode: u32,
+                                  connectivity: u32, min_pixels: u32, region_flags: u32, klass: *mut u8, conf: *mut u8,
+                                  plane_capacity: usize, labels: *mut u32, labels_capacity: usize, table: *mut u64, table_rows: u32,
+                                  n_regions: *mut u32, scaled_bgr: *mut u8, ow: *mut u32, oh: *mut u32, appearance_table: *mut u64,
+                                  appearance_rows: u32, appearance_hist: *mut u32, appearance_counts: *mut u32) -> i32;
+    pub fn infur_frame_appearance_dev(c: *mut infur_ctx, d_bgr: *const c_void, w: u32, h: u32, factor: f32, scale_mode: u32, decode: u32,
+                                      connectivity: u32, min_pixels: u32, region_flags: u32, d_klass: *mut c_void, d_conf: *mut c_void,
+                                      plane_capacity: usize, d_labels: *mut c_void, labels_capacity: usize, d_table: *mut c_void,
+                                      table_rows: u32, d_n_regions: *mut c_void, d_scaled_bgr: *mut c_void, ow: *mut u32, oh: *mut u32,
+                                      d_appearance_table: *mut c_void, appearance_rows: u32, d_appearance_hist: *mut c_void,
+                                      d_appearance_counts: *mut c_void) -> i32;
 }

@@ -827,6 +827,78 @@ impl Processor for HipRedact {
     }
 }
 
+// ---------------------------------------------------------------- Appearance (colour sums and histogram per value of a plane)
+/// What `HipAppearance` produces for `rows` values: `table` rows of `INFUR_APPEARANCE_WORDS` words, `hist` rows of
+/// `INFUR_APPEARANCE_BINS` bins (either empty when not wanted) and the `INFUR_APPEARANCE_COUNT_WORDS` counts.
+pub struct AppearanceOut {
+    pub want_table: bool,
+    pub want_hist: bool,
+    pub table: Vec<u64>,
+    pub hist: Vec<u32>,
+    pub counts: [u32; sys::INFUR_APPEARANCE_COUNT_WORDS as usize],
+}
+impl Default for AppearanceOut {
+    fn default() -> Self {
+        Self { want_table: true, want_hist: true, table: Vec::new(), hist: Vec::new(), counts: [0; sys::INFUR_APPEARANCE_COUNT_WORDS as usize] }
+    }
+}
+impl AppearanceOut {
+    /// no pixel reached a row
+    pub fn nothing(&self) -> bool { self.counts[sys::INFUR_APPEARANCE_COUNT_STATUS as usize] & sys::INFUR_APPEARANCE_NOTHING != 0 }
+    /// the mean (B, G, R) of value `v`; None where it has no pixel
+    pub fn mean(&self, v: usize) -> Option<[f64; 3]> {
+        let row = &self.table[v * sys::INFUR_APPEARANCE_WORDS as usize..][..sys::INFUR_APPEARANCE_WORDS as usize];
+        let n = row[sys::INFUR_APPEARANCE_PIXELS as usize];
+        if n == 0 { return None; }
+        Some([row[1] as f64 / n as f64, row[2] as f64 / n as f64, row[3] as f64 / n as f64])
+    }
+}
+/// `rows` rows of the table and the histogram; `skip`: the value whose pixels are left out
+pub struct AppearanceCmd { pub rows: u32, pub skip: Option<u32> }
+/// The frame and the plane that keys its pixels, both `size` = [w, h]
+pub struct AppearanceInput { pub frame: Vec<u8>, pub plane: RunsPlane }
+/// What every value of a plane looks like in the packed BGR frame.  Integer results, identical from run to run.
+pub struct HipAppearance { ctx: Rc<Ctx>, rows: u32, skip: Option<u32>, dirty: bool }
+impl HipAppearance {
+    pub fn new(ctx: Rc<Ctx>) -> Self { Self { ctx, rows: 256, skip: None, dirty: true } }
+}
+impl Processor for HipAppearance {
+    type Command = AppearanceCmd;
+    type ControlError = HipError;
+    type Input = AppearanceInput;
+    type Output = AppearanceOut;
+    type ProcessResult = Result<(), HipError>;
+
+    fn control(&mut self, cmd: AppearanceCmd) -> Result<&mut Self, HipError> {
+        (self.rows, self.skip) = (cmd.rows, cmd.skip);
+        self.dirty = true;
+        Ok(self)
+    }
+    fn is_dirty(&self) -> bool { self.dirty }
+    fn advance(&mut self, inp: &AppearanceInput, out: &mut AppearanceOut) -> Result<(), HipError> {
+        self.dirty = false;
+        let [w, h] = inp.plane.size;
+        let (ptr, len, elem_bytes) = match &inp.plane.data {
+            RunsPlaneData::U8(p) => (p.as_ptr() as *const std::ffi::c_void, p.len(), 1u32),
+            RunsPlaneData::U32(p) => (p.as_ptr() as *const std::ffi::c_void, p.len(), 4u32),
+        };
+        if len != w * h || inp.frame.len() != w * h * 3 { return Err(HipError::status(sys::INFUR_E_SHAPE)); }
+        let rows = self.rows as usize;
+        out.table.clear();
+        out.table.resize(if out.want_table { rows * sys::INFUR_APPEARANCE_WORDS as usize } else { 0 }, 0);
+        out.hist.clear();
+        out.hist.resize(if out.want_hist { rows * sys::INFUR_APPEARANCE_BINS as usize } else { 0 }, 0);
+        let rc = unsafe {
+            sys::infur_appearance(self.ctx.0, inp.frame.as_ptr(), ptr, elem_bytes, h as u32, w as u32,
+                                  if self.skip.is_some() { sys::INFUR_APPEARANCE_SKIP } else { 0 }, self.skip.unwrap_or(0),
+                                  if out.want_table { out.table.as_mut_ptr() } else { std::ptr::null_mut() }, self.rows,
+                                  if out.want_hist { out.hist.as_mut_ptr() } else { std::ptr::null_mut() }, out.counts.as_mut_ptr())
+        };
+        if rc != sys::INFUR_OK { return Err(HipError::from_ctx(&self.ctx, rc)); }
+        Ok(())
+    }
+}
+
 // ---------------------------------------------------------------- Compare (confusion matrix, best partner per value)
 /// What `HipCompare` produces for `rows_a` x `rows_b` values: `matrix` row-major (`matrix[i * rows_b + j]`: the pixels with a == i
 /// and b == j), `a` and `b` rows of `INFUR_COMPARE_WORDS` words (PIXELS, PARTNER, INTER, UNION) per value of either plane --
