@@ -1901,7 +1901,102 @@ int32_t infur_frame_appearance_dev(infur_ctx* ctx, const void* d_bgr, uint32_t w
                                    void* d_appearance_table, uint32_t appearance_rows, void* d_appearance_hist,
                                    void* d_appearance_counts);
 
-/* ---- streaming (infur/src/main.rs:27-99,105): bounded queue, copies overlapped with compute ----
+/* ---- Matte and Composite: an edge-aware alpha of chosen values, and the frame laid over a backdrop with it ----
+ * Every stage above treats the class plane as the truth about where an object ends.  It is not: the logits leave the network at one
+ * eighth of the frame and are up-sampled, so the argmax border is a smooth blob that ignores the picture's own edges, and Redact
+ * hides what a mask marks with a hard edge.  Matte makes the soft alpha that follows the edges of the frame (a joint bilateral
+ * filter of the mask guided by the picture, what a host otherwise runs on the CPU after pulling frame and plane across PCIe);
+ * Composite lays the frame over a colour or another picture with it, or cuts it out: background replacement, a cut-out with alpha,
+ * background blur without a seam.  Announced by infur_features() & INFUR_FEATURE_MATTE (INFUR_ABI_VERSION does not move).
+ *
+ * MATTE, INPUTS.  `frame`: h x w x 3 bytes, B G R.  `plane`: h x w elements of elem_bytes = 1 or 4; h and w 1 to
+ * INFUR_MATTE_MAX_SIDE.  `select`: select_rows bytes, used exactly as Redact uses it: a pixel with value v is SELECTED iff
+ * v < select_rows && select[v] != 0, a value beyond the table is not selected and is counted OUTSIDE, and INFUR_MATTE_INVERT in
+ * `flags` flips the answer afterwards.  select may be NULL when select_rows is 0.  `conf`: h x w bytes, read only with
+ * INFUR_MATTE_CONF (any other flag bit is INFUR_E_INVALID_ARG).  `radius` 1 to INFUR_MATTE_MAX_RADIUS, `sigma` 1 to 255.
+ *
+ * THE RULE, exact integers throughout:
+ *   m(q)       0 for an unselected pixel; for a selected one 255, or conf[q] with INFUR_MATTE_CONF
+ *   d(p, q)    |B_p - B_q| + |G_p - G_q| + |R_p - R_q|, 0 to 765
+ *   weight(d)  (4096 * sigma^2) / (sigma^2 + d^2), rounded down: 4096 at the centre tap, so no denominator is zero.
+ *              sigma 12: 4096, 2048, 819, 58, 1 at d = 0, 12, 24, 100, 765
+ *   window(p)  every q with |dx|, |dy| <= radius inside the frame: clipped at the borders, not padded
+ *   alpha(p)   (2N + D) / (2D) rounded down, N = sum of weight * m and D = sum of weight over the window
+ * N <= 33^2 * 4096 * 255 = 1 137 438 720 and 2N + D <= 2 279 337 984 < 2^32: every sum is a uint32_t, but not an int32_t.  Wherever
+ * every m in a pixel's window is the same c, alpha is c: most of a frame.  A function of the inputs alone, identical bytes from run
+ * to run.  Left out: spatial weights inside the window, radii above 16, iterating the filter, a trimap.
+ *
+ * MATTE, OUTPUTS, each optional (NULL = not wanted; neither is INFUR_E_INVALID_ARG), none needs initialisation:
+ *   alpha   h*w bytes.  It may overlap none of the inputs
+ *   counts  INFUR_MATTE_COUNT_WORDS uint32_t: SELECTED, OUTSIDE (the pixels whose value is >= select_rows, counted before INVERT),
+ *           CLEAR (alpha 0), SOFT (1 to 254), OPAQUE (255), two zeros, STATUS (INFUR_MATTE_NOTHING: nothing is selected).
+ *           CLEAR + SOFT + OPAQUE = h * w
+ * The checks come in this order: elem_bytes, flags, radius, sigma, the sides, a NULL select with rows, nothing wanted, a NULL plane
+ * or frame, INFUR_MATTE_CONF without conf.  No output is touched when a call is rejected.
+ *
+ * EXAMPLE.  The 1 x 6 frame with B = 10 10 10 200 200 200 (G = R = 0), the byte plane 1 1 1 1 0 0 and select = {0, 1}: the mask
+ * ends one pixel behind the picture's edge.  radius 1, sigma 12 (weight(190) = 16):
+ *   alpha            255 255 255 128 85 0    pixel 3: D = 16 + 4096 + 4096, N = 255 (16 + 4096), (2N + D) / (2D) = 128
+ *   counts           SELECTED 4, OUTSIDE 0, CLEAR 1, SOFT 2, OPAQUE 3, 0, 0, STATUS 0
+ *   radius 2         255 255 255 85 85 85    with INVERT, radius 1: 0 0 0 127 170 255
+ *   with CONF        conf = 200 200 200 200 7 7: 200 200 200 100 67 0
+ *   select = {0}     value 1 lies beyond the table: alpha 0 everywhere, counts 0, 4, 6, 0, 0, 0, 0, INFUR_MATTE_NOTHING
+ *
+ * COMPOSITE.  `frame` and `alpha` as above; `out` = the frame over a backdrop:
+ *   INFUR_COMPOSITE_COLOUR  the backdrop is `colour` (B = bits 0-7, G = bits 8-15, R = bits 16-23, as Redact's FILL reads it)
+ *   INFUR_COMPOSITE_IMAGE   the backdrop is the packed BGR picture `back` of the same h x w
+ *   INFUR_COMPOSITE_CUTOUT  out holds four bytes a pixel, B G R alpha, not premultiplied; there is no backdrop
+ * In the first two modes each channel is (alpha * F + (255 - alpha) * B + 127) / 255 rounded down, out is h*w*3 bytes and may be the
+ * frame itself (in place); any other overlap of the two, and any overlap of a cut-out with the frame, is INFUR_E_INVALID_ARG.
+ * Over blue (colour 255) the B channel above with alpha 0 1 127 128 254 255 reads 255 254 133 227 200 200.
+ * infur_redact_dev (INFUR_REDACT_BLUR, INFUR_REDACT_INVERT) into a second buffer, then infur_composite_dev (INFUR_COMPOSITE_IMAGE)
+ * with that buffer as `back`, is background blur with a soft seam and no halo of the foreground.
+ * The checks: mode, the sides, a NULL frame, alpha or out, INFUR_COMPOSITE_IMAGE without back, the overlap. */
+enum { INFUR_MATTE_INVERT = 1, INFUR_MATTE_CONF = 2 };
+enum { INFUR_MATTE_COUNT_SELECTED = 0, INFUR_MATTE_COUNT_OUTSIDE = 1, INFUR_MATTE_COUNT_CLEAR = 2, INFUR_MATTE_COUNT_SOFT = 3,
+       INFUR_MATTE_COUNT_OPAQUE = 4, INFUR_MATTE_COUNT_STATUS = 7, INFUR_MATTE_COUNT_WORDS = 8 };
+enum { INFUR_MATTE_NOTHING = 1 };
+enum { INFUR_MATTE_MAX_RADIUS = 16, INFUR_MATTE_MAX_SIDE = 32768 };
+enum { INFUR_COMPOSITE_COLOUR = 0, INFUR_COMPOSITE_IMAGE = 1, INFUR_COMPOSITE_CUTOUT = 2 };
+enum { INFUR_FEATURE_MATTE = 524288 };
+
+/* on a given frame and plane, host pointers */
+int32_t infur_matte(infur_ctx* ctx, const uint8_t* frame, const void* plane, uint32_t elem_bytes, uint32_t h, uint32_t w,
+                    const uint8_t* select, uint32_t select_rows, uint32_t flags, const uint8_t* conf, uint32_t radius, uint32_t sigma,
+                    uint8_t* alpha, uint32_t* counts);
+/* device pointers throughout, the table included; enqueued on the context's stream as launches only -- no memset, nothing read
+ * back: a prepare launch (the count words and the weight table of this sigma), the tiles, and a counts launch where counts are
+ * wanted.  The call never synchronises and is capturable after one call outside the capture, which allocates the scratch (under
+ * 2 KB, owned by the context). */
+int32_t infur_matte_dev(infur_ctx* ctx, const void* d_frame, const void* d_plane, uint32_t elem_bytes, uint32_t h, uint32_t w,
+                        const void* d_select, uint32_t select_rows, uint32_t flags, const void* d_conf, uint32_t radius, uint32_t sigma,
+                        void* d_alpha, void* d_counts);
+int32_t infur_composite(infur_ctx* ctx, const uint8_t* frame, const uint8_t* alpha, uint32_t h, uint32_t w, uint32_t mode,
+                        const uint8_t* back, uint32_t colour, uint8_t* out);
+/* one launch, no scratch: capturable as it is */
+int32_t infur_composite_dev(infur_ctx* ctx, const void* d_frame, const void* d_alpha, uint32_t h, uint32_t w, uint32_t mode,
+                            const void* d_back, uint32_t colour, void* d_out);
+/* The fused frame path with the matte: scale -> model -> Segments decode(out[0]) -> Matte of the scaled frame by the class plane
+ * (with INFUR_MATTE_CONF: weighted by the decode's confidence plane) -> Composite where `composed` is wanted, in one call.  `back`
+ * (INFUR_COMPOSITE_IMAGE only) has the scaled size.  `composed` takes ow*oh*3 bytes, ow*oh*4 for a cut-out (less is
+ * INFUR_E_CAPACITY, checked once a model is loaded); alpha, klass and conf take plane_capacity bytes each.  Every output is
+ * optional; at least one of alpha, composed, klass, conf and counts must be given.  The planes go to scratch of the library's own
+ * when the caller does not want them; d_composed may be d_scaled_bgr (in place; not a cut-out).  Every check and error behind
+ * Matte's and Composite's own argument checks is infur_frame_segments' own: with no model loaded the Scale stage still runs and the
+ * call returns INFUR_E_MODEL_NOT_LOADED.  The calls always enqueue eagerly and leave the graphs cached for infur_frame_advance_dev
+ * alone.  Left out: the stream ring, batch and group calls. */
+int32_t infur_frame_matte(infur_ctx* ctx, const uint8_t* bgr, uint32_t w, uint32_t h, float factor, uint32_t scale_mode, uint32_t decode,
+                          const uint8_t* select, uint32_t select_rows, uint32_t matte_flags, uint32_t radius, uint32_t sigma,
+                          uint32_t composite_mode, const uint8_t* back, uint32_t colour, uint8_t* alpha, uint8_t* composed,
+                          size_t composed_capacity, uint8_t* klass, uint8_t* conf, size_t plane_capacity, uint32_t* counts,
+                          uint8_t* scaled_bgr, uint32_t* ow, uint32_t* oh);
+int32_t infur_frame_matte_dev(infur_ctx* ctx, const void* d_bgr, uint32_t w, uint32_t h, float factor, uint32_t scale_mode,
+                              uint32_t decode, const void* d_select, uint32_t select_rows, uint32_t matte_flags, uint32_t radius,
+                              uint32_t sigma, uint32_t composite_mode, const void* d_back, uint32_t colour, void* d_alpha,
+                              void* d_composed, size_t composed_capacity, void* d_klass, void* d_conf, size_t plane_capacity,
+                              void* d_counts, void* d_scaled_bgr, uint32_t* ow, uint32_t* oh);
+
+/* ---- streaming(infur/src/main.rs:27-99,105): bounded queue, copies overlapped with compute ----
  * The reference back-pressures its producer with sync_channel(2) (main.rs:105); a stream
  * here is a ring of `depth` pinned + device slots.  submit() copies the caller's frame into a
  * pinned slot and enqueues H2D -> scale/model/decode -> D2H on three HIP streams (so frame

@@ -679,6 +679,67 @@ private:
     bool dirty_ = true;
 };
 
+/// What `Matte` produces: the alpha plane (`width * height` bytes; empty with `want_alpha` false) and the eight counts.
+struct MatteOut {
+    bool want_alpha = true;  // what to provide
+    uint32_t width = 0, height = 0;
+    std::vector<uint8_t> alpha;
+    uint32_t counts[INFUR_MATTE_COUNT_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
+    bool nothing() const { return (counts[INFUR_MATTE_COUNT_STATUS] & INFUR_MATTE_NOTHING) != 0; }
+};
+
+/// The soft alpha of the pixels a plane selects (value v is selected iff v < select.size() && select[v] != 0; the opposite with
+/// `invert`), following the edges of the packed BGR frame; `compose` lays the frame over a colour or a picture with it, or cuts it
+/// out.  Integer results, identical from run to run.  Command = what is foreground and how far the filter looks; Input = a frame
+/// and a plane of uint8_t or uint32_t (and a confidence plane with `use_conf`), Output = MatteOut.
+class Matte {
+public:
+    struct Cmd {
+        std::vector<uint8_t> select;
+        uint32_t radius = 8, sigma = 24;
+        bool invert = false, use_conf = false;
+    };
+    explicit Matte(Context& c) : c_(c) {}
+    Status control(Cmd cmd) {
+        cmd_ = std::move(cmd);
+        dirty_ = true;
+        return INFUR_OK;
+    }
+    bool is_dirty() const { return dirty_; }
+    Status advance(const std::vector<uint8_t>& frame, const std::vector<uint8_t>& plane, const std::vector<uint8_t>& conf, uint32_t height,
+                   uint32_t width, MatteOut& out) {
+        return run(frame, plane.data(), plane.size(), 1, conf, height, width, out);
+    }
+    Status advance(const std::vector<uint8_t>& frame, const std::vector<uint32_t>& plane, const std::vector<uint8_t>& conf, uint32_t height,
+                   uint32_t width, MatteOut& out) {
+        return run(frame, plane.data(), plane.size(), 4, conf, height, width, out);
+    }
+    /// `out` = the frame over `back` (INFUR_COMPOSITE_IMAGE) or `colour` by `alpha`: three bytes a pixel, four for a cut-out
+    Status compose(const std::vector<uint8_t>& frame, const std::vector<uint8_t>& alpha, uint32_t height, uint32_t width, uint32_t mode,
+                   const std::vector<uint8_t>& back, uint32_t colour, std::vector<uint8_t>& out) {
+        const size_t n = (size_t)width * height;
+        if (alpha.size() != n || frame.size() != n * 3 || (mode == INFUR_COMPOSITE_IMAGE && back.size() != n * 3)) return INFUR_E_SHAPE;
+        out.assign(n * (mode == INFUR_COMPOSITE_CUTOUT ? 4 : 3), 0);
+        return infur_composite(c_.get(), frame.data(), alpha.data(), height, width, mode, back.empty() ? nullptr : back.data(), colour, out.data());
+    }
+
+private:
+    Status run(const std::vector<uint8_t>& frame, const void* plane, size_t elems, uint32_t elem_bytes, const std::vector<uint8_t>& conf,
+               uint32_t height, uint32_t width, MatteOut& out) {
+        dirty_ = false;
+        if (elems != (size_t)width * height || frame.size() != elems * 3 || (cmd_.use_conf && conf.size() != elems)) return INFUR_E_SHAPE;
+        out.width = width;
+        out.height = height;
+        out.alpha.assign(out.want_alpha ? elems : 0, 0);
+        return infur_matte(c_.get(), frame.data(), plane, elem_bytes, height, width, cmd_.select.empty() ? nullptr : cmd_.select.data(),
+                           (uint32_t)cmd_.select.size(), (cmd_.invert ? INFUR_MATTE_INVERT : 0) | (cmd_.use_conf ? INFUR_MATTE_CONF : 0),
+                           cmd_.use_conf ? conf.data() : nullptr, cmd_.radius, cmd_.sigma, out.want_alpha ? out.alpha.data() : nullptr, out.counts);
+    }
+    Context& c_;
+    Cmd cmd_;
+    bool dirty_ = true;
+};
+
 /// What `Compare` produces for `rows_a` x `rows_b` values: `matrix` row-major (pixels with a == i and b == j), `a` and `b` rows of
 /// INFUR_COMPARE_WORDS words per value of either plane ((0, INFUR_COMPARE_NONE, 0, 0): no compared pixel holds the value) and the
 /// INFUR_COMPARE_COUNT_WORDS counts.

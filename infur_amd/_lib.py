@@ -169,6 +169,16 @@ APPEARANCE_BINS = 64
 APPEARANCE_NOTHING = 1
 APPEARANCE_MAX_SIDE = 32768
 FEATURE_APPEARANCE = 262144
+# Matte and Composite (infur_matte / infur_composite / infur_frame_matte): the flags, the words of the counts, the status bit, the
+# limits, the modes; the output tile of a workgroup (kernels.h: kMatteTileH, kMatteTileW), for tests that place their shapes
+MATTE_INVERT, MATTE_CONF = 1, 2
+(MATTE_COUNT_SELECTED, MATTE_COUNT_OUTSIDE, MATTE_COUNT_CLEAR, MATTE_COUNT_SOFT, MATTE_COUNT_OPAQUE, MATTE_COUNT_STATUS,
+ MATTE_COUNT_WORDS) = 0, 1, 2, 3, 4, 7, 8
+MATTE_NOTHING = 1
+MATTE_MAX_RADIUS, MATTE_MAX_SIDE = 16, 32768
+MATTE_TILE_H, MATTE_TILE_W = 16, 64
+COMPOSITE_COLOUR, COMPOSITE_IMAGE, COMPOSITE_CUTOUT = 0, 1, 2
+FEATURE_MATTE = 524288
 
 
 class Options(C.Structure):
@@ -375,6 +385,14 @@ SIGNATURES = {
                                            _u32p, _u32p, _vp, _u32, _vp, _vp]),
     "infur_frame_appearance_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp, _vp,
                                                _u32p, _u32p, _vp, _u32, _vp, _vp]),
+    "infur_matte": (C.c_int32, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _u32, _u32, _vp, _u32, _u32, _vp, _vp]),
+    "infur_matte_dev": (C.c_int32, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _u32, _u32, _vp, _u32, _u32, _vp, _vp]),
+    "infur_composite": (C.c_int32, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp]),
+    "infur_composite_dev": (C.c_int32, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp]),
+    "infur_frame_matte": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _vp, _sz, _vp, _vp, _sz,
+                                      _vp, _vp, _u32p, _u32p]),
+    "infur_frame_matte_dev": (C.c_int32, [_vp, _vp, _u32, _u32, _f, _u32, _u32, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _vp, _sz, _vp, _vp,
+                                          _sz, _vp, _vp, _u32p, _u32p]),
     "infur_stream_create":(C.c_int32, [_vp, _u32, C.POINTER(_vp)]),
     "infur_stream_destroy": (None, [_vp]),
     "infur_stream_add_lane": (C.c_int32, [_vp, _vp]),

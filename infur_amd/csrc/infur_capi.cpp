@@ -1157,7 +1157,8 @@ void infur_ctx_destroy(infur_ctx* c) {
                    &c->st_shapes_plane, &c->st_shapes_poly, &c->st_shapes_io, &c->st_raster, &c->st_raster_io, &c->st_split, &c->st_split_plane,
                    &c->st_split_io, &c->st_skel, &c->st_skel_plane, &c->st_skel_io, &c->st_cl,
                    &c->st_cl_plane, &c->st_cl_io, &c->st_exp, &c->st_exp_plane, &c->st_exp_io, &c->st_redact,
-                   &c->st_redact_plane, &c->st_redact_io, &c->st_app, &c->st_app_plane, &c->st_app_io})
+                   &c->st_redact_plane, &c->st_redact_io, &c->st_app, &c->st_app_plane, &c->st_app_io,
+                   &c->st_matte, &c->st_matte_plane, &c->st_matte_io})
         if (b->p) (void)hipFree(b->p);
     prof_reset(c);
     for (auto e : c->ev_free) (void)hipEventDestroy(e);

@@ -218,6 +218,9 @@ struct infur_ctx {
     // Appearance (infur_appearance.cpp): the count words and the histogram of a call that wants none; the label plane the frame calls
     // let Regions write when the caller does not want it; the host-pointer calls' staging.  Private like the above.
     infur::Buf st_app, st_app_plane, st_app_io;
+    // Matte (infur_matte.cpp): the count words and the weight table; the class, confidence and alpha planes the frame calls keep when
+    // the caller does not want them; the host-pointer calls' staging (Composite's too).  Private like the above.
+    infur::Buf st_matte, st_matte_plane, st_matte_io;
     // Tracks (infur_tracks.cpp): the live trackers of this context; infur_ctx_destroy releases their device memory and orphans them
     std::vector<infur_tracker*> trackers;
 

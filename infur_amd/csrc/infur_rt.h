@@ -21,6 +21,7 @@
 //   infur_expand.cpp        Expand (every open pixel takes the value of its exact nearest seed, within a reach: the nearest-seed transform): C entry points
 //   infur_redact.cpp        Redact (the pixels a plane selects filled, pixelated or blurred in the BGR frame: the stage that writes the picture): C entry points
 //   infur_appearance.cpp    Appearance (per value of a plane the colour sums, second moments and joint histogram of the BGR frame: what an object looks like): C entry points
+//   infur_matte.cpp         Matte (the soft alpha of the pixels a plane selects, following the frame's edges) and Composite (the frame over a backdrop by it): C entry points
 //   infur_sieve.cpp         Adjacency (which values of a plane touch, along how many edges) and Sieve (speckle regions merged into their neighbours): C entry points
 // (infur_egress.h, beside this header: what the last four share -- the argument checks with their messages, the read-back of a
 //  polygon stage, the host-pointer frame wrapper and the front halves of the _dev frame calls)

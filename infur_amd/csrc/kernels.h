@@ -416,6 +416,32 @@ size_t appearance_scratch_bytes(unsigned rows, bool own_hist);
 hipError_t launch_appearance(const uint8_t* frame, const void* plane, int elem_bytes, unsigned H, unsigned W, int skip, unsigned skip_value, void* scratch,
                              unsigned long long* table, unsigned rows, unsigned* hist, unsigned* counts, hipStream_t s);
 
+// Matte (matte.hip): the soft alpha[H * W] of the pixels the H x W plane (1- or 4-byte elements) selects -- value v is selected when
+// v < select_rows and select[v] is not zero, the opposite with invert -- following the edges of the packed BGR frame[H * W * 3]:
+// alpha(p) = (2N + D) / (2D) with D the sum of weight(d(p, q)) and N that of weight * m(q) over the window |dx|, |dy| <= radius
+// clipped at the frame; d the sum of the three absolute channel differences, weight(d) = (4096 sigma^2) / (sigma^2 + d^2), m 255
+// (conf[q] with a conf plane) for a selected pixel and 0 for any other.  counts[kMatteCountWords] = {SELECTED, OUTSIDE, CLEAR, SOFT,
+// OPAQUE, 0, 0, STATUS} (alpha and counts each optional; device memory; neither needs initialisation).  Sides 1 to kMatteMaxSide,
+// radius 1 to kMatteMaxRadius, sigma 1 to 255.  A workgroup owns kMatteTileW x kMatteTileH outputs.  scratch:
+// matte_scratch_bytes() bytes the launches own for the call.  Stream-ordered, two launches and a third for the counts, no
+// memset; no workgroup waits for another.
+constexpr unsigned kMatteTileW = 64, kMatteTileH = 16;
+constexpr unsigned kMatteMaxRadius = 16;
+constexpr int kMatteCountWords = 8;
+constexpr unsigned kMatteInvert = 1u, kMatteConf = 2u;
+constexpr unsigned kMatteNothing = 1u;
+constexpr unsigned kMatteMaxSide = 32768;
+size_t matte_scratch_bytes();
+hipError_t launch_matte(const uint8_t* frame, const void* plane, int elem_bytes, unsigned H, unsigned W, const uint8_t* select, unsigned select_rows,
+                        int invert, const uint8_t* conf, unsigned radius, unsigned sigma, void* scratch, uint8_t* alpha, unsigned* counts,
+                        hipStream_t s);
+// Composite (matte.hip): out = the frame over a backdrop by alpha[H * W], per channel (alpha F + (255 - alpha) B + 127) / 255; the
+// backdrop is `colour` (B = bits 0-7, G = bits 8-15, R = bits 16-23) or the picture back[H * W * 3]; kCompositeCutout writes
+// out[H * W * 4] = B G R alpha instead.  In the first two modes out may be the frame itself.  One launch.
+constexpr unsigned kCompositeColour = 0u, kCompositeImage = 1u, kCompositeCutout = 2u;
+hipError_t launch_composite(const uint8_t* frame, const uint8_t* alpha, unsigned H, unsigned W, unsigned mode, const uint8_t* back, unsigned colour,
+                            uint8_t* out, hipStream_t s);
+
 // Compare (compare.hip): two H x W planes (both sides at most 65535) of 1- or 4-byte elements against each other.  A pixel whose
 // a equals ignore_a (ign_a set) or whose b equals ignore_b (ign_b set) is ignored; a compared pixel with a >= rows_a or
 // b >= rows_b is outside; the rest are inside.  matrix[rows_a x rows_b] u32 counts the inside pixels per (a, b); rows_a_out and

@@ -1203,6 +1203,160 @@ class RedactFrame(NamedTuple):
 
 
 @dataclass
+class MatteCmd:
+    """``Matte``'s command: which values are the foreground (``select`` lists them, or is a ready table of bytes as a ``np.uint8``
+    array; ``invert`` takes everything else), the window ``radius`` (1 to 16), the colour tolerance ``sigma`` (1 to 255: the
+    distance at which a tap weighs half) and ``use_conf``: a selected pixel weighs its confidence byte instead of 255."""
+
+    select: Sequence[int] = ()
+    radius: int = 8
+    sigma: int = 24
+    invert: bool = False
+    use_conf: bool = False
+
+    def table(self) -> np.ndarray:
+        if isinstance(self.select, np.ndarray) and self.select.dtype == np.uint8:
+            return np.ascontiguousarray(self.select.ravel())
+        return _select_table(self.select)
+
+    def flags(self) -> int:
+        return (_lib.MATTE_INVERT if self.invert else 0) | (_lib.MATTE_CONF if self.use_conf else 0)
+
+
+class MatteOut:
+    """``Matte``'s ``&mut Output``: after ``advance`` ``alpha`` [H, W] u8 (None with ``want_alpha=False``) and ``counts`` [8] u32
+    (``_lib.MATTE_COUNT_SELECTED`` ..); ``nothing`` says that no pixel was selected."""
+
+    def __init__(self, want_alpha: bool = True):
+        self.want_alpha = want_alpha
+        self.alpha = self.counts = None
+
+    @property
+    def nothing(self) -> bool:
+        return bool(self.counts is not None and self.counts[_lib.MATTE_COUNT_STATUS] & _lib.MATTE_NOTHING)
+
+
+class Matte(Processor):
+    """The soft alpha of the pixels a class plane (u8) or a label / track plane (u32) selects, following the edges of the packed BGR
+    frame: a joint bilateral filter of the mask guided by the picture, in exact integers.
+
+    Command = ``MatteCmd``.  Input = (frame [H, W, 3] u8, plane [H, W] of u8 or u32) or (frame, plane, conf [H, W] u8) with
+    ``use_conf``; Output = ``MatteOut``.  Identical from run to run.
+    """
+
+    def __init__(self, ctx: Context, cmd: Optional[MatteCmd] = None):
+        self.ctx = ctx
+        self.cmd = cmd or MatteCmd()
+        self.dirty = True
+
+    def control(self, cmd: MatteCmd) -> "Matte":
+        key = lambda c: (c.table().tobytes(), c.radius, c.sigma, c.flags())  # noqa: E731
+        self.dirty = self.dirty or key(cmd) != key(self.cmd)
+        self.cmd = cmd
+        return self
+
+    def is_dirty(self) -> bool:
+        return self.dirty
+
+    def advance(self, inp, out: MatteOut) -> None:
+        self.dirty = False
+        frame, plane, conf = (tuple(inp) + (None,))[:3]
+        frame = _check_bgr(frame)
+        if plane.ndim != 2 or plane.dtype.itemsize not in (1, 4) or plane.dtype.kind not in "ui" or plane.shape != frame.shape[:2]:
+            raise InfurError(_lib.E_SHAPE, f"expected an [H,W] plane of 1- or 4-byte integers for a {frame.shape} frame, got {plane.shape} {plane.dtype}")
+        if conf is not None and (conf.dtype != np.uint8 or conf.shape != plane.shape):
+            raise InfurError(_lib.E_SHAPE, f"expected an [H,W] u8 confidence plane for a {frame.shape} frame, got {conf.shape} {conf.dtype}")
+        plane, conf = np.ascontiguousarray(plane), np.ascontiguousarray(conf) if conf is not None else None
+        h, w = plane.shape
+        cmd, table = self.cmd, self.cmd.table()
+        alpha = np.empty((h, w), np.uint8) if out.want_alpha else None
+        counts = np.zeros(_lib.MATTE_COUNT_WORDS, np.uint32)
+        self.ctx.check(self.ctx.L.infur_matte(self.ctx.h, frame.ctypes.data, plane.ctypes.data, plane.dtype.itemsize, h, w, _ptr_some(table), table.size,
+                                              cmd.flags(), _ptr(conf), cmd.radius, cmd.sigma, _ptr(alpha), counts.ctypes.data))
+        out.alpha, out.counts = alpha, counts
+
+
+@dataclass
+class CompositeCmd:
+    """``Composite``'s command: ``Colour((B, G, R))`` lays the frame over a colour, ``Image()`` over the picture given with the
+    input, ``Cutout()`` writes B G R alpha, four bytes a pixel, not premultiplied."""
+
+    mode: int = _lib.COMPOSITE_COLOUR
+    colour: Tuple[int, int, int] = (0, 0, 0)
+
+    @staticmethod
+    def Colour(colour=(0, 0, 0)) -> "CompositeCmd":
+        return CompositeCmd(_lib.COMPOSITE_COLOUR, tuple(colour))
+
+    @staticmethod
+    def Image() -> "CompositeCmd":
+        return CompositeCmd(_lib.COMPOSITE_IMAGE)
+
+    @staticmethod
+    def Cutout() -> "CompositeCmd":
+        return CompositeCmd(_lib.COMPOSITE_CUTOUT)
+
+    def colour_word(self) -> int:
+        b, g, r = (int(v) & 255 for v in self.colour)
+        return b | (g << 8) | (r << 16)
+
+
+class CompositeOut:
+    """``Composite``'s ``&mut Output``: after ``advance`` ``out`` [H, W, 3] u8, or [H, W, 4] for a cut-out"""
+
+    def __init__(self):
+        self.out = None
+
+
+class Composite(Processor):
+    """The frame over a backdrop by an alpha plane: per channel (alpha F + (255 - alpha) B + 127) // 255.
+
+    Command = ``CompositeCmd``.  Input = (frame [H, W, 3] u8, alpha [H, W] u8) or (frame, alpha, back [H, W, 3] u8) for
+    ``Image()``; Output = ``CompositeOut``.
+    """
+
+    def __init__(self, ctx: Context, cmd: Optional[CompositeCmd] = None):
+        self.ctx = ctx
+        self.cmd = cmd or CompositeCmd()
+        self.dirty = True
+
+    def control(self, cmd: CompositeCmd) -> "Composite":
+        self.dirty = self.dirty or (cmd.mode, cmd.colour_word()) != (self.cmd.mode, self.cmd.colour_word())
+        self.cmd = cmd
+        return self
+
+    def is_dirty(self) -> bool:
+        return self.dirty
+
+    def advance(self, inp, out: CompositeOut) -> None:
+        self.dirty = False
+        frame, alpha, back = (tuple(inp) + (None,))[:3]
+        frame = _check_bgr(frame)
+        h, w = frame.shape[:2]
+        if alpha.dtype != np.uint8 or alpha.shape != (h, w):
+            raise InfurError(_lib.E_SHAPE, f"expected an [H,W] u8 alpha plane for a {frame.shape} frame, got {alpha.shape} {alpha.dtype}")
+        if back is not None and _check_bgr(back).shape != frame.shape:
+            raise InfurError(_lib.E_SHAPE, f"expected a backdrop of the frame's shape {frame.shape}, got {back.shape}")
+        alpha, back = np.ascontiguousarray(alpha), np.ascontiguousarray(back) if back is not None else None
+        res = np.empty((h, w, 4 if self.cmd.mode == _lib.COMPOSITE_CUTOUT else 3), np.uint8)
+        self.ctx.check(self.ctx.L.infur_composite(self.ctx.h, frame.ctypes.data, alpha.ctypes.data, h, w, self.cmd.mode, _ptr(back),
+                                                  self.cmd.colour_word(), res.ctypes.data))
+        out.out = res
+
+
+class MatteFrame(NamedTuple):
+    """``FramePath.advance_matte``: the alpha plane [oh, ow] u8, the composed frame [oh, ow, 3] u8 ([oh, ow, 4] for a cut-out), the
+    class and confidence planes and the scaled frame (None where not wanted) and the eight counts"""
+
+    alpha: Optional[np.ndarray]
+    composed: Optional[np.ndarray]
+    klass: Optional[np.ndarray]
+    conf: Optional[np.ndarray]
+    counts: Optional[np.ndarray]
+    scaled: Optional[np.ndarray]
+
+
+@dataclass
 class AppearanceCmd:
     """``Appearance``'s command: ``rows`` rows of the table and the histogram (values at or above it count only as OUTSIDE), and the
     value whose pixels are left out (``skip``: class 0, ``_lib.REGION_NONE``, ``_lib.TRACK_NONE``; None: every pixel counts)."""
@@ -2705,6 +2859,34 @@ class FramePath:
         if not self._loaded(rc):
             return RedactFrame(None, None, None, None, scaled)
         return RedactFrame(redacted, klass, conf, counts, scaled)
+
+    def advance_matte(self, img: np.ndarray, cmd: MatteCmd, composite: Optional[CompositeCmd] = None, back: Optional[np.ndarray] = None,
+                      factor: float = 1.0, decode: int = _lib.DECODE_RAW, want_alpha: bool = True, want_klass: bool = False,
+                      want_conf: bool = False, want_scaled: bool = False) -> MatteFrame:
+        """The fused path with the matte, scale -> model -> Segments decode -> Matte of the scaled frame by the class plane (with
+        ``cmd.use_conf`` weighted by the decode's confidence) -> Composite when ``composite`` is given (``back``: the backdrop of
+        ``CompositeCmd.Image()``, of the scaled size), in one call -> ``MatteFrame``; every result field is None when no model is
+        loaded (``scaled`` is still produced)."""
+        img, w, h, f, ow, oh = self._front(img, factor)
+        npix = oh.value * ow.value
+        table = cmd.table()
+        mode = composite.mode if composite is not None else _lib.COMPOSITE_COLOUR
+        channels = 4 if mode == _lib.COMPOSITE_CUTOUT else 3
+        if back is not None and _check_bgr(back).shape != (oh.value, ow.value, 3):
+            raise InfurError(_lib.E_SHAPE, f"expected a backdrop of the scaled frame's shape {(oh.value, ow.value, 3)}, got {back.shape}")
+        back = np.ascontiguousarray(back) if back is not None else None
+        alpha = self._plane(ow, oh, want_alpha)
+        composed = self._plane(ow, oh, composite is not None, channels=channels)
+        klass, conf = self._plane(ow, oh, want_klass), self._plane(ow, oh, want_conf)
+        scaled = self._plane(ow, oh, want_scaled, channels=3)
+        counts = np.zeros(_lib.MATTE_COUNT_WORDS, np.uint32)
+        rc = self.ctx.L.infur_frame_matte(self.ctx.h, img.ctypes.data, w, h, f, self.scale_mode, decode, _ptr_some(table), table.size, cmd.flags(),
+                                          cmd.radius, cmd.sigma, mode, _ptr(back), composite.colour_word() if composite is not None else 0,
+                                          _ptr(alpha), _ptr(composed), npix * channels, _ptr(klass), _ptr(conf), npix, counts.ctypes.data,
+                                          _ptr(scaled), C.byref(ow), C.byref(oh))
+        if not self._loaded(rc):
+            return MatteFrame(None, None, None, None, None, scaled)
+        return MatteFrame(alpha, composed, klass, conf, counts, scaled)
 
     def advance_appearance(self, img: np.ndarray, factor: float = 1.0, decode: int = _lib.DECODE_RAW, connectivity: int = _lib.CONNECT_8,
                            min_pixels: int = 0, flags: int = 0, table_rows: int = 1024, want_labels: bool = True, want_klass: bool = True,

@@ -84,6 +84,12 @@ every region record gains ``"colour"``, its mean [b, g, r], and ``"dominant"``, 
 BBGGRR``); ``--redact-invert`` hides everything else instead (background blur).  Every line gains ``"redact"``: the frame's selected
 pixels.
 
+``--matte-out FILE`` makes the soft, edge-aware alpha of the classes ``--matte-classes 15[,2,..]`` in the scaled frame on the device
+(``infur_frame_matte``; ``--matte-radius`` 1 to 16, ``--matte-sigma`` 1 to 255, ``--matte-conf`` weighs the decode's confidence,
+``--matte-invert`` takes everything else) and writes it to FILE, one byte a pixel; with ``--matte-over BBGGRR`` FILE receives the
+bgr24 frames laid over that colour instead, with ``--matte-cutout`` the frames as B G R alpha, four bytes a pixel.  Every line
+gains ``"matte"``: the frame's selected, clear, soft and opaque pixels.
+
 ``--truth FILE`` grades every frame: FILE holds one u8 ground-truth class plane of the scaled frame's size per frame, back to back;
 the class plane is compared with it (``infur_compare``; ``--truth-ignore V`` leaves the pixels whose truth is V, a "void" label,
 out), every line gains ``"pixel_accuracy"`` and ``"miou"``, and one last line holds the totals of the confusion matrices added up
@@ -187,7 +193,32 @@ def main(argv=None) -> int:
     ap.add_argument("--redact-passes", type=int, default=3, metavar="K", help="blur passes, 1 to 3 (three approximate a Gaussian)")
     ap.add_argument("--redact-invert", action="store_true", help="hide everything but --redact-classes")
     ap.add_argument("--redact-colour", default="000000", metavar="BBGGRR", help="the colour of --redact-mode fill")
+    ap.add_argument("--matte-out", default="", help="the alpha planes of --matte-classes, or the composed frames with --matte-over / --matte-cutout")
+    ap.add_argument("--matte-classes", default="", metavar="K[,K..]", help="the foreground classes (needs --matte-out)")
+    ap.add_argument("--matte-radius", type=int, default=8, metavar="N", help="the window's radius, 1 to 16")
+    ap.add_argument("--matte-sigma", type=int, default=24, metavar="S", help="the colour distance at which a tap weighs half, 1 to 255")
+    ap.add_argument("--matte-conf", action="store_true", help="a foreground pixel weighs its confidence byte")
+    ap.add_argument("--matte-invert", action="store_true", help="everything but --matte-classes is foreground")
+    ap.add_argument("--matte-over", default="", metavar="BBGGRR", help="write the frame over this colour instead of the alpha plane")
+    ap.add_argument("--matte-cutout", action="store_true", help="write B G R alpha, four bytes a pixel, instead of the alpha plane")
     a = ap.parse_args(argv)
+    matte_classes, matte_colour = [], 0
+    if a.matte_out:
+        try:
+            matte_classes = [int(v) for v in a.matte_classes.split(",") if v != ""]
+            matte_colour = int(a.matte_over, 16) if a.matte_over else 0
+        except ValueError:
+            ap.error("--matte-classes: class numbers separated by commas; --matte-over: six hexadecimal digits BBGGRR")
+        if not matte_classes or min(matte_classes) < 0 or max(matte_classes) > 255:
+            ap.error("--matte-out needs --matte-classes, each 0 to 255")
+        if a.matte_over and a.matte_cutout:
+            ap.error("--matte-over and --matte-cutout exclude each other")
+        for given, name in ((a.regions, "--regions"), (a.runs_out, "--runs-out"), (a.outlines_out, "--outlines-out"), (a.truth, "--truth"),
+                            (a.outlines_fidelity, "--outlines-fidelity"), (a.redact_out, "--redact-out")):
+            if given:
+                ap.error(f"--matte-out does not combine with {name}: the fused matte call returns the alpha, the picture and the two planes")
+    elif a.matte_classes or a.matte_invert or a.matte_conf or a.matte_over or a.matte_cutout:
+        ap.error("--matte-classes, --matte-invert, --matte-conf, --matte-over and --matte-cutout need --matte-out")
     redact_classes = []
     if a.redact_out:
         try:
@@ -360,6 +391,13 @@ def main(argv=None) -> int:
         redact_cmd = {"blur": RedactCmd.Blur(redact_classes, a.redact_size, a.redact_passes, a.redact_invert),
                       "pixelate": RedactCmd.Pixelate(redact_classes, a.redact_size, a.redact_invert),
                       "fill": RedactCmd.Fill(redact_classes, colour, a.redact_invert)}[a.redact_mode]
+    fmat = open(a.matte_out, "wb") if a.matte_out else None
+    if fmat is not None:
+        from .processors import CompositeCmd, MatteCmd
+
+        matte_cmd = MatteCmd(matte_classes, a.matte_radius, a.matte_sigma, a.matte_invert, a.matte_conf)
+        matte_over = (CompositeCmd.Cutout() if a.matte_cutout else
+                      CompositeCmd.Colour((matte_colour >> 16 & 255, matte_colour >> 8 & 255, matte_colour & 255)) if a.matte_over else None)  # BBGGRR -> (B, G, R)
     if a.regions and (a.sieve is not None or a.shapes or a.split is not None or a.skeleton or a.expand is not None or a.appearance):
         flags = _lib.REGIONS_SKIP_BACKGROUND if a.skip_background else 0
     elif a.regions:
@@ -405,6 +443,9 @@ def main(argv=None) -> int:
             labels, table, nreg = r.labels, r.table, r.n
         elif fred is not None:  # scale -> model -> decode -> Redact of the scaled frame by the class plane, in one call
             r = fp.advance_redact(img, redact_cmd, a.scale, decode, want_klass=True, want_conf=True)
+            s = SegmentsFrame(r.klass, r.conf, _class_stats(r.klass, r.conf, model.get_info().num_classes), None, None)
+        elif fmat is not None:  # scale -> model -> decode -> Matte of the scaled frame by the class plane -> Composite, in one call
+            r = fp.advance_matte(img, matte_cmd, matte_over, None, a.scale, decode, want_alpha=matte_over is None, want_klass=True, want_conf=True)
             s = SegmentsFrame(r.klass, r.conf, _class_stats(r.klass, r.conf, model.get_info().num_classes), None, None)
         elif fcl is not None:  # the call below, then Centrelines of the label plane and the kind plane under dist2, in one call
             r = fp.advance_centrelines(img, a.scale, decode, a.connectivity, a.min_pixels, flags, table_rows=max(0, a.max_regions),
@@ -512,6 +553,10 @@ def main(argv=None) -> int:
         if fred is not None:
             rec["redact"] = {"selected": int(r.counts[_lib.REDACT_COUNT_SELECTED]), "mode": a.redact_mode}
             fred.write(memoryview(r.redacted).cast("B"))
+        if fmat is not None:
+            rec["matte"] = {k: int(r.counts[i]) for k, i in (("selected", _lib.MATTE_COUNT_SELECTED), ("clear", _lib.MATTE_COUNT_CLEAR),
+                                                             ("soft", _lib.MATTE_COUNT_SOFT), ("opaque", _lib.MATTE_COUNT_OPAQUE))}
+            fmat.write(memoryview(r.alpha if matte_over is None else r.composed).cast("B"))
         if a.appearance:
             rec["n_regions"], rec["regions"] = nreg, region_summary(table, nreg, ow, oh)
             looks = {e["value"]: e for e in appearance_summary(r.appearance_table if r.appearance_table is not None else ())}
@@ -587,7 +632,7 @@ def main(argv=None) -> int:
         ftruth.close()
     if a.outlines_fidelity:
         fst.write(json.dumps({"frames": n, "polygon_fidelity": fid_total}) + "\n")
-    for f in (flab, fconf, freg, ftrk, fruns, foutl, fdist, fhull, fsplit, fskel, fcl, fexp, fred, fst):
+    for f in (flab, fconf, freg, ftrk, fruns, foutl, fdist, fhull, fsplit, fskel, fcl, fexp, fred, fmat, fst):
         if f is not None:
             f.flush()
     el = time.perf_counter() - t0

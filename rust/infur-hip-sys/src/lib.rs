@@ -434,6 +434,24 @@ pub const INFUR_APPEARANCE_NOTHING: u32 = 1;
 pub const INFUR_APPEARANCE_MAX_SIDE: u32 = 32768;
 /// bit of `infur_features()`: the Appearance calls below exist
 pub const INFUR_FEATURE_APPEARANCE: u32 = 262144;
+/// Matte and Composite: the flags, the words of the counts, the status bit, the limits, the modes
+pub const INFUR_MATTE_INVERT: u32 = 1;
+pub const INFUR_MATTE_CONF: u32 = 2;
+pub const INFUR_MATTE_COUNT_SELECTED: u32 = 0;
+pub const INFUR_MATTE_COUNT_OUTSIDE: u32 = 1;
+pub const INFUR_MATTE_COUNT_CLEAR: u32 = 2;
+pub const INFUR_MATTE_COUNT_SOFT: u32 = 3;
+pub const INFUR_MATTE_COUNT_OPAQUE: u32 = 4;
+pub const INFUR_MATTE_COUNT_STATUS: u32 = 7;
+pub const INFUR_MATTE_COUNT_WORDS: u32 = 8;
+pub const INFUR_MATTE_NOTHING: u32 = 1;
+pub const INFUR_MATTE_MAX_RADIUS: u32 = 16;
+pub const INFUR_MATTE_MAX_SIDE: u32 = 32768;
+pub const INFUR_COMPOSITE_COLOUR: u32 = 0;
+pub const INFUR_COMPOSITE_IMAGE: u32 = 1;
+pub const INFUR_COMPOSITE_CUTOUT: u32 = 2;
+/// bit of `infur_features()`: the Matte and Composite calls below exist
+pub const INFUR_FEATURE_MATTE: u32 = 524288;
 
 extern "C" {
     pub fn infur_abi_version() -> u32;
@@ -867,4 +885,23 @@ extern "C" {
                                       table_rows: u32, d_n_regions: *mut c_void, d_scaled_bgr: *mut c_void, ow: *mut u32, oh: *mut u32,
                                       d_appearance_table: *mut c_void, appearance_rows: u32, d_appearance_hist: *mut c_void,
                                       d_appearance_counts: *mut c_void) -> i32;
+    // Matte and Composite: the edge-aware alpha of the pixels a plane selects, and the frame over a backdrop by it
+    pub fn infur_matte(c: *mut infur_ctx, frame: *const u8, plane: *const c_void, elem_bytes: u32, h: u32, w: u32, select: *const u8,
+                       select_rows: u32, flags: u32, conf: *const u8, radius: u32, sigma: u32, alpha: *mut u8, counts: *mut u32) -> i32;
+    pub fn infur_matte_dev(c: *mut infur_ctx, d_frame: *const c_void, d_plane: *const c_void, elem_bytes: u32, h: u32, w: u32,
+                           d_select: *const c_void, select_rows: u32, flags: u32, d_conf: *const c_void, radius: u32, sigma: u32,
+                           d_alpha: *mut c_void, d_counts: *mut c_void) -> i32;
+    pub fn infur_composite(c: *mut infur_ctx, frame: *const u8, alpha: *const u8, h: u32, w: u32, mode: u32, back: *const u8, colour: u32,
+                           out: *mut u8) -> i32;
+    pub fn infur_composite_dev(c: *mut infur_ctx, d_frame: *const c_void, d_alpha: *const c_void, h: u32, w: u32, mode: u32,
+                               d_back: *const c_void, colour: u32, d_out: *mut c_void) -> i32;
+    pub fn infur_frame_matte(c: *mut infur_ctx, bgr: *const u8, w: u32, h: u32, factor: f32, scale_mode: u32, decode: u32, select: *const u8,
+                             select_rows: u32, matte_flags: u32, radius: u32, sigma: u32, composite_mode: u32, back: *const u8, colour: u32,
+                             alpha: *mut u8, composed: *mut u8, composed_capacity: usize, klass: *mut u8, conf: *mut u8, plane_capacity: usize,
+                             counts: *mut u32, scaled_bgr: *mut u8, ow: *mut u32, oh: *mut u32) -> i32;
+    pub fn infur_frame_matte_dev(c: *mut infur_ctx, d_bgr: *const c_void, w: u32, h: u32, factor: f32, scale_mode: u32, decode: u32,
+                                 d_select: *const c_void, select_rows: u32, matte_flags: u32, radius: u32, sigma: u32, composite_mode: u32,
+                                 d_back: *const c_void, colour: u32, d_alpha: *mut c_void, d_composed: *mut c_void, composed_capacity: usize,
+                                 d_klass: *mut c_void, d_conf: *mut c_void, plane_capacity: usize, d_counts: *mut c_void,
+                                 d_scaled_bgr: *mut c_void, ow: *mut u32, oh: *mut u32) -> i32;
 }

@@ -899,6 +899,78 @@ impl Processor for HipAppearance {
     }
 }
 
+// ---------------------------------------------------------------- Matte (the edge-aware alpha of the pixels a plane selects)
+/// What `HipMatte` produces: the alpha plane (`w * h` bytes; empty with `want_alpha` false) and the `INFUR_MATTE_COUNT_WORDS` counts.
+pub struct Matted { pub want_alpha: bool, pub alpha: Vec<u8>, pub counts: [u32; sys::INFUR_MATTE_COUNT_WORDS as usize] }
+impl Default for Matted {
+    fn default() -> Self { Self { want_alpha: true, alpha: Vec::new(), counts: [0; sys::INFUR_MATTE_COUNT_WORDS as usize] } }
+}
+impl Matted {
+    /// nothing was selected
+    pub fn nothing(&self) -> bool { self.counts[sys::INFUR_MATTE_COUNT_STATUS as usize] & sys::INFUR_MATTE_NOTHING != 0 }
+}
+/// `select[v] != 0` makes value `v` foreground; `invert` takes everything else; `radius` 1 to 16, `sigma` 1 to 255; `use_conf`: a
+/// selected pixel weighs its confidence byte instead of 255.
+pub struct MatteCmd { pub select: Vec<u8>, pub invert: bool, pub use_conf: bool, pub radius: u32, pub sigma: u32 }
+/// The frame, the plane that selects its pixels (both `size` = [w, h]) and, with `use_conf`, the confidence plane
+pub struct MatteInput { pub frame: Vec<u8>, pub plane: RunsPlane, pub conf: Vec<u8> }
+/// The soft alpha that follows the frame's edges.  Integer results, identical from run to run.
+pub struct HipMatte { ctx: Rc<Ctx>, cmd: MatteCmd, dirty: bool }
+impl HipMatte {
+    pub fn new(ctx: Rc<Ctx>) -> Self {
+        Self { ctx, cmd: MatteCmd { select: Vec::new(), invert: false, use_conf: false, radius: 8, sigma: 24 }, dirty: true }
+    }
+    /// the frame over `back` (`INFUR_COMPOSITE_IMAGE`) or `colour` by `alpha`: three bytes a pixel, four for a cut-out
+    pub fn compose(&self, frame: &[u8], alpha: &[u8], size: [usize; 2], mode: u32, back: &[u8], colour: u32) -> Result<Vec<u8>, HipError> {
+        let [w, h] = size;
+        if alpha.len() != w * h || frame.len() != w * h * 3 || (mode == sys::INFUR_COMPOSITE_IMAGE && back.len() != w * h * 3) {
+            return Err(HipError::status(sys::INFUR_E_SHAPE));
+        }
+        let mut out = vec![0u8; w * h * if mode == sys::INFUR_COMPOSITE_CUTOUT { 4 } else { 3 }];
+        let rc = unsafe {
+            sys::infur_composite(self.ctx.0, frame.as_ptr(), alpha.as_ptr(), h as u32, w as u32, mode,
+                                 if back.is_empty() { std::ptr::null() } else { back.as_ptr() }, colour, out.as_mut_ptr())
+        };
+        if rc != sys::INFUR_OK { return Err(HipError::from_ctx(&self.ctx, rc)); }
+        Ok(out)
+    }
+}
+impl Processor for HipMatte {
+    type Command = MatteCmd;
+    type ControlError = HipError;
+    type Input = MatteInput;
+    type Output = Matted;
+    type ProcessResult = Result<(), HipError>;
+
+    fn control(&mut self, cmd: MatteCmd) -> Result<&mut Self, HipError> {
+        self.cmd = cmd;
+        self.dirty = true;
+        Ok(self)
+    }
+    fn is_dirty(&self) -> bool { self.dirty }
+    fn advance(&mut self, inp: &MatteInput, out: &mut Matted) -> Result<(), HipError> {
+        self.dirty = false;
+        let [w, h] = inp.plane.size;
+        let (ptr, len, elem_bytes) = match &inp.plane.data {
+            RunsPlaneData::U8(p) => (p.as_ptr() as *const std::ffi::c_void, p.len(), 1u32),
+            RunsPlaneData::U32(p) => (p.as_ptr() as *const std::ffi::c_void, p.len(), 4u32),
+        };
+        if len != w * h || inp.frame.len() != w * h * 3 || (self.cmd.use_conf && inp.conf.len() != w * h) {
+            return Err(HipError::status(sys::INFUR_E_SHAPE));
+        }
+        out.alpha.resize(if out.want_alpha { w * h } else { 0 }, 0);
+        let flags = (if self.cmd.invert { sys::INFUR_MATTE_INVERT } else { 0 }) | (if self.cmd.use_conf { sys::INFUR_MATTE_CONF } else { 0 });
+        let rc = unsafe {
+            sys::infur_matte(self.ctx.0, inp.frame.as_ptr(), ptr, elem_bytes, h as u32, w as u32,
+                             if self.cmd.select.is_empty() { std::ptr::null() } else { self.cmd.select.as_ptr() }, self.cmd.select.len() as u32, flags,
+                             if self.cmd.use_conf { inp.conf.as_ptr() } else { std::ptr::null() }, self.cmd.radius, self.cmd.sigma,
+                             if out.want_alpha { out.alpha.as_mut_ptr() } else { std::ptr::null_mut() }, out.counts.as_mut_ptr())
+        };
+        if rc != sys::INFUR_OK { return Err(HipError::from_ctx(&self.ctx, rc)); }
+        Ok(())
+    }
+}
+
 // ---------------------------------------------------------------- Compare (confusion matrix, best partner per value)
 /// What `HipCompare` produces for `rows_a` x `rows_b` values: `matrix` row-major (`matrix[i * rows_b + j]`: the pixels with a == i
 /// and b == j), `a` and `b` rows of `INFUR_COMPARE_WORDS` words (PIXELS, PARTNER, INTER, UNION) per value of either plane --
